@@ -229,11 +229,17 @@ inline long long persist_grid_x(long long M, int H, int cus) {
     return gx > nblk ? nblk : gx;
 }
 
-template <int METRIC, bool TRAIN = false>
+template <int METRIC, bool TRAIN = false, bool SCREEN = false>
 int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s) {
     using G = Geo<256, 8>;
     const size_t lds = (size_t)G::MAIN_FLOATS_S * 4 + 2 * 8 * 32 * 4;
-    auto kern = vq_search_persist<256, 8, METRIC, TRAIN>;
+    auto kern = vq_search_persist<256, 8, METRIC, TRAIN, SCREEN>;
+    if constexpr (SCREEN) {  // the bf16x3 images of this call's codebooks, from their fp32 packed images
+        hipLaunchKernelGGL(vq_pack_scr_kernel<256>, dim3((unsigned)p.ntiles, (unsigned)H), dim3(256), 0, s, p.packed, p.pk_hs, p.K,
+                           p.ntiles, (char *)p.scr, p.scr_hs);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "vq_pack_scr launch");
+    }
     static thread_local bool attr_done[kMaxDevices] = {};
     if (int rc = allow_big_lds(kern, attr_done)) return rc;
     const long long gx = persist_grid_x(p.M, H, cus);
@@ -444,6 +450,7 @@ VQ_DEFINE_RESIDENT_PART(128)
 #if VQ_OWN(3)
 VQ_DEFINE_SEARCH_PART(256, 4)
 int part_persist(const SearchParams &p, int H, int cus, int metric, hipStream_t s) {
+    if (p.scr) return launch_persist_t<VQ_METRIC_EUCLID, false, true>(p, H, cus, s);  // (screen_image_for: Euclid inference calls)
     if (p.ste || p.loss_part)  // training-mode call: the deferred copy does the straight-through / squared-error arithmetic
         return metric == VQ_METRIC_EUCLID ? launch_persist_t<VQ_METRIC_EUCLID, true>(p, H, cus, s) : launch_persist_t<VQ_METRIC_DOT, true>(p, H, cus, s);
     return metric == VQ_METRIC_EUCLID ? launch_persist_t<VQ_METRIC_EUCLID>(p, H, cus, s) : launch_persist_t<VQ_METRIC_DOT>(p, H, cus, s);
@@ -516,6 +523,23 @@ bool persist_selected(int DP, int waves, const SearchParams &p, int H, int split
 }
 
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// The screened sweep (vq_search_persist.inc, SCREEN) for a call the persistent kernel takes: Euclid, fp32 rows, inference
+// (no straight-through / loss), no winning distances requested.  Its bf16x3 images are built per call into the key area of
+// the workspace, which a fused call does not use; a call whose images do not fit there keeps the fp32 sweep.  Sets p.scr (or
+// leaves it NULL).  VQ_NO_SCREEN in the environment keeps the fp32 sweep (read per call: tests compare both in one process).
+long long ws_keys_bytes(int H, long long M);
+void screen_image_for(SearchParams &p, const vq_args *a, int DP, int waves, int cus) {
+    p.scr = nullptr;
+    if (getenv("VQ_NO_SCREEN") != nullptr) return;
+    if (a->metric != VQ_METRIC_EUCLID || p.xt || p.ste || p.loss_part || p.best || p.lse) return;
+    if (!persist_selected(DP, waves, p, a->H, 1, cus)) return;
+    const long long img = scr_image_bytes(p.ntiles);
+    if (!a->workspace || (long long)a->H * img > ws_keys_bytes(a->H, a->M) || img >= (1ll << 31)) return;
+    p.scr = (const float *)a->workspace;
+    p.scr_hs = img;
+    p.scr_bytes = (unsigned)img;
+}
 
 // Small codebook, plain inference call (one stage, no straight-through / loss / LSE, aligned fp32 rows of D % 16 == 0 dims,
 // Dp <= 128) whose image fits the LDS beside the row slabs, and enough rows to give every wave slot of the chip a few 32-row
@@ -979,6 +1003,17 @@ int vq_debug_read_stamps(unsigned long long *host, size_t n) {  // diagnostic bu
 }
 #endif
 
+#ifdef VQ_EXP_SCREEN_COUNT
+int vq_debug_screen_rows(unsigned long long *host2, int reset) {  // diagnostic build only (single translation unit): {rows searched in full, rows, rows rescored}
+    hipError_t e = hipMemcpyFromSymbol(host2, HIP_SYMBOL(g_scr_rows), 3 * sizeof(unsigned long long));
+    if (e == hipSuccess && reset) {
+        const unsigned long long z[3] = {0, 0, 0};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_scr_rows), z, sizeof(z));
+    }
+    return (int)e;
+}
+#endif
+
 int vq_device_info(char *buf, size_t n) {
     const DevInfo &di = dev_info();
     if (!di.ok) return fail(VQ_E_NODEVICE, "vq: no HIP device");
@@ -1334,6 +1369,7 @@ static int quantize_impl(const vq_args *a, void *stream, float *lse) {
             const size_t full = ((size_t)res_img + 8 * (DP / 16) * 512) * 4 + 2 * 8 * 32 * 4;  // a slab buffer per slab of a block
             p.res_nbuf = (DP < 128 && full <= 160 * 1024) ? DP / 16 : 1;
         }
+        if (!res_img) screen_image_for(p, a, DP, waves, cus);
         rc = launch_search(DP, waves, p, a->H, 1, a->metric, s);
         if (rc) return rc;
         if (a->sq_err) {

@@ -47,6 +47,11 @@ struct SearchParams {
     const float *xn_ws;  // [head][xn_hs]: |x|^2 chain over the dims of the earlier slices
     float *xn_out;       // the chain including this slice (another buffer: the workgroups of a K split share the rows)
     long long xn_hs;
+    // Dp = 256 screened sweep (vq_search_persist.inc, SCREEN): the bf16x3 image of every head, `scr_hs` bytes apart, each
+    // `scr_bytes` long (NULL: the fp32 sweep)
+    const float *scr;
+    long long scr_hs;
+    unsigned scr_bytes;
 };
 }  // namespace vqi
 namespace {

@@ -14,8 +14,274 @@
 // TRAIN (round 3): the training-mode call -- straight-through output x + (c - x) and / or the squared error sum -- copies the
 // same way: the deferred step of a row loads the code row AND the x row (read again: the fragment registers of that block are
 // gone), does the finalize's arithmetic on the float4 and stores; the wave's squared-error partial is written once at the end.
-template <int DP, int WAVES, int METRIC, bool TRAIN = false>
+// ------------------------------------------------------------------------------------------------
+// SCREEN (Dp = 256, Euclid, plain inference call): a bf16x3 screen with a proven error bound, exact rule for the rest
+// ------------------------------------------------------------------------------------------------
+// The fp32 sweep runs v_mfma_f32_32x32x2_f32 (4 096 FLOP in 64 cycles); v_mfma_f32_32x32x16_bf16 does 32 768 FLOP in 32.
+// The screened sweep splits both operands into bf16 pairs, v = hi + lo + r with hi = bf16(v), lo = bf16(v - hi), and
+// accumulates hi_c * hi_x + lo_c * hi_x + hi_c * lo_x (3 bf16 MFMAs per 16 dims: 48 per 32 x 32 sub-tile instead of 129 fp32
+// ones), starting from |c|^2 (the fp32 chain of the packed image) in the accumulator.  Each lane keeps the three lowest
+// screened values of its codes over distinct codes, and the codes of the two lowest.  A row whose two lowest screened values
+// are further apart than the bound below can only have the screened winner as its exact winner.  The other rows rescore
+// their few candidates by the exact chain (exact_pair_euclid), or, when a lane half holds more candidates than it tracks,
+// are searched again in full (exact_rows_euclid).  Results are those of the fp32 kernel bit for bit.
+//
+// The bound.  u = 2^-24; for a row x (fp32 chain xn = d-ordered sum of squares) and code c (fp32 chain cn), c' = -2c as
+// packed (exact), Q = sum_k x_k c'_k in real arithmetic, nx = sqrt(xn), nc = sqrt(max cn) over the codebook, L = 2 nx nc.
+// Cauchy-Schwarz: sum_k |x_k c'_k| <= 2 |x| |c| <= L (1 + gamma_256) (the chains xn, cn are sums of non-negative terms,
+// relative error <= gamma_256 = 256u / (1 - 256u) < 1.6e-5).
+//  S = screened value, E = exact fp32 value minus xn (the kernels' D = fl(fl(P + xn) + cn), P the k-ordered fmaf chain).
+//  (1) split: x = xh + xl + rx with |xh - x| <= 2^-9 |x| (round to nearest, 8-bit significand), x - xh exact in fp32,
+//      |rx| <= 2^-8 |x - xh| <= 2^-16 |x|, the same for c'.  x c' - (xh ch + xh cl + xl ch) = rx c' + x rc - rx rc + xl cl,
+//      and |xl cl| <= 2^-16 (1 + 2^-8)^2 |x c'|: in all <= 3.0001 * 2^-16 |x_k c'_k| per term, <= 4.58e-5 * 1.0001 L.
+//  (2) bf16 x bf16 products are exact in fp32 (16 significant bits); the MFMA adds the 3 D = 768 products and the
+//      initial cn in an undocumented order: any order of n - 1 = 768 additions is within gamma_768 < 4.59e-5 of the sum of
+//      the absolute values, here <= (1 + 4 * 2^-8) L * 1.0001 + cn: <= 4.59e-5 (1.016 L + nc^2).
+//  (3) denormals: bf16 operands and fp32 partial sums below 2^-126 may be flushed (the ISA does not promise either way).
+//      A flushed operand changes a product by < 2^-126 * 2 max(|x_k|, |c'_k|), a flushed product or sum by < 2^-126: over
+//      768 products and sums < 2^-115 (1 + nx + 2 nc) in absolute terms.
+//  (4) the exact side: |P - Q| <= gamma_256 sum |x_k c'_k| <= 1.53e-5 L * 1.0001 (k-ordered fmaf chain), the two
+//      additions of xn and cn add <= u (|P + xn| + |D|) <= 1.2e-7 (L + xn + nc^2) * 1.0001; fp32 denormals in the chain
+//      < 258 * 2^-149.
+//  => |S - E| <= 1.080e-4 L + 4.61e-5 nc^2 + 1.2e-7 xn + 2^-114 (1 + nx + nc) =: delta_0.  The kernel uses
+//     delta = 2.5e-4 L + 1e-4 nc^2 + 3e-7 xn + 2^-110 (1 + nx + nc) >= 2.16 delta_0 (the rounding of delta's own evaluation
+//     and of the fp32 sqrt are far inside that factor).
+// A row is CERTAIN when (b1, b2 = lowest and second lowest screened values over distinct codes of the row)
+//  * b2 - b1 > 2 delta + w, w = 2^-20 (|b1| + xn + delta): every other code j has E_j >= b2 - delta > b1 + delta + w >=
+//    E_win + w, so D_j - D_win > w >= 2^-21 D_win * 2: the two squared distances cannot share a correctly rounded sqrt (two
+//    values more than 2^-21 apart relative never do -- the fp32 sweep's tie rule), the screened argmin is the unique winner;
+//  * b1 + xn > 2 delta: the winner's D is positive, so no code clamps to 0 (several clamped codes would tie at 0 and the
+//    lowest index, not the screened argmin, would win);
+//  * eligibility: xn <= 2^100 and max cn <= 2^100 (no partial sum can overflow; NaN / inf rows fail this test and take the
+//    exact path, which follows the non-finite rule), and the codebook is not flagged non-finite.
+// The winning distance is then known only through the screen, so calls that request it (`best`) keep the fp32 sweep.
+constexpr int kScrRowBytes = 1040;                             // one code: 16 groups of 16 dims x (hi, lo) x 16 B, + 16 B pad
+constexpr int kScrTileBytes = kTileCodes * kScrRowBytes + 128;  // 32 codes + their 32 fp32 |c|^2
+constexpr int kScrCnOffset = kTileCodes * kScrRowBytes;
+inline long long scr_image_bytes(int ntiles) { return ((long long)ntiles * kScrTileBytes + 4ll * ntiles + 255) / 256 * 256; }
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+
+// hi = bf16(v), lo = bf16(v - hi) of 8 floats (plain round-to-nearest casts: v_cvt_pk_bf16_f32)
+__device__ __forceinline__ void split_bf16x2(const f32x8 &v, bf16x8 &hi, bf16x8 &lo) {
+    hi = __builtin_convertvector(v, bf16x8);
+    const f32x8 r = v - __builtin_convertvector(hi, f32x8);
+    lo = __builtin_convertvector(r, bf16x8);
+}
+
+// The bf16x3 image of a Dp = 256 Euclid codebook, built from its fp32 packed image (values -2c, |c|^2 at float Dp, +inf for
+// the padding rows).  Per 32-code tile: row c at c * 1040 bytes, for each group s of 16 dims hi[16s .. 16s+7], hi[16s+8 ..
+// 16s+15], lo[16s ..], lo[16s+8 ..] (16 B each: one ds_read_b128 is one MFMA's A fragment), then the 32 |c|^2 of the tile;
+// behind the tiles the maximum |c|^2 of each tile's real codes.  Grid (tiles, heads), 256 threads: 8 per code.
+template <int DP>
+__global__ void __launch_bounds__(256) vq_pack_scr_kernel(const float *__restrict__ packed, long long pk_hs, int K, int ntiles,
+                                                          char *__restrict__ img, long long img_hs) {
+    static_assert(DP == 256, "the screened sweep is built for Dp = 256");
+    constexpr int RS = DP + 4;
+    const int t = blockIdx.x, c = threadIdx.x >> 3, part = threadIdx.x & 7;
+    const int k = t * kTileCodes + c;
+    const float *prow = packed + (long long)blockIdx.y * pk_hs + (long long)k * RS;
+    char *tile = img + (long long)blockIdx.y * img_hs + (long long)t * kScrTileBytes;
+    char *dst = tile + c * kScrRowBytes;
+#pragma unroll
+    for (int ss = 0; ss < 2; ++ss) {
+        const int s = 2 * part + ss;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int g = 2 * s + h;  // 8-dim group of the fp32 image: evens first, then odds
+            const f32x4 ev = *(const f32x4 *)(prow + 8 * g), od = *(const f32x4 *)(prow + 8 * g + 4);
+            const f32x8 v = {ev.x, od.x, ev.y, od.y, ev.z, od.z, ev.w, od.w};
+            bf16x8 hi, lo;
+            split_bf16x2(v, hi, lo);
+            *(bf16x8 *)(dst + 64 * s + 16 * h) = hi;
+            *(bf16x8 *)(dst + 64 * s + 32 + 16 * h) = lo;
+        }
+    }
+    if (part == 0) *(f32x4 *)(dst + 1024) = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+    float cmax = 0.0f;
+    if (part == 0) {
+        *(float *)(tile + kScrCnOffset + 4 * c) = prow[DP];  // the packed |c|^2 (+inf for padding rows)
+        cmax = (k < K) ? prow[DP + 2] : 0.0f;
+    }
+    // (threads 8c of the first 4 waves hold the values: a max over the workgroup through LDS)
+    __shared__ float red[kTileCodes];
+    if (part == 0) red[c] = cmax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float m = 0.0f;
+        for (int i = 0; i < kTileCodes; ++i) m = (red[i] > m || red[i] != red[i]) ? red[i] : m;
+        *(float *)(img + (long long)blockIdx.y * img_hs + (long long)ntiles * kScrTileBytes + 4 * t) = m;
+    }
+}
+
+// The exact rule (oracle/vq_oracle.c; repair_nonfinite_rows) for the rows of `todo`, Euclid: one row at a time, the row in
+// wave-private LDS, the 64 lanes stride over the codes TWO at a time (k, k + 64: two k-ordered fmaf chains in one v_pk_fma_f32,
+// bit for bit the scalar chains), the 16 code values of 8 dims of both codes loaded 16 dims ahead of their use so that the
+// L2 latency of the packed image overlaps the arithmetic.  First NaN, else first minimum of the correctly rounded sqrt, then
+// the 6-step butterfly (NaN first, value, index).  `xn_of(rr)` = the row's d-ordered |x|^2 chain.
+template <int DP, typename FillRow, typename XnOf>
+__device__ __forceinline__ void exact_rows_euclid(unsigned todo, float *rowbuf, const float *pk, int K, int lane, FillRow fill_row,
+                                                  XnOf xn_of, float &best_s, int &best_i) {
+    constexpr int RS = DP + 4;
+    constexpr int GC = 2;  // 8-dim groups per chunk
+    const int c = lane & 31;
+    while (todo) {
+        const int rr = __builtin_ctz(todo);  // wave-uniform
+        todo &= todo - 1;
+        fill_row(rr);
+        const float xn = xn_of(rr);
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        float bv = __builtin_inff();
+        int bi = (lane < K) ? lane : 0x7FFFFFFF;
+        bool bn = false;
+#pragma clang loop unroll(disable)
+        for (int k0 = lane; k0 < K; k0 += 128) {
+            const int k1 = k0 + 64;
+            const bool ok1 = k1 < K;
+            const float *p0 = pk + (long long)k0 * RS;
+            const float *p1 = pk + (long long)(ok1 ? k1 : k0) * RS;
+            f32x2 acc = {0.0f, 0.0f};
+            f32x4 e0[GC], o0[GC], e1[GC], o1[GC];
+#pragma unroll
+            for (int g = 0; g < GC; ++g) {
+                e0[g] = *(const f32x4 *)(p0 + 8 * g); o0[g] = *(const f32x4 *)(p0 + 8 * g + 4);
+                e1[g] = *(const f32x4 *)(p1 + 8 * g); o1[g] = *(const f32x4 *)(p1 + 8 * g + 4);
+            }
+#pragma clang loop unroll(disable)
+            for (int ch = 0; ch < DP / (8 * GC); ++ch) {
+                f32x4 ce0[GC], co0[GC], ce1[GC], co1[GC];
+#pragma unroll
+                for (int g = 0; g < GC; ++g) {
+                    ce0[g] = e0[g]; co0[g] = o0[g]; ce1[g] = e1[g]; co1[g] = o1[g];
+                }
+                if (ch + 1 < DP / (8 * GC)) {
+#pragma unroll
+                    for (int g = 0; g < GC; ++g) {
+                        const int gg = (ch + 1) * GC + g;
+                        e0[g] = *(const f32x4 *)(p0 + 8 * gg); o0[g] = *(const f32x4 *)(p0 + 8 * gg + 4);
+                        e1[g] = *(const f32x4 *)(p1 + 8 * gg); o1[g] = *(const f32x4 *)(p1 + 8 * gg + 4);
+                    }
+                }
+#pragma unroll
+                for (int g = 0; g < GC; ++g) {
+                    const int gg = ch * GC + g;
+                    const f32x4 xa = *(const f32x4 *)(rowbuf + 8 * gg), xb = *(const f32x4 *)(rowbuf + 8 * gg + 4);
+                    acc = __builtin_elementwise_fma((f32x2){xa.x, xa.x}, (f32x2){ce0[g].x, ce1[g].x}, acc);
+                    acc = __builtin_elementwise_fma((f32x2){xa.y, xa.y}, (f32x2){co0[g].x, co1[g].x}, acc);
+                    acc = __builtin_elementwise_fma((f32x2){xa.z, xa.z}, (f32x2){ce0[g].y, ce1[g].y}, acc);
+                    acc = __builtin_elementwise_fma((f32x2){xa.w, xa.w}, (f32x2){co0[g].y, co1[g].y}, acc);
+                    acc = __builtin_elementwise_fma((f32x2){xb.x, xb.x}, (f32x2){ce0[g].z, ce1[g].z}, acc);
+                    acc = __builtin_elementwise_fma((f32x2){xb.y, xb.y}, (f32x2){co0[g].z, co1[g].z}, acc);
+                    acc = __builtin_elementwise_fma((f32x2){xb.z, xb.z}, (f32x2){ce0[g].w, ce1[g].w}, acc);
+                    acc = __builtin_elementwise_fma((f32x2){xb.w, xb.w}, (f32x2){co0[g].w, co1[g].w}, acc);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                if (j == 1 && !ok1) break;
+                const int k = j ? k1 : k0;
+                float tt = fmaf(1.0f, xn, acc[j]);
+                tt = fmaf((j ? p1 : p0)[DP], 1.0f, tt);
+                tt = (tt < 0.0f) ? 0.0f : tt;  // clamp_min_(0): keeps NaN
+                const float s = sqrtf(tt);
+                if (!bn) {
+                    if (s != s) {
+                        bn = true;
+                        bv = s;
+                        bi = k;
+                    } else if (s < bv) {
+                        bv = s;
+                        bi = k;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int on = __shfl_xor((int)bn, o);
+            const float ov = __shfl_xor(bv, o);
+            const int oi = __shfl_xor(bi, o);
+            bool take;
+            if (on != (int)bn) take = on != 0;
+            else if (bn) take = oi < bi;
+            else take = (ov < bv) || (ov == bv && oi < bi);
+            if (take) {
+                bn = on != 0;
+                bv = ov;
+                bi = oi;
+            }
+        }
+        if (c == rr) {
+            best_s = bv;
+            best_i = bi;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the row buffer is rewritten by the next row
+    }
+}
+
+
+// The exact distances (oracle/vq_oracle.c's chain: k-ordered fmaf over the dims, + |x|^2, + |c|^2, clamp_min(0), correctly
+// rounded sqrt) of one row and TWO codes of the fp32 packed image at once: the two chains run in one v_pk_fma_f32, bit for bit
+// the scalar chains.  `xr` = the natural fp32 row (D % 4 == 0, 16-B aligned), `xn` = its d-ordered |x|^2 chain.  Loads run
+// one chunk of 16 dims ahead of the arithmetic.
+template <int DP>
+__device__ __forceinline__ f32x2 exact_pair_euclid(const float *xr, int D, const float *p0, const float *p1, float xn) {
+    constexpr int GC = 2, NCH = DP / (8 * GC);
+    f32x2 acc = {0.0f, 0.0f};
+    f32x4 e0[GC], o0[GC], e1[GC], o1[GC], xa[GC], xb[GC];
+    auto load = [&](int ch) {
+#pragma unroll
+        for (int g = 0; g < GC; ++g) {
+            const int gg = ch * GC + g;
+            e0[g] = *(const f32x4 *)(p0 + 8 * gg); o0[g] = *(const f32x4 *)(p0 + 8 * gg + 4);
+            e1[g] = *(const f32x4 *)(p1 + 8 * gg); o1[g] = *(const f32x4 *)(p1 + 8 * gg + 4);
+            const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
+            xa[g] = (8 * gg < D) ? *(const f32x4 *)(xr + 8 * gg) : z;
+            xb[g] = (8 * gg + 4 < D) ? *(const f32x4 *)(xr + 8 * gg + 4) : z;
+        }
+    };
+    load(0);
+#pragma clang loop unroll(disable)
+    for (int ch = 0; ch < NCH; ++ch) {
+        f32x4 ce0[GC], co0[GC], ce1[GC], co1[GC], cxa[GC], cxb[GC];
+#pragma unroll
+        for (int g = 0; g < GC; ++g) {
+            ce0[g] = e0[g]; co0[g] = o0[g]; ce1[g] = e1[g]; co1[g] = o1[g]; cxa[g] = xa[g]; cxb[g] = xb[g];
+        }
+        if (ch + 1 < NCH) load(ch + 1);
+#pragma unroll
+        for (int g = 0; g < GC; ++g) {
+            const f32x4 a = cxa[g], b = cxb[g];
+            acc = __builtin_elementwise_fma((f32x2){a.x, a.x}, (f32x2){ce0[g].x, ce1[g].x}, acc);
+            acc = __builtin_elementwise_fma((f32x2){a.y, a.y}, (f32x2){co0[g].x, co1[g].x}, acc);
+            acc = __builtin_elementwise_fma((f32x2){a.z, a.z}, (f32x2){ce0[g].y, ce1[g].y}, acc);
+            acc = __builtin_elementwise_fma((f32x2){a.w, a.w}, (f32x2){co0[g].y, co1[g].y}, acc);
+            acc = __builtin_elementwise_fma((f32x2){b.x, b.x}, (f32x2){ce0[g].z, ce1[g].z}, acc);
+            acc = __builtin_elementwise_fma((f32x2){b.y, b.y}, (f32x2){co0[g].z, co1[g].z}, acc);
+            acc = __builtin_elementwise_fma((f32x2){b.z, b.z}, (f32x2){ce0[g].w, ce1[g].w}, acc);
+            acc = __builtin_elementwise_fma((f32x2){b.w, b.w}, (f32x2){co0[g].w, co1[g].w}, acc);
+        }
+    }
+    f32x2 r;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        float tt = fmaf(1.0f, xn, acc[j]);
+        tt = fmaf((j ? p1 : p0)[DP], 1.0f, tt);
+        tt = (tt < 0.0f) ? 0.0f : tt;
+        r[j] = sqrtf(tt);
+    }
+    return r;
+}
+
+#ifdef VQ_EXP_SCREEN_COUNT
+__device__ unsigned long long g_scr_rows[3];  // [0] rows searched again in full, [1] rows screened, [2] rows rescored
+#endif
+
+// SCREEN: the screened sweep described above (Dp = 256, Euclid, no TRAIN); p.scr holds the bf16x3 images.
+template <int DP, int WAVES, int METRIC, bool TRAIN = false, bool SCREEN = false>
 __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchParams p) {
+    static_assert(!SCREEN || (DP == 256 && METRIC == VQ_METRIC_EUCLID && !TRAIN), "screened sweep: Dp = 256, Euclid, inference");
     using G = Geo<DP, WAVES>;
     constexpr int RS = G::RS, RS4 = G::RS4, CH = G::CH, XS = G::XS, NS = G::NS, SUB = G::SUB;
     constexpr bool EUCLID = (METRIC == VQ_METRIC_EUCLID);
@@ -35,6 +301,22 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
     const float *xh = p.x + (long long)head * p.x_hs;
     const float *pk = p.packed + (long long)head * p.pk_hs;
     const float *cbh = p.cb + (long long)head * p.cb_hs;
+    const float *scrh = SCREEN ? (const float *)((const char *)p.scr + head * p.scr_hs) : nullptr;
+    // SCREEN: max |c|^2 of the codebook (the bound's nc^2) from the per-tile maxima behind the tiles
+    float scr_mcn = 0.0f;
+    if constexpr (SCREEN) {
+        const float *tmax = (const float *)((const char *)scrh + (long long)p.ntiles * kScrTileBytes);
+        for (int i = lane; i < p.ntiles; i += 64) {
+            const float v = tmax[i];
+            scr_mcn = (v > scr_mcn || v != v) ? v : scr_mcn;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float v = __shfl_xor(scr_mcn, o);
+            scr_mcn = (v > scr_mcn || v != v) ? v : scr_mcn;
+        }
+        scr_mcn = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scr_mcn)));  // (wave-uniform: a scalar register)
+    }
     float *outh = p.out ? p.out + (long long)head * p.out_hs : nullptr;
     const float INF = __builtin_inff();
     const int nblk = (int)((p.M + 32 * WAVES - 1) / (32 * WAVES));
@@ -84,8 +366,13 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
 #pragma unroll
         for (int i2 = 0; i2 < (G::TILE_CHUNKS + WAVES - 1) / WAVES; ++i2) {
             const int ck = i2 * WAVES + wave;
-            if (ck < G::TILE_CHUNKS)
+            if constexpr (SCREEN) {
+                static_assert(kScrTileBytes <= G::BUF_F4 * 16, "a bf16x3 tile fits the fp32 tile's buffer");
+                if (ck < (kScrTileBytes + 1023) / 1024)
+                    lds_dma16(scrh, p.scr_bytes, lane * 16, tile * kScrTileBytes + ck * 1024, tile4_lds + buf * G::BUF_F4 + ck * 64);
+            } else if (ck < G::TILE_CHUNKS) {
                 lds_dma16(pk, p.pk_bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16, tile4_lds + buf * G::BUF_F4 + ck * 64);
+            }
         }
     };
     int it = 0;
@@ -97,7 +384,8 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         stage(0, 0);
         // ---------------- prologue: this wave's 32 rows -> MFMA fragments in registers (vq_search_mfma's) ----------------
         __builtin_amdgcn_s_setprio(2);
-        float xf[NS];
+        float xf[NS];  // (unused by SCREEN)
+        bf16x8 xhf[SCREEN ? DP / 16 : 1], xlf[SCREEN ? DP / 16 : 1];  // SCREEN: B fragments of group s = 16 dims (hi, lo)
         float xn0 = 0.0f;
         {
             float *xs = smem + G::NBUF * G::BUF_F4 * 4 + wave * (32 * XS);
@@ -129,6 +417,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 const float *rp = xs + c * XS;
+                f32x4 plo, phi;  // SCREEN: the previous (even) group of 8 dims
 #pragma unroll
                 for (int j = 0; j < CH / 8; ++j) {
                     const f32x4 lo = *(const f32x4 *)(rp + 8 * j);
@@ -143,6 +432,19 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
                         xn0 = fmaf(hi.z, hi.z, xn0);
                         xn0 = fmaf(hi.w, hi.w, xn0);
                         asm volatile("" : "+v"(xn0));
+                    }
+                    if constexpr (SCREEN) {
+                        // B operand of v_mfma_f32_32x32x16_bf16: lane (c, h) holds dims 16 s + 8 h .. + 7 of row c
+                        if (j & 1) {
+                            const f32x8 v8 = h ? (f32x8){lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}
+                                               : (f32x8){plo.x, plo.y, plo.z, plo.w, phi.x, phi.y, phi.z, phi.w};
+                            const int sg = ch * (CH / 16) + (j >> 1);
+                            split_bf16x2(v8, xhf[sg], xlf[sg]);
+                        } else {
+                            plo = lo;
+                            phi = hi;
+                        }
+                        continue;
                     }
                     const f32x4 m = h ? hi : lo;
                     const auto xy = __builtin_amdgcn_permlane32_swap(__float_as_uint(m.x), __float_as_uint(m.y), false, false);
@@ -162,7 +464,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         const float b_aug = EUCLID ? (h ? 1.0f : xn0) : 1.0f;
 
         LaneBest lb;
-        lb.best_t = sweep_start_value<METRIC>(codebook_flag(pk, p.pk_bytes));
+        lb.best_t = sweep_start_value<METRIC>(codebook_flag(pk, p.pk_bytes));  // (SCREEN: reset below)
         lb.pend_u = 0;
         lb.pend = (f32x16){0};
         lb.run_m = -INF;
@@ -170,8 +472,98 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
 #pragma unroll
         for (int r = 0; r < 16; ++r) lb.pend[r] = EUCLID ? INF : -INF;
 
+        const unsigned cb_flag = codebook_flag(pk, p.pk_bytes);
+        if constexpr (SCREEN) lb.best_t = INF;  // (a flagged codebook makes every row uncertain instead, below)
+        // SCREEN, per lane over its codes: lowest value b1 (lb.best_t, its code lb.pend_u), second lowest b2 (code scr_i2) and
+        // third lowest b3 over distinct codes.  Per value v: b3 = med3(b2, b3, v), b2 = med3(b1, b2, v), b1 = min(b1, v) (each
+        // med3 is the new k-th lowest because b1 <= b2 <= b3); the codes are looked up only when the two lowest change.
+        float scr_b2 = INF, scr_b3 = INF;
+        int scr_i2 = 0;
+        auto epilogue = [&](const f32x16 &v, int u) {
+            if constexpr (SCREEN) {
+                const float o1 = lb.best_t, o2 = scr_b2;
+                float b1 = o1, b2 = o2;
+#define VQ_SCR_STEP(r) "v_med3_f32 %2, %1, %2, %" #r "\n\tv_med3_f32 %1, %0, %1, %" #r "\n\tv_min_f32 %0, %0, %" #r "\n\t"
+                asm(VQ_SCR_STEP(3) VQ_SCR_STEP(4) VQ_SCR_STEP(5) VQ_SCR_STEP(6) VQ_SCR_STEP(7) VQ_SCR_STEP(8) VQ_SCR_STEP(9)
+                    VQ_SCR_STEP(10) VQ_SCR_STEP(11) VQ_SCR_STEP(12) VQ_SCR_STEP(13) VQ_SCR_STEP(14) VQ_SCR_STEP(15) VQ_SCR_STEP(16)
+                    VQ_SCR_STEP(17) VQ_SCR_STEP(18)
+                    : "+v"(b1), "+v"(b2), "+v"(scr_b3)
+                    : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]), "v"(v[9]),
+                      "v"(v[10]), "v"(v[11]), "v"(v[12]), "v"(v[13]), "v"(v[14]), "v"(v[15]));
+#undef VQ_SCR_STEP
+                const bool nb1 = b1 < o1;
+                if (nb1 || b2 < o2) {  // the two lowest changed: their codes (lowest r holding the value, distinct codes)
+                    int off1 = 0, off2 = 0;
+#pragma unroll
+                    for (int r = 15; r >= 0; --r) off1 = (v[r] == b1) ? (r & 3) + 8 * (r >> 2) : off1;
+#pragma unroll
+                    for (int r = 15; r >= 0; --r) {
+                        const int o = (r & 3) + 8 * (r >> 2);
+                        off2 = (v[r] == b2 && !(nb1 && o == off1)) ? o : off2;
+                    }
+                    const int base = u * kTileCodes + 4 * h;
+                    const int i1 = lb.pend_u;
+                    scr_i2 = (nb1 && b2 == o1) ? i1 : base + off2;  // the old lowest demoted, or a code of this sub-tile
+                    if (nb1) lb.pend_u = base + off1;
+                    lb.best_t = b1;
+                    scr_b2 = b2;
+                }
+            } else {
+                tile_epilogue<METRIC, DP, false>(v, u, h, p.K, lb);
+            }
+        };
+
         const int t1 = p.ntiles;
+        // SCREEN sub-tile: 16 groups of 16 dims, 3 bf16 MFMAs each (hi.hi, lo.hi, hi.lo), |c|^2 as the accumulator's start;
+        // fragments read PF groups ahead, two ds_read_b128 per 3 MFMAs (the fp32 body's reads, same addresses per lane)
+        auto run_sub_scr = [&](f32x16 &acc, f32x16 &prev, int u, bool have_prev) {
+            constexpr int NGS = DP / 16, PF = 3;
+            const int cur = u & 1;
+            const char *tb = (const char *)(tile4 + cur * G::BUF_F4);
+            const char *ta = tb + c * kScrRowBytes + 16 * h;
+            bf16x8 ah[NGS], al[NGS];
+            {
+                const f32x4 *cn4 = (const f32x4 *)(tb + kScrCnOffset);  // acc[r] <-> code 4 h + (r & 3) + 8 (r >> 2)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 cv = cn4[2 * q + h];
+                    acc[4 * q + 0] = cv.x; acc[4 * q + 1] = cv.y; acc[4 * q + 2] = cv.z; acc[4 * q + 3] = cv.w;
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < PF; ++g) {
+                ah[g] = *(const bf16x8 *)(ta + 64 * g);
+                al[g] = *(const bf16x8 *)(ta + 64 * g + 32);
+            }
+            copy_step();
+            auto groups = [&](auto g0c, auto g1c) {
+                constexpr int G0 = decltype(g0c)::value, G1 = decltype(g1c)::value;
+#pragma unroll
+                for (int g = G0; g < G1; ++g) {
+                    if (g + PF < NGS) {
+                        ah[g + PF] = *(const bf16x8 *)(ta + 64 * (g + PF));
+                        al[g + PF] = *(const bf16x8 *)(ta + 64 * (g + PF) + 32);
+                    }
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[g], xhf[g], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[g], xhf[g], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[g], xlf[g], acc, 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            groups(IntC<0>{}, IntC<1>{});
+            if (have_prev) epilogue(prev, u - 1);
+            __builtin_amdgcn_sched_barrier(0);
+            groups(IntC<1>{}, IntC<3>{});
+            if (u + 1 < t1) stage(u + 1, cur ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
+            groups(IntC<3>{}, IntC<NGS>{});
+            __syncthreads();
+        };
         auto run_sub = [&](f32x16 &acc, f32x16 &prev, int u, bool have_prev) {
+            if constexpr (SCREEN) {
+                run_sub_scr(acc, prev, u, have_prev);
+                return;
+            }
             const int t = u / SUB, st = u % SUB;
             const int cur = t & 1;
             const f32x4 *tb = tile4 + cur * G::BUF_F4 + st * (kTileCodes * RS4);
@@ -185,7 +577,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             copy_step();  // one row of the PREVIOUS block: store the row loaded a sub-tile ago, load the next one (right after
                           // the barrier: the whole sub-tile lies between these accesses and the next barrier's vmcnt(0))
             mfma_range<DP, 0, G1>(acc, a, ta, xf);
-            if (have_prev) tile_epilogue<METRIC, DP, false>(prev, u - 1, h, p.K, lb);
+            if (have_prev) epilogue(prev, u - 1);
             __builtin_amdgcn_sched_barrier(0);
             mfma_range<DP, G1, G2>(acc, a, ta, xf);
             if (st == 0 && t + 1 < t1) stage(t + 1, cur ^ 1);
@@ -210,9 +602,9 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             }
             if (u < u1) {
                 run_sub(acc0, acc1, u, have_prev);
-                tile_epilogue<METRIC, DP, false>(acc0, u, h, p.K, lb);
+                epilogue(acc0, u);
             } else if (have_prev) {
-                tile_epilogue<METRIC, DP, false>(acc1, u - 1, h, p.K, lb);
+                epilogue(acc1, u - 1);
             }
         }
         // rows of the previous block the sweep did not get to (short sweeps), and the last store
@@ -220,6 +612,71 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
 
         float best_s;
         int best_i;
+        if constexpr (SCREEN) {
+            // the screened argmin of this lane (lowest code holding the lowest value), then both lane halves of the row
+            const float l1 = lb.best_t, l2 = scr_b2;  // this lane's two lowest (codes lb.pend_u, scr_i2)
+            const int li1 = lb.pend_u, li2 = scr_i2;
+            best_i = li1 < p.K ? li1 : p.K - 1;
+            float b1 = l1;
+            const float ob1 = __shfl_xor(l1, 32), ob2 = __shfl_xor(l2, 32), ob3 = __shfl_xor(scr_b3, 32);
+            const int oi = __shfl_xor(best_i, 32);
+            const float b2 = fminf(fmaxf(l1, ob1), fminf(l2, ob2));  // second lowest of the row over distinct codes
+            if (ob1 < b1 || (ob1 == b1 && oi < best_i)) {
+                b1 = ob1;
+                best_i = oi;
+            }
+            // certainty test (the bound: top of this file)
+            const float nx = sqrtf(xn0), nc = sqrtf(scr_mcn);
+            const float delta = 2.5e-4f * (2.0f * nx * nc) + 1e-4f * scr_mcn + 3e-7f * xn0 + 0x1p-110f * (1.0f + nx + nc);
+            const float w = 0x1p-20f * (__builtin_fabsf(b1) + xn0 + delta);
+            const bool eligible = cb_flag == 0u && xn0 <= 0x1p100f && scr_mcn <= 0x1p100f && (b1 + xn0 > 2.0f * delta);
+            const bool certain = eligible && (b2 - b1 > 2.0f * delta + w);
+            best_s = 0.0f;  // (the screened calls do not return distances)
+            // Uncertain rows.  Only a code with S <= thr = b1 + 2 delta + w can beat or tie the exact winner (its D would
+            // otherwise exceed the winner's by more than the sqrt rounding window, and `eligible` excludes clamping).  When
+            // the third lowest value of BOTH lane halves is above thr, the row's candidates are among the <= 4 codes the
+            // halves hold: they are rescored by the exact chain (rescore), every other row is searched again in full.
+            const float thr = b1 + 2.0f * delta + w;
+            const bool complete = eligible && scr_b3 > thr && ob3 > thr;
+            const unsigned rescore = (unsigned)__ballot(row_ok && !certain && complete);
+            const unsigned todo = (unsigned)__ballot(row_ok && !certain && !complete);
+#ifdef VQ_EXP_SCREEN_COUNT
+            const unsigned rows_here = (unsigned)__ballot(row_ok);  // (outside the branch: a ballot sees the active lanes only)
+            if (lane == 0) {
+                atomicAdd(&g_scr_rows[0], (unsigned long long)__builtin_popcount(todo));
+                atomicAdd(&g_scr_rows[1], (unsigned long long)__builtin_popcount(rows_here));
+                atomicAdd(&g_scr_rows[2], (unsigned long long)__builtin_popcount(rescore));
+            }
+#endif
+            if (rescore != 0u) {
+                // lane (c, h): the exact chains of its own candidates for row c (two k-ordered fmaf chains in one v_pk_fma_f32)
+                const bool mine = (rescore >> c) & 1u;
+                const bool u1 = mine && l1 <= thr, u2 = mine && l2 <= thr;
+                const int k1 = u1 ? li1 : 0, k2 = u2 ? li2 : k1;
+                const f32x2 sd = exact_pair_euclid<DP>(xh + (row_ok ? row : p.M - 1) * p.x_rs, p.D, pk + (long long)k1 * (DP + 4),
+                                                       pk + (long long)k2 * (DP + 4), xn0);
+                // lowest distance, then lowest code, over the lane's candidates and then over both halves of the row
+                float bv = u1 ? sd.x : INF;
+                int bk = u1 ? k1 : 0x7FFFFFFF;
+                if (u2 && (sd.y < bv || (sd.y == bv && k2 < bk))) {
+                    bv = sd.y;
+                    bk = k2;
+                }
+                const float ov = __shfl_xor(bv, 32);
+                const int ok = __shfl_xor(bk, 32);
+                if (ov < bv || (ov == bv && ok < bk)) bk = ok;
+                if (mine) best_i = bk;
+            }
+            if (todo != 0u) {
+                float *rowbuf = smem + G::NBUF * G::BUF_F4 * 4 + wave * (32 * XS);  // this wave's row staging region
+                auto fill_row = [&](int rr) {
+#pragma clang loop unroll(disable)
+                    for (int d = lane; d < DP; d += 64) rowbuf[d] = (d < p.D) ? xh[(row0 + rr) * p.x_rs + d] : 0.0f;
+                };
+                auto xn_of = [&](int rr) -> float { return __shfl(xn0, rr); };
+                exact_rows_euclid<DP>(todo, rowbuf, pk, p.K, lane, fill_row, xn_of, best_s, best_i);  // (lanes c and c + 32)
+            }
+        } else {
         resolve_best<METRIC>(lb, h, p.K, best_s, best_i);
         {
             const float os = __shfl_xor(best_s, 32);
@@ -241,6 +698,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             };
             auto acc_init = [&](int, int) -> float { return 0.0f; };
             repair_nonfinite_rows<METRIC, DP>(todo, rowbuf, pk, 0, p.K, lane, fill_row, acc_init, best_s, best_i);
+        }
         }
         if (h == 0 && row_ok) {
             const long long o = (long long)head * p.idx_hs + row * p.idx_rs;
