@@ -231,6 +231,37 @@ int vq_softmax_stats_f32(const vq_args *a, float scale, const int64_t *target, i
 int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_logit, const int64_t *target, int64_t tgt_rs,
                        int64_t tgt_hs, const float *coef, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream);
 
+/*
+ * Lookup-free quantization (LFQ) over C codebooks of d sign bits each, 1 <= d <= 20 (implicit codebook {-a, +a}^d).
+ * v: [N][C][d] fp32, element (m, c, i) at v[m * v_rs + c * d + i] (rows may be strided, each row's C * d values contiguous).
+ *
+ * vq_lfq_quantize_f32 -- the quantize step, lookup_free_quantization.py:250-276 (and the commitment loss, :323-336):
+ *   q[(m * C + c) * d + i] = v > 0 ? qmag : -qmag  (0 and NaN give -qmag; qmag = codebook_scale, or the spherical code's
+ *   l2-normalised magnitude); idx[m * C + c] = sum_i (v > 0) << (d - 1 - i)  (dim 0 is the MSB, the reference's mask);
+ *   out (may be NULL) = xa + (q - xa) with xa [N][C][d] at xa[m * xa_rs + c * d + i] (straight-through, :281-283);
+ *   commit_sum (device double, may be NULL) = sum over rows with mask[m] != 0 (mask NULL: all rows) of (v - q)^2, fixed
+ *   summation order.  workspace: vq_lfq_workspace_bytes(N, 0, C, d) bytes when commit_sum is set.
+ * vq_lfq_entropy_fwd_f32 -- the entropy aux loss, lookup_free_quantization.py:294-331, for the R rows listed in `rows`
+ *   (int64 row numbers of v; NULL = rows 0 .. R-1), with a = code_scale and tau = inv_temperature:
+ *   per_sample_sum (device double) = sum over (row, c) of -sum_k p_k log(max(p_k, 1e-5));  avg_prob [C][2^d] =
+ *   mean over the rows of p  (p = softmax_k(2 tau a sum_i v_i (2 b_{k,i} - 1)), factorised per dim: no [R][2^d] buffer).
+ *   workspace: vq_lfq_workspace_bytes(R, R, C, d) bytes (O(R * C * 2^ceil(d/2) + C * 2^d)).  Fixed summation order.
+ * vq_lfq_entropy_bwd_f32 -- its backward with respect to v for the same rows (other rows of grad_v are not written):
+ *   grad_v = d/dv [ w_ps[0] * sum_(row, c) H(p) + sum_(row, c, k) w_cb[c * 2^d + k] * p_k ]  where H(p) is the clamped entropy
+ *   above;  the caller folds the upstream gradients and every mean factor into the device scalar w_ps and the table w_cb
+ *   (for the codebook entropy: w_cb = g * dH/d avg_prob / (C * R * world size)).
+ */
+int64_t vq_lfq_workspace_bytes(int64_t N, int64_t R, int C, int d);
+int vq_lfq_quantize_f32(const float *v, int64_t v_rs, const float *xa, int64_t xa_rs, int64_t N, int C, int d, float qmag,
+                        const uint8_t *mask, float *q, float *out, int64_t *idx, double *commit_sum, void *workspace,
+                        int64_t workspace_bytes, void *stream);
+int vq_lfq_entropy_fwd_f32(const float *v, int64_t v_rs, const int64_t *rows, int64_t R, int C, int d, float code_scale,
+                           float inv_temperature, float *avg_prob, double *per_sample_sum, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+int vq_lfq_entropy_bwd_f32(const float *v, int64_t v_rs, const int64_t *rows, int64_t R, int C, int d, float code_scale,
+                           float inv_temperature, const float *w_ps, const float *w_cb, float *grad_v, int64_t gv_rs,
+                           void *stream);
+
 const char *vq_last_error(void);
 int vq_device_info(char *buf, size_t n); /* "gfx950 ... CUs" of the current device */
 

@@ -30,6 +30,7 @@
 //   vq_search_resident.inc small codebooks: the packed image stays in LDS, no barriers, rows streamed past it by LDS-DMA slabs
 //   vq_similarity.inc    the same sweep with the similarity / online-softmax epilogues, fused cross-entropy backward
 //   vq_finalize_ema.inc  scalar fallback search, finalize-from-keys, loss reduction, EMA codebook update
+//   vq_lfq.inc           lookup-free quantization: sign quantizer, factorised entropy loss forward / backward
 //   this file            host-side dispatch and the C ABI (include/vq_mi355x.h)
 //
 // Reference lines replaced (relative to the reference root): vector_quantization/codebooks.py:386-397,
@@ -47,7 +48,7 @@
 // the same file once per part (-DVQ_PART=n, in parallel) and links the objects: every part sees the same templates, but only
 // its own launchers are defined -- and with them instantiated -- there; the other parts call them through the
 // vqi::part_* entry points declared below.
-//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA)      4 search Dp = 512 + wave-pair kernel
+//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward
 #ifndef VQ_PART
@@ -72,6 +73,7 @@ namespace {
 #include "vq_similarity.inc"
 #if VQ_OWN(0)
 #include "vq_finalize_ema.inc"
+#include "vq_lfq.inc"
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1683,6 +1685,84 @@ int vq_nearest_f32(const vq_args *a, void *stream) {
 }
 
 int vq_residual_f32(const vq_args *a, void *stream) { return vq_quantize_f32(a, stream); }
+
+int64_t vq_lfq_workspace_bytes(int64_t N, int64_t R, int C, int d) {
+    if (lfq_check_shape(N, C, d) || R < 0 || R > N) return 0;
+    return lfq_ws_layout(N, R, C, d).total;
+}
+
+int vq_lfq_quantize_f32(const float *v, int64_t v_rs, const float *xa, int64_t xa_rs, int64_t N, int C, int d, float qmag,
+                        const uint8_t *mask, float *q, float *out, int64_t *idx, double *commit_sum, void *workspace,
+                        int64_t workspace_bytes, void *stream) {
+    int rc = lfq_check_shape(N, C, d);
+    if (rc) return rc;
+    if (!v || !q || !idx || (out && !xa)) return fail(VQ_E_BADARG, "vq_lfq_quantize: null pointer");
+    if (v_rs < (int64_t)C * d || (out && xa_rs < (int64_t)C * d)) return fail(VQ_E_BADARG, "vq_lfq_quantize: row stride < C * d");
+    const LfqWs ws = lfq_ws_layout(N, 0, C, d);
+    if (commit_sum && (!workspace || workspace_bytes < ws.ent)) return fail(VQ_E_BADARG, "vq_lfq_quantize: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t blocks = lfq_quant_blocks(N, C);
+    double *part = commit_sum ? (double *)((char *)workspace + ws.commit) : nullptr;
+    if (blocks > 0)
+        hipLaunchKernelGGL(lfq_quantize_kernel, dim3((unsigned)blocks), dim3(kLfqQuantThreads), 0, s, v, v_rs, xa, xa_rs, N, C, d,
+                           qmag, mask, q, out, idx, part);
+    if (commit_sum) hipLaunchKernelGGL(lfq_sum_kernel<double>, dim3(1), dim3(kLfqSumThreads), 0, s, part, blocks, commit_sum);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "vq_lfq_quantize launch");
+    return 0;
+}
+
+int vq_lfq_entropy_fwd_f32(const float *v, int64_t v_rs, const int64_t *rows, int64_t R, int C, int d, float code_scale,
+                           float inv_temperature, float *avg_prob, double *per_sample_sum, void *workspace,
+                           int64_t workspace_bytes, void *stream) {
+    int rc = lfq_check_shape(R, C, d);
+    if (rc) return rc;
+    if (R < 1) return fail(VQ_E_BADARG, "vq_lfq_entropy_fwd: no rows selected");
+    if (!v || !avg_prob || !per_sample_sum || !workspace) return fail(VQ_E_BADARG, "vq_lfq_entropy_fwd: null pointer");
+    if (v_rs < (int64_t)C * d) return fail(VQ_E_BADARG, "vq_lfq_entropy_fwd: row stride < C * d");
+    const LfqWs ws = lfq_ws_layout(R, R, C, d);
+    if (workspace_bytes < ws.total) return fail(VQ_E_BADARG, "vq_lfq_entropy_fwd: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    char *base = (char *)workspace;
+    float *ent = (float *)(base + ws.ent), *tabA = (float *)(base + ws.tabA), *tabB = (float *)(base + ws.tabB);
+    double *part = (double *)(base + ws.part);
+    const float coef = 4.0f * inv_temperature * code_scale;
+    const int waves = lfq_task_waves(d);
+    const int64_t tasks = R * C;
+    hipLaunchKernelGGL(lfq_entropy_fwd_kernel, dim3((unsigned)((tasks + waves - 1) / waves)), dim3(waves * 64),
+                       lfq_block_lds_bytes(d), s, v, v_rs, rows, R, C, d, coef, ent, tabA, tabB);
+    hipLaunchKernelGGL(lfq_sum_kernel<float>, dim3(1), dim3(kLfqSumThreads), 0, s, ent, tasks, per_sample_sum);
+    const int64_t rps = lfq_rows_per_split(R, C, d);
+    const int64_t splits = (R + rps - 1) / rps;
+    const int P = 1 << d;
+    hipLaunchKernelGGL(lfq_avg_prob_kernel, dim3((unsigned)((P + kLfqAvgCodes - 1) / kLfqAvgCodes), (unsigned)splits, (unsigned)C),
+                       dim3(kLfqAvgCodes), 0, s, tabA, tabB, R, C, d, rps, part);
+    const int64_t CP = (int64_t)C * P;
+    hipLaunchKernelGGL(lfq_avg_reduce_kernel, dim3((unsigned)((CP + 255) / 256)), dim3(256), 0, s, part, (int)splits, CP,
+                       1.0 / (double)R, avg_prob);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "vq_lfq_entropy_fwd launch");
+    return 0;
+}
+
+int vq_lfq_entropy_bwd_f32(const float *v, int64_t v_rs, const int64_t *rows, int64_t R, int C, int d, float code_scale,
+                           float inv_temperature, const float *w_ps, const float *w_cb, float *grad_v, int64_t gv_rs,
+                           void *stream) {
+    int rc = lfq_check_shape(R, C, d);
+    if (rc) return rc;
+    if (R == 0) return 0;
+    if (!v || !w_ps || !w_cb || !grad_v) return fail(VQ_E_BADARG, "vq_lfq_entropy_bwd: null pointer");
+    if (v_rs < (int64_t)C * d || gv_rs < (int64_t)C * d) return fail(VQ_E_BADARG, "vq_lfq_entropy_bwd: row stride < C * d");
+    hipStream_t s = (hipStream_t)stream;
+    const float coef = 4.0f * inv_temperature * code_scale;
+    const int waves = lfq_task_waves(d);
+    const int64_t tasks = R * C;
+    hipLaunchKernelGGL(lfq_entropy_bwd_kernel, dim3((unsigned)((tasks + waves - 1) / waves)), dim3(waves * 64),
+                       lfq_block_lds_bytes(d), s, v, v_rs, rows, R, C, d, coef, w_ps, w_cb, grad_v, gv_rs);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "vq_lfq_entropy_bwd launch");
+    return 0;
+}
 
 }  // extern "C"
 #endif  // VQ_OWN(0)

@@ -1,0 +1,344 @@
+// vq_lfq.inc -- lookup-free quantization (LFQ, lookup_free_quantization.py:294-348 of the reference): the sign quantizer
+// and the entropy aux loss over the implicit codebook {-a, +a}^d, without ever holding a [rows, 2^d] matrix.
+// Included by vq_kernels.hip inside its anonymous namespace, build part 0 (see "Build parts" there).
+//
+// The softmax over {+-a}^d factorises per dim: p_k = prod_i pi_i(b_{k,i}), pi_i(1) = sigmoid(z_i), pi_i(0) = sigmoid(-z_i),
+// z_i = 4 tau a v_i (the reference's logits are 2 tau a sum_i v_i (2 b_{k,i} - 1)).  Code k = u * NB + w: the high
+// h = ceil(d / 2) dims are the bits of u, the low d - h dims the bits of w, so p_k = A_u * B_w with two per-row tables of
+// at most 1024 entries (log p_k = LA_u + LB_w).  Bit b_{k,i} is bit d - 1 - i of k (dim 0 is the MSB, the reference's mask).
+//
+//   lfq_quantize_kernel     one thread per (row, codebook): signs -> +-qmag, int64 index, straight-through, squared error
+//                           (fp64 per-block partials, summed in a fixed order by lfq_sum_kernel)
+//   lfq_entropy_fwd_kernel  one wave per (selected row, codebook): tables in LDS, the 2^d-pair sweep of the clamped
+//                           per-sample entropy; writes A and B to the workspace for the codebook term
+//   lfq_avg_prob_kernel     avg_prob[c, k] = sum_rows A_u B_w: one thread per code, rows split over blockIdx.y, fp64
+//                           partials; lfq_avg_reduce_kernel adds the splits in order and divides by the row count
+//   lfq_entropy_bwd_kernel  one wave per (selected row, codebook): tables rebuilt in LDS, one sweep gives
+//                           S0 = sum_k g_k p_k and S_i = sum_k g_k p_k b_{k,i};  dL/dv_i = 4 tau a (S_i - pi_i(1) S0)
+// No float atomics anywhere: every sum has one fixed order, so results are bitwise run-to-run reproducible.
+
+constexpr int kLfqMaxDim = 20;
+constexpr int kLfqSumThreads = 1024;
+constexpr int kLfqQuantThreads = 256;
+constexpr int kLfqAvgCodes = 256;  // codes per lfq_avg_prob_kernel block
+constexpr float kLfqEps = 1e-5f;   // the reference's log clamp (utils/general.py:25-26)
+
+__device__ __forceinline__ float lfq_sigmoid(float z) {
+    // both branches are exact-ish: no 1 - sigmoid cancellation (pi_i(0) is sigmoid(-z) evaluated directly)
+    if (z >= 0.0f) return 1.0f / (1.0f + expf(-z));
+    const float e = expf(z);
+    return e / (1.0f + e);
+}
+
+__device__ __forceinline__ float lfq_logsigmoid(float z) { return fminf(z, 0.0f) - log1pf(expf(-fabsf(z))); }
+
+__device__ __forceinline__ float lfq_wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// quantize step (lookup_free_quantization.py:250-276, 323-336 commitment)
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kLfqQuantThreads) lfq_quantize_kernel(
+    const float *__restrict__ v, int64_t v_rs, const float *__restrict__ xa, int64_t xa_rs, int64_t N, int C, int d,
+    float qmag, const uint8_t *__restrict__ mask, float *__restrict__ q, float *__restrict__ out, int64_t *__restrict__ idx,
+    double *__restrict__ part) {
+    __shared__ double red[kLfqQuantThreads];
+    const int64_t task = (int64_t)blockIdx.x * kLfqQuantThreads + threadIdx.x;
+    double se = 0.0;
+    if (task < N * C) {
+        const int64_t m = task / C;
+        const int c = (int)(task - m * C);
+        const float *vr = v + m * v_rs + (int64_t)c * d;
+        const int64_t o = task * d;
+        const bool use = mask == nullptr || mask[m] != 0;
+        int64_t code = 0;
+        for (int i = 0; i < d; ++i) {
+            const float x = vr[i];
+            const bool pos = x > 0.0f;  // zero and NaN quantize to -a (torch.where(x > 0, ...))
+            const float qi = pos ? qmag : -qmag;
+            code = (code << 1) | (pos ? 1 : 0);
+            q[o + i] = qi;
+            if (out) {
+                const float a = xa[m * xa_rs + (int64_t)c * d + i];
+                out[o + i] = a + (qi - a);
+            }
+            if (use) {
+                const double e = (double)x - (double)qi;
+                se += e * e;
+            }
+        }
+        idx[task] = code;
+    }
+    if (part) {
+        red[threadIdx.x] = se;
+        __syncthreads();
+        for (int s = kLfqQuantThreads / 2; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+    }
+}
+
+// one block: out[0] = sum of n values in a fixed order (thread-strided fp64 sums, then a tree)
+template <typename T>
+__global__ void __launch_bounds__(kLfqSumThreads) lfq_sum_kernel(const T *__restrict__ in, int64_t n, double *__restrict__ out) {
+    __shared__ double red[kLfqSumThreads];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += kLfqSumThreads) s += (double)in[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = kLfqSumThreads / 2; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = red[0];
+}
+
+// ------------------------------------------------------------------------------------------------
+// per-row tables in LDS (one wave per (selected row, codebook) task)
+// ------------------------------------------------------------------------------------------------
+struct LfqShape {
+    int d, h, l, NA, NB;  // h = ceil(d / 2) high dims (bits of u), l = d - h low dims (bits of w), NA = 2^h, NB = 2^l
+};
+
+__host__ __device__ inline LfqShape lfq_shape(int d) {
+    LfqShape s;
+    s.d = d;
+    s.h = (d + 1) / 2;
+    s.l = d - s.h;
+    s.NA = 1 << s.h;
+    s.NB = 1 << s.l;
+    return s;
+}
+
+// floats of LDS one task uses: 4 per-dim arrays (padded to 32) + A, LA, B, LB
+__host__ __device__ inline int lfq_task_lds_floats(const LfqShape &s) { return 4 * 32 + 2 * s.NA + 2 * s.NB; }
+
+// Fills the task's LDS region: s1/s0 = sigmoid(+-z), l1/l0 = logsigmoid(+-z) per dim, then A/LA (high dims) and B/LB
+// (low dims).  Lane i < d holds z_i on return (0 elsewhere).  Every lane of the block must reach both barriers.
+__device__ __forceinline__ float lfq_build_tables(float *lds, const LfqShape &S, const float *vr, float coef, bool valid,
+                                                  int lane) {
+    float *s1 = lds, *s0 = lds + 32, *l1 = lds + 64, *l0 = lds + 96;
+    float *A = lds + 128, *LA = A + S.NA, *B = LA + S.NA, *LB = B + S.NB;
+    float z = 0.0f;
+    if (valid && lane < S.d) {
+        z = coef * vr[lane];
+        s1[lane] = lfq_sigmoid(z);
+        s0[lane] = lfq_sigmoid(-z);
+        l1[lane] = lfq_logsigmoid(z);
+        l0[lane] = lfq_logsigmoid(-z);
+    }
+    __syncthreads();
+    if (valid) {
+        for (int u = lane; u < S.NA; u += 64) {
+            float p = 1.0f, lp = 0.0f;
+            for (int i = 0; i < S.h; ++i) {
+                const bool b = (u >> (S.h - 1 - i)) & 1;
+                p *= b ? s1[i] : s0[i];
+                lp += b ? l1[i] : l0[i];
+            }
+            A[u] = p;
+            LA[u] = lp;
+        }
+        for (int w = lane; w < S.NB; w += 64) {
+            float p = 1.0f, lp = 0.0f;
+            for (int j = 0; j < S.l; ++j) {
+                const int i = S.h + j;
+                const bool b = (w >> (S.l - 1 - j)) & 1;
+                p *= b ? s1[i] : s0[i];
+                lp += b ? l1[i] : l0[i];
+            }
+            B[w] = p;
+            LB[w] = lp;
+        }
+    }
+    __syncthreads();
+    return z;
+}
+
+// ------------------------------------------------------------------------------------------------
+// entropy forward: per-sample entropy of every task + the A / B tables for the codebook term
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) lfq_entropy_fwd_kernel(const float *__restrict__ v, int64_t v_rs,
+                                                              const int64_t *__restrict__ rows, int64_t R, int C, int d,
+                                                              float coef, float *__restrict__ ent, float *__restrict__ tabA,
+                                                              float *__restrict__ tabB) {
+    extern __shared__ float lfq_lds[];
+    const LfqShape S = lfq_shape(d);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t task = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    const bool valid = task < R * C;
+    const int64_t j = valid ? task / C : 0;
+    const int c = valid ? (int)(task - j * C) : 0;
+    const int64_t m = valid ? (rows ? rows[j] : j) : 0;
+    float *lds = lfq_lds + wave * lfq_task_lds_floats(S);
+    lfq_build_tables(lds, S, v + m * v_rs + (int64_t)c * d, coef, valid, lane);
+    if (!valid) return;
+    const float *A = lds + 128, *LA = A + S.NA, *B = LA + S.NA, *LB = B + S.NB;
+    float *gA = tabA + task * S.NA, *gB = tabB + task * S.NB;
+    for (int u = lane; u < S.NA; u += 64) gA[u] = A[u];
+    for (int w = lane; w < S.NB; w += 64) gB[w] = B[w];
+    const int P = 1 << d;
+    const float log_eps = logf(kLfqEps);
+    float acc = 0.0f;
+    for (int k = lane; k < P; k += 64) {
+        const int u = k >> S.l, w = k & (S.NB - 1);
+        const float p = A[u] * B[w];
+        const float lg = p >= kLfqEps ? LA[u] + LB[w] : log_eps;
+        acc = fmaf(p, lg, acc);
+    }
+    acc = lfq_wave_sum(acc);
+    if (lane == 0) ent[task] = -acc;
+}
+
+// avg_prob partials: part[(split * C + c) * P + k] = sum over the split's rows of A_u B_w  (fp64, rows in order)
+__global__ void __launch_bounds__(kLfqAvgCodes) lfq_avg_prob_kernel(const float *__restrict__ tabA, const float *__restrict__ tabB,
+                                                                    int64_t R, int C, int d, int64_t rows_per_split,
+                                                                    double *__restrict__ part) {
+    const LfqShape S = lfq_shape(d);
+    const int P = 1 << d;
+    const int k = blockIdx.x * kLfqAvgCodes + threadIdx.x;
+    const int c = blockIdx.z;
+    const int split = blockIdx.y;
+    if (k >= P) return;
+    const int u = k >> S.l, w = k & (S.NB - 1);
+    const int64_t r0 = (int64_t)split * rows_per_split;
+    const int64_t r1 = r0 + rows_per_split < R ? r0 + rows_per_split : R;
+    double acc = 0.0;
+    for (int64_t r = r0; r < r1; ++r) {
+        const int64_t t = r * C + c;
+        acc += (double)(tabA[t * S.NA + u] * tabB[t * S.NB + w]);
+    }
+    part[((int64_t)split * C + c) * P + k] = acc;
+}
+
+__global__ void __launch_bounds__(256) lfq_avg_reduce_kernel(const double *__restrict__ part, int splits, int64_t CP,
+                                                             double inv_rows, float *__restrict__ avg) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= CP) return;
+    double s = 0.0;
+    for (int z = 0; z < splits; ++z) s += part[(int64_t)z * CP + i];
+    avg[i] = (float)(s * inv_rows);
+}
+
+// ------------------------------------------------------------------------------------------------
+// entropy backward.  g_k = w_ps * G(p_k) + w_cb[c, k]: G(x) = -(log x + 1) for x >= 1e-5, -log 1e-5 below (the clamp);
+// w_ps (device scalar) carries the upstream gradient of the per-sample entropy and its 1 / (rows * C); w_cb the codebook
+// term's G(avg_prob) with its upstream gradient, 1 / (C * world * rows) folded in by the caller.
+// Pair k = s * 64 + lane: the low 6 bits of k are the lane's own, so their S_i are bit * S0 of the lane; the bits above
+// are the same for the whole wave (one add per set bit per pair).
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) lfq_entropy_bwd_kernel(const float *__restrict__ v, int64_t v_rs,
+                                                              const int64_t *__restrict__ rows, int64_t R, int C, int d,
+                                                              float coef, const float *__restrict__ w_ps,
+                                                              const float *__restrict__ w_cb, float *__restrict__ gv,
+                                                              int64_t gv_rs) {
+    extern __shared__ float lfq_lds[];
+    const LfqShape S = lfq_shape(d);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t task = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
+    const bool valid = task < R * C;
+    const int64_t j = valid ? task / C : 0;
+    const int c = valid ? (int)(task - j * C) : 0;
+    const int64_t m = valid ? (rows ? rows[j] : j) : 0;
+    float *lds = lfq_lds + wave * lfq_task_lds_floats(S);
+    lfq_build_tables(lds, S, v + m * v_rs + (int64_t)c * d, coef, valid, lane);
+    if (!valid) return;
+    const float *A = lds + 128, *LA = A + S.NA, *B = LA + S.NA, *LB = B + S.NB;
+    const float *wc = w_cb + (int64_t)c * ((int64_t)1 << d);
+    const float wps = w_ps[0];
+    const int P = 1 << d;
+    const float neg_log_eps = -logf(kLfqEps);
+    constexpr int kHi = kLfqMaxDim - 6;
+    const int nhi = d > 6 ? d - 6 : 0;
+    float s0 = 0.0f;
+    float hi[kHi];
+#pragma unroll
+    for (int b = 0; b < kHi; ++b) hi[b] = 0.0f;
+    for (int k = lane, s = 0; k < P; k += 64, ++s) {
+        const int u = k >> S.l, w = k & (S.NB - 1);
+        const float p = A[u] * B[w];
+        const float G = p >= kLfqEps ? -(LA[u] + LB[w] + 1.0f) : neg_log_eps;
+        const float t = fmaf(wps, G, wc[k]) * p;
+        s0 += t;
+#pragma unroll
+        for (int b = 0; b < kHi; ++b)
+            if (b < nhi && ((s >> b) & 1)) hi[b] += t;
+    }
+    // dim i is bit pos = d - 1 - i of k: pos < 6 -> the lane's own bit; pos >= 6 -> bit pos - 6 of s
+    float mine = 0.0f;
+    for (int i = 0; i < d; ++i) {
+        const int pos = d - 1 - i;
+        float si = 0.0f;
+        if (pos < 6) {
+            si = ((lane >> pos) & 1) ? s0 : 0.0f;
+        } else {
+#pragma unroll
+            for (int b = 0; b < kHi; ++b)
+                if (b == pos - 6) si = hi[b];
+        }
+        si = lfq_wave_sum(si);
+        if (lane == i) mine = si;
+    }
+    const float S0 = lfq_wave_sum(s0);
+    if (lane < d) {
+        const float s1 = lds[lane];  // sigmoid(z_lane) = pi_lane(1)
+        gv[m * gv_rs + (int64_t)c * d + lane] = coef * (mine - s1 * S0);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+int lfq_task_waves(int d) { return d >= 19 ? 2 : 4; }  // 64 KiB of LDS per block at most
+
+size_t lfq_block_lds_bytes(int d) { return (size_t)lfq_task_waves(d) * lfq_task_lds_floats(lfq_shape(d)) * sizeof(float); }
+
+int64_t lfq_quant_blocks(int64_t N, int C) { return (N * C + kLfqQuantThreads - 1) / kLfqQuantThreads; }
+
+// rows per split of the codebook-term sum: ~1024 blocks in all, at least 32 rows per split (fixed by (R, C, d) alone)
+int64_t lfq_rows_per_split(int64_t R, int C, int d) {
+    const int64_t ktiles = ((1 << d) + kLfqAvgCodes - 1) / kLfqAvgCodes;
+    int64_t splits = (1024 + ktiles * C - 1) / (ktiles * C);
+    const int64_t max_splits = (R + 31) / 32;
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    return (R + splits - 1) / splits;
+}
+
+inline int64_t lfq_align(int64_t b) { return (b + 255) / 256 * 256; }
+
+struct LfqWs {
+    int64_t commit, ent, tabA, tabB, part, total;  // byte offsets
+};
+
+LfqWs lfq_ws_layout(int64_t N, int64_t R, int C, int d) {
+    const LfqShape S = lfq_shape(d);
+    const int64_t rps = lfq_rows_per_split(R > 0 ? R : 1, C, d);
+    const int64_t splits = ((R > 0 ? R : 1) + rps - 1) / rps;
+    LfqWs w;
+    int64_t off = 0;
+    w.commit = off;
+    off += lfq_align(lfq_quant_blocks(N, C) * (int64_t)sizeof(double));
+    w.ent = off;
+    off += lfq_align(R * C * (int64_t)sizeof(float));
+    w.tabA = off;
+    off += lfq_align(R * C * S.NA * (int64_t)sizeof(float));
+    w.tabB = off;
+    off += lfq_align(R * C * S.NB * (int64_t)sizeof(float));
+    w.part = off;
+    off += lfq_align(splits * C * ((int64_t)1 << d) * (int64_t)sizeof(double));
+    w.total = off;
+    return w;
+}
+
+int lfq_check_shape(int64_t N, int C, int d) {
+    if (N < 0 || C < 1) return fail(VQ_E_BADARG, "vq_lfq: N must be >= 0 and C >= 1");
+    if (d < 1 || d > kLfqMaxDim) return fail(VQ_E_UNSUPPORTED, "vq_lfq: codebook_dim must be in [1, 20]");
+    if (N * C > ((int64_t)1 << 40)) return fail(VQ_E_BADARG, "vq_lfq: too many rows");
+    return 0;
+}

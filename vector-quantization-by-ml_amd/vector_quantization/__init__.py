@@ -7,12 +7,14 @@ Import surface kept from the reference (``vector_quantization/__init__.py:11-12,
 
 The search itself (distance -> first argmax -> gather, straight-through, squared error, residual loop) is
 hand-written HIP for gfx950 behind the C ABI in ``include/vq_mi355x.h``; there is no PyTorch/CPU fallback.
-The reference's other quantizer families (FSQ, LFQ, latent quantization and their residual variants) never
-touch the codebook search and are not part of this build.
+``LFQ`` (lookup-free quantization) runs its sign quantizer and its entropy aux loss -- a sweep over an implicit codebook
+of 2^d codes -- in HIP as well.  The reference's other families (FSQ, latent quantization, the residual LFQ / FSQ
+variants) never touch a codebook search and are not part of this build.
 """
 from . import ops  # noqa: F401  (registers torch.ops.vq_mi355x.*)
 from .codebook import Codebook
 from .graphs import GraphedForward
+from .lookup_free_quantization import LFQ
 from .params import AffineParameters, CodebookParams, GumbelParams, KmeansParameters
 from .projection import RandomProjectionQuantizer
 from .quantizer import LossBreakdown, VectorQuantize
@@ -27,6 +29,7 @@ __all__ = [
     "GroupedResidualVQ",
     "GumbelParams",
     "KmeansParameters",
+    "LFQ",
     "LossBreakdown",
     "RandomProjectionQuantizer",
     "ResidualVQ",

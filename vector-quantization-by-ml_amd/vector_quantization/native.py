@@ -143,6 +143,17 @@ def load():
         lib.vq_ema_accumulate_residual_f32.restype = ctypes.c_int
         lib.vq_max_fused_stages.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.vq_max_fused_stages.restype = ctypes.c_int
+        lib.vq_lfq_workspace_bytes.argtypes = [_i64, _i64, ctypes.c_int, ctypes.c_int]
+        lib.vq_lfq_workspace_bytes.restype = _i64
+        lib.vq_lfq_quantize_f32.argtypes = [_vp, _i64, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _i64, _vp]
+        lib.vq_lfq_quantize_f32.restype = ctypes.c_int
+        lib.vq_lfq_entropy_fwd_f32.argtypes = [_vp, _i64, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                               _vp, _vp, _vp, _i64, _vp]
+        lib.vq_lfq_entropy_fwd_f32.restype = ctypes.c_int
+        lib.vq_lfq_entropy_bwd_f32.argtypes = [_vp, _i64, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                               _vp, _vp, _vp, _i64, _vp]
+        lib.vq_lfq_entropy_bwd_f32.restype = ctypes.c_int
         lib.vq_device_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         lib.vq_device_info.restype = ctypes.c_int
         _lib = lib
@@ -156,6 +167,7 @@ EXPORTED_SYMBOLS = (
     "vq_ce_backward_f32", "vq_quantize_lse_f32",
     "vq_quantize_backward_f32", "vq_ema_accumulate_residual_f32", "vq_max_fused_stages", "vq_ema_accumulate_det_f32",
     "vq_ema_det_workspace_bytes", "vq_key_planes", "vq_search_key_planes_f32", "vq_finalize_key_planes_f32",
+    "vq_lfq_workspace_bytes", "vq_lfq_quantize_f32", "vq_lfq_entropy_fwd_f32", "vq_lfq_entropy_bwd_f32",
 )
 
 
@@ -648,3 +660,99 @@ def ema_accumulate_residual(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor
         _check(load().vq_ema_accumulate_residual_f32(ctypes.byref(a), counts.data_ptr(), sums.data_ptr(),
                                                      _stream_ptr(x.device)), "vq_ema_accumulate_residual_f32")
     return counts, sums
+
+
+# ------------------------------------------------------------------------------------------------
+# lookup-free quantization (vq_lfq_* in include/vq_mi355x.h)
+# ------------------------------------------------------------------------------------------------
+LFQ_MAX_DIM = 20
+
+
+def _lfq_rows(v: torch.Tensor):
+    """v is [N, C, d] with each row's C * d values contiguous -> row stride in elements."""
+    assert v.dim() == 3 and v.dtype == torch.float32, "v must be [N, C, d] fp32"
+    N, C, d = v.shape
+    assert N <= 1 or C * d == 1 or (v.stride(2) == 1 and v.stride(1) == d), "each row's C * d values must be contiguous"
+    return int(v.stride(0)) if N > 1 else C * d
+
+
+def _lfq_workspace(N: int, R: int, C: int, d: int, device) -> torch.Tensor:
+    nbytes = int(load().vq_lfq_workspace_bytes(N, R, C, d))
+    if nbytes <= 0:
+        raise RuntimeError(f"vq_lfq_workspace_bytes({N}, {R}, {C}, {d}) failed: {load().vq_last_error().decode()}")
+    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=device)
+
+
+def lfq_quantize(v: torch.Tensor, qmag: float, *, xa: torch.Tensor | None = None, mask: torch.Tensor | None = None,
+                 want_commit: bool = False):
+    """v [N, C, d] -> (q [N, C, d], out [N, C, d] = xa + (q - xa) (q itself without xa), idx [N, C] int64,
+    commit_sum float64 scalar or None).
+    mask: [N] bool (rows counted in the squared-error sum)."""
+    _require_gpu(v, xa, mask)
+    lib = load()
+    N, C, d = v.shape
+    v_rs = _lfq_rows(v)
+    dev = v.device
+    q = torch.empty((N, C, d), dtype=torch.float32, device=dev)
+    idx = torch.empty((N, C), dtype=torch.int64, device=dev)
+    out = xa_rs = None
+    if xa is not None:
+        assert xa.shape == v.shape
+        xa_rs = _lfq_rows(xa)
+        out = torch.empty_like(q)
+    m8 = None
+    if mask is not None:
+        m8 = mask.reshape(N).to(torch.uint8).contiguous()
+    commit = ws = None
+    if want_commit:
+        commit = torch.empty((), dtype=torch.float64, device=dev)
+        ws = _lfq_workspace(N, 0, C, d, dev)
+    with torch.cuda.device(dev):
+        _check(lib.vq_lfq_quantize_f32(v.data_ptr(), v_rs, xa.data_ptr() if xa is not None else None, xa_rs or 0, N, C, d,
+                                       float(qmag), m8.data_ptr() if m8 is not None else None, q.data_ptr(),
+                                       out.data_ptr() if out is not None else None, idx.data_ptr(),
+                                       commit.data_ptr() if commit is not None else None,
+                                       ws.data_ptr() if ws is not None else None, ws.numel() * 8 if ws is not None else 0,
+                                       _stream_ptr(dev)), "vq_lfq_quantize_f32")
+    return q, (out if out is not None else q), idx, commit
+
+
+def lfq_entropy_forward(v: torch.Tensor, rows: torch.Tensor | None, code_scale: float, inv_temperature: float):
+    """Entropy statistics of the selected rows of v [N, C, d] (rows: int64 row numbers on v's device, None = all rows)
+    -> (per_sample_sum float64 scalar = sum over (row, c) of the clamped entropy, avg_prob [C, 2^d] fp32)."""
+    _require_gpu(v, rows)
+    lib = load()
+    N, C, d = v.shape
+    R = N if rows is None else int(rows.numel())
+    dev = v.device
+    if rows is not None:
+        rows = rows.to(torch.int64).contiguous()
+    avg = torch.empty((C, 1 << d), dtype=torch.float32, device=dev)
+    ps = torch.empty((), dtype=torch.float64, device=dev)
+    ws = _lfq_workspace(R, R, C, d, dev)
+    with torch.cuda.device(dev):
+        _check(lib.vq_lfq_entropy_fwd_f32(v.data_ptr(), _lfq_rows(v), rows.data_ptr() if rows is not None else None, R, C, d,
+                                          float(code_scale), float(inv_temperature), avg.data_ptr(), ps.data_ptr(),
+                                          ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)), "vq_lfq_entropy_fwd_f32")
+    return ps, avg
+
+
+def lfq_entropy_backward(v: torch.Tensor, rows: torch.Tensor | None, code_scale: float, inv_temperature: float,
+                         w_ps: torch.Tensor, w_cb: torch.Tensor) -> torch.Tensor:
+    """dL/dv [N, C, d] (zero on rows not selected) for L = w_ps * sum of per-sample entropies + sum w_cb * p (see the header)."""
+    _require_gpu(v, rows, w_ps, w_cb)
+    lib = load()
+    N, C, d = v.shape
+    R = N if rows is None else int(rows.numel())
+    dev = v.device
+    if rows is not None:
+        rows = rows.to(torch.int64).contiguous()
+    w_ps = w_ps.to(torch.float32).reshape(1).contiguous()
+    w_cb = w_cb.to(torch.float32).contiguous()
+    assert w_cb.numel() == C << d
+    gv = torch.zeros((N, C, d), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.vq_lfq_entropy_bwd_f32(v.data_ptr(), _lfq_rows(v), rows.data_ptr() if rows is not None else None, R, C, d,
+                                          float(code_scale), float(inv_temperature), w_ps.data_ptr(), w_cb.data_ptr(),
+                                          gv.data_ptr(), C * d, _stream_ptr(dev)), "vq_lfq_entropy_bwd_f32")
+    return gv
