@@ -262,6 +262,50 @@ int vq_lfq_entropy_bwd_f32(const float *v, int64_t v_rs, const int64_t *rows, in
                            float inv_temperature, const float *w_ps, const float *w_cb, float *grad_v, int64_t gv_rs,
                            void *stream);
 
+/*
+ * Residual LFQ (ResidualLFQ / GroupedResidualLFQ, residual_lfq.py of the reference), one codebook of d bits per stage.
+ *
+ * vq_lfq_entropy_staged_fwd_f32 / vq_lfq_entropy_staged_bwd_f32 -- vq_lfq_entropy_{fwd,bwd}_f32 (C = 1) for T stages in one
+ *   call: stage t reads v + t * v_ss (rows [R][d] at row stride v_rs) and the row list rows + t * rows_ss (rows NULL: rows
+ *   0 .. R-1 of every stage; rows_ss = 0: one list for all stages), uses code scale code_scale[t % period] (a device
+ *   array of period floats), and writes per_sample_sum[t], avg_prob[t * 2^d ...] (forward) or reads
+ *   w_ps[t], w_cb[t * 2^d ...] and writes grad_v + t * gv_ss (backward).  Stage t is bitwise equal to a single-stage call
+ *   on its own inputs (same kernels, same row split, same summation order).  workspace: vq_lfq_staged_workspace_bytes(R, T, d)
+ *   bytes (T times a single-stage call's).
+ */
+int64_t vq_lfq_staged_workspace_bytes(int64_t R, int T, int d);
+int vq_lfq_entropy_staged_fwd_f32(const float *v, int64_t v_rs, int64_t v_ss, const int64_t *rows, int64_t rows_ss, int64_t R,
+                                  int T, int d, const float *code_scale, int period, float inv_temperature, float *avg_prob,
+                                  double *per_sample_sum, void *workspace, int64_t workspace_bytes, void *stream);
+int vq_lfq_entropy_staged_bwd_f32(const float *v, int64_t v_rs, int64_t v_ss, const int64_t *rows, int64_t rows_ss, int64_t R,
+                                  int T, int d, const float *code_scale, int period, float inv_temperature, const float *w_ps,
+                                  const float *w_cb, float *grad_v, int64_t gv_rs, int64_t gv_ss, void *stream);
+
+/*
+ * vq_rlfq_quantize_f32 -- all S stages' quantize steps of G groups in one pass, each row's d <= 20 values in registers.
+ *   Row m of group g is x[g * x_gs + m * x_rs + i] (i < d, contiguous).  stage_consts: device floats [3][S], rows
+ *   qmag (|code entry| of stage s: its codebook scale, or the l2-normalised code's magnitude), clamp (soft clamp value,
+ *   0 = none) and scale (codebook scale, the spherical l2norm's factor).  Per stage s:
+ *   u = clamp[s] > 0 ? tanh(r / clamp[s]) * clamp[s] : r;  v = spherical ? u / max(|u|, 1e-12) * scale[s] : u;
+ *   q = v > 0 ? qmag[s] : -qmag[s];  o = ste ? v + (q - v) : q;  r -= o;  out += o  (r starts at x, out at 0, stage order).
+ *   Writes out[g * out_gs + m * out_rs + i], idx[(g * N + m) * S + s] (MSB first), v_all (may be NULL) [G][S][N][d] the stage
+ *   inputs v, and commit_sum (device doubles, may be NULL) [G][S] = sum over rows with mask[m] != 0 (mask NULL: all) of
+ *   (v - q)^2, each in the fixed order of vq_lfq_quantize_f32 (workspace: vq_rlfq_workspace_bytes(G, N, S) bytes).
+ *   Without clamp and l2norm, out, idx and commit_sum are bitwise those of S vq_lfq_quantize_f32 calls chained in torch.
+ * vq_rlfq_backward_f32 -- grad_x of the same chain (training, ste):  grad_x = sum_s J_s^T (g_out + (v - q) * w_commit[g * S + s]
+ *   * mask + g_ent[((g * S + s) * N + m) * d + i]), J_s the clamp and l2norm Jacobians (the residual is detached, so
+ *   d r_s / d x = I).  g_out, w_commit (device [G][S], 2 * the commitment sums' upstream gradient) and g_ent may be NULL.
+ * Limits: 1 <= d <= 20, 1 <= S <= VQ_RLFQ_MAX_STAGES, 1 <= G <= 65535.
+ */
+#define VQ_RLFQ_MAX_STAGES 32
+int64_t vq_rlfq_workspace_bytes(int64_t G, int64_t N, int S);
+int vq_rlfq_quantize_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, int S, const float *stage_consts,
+                         int spherical, int ste, const uint8_t *mask, float *out, int64_t out_gs, int64_t out_rs, int64_t *idx,
+                         float *v_all, double *commit_sum, void *workspace, int64_t workspace_bytes, void *stream);
+int vq_rlfq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, int S, const float *stage_consts,
+                         int spherical, const uint8_t *mask, const float *g_out, int64_t g_gs, int64_t g_rs,
+                         const float *w_commit, const float *g_ent, float *grad_x, int64_t gx_gs, int64_t gx_rs, void *stream);
+
 const char *vq_last_error(void);
 int vq_device_info(char *buf, size_t n); /* "gfx950 ... CUs" of the current device */
 

@@ -30,7 +30,8 @@
 //   vq_search_resident.inc small codebooks: the packed image stays in LDS, no barriers, rows streamed past it by LDS-DMA slabs
 //   vq_similarity.inc    the same sweep with the similarity / online-softmax epilogues, fused cross-entropy backward
 //   vq_finalize_ema.inc  scalar fallback search, finalize-from-keys, loss reduction, EMA codebook update
-//   vq_lfq.inc           lookup-free quantization: sign quantizer, factorised entropy loss forward / backward
+//   vq_lfq.inc           lookup-free quantization: sign quantizer, factorised entropy loss forward / backward (stage axis)
+//   vq_rlfq.inc          residual LFQ: every stage's quantize step in one pass (residual in registers), its backward
 //   this file            host-side dispatch and the C ABI (include/vq_mi355x.h)
 //
 // Reference lines replaced (relative to the reference root): vector_quantization/codebooks.py:386-397,
@@ -74,6 +75,7 @@ namespace {
 #if VQ_OWN(0)
 #include "vq_finalize_ema.inc"
 #include "vq_lfq.inc"
+#include "vq_rlfq.inc"
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1706,7 +1708,8 @@ int vq_lfq_quantize_f32(const float *v, int64_t v_rs, const float *xa, int64_t x
     if (blocks > 0)
         hipLaunchKernelGGL(lfq_quantize_kernel, dim3((unsigned)blocks), dim3(kLfqQuantThreads), 0, s, v, v_rs, xa, xa_rs, N, C, d,
                            qmag, mask, q, out, idx, part);
-    if (commit_sum) hipLaunchKernelGGL(lfq_sum_kernel<double>, dim3(1), dim3(kLfqSumThreads), 0, s, part, blocks, commit_sum);
+    if (commit_sum)
+        hipLaunchKernelGGL(lfq_sum_kernel<double>, dim3(1), dim3(kLfqSumThreads), 0, s, part, blocks, commit_sum, (int64_t)0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "vq_lfq_quantize launch");
     return 0;
@@ -1715,52 +1718,75 @@ int vq_lfq_quantize_f32(const float *v, int64_t v_rs, const float *xa, int64_t x
 int vq_lfq_entropy_fwd_f32(const float *v, int64_t v_rs, const int64_t *rows, int64_t R, int C, int d, float code_scale,
                            float inv_temperature, float *avg_prob, double *per_sample_sum, void *workspace,
                            int64_t workspace_bytes, void *stream) {
-    int rc = lfq_check_shape(R, C, d);
-    if (rc) return rc;
-    if (R < 1) return fail(VQ_E_BADARG, "vq_lfq_entropy_fwd: no rows selected");
-    if (!v || !avg_prob || !per_sample_sum || !workspace) return fail(VQ_E_BADARG, "vq_lfq_entropy_fwd: null pointer");
-    if (v_rs < (int64_t)C * d) return fail(VQ_E_BADARG, "vq_lfq_entropy_fwd: row stride < C * d");
-    const LfqWs ws = lfq_ws_layout(R, R, C, d);
-    if (workspace_bytes < ws.total) return fail(VQ_E_BADARG, "vq_lfq_entropy_fwd: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    char *base = (char *)workspace;
-    float *ent = (float *)(base + ws.ent), *tabA = (float *)(base + ws.tabA), *tabB = (float *)(base + ws.tabB);
-    double *part = (double *)(base + ws.part);
-    const float coef = 4.0f * inv_temperature * code_scale;
-    const int waves = lfq_task_waves(d);
-    const int64_t tasks = R * C;
-    hipLaunchKernelGGL(lfq_entropy_fwd_kernel, dim3((unsigned)((tasks + waves - 1) / waves)), dim3(waves * 64),
-                       lfq_block_lds_bytes(d), s, v, v_rs, rows, R, C, d, coef, ent, tabA, tabB);
-    hipLaunchKernelGGL(lfq_sum_kernel<float>, dim3(1), dim3(kLfqSumThreads), 0, s, ent, tasks, per_sample_sum);
-    const int64_t rps = lfq_rows_per_split(R, C, d);
-    const int64_t splits = (R + rps - 1) / rps;
-    const int P = 1 << d;
-    hipLaunchKernelGGL(lfq_avg_prob_kernel, dim3((unsigned)((P + kLfqAvgCodes - 1) / kLfqAvgCodes), (unsigned)splits, (unsigned)C),
-                       dim3(kLfqAvgCodes), 0, s, tabA, tabB, R, C, d, rps, part);
-    const int64_t CP = (int64_t)C * P;
-    hipLaunchKernelGGL(lfq_avg_reduce_kernel, dim3((unsigned)((CP + 255) / 256)), dim3(256), 0, s, part, (int)splits, CP,
-                       1.0 / (double)R, avg_prob);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_lfq_entropy_fwd launch");
-    return 0;
+    return lfq_entropy_fwd_run(v, v_rs, 0, rows, 0, R, 1, C, d, &code_scale, nullptr, 1, inv_temperature, avg_prob, per_sample_sum,
+                               workspace, workspace_bytes, stream, "vq_lfq_entropy_fwd");
 }
 
 int vq_lfq_entropy_bwd_f32(const float *v, int64_t v_rs, const int64_t *rows, int64_t R, int C, int d, float code_scale,
                            float inv_temperature, const float *w_ps, const float *w_cb, float *grad_v, int64_t gv_rs,
                            void *stream) {
-    int rc = lfq_check_shape(R, C, d);
+    return lfq_entropy_bwd_run(v, v_rs, 0, rows, 0, R, 1, C, d, &code_scale, nullptr, 1, inv_temperature, w_ps, w_cb, grad_v, gv_rs, 0,
+                               stream, "vq_lfq_entropy_bwd");
+}
+
+int64_t vq_lfq_staged_workspace_bytes(int64_t R, int T, int d) {
+    if (T < 1 || lfq_check_shape(R, 1, d)) return 0;
+    return lfq_ws_layout(R, R, 1, d, T).total;
+}
+
+int vq_lfq_entropy_staged_fwd_f32(const float *v, int64_t v_rs, int64_t v_ss, const int64_t *rows, int64_t rows_ss, int64_t R,
+                                  int T, int d, const float *code_scale, int period, float inv_temperature, float *avg_prob,
+                                  double *per_sample_sum, void *workspace, int64_t workspace_bytes, void *stream) {
+    return lfq_entropy_fwd_run(v, v_rs, v_ss, rows, rows_ss, R, T, 1, d, nullptr, code_scale, period, inv_temperature, avg_prob,
+                               per_sample_sum, workspace, workspace_bytes, stream, "vq_lfq_entropy_staged_fwd");
+}
+
+int vq_lfq_entropy_staged_bwd_f32(const float *v, int64_t v_rs, int64_t v_ss, const int64_t *rows, int64_t rows_ss, int64_t R,
+                                  int T, int d, const float *code_scale, int period, float inv_temperature, const float *w_ps,
+                                  const float *w_cb, float *grad_v, int64_t gv_rs, int64_t gv_ss, void *stream) {
+    return lfq_entropy_bwd_run(v, v_rs, v_ss, rows, rows_ss, R, T, 1, d, nullptr, code_scale, period, inv_temperature, w_ps, w_cb, grad_v,
+                               gv_rs, gv_ss, stream, "vq_lfq_entropy_staged_bwd");
+}
+
+int64_t vq_rlfq_workspace_bytes(int64_t G, int64_t N, int S) {
+    if (G < 1 || N < 0 || S < 1 || S > VQ_RLFQ_MAX_STAGES) return 0;
+    return rlfq_ws_bytes(G, N, S);
+}
+
+int vq_rlfq_quantize_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, int S, const float *stage_consts,
+                         int spherical, int ste, const uint8_t *mask, float *out, int64_t out_gs, int64_t out_rs, int64_t *idx,
+                         float *v_all, double *commit_sum, void *workspace, int64_t workspace_bytes, void *stream) {
+    int rc = rlfq_check(G, N, d, S, stage_consts, "vq_rlfq_quantize");
     if (rc) return rc;
-    if (R == 0) return 0;
-    if (!v || !w_ps || !w_cb || !grad_v) return fail(VQ_E_BADARG, "vq_lfq_entropy_bwd: null pointer");
-    if (v_rs < (int64_t)C * d || gv_rs < (int64_t)C * d) return fail(VQ_E_BADARG, "vq_lfq_entropy_bwd: row stride < C * d");
+    if (!x || !out || !idx) return fail(VQ_E_BADARG, "vq_rlfq_quantize: null pointer");
+    if (commit_sum && (!workspace || workspace_bytes < rlfq_ws_bytes(G, N, S)))
+        return fail(VQ_E_BADARG, "vq_rlfq_quantize: workspace too small");
+    if (N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const float coef = 4.0f * inv_temperature * code_scale;
-    const int waves = lfq_task_waves(d);
-    const int64_t tasks = R * C;
-    hipLaunchKernelGGL(lfq_entropy_bwd_kernel, dim3((unsigned)((tasks + waves - 1) / waves)), dim3(waves * 64),
-                       lfq_block_lds_bytes(d), s, v, v_rs, rows, R, C, d, coef, w_ps, w_cb, grad_v, gv_rs);
+    const int64_t blocks = rlfq_blocks(N);
+    double *part = commit_sum ? (double *)workspace : nullptr;
+    rlfq_launch_quantize(d, dim3((unsigned)blocks, (unsigned)G), s, x, x_gs, x_rs, N, S, stage_consts, spherical != 0, ste != 0, mask,
+                         out, out_gs, out_rs, idx, v_all, part);
+    if (commit_sum)
+        hipLaunchKernelGGL(lfq_sum_kernel<double>, dim3((unsigned)(G * S)), dim3(kLfqSumThreads), 0, s, part, blocks, commit_sum,
+                           blocks);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_lfq_entropy_bwd launch");
+    if (e != hipSuccess) return hip_fail(e, "vq_rlfq_quantize launch");
+    return 0;
+}
+
+int vq_rlfq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, int S, const float *stage_consts,
+                         int spherical, const uint8_t *mask, const float *g_out, int64_t g_gs, int64_t g_rs,
+                         const float *w_commit, const float *g_ent, float *grad_x, int64_t gx_gs, int64_t gx_rs, void *stream) {
+    int rc = rlfq_check(G, N, d, S, stage_consts, "vq_rlfq_backward");
+    if (rc) return rc;
+    if (!x || !grad_x) return fail(VQ_E_BADARG, "vq_rlfq_backward: null pointer");
+    if (N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    rlfq_launch_backward(d, dim3((unsigned)rlfq_blocks(N), (unsigned)G), s, x, x_gs, x_rs, N, S, stage_consts, spherical != 0, mask,
+                         g_out, g_gs, g_rs, w_commit, g_ent, grad_x, gx_gs, gx_rs);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "vq_rlfq_backward launch");
     return 0;
 }
 

@@ -16,12 +16,30 @@
 //   lfq_entropy_bwd_kernel  one wave per (selected row, codebook): tables rebuilt in LDS, one sweep gives
 //                           S0 = sum_k g_k p_k and S_i = sum_k g_k p_k b_{k,i};  dL/dv_i = 4 tau a (S_i - pi_i(1) S0)
 // No float atomics anywhere: every sum has one fixed order, so results are bitwise run-to-run reproducible.
+//
+// Stage axis (the residual LFQ's stage-batched calls, vq_lfq_entropy_staged_*): every entropy kernel and lfq_sum_kernel take
+// a stage index from one grid axis and offset their inputs and outputs by per-stage strides; the code scale comes from
+// LfqCoef.  A single-stage call is the T = 1 case of the same kernels, so stage t of a staged call runs exactly the
+// arithmetic of a single-stage call on that stage's inputs (same row split, same summation order: bitwise equal).
 
 constexpr int kLfqMaxDim = 20;
 constexpr int kLfqSumThreads = 1024;
 constexpr int kLfqQuantThreads = 256;
 constexpr int kLfqAvgCodes = 256;  // codes per lfq_avg_prob_kernel block
 constexpr float kLfqEps = 1e-5f;   // the reference's log clamp (utils/general.py:25-26)
+// The stage coefficient 4 tau a of an entropy kernel: coef0 for a single-stage call; with a device array code_scale
+// (a staged call), four_tau * code_scale[t % period].  (Not a by-value array indexed by the stage: such an argument is
+// copied into registers, which doubled lfq_entropy_fwd_kernel's VGPRs.  A device array indexed by the block-uniform t is
+// a scalar load.)  four_tau * code_scale is the host's 4.0f * tau * code_scale, operation for operation.
+struct LfqCoef {
+    float coef0, four_tau;
+    const float *code_scale;
+    int period;
+};
+
+__device__ __forceinline__ float lfq_coef(const LfqCoef &k, int t) {
+    return k.code_scale ? k.four_tau * k.code_scale[t % k.period] : k.coef0;
+}
 
 __device__ __forceinline__ float lfq_sigmoid(float z) {
     // both branches are exact-ish: no 1 - sigmoid cancellation (pi_i(0) is sigmoid(-z) evaluated directly)
@@ -84,9 +102,13 @@ __global__ void __launch_bounds__(kLfqQuantThreads) lfq_quantize_kernel(
 }
 
 // one block: out[0] = sum of n values in a fixed order (thread-strided fp64 sums, then a tree)
+// (block b sums in[b * in_stride ...] into out[b]: one block per stage of a staged call)
 template <typename T>
-__global__ void __launch_bounds__(kLfqSumThreads) lfq_sum_kernel(const T *__restrict__ in, int64_t n, double *__restrict__ out) {
+__global__ void __launch_bounds__(kLfqSumThreads) lfq_sum_kernel(const T *__restrict__ in, int64_t n, double *__restrict__ out,
+                                                                 int64_t in_stride) {
     __shared__ double red[kLfqSumThreads];
+    in += (int64_t)blockIdx.x * in_stride;
+    out += blockIdx.x;
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += kLfqSumThreads) s += (double)in[i];
     red[threadIdx.x] = s;
@@ -163,12 +185,20 @@ __device__ __forceinline__ float lfq_build_tables(float *lds, const LfqShape &S,
 // ------------------------------------------------------------------------------------------------
 // entropy forward: per-sample entropy of every task + the A / B tables for the codebook term
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) lfq_entropy_fwd_kernel(const float *__restrict__ v, int64_t v_rs,
-                                                              const int64_t *__restrict__ rows, int64_t R, int C, int d,
-                                                              float coef, float *__restrict__ ent, float *__restrict__ tabA,
-                                                              float *__restrict__ tabB) {
+// stage t = blockIdx.y: v + t * v_ss, rows + t * rows_ss; ent / tabA / tabB are [T][R * C][...]
+__global__ void __launch_bounds__(256) lfq_entropy_fwd_kernel(const float *__restrict__ v, int64_t v_rs, int64_t v_ss,
+                                                              const int64_t *__restrict__ rows, int64_t rows_ss, int64_t R,
+                                                              int C, int d, LfqCoef coefs, float *__restrict__ ent,
+                                                              float *__restrict__ tabA, float *__restrict__ tabB) {
     extern __shared__ float lfq_lds[];
     const LfqShape S = lfq_shape(d);
+    const int t = blockIdx.y;
+    const float coef = lfq_coef(coefs, t);
+    v += (int64_t)t * v_ss;
+    if (rows) rows += (int64_t)t * rows_ss;
+    ent += (int64_t)t * R * C;
+    tabA += (int64_t)t * R * C * S.NA;
+    tabB += (int64_t)t * R * C * S.NB;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t task = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     const bool valid = task < R * C;
@@ -196,15 +226,20 @@ __global__ void __launch_bounds__(256) lfq_entropy_fwd_kernel(const float *__res
 }
 
 // avg_prob partials: part[(split * C + c) * P + k] = sum over the split's rows of A_u B_w  (fp64, rows in order)
+// (stage t = blockIdx.z / C: its tables at tabA / tabB + t * R * C * NA / NB, its partials at part + t * splits * C * P)
 __global__ void __launch_bounds__(kLfqAvgCodes) lfq_avg_prob_kernel(const float *__restrict__ tabA, const float *__restrict__ tabB,
                                                                     int64_t R, int C, int d, int64_t rows_per_split,
-                                                                    double *__restrict__ part) {
+                                                                    int64_t splits, double *__restrict__ part) {
     const LfqShape S = lfq_shape(d);
     const int P = 1 << d;
     const int k = blockIdx.x * kLfqAvgCodes + threadIdx.x;
-    const int c = blockIdx.z;
+    const int t = blockIdx.z / C;
+    const int c = blockIdx.z - t * C;
     const int split = blockIdx.y;
     if (k >= P) return;
+    tabA += (int64_t)t * R * C * S.NA;
+    tabB += (int64_t)t * R * C * S.NB;
+    part += (int64_t)t * splits * C * P;
     const int u = k >> S.l, w = k & (S.NB - 1);
     const int64_t r0 = (int64_t)split * rows_per_split;
     const int64_t r1 = r0 + rows_per_split < R ? r0 + rows_per_split : R;
@@ -220,6 +255,8 @@ __global__ void __launch_bounds__(256) lfq_avg_reduce_kernel(const double *__res
                                                              double inv_rows, float *__restrict__ avg) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= CP) return;
+    part += (int64_t)blockIdx.y * splits * CP;  // stage blockIdx.y
+    avg += (int64_t)blockIdx.y * CP;
     double s = 0.0;
     for (int z = 0; z < splits; ++z) s += part[(int64_t)z * CP + i];
     avg[i] = (float)(s * inv_rows);
@@ -232,13 +269,21 @@ __global__ void __launch_bounds__(256) lfq_avg_reduce_kernel(const double *__res
 // Pair k = s * 64 + lane: the low 6 bits of k are the lane's own, so their S_i are bit * S0 of the lane; the bits above
 // are the same for the whole wave (one add per set bit per pair).
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) lfq_entropy_bwd_kernel(const float *__restrict__ v, int64_t v_rs,
-                                                              const int64_t *__restrict__ rows, int64_t R, int C, int d,
-                                                              float coef, const float *__restrict__ w_ps,
+// stage t = blockIdx.y: v + t * v_ss, rows + t * rows_ss, w_ps + t, w_cb + t * C * 2^d, gv + t * gv_ss
+__global__ void __launch_bounds__(256) lfq_entropy_bwd_kernel(const float *__restrict__ v, int64_t v_rs, int64_t v_ss,
+                                                              const int64_t *__restrict__ rows, int64_t rows_ss, int64_t R,
+                                                              int C, int d, LfqCoef coefs, const float *__restrict__ w_ps,
                                                               const float *__restrict__ w_cb, float *__restrict__ gv,
-                                                              int64_t gv_rs) {
+                                                              int64_t gv_rs, int64_t gv_ss) {
     extern __shared__ float lfq_lds[];
     const LfqShape S = lfq_shape(d);
+    const int t = blockIdx.y;
+    const float coef = lfq_coef(coefs, t);
+    v += (int64_t)t * v_ss;
+    if (rows) rows += (int64_t)t * rows_ss;
+    w_ps += t;
+    w_cb += (int64_t)t * C * ((int64_t)1 << d);
+    gv += (int64_t)t * gv_ss;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t task = (int64_t)blockIdx.x * (blockDim.x >> 6) + wave;
     const bool valid = task < R * C;
@@ -316,7 +361,8 @@ struct LfqWs {
     int64_t commit, ent, tabA, tabB, part, total;  // byte offsets
 };
 
-LfqWs lfq_ws_layout(int64_t N, int64_t R, int C, int d) {
+// T stages of R selected rows each (T = 1: a single-stage call)
+LfqWs lfq_ws_layout(int64_t N, int64_t R, int C, int d, int64_t T = 1) {
     const LfqShape S = lfq_shape(d);
     const int64_t rps = lfq_rows_per_split(R > 0 ? R : 1, C, d);
     const int64_t splits = ((R > 0 ? R : 1) + rps - 1) / rps;
@@ -325,13 +371,13 @@ LfqWs lfq_ws_layout(int64_t N, int64_t R, int C, int d) {
     w.commit = off;
     off += lfq_align(lfq_quant_blocks(N, C) * (int64_t)sizeof(double));
     w.ent = off;
-    off += lfq_align(R * C * (int64_t)sizeof(float));
+    off += lfq_align(T * R * C * (int64_t)sizeof(float));
     w.tabA = off;
-    off += lfq_align(R * C * S.NA * (int64_t)sizeof(float));
+    off += lfq_align(T * R * C * S.NA * (int64_t)sizeof(float));
     w.tabB = off;
-    off += lfq_align(R * C * S.NB * (int64_t)sizeof(float));
+    off += lfq_align(T * R * C * S.NB * (int64_t)sizeof(float));
     w.part = off;
-    off += lfq_align(splits * C * ((int64_t)1 << d) * (int64_t)sizeof(double));
+    off += lfq_align(T * splits * C * ((int64_t)1 << d) * (int64_t)sizeof(double));
     w.total = off;
     return w;
 }
@@ -340,5 +386,78 @@ int lfq_check_shape(int64_t N, int C, int d) {
     if (N < 0 || C < 1) return fail(VQ_E_BADARG, "vq_lfq: N must be >= 0 and C >= 1");
     if (d < 1 || d > kLfqMaxDim) return fail(VQ_E_UNSUPPORTED, "vq_lfq: codebook_dim must be in [1, 20]");
     if (N * C > ((int64_t)1 << 40)) return fail(VQ_E_BADARG, "vq_lfq: too many rows");
+    return 0;
+}
+
+// code_scale_dev (device, `period` values) for a staged call, else the host value *code_scale
+LfqCoef lfq_coef_args(const float *code_scale, const float *code_scale_dev, int period, float inv_temperature) {
+    LfqCoef k;
+    k.four_tau = 4.0f * inv_temperature;
+    k.coef0 = code_scale_dev ? 0.0f : 4.0f * inv_temperature * code_scale[0];
+    k.code_scale = code_scale_dev;
+    k.period = period;
+    return k;
+}
+
+int lfq_fail(int code, const char *who, const char *msg) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", who, msg);
+    return code;
+}
+
+// The entropy forward of T stages (T = 1: vq_lfq_entropy_fwd_f32).  Stage t uses code_scale_dev[t % period] (a device
+// array) or, when code_scale_dev is NULL, the host value code_scale[0].
+int lfq_entropy_fwd_run(const float *v, int64_t v_rs, int64_t v_ss, const int64_t *rows, int64_t rows_ss, int64_t R, int T, int C,
+                        int d, const float *code_scale, const float *code_scale_dev, int period, float inv_temperature, float *avg_prob,
+                        double *per_sample_sum, void *workspace, int64_t workspace_bytes, void *stream, const char *who) {
+    int rc = lfq_check_shape(R, C, d);
+    if (rc) return rc;
+    if (R < 1) return lfq_fail(VQ_E_BADARG, who, "no rows selected");
+    if (T < 1 || T > 65535 || period < 1 || (!code_scale_dev && period != 1)) return lfq_fail(VQ_E_BADARG, who, "bad stage count");
+    if (!v || !avg_prob || !per_sample_sum || !workspace || (!code_scale && !code_scale_dev)) return lfq_fail(VQ_E_BADARG, who, "null pointer");
+    if (v_rs < (int64_t)C * d) return lfq_fail(VQ_E_BADARG, who, "row stride < C * d");
+    const LfqWs ws = lfq_ws_layout(R, R, C, d, T);
+    if (workspace_bytes < ws.total) return lfq_fail(VQ_E_BADARG, who, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    char *base = (char *)workspace;
+    float *ent = (float *)(base + ws.ent), *tabA = (float *)(base + ws.tabA), *tabB = (float *)(base + ws.tabB);
+    double *part = (double *)(base + ws.part);
+    const LfqCoef coefs = lfq_coef_args(code_scale, code_scale_dev, period, inv_temperature);
+    const int waves = lfq_task_waves(d);
+    const int64_t tasks = R * C;
+    hipLaunchKernelGGL(lfq_entropy_fwd_kernel, dim3((unsigned)((tasks + waves - 1) / waves), (unsigned)T), dim3(waves * 64),
+                       lfq_block_lds_bytes(d), s, v, v_rs, v_ss, rows, rows_ss, R, C, d, coefs, ent, tabA, tabB);
+    hipLaunchKernelGGL(lfq_sum_kernel<float>, dim3((unsigned)T), dim3(kLfqSumThreads), 0, s, ent, tasks, per_sample_sum, tasks);
+    const int64_t rps = lfq_rows_per_split(R, C, d);
+    const int64_t splits = (R + rps - 1) / rps;
+    const int P = 1 << d;
+    hipLaunchKernelGGL(lfq_avg_prob_kernel,
+                       dim3((unsigned)((P + kLfqAvgCodes - 1) / kLfqAvgCodes), (unsigned)splits, (unsigned)(C * T)),
+                       dim3(kLfqAvgCodes), 0, s, tabA, tabB, R, C, d, rps, splits, part);
+    const int64_t CP = (int64_t)C * P;
+    hipLaunchKernelGGL(lfq_avg_reduce_kernel, dim3((unsigned)((CP + 255) / 256), (unsigned)T), dim3(256), 0, s, part, (int)splits,
+                       CP, 1.0 / (double)R, avg_prob);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, who);
+    return 0;
+}
+
+// The entropy backward of T stages (T = 1: vq_lfq_entropy_bwd_f32).
+int lfq_entropy_bwd_run(const float *v, int64_t v_rs, int64_t v_ss, const int64_t *rows, int64_t rows_ss, int64_t R, int T, int C,
+                        int d, const float *code_scale, const float *code_scale_dev, int period, float inv_temperature, const float *w_ps, const float *w_cb,
+                        float *grad_v, int64_t gv_rs, int64_t gv_ss, void *stream, const char *who) {
+    int rc = lfq_check_shape(R, C, d);
+    if (rc) return rc;
+    if (R == 0) return 0;
+    if (T < 1 || T > 65535 || period < 1 || (!code_scale_dev && period != 1)) return lfq_fail(VQ_E_BADARG, who, "bad stage count");
+    if (!v || !w_ps || !w_cb || !grad_v || (!code_scale && !code_scale_dev)) return lfq_fail(VQ_E_BADARG, who, "null pointer");
+    if (v_rs < (int64_t)C * d || gv_rs < (int64_t)C * d) return lfq_fail(VQ_E_BADARG, who, "row stride < C * d");
+    hipStream_t s = (hipStream_t)stream;
+    const LfqCoef coefs = lfq_coef_args(code_scale, code_scale_dev, period, inv_temperature);
+    const int waves = lfq_task_waves(d);
+    const int64_t tasks = R * C;
+    hipLaunchKernelGGL(lfq_entropy_bwd_kernel, dim3((unsigned)((tasks + waves - 1) / waves), (unsigned)T), dim3(waves * 64),
+                       lfq_block_lds_bytes(d), s, v, v_rs, v_ss, rows, rows_ss, R, C, d, coefs, w_ps, w_cb, grad_v, gv_rs, gv_ss);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, who);
     return 0;
 }

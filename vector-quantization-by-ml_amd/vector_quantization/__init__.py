@@ -8,8 +8,9 @@ Import surface kept from the reference (``vector_quantization/__init__.py:11-12,
 The search itself (distance -> first argmax -> gather, straight-through, squared error, residual loop) is
 hand-written HIP for gfx950 behind the C ABI in ``include/vq_mi355x.h``; there is no PyTorch/CPU fallback.
 ``LFQ`` (lookup-free quantization) runs its sign quantizer and its entropy aux loss -- a sweep over an implicit codebook
-of 2^d codes -- in HIP as well.  The reference's other families (FSQ, latent quantization, the residual LFQ / FSQ
-variants) never touch a codebook search and are not part of this build.
+of 2^d codes -- in HIP as well, and so do ``ResidualLFQ`` / ``GroupedResidualLFQ`` (every stage's quantize step in one
+fused pass, every stage's entropy terms in one stage-batched call).  The reference's other families (FSQ, latent
+quantization, residual FSQ) never touch a codebook search and are not part of this build.
 """
 from . import ops  # noqa: F401  (registers torch.ops.vq_mi355x.*)
 from .codebook import Codebook
@@ -19,6 +20,7 @@ from .params import AffineParameters, CodebookParams, GumbelParams, KmeansParame
 from .projection import RandomProjectionQuantizer
 from .quantizer import LossBreakdown, VectorQuantize
 from .residual import GroupedResidualVQ, ResidualVQ
+from .residual_lfq import GroupedResidualLFQ, ResidualLFQ
 from .sharded import ShardedCodebookSearch
 
 __all__ = [
@@ -26,12 +28,14 @@ __all__ = [
     "Codebook",
     "CodebookParams",
     "GraphedForward",
+    "GroupedResidualLFQ",
     "GroupedResidualVQ",
     "GumbelParams",
     "KmeansParameters",
     "LFQ",
     "LossBreakdown",
     "RandomProjectionQuantizer",
+    "ResidualLFQ",
     "ResidualVQ",
     "ShardedCodebookSearch",
     "VectorQuantize",

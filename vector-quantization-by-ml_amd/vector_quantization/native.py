@@ -154,6 +154,22 @@ def load():
         lib.vq_lfq_entropy_bwd_f32.argtypes = [_vp, _i64, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                                _vp, _vp, _vp, _i64, _vp]
         lib.vq_lfq_entropy_bwd_f32.restype = ctypes.c_int
+        lib.vq_lfq_staged_workspace_bytes.argtypes = [_i64, ctypes.c_int, ctypes.c_int]
+        lib.vq_lfq_staged_workspace_bytes.restype = _i64
+        lib.vq_lfq_entropy_staged_fwd_f32.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp,
+                                                      ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _i64, _vp]
+        lib.vq_lfq_entropy_staged_fwd_f32.restype = ctypes.c_int
+        lib.vq_lfq_entropy_staged_bwd_f32.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp,
+                                                      ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _vp]
+        lib.vq_lfq_entropy_staged_bwd_f32.restype = ctypes.c_int
+        lib.vq_rlfq_workspace_bytes.argtypes = [_i64, _i64, ctypes.c_int]
+        lib.vq_rlfq_workspace_bytes.restype = _i64
+        lib.vq_rlfq_quantize_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                             ctypes.c_int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]
+        lib.vq_rlfq_quantize_f32.restype = ctypes.c_int
+        lib.vq_rlfq_backward_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,
+                                             _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp]
+        lib.vq_rlfq_backward_f32.restype = ctypes.c_int
         lib.vq_device_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         lib.vq_device_info.restype = ctypes.c_int
         _lib = lib
@@ -168,6 +184,8 @@ EXPORTED_SYMBOLS = (
     "vq_quantize_backward_f32", "vq_ema_accumulate_residual_f32", "vq_max_fused_stages", "vq_ema_accumulate_det_f32",
     "vq_ema_det_workspace_bytes", "vq_key_planes", "vq_search_key_planes_f32", "vq_finalize_key_planes_f32",
     "vq_lfq_workspace_bytes", "vq_lfq_quantize_f32", "vq_lfq_entropy_fwd_f32", "vq_lfq_entropy_bwd_f32",
+    "vq_lfq_staged_workspace_bytes", "vq_lfq_entropy_staged_fwd_f32", "vq_lfq_entropy_staged_bwd_f32",
+    "vq_rlfq_workspace_bytes", "vq_rlfq_quantize_f32", "vq_rlfq_backward_f32",
 )
 
 
@@ -755,4 +773,155 @@ def lfq_entropy_backward(v: torch.Tensor, rows: torch.Tensor | None, code_scale:
         _check(lib.vq_lfq_entropy_bwd_f32(v.data_ptr(), _lfq_rows(v), rows.data_ptr() if rows is not None else None, R, C, d,
                                           float(code_scale), float(inv_temperature), w_ps.data_ptr(), w_cb.data_ptr(),
                                           gv.data_ptr(), C * d, _stream_ptr(dev)), "vq_lfq_entropy_bwd_f32")
+    return gv
+
+
+# ------------------------------------------------------------------------------------------------
+# residual LFQ (vq_rlfq_* and vq_lfq_entropy_staged_* in include/vq_mi355x.h)
+# ------------------------------------------------------------------------------------------------
+RLFQ_MAX_STAGES = 32
+
+
+def rlfq_stages(qmag, clamp, scale, device) -> torch.Tensor:
+    """The per-stage constants as the kernels read them: device floats [3, S] (qmag, clamp (None / 0 = none), scale)."""
+    S = len(qmag)
+    assert 1 <= S <= RLFQ_MAX_STAGES and len(clamp) == S and len(scale) == S
+    rows = [[float(a) for a in qmag], [float(c or 0.0) for c in clamp], [float(a) for a in scale]]
+    return torch.tensor(rows, dtype=torch.float32).to(device, non_blocking=False)
+
+
+def _rlfq_rows(x: torch.Tensor):
+    """x [G, N, d] fp32 whose rows are contiguous -> (group stride, row stride) in elements."""
+    assert x.dim() == 3 and x.dtype == torch.float32, "x must be [G, N, d] fp32"
+    assert x.shape[2] <= 1 or x.stride(2) == 1, "each row's d values must be contiguous"
+    return int(x.stride(0)), int(x.stride(1))
+
+
+def rlfq_quantize(x: torch.Tensor, qmag, clamp, scale, *, spherical: bool = False, ste: bool = True,
+                  mask: torch.Tensor | None = None, want_v: bool = False, want_commit: bool = False,
+                  out: torch.Tensor | None = None):
+    """Every stage of a residual LFQ over x [G, N, d] (per-stage lists qmag / clamp (None = no clamp) / scale, S entries)
+    -> (out [G, N, d] (the caller's view when given), idx [G, N, S] int64, v_all [G, S, N, d] or None,
+    commit_sum [G, S] float64 or None).  mask: [N] bool (rows counted in the commitment sums)."""
+    _require_gpu(x, mask)
+    lib = load()
+    G, N, d = x.shape
+    dev = x.device
+    st = rlfq_stages(qmag, clamp, scale, dev)
+    S = st.shape[1]
+    x_gs, x_rs = _rlfq_rows(x)
+    if out is None:
+        out = torch.empty((G, N, d), dtype=torch.float32, device=dev)
+    o_gs, o_rs = _rlfq_rows(out)
+    idx = torch.empty((G, N, S), dtype=torch.int64, device=dev)
+    v_all = torch.empty((G, S, N, d), dtype=torch.float32, device=dev) if want_v else None
+    m8 = mask.reshape(N).to(torch.uint8).contiguous() if mask is not None else None
+    commit = ws = None
+    if want_commit:
+        commit = torch.empty((G, S), dtype=torch.float64, device=dev)
+        nbytes = int(lib.vq_rlfq_workspace_bytes(G, N, S))
+        if nbytes <= 0:
+            raise RuntimeError(f"vq_rlfq_workspace_bytes({G}, {N}, {S}) failed: {lib.vq_last_error().decode()}")
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.vq_rlfq_quantize_f32(x.data_ptr(), x_gs, x_rs, G, N, d, S, st.data_ptr(), int(spherical), int(ste),
+                                        m8.data_ptr() if m8 is not None else None, out.data_ptr(), o_gs, o_rs, idx.data_ptr(),
+                                        v_all.data_ptr() if v_all is not None else None,
+                                        commit.data_ptr() if commit is not None else None,
+                                        ws.data_ptr() if ws is not None else None, ws.numel() * 8 if ws is not None else 0,
+                                        _stream_ptr(dev)), "vq_rlfq_quantize_f32")
+    return out, idx, v_all, commit
+
+
+def rlfq_backward(x: torch.Tensor, qmag, clamp, scale, *, spherical: bool = False, mask: torch.Tensor | None = None,
+                  g_out: torch.Tensor | None = None, w_commit: torch.Tensor | None = None, g_ent: torch.Tensor | None = None,
+                  grad_x: torch.Tensor | None = None) -> torch.Tensor:
+    """dL/dx [G, N, d] of the training chain of rlfq_quantize (see the header): g_out [G, N, d] upstream gradient of out,
+    w_commit [G, S] = 2 * upstream gradient of the commitment sums, g_ent [G, S, N, d] gradient at the stage inputs."""
+    _require_gpu(x, mask, g_out, w_commit, g_ent)
+    lib = load()
+    G, N, d = x.shape
+    dev = x.device
+    st = rlfq_stages(qmag, clamp, scale, dev)
+    S = st.shape[1]
+    x_gs, x_rs = _rlfq_rows(x)
+    if g_out is not None:
+        if g_out.shape[2] > 1 and g_out.stride(2) != 1:
+            g_out = g_out.contiguous()
+        g_gs, g_rs = _rlfq_rows(g_out)
+    else:
+        g_gs = g_rs = 0
+    if w_commit is not None:
+        w_commit = w_commit.to(torch.float32).reshape(G * S).contiguous()
+    if g_ent is not None:
+        assert g_ent.shape == (G, S, N, d)
+        g_ent = g_ent.contiguous()
+    if grad_x is None:
+        grad_x = torch.empty((G, N, d), dtype=torch.float32, device=dev)
+    gx_gs, gx_rs = _rlfq_rows(grad_x)
+    m8 = mask.reshape(N).to(torch.uint8).contiguous() if mask is not None else None
+    with torch.cuda.device(dev):
+        _check(lib.vq_rlfq_backward_f32(x.data_ptr(), x_gs, x_rs, G, N, d, S, st.data_ptr(), int(spherical),
+                                        m8.data_ptr() if m8 is not None else None,
+                                        g_out.data_ptr() if g_out is not None else None, g_gs, g_rs,
+                                        w_commit.data_ptr() if w_commit is not None else None,
+                                        g_ent.data_ptr() if g_ent is not None else None, grad_x.data_ptr(), gx_gs, gx_rs,
+                                        _stream_ptr(dev)), "vq_rlfq_backward_f32")
+    return grad_x
+
+
+def _staged_args(v: torch.Tensor, rows: torch.Tensor | None, code_scale):
+    """v [T, N, d] (rows contiguous), rows None / [R] (every stage) / [T, R] -> (T, N, d, R, v_ss, v_rs, rows, rows_ss, scales)"""
+    assert v.dim() == 3 and v.dtype == torch.float32 and (v.shape[2] <= 1 or v.stride(2) == 1)
+    T, N, d = v.shape
+    rows_ss = 0
+    if rows is not None:
+        rows = rows.to(torch.int64).contiguous()
+        if rows.dim() == 2:
+            assert rows.shape[0] == T
+            rows_ss = int(rows.shape[1])
+        R = int(rows.shape[-1])
+    else:
+        R = N
+    scales = torch.tensor([float(a) for a in code_scale], dtype=torch.float32).to(v.device)
+    return T, N, d, R, int(v.stride(0)), int(v.stride(1)) if N > 1 else d, rows, rows_ss, scales
+
+
+def lfq_entropy_staged_forward(v: torch.Tensor, rows: torch.Tensor | None, code_scale, inv_temperature: float):
+    """lfq_entropy_forward of T stages at once: v [T, N, d], rows None / [R] / [T, R], code_scale a list whose entry
+    t % len applies to stage t -> (per_sample_sum float64 [T], avg_prob [T, 2^d])."""
+    _require_gpu(v, rows)
+    lib = load()
+    T, N, d, R, v_ss, v_rs, rows, rows_ss, scales = _staged_args(v, rows, code_scale)
+    dev = v.device
+    avg = torch.empty((T, 1 << d), dtype=torch.float32, device=dev)
+    ps = torch.empty((T,), dtype=torch.float64, device=dev)
+    nbytes = int(lib.vq_lfq_staged_workspace_bytes(R, T, d))
+    if nbytes <= 0:
+        raise RuntimeError(f"vq_lfq_staged_workspace_bytes({R}, {T}, {d}) failed: {lib.vq_last_error().decode()}")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.vq_lfq_entropy_staged_fwd_f32(v.data_ptr(), v_rs, v_ss, rows.data_ptr() if rows is not None else None,
+                                                 rows_ss, R, T, d, scales.data_ptr(), scales.numel(), float(inv_temperature), avg.data_ptr(),
+                                                 ps.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)),
+               "vq_lfq_entropy_staged_fwd_f32")
+    return ps, avg
+
+
+def lfq_entropy_staged_backward(v: torch.Tensor, rows: torch.Tensor | None, code_scale, inv_temperature: float,
+                                w_ps: torch.Tensor, w_cb: torch.Tensor) -> torch.Tensor:
+    """lfq_entropy_backward of T stages at once: w_ps [T], w_cb [T, 2^d] -> dL/dv [T, N, d] (zero on rows not selected)."""
+    _require_gpu(v, rows, w_ps, w_cb)
+    lib = load()
+    T, N, d, R, v_ss, v_rs, rows, rows_ss, scales = _staged_args(v, rows, code_scale)
+    dev = v.device
+    w_ps = w_ps.to(torch.float32).reshape(T).contiguous()
+    w_cb = w_cb.to(torch.float32).contiguous()
+    assert w_cb.numel() == T << d
+    gv = torch.zeros((T, N, d), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.vq_lfq_entropy_staged_bwd_f32(v.data_ptr(), v_rs, v_ss, rows.data_ptr() if rows is not None else None,
+                                                 rows_ss, R, T, d, scales.data_ptr(), scales.numel(), float(inv_temperature),
+                                                 w_ps.data_ptr(), w_cb.data_ptr(), gv.data_ptr(), d, N * d, _stream_ptr(dev)),
+               "vq_lfq_entropy_staged_bwd_f32")
     return gv

@@ -8,6 +8,8 @@ instead of breaking the graph at an opaque Python call:
     torch.ops.vq_mi355x.quantize_into(x, cb, packed, out, idx, metric, ste, want_sq_err, share, per_head) -> sq_err
         (writes the quantized rows and the indices into the caller's -- possibly strided -- ``out`` / ``idx`` views)
     torch.ops.vq_mi355x.lfq_quantize / lfq_entropy_fwd / lfq_entropy_bwd   (lookup-free quantization, native.lfq_*)
+    torch.ops.vq_mi355x.rlfq_quantize / rlfq_backward / lfq_entropy_staged_fwd / lfq_entropy_staged_bwd
+        (residual LFQ, native.rlfq_* and native.lfq_entropy_staged_*)
 
 Eager forwards keep calling ``native.quantize`` directly (a custom-op dispatch costs tens of microseconds of host time,
 which is most of a small launch); the modules switch to these ops only while being compiled
@@ -93,5 +95,68 @@ def lfq_entropy_bwd(v: torch.Tensor, rows: Optional[torch.Tensor], code_scale: f
 
 
 @lfq_entropy_bwd.register_fake
+def _(v, rows, code_scale, inv_temperature, w_ps, w_cb):
+    return v.new_empty(v.shape)
+
+
+# residual LFQ (native.rlfq_*, native.lfq_entropy_staged_*).  clamp entries of 0 mean no clamp; outputs that were not
+# requested come back as empty tensors (a custom op returns no None).
+@torch.library.custom_op(f"{_LIB_NS}::rlfq_quantize", mutates_args=())
+def rlfq_quantize(x: torch.Tensor, qmag: list[float], clamp: list[float], scale: list[float], spherical: bool, ste: bool,
+                  mask: Optional[torch.Tensor], want_v: bool,
+                  want_commit: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """x [G, N, d] -> (out [G, N, d], idx [G, N, S] int64, v_all [G, S, N, d] (or empty), commit sums [G, S] float64 (or empty))."""
+    out, idx, v_all, commit = native.rlfq_quantize(x, qmag, clamp, scale, spherical=spherical, ste=ste, mask=mask,
+                                                   want_v=want_v, want_commit=want_commit)
+    if v_all is None:
+        v_all = x.new_empty((0,))
+    if commit is None:
+        commit = x.new_empty((0,), dtype=torch.float64)
+    return out, idx, v_all, commit
+
+
+@rlfq_quantize.register_fake
+def _(x, qmag, clamp, scale, spherical, ste, mask, want_v, want_commit):
+    G, N, d = x.shape
+    S = len(qmag)
+    return (x.new_empty((G, N, d)), x.new_empty((G, N, S), dtype=torch.int64),
+            x.new_empty((G, S, N, d) if want_v else (0,)), x.new_empty((G, S) if want_commit else (0,), dtype=torch.float64))
+
+
+@torch.library.custom_op(f"{_LIB_NS}::rlfq_backward", mutates_args=())
+def rlfq_backward(x: torch.Tensor, qmag: list[float], clamp: list[float], scale: list[float], spherical: bool,
+                  mask: Optional[torch.Tensor], g_out: Optional[torch.Tensor], w_commit: Optional[torch.Tensor],
+                  g_ent: Optional[torch.Tensor]) -> torch.Tensor:
+    """dL/dx [G, N, d] of the residual LFQ chain (native.rlfq_backward)."""
+    return native.rlfq_backward(x, qmag, clamp, scale, spherical=spherical, mask=mask, g_out=g_out, w_commit=w_commit,
+                                g_ent=g_ent)
+
+
+@rlfq_backward.register_fake
+def _(x, qmag, clamp, scale, spherical, mask, g_out, w_commit, g_ent):
+    return x.new_empty(x.shape)
+
+
+@torch.library.custom_op(f"{_LIB_NS}::lfq_entropy_staged_fwd", mutates_args=())
+def lfq_entropy_staged_fwd(v: torch.Tensor, rows: Optional[torch.Tensor], code_scale: list[float],
+                           inv_temperature: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """v [T, N, d] -> (per-sample entropy sums float64 [T], avg_prob [T, 2^d])."""
+    return native.lfq_entropy_staged_forward(v, rows, code_scale, inv_temperature)
+
+
+@lfq_entropy_staged_fwd.register_fake
+def _(v, rows, code_scale, inv_temperature):
+    T = v.shape[0]
+    return v.new_empty((T,), dtype=torch.float64), v.new_empty((T, 1 << v.shape[2]))
+
+
+@torch.library.custom_op(f"{_LIB_NS}::lfq_entropy_staged_bwd", mutates_args=())
+def lfq_entropy_staged_bwd(v: torch.Tensor, rows: Optional[torch.Tensor], code_scale: list[float], inv_temperature: float,
+                           w_ps: torch.Tensor, w_cb: torch.Tensor) -> torch.Tensor:
+    """dL/dv [T, N, d] of the staged entropy terms (native.lfq_entropy_staged_backward)."""
+    return native.lfq_entropy_staged_backward(v, rows, code_scale, inv_temperature, w_ps, w_cb)
+
+
+@lfq_entropy_staged_bwd.register_fake
 def _(v, rows, code_scale, inv_temperature, w_ps, w_cb):
     return v.new_empty(v.shape)

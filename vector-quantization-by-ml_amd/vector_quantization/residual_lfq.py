@@ -1,0 +1,397 @@
+"""Residual lookup-free quantization: the reference's ``ResidualLFQ`` and ``GroupedResidualLFQ``
+(``vector_quantization/residual_lfq.py``), a stack of ``LFQ`` layers whose stage q quantizes what the stages before it left
+over, with codebook scale 2^-q.
+
+Fused path (the hot path).  After ``project_in``, every stage's quantize step is one HIP pass (``vq_rlfq_quantize_f32``:
+one thread per row, the row's d <= 20 values held in registers across the stages), every stage's entropy terms one
+stage-batched call (``vq_lfq_entropy_staged_{fwd,bwd}_f32``, each stage bitwise a single-stage LFQ call), and dL/dx one
+per-row pass (``vq_rlfq_backward_f32``) that sums the stages' terms.  ``GroupedResidualLFQ`` runs its G groups as the
+kernels' group axis: G groups x Q stages are still one launch each.  The loss arithmetic around the kernels is vectorised
+over stages (and groups), and ``maybe_distributed_mean`` is one collective over all stages' ``avg_prob``.
+
+Fallback path.  A stage-by-stage loop over the module's own ``LFQ`` layers, line for line the reference's ``forward``.  It
+serves configurations the fused kernels do not cover: a straight-through activation other than ``nn.Identity``, more than
+``MAX_FUSED_STAGES`` active stages, ``channel_first`` / several codebooks per layer, ``accept_image_fmap`` groups.
+
+Both paths run only on the GPU: CPU tensors raise ``native.NativeUnavailable`` (``get_codes_from_indices``,
+``get_output_from_indices`` and ``codebooks`` are pure torch and work anywhere).  DESIGN.md section 11 states the accuracy
+contract between the two paths and against the reference.
+"""
+from __future__ import annotations
+
+import random
+from math import ceil, log2
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from . import native
+from .lookup_free_quantization import _EPS, LFQ, _entropy, _maybe_distributed_mean
+
+MAX_FUSED_STAGES = native.RLFQ_MAX_STAGES
+_ENTROPY_WS_BUDGET = 2 << 30  # bytes of staged-entropy workspace per call; more stages than fit run in several calls
+_INV_TEMPERATURE = 100.0  # ResidualLFQ.forward passes none to its layers: LFQ's default
+
+
+def _round_up_multiple(num, mult):
+    return ceil(num / mult) * mult
+
+
+def _compiling() -> bool:
+    return torch.compiler.is_compiling()
+
+
+def _staged_entropy_fwd(v: torch.Tensor, rows, scales, tau):
+    """native.lfq_entropy_staged_forward over v [T, N, d], in as few calls as the workspace budget allows."""
+    T, N, d = v.shape
+    R = N if rows is None else int(rows.shape[-1])
+    per_stage = int(native.load().vq_lfq_staged_workspace_bytes(max(R, 1), 1, d))
+    chunk = max(1, _ENTROPY_WS_BUDGET // max(per_stage, 1))
+    if T <= chunk:
+        return native.lfq_entropy_staged_forward(v, rows, scales, tau)
+    ps, avg = [], []
+    S = len(scales)
+    for t0 in range(0, T, chunk):
+        t1 = min(T, t0 + chunk)
+        r = rows[t0:t1] if rows is not None and rows.dim() == 2 else rows
+        p, a = native.lfq_entropy_staged_forward(v[t0:t1], r, [scales[(t0 + j) % S] for j in range(S)], tau)
+        ps.append(p)
+        avg.append(a)
+    return torch.cat(ps), torch.cat(avg)
+
+
+def _staged_entropy_bwd(v: torch.Tensor, rows, scales, tau, w_ps, w_cb):
+    T, N, d = v.shape
+    R = N if rows is None else int(rows.shape[-1])
+    per_stage = int(native.load().vq_lfq_staged_workspace_bytes(max(R, 1), 1, d))
+    chunk = max(1, _ENTROPY_WS_BUDGET // max(per_stage, 1))
+    if T <= chunk:
+        return native.lfq_entropy_staged_backward(v, rows, scales, tau, w_ps, w_cb)
+    S = len(scales)
+    parts = []
+    for t0 in range(0, T, chunk):
+        t1 = min(T, t0 + chunk)
+        r = rows[t0:t1] if rows is not None and rows.dim() == 2 else rows
+        parts.append(native.lfq_entropy_staged_backward(v[t0:t1], r, [scales[(t0 + j) % S] for j in range(S)], tau,
+                                                        w_ps[t0:t1], w_cb[t0:t1]))
+    return torch.cat(parts)
+
+
+class _RlfqTrain(torch.autograd.Function):
+    """x [G, N, d] (the stage-0 residual of every group) -> out [G, N, d] (sum of the stages' straight-through values),
+    idx [G, N, S], commitment squared-error sums [G, S] (float64), per-sample entropies [G, S], codebook entropies [G, S]."""
+
+    @staticmethod
+    def forward(ctx, x, mask, rows, qmag, clamp, scale, spherical, want_commit):
+        G, N, d = x.shape
+        S = len(qmag)
+        out, idx, v_all, commit = native.rlfq_quantize(x.detach(), qmag, clamp, scale, spherical=spherical, ste=True,
+                                                       mask=mask, want_v=True, want_commit=want_commit)
+        if commit is None:
+            commit = torch.zeros((G, S), dtype=torch.float64, device=x.device)
+        v_flat = v_all.view(G * S, N, d)
+        R = N if rows is None else int(rows.shape[-1])
+        ps_sum, avg = _staged_entropy_fwd(v_flat, rows, qmag, _INV_TEMPERATURE)
+        avg, world = _maybe_distributed_mean(avg)  # one collective for every stage: elementwise the per-stage ones
+        per_sample = (ps_sum / R).to(torch.float32).view(G, S)
+        codebook = _entropy(avg).view(G, S)
+        ctx.save_for_backward(x, v_all, avg, mask if mask is not None else torch.empty(0),
+                              rows if rows is not None else torch.empty(0))
+        ctx.meta = (mask is not None, rows is not None, R, world, qmag, clamp, scale, spherical, want_commit)
+        ctx.mark_non_differentiable(idx)
+        return out, idx, commit, per_sample, codebook
+
+    @staticmethod
+    def backward(ctx, g_out, g_idx, g_commit, g_ps, g_cb):
+        x, v_all, avg, mask, rows = ctx.saved_tensors
+        has_mask, has_rows, R, world, qmag, clamp, scale, spherical, want_commit = ctx.meta
+        mask = mask if has_mask else None
+        rows = rows if has_rows else None
+        G, S, N, d = v_all.shape
+        dev = x.device
+        g_ps = torch.zeros((G, S), device=dev) if g_ps is None else g_ps
+        g_cb = torch.zeros((G, S), device=dev) if g_cb is None else g_cb
+        w_ps = g_ps.to(torch.float32).reshape(G * S) / R
+        # d/dx of -x log(max(x, eps)): -(log x + 1) above the clamp, -log eps below it (as LFQ's backward)
+        dh = -(avg.clamp(min=_EPS).log() + (avg >= _EPS).to(avg.dtype))
+        w_cb = dh * (g_cb.to(torch.float32).reshape(G * S, 1) / (R * world))
+        g_ent = _staged_entropy_bwd(v_all.view(G * S, N, d), rows, qmag, _INV_TEMPERATURE, w_ps, w_cb).view(G, S, N, d)
+        w_commit = None
+        if want_commit and g_commit is not None:
+            w_commit = 2.0 * g_commit.to(torch.float32)
+        gx = native.rlfq_backward(x.detach(), qmag, clamp, scale, spherical=spherical, mask=mask, g_out=g_out,
+                                  w_commit=w_commit, g_ent=g_ent)
+        return gx, None, None, None, None, None, None, None
+
+
+def _rows_contiguous(xg: torch.Tensor) -> torch.Tensor:
+    """xg [G, N, d] with each row's d values contiguous (the kernels' layout; any group and row strides): a copy only
+    when they are not, e.g. a batch-1 [b, d, t] feature map passed as .transpose(1, 2) (as LFQ's _rows_view does)."""
+    if xg.shape[2] > 1 and xg.stride(2) != 1:
+        xg = xg.contiguous()
+    return xg
+
+
+def _fused_ok(rvq: "ResidualLFQ", x: torch.Tensor, stages: int) -> bool:
+    l0 = rvq.layers[0]
+    return ((x.is_cuda or _compiling()) and 1 <= stages <= MAX_FUSED_STAGES
+            and all(type(layer.activation) is nn.Identity for layer in rvq.layers)
+            and not l0.channel_first and l0.num_codebooks == 1 and not l0.keep_num_codebooks_dim and not l0.has_projections)
+
+
+def _fused_forward(rvqs, xg: torch.Tensor, mask, stages: int):
+    """The fused path of G residual stacks with identical configurations: xg [G, N, d] (fp32, rows contiguous) ->
+    (out [G, N, d], idx [G, N, stages], losses [G, stages])."""
+    rvq = rvqs[0]
+    layers = rvq.layers[:stages]
+    l0 = layers[0]
+    G, N, d = xg.shape
+    qmag = [layer._code_mag for layer in layers]
+    clamp = [float(layer.soft_clamp_input_value or 0.0) for layer in layers]
+    scale = [float(layer.codebook_scale) for layer in layers]
+    if mask is not None:
+        mask = mask.reshape(N).to(xg.device)
+    if not rvq.training:
+        if _compiling():
+            out, idx, _, _ = torch.ops.vq_mi355x.rlfq_quantize(xg, qmag, clamp, scale, l0.spherical, False, None, False, False)
+        else:
+            out, idx, _, _ = native.rlfq_quantize(xg.detach(), qmag, clamp, scale, spherical=l0.spherical, ste=False)
+        return out, idx, torch.zeros((G, stages), dtype=torch.float32, device=xg.device)
+
+    # entropy rows.  Without frac_per_sample_entropy every stage uses the mask's rows (or all rows): one selection.  With
+    # it, each (group, stage) draws in the reference's order: group-major, then stage (LFQ._entropy_rows per layer).
+    if l0.frac_per_sample_entropy >= 1.0:
+        rows = l0._entropy_rows(N, mask, xg.device)
+    else:
+        rows = torch.stack([r.layers[s]._entropy_rows(N, mask, xg.device) for r in rvqs for s in range(stages)])
+    want_commit = l0.commitment_loss_weight > 0.0
+    out, idx, commit_sum, per_sample, codebook = _RlfqTrain.apply(xg, mask, rows, qmag, clamp, scale, l0.spherical,
+                                                                   want_commit)
+    entropy_aux = per_sample - l0.diversity_gamma * codebook
+    if l0.experimental_softplus_entropy_loss:
+        entropy_aux = F.softplus(entropy_aux + l0.entropy_loss_offset)
+    if want_commit:
+        kept = N if mask is None else mask.sum()
+        commit_loss = (commit_sum / (kept * d)).to(torch.float32)
+    else:
+        commit_loss = torch.zeros((G, stages), dtype=torch.float32, device=xg.device)
+    losses = entropy_aux * l0.entropy_loss_weight + commit_loss * l0.commitment_loss_weight
+    return out, idx, losses
+
+
+def _pad_stages(idx: torch.Tensor, losses: torch.Tensor, Q: int, loss_dtype):
+    """Dropped stages: indices -1 and a loss of 0 (residual_lfq.py:149-152)."""
+    S = idx.shape[-1]
+    losses = losses.to(loss_dtype)
+    if S == Q:
+        return idx, losses
+    idx = torch.cat([idx, idx.new_full((*idx.shape[:-1], Q - S), -1)], dim=-1)
+    losses = torch.cat([losses, losses.new_zeros((*losses.shape[:-1], Q - S))], dim=-1)
+    return idx, losses
+
+
+class ResidualLFQ(nn.Module):
+    """Follows Algorithm 1. in https://arxiv.org/pdf/2107.03312.pdf"""
+
+    def __init__(
+        self,
+        *,
+        dim,
+        num_quantizers,
+        codebook_size,
+        quantize_dropout=False,
+        quantize_dropout_cutoff_index=0,
+        quantize_dropout_multiple_of=1,
+        soft_clamp_input_value=None,
+        **kwargs,
+    ):
+        super().__init__()
+        codebook_dim = int(log2(codebook_size))
+
+        requires_projection = codebook_dim != dim
+        self.project_in = nn.Linear(dim, codebook_dim) if requires_projection else nn.Identity()
+        self.project_out = nn.Linear(codebook_dim, dim) if requires_projection else nn.Identity()
+        self.has_projections = requires_projection
+
+        self.num_quantizers = num_quantizers
+        self.codebook_dim = codebook_dim
+
+        self.layers = nn.ModuleList([])
+        for ind in range(num_quantizers):
+            codebook_scale = 2**-ind
+            lfq = LFQ(dim=codebook_dim, codebook_scale=codebook_scale, soft_clamp_input_value=soft_clamp_input_value, **kwargs)
+            self.layers.append(lfq)
+            if soft_clamp_input_value is not None:
+                soft_clamp_input_value *= 0.5
+
+        assert all([not lfq.has_projections for lfq in self.layers])
+
+        self.quantize_dropout = quantize_dropout and num_quantizers > 1
+        assert quantize_dropout_cutoff_index >= 0
+        self.quantize_dropout_cutoff_index = quantize_dropout_cutoff_index
+        self.quantize_dropout_multiple_of = quantize_dropout_multiple_of
+
+    @property
+    def codebooks(self):
+        return torch.stack([layer.codebook for layer in self.layers], dim=0)
+
+    def get_codes_from_indices(self, indices):
+        """indices [b, ..., q] (q <= num_quantizers; -1 = dropped) -> codes [num_quantizers, b, ..., codebook_dim], the
+        unnormalised codes (bits_to_codes) of each stage, zero where dropped.  Computed from the index bits."""
+        quantize_dim = indices.shape[-1]
+        lead = indices.shape[:-1]
+        indices = indices.reshape(lead[0] if len(lead) else 1, -1, quantize_dim)
+        if quantize_dim < self.num_quantizers:
+            assert self.quantize_dropout > 0.0, (
+                "quantize dropout must be greater than 0 if you wish to reconstruct from a signal with less fine quantizations"
+            )
+            indices = F.pad(indices, (0, self.num_quantizers - quantize_dim), value=-1)
+        dropped = indices == -1
+        indices = indices.masked_fill(dropped, 0)
+        codes = []
+        for q, layer in enumerate(self.layers):
+            bits = ((indices[..., q, None].int() & layer.mask) != 0).to(torch.float32)
+            codes.append(layer.bits_to_codes(bits))
+        all_codes = torch.stack(codes)  # [q, b, n, d]
+        all_codes = all_codes.masked_fill(dropped.permute(2, 0, 1)[..., None], 0.0)
+        return all_codes.reshape(self.num_quantizers, *lead, all_codes.shape[-1])
+
+    def get_output_from_indices(self, indices):
+        codes = self.get_codes_from_indices(indices)
+        return self.project_out(codes.sum(dim=0))
+
+    def _dropout_cut(self, seed):
+        """The last active stage under quantize dropout (None: every stage runs), consuming `random` as the reference."""
+        if not (self.training and self.quantize_dropout):
+            return None
+        rand = random.Random(seed) if seed is not None else random
+        cut = rand.randrange(self.quantize_dropout_cutoff_index, self.num_quantizers)
+        if self.quantize_dropout_multiple_of != 1:
+            cut = _round_up_multiple(cut + 1, self.quantize_dropout_multiple_of) - 1
+        return cut
+
+    def forward(self, x, mask=None, return_all_codes=False, rand_quantize_dropout_fixed_seed=None):
+        num_quant = self.num_quantizers
+        x = self.project_in(x)
+        cut = self._dropout_cut(rand_quantize_dropout_fixed_seed)
+        stages = num_quant if cut is None else min(cut + 1, num_quant)
+
+        if _fused_ok(self, x, stages):
+            xf = x.float()
+            assert xf.shape[-1] == self.codebook_dim
+            xg = _rows_contiguous(xf.reshape(1, -1, self.codebook_dim))
+            with torch.autocast(device_type="cuda", enabled=False):
+                out, idx, losses = _fused_forward([self], xg, mask, stages)
+            quantized_out = self.project_out(out.reshape(xf.shape))
+            all_indices, all_losses = _pad_stages(idx.reshape(*xf.shape[:-1], stages), losses[0], num_quant, x.dtype)
+        else:
+            quantized_out, all_indices, all_losses = self._forward_stagewise(x, mask, cut)
+
+        ret = (quantized_out, all_indices, all_losses)
+        if not return_all_codes:
+            return ret
+        return (*ret, self.get_codes_from_indices(all_indices))
+
+    def _forward_stagewise(self, x, mask, cut):
+        """The fallback: the reference's loop over the LFQ layers (residual_lfq.py:128-197)."""
+        quantized_out = 0.0
+        residual = x
+        all_losses = []
+        all_indices = []
+        if cut is not None:
+            null_indices = torch.full(x.shape[:2], -1.0, device=x.device, dtype=torch.long)
+            null_loss = torch.tensor(0.0, device=x.device, dtype=x.dtype)
+        with torch.autocast(device_type="cuda", enabled=False):
+            for quantizer_index, layer in enumerate(self.layers):
+                if cut is not None and quantizer_index > cut:
+                    all_indices.append(null_indices)
+                    all_losses.append(null_loss)
+                    continue
+                quantized, indices, loss = layer(residual, mask=mask)
+                residual = residual - quantized.detach()
+                quantized_out = quantized_out + quantized
+                all_indices.append(indices)
+                all_losses.append(loss)
+        quantized_out = self.project_out(quantized_out)
+        return quantized_out, torch.stack(all_indices, dim=-1), torch.stack(all_losses, dim=-1)
+
+
+class GroupedResidualLFQ(nn.Module):
+    def __init__(self, *, dim, groups=1, accept_image_fmap=False, **kwargs):
+        super().__init__()
+        self.dim = dim
+        self.groups = groups
+        assert (dim % groups) == 0
+        dim_per_group = dim // groups
+        self.accept_image_fmap = accept_image_fmap
+        self.rvqs = nn.ModuleList([])
+        for _ in range(groups):
+            self.rvqs.append(ResidualLFQ(dim=dim_per_group, **kwargs))
+
+    @property
+    def codebooks(self):
+        return torch.stack(tuple(rvq.codebooks for rvq in self.rvqs))
+
+    @property
+    def split_dim(self):
+        return 1 if self.accept_image_fmap else -1
+
+    def get_codes_from_indices(self, indices):
+        codes = tuple(rvq.get_codes_from_indices(chunk_indices) for rvq, chunk_indices in zip(self.rvqs, indices))
+        return torch.stack(codes)
+
+    def get_output_from_indices(self, indices):
+        outputs = tuple(rvq.get_output_from_indices(chunk_indices) for rvq, chunk_indices in zip(self.rvqs, indices))
+        return torch.cat(outputs, dim=self.split_dim)
+
+    def forward(self, x, mask=None, return_all_codes=False):
+        shape, split_dim = x.shape, self.split_dim
+        assert shape[split_dim] == self.dim
+        seed = random.randint(0, int(1e7))  # drawn in eval too, as the reference does
+        rvq0 = self.rvqs[0]
+        cut = rvq0._dropout_cut(seed)  # every group gets the same seed, so the same cut
+        Q = rvq0.num_quantizers
+        stages = Q if cut is None else min(cut + 1, Q)
+        G = self.groups
+
+        if split_dim == -1 and _fused_ok(rvq0, x, stages):
+            return self._forward_fused(x, mask, return_all_codes, stages)
+
+        chunks = x.chunk(G, dim=split_dim)
+        forward_kwargs = dict(mask=mask, return_all_codes=return_all_codes, rand_quantize_dropout_fixed_seed=seed)
+        out = tuple(rvq(chunk, **forward_kwargs) for rvq, chunk in zip(self.rvqs, chunks))
+        out = tuple(zip(*out))
+        quantized, all_indices, commit_losses, *maybe_all_codes = out
+        quantized = torch.cat(quantized, dim=split_dim)
+        all_indices = torch.stack(all_indices)
+        commit_losses = torch.stack(commit_losses)
+        return (quantized, all_indices, commit_losses, *maybe_all_codes)
+
+    def _forward_fused(self, x, mask, return_all_codes, stages):
+        G = self.groups
+        rvq0 = self.rvqs[0]
+        Q = rvq0.num_quantizers
+        lead = x.shape[:-1]
+        if rvq0.has_projections:
+            chunks = x.chunk(G, dim=-1)
+            xp = [rvq.project_in(chunk) for rvq, chunk in zip(self.rvqs, chunks)]
+            loss_dtype = xp[0].dtype
+            d = rvq0.codebook_dim
+            xg = torch.stack([t.float().reshape(-1, d) for t in xp])  # [G, N, d]
+        else:
+            loss_dtype = x.dtype
+            d = self.dim // G
+            # the chunk views in place (group stride d, row stride G * d) when each row's values are contiguous
+            xg = _rows_contiguous(x.float().reshape(-1, G, d).transpose(0, 1))
+        with torch.autocast(device_type="cuda", enabled=False):
+            out, idx, losses = _fused_forward(list(self.rvqs), xg, mask, stages)
+        if rvq0.has_projections:
+            quantized = torch.cat([rvq.project_out(out[g].reshape(*lead, d)) for g, rvq in enumerate(self.rvqs)], dim=-1)
+        else:
+            quantized = out.transpose(0, 1).reshape(*lead, G * d)
+        all_indices, commit_losses = _pad_stages(idx.reshape(G, *lead, stages), losses, Q, loss_dtype)
+        ret = (quantized, all_indices, commit_losses)
+        if not return_all_codes:
+            return ret
+        return (*ret, tuple(rvq.get_codes_from_indices(all_indices[g]) for g, rvq in enumerate(self.rvqs)))
