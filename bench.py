@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- vectors quantized / second on the nearest-codebook hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|k8192|cfg3a|cfg3b|cfg4|cfg1|wide1024] [--legs a,b,...]
-                    [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|k8192|cfg3a|cfg3b|cfg4|cfg1|wide1024]
+                    [--dump-outputs DIR] [--full [--legs a,b,...]]
 
-N > 1 is launched by the driver as  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+N > 1 is launched as  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 (one rank per GPU, RCCL).  A "step" is one full eval-mode module forward (fused search/gather launch; the packed
 codebook image is cached by the module) over one batch of synthetic input already resident in HBM.  Rank 0 prints
 ONE JSON line.
@@ -12,18 +12,24 @@ ONE JSON line.
 Headline workload = BASELINE configs[1]: VectorQuantize(dim=256, codebook_size=1024) on a [256, 1024, 256] batch per
 GPU (M = 262 144 rows per GPU; rows shard over ranks with no data-path collective -> weak scaling).
 
+A plain run does only what the headline figure needs: set up, settle the clock, W warm-up steps, K timed steps, the
+--dump-outputs write, the JSON line.  --full adds everything else the line can report (the isolated-kernel cross-check,
+the CPU-oracle parity gate, cpu_baseline, legs, sharded_k65536); without it those objects are null.
+
 Objects in the JSON line beside the contract's keys:
   roofline      dominant kernel (vq_search_mfma) priced against the fp32 MFMA peak: algorithmic FLOPs (2*K*D per
                 searched row and stage) / mean launch duration measured with HIP events on the launch stream INSIDE
                 the timed region.  `traffic` = HBM bytes per launch from the rocprofv3 PMC passes of the same command
                 (profiles/traffic.json; gfx950 correction of MI355X_MICROARCH.md applied), null if not collected.
-  cpu_baseline  the reference's ATen op sequence (oracle/ref_path.py, "port") timed on the host cores on a bounded
+                `kernel_ms_isolated` (--full) = the search kernel alone, back to back, after the timed region.
+  parity        (--full, rank 0 / N = 1) the CPU oracle checks a sample of the headline workload's indices.
+  cpu_baseline  (--full) the reference's ATen op sequence (oracle/ref_path.py, "port") timed on the host cores on a bounded
                 sample, rank 0 / N = 1 only; also the 1-thread figure and the CPU model.
-  legs          (N = 1) the other single-GPU BASELINE workloads, each run like the headline (same W / K): k8192
+  legs          (--full, N = 1) the other single-GPU BASELINE workloads, each run like the headline (same W / K): k8192
                 (north-star roofline shape), cfg3a / cfg3b (multi-head, per-head dim 64 / 512), cfg4 (ResidualVQ) --
                 value, ms_per_step, roofline and a CPU-oracle parity gate per leg; plus wide1024 (rows of 1024 dims:
                 not a BASELINE config, the sliced sweep for rows wider than one launch holds).
-  sharded_k65536  BASELINE configs[4]: K = 65536, D = 512 sharded over the N ranks (packed-key planes, MIN all-reduce or
+  sharded_k65536  (--full) BASELINE configs[4]: K = 65536, D = 512 sharded over the N ranks (packed-key planes, MIN all-reduce or
                 one-hop all-gather + MIN in the finalize), M = 8192 and M = 65536, each with per-phase times (search /
                 exchange / finalize / host enqueue); at N = 1 the full-codebook 1-GPU figure of the same kernels.
   dumped_outputs  (--dump-outputs DIR only) name -> shape of each array written by dump_outputs().
@@ -317,7 +323,8 @@ def dump_outputs(dump_dir, result):
 
 def run_workload(name, args, device, rank, world, want_parity, dump_dir=None):
     """W warm-up + K timed steps of one workload; -> (value rows/s over all ranks, ms_per_step, roofline, parity, w, dumped).
-    dump_dir: write the last timed step's outputs there (dump_outputs), after the timed region; dumped = what was written."""
+    dump_dir: write the last timed step's outputs there (dump_outputs), after the timed region; dumped = what was written.
+    args.full: also the isolated-kernel cross-check (kernel_ms_isolated, else null)."""
     from vector_quantization import native
 
     w = dict(WORKLOADS[name], name=name)
@@ -356,8 +363,10 @@ def run_workload(name, args, device, rank, world, want_parity, dump_dir=None):
 
     fl = flops_per_step(w)
     live_ms = sum(a.elapsed_time(b) for a, b in kernel_events) / max(1, len(kernel_events))
-    with torch.no_grad():
-        iso_ms = isolated_kernel_ms(w, device, mod, x)
+    iso_ms = None
+    if args.full:
+        with torch.no_grad():
+            iso_ms = round(isolated_kernel_ms(w, device, mod, x), 4)
     # after the isolated cross-check too: the host-side write idles the chip, and its clock drops (see the settle phase)
     dumped = dump_outputs(dump_dir, result) if dump_dir else None
     del result
@@ -372,7 +381,7 @@ def run_workload(name, args, device, rank, world, want_parity, dump_dir=None):
                         "vq_search_pair512" if (head_dim(w) > 256 and w.get("Q", 1) == 1) else
                         "vq_search_persist" if (128 < head_dim(w) <= 256 and w.get("Q", 1) == 1 and 1024 <= w["K"] <= 3072) else
                         "vq_search_mfma"),
-                kernel_ms=round(live_ms, 4), kernel_ms_isolated=round(iso_ms, 4), launches_timed=len(kernel_events),
+                kernel_ms=round(live_ms, 4), kernel_ms_isolated=iso_ms, launches_timed=len(kernel_events),
                 algorithmic_flops_per_launch=fl, algorithmic_hbm_bytes_per_launch=ab,
                 hbm_gbs_algorithmic=round(ab / (live_ms * 1e-3) / 1e9, 1), hbm_frac_of_peak=round(ab / (live_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4))
     parity = parity_gate(w, mod, x) if want_parity else None
@@ -441,10 +450,14 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=30)  # the chip needs ~30 ms of load to settle its clock
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--legs", default=None, help=f"comma list of extra workloads (N = 1 only; default {DEFAULT_LEGS} beside cfg2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the isolated-kernel cross-check, parity gate, legs, sharded_k65536 and cpu_baseline "
+                         "(the --no-* / --legs / --cpu-seconds options below trim a --full run)")
+    ap.add_argument("--legs", default=None,
+                    help=f"--full: comma list of extra workloads (N = 1 only; default {DEFAULT_LEGS} beside cfg2)")
     ap.add_argument("--no-legs", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: neither the parity gate nor cpu_baseline")
     ap.add_argument("--no-sharded", action="store_true")
     ap.add_argument("--settle-ms", type=float, default=60.0,
                     help="untimed load before the W warm-up steps so the chip's clock has settled (DVFS ramp ~30 ms)")
@@ -455,6 +468,8 @@ def main():
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
+    if args.legs is not None and not args.full:
+        ap.error("--legs needs --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -484,12 +499,12 @@ def main():
     native.load()
     solo = rank == 0 and world == 1
     value, ms_per_step, roof, parity, w, dumped = run_workload(args.workload, args, device, rank, world,
-                                                               want_parity=solo and not args.no_cpu_baseline,
+                                                               want_parity=args.full and solo and not args.no_cpu_baseline,
                                                                dump_dir=args.dump_outputs if rank == 0 else None)
 
     legs = None
-    leg_names = [] if (args.no_legs or world > 1) else [n for n in (args.legs if args.legs is not None else
-                                                                    (DEFAULT_LEGS if args.workload == "cfg2" else "")).split(",") if n]
+    leg_names = [] if (not args.full or args.no_legs or world > 1) else [
+        n for n in (args.legs if args.legs is not None else (DEFAULT_LEGS if args.workload == "cfg2" else "")).split(",") if n]
     if leg_names:
         legs = {}
         for n in leg_names:
@@ -503,14 +518,14 @@ def main():
                 legs[n] = dict(error=f"{type(e).__name__}: {str(e)[:200]}")
 
     sharded = None
-    if not args.no_sharded:
+    if args.full and not args.no_sharded:
         try:
             with torch.no_grad():
                 sharded = sharded_k65536(device, rank, world)
         except Exception as e:  # informational leg: never fail the bench line
             sharded = dict(error=f"{type(e).__name__}: {str(e)[:200]}")
     cpu = None
-    if solo and not args.no_cpu_baseline:
+    if args.full and solo and not args.no_cpu_baseline:
         cpu = cpu_baseline(w, args.cpu_seconds)
 
     if rank == 0:

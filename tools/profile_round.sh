@@ -13,7 +13,7 @@ OUT=$ROOT/gpurun_out/$RND/prof
 mkdir -p $OUT
 cd /tmp
 for wl in $WLS; do
-  CMD="python3 $ROOT/bench.py --workload $wl --no-legs --no-cpu-baseline --no-sharded --steps 20 --warmup 5"
+  CMD="python3 $ROOT/bench.py --full --workload $wl --no-legs --no-cpu-baseline --no-sharded --steps 20 --warmup 5"
   echo "== $wl: kernel trace ($(date +%T))"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$wl/stats -o $wl -- $CMD > $OUT/$wl.stats.log 2>&1 || { echo "FAILED stats $wl"; tail -5 $OUT/$wl.stats.log; exit 1; }
   grep '^{' $OUT/$wl.stats.log > $OUT/$wl.bench_under_trace.json || true
   echo "== $wl: FETCH_SIZE"; rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/$wl/fetch -o $wl -- $CMD > $OUT/$wl.fetch.log 2>&1 || { echo "FAILED fetch $wl"; tail -5 $OUT/$wl.fetch.log; exit 1; }
