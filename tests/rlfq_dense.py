@@ -3,7 +3,8 @@
 The residual chain itself runs in fp32, op for op as the reference writes it (soft clamp, l2norm, sign, straight-through
 value, residual -= quantized), so every stage sees the reference's stage input.  Each stage's losses and gradient are then
 restated in fp64: the entropy terms by tests/lfq_dense.py, the commitment term and the clamp / l2norm Jacobians by fp64
-autograd.  The residual's detach makes d r_q / d x the identity, so dL/dx is the sum of the stages' terms.
+autograd.  Everything is allocated on x's device.  The residual's detach makes d r_q / d x the identity, so dL/dx is the
+sum of the stages' terms.
 """
 from __future__ import annotations
 
@@ -72,7 +73,7 @@ def restate(kwargs: dict, sd: dict, x: torch.Tensor, mask, g_out: torch.Tensor, 
     kept = N if m is None else int(m.sum())
     residual = xp.clone()
     out_sum = torch.zeros_like(xp)
-    g_xp = torch.zeros(N, d, dtype=torch.float64)
+    g_xp = torch.zeros(N, d, dtype=torch.float64, device=x.device)
     losses = []
     for q in range(stages):
         scale, clamp, mag = stage_params(kwargs, q)
@@ -107,4 +108,4 @@ def restate(kwargs: dict, sd: dict, x: torch.Tensor, mask, g_out: torch.Tensor, 
         residual = residual - out
         out_sum = out_sum + out
     grad = g_xp @ sd["project_in.weight"].double() if proj else g_xp
-    return dict(grad=grad.reshape(x.shape), losses=torch.tensor(losses, dtype=torch.float64), out=out_sum)
+    return dict(grad=grad.reshape(x.shape), losses=torch.tensor(losses, dtype=torch.float64, device=x.device), out=out_sum)

@@ -15,6 +15,7 @@
 //                           partials; lfq_avg_reduce_kernel adds the splits in order and divides by the row count
 //   lfq_entropy_bwd_kernel  one wave per (selected row, codebook): tables rebuilt in LDS, one sweep gives
 //                           S0 = sum_k g_k p_k and S_i = sum_k g_k p_k b_{k,i};  dL/dv_i = 4 tau a (S_i - pi_i(1) S0)
+//                           with g_k centred first (see the kernel: the difference cancels when g_k is nearly constant)
 // No float atomics anywhere: every sum has one fixed order, so results are bitwise run-to-run reproducible.
 //
 // Stage axis (the residual LFQ's stage-batched calls, vq_lfq_entropy_staged_*): every entropy kernel and lfq_sum_kernel take
@@ -54,6 +55,11 @@ __device__ __forceinline__ float lfq_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// lane 0's value in every lane (a butterfly sum may differ in its last bit from lane to lane)
+__device__ __forceinline__ float lfq_readfirstlane(float v) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -142,17 +148,30 @@ __host__ __device__ inline int lfq_task_lds_floats(const LfqShape &s) { return 4
 
 // Fills the task's LDS region: s1/s0 = sigmoid(+-z), l1/l0 = logsigmoid(+-z) per dim, then A/LA (high dims) and B/LB
 // (low dims).  Lane i < d holds z_i on return (0 elsewhere).  Every lane of the block must reach both barriers.
+// Centred (the backward): l1/l0 hold the logs minus their mean under pi, logsigmoid(+-z) + H_i = s0 z and -s1 z (exact
+// because logsigmoid(z) - logsigmoid(-z) = z), so LA_u + LB_w = log p_k + H with H = sum_i H_i the row's entropy; lane
+// i < d returns H_i in *h_i and max(logsigmoid(+-z_i)) in *lmax_i (0 elsewhere).
 __device__ __forceinline__ float lfq_build_tables(float *lds, const LfqShape &S, const float *vr, float coef, bool valid,
-                                                  int lane) {
+                                                  int lane, float *h_i = nullptr, float *lmax_i = nullptr) {
     float *s1 = lds, *s0 = lds + 32, *l1 = lds + 64, *l0 = lds + 96;
     float *A = lds + 128, *LA = A + S.NA, *B = LA + S.NA, *LB = B + S.NB;
     float z = 0.0f;
     if (valid && lane < S.d) {
         z = coef * vr[lane];
-        s1[lane] = lfq_sigmoid(z);
-        s0[lane] = lfq_sigmoid(-z);
-        l1[lane] = lfq_logsigmoid(z);
-        l0[lane] = lfq_logsigmoid(-z);
+        const float p1 = lfq_sigmoid(z), p0 = lfq_sigmoid(-z);
+        const float g1 = lfq_logsigmoid(z), g0 = lfq_logsigmoid(-z);
+        s1[lane] = p1;
+        s0[lane] = p0;
+        if (h_i) {
+            // (a zero probability times an infinite log or z counts as 0: an infinite input stays finite here)
+            *h_i = -((p1 > 0.0f ? p1 * g1 : 0.0f) + (p0 > 0.0f ? p0 * g0 : 0.0f));
+            *lmax_i = fmaxf(g1, g0);
+            l1[lane] = p0 > 0.0f ? p0 * z : 0.0f;
+            l0[lane] = p1 > 0.0f ? -(p1 * z) : 0.0f;
+        } else {
+            l1[lane] = g1;
+            l0[lane] = g0;
+        }
     }
     __syncthreads();
     if (valid) {
@@ -268,6 +287,22 @@ __global__ void __launch_bounds__(256) lfq_avg_reduce_kernel(const double *__res
 // term's G(avg_prob) with its upstream gradient, 1 / (C * world * rows) folded in by the caller.
 // Pair k = s * 64 + lane: the low 6 bits of k are the lane's own, so their S_i are bit * S0 of the lane; the bits above
 // are the same for the whole wave (one add per set bit per pair).
+// Centring.  sum_k p_k (b_{k,i} - pi_i(1)) = 0, so S_i - pi_i(1) S0 does not change when one constant is subtracted from
+// every g_k; in fp32 it decides whether the difference cancels.  Uncentred, g_k nearly constant (the codebook term once
+// avg_prob is near uniform, the per-sample term at small tau a |v|) left fp32 sums of 2^d / 64 terms of size |g| whose
+// difference is a small fraction of |g|: errors of percents of the gradient at d = 16, all of it at d = 20.  The kernel
+// subtracts w_ps (H - 1 + D) + c_cb, an estimate of sum_k g_k p_k made of wave-uniform constants of the task:
+//   H - 1   the p-weighted mean of G without the clamp (H = sum_i H_i, the row's entropy), so the unclamped branch is
+//           G - (H - 1) = -(LA_u + LB_w) on the centred tables (no rounding of log p_k against H);
+//   D       0, or -log 1e-5 + 1 - H when every code lies below the clamp (sum_i max logsigmoid < log 1e-5): then every
+//           centred G is exactly 0, as is the exact per-sample gradient;
+//   c_cb    p_m w_cb[c, k_m] + (1 - p_m) wbar: k_m the row's most likely code (the signs of z), p_m its probability,
+//           wbar the mean of w_cb[c, .] over 64 codes spread evenly over the 2^d (all of them when d < 6).  A saturated
+//           row puts its weight on k_m, a flat one spreads it: either way c_cb is close to the p-weighted mean of w_cb.
+// Per pair that is one subtraction, w_cb[k] - c_cb, before the fma: the difference of two nearby fp32 values is exact, and
+// the fma then rounds the centred g_k once.  (Folding c_cb / w_ps into D instead saves the subtraction but rounds
+// -(LA + LB + D) at the scale of c_cb / w_ps, which is the cancellation again when the two terms nearly cancel.)
+// Each constant is read from lane 0 (readfirstlane): one value for the whole sweep, or the identity would not hold.
 // ------------------------------------------------------------------------------------------------
 // stage t = blockIdx.y: v + t * v_ss, rows + t * rows_ss, w_ps + t, w_cb + t * C * 2^d, gv + t * gv_ss
 __global__ void __launch_bounds__(256) lfq_entropy_bwd_kernel(const float *__restrict__ v, int64_t v_rs, int64_t v_ss,
@@ -291,13 +326,25 @@ __global__ void __launch_bounds__(256) lfq_entropy_bwd_kernel(const float *__res
     const int c = valid ? (int)(task - j * C) : 0;
     const int64_t m = valid ? (rows ? rows[j] : j) : 0;
     float *lds = lfq_lds + wave * lfq_task_lds_floats(S);
-    lfq_build_tables(lds, S, v + m * v_rs + (int64_t)c * d, coef, valid, lane);
+    const float wps = w_ps[0];
+    float h_i = 0.0f, lmax_i = 0.0f;
+    const float z = lfq_build_tables(lds, S, v + m * v_rs + (int64_t)c * d, coef, valid, lane, &h_i, &lmax_i);
     if (!valid) return;
     const float *A = lds + 128, *LA = A + S.NA, *B = LA + S.NA, *LB = B + S.NB;
     const float *wc = w_cb + (int64_t)c * ((int64_t)1 << d);
-    const float wps = w_ps[0];
     const int P = 1 << d;
-    const float neg_log_eps = -logf(kLfqEps);
+    // the centring constants (see above)
+    const float H = lfq_readfirstlane(lfq_wave_sum(h_i));
+    const float lmax = lfq_readfirstlane(lfq_wave_sum(lmax_i));
+    const float gclamp = -logf(kLfqEps) + 1.0f - H;  // G - (H - 1) below the clamp
+    const float dlt = lfq_readfirstlane(lmax < logf(kLfqEps) ? gclamp : 0.0f);
+    const float gcl = lfq_readfirstlane(gclamp - dlt);
+    const unsigned long long pos = __ballot(lane < d && z > 0.0f);  // bit i: dim i of the most likely code
+    const int km = (int)(__brevll(pos) >> (64 - d));
+    const float wsamp = P >= 64 ? wc[lane * (P >> 6)] : (lane < P ? wc[lane] : 0.0f);
+    const float wbar = lfq_readfirstlane(lfq_wave_sum(wsamp) * (P >= 64 ? 1.0f / 64.0f : 1.0f / (float)P));
+    const float pm = expf(lmax);
+    const float ccb = lfq_readfirstlane(pm * wc[km] + (1.0f - pm) * wbar);
     constexpr int kHi = kLfqMaxDim - 6;
     const int nhi = d > 6 ? d - 6 : 0;
     float s0 = 0.0f;
@@ -307,8 +354,8 @@ __global__ void __launch_bounds__(256) lfq_entropy_bwd_kernel(const float *__res
     for (int k = lane, s = 0; k < P; k += 64, ++s) {
         const int u = k >> S.l, w = k & (S.NB - 1);
         const float p = A[u] * B[w];
-        const float G = p >= kLfqEps ? -(LA[u] + LB[w] + 1.0f) : neg_log_eps;
-        const float t = fmaf(wps, G, wc[k]) * p;
+        const float G = p >= kLfqEps ? -(LA[u] + LB[w] + dlt) : gcl;
+        const float t = fmaf(wps, G, wc[k] - ccb) * p;
         s0 += t;
 #pragma unroll
         for (int b = 0; b < kHi; ++b)
