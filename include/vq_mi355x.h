@@ -306,6 +306,33 @@ int vq_rlfq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, 
                          int spherical, const uint8_t *mask, const float *g_out, int64_t g_gs, int64_t g_rs,
                          const float *w_commit, const float *g_ent, float *grad_x, int64_t gx_gs, int64_t gx_rs, void *stream);
 
+/*
+ * vq_fsq_quantize_f32 -- finite scalar quantization (FSQ, ResidualFSQ): all S stages of G groups in one pass, one thread per
+ *   row of d <= 16 values.  Row m of group g is x[g * x_gs + m * x_rs + i] (i < d, contiguous).  levels: HOST int32 [d]
+ *   (each >= 2; basis = cumprod of the levels before, which must fit int32).  consts: DEVICE floats [3 + S][d], rows
+ *   half_l, offset, shift (the reference's bound constants, computed by the caller), then the S stage scales.  With
+ *   bound(z) = tanh(z + shift) * half_l - offset and hw = L / 2, r starts at x (prebound = 0) or bound(x) (prebound = 1,
+ *   ResidualFSQ), and per stage s:  c = rint(bound(r / scale[s])) / hw;  o = c * scale[s];  r -= o;  out += o  (out from
+ *   +0, stage order);  idx[(g * N + m) * S + s] = (int32) sum_i ((c_i * hw_i) + hw_i) * basis_i in fp32, summed in the
+ *   order of torch's CPU sum over d <= 7 (partials k < 4 from term k, terms 4 .. d-1 into partial 0, then p0 += p1, p2,
+ *   p3), truncated; NaN gives INT32_MIN.  Writes out[g * out_gs + m * out_rs + i]; idx may be NULL.
+ * vq_fsq_backward_f32 -- grad_x of the same chain (straight-through rounding):  grad_x = [bound'(x) if prebound] *
+ *   sum_s bound'(r_s / scale[s]) / hw * g_out, recomputing r_s from x with the forward's code.  No atomics.
+ * vq_fsq_decode_f32 -- idx [N][Q] (int32, or int64 when idx_64) -> codes ((i // basis) % L - hw) / hw * scales[q][i]
+ *   (floor division and Python modulo, as torch's integer // and %), scales a DEVICE float array [Q][d].  With drop_null,
+ *   an index of -1 gives a zero code.  codes_sum [N][d] (the sum over q in stage order) and all_codes [Q][N][d] may each
+ *   be NULL, not both.
+ * Errors (-1, vq_last_error): a null pointer, d outside [1, 16], a level below 2, G, N, S (Q) not positive, G > 65535.
+ */
+int vq_fsq_quantize_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, const int32_t *levels, int S,
+                        const float *consts, int prebound, float *out, int64_t out_gs, int64_t out_rs, int32_t *idx,
+                        void *stream);
+int vq_fsq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, const int32_t *levels, int S,
+                        const float *consts, int prebound, const float *g_out, int64_t g_gs, int64_t g_rs, float *grad_x,
+                        int64_t gx_gs, int64_t gx_rs, void *stream);
+int vq_fsq_decode_f32(const void *idx, int idx_64, int64_t N, int Q, int d, const int32_t *levels, const float *scales,
+                      int drop_null, float *codes_sum, float *all_codes, void *stream);
+
 const char *vq_last_error(void);
 int vq_device_info(char *buf, size_t n); /* "gfx950 ... CUs" of the current device */
 

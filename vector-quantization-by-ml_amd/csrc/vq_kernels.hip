@@ -32,6 +32,8 @@
 //   vq_finalize_ema.inc  scalar fallback search, finalize-from-keys, loss reduction, EMA codebook update
 //   vq_lfq.inc           lookup-free quantization: sign quantizer, factorised entropy loss forward / backward (stage axis)
 //   vq_rlfq.inc          residual LFQ: every stage's quantize step in one pass (residual in registers), its backward
+//   vq_fsq.inc           finite scalar quantization (FSQ / residual FSQ): every stage of every group in one pass, its
+//                        backward, index -> code decode
 //   this file            host-side dispatch and the C ABI (include/vq_mi355x.h)
 //
 // Reference lines replaced (relative to the reference root): vector_quantization/codebooks.py:386-397,
@@ -49,7 +51,7 @@
 // the same file once per part (-DVQ_PART=n, in parallel) and links the objects: every part sees the same templates, but only
 // its own launchers are defined -- and with them instantiated -- there; the other parts call them through the
 // vqi::part_* entry points declared below.
-//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ) 4 search Dp = 512 + wave-pair kernel
+//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward
 #ifndef VQ_PART
@@ -76,6 +78,7 @@ namespace {
 #include "vq_finalize_ema.inc"
 #include "vq_lfq.inc"
 #include "vq_rlfq.inc"
+#include "vq_fsq.inc"
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1787,6 +1790,50 @@ int vq_rlfq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, 
                          g_out, g_gs, g_rs, w_commit, g_ent, grad_x, gx_gs, gx_rs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "vq_rlfq_backward launch");
+    return 0;
+}
+
+int vq_fsq_quantize_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, const int32_t *levels, int S,
+                        const float *consts, int prebound, float *out, int64_t out_gs, int64_t out_rs, int32_t *idx,
+                        void *stream) {
+    FsqLevels lv;
+    int rc = fsq_check(G, N, d, S, levels, consts, lv, "vq_fsq_quantize");
+    if (rc) return rc;
+    if (!x || !out) return fail(VQ_E_BADARG, "vq_fsq_quantize: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    fsq_launch_quantize(d, dim3((unsigned)fsq_blocks(N), (unsigned)G), s, x, x_gs, x_rs, N, S, lv, consts, prebound != 0, out,
+                        out_gs, out_rs, idx);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "vq_fsq_quantize launch");
+    return 0;
+}
+
+int vq_fsq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, const int32_t *levels, int S,
+                        const float *consts, int prebound, const float *g_out, int64_t g_gs, int64_t g_rs, float *grad_x,
+                        int64_t gx_gs, int64_t gx_rs, void *stream) {
+    FsqLevels lv;
+    int rc = fsq_check(G, N, d, S, levels, consts, lv, "vq_fsq_backward");
+    if (rc) return rc;
+    if (!x || !g_out || !grad_x) return fail(VQ_E_BADARG, "vq_fsq_backward: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    fsq_launch_backward(d, dim3((unsigned)fsq_blocks(N), (unsigned)G), s, x, x_gs, x_rs, N, S, lv, consts, prebound != 0, g_out,
+                        g_gs, g_rs, grad_x, gx_gs, gx_rs);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "vq_fsq_backward launch");
+    return 0;
+}
+
+int vq_fsq_decode_f32(const void *idx, int idx_64, int64_t N, int Q, int d, const int32_t *levels, const float *scales,
+                      int drop_null, float *codes_sum, float *all_codes, void *stream) {
+    FsqLevels lv;
+    int rc = fsq_check(1, N, d, Q, levels, scales, lv, "vq_fsq_decode");
+    if (rc) return rc;
+    if (!idx || (!codes_sum && !all_codes)) return fail(VQ_E_BADARG, "vq_fsq_decode: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    fsq_launch_decode(d, dim3((unsigned)fsq_blocks(N)), s, idx, idx_64 != 0, N, Q, lv, scales, drop_null != 0, codes_sum,
+                      all_codes);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "vq_fsq_decode launch");
     return 0;
 }
 

@@ -9,17 +9,20 @@ The search itself (distance -> first argmax -> gather, straight-through, squared
 hand-written HIP for gfx950 behind the C ABI in ``include/vq_mi355x.h``; there is no PyTorch/CPU fallback.
 ``LFQ`` (lookup-free quantization) runs its sign quantizer and its entropy aux loss -- a sweep over an implicit codebook
 of 2^d codes -- in HIP as well, and so do ``ResidualLFQ`` / ``GroupedResidualLFQ`` (every stage's quantize step in one
-fused pass, every stage's entropy terms in one stage-batched call).  The reference's other families (FSQ, latent
-quantization, residual FSQ) never touch a codebook search and are not part of this build.
+fused pass, every stage's entropy terms in one stage-batched call).  ``FSQ`` (finite scalar quantization) and
+``ResidualFSQ`` / ``GroupedResidualFSQ`` run bound, round, index and every residual stage of every group in one HIP pass,
+and their backward in one more.  The reference's latent quantization (``LatentQuantize``) is not part of this build.
 """
 from . import ops  # noqa: F401  (registers torch.ops.vq_mi355x.*)
 from .codebook import Codebook
+from .finite_scalar_quantization import FSQ
 from .graphs import GraphedForward
 from .lookup_free_quantization import LFQ
 from .params import AffineParameters, CodebookParams, GumbelParams, KmeansParameters
 from .projection import RandomProjectionQuantizer
 from .quantizer import LossBreakdown, VectorQuantize
 from .residual import GroupedResidualVQ, ResidualVQ
+from .residual_fsq import GroupedResidualFSQ, ResidualFSQ
 from .residual_lfq import GroupedResidualLFQ, ResidualLFQ
 from .sharded import ShardedCodebookSearch
 
@@ -27,7 +30,9 @@ __all__ = [
     "AffineParameters",
     "Codebook",
     "CodebookParams",
+    "FSQ",
     "GraphedForward",
+    "GroupedResidualFSQ",
     "GroupedResidualLFQ",
     "GroupedResidualVQ",
     "GumbelParams",
@@ -35,6 +40,7 @@ __all__ = [
     "LFQ",
     "LossBreakdown",
     "RandomProjectionQuantizer",
+    "ResidualFSQ",
     "ResidualLFQ",
     "ResidualVQ",
     "ShardedCodebookSearch",

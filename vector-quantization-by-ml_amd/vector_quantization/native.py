@@ -170,6 +170,15 @@ def load():
         lib.vq_rlfq_backward_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,
                                              _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp]
         lib.vq_rlfq_backward_f32.restype = ctypes.c_int
+        lib.vq_fsq_quantize_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int,
+                                            _vp, _i64, _i64, _vp, _vp]
+        lib.vq_fsq_quantize_f32.restype = ctypes.c_int
+        lib.vq_fsq_backward_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int,
+                                            _vp, _i64, _i64, _vp, _i64, _i64, _vp]
+        lib.vq_fsq_backward_f32.restype = ctypes.c_int
+        lib.vq_fsq_decode_f32.argtypes = [_vp, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp,
+                                          _vp]
+        lib.vq_fsq_decode_f32.restype = ctypes.c_int
         lib.vq_device_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         lib.vq_device_info.restype = ctypes.c_int
         _lib = lib
@@ -186,6 +195,7 @@ EXPORTED_SYMBOLS = (
     "vq_lfq_workspace_bytes", "vq_lfq_quantize_f32", "vq_lfq_entropy_fwd_f32", "vq_lfq_entropy_bwd_f32",
     "vq_lfq_staged_workspace_bytes", "vq_lfq_entropy_staged_fwd_f32", "vq_lfq_entropy_staged_bwd_f32",
     "vq_rlfq_workspace_bytes", "vq_rlfq_quantize_f32", "vq_rlfq_backward_f32",
+    "vq_fsq_quantize_f32", "vq_fsq_backward_f32", "vq_fsq_decode_f32",
 )
 
 
@@ -925,3 +935,98 @@ def lfq_entropy_staged_backward(v: torch.Tensor, rows: torch.Tensor | None, code
                                                  w_ps.data_ptr(), w_cb.data_ptr(), gv.data_ptr(), d, N * d, _stream_ptr(dev)),
                "vq_lfq_entropy_staged_bwd_f32")
     return gv
+
+
+# ------------------------------------------------------------------------------------------------
+# finite scalar quantization (vq_fsq_* in include/vq_mi355x.h)
+# ------------------------------------------------------------------------------------------------
+FSQ_MAX_DIM = 16
+
+
+def _levels_arg(levels):
+    """Host int32 copy of the levels (the C ABI reads them on the host)."""
+    arr = (ctypes.c_int32 * len(levels))(*[int(v) for v in levels])
+    return arr
+
+
+def _fsq_rows(x: torch.Tensor):
+    """x [G, N, d] fp32 whose rows are contiguous -> (group stride, row stride) in elements."""
+    assert x.dim() == 3 and x.dtype == torch.float32, "x must be [G, N, d] fp32"
+    assert x.shape[2] <= 1 or x.stride(2) == 1, "each row's d values must be contiguous"
+    return int(x.stride(0)), int(x.stride(1))
+
+
+def fsq_quantize(x: torch.Tensor, levels, consts: torch.Tensor, *, prebound: bool = False, want_idx: bool = True,
+                 out: torch.Tensor | None = None):
+    """Every stage of an FSQ stack over x [G, N, d] -> (out [G, N, d] (the caller's view when given), idx [G, N, S] int32
+    or None).  consts: device fp32 [3 + S, d] (half_l, offset, shift, then the stage scales; see the header)."""
+    _require_gpu(x, consts)
+    lib = load()
+    G, N, d = x.shape
+    dev = x.device
+    S = consts.shape[0] - 3
+    assert consts.dtype == torch.float32 and consts.shape == (3 + S, d) and consts.is_contiguous()
+    x_gs, x_rs = _fsq_rows(x)
+    if out is None:
+        out = torch.empty((G, N, d), dtype=torch.float32, device=dev)
+    o_gs, o_rs = _fsq_rows(out)
+    idx = torch.empty((G, N, S), dtype=torch.int32, device=dev) if want_idx else None
+    if N == 0:
+        return out, idx
+    with torch.cuda.device(dev):
+        _check(lib.vq_fsq_quantize_f32(x.data_ptr(), x_gs, x_rs, G, N, d, _levels_arg(levels), S, consts.data_ptr(),
+                                       int(prebound), out.data_ptr(), o_gs, o_rs, idx.data_ptr() if idx is not None else None,
+                                       _stream_ptr(dev)), "vq_fsq_quantize_f32")
+    return out, idx
+
+
+def fsq_backward(x: torch.Tensor, levels, consts: torch.Tensor, g_out: torch.Tensor, *, prebound: bool = False,
+                 grad_x: torch.Tensor | None = None) -> torch.Tensor:
+    """dL/dx [G, N, d] of fsq_quantize's out for the upstream gradient g_out [G, N, d] (straight-through rounding)."""
+    _require_gpu(x, consts, g_out)
+    lib = load()
+    G, N, d = x.shape
+    dev = x.device
+    S = consts.shape[0] - 3
+    assert consts.dtype == torch.float32 and consts.shape == (3 + S, d) and consts.is_contiguous()
+    x_gs, x_rs = _fsq_rows(x)
+    g_out = g_out.to(torch.float32)
+    if g_out.shape[2] > 1 and g_out.stride(2) != 1:
+        g_out = g_out.contiguous()
+    g_gs, g_rs = _fsq_rows(g_out)
+    if grad_x is None:
+        grad_x = torch.empty((G, N, d), dtype=torch.float32, device=dev)
+    gx_gs, gx_rs = _fsq_rows(grad_x)
+    if N == 0:
+        return grad_x
+    with torch.cuda.device(dev):
+        _check(lib.vq_fsq_backward_f32(x.data_ptr(), x_gs, x_rs, G, N, d, _levels_arg(levels), S, consts.data_ptr(),
+                                       int(prebound), g_out.data_ptr(), g_gs, g_rs, grad_x.data_ptr(), gx_gs, gx_rs,
+                                       _stream_ptr(dev)), "vq_fsq_backward_f32")
+    return grad_x
+
+
+def fsq_decode(indices: torch.Tensor, levels, scales: torch.Tensor, *, drop_null: bool = False, want_sum: bool = True,
+               want_all: bool = False):
+    """indices [N, Q] (int32 / int64) -> (sum over q of the codes [N, d] or None, all codes [Q, N, d] or None), the code of
+    index i at stage q being ((i // basis) % L - hw) / hw * scales[q] (scales: device fp32 [Q, d]); -1 gives a zero code
+    when drop_null."""
+    _require_gpu(indices, scales)
+    lib = load()
+    N, Q = indices.shape
+    d = len(levels)
+    dev = indices.device
+    assert indices.dtype in (torch.int32, torch.int64)
+    assert scales.dtype == torch.float32 and scales.shape == (Q, d) and scales.is_contiguous()
+    indices = indices.contiguous()
+    codes_sum = torch.empty((N, d), dtype=torch.float32, device=dev) if want_sum else None
+    all_codes = torch.empty((Q, N, d), dtype=torch.float32, device=dev) if want_all else None
+    if N == 0:
+        return codes_sum, all_codes
+    with torch.cuda.device(dev):
+        _check(lib.vq_fsq_decode_f32(indices.data_ptr(), int(indices.dtype == torch.int64), N, Q, d, _levels_arg(levels),
+                                     scales.data_ptr(), int(drop_null),
+                                     codes_sum.data_ptr() if codes_sum is not None else None,
+                                     all_codes.data_ptr() if all_codes is not None else None, _stream_ptr(dev)),
+               "vq_fsq_decode_f32")
+    return codes_sum, all_codes

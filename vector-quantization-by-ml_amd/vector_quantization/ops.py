@@ -10,6 +10,7 @@ instead of breaking the graph at an opaque Python call:
     torch.ops.vq_mi355x.lfq_quantize / lfq_entropy_fwd / lfq_entropy_bwd   (lookup-free quantization, native.lfq_*)
     torch.ops.vq_mi355x.rlfq_quantize / rlfq_backward / lfq_entropy_staged_fwd / lfq_entropy_staged_bwd
         (residual LFQ, native.rlfq_* and native.lfq_entropy_staged_*)
+    torch.ops.vq_mi355x.fsq_quantize / fsq_backward / fsq_decode   (finite scalar quantization, native.fsq_*)
 
 Eager forwards keep calling ``native.quantize`` directly (a custom-op dispatch costs tens of microseconds of host time,
 which is most of a small launch); the modules switch to these ops only while being compiled
@@ -160,3 +161,53 @@ def lfq_entropy_staged_bwd(v: torch.Tensor, rows: Optional[torch.Tensor], code_s
 @lfq_entropy_staged_bwd.register_fake
 def _(v, rows, code_scale, inv_temperature, w_ps, w_cb):
     return v.new_empty(v.shape)
+
+
+# finite scalar quantization (native.fsq_*).  consts [3 + S, d] as the kernels read them; indices that were not requested
+# come back as an empty tensor (a custom op returns no None).
+@torch.library.custom_op(f"{_LIB_NS}::fsq_quantize", mutates_args=())
+def fsq_quantize(x: torch.Tensor, levels: list[int], consts: torch.Tensor, prebound: bool,
+                 want_idx: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """x [G, N, d] -> (out [G, N, d], idx [G, N, S] int32 (or empty))."""
+    out, idx = native.fsq_quantize(x, levels, consts, prebound=prebound, want_idx=want_idx)
+    if idx is None:
+        idx = x.new_empty((0,), dtype=torch.int32)
+    return out, idx
+
+
+@fsq_quantize.register_fake
+def _(x, levels, consts, prebound, want_idx):
+    G, N, d = x.shape
+    S = consts.shape[0] - 3
+    return x.new_empty((G, N, d)), x.new_empty((G, N, S) if want_idx else (0,), dtype=torch.int32)
+
+
+@torch.library.custom_op(f"{_LIB_NS}::fsq_backward", mutates_args=())
+def fsq_backward(x: torch.Tensor, levels: list[int], consts: torch.Tensor, prebound: bool, g_out: torch.Tensor) -> torch.Tensor:
+    """dL/dx [G, N, d] of fsq_quantize's out (native.fsq_backward)."""
+    return native.fsq_backward(x, levels, consts, g_out, prebound=prebound)
+
+
+@fsq_backward.register_fake
+def _(x, levels, consts, prebound, g_out):
+    return x.new_empty(x.shape)
+
+
+@torch.library.custom_op(f"{_LIB_NS}::fsq_decode", mutates_args=())
+def fsq_decode(indices: torch.Tensor, levels: list[int], scales: torch.Tensor, drop_null: bool, want_sum: bool,
+               want_all: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """indices [N, Q] -> (codes summed over q [N, d] (or empty), all codes [Q, N, d] (or empty))."""
+    codes_sum, all_codes = native.fsq_decode(indices, levels, scales, drop_null=drop_null, want_sum=want_sum,
+                                             want_all=want_all)
+    if codes_sum is None:
+        codes_sum = scales.new_empty((0,))
+    if all_codes is None:
+        all_codes = scales.new_empty((0,))
+    return codes_sum, all_codes
+
+
+@fsq_decode.register_fake
+def _(indices, levels, scales, drop_null, want_sum, want_all):
+    N, Q = indices.shape
+    d = len(levels)
+    return scales.new_empty((N, d) if want_sum else (0,)), scales.new_empty((Q, N, d) if want_all else (0,))
