@@ -333,6 +333,36 @@ int vq_fsq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, i
 int vq_fsq_decode_f32(const void *idx, int idx_64, int64_t N, int Q, int d, const int32_t *levels, const float *scales,
                       int drop_null, float *codes_sum, float *all_codes, void *stream);
 
+/*
+ * vq_lq_quantize_f32 -- latent quantization (LatentQuantize): the per-dimension level search of every (batch, position,
+ *   codebook) sub-row in one pass, one thread per sub-row of d <= 16 values.  Element i of sub-row (b, p, c) is
+ *   z[b * z_bs + p * z_ps + (c * d + i) * z_cs] (strides in elements: a channel-first [B][C * d][P] tensor is z_ps = 1,
+ *   z_cs = P; a channel-last one z_ps = C * d, z_cs = 1); codes is written with its own three strides.  levels: HOST int32
+ *   [d] (each >= 2, their product below 2^31).  tables: DEVICE floats, the d value tables back to back (table i holds
+ *   levels[i] floats at offset levels[0] + .. + levels[i-1]; any order, duplicates allowed; at most 4096 floats).  Per
+ *   dimension:  j = argmin_j |z_i - v_i[j]| (the first minimum; a NaN distance is the minimum, the first NaN wins, as
+ *   ATen's argmin);  q = v_i[j];  c_i = z_i + (q - z_i);  t_i = ((c_i * 2) * hw_i + hw_i) * basis_i (hw = L / 2, basis =
+ *   cumprod of the levels before), every step one fp32 operation.  idx[(b * P + p) * C + c] = (int32) sum_i t_i, summed
+ *   and truncated as vq_fsq_quantize_f32 does (NaN or out of range: INT32_MIN); idx may be NULL.
+ *   loss (DEVICE float[2], may be NULL): loss[1] = m = sum (c_i - z_i)^2 / (B * P * C * d) (fp32 per-workgroup partials in
+ *   workspace, added in a fixed order in fp64: no atomics), loss[0] = w_c * m + w_q * m in fp32, a zero weight
+ *   multiplying 0 instead of m.  workspace: vq_lq_workspace_bytes(B, P, C) bytes when loss is given.
+ * vq_lq_backward_f32 -- grad_x = g_out + (g_loss[0] * coef) * (out - x) over [B][P][W] elements, each tensor with its own
+ *   three strides (batch, position, channel); g_loss a DEVICE scalar.  With coef = 2 / numel * (w_c - w_q) it is dL/dx of
+ *   vq_lq_quantize_f32's codes and loss[0] (the straight-through value passes g_out on unchanged).
+ * Errors (-1, vq_last_error): a null pointer, d outside [1, 16], a level below 2, a codebook size or a row count that
+ *   overflows, tables above 4096 floats, B, P, C (W) not positive, a workspace that is too small.
+ */
+int64_t vq_lq_workspace_bytes(int64_t B, int64_t P, int C);
+int vq_lq_quantize_f32(const float *z, int64_t z_bs, int64_t z_ps, int64_t z_cs, int64_t B, int64_t P, int C, int d,
+                       const int32_t *levels, const float *tables, float *codes, int64_t c_bs, int64_t c_ps, int64_t c_cs,
+                       int32_t *idx, float *loss, float w_c, float w_q, void *workspace, int64_t workspace_bytes,
+                       void *stream);
+int vq_lq_backward_f32(const float *x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const float *out, int64_t o_bs, int64_t o_ps,
+                       int64_t o_cs, const float *g_out, int64_t g_bs, int64_t g_ps, int64_t g_cs, const float *g_loss,
+                       float coef, int64_t B, int64_t P, int W, float *grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
+                       void *stream);
+
 const char *vq_last_error(void);
 int vq_device_info(char *buf, size_t n); /* "gfx950 ... CUs" of the current device */
 

@@ -34,6 +34,8 @@
 //   vq_rlfq.inc          residual LFQ: every stage's quantize step in one pass (residual in registers), its backward
 //   vq_fsq.inc           finite scalar quantization (FSQ / residual FSQ): every stage of every group in one pass, its
 //                        backward, index -> code decode
+//   vq_lq.inc            latent quantization: per-dimension level search against learnable value tables (in LDS), index,
+//                        fused squared-error loss and its backward
 //   this file            host-side dispatch and the C ABI (include/vq_mi355x.h)
 //
 // Reference lines replaced (relative to the reference root): vector_quantization/codebooks.py:386-397,
@@ -51,7 +53,7 @@
 // the same file once per part (-DVQ_PART=n, in parallel) and links the objects: every part sees the same templates, but only
 // its own launchers are defined -- and with them instantiated -- there; the other parts call them through the
 // vqi::part_* entry points declared below.
-//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ) 4 search Dp = 512 + wave-pair kernel
+//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward
 #ifndef VQ_PART
@@ -79,6 +81,7 @@ namespace {
 #include "vq_lfq.inc"
 #include "vq_rlfq.inc"
 #include "vq_fsq.inc"
+#include "vq_lq.inc"
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1834,6 +1837,56 @@ int vq_fsq_decode_f32(const void *idx, int idx_64, int64_t N, int Q, int d, cons
                       all_codes);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "vq_fsq_decode launch");
+    return 0;
+}
+
+int64_t vq_lq_workspace_bytes(int64_t B, int64_t P, int C) {
+    if (B < 1 || P < 1 || C < 1 || B > INT64_MAX / P || B * P > INT64_MAX / C) return 0;
+    return lq_blocks(B * P * C) * (int64_t)sizeof(float);
+}
+
+int vq_lq_quantize_f32(const float *z, int64_t z_bs, int64_t z_ps, int64_t z_cs, int64_t B, int64_t P, int C, int d,
+                       const int32_t *levels, const float *tables, float *codes, int64_t c_bs, int64_t c_ps, int64_t c_cs,
+                       int32_t *idx, float *loss, float w_c, float w_q, void *workspace, int64_t workspace_bytes,
+                       void *stream) {
+    FsqLevels lv;
+    int rc = fsq_check(1, 1, d, 1, levels, tables, lv, "vq_lq_quantize");
+    if (rc) return rc;
+    int n_table = 0;
+    rc = lq_check(B, P, C, d, levels, n_table, "vq_lq_quantize");
+    if (rc) return rc;
+    if (!z || !codes) return fail(VQ_E_BADARG, "vq_lq_quantize: null pointer");
+    const int64_t N = B * P * C;
+    const int64_t blocks = lq_blocks(N);
+    if (loss && (!workspace || workspace_bytes < blocks * (int64_t)sizeof(float)))
+        return fail(VQ_E_BADARG, "vq_lq_quantize: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    float *part = loss ? (float *)workspace : nullptr;
+    lq_launch_quantize(d, dim3((unsigned)blocks), s, z, LqStrides{z_bs, z_ps, z_cs}, P, C, N, lv, tables, n_table, codes,
+                       LqStrides{c_bs, c_ps, c_cs}, idx, part);
+    if (loss)
+        hipLaunchKernelGGL(lq_loss_kernel, dim3(1), dim3(kLqLossThreads), 0, s, part, blocks, (double)N * (double)d, w_c, w_q,
+                           loss);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "vq_lq_quantize launch");
+    return 0;
+}
+
+int vq_lq_backward_f32(const float *x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const float *out, int64_t o_bs, int64_t o_ps,
+                       int64_t o_cs, const float *g_out, int64_t g_bs, int64_t g_ps, int64_t g_cs, const float *g_loss,
+                       float coef, int64_t B, int64_t P, int W, float *grad_x, int64_t gx_bs, int64_t gx_ps, int64_t gx_cs,
+                       void *stream) {
+    if (B < 1 || P < 1 || W < 1) return fail(VQ_E_BADARG, "vq_lq_backward: sizes must be positive");
+    if (!x || !out || !g_out || !g_loss || !grad_x) return fail(VQ_E_BADARG, "vq_lq_backward: null pointer");
+    if (B > INT64_MAX / P || B * P > INT64_MAX / W || lq_blocks(B * P * W) > 0x7fffffff)
+        return fail(VQ_E_BADARG, "vq_lq_backward: too many elements");
+    const int64_t N = B * P * W;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(lq_backward_kernel, dim3((unsigned)lq_blocks(N)), dim3(kLqThreads), 0, s, x, LqStrides{x_bs, x_ps, x_cs},
+                       out, LqStrides{o_bs, o_ps, o_cs}, g_out, LqStrides{g_bs, g_ps, g_cs}, g_loss, coef, P, W, N, grad_x,
+                       LqStrides{gx_bs, gx_ps, gx_cs});
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "vq_lq_backward launch");
     return 0;
 }
 

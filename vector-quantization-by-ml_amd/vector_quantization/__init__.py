@@ -11,12 +11,15 @@ hand-written HIP for gfx950 behind the C ABI in ``include/vq_mi355x.h``; there i
 of 2^d codes -- in HIP as well, and so do ``ResidualLFQ`` / ``GroupedResidualLFQ`` (every stage's quantize step in one
 fused pass, every stage's entropy terms in one stage-batched call).  ``FSQ`` (finite scalar quantization) and
 ``ResidualFSQ`` / ``GroupedResidualFSQ`` run bound, round, index and every residual stage of every group in one HIP pass,
-and their backward in one more.  The reference's latent quantization (``LatentQuantize``) is not part of this build.
+and their backward in one more.  ``LatentQuantize`` (latent quantization: every latent dimension against its own learnable
+table of values) runs the per-dimension level search, the straight-through value, the index and the squared-error loss
+in one HIP pass over the caller's channel-first tensor.
 """
 from . import ops  # noqa: F401  (registers torch.ops.vq_mi355x.*)
 from .codebook import Codebook
 from .finite_scalar_quantization import FSQ
 from .graphs import GraphedForward
+from .latent_quantization import LatentQuantize
 from .lookup_free_quantization import LFQ
 from .params import AffineParameters, CodebookParams, GumbelParams, KmeansParameters
 from .projection import RandomProjectionQuantizer
@@ -38,6 +41,7 @@ __all__ = [
     "GumbelParams",
     "KmeansParameters",
     "LFQ",
+    "LatentQuantize",
     "LossBreakdown",
     "RandomProjectionQuantizer",
     "ResidualFSQ",

@@ -179,6 +179,14 @@ def load():
         lib.vq_fsq_decode_f32.argtypes = [_vp, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp,
                                           _vp]
         lib.vq_fsq_decode_f32.restype = ctypes.c_int
+        lib.vq_lq_workspace_bytes.argtypes = [_i64, _i64, ctypes.c_int]
+        lib.vq_lq_workspace_bytes.restype = _i64
+        lib.vq_lq_quantize_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64,
+                                           _i64, _i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _i64, _vp]
+        lib.vq_lq_quantize_f32.restype = ctypes.c_int
+        lib.vq_lq_backward_f32.argtypes = [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
+                                           ctypes.c_float, _i64, _i64, ctypes.c_int, _vp, _i64, _i64, _i64, _vp]
+        lib.vq_lq_backward_f32.restype = ctypes.c_int
         lib.vq_device_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         lib.vq_device_info.restype = ctypes.c_int
         _lib = lib
@@ -196,6 +204,7 @@ EXPORTED_SYMBOLS = (
     "vq_lfq_staged_workspace_bytes", "vq_lfq_entropy_staged_fwd_f32", "vq_lfq_entropy_staged_bwd_f32",
     "vq_rlfq_workspace_bytes", "vq_rlfq_quantize_f32", "vq_rlfq_backward_f32",
     "vq_fsq_quantize_f32", "vq_fsq_backward_f32", "vq_fsq_decode_f32",
+    "vq_lq_workspace_bytes", "vq_lq_quantize_f32", "vq_lq_backward_f32",
 )
 
 
@@ -1030,3 +1039,80 @@ def fsq_decode(indices: torch.Tensor, levels, scales: torch.Tensor, *, drop_null
                                      all_codes.data_ptr() if all_codes is not None else None, _stream_ptr(dev)),
                "vq_fsq_decode_f32")
     return codes_sum, all_codes
+
+
+# ------------------------------------------------------------------------------------------------
+# latent quantization (vq_lq_* in include/vq_mi355x.h)
+# ------------------------------------------------------------------------------------------------
+LQ_MAX_DIM = 16
+LQ_MAX_TABLE_FLOATS = 4096
+
+
+def _lq_strides(t: torch.Tensor):
+    """t [B, P, W] fp32 (any strides) -> (batch, position, channel) strides in elements."""
+    assert t.dim() == 3 and t.dtype == torch.float32, "expected a [B, P, W] fp32 tensor"
+    return int(t.stride(0)), int(t.stride(1)), int(t.stride(2))
+
+
+def lq_quantize(z: torch.Tensor, levels, tables: torch.Tensor, num_codebooks: int = 1, *, want_idx: bool = True,
+                loss_weights=None, out: torch.Tensor | None = None):
+    """The level search over z [B, P, C * d] (any strides: a permuted view of a channel-first tensor is taken as it lies)
+    -> (codes [B, P, C * d] (the caller's view when given, else contiguous), idx [B, P, C] int32 or None, loss or None).
+    tables: device fp32 [sum(levels)], the d value tables back to back.  loss_weights (w_c, w_q): also the fused
+    squared-error loss, a device fp32 [2] = (w_c * m + w_q * m, m) with m the mean of (codes - z)^2."""
+    _require_gpu(z, tables)
+    lib = load()
+    B, P, W = z.shape
+    C = int(num_codebooks)
+    d = len(levels)
+    dev = z.device
+    assert W == C * d, "z's last dim must be num_codebooks * len(levels)"
+    assert tables.dtype == torch.float32 and tables.dim() == 1 and tables.is_contiguous()
+    assert tables.numel() == sum(int(v) for v in levels), "tables must hold sum(levels) floats"
+    zs = _lq_strides(z)
+    if out is None:
+        out = torch.empty((B, P, W), dtype=torch.float32, device=dev)
+    assert out.shape == z.shape
+    os_ = _lq_strides(out)
+    idx = torch.empty((B, P, C), dtype=torch.int32, device=dev) if want_idx else None
+    loss = ws = None
+    w_c = w_q = 0.0
+    if loss_weights is not None:
+        w_c, w_q = float(loss_weights[0]), float(loss_weights[1])
+        loss = torch.empty((2,), dtype=torch.float32, device=dev)
+    if B * P == 0:
+        if loss is not None:
+            loss.fill_(float("nan"))  # the mean over no element
+        return out, idx, loss
+    if loss is not None:
+        ws = torch.empty((int(lib.vq_lq_workspace_bytes(B, P, C)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.vq_lq_quantize_f32(z.data_ptr(), *zs, B, P, C, d, _levels_arg(levels), tables.data_ptr(), out.data_ptr(),
+                                      *os_, idx.data_ptr() if idx is not None else None,
+                                      loss.data_ptr() if loss is not None else None, w_c, w_q,
+                                      ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
+                                      _stream_ptr(dev)), "vq_lq_quantize_f32")
+    return out, idx, loss
+
+
+def lq_backward(x: torch.Tensor, out: torch.Tensor, g_out: torch.Tensor, g_loss: torch.Tensor, coef: float,
+                grad_x: torch.Tensor | None = None) -> torch.Tensor:
+    """grad_x = g_out + (g_loss * coef) * (out - x) over [B, P, W] fp32 tensors of any strides (g_loss a device scalar);
+    grad_x is laid out as x unless given."""
+    _require_gpu(x, out, g_out, g_loss)
+    lib = load()
+    B, P, W = x.shape
+    dev = x.device
+    assert out.shape == x.shape and g_out.shape == x.shape
+    g_out = g_out.to(torch.float32)
+    g_loss = g_loss.to(torch.float32).reshape(1)
+    if grad_x is None:
+        grad_x = torch.empty_like(x)  # x's strides when they are dense, else contiguous
+    if x.numel() == 0:
+        return grad_x
+    with torch.cuda.device(dev):
+        _check(lib.vq_lq_backward_f32(x.data_ptr(), *_lq_strides(x), out.data_ptr(), *_lq_strides(out), g_out.data_ptr(),
+                                      *_lq_strides(g_out), g_loss.data_ptr(), float(coef), B, P, W, grad_x.data_ptr(),
+                                      *_lq_strides(grad_x), _stream_ptr(dev)), "vq_lq_backward_f32")
+    return grad_x
+

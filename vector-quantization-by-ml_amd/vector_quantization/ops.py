@@ -11,6 +11,7 @@ instead of breaking the graph at an opaque Python call:
     torch.ops.vq_mi355x.rlfq_quantize / rlfq_backward / lfq_entropy_staged_fwd / lfq_entropy_staged_bwd
         (residual LFQ, native.rlfq_* and native.lfq_entropy_staged_*)
     torch.ops.vq_mi355x.fsq_quantize / fsq_backward / fsq_decode   (finite scalar quantization, native.fsq_*)
+    torch.ops.vq_mi355x.lq_quantize / lq_backward   (latent quantization, native.lq_*)
 
 Eager forwards keep calling ``native.quantize`` directly (a custom-op dispatch costs tens of microseconds of host time,
 which is most of a small launch); the modules switch to these ops only while being compiled
@@ -211,3 +212,38 @@ def _(indices, levels, scales, drop_null, want_sum, want_all):
     N, Q = indices.shape
     d = len(levels)
     return scales.new_empty((N, d) if want_sum else (0,)), scales.new_empty((Q, N, d) if want_all else (0,))
+
+
+# latent quantization (native.lq_*).  z [B, P, C * d] of any strides; the codes come back laid out as z; indices or a loss
+# that were not requested come back as empty tensors.
+@torch.library.custom_op(f"{_LIB_NS}::lq_quantize", mutates_args=())
+def lq_quantize(z: torch.Tensor, levels: list[int], tables: torch.Tensor, num_codebooks: int, want_idx: bool, want_loss: bool,
+                w_c: float, w_q: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """z [B, P, C * d] -> (codes [B, P, C * d], idx [B, P, C] int32 (or empty), loss [2] = (weighted, mean) (or empty))."""
+    out = torch.empty_like(z)
+    _, idx, loss = native.lq_quantize(z, levels, tables, num_codebooks, want_idx=want_idx,
+                                      loss_weights=(w_c, w_q) if want_loss else None, out=out)
+    if idx is None:
+        idx = z.new_empty((0,), dtype=torch.int32)
+    if loss is None:
+        loss = z.new_empty((0,))
+    return out, idx, loss
+
+
+@lq_quantize.register_fake
+def _(z, levels, tables, num_codebooks, want_idx, want_loss, w_c, w_q):
+    B, P, _ = z.shape
+    return (torch.empty_like(z), z.new_empty((B, P, num_codebooks) if want_idx else (0,), dtype=torch.int32),
+            z.new_empty((2,) if want_loss else (0,)))
+
+
+@torch.library.custom_op(f"{_LIB_NS}::lq_backward", mutates_args=())
+def lq_backward(x: torch.Tensor, out: torch.Tensor, g_out: torch.Tensor, g_loss: torch.Tensor, coef: float) -> torch.Tensor:
+    """g_out + (g_loss * coef) * (out - x) (native.lq_backward), laid out as x."""
+    grad_x = torch.empty_like(x)
+    return native.lq_backward(x, out, g_out, g_loss, coef, grad_x=grad_x)
+
+
+@lq_backward.register_fake
+def _(x, out, g_out, g_loss, coef):
+    return torch.empty_like(x)
