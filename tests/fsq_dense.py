@@ -6,6 +6,9 @@ sum uses for a row of d <= 7 values, truncated to int32).
     restate(kind, kwargs, sd, x, r, stages)  -> dict(out, grad): the module's forward in fp64, dL/dx of (out * r).sum()
     indices_np(codes, levels)             codes [..., d] fp32 numpy -> int32 indices (fp32 arithmetic, torch's order)
     torch_sum_order_np(t)                 t [..., d] fp32 -> the fp32 sum in that order
+    levels_for(d), sweep_input(rows, width, seed, scale), whole_terms(codes, levels), exact_indices(codes, levels)
+                                          the levels and inputs of the every-d sweeps, their order-free rows and the
+                                          integer index
 """
 from __future__ import annotations
 
@@ -129,3 +132,44 @@ def indices_np(codes, levels):
         ok = (s >= -2147483648.0) & (s < 2147483648.0)
         out = np.where(ok, np.trunc(np.where(ok, s, 0)), -2147483648).astype(np.int64)
     return out.astype(np.int32)
+
+
+def levels_for(d):
+    """The levels of the every-d sweeps (tests/test_gpu_fsq_dims.py and its host self-check), d = 1 .. 16: every level is
+    at most 25, where fl(fl(k / hw) * hw) == k for every code k, so every index term is a whole number; the codebook stays
+    at most 2^24 (504 000 up to d = 7, 60 * 2^(d - 3) above), so the terms sum exactly in any order."""
+    assert 1 <= d <= 16
+    if d <= 7:
+        return [8, 5, 7, 6, 25, 3, 4][:d]
+    levels = [2] * d
+    levels[0], levels[d // 2], levels[d - 1] = 5, 4, 3
+    return levels
+
+
+def sweep_input(rows, width, seed, scale=2.0):
+    """randn * scale, fp32 [rows, width], the same values on every machine (torch's CPU generator)."""
+    return (torch.randn(rows, width, generator=torch.Generator().manual_seed(seed)) * scale).numpy()
+
+
+def terms_np(codes, levels):
+    codes = np.asarray(codes, dtype=np.float32)
+    hw = np.array([v // 2 for v in levels], dtype=np.float32)
+    basis = np.cumprod([1] + list(levels[:-1])).astype(np.int64).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        return (((codes * hw).astype(np.float32) + hw).astype(np.float32) * basis).astype(np.float32)
+
+
+def whole_terms(codes, levels):
+    """Rows whose every index term is a whole number while the codebook holds at most 2^24 codes: their fp32 sum is exact
+    in any order."""
+    t = terms_np(codes, levels)
+    with np.errstate(invalid="ignore"):
+        whole = np.isfinite(t) & (t == np.trunc(t))
+    return whole.all(axis=-1) & (int(np.prod(np.array(levels, dtype=np.int64))) <= 2**24)
+
+
+def exact_indices(k, levels):
+    """k [..., d] integer codes in [-hw, L - 1 - hw] -> sum_i (k_i + hw_i) * basis_i in int64."""
+    hw = np.array([v // 2 for v in levels], dtype=np.int64)
+    basis = np.cumprod([1] + list(levels[:-1])).astype(np.int64)
+    return ((np.asarray(k, dtype=np.int64) + hw) * basis).sum(axis=-1)

@@ -12,13 +12,16 @@ computes), and an fp64 forward / loss / gradient.
                                          is exact in any order
     smallest_gap(z, tables)              per sub-row, the smallest difference between the two smallest distances of any dim
     restate64(kwargs, sd, x, r, train)   the module's forward in fp64 -> dict(out, loss, grad of (out * r).sum() + loss)
+    levels_for(d), learned_tables(levels, seed), sweep_input(rows, width, seed)
+                                         the levels, trained-looking tables and inputs of the every-d sweeps
+    nearest64(z, tables)                 the fp64 nearest table value per element
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from fsq_dense import torch_sum_order_np
+from fsq_dense import sweep_input as fsq_sweep_input, torch_sum_order_np
 
 
 def levels_of(kwargs):
@@ -85,6 +88,48 @@ def smallest_gap(z, tables):
             dist = np.sort(np.abs(z[..., i, None] - np.asarray(tab, dtype=np.float64)), axis=-1)
             gap = np.minimum(gap, dist[..., 1] - dist[..., 0])
     return gap
+
+
+def levels_for(d):
+    """The levels of the every-d sweeps (tests/test_gpu_lq_dims.py and its host self-check), d = 1 .. 16.  d <= 7: levels 6
+    and 7 are in, so that terms that are not whole numbers meet the pinned torch order.  d >= 8: only levels whose default
+    tables are dyadic (2, 3, 4, 5, 8), so that z + (q - z) is q, every term a whole number and the sum exact in any order;
+    the codebook stays at 480 * 2^(d - 4) <= 2^21 entries."""
+    assert 1 <= d <= 16
+    if d <= 7:
+        return [5, 8, 3, 6, 7, 4, 2][:d]
+    levels = [2] * d
+    levels[0], levels[3], levels[d // 2], levels[d - 1] = 5, 8, 4, 3
+    return levels
+
+
+def learned_tables(levels, seed):
+    """Tables as training leaves them: the default values + 0.01 * randn, shuffled, one value of each table duplicated."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for tab in default_tables(levels):
+        t = (tab + np.float32(0.01) * rng.standard_normal(len(tab)).astype(np.float32)).astype(np.float32)
+        rng.shuffle(t)
+        a, b = rng.choice(len(t), 2, replace=False)
+        t[b] = t[a]
+        out.append(t)
+    return out
+
+
+def sweep_input(rows, width, seed):
+    """randn * 0.5, fp32 [rows, width], the same values on every machine (torch's CPU generator)."""
+    return fsq_sweep_input(rows, width, seed, 0.5)
+
+
+def nearest64(z, tables):
+    """The table value nearest to every z[..., i] in fp64 (the first one on an exact tie)."""
+    z = np.asarray(z, dtype=np.float64)
+    q = np.empty_like(z)
+    for i, tab in enumerate(tables):
+        t = np.asarray(tab, dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            q[..., i] = t[np.argmin(np.abs(z[..., i, None] - t), axis=-1)]
+    return q
 
 
 def restate64(kwargs, sd, x, r, train, tables=None):

@@ -310,3 +310,33 @@ def test_dropout_cut_sequence():
         cut = -(-(cut + 1) // 2) * 2 - 1
         assert m._dropout_cut(seed) == cut
     assert m.eval()._dropout_cut(3) is None
+
+
+@pytest.mark.parametrize("d", range(1, 17))
+def test_sweep_recipe_against_the_cpu_helpers(d):
+    """The oracle of tests/test_gpu_fsq_dims.py checked on the CPU: with levels_for(d) and the sweep's inputs every index
+    term of the CPU module's codes is a whole number (so the sum is exact in any order), the numpy index model and the
+    int64 index both equal the module's codes_to_indices, and fewer than 1 % of the rows lie within 1e-5 of a rounding
+    boundary at any stage of Q = 1 and of Q = 3."""
+    from fsq_dense import chain64, exact_indices, levels_for, sweep_input, whole_terms
+
+    from vector_quantization import FSQ
+
+    levels = levels_for(d)
+    assert max(levels) <= 25 and int(np.prod(np.array(levels, dtype=np.int64))) <= 2**24
+    x = torch.from_numpy(sweep_input(20011, d, d))
+    mod = FSQ(levels)
+    codes = mod.quantize(x)
+    want = mod.codes_to_indices(codes).numpy()
+    keep = whole_terms(codes.numpy(), levels)
+    assert keep.all()
+    assert np.array_equal(indices_np(codes.numpy(), levels), want)
+    k = np.rint(codes.numpy().astype(np.float64) * np.array([v // 2 for v in levels]))
+    assert np.array_equal(exact_indices(k, levels), want.astype(np.int64))
+    lv = torch.tensor(levels, dtype=torch.float32)
+    for Q, prebound in ((1, False), (3, True)):
+        scales = torch.stack([(lv - 1) ** -q for q in range(Q)]).double()
+        _, margin = chain64(x.double(), levels, scales, prebound)
+        left_out = float((margin < 1e-5).double().mean())
+        print(f"d={d} Q={Q}: {left_out:.4%} of rows within 1e-5 of a rounding boundary")
+        assert left_out < 0.01

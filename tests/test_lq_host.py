@@ -346,3 +346,41 @@ def test_cabi_argument_validation():
         assert bw(**kw) == -1 and "null" in err()
     for kw in (dict(B=0), dict(P=0), dict(W=0)):
         assert bw(**kw) == -1 and "positive" in err()
+
+
+SWEEP_ROWS = 20011
+
+
+@pytest.mark.parametrize("tables", ["default", "learned"])
+@pytest.mark.parametrize("d", range(1, 17))
+def test_sweep_recipe_against_the_cpu_helpers(d, tables):
+    """The oracle of tests/test_gpu_lq_dims.py checked on the CPU: with levels_for(d) and the sweep's inputs the numpy fp32
+    model equals the module's CPU helpers (quantize and codes_to_indices, the reference's arithmetic) bitwise, on every row
+    for d <= 7 and on the order-free rows for d >= 8, and the shares of rows the GPU tests leave out stay under their caps
+    (1 % within 1e-6 of a tie; with default tables at d >= 8 at least 99 % order-free)."""
+    from lq_dense import default_tables, learned_tables, levels_for, sweep_input
+
+    from vector_quantization import LatentQuantize
+
+    levels = levels_for(d)
+    size = int(np.prod(np.array(levels, dtype=np.int64)))
+    assert size <= 2**24 and (d <= 7 or set(levels) <= {2, 3, 4, 5, 8}) and (d < 4 or d > 7 or 6 in levels)
+    tabs = default_tables(levels) if tables == "default" else learned_tables(levels, 100 + d)
+    z = sweep_input(SWEEP_ROWS, d, d)
+    mod = LatentQuantize(levels=levels, dim=d)
+    with torch.no_grad():
+        for p, t in zip(mod.values_per_latent, tabs):
+            p.copy_(torch.from_numpy(t))
+        want = mod.quantize(torch.from_numpy(z))
+        want_idx = mod.codes_to_indices(want).numpy()
+    codes, _ = quantize_np(z, tabs)
+    assert np.array_equal(codes.view(np.uint32), want.numpy().view(np.uint32))
+    keep = np.ones(SWEEP_ROWS, dtype=bool) if d <= 7 else order_free(codes, levels)
+    got_idx = indices_np(codes, levels)
+    assert got_idx.dtype == want_idx.dtype == np.int32
+    assert np.array_equal(got_idx[keep], want_idx[keep])
+    near_tie = float((smallest_gap(z, [np.unique(t) for t in tabs]) < 1e-6).mean())
+    print(f"d={d} {tables}: {1 - keep.mean():.4%} of rows not order-free, {near_tie:.4%} within 1e-6 of a tie")
+    assert near_tie <= 0.01
+    if tables == "default" and d >= 8:
+        assert keep.mean() >= 0.99

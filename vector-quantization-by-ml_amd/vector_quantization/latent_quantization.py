@@ -253,7 +253,21 @@ class LatentQuantize(Module):
         """Converts a `code` which contains the number per latent to an index in the codebook."""
         assert zhat.shape[-1] == self.codebook_dim
         zhat = self._scale_and_shift(zhat)
-        index = (zhat * self._basis).sum(dim=-1)
+        terms = zhat * self._basis
+        if terms.is_cuda and terms.dtype == torch.float32 and terms.shape[-1] <= 7:
+            # torch's GPU sum chooses its order by shape and strides (d = 6 with three codebooks on channel-first rows
+            # gave other indices than the same codes laid out otherwise); the reference's values are those of torch's
+            # CPU order, which for fp32 and d <= 7 is term 0, terms 4 .. d - 1, then terms 1, 2, 3 (DESIGN.md section
+            # 12).  Other dtypes keep torch.sum: it accumulates bf16 / fp16 in fp32 and rounds once, which a chain of
+            # half-precision additions would not, and the CPU order was established for fp32 only
+            t = terms.unbind(dim=-1)
+            index = t[0]
+            for i in range(4, len(t)):
+                index = index + t[i]
+            for i in range(1, min(len(t), 4)):
+                index = index + t[i]
+        else:
+            index = terms.sum(dim=-1)
         # NaN -> INT32_MIN, what the reference's CPU cast gives (a GPU cast does not promise it)
         return torch.where(index.isnan(), torch.iinfo(int32).min, index.to(int32))
 
