@@ -246,7 +246,7 @@ int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s) {
     auto kern = vq_search_persist<256, 8, METRIC, TRAIN, SCREEN>;
     if constexpr (SCREEN) {  // the bf16x3 images of this call's codebooks, from their fp32 packed images
         hipLaunchKernelGGL(vq_pack_scr_kernel<256>, dim3((unsigned)p.ntiles, (unsigned)H), dim3(256), 0, s, p.packed, p.pk_hs, p.K,
-                           p.ntiles, (char *)p.scr, p.scr_hs);
+                           p.ntiles, (char *)p.scr, p.scr_hs, p.scr_count);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "vq_pack_scr launch");
     }
@@ -256,6 +256,16 @@ int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)H, 1), dim3(512), lds, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "vq_search_persist launch");
+    if constexpr (SCREEN) {
+        // second pass: the listed rows, in stream order behind the sweep.  One workgroup per CU: the few rows of a usual call
+        // (tens) take one round, and a workgroup that finds no entry for itself ends after one load of the count.
+        auto rkern = vq_resolve_rows_kernel<256>;
+        static thread_local bool attr_done_r[kMaxDevices] = {};
+        if (int rc = allow_big_lds(rkern, attr_done_r)) return rc;
+        hipLaunchKernelGGL(rkern, dim3((unsigned)(cus > 0 ? cus : 1)), dim3(kResolveWaves * 64), resolve_lds_bytes<256>(), s, p, H);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "vq_resolve_rows launch");
+    }
     return 0;
 }
 
@@ -536,19 +546,22 @@ bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 // The screened sweep (vq_search_persist.inc, SCREEN) for a call the persistent kernel takes: Euclid, fp32 rows, inference
 // (no straight-through / loss), no winning distances requested.  Its bf16x3 images are built per call into the key area of
-// the workspace, which a fused call does not use; a call whose images do not fit there keeps the fp32 sweep.  Sets p.scr (or
-// leaves it NULL).  VQ_NO_SCREEN in the environment keeps the fp32 sweep (read per call: tests compare both in one process).
+// the workspace, which a fused call does not use, and behind them the list of rows that the second pass searches in full
+// (vq_resolve_rows_kernel); a call whose images and list do not fit there keeps the fp32 sweep.  Sets p.scr (or leaves it NULL).  VQ_NO_SCREEN in the environment keeps the fp32 sweep (read per call: tests compare both in one process).
 long long ws_keys_bytes(int H, long long M);
 void screen_image_for(SearchParams &p, const vq_args *a, int DP, int waves, int cus) {
     p.scr = nullptr;
     if (getenv("VQ_NO_SCREEN") != nullptr) return;
     if (a->metric != VQ_METRIC_EUCLID || p.xt || p.ste || p.loss_part || p.best || p.lse) return;
     if (!persist_selected(DP, waves, p, a->H, 1, cus)) return;
-    const long long img = scr_image_bytes(p.ntiles);
-    if (!a->workspace || (long long)a->H * img > ws_keys_bytes(a->H, a->M) || img >= (1ll << 31)) return;
+    const long long img = scr_image_bytes(p.ntiles), rows = (long long)a->H * a->M;
+    // [images][count, 256 B][list of rows for the second pass: one uint32 per row of the call]
+    if (!a->workspace || (long long)a->H * img + 256 + 4 * rows > ws_keys_bytes(a->H, a->M) || img >= (1ll << 31) || rows >= (1ll << 31)) return;
     p.scr = (const float *)a->workspace;
     p.scr_hs = img;
     p.scr_bytes = (unsigned)img;
+    p.scr_count = (unsigned *)((char *)a->workspace + (long long)a->H * img);
+    p.scr_list = p.scr_count + 64;
 }
 
 // Small codebook, plain inference call (one stage, no straight-through / loss / LSE, aligned fp32 rows of D % 16 == 0 dims,
@@ -1014,7 +1027,7 @@ int vq_debug_read_stamps(unsigned long long *host, size_t n) {  // diagnostic bu
 #endif
 
 #ifdef VQ_EXP_SCREEN_COUNT
-int vq_debug_screen_rows(unsigned long long *host2, int reset) {  // diagnostic build only (single translation unit): {rows searched in full, rows, rows rescored}
+int vq_debug_screen_rows(unsigned long long *host2, int reset) {  // diagnostic build only (single translation unit): {rows listed for the full search of the second pass, rows, rows rescored}
     hipError_t e = hipMemcpyFromSymbol(host2, HIP_SYMBOL(g_scr_rows), 3 * sizeof(unsigned long long));
     if (e == hipSuccess && reset) {
         const unsigned long long z[3] = {0, 0, 0};

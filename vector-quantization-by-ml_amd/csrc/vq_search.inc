@@ -52,6 +52,10 @@ struct SearchParams {
     const float *scr;
     long long scr_hs;
     unsigned scr_bytes;
+    // rows the screen cannot bound: `*scr_count` entries head * M + row in `scr_list` (room for all H M rows), behind the
+    // images; the count is zeroed by vq_pack_scr_kernel, the entries are searched in full by vq_resolve_rows_kernel
+    unsigned *scr_count;
+    unsigned *scr_list;
 };
 }  // namespace vqi
 namespace {

@@ -24,7 +24,8 @@
 // screened values of its codes over distinct codes, and the codes of the two lowest.  A row whose two lowest screened values
 // are further apart than the bound below can only have the screened winner as its exact winner.  The other rows rescore
 // their few candidates by the exact chain (exact_pair_euclid), or, when a lane half holds more candidates than it tracks,
-// are searched again in full (exact_rows_euclid).  Results are those of the fp32 kernel bit for bit.
+// are put on a list and searched again in full by a second kernel on the same stream (vq_resolve_rows_kernel, which runs
+// exact_row_euclid).  Results are those of the fp32 kernel bit for bit.
 //
 // The bound.  u = 2^-24; for a row x (fp32 chain xn = d-ordered sum of squares) and code c (fp32 chain cn), c' = -2c as
 // packed (exact), Q = sum_k x_k c'_k in real arithmetic, nx = sqrt(xn), nc = sqrt(max cn) over the codebook, L = 2 nx nc.
@@ -74,10 +75,13 @@ __device__ __forceinline__ void split_bf16x2(const f32x8 &v, bf16x8 &hi, bf16x8 
 // the padding rows).  Per 32-code tile: row c at c * 1040 bytes, for each group s of 16 dims hi[16s .. 16s+7], hi[16s+8 ..
 // 16s+15], lo[16s ..], lo[16s+8 ..] (16 B each: one ds_read_b128 is one MFMA's A fragment), then the 32 |c|^2 of the tile;
 // behind the tiles the maximum |c|^2 of each tile's real codes.  Grid (tiles, heads), 256 threads: 8 per code.
+// One thread also zeroes the count of the call's list of rows for the second pass (vq_resolve_rows_kernel).
 template <int DP>
 __global__ void __launch_bounds__(256) vq_pack_scr_kernel(const float *__restrict__ packed, long long pk_hs, int K, int ntiles,
-                                                          char *__restrict__ img, long long img_hs) {
+                                                          char *__restrict__ img, long long img_hs, unsigned *__restrict__ list_count) {
     static_assert(DP == 256, "the screened sweep is built for Dp = 256");
+    // first on the stream in every screened call: the list of rows for the second pass starts empty
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *list_count = 0u;
     constexpr int RS = DP + 4;
     const int t = blockIdx.x, c = threadIdx.x >> 3, part = threadIdx.x & 7;
     const int k = t * kTileCodes + c;
@@ -115,108 +119,175 @@ __global__ void __launch_bounds__(256) vq_pack_scr_kernel(const float *__restric
     }
 }
 
-// The exact rule (oracle/vq_oracle.c; repair_nonfinite_rows) for the rows of `todo`, Euclid: one row at a time, the row in
-// wave-private LDS, the 64 lanes stride over the codes TWO at a time (k, k + 64: two k-ordered fmaf chains in one v_pk_fma_f32,
-// bit for bit the scalar chains), the 16 code values of 8 dims of both codes loaded 16 dims ahead of their use so that the
-// L2 latency of the packed image overlaps the arithmetic.  First NaN, else first minimum of the correctly rounded sqrt, then
-// the 6-step butterfly (NaN first, value, index).  `xn_of(rr)` = the row's d-ordered |x|^2 chain.
-template <int DP, typename FillRow, typename XnOf>
-__device__ __forceinline__ void exact_rows_euclid(unsigned todo, float *rowbuf, const float *pk, int K, int lane, FillRow fill_row,
-                                                  XnOf xn_of, float &best_s, int &best_i) {
-    constexpr int RS = DP + 4;
-    constexpr int GC = 2;  // 8-dim groups per chunk
-    const int c = lane & 31;
-    while (todo) {
-        const int rr = __builtin_ctz(todo);  // wave-uniform
-        todo &= todo - 1;
-        fill_row(rr);
-        const float xn = xn_of(rr);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        float bv = __builtin_inff();
-        int bi = (lane < K) ? lane : 0x7FFFFFFF;
-        bool bn = false;
+// The exact rule (oracle/vq_oracle.c; repair_nonfinite_rows) for ONE row and the codes kbeg <= k < kend, Euclid, by one wave,
+// 64 codes at a time, one per lane: the k-ordered fmaf chain over the dims, + |x|^2, + |c|^2, clamp_min(0), correctly rounded
+// sqrt; first NaN, else first minimum, then the 6-step butterfly (NaN first, value, index): every lane returns the wave's
+// (bn = a NaN was met, bv, bi).  better_euclid is the order of that rule.  `rowbuf` = the row in LDS (Dp floats, zeros behind
+// D), `xn` = its d-ordered |x|^2 chain.
+// A lane walking its own code row of the packed image reads 16 B of a different cache line than every other lane: 64 tag
+// look-ups per load instruction, 66 k per row at K = 1024, which is what such a search costs (30 us on one CU, measured).
+// So the codes come through `stage` (wave-private LDS, 64 rows of kExStageRow floats), 32 dims at a time: 8 lanes load the
+// 128 B of one code, 8 codes per instruction, one chunk ahead of the arithmetic, and each lane reads its own code's 32 dims
+// back (20 us per row, measured; two codes per lane and 128 codes per pass were no faster).  LDS operations of one wave
+// execute in order, so the wave needs no barrier between its stores and loads.
+constexpr int kExChunk = 32;                // dims per staged chunk
+constexpr int kExStageRow = kExChunk + 4;   // floats per staged code (144 B: 16 lanes' ds_read_b128 cover the 64 banks once)
+constexpr int kExCodes = 64;                // codes per wave and pass
+__device__ __forceinline__ bool better_euclid(bool on, float ov, int oi, bool bn, float bv, int bi) {
+    if (on != bn) return on;
+    if (bn) return oi < bi;
+    return (ov < bv) || (ov == bv && oi < bi);
+}
+template <int DP>
+__device__ __forceinline__ void exact_row_euclid(const float *rowbuf, float *stage, const float *pk, int kbeg, int kend, int lane,
+                                                 float xn, bool &bn, float &bv, int &bi) {
+    constexpr int RS = DP + 4, CD = kExChunk, SR = kExStageRow, NCH = DP / CD, NL = kExCodes / 8;
+    static_assert(DP % CD == 0, "whole chunks");
+    bv = __builtin_inff();
+    bi = (kbeg + lane < kend) ? kbeg + lane : 0x7FFFFFFF;
+    bn = false;
+    const int piece = lane & 7, sub = lane >> 3;  // this lane loads float4 `piece` of the chunk of codes kb + sub + 8 i
+    const float *cr = stage + lane * SR;
 #pragma clang loop unroll(disable)
-        for (int k0 = lane; k0 < K; k0 += 128) {
-            const int k1 = k0 + 64;
-            const bool ok1 = k1 < K;
-            const float *p0 = pk + (long long)k0 * RS;
-            const float *p1 = pk + (long long)(ok1 ? k1 : k0) * RS;
-            f32x2 acc = {0.0f, 0.0f};
-            f32x4 e0[GC], o0[GC], e1[GC], o1[GC];
+    for (int kb = kbeg; kb < kend; kb += kExCodes) {  // (wave-uniform)
+        const int k = kb + lane;
+        const bool ok = k < kend;
+        const float *src[NL];
 #pragma unroll
-            for (int g = 0; g < GC; ++g) {
-                e0[g] = *(const f32x4 *)(p0 + 8 * g); o0[g] = *(const f32x4 *)(p0 + 8 * g + 4);
-                e1[g] = *(const f32x4 *)(p1 + 8 * g); o1[g] = *(const f32x4 *)(p1 + 8 * g + 4);
-            }
+        for (int i = 0; i < NL; ++i) {
+            const int kk = kb + sub + 8 * i;
+            src[i] = pk + (long long)(kk < kend ? kk : kend - 1) * RS + 4 * piece;
+        }
+        f32x4 g[NL];
+#pragma unroll
+        for (int i = 0; i < NL; ++i) g[i] = *(const f32x4 *)(src[i]);
+        const float cn = pk[(long long)(ok ? k : kend - 1) * RS + DP];
+        float acc = 0.0f;
 #pragma clang loop unroll(disable)
-            for (int ch = 0; ch < DP / (8 * GC); ++ch) {
-                f32x4 ce0[GC], co0[GC], ce1[GC], co1[GC];
+        for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
-                for (int g = 0; g < GC; ++g) {
-                    ce0[g] = e0[g]; co0[g] = o0[g]; ce1[g] = e1[g]; co1[g] = o1[g];
-                }
-                if (ch + 1 < DP / (8 * GC)) {
+            for (int i = 0; i < NL; ++i) *(f32x4 *)(stage + (sub + 8 * i) * SR + 4 * piece) = g[i];
+            if (ch + 1 < NCH) {
 #pragma unroll
-                    for (int g = 0; g < GC; ++g) {
-                        const int gg = (ch + 1) * GC + g;
-                        e0[g] = *(const f32x4 *)(p0 + 8 * gg); o0[g] = *(const f32x4 *)(p0 + 8 * gg + 4);
-                        e1[g] = *(const f32x4 *)(p1 + 8 * gg); o1[g] = *(const f32x4 *)(p1 + 8 * gg + 4);
-                    }
-                }
-#pragma unroll
-                for (int g = 0; g < GC; ++g) {
-                    const int gg = ch * GC + g;
-                    const f32x4 xa = *(const f32x4 *)(rowbuf + 8 * gg), xb = *(const f32x4 *)(rowbuf + 8 * gg + 4);
-                    acc = __builtin_elementwise_fma((f32x2){xa.x, xa.x}, (f32x2){ce0[g].x, ce1[g].x}, acc);
-                    acc = __builtin_elementwise_fma((f32x2){xa.y, xa.y}, (f32x2){co0[g].x, co1[g].x}, acc);
-                    acc = __builtin_elementwise_fma((f32x2){xa.z, xa.z}, (f32x2){ce0[g].y, ce1[g].y}, acc);
-                    acc = __builtin_elementwise_fma((f32x2){xa.w, xa.w}, (f32x2){co0[g].y, co1[g].y}, acc);
-                    acc = __builtin_elementwise_fma((f32x2){xb.x, xb.x}, (f32x2){ce0[g].z, ce1[g].z}, acc);
-                    acc = __builtin_elementwise_fma((f32x2){xb.y, xb.y}, (f32x2){co0[g].z, co1[g].z}, acc);
-                    acc = __builtin_elementwise_fma((f32x2){xb.z, xb.z}, (f32x2){ce0[g].w, ce1[g].w}, acc);
-                    acc = __builtin_elementwise_fma((f32x2){xb.w, xb.w}, (f32x2){co0[g].w, co1[g].w}, acc);
-                }
+                for (int i = 0; i < NL; ++i) g[i] = *(const f32x4 *)(src[i] + (ch + 1) * CD);
             }
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                if (j == 1 && !ok1) break;
-                const int k = j ? k1 : k0;
-                float tt = fmaf(1.0f, xn, acc[j]);
-                tt = fmaf((j ? p1 : p0)[DP], 1.0f, tt);
-                tt = (tt < 0.0f) ? 0.0f : tt;  // clamp_min_(0): keeps NaN
-                const float s = sqrtf(tt);
-                if (!bn) {
-                    if (s != s) {
-                        bn = true;
-                        bv = s;
-                        bi = k;
-                    } else if (s < bv) {
-                        bv = s;
-                        bi = k;
-                    }
+            for (int q = 0; q < CD / 8; ++q) {
+                const f32x4 ce = *(const f32x4 *)(cr + 8 * q), co = *(const f32x4 *)(cr + 8 * q + 4);
+                const f32x4 xa = *(const f32x4 *)(rowbuf + ch * CD + 8 * q), xb = *(const f32x4 *)(rowbuf + ch * CD + 8 * q + 4);
+                acc = fmaf(xa.x, ce.x, acc);
+                acc = fmaf(xa.y, co.x, acc);
+                acc = fmaf(xa.z, ce.y, acc);
+                acc = fmaf(xa.w, co.y, acc);
+                acc = fmaf(xb.x, ce.z, acc);
+                acc = fmaf(xb.y, co.z, acc);
+                acc = fmaf(xb.z, ce.w, acc);
+                acc = fmaf(xb.w, co.w, acc);
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the chunk has been read: the next one may overwrite it
+        }
+        float tt = fmaf(1.0f, xn, acc);
+        tt = fmaf(cn, 1.0f, tt);
+        tt = (tt < 0.0f) ? 0.0f : tt;  // clamp_min_(0): keeps NaN
+        const float s = sqrtf(tt);
+        if (ok && !bn) {
+            if (s != s) {
+                bn = true;
+                bv = s;
+                bi = k;
+            } else if (s < bv) {
+                bv = s;
+                bi = k;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const bool on = __shfl_xor((int)bn, o) != 0;
+        const float ov = __shfl_xor(bv, o);
+        const int oi = __shfl_xor(bi, o);
+        if (better_euclid(on, ov, oi, bn, bv, bi)) {
+            bn = on;
+            bv = ov;
+            bi = oi;
+        }
+    }
+}
+
+// Second pass of the screened sweep: the rows it could not bound (list entries head * M + row, `*p.scr_count` of them, written
+// by vq_search_persist<.., SCREEN> earlier on the stream) searched again in full by the exact rule.  Grid-stride over the
+// entries, one 8-wave workgroup per entry at a time: the row staged in LDS once, its |x|^2 chain recomputed in the prologue's
+// order (d-ordered fmaf from 0), the waves split the K codes in runs of 64 (exact_row_euclid), the winner reduced over the
+// waves through LDS in the order of the rule; then idx and the quantized row are stored over the provisional ones.
+// Dynamic LDS only (the launcher raises the kernel's dynamic limit to the CU's 160 KiB, which leaves no room for static
+// arrays): [row, Dp floats][8 waves x 64 x kExStageRow floats of code staging][the waves' winners: 3 x 8 words].
+constexpr int kResolveWaves = 8;
+template <int DP>
+constexpr size_t resolve_lds_bytes() { return ((size_t)DP + kResolveWaves * kExCodes * kExStageRow + 3 * kResolveWaves) * 4; }
+template <int DP>
+__global__ void __launch_bounds__(kResolveWaves * 64) vq_resolve_rows_kernel(const SearchParams p, int H) {
+    constexpr int WAVES = kResolveWaves;
+    const unsigned cap = (unsigned)((long long)H * p.M);  // (screen_image_for: H M < 2^31, the list holds them all)
+    unsigned count = *p.scr_count;
+    if (count > cap) count = cap;
+    if (blockIdx.x >= count) return;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *rowbuf = smem;
+    float *red_v = smem + DP + WAVES * kExCodes * kExStageRow;
+    int *red_i = (int *)(red_v + WAVES), *red_n = red_i + WAVES;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    float *stage = smem + DP + wave * (kExCodes * kExStageRow);
+    const int per = ((p.K + WAVES - 1) / WAVES + kExCodes - 1) / kExCodes * kExCodes;  // codes per wave: whole passes
+    const int kbeg = wave * per < p.K ? wave * per : p.K, kend = kbeg + per < p.K ? kbeg + per : p.K;
+    for (unsigned e = blockIdx.x; e < count; e += gridDim.x) {
+        const unsigned ent = p.scr_list[e];
+        if (ent >= cap) continue;  // (workgroup-uniform; never true for a list the sweep wrote)
+        const int head = (int)(ent / (unsigned long long)p.M);
+        const long long row = (long long)ent - (long long)head * p.M;
+        const float *xr = p.x + (long long)head * p.x_hs + row * p.x_rs;
+        if (tid < DP) rowbuf[tid] = (tid < p.D) ? xr[tid] : 0.0f;
+        __syncthreads();
+        float xn = 0.0f;
+#pragma unroll 16
+        for (int d = 0; d < DP; d += 4) {
+            const f32x4 v = *(const f32x4 *)(rowbuf + d);
+            xn = fmaf(v.x, v.x, xn);
+            xn = fmaf(v.y, v.y, xn);
+            xn = fmaf(v.z, v.z, xn);
+            xn = fmaf(v.w, v.w, xn);
+        }
+        bool bn;
+        float bv;
+        int bi;
+        exact_row_euclid<DP>(rowbuf, stage, p.packed + (long long)head * p.pk_hs, kbeg, kend, lane, xn, bn, bv, bi);
+        if (lane == 0) {
+            red_n[wave] = (int)bn;
+            red_v[wave] = bv;
+            red_i[wave] = bi;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            bn = red_n[0] != 0;
+            bv = red_v[0];
+            bi = red_i[0];
+#pragma unroll
+            for (int w = 1; w < WAVES; ++w) {
+                const bool on = red_n[w] != 0;
+                const float ov = red_v[w];
+                const int oi = red_i[w];
+                if (better_euclid(on, ov, oi, bn, bv, bi)) {
+                    bn = on;
+                    bv = ov;
+                    bi = oi;
                 }
             }
+            if (lane == 0) p.idx[(long long)head * p.idx_hs + row * p.idx_rs] = bi;
+            const int dl = 4 * lane;
+            if (p.out && dl < p.D)  // (the persistent kernel's deferred copy: float4 of natural rows)
+                *(f32x4 *)(p.out + (long long)head * p.out_hs + row * p.out_rs + dl) =
+                    *(const f32x4 *)(p.cb + (long long)head * p.cb_hs + (long long)bi * p.D + dl);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int on = __shfl_xor((int)bn, o);
-            const float ov = __shfl_xor(bv, o);
-            const int oi = __shfl_xor(bi, o);
-            bool take;
-            if (on != (int)bn) take = on != 0;
-            else if (bn) take = oi < bi;
-            else take = (ov < bv) || (ov == bv && oi < bi);
-            if (take) {
-                bn = on != 0;
-                bv = ov;
-                bi = oi;
-            }
-        }
-        if (c == rr) {
-            best_s = bv;
-            best_i = bi;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the row buffer is rewritten by the next row
     }
 }
 
@@ -275,7 +346,7 @@ __device__ __forceinline__ f32x2 exact_pair_euclid(const float *xr, int D, const
 }
 
 #ifdef VQ_EXP_SCREEN_COUNT
-__device__ unsigned long long g_scr_rows[3];  // [0] rows searched again in full, [1] rows screened, [2] rows rescored
+__device__ unsigned long long g_scr_rows[3];  // [0] rows listed for the second pass, [1] rows screened, [2] rows rescored
 #endif
 
 // SCREEN: the screened sweep described above (Dp = 256, Euclid, no TRAIN); p.scr holds the bf16x3 images.
@@ -375,10 +446,16 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             }
         }
     };
+    // Diagnostic build (-DVQ_EXP_STAMPS; tools/stamps_persist.py): per wave and row block `it` < 14 the shader-clock time of
+    // block start, prologue end, sweep end and resolve end in slots 4 it .. 4 it + 3, the end of the open finalize in slot 56,
+    // the wave's block count in slot 57, the real-time pair in slots 60 / 61.
+#define PSTAMP(j) do { if (it < 14) STAMP(4 * it + (j)); } while (0)
     int it = 0;
     long long row0 = 0;
+    STAMP_RT(60);
     for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x, ++it) {
         row0 = ((long long)blk * WAVES + wave) * 32;
+        PSTAMP(0);
         // the sweep's first tile goes out before the rows are loaded: the tile buffers are free (the previous sweep ended with a
         // barrier) and the rows are staged behind them
         stage(0, 0);
@@ -589,6 +666,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             if (st == SUB - 1) __syncthreads();
         };
 
+        PSTAMP(1);
         __syncthreads();  // the first tile (issued before the prologue) has landed for every wave
         {
             f32x16 acc0, acc1;
@@ -609,6 +687,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         }
         // rows of the previous block the sweep did not get to (short sweeps), and the last store
         while (cp_next < cp_rows || cp_pend >= 0) copy_step();
+        PSTAMP(2);
 
         float best_s;
         int best_i;
@@ -635,7 +714,8 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             // Uncertain rows.  Only a code with S <= thr = b1 + 2 delta + w can beat or tie the exact winner (its D would
             // otherwise exceed the winner's by more than the sqrt rounding window, and `eligible` excludes clamping).  When
             // the third lowest value of BOTH lane halves is above thr, the row's candidates are among the <= 4 codes the
-            // halves hold: they are rescored by the exact chain (rescore), every other row is searched again in full.
+            // halves hold: they are rescored by the exact chain (rescore), every other row goes onto the list of rows that the
+            // second pass searches again in full (candidate overflow, NaN / inf rows, ineligible magnitudes, flagged codebooks).
             const float thr = b1 + 2.0f * delta + w;
             const bool complete = eligible && scr_b3 > thr && ob3 > thr;
             const unsigned rescore = (unsigned)__ballot(row_ok && !certain && complete);
@@ -668,13 +748,13 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
                 if (mine) best_i = bk;
             }
             if (todo != 0u) {
-                float *rowbuf = smem + G::NBUF * G::BUF_F4 * 4 + wave * (32 * XS);  // this wave's row staging region
-                auto fill_row = [&](int rr) {
-#pragma clang loop unroll(disable)
-                    for (int d = lane; d < DP; d += 64) rowbuf[d] = (d < p.D) ? xh[(row0 + rr) * p.x_rs + d] : 0.0f;
-                };
-                auto xn_of = [&](int rr) -> float { return __shfl(xn0, rr); };
-                exact_rows_euclid<DP>(todo, rowbuf, pk, p.K, lane, fill_row, xn_of, best_s, best_i);  // (lanes c and c + 32)
+                // onto the list of vq_resolve_rows_kernel, which stores their idx and quantized rows after this kernel; until
+                // then they keep the screened argmin (best_i < K: the deferred copy gathers a valid code row)
+                unsigned at = 0u;
+                if (lane == 0) at = atomicAdd(p.scr_count, (unsigned)__builtin_popcount(todo));
+                at = __builtin_amdgcn_readfirstlane(at);
+                if (h == 0 && ((todo >> c) & 1u))
+                    p.scr_list[at + __builtin_popcount(todo & ((1u << c) - 1u))] = (unsigned)((long long)head * p.M + row);
             }
         } else {
         resolve_best<METRIC>(lb, h, p.K, best_s, best_i);
@@ -700,6 +780,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             repair_nonfinite_rows<METRIC, DP>(todo, rowbuf, pk, 0, p.K, lane, fill_row, acc_init, best_s, best_i);
         }
         }
+        PSTAMP(3);
         if (h == 0 && row_ok) {
             const long long o = (long long)head * p.idx_hs + row * p.idx_rs;
             p.idx[o] = best_i;
@@ -743,4 +824,10 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             if (lane == 0) p.loss_part[((long long)head * gridDim.x + blockIdx.x) * WAVES + wave] = cp_e;
         }
     }
+    STAMP(56);
+    STAMP_RT(61);
+#ifdef VQ_EXP_STAMPS
+    if (lane == 0) g_stamps[(((long long)blockIdx.x * WAVES + wave) & 8191) * VQ_NSTAMP + 57] = (unsigned long long)it;
+#endif
+#undef PSTAMP
 }
