@@ -181,6 +181,8 @@ int vq_quantize_backward_f32(const vq_args *a, const float *grad_out, int64_t go
  *   Replaces embed_onehot.sum(1) and einsum("h n d, h n c -> h c d") -- codebooks.py:405-415 -- without the one-hot.
  * vq_ema_update_f32: cluster_size.lerp_(counts, 1-decay); embed_avg.lerp_(sums, 1-decay); embeddings =
  *   [l2norm](embed_avg / laplace_smoothing(cluster_size) * total) -- codebooks.py:411,417-425.  total_scratch: H floats.
+ *   decay is a double because the reference forms 1 - decay in double and rounds the WEIGHT to fp32 once: rounding decay
+ *   first moves the weight by up to u * decay / (1 - decay) (16 ulp of the weight at decay = 0.99).
  * The sums are exact up to fp32 summation order (float atomics / per-wave partial sums: run-to-run differences at the
  * 1e-7 relative level).
  */
@@ -200,7 +202,7 @@ int vq_ema_accumulate_det_f32(const float *x, int64_t x_rs, int64_t x_hs, const 
  * and VQ_F_STE (train-mode residual rule).  counts [H][Q][K], sums [H][Q][K][D], zeroed by the caller. */
 int vq_ema_accumulate_residual_f32(const vq_args *a, float *counts, float *sums, void *stream);
 int vq_ema_update_f32(float *cluster_size, float *embed_avg, float *embeddings, const float *counts, const float *sums,
-                      float *total_scratch, int H, int K, int D, float decay, float eps, int l2norm, void *stream);
+                      float *total_scratch, int H, int K, int D, double decay, float eps, int l2norm, void *stream);
 
 /*
  * Consumers of the similarity matrix.  Both use a->x, a->packed (a->cb for D > 512 / VQ_F_FORCE_SIMPLE),

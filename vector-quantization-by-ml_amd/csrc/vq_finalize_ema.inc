@@ -484,7 +484,8 @@ __global__ void __launch_bounds__(256) vq_ema_codes_kernel(const float *__restri
     if (l2norm) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) nrm += __shfl_xor(nrm, o);
-        const float inv = 1.0f / fmaxf(sqrtf(nrm), 1e-12f);
+        const float n = sqrtf(nrm);
+        const float inv = 1.0f / (n < 1e-12f ? 1e-12f : n);  // clamp_min keeps a NaN norm (fmaxf would drop it): the row is NaN
         for (int d = lane; d < D; d += 64) emb[d] = emb[d] * inv;  // same lane wrote it
     }
 }

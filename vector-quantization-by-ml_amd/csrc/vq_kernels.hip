@@ -1572,11 +1572,11 @@ int vq_ema_accumulate_residual_f32(const vq_args *a, float *counts, float *sums,
 }
 
 int vq_ema_update_f32(float *cluster_size, float *embed_avg, float *embeddings, const float *counts, const float *sums,
-                      float *total_scratch, int H, int K, int D, float decay, float eps, int l2norm, void *stream) {
+                      float *total_scratch, int H, int K, int D, double decay, float eps, int l2norm, void *stream) {
     if (!cluster_size || !embed_avg || !embeddings || !counts || !sums || !total_scratch || H <= 0 || K <= 0 || D <= 0)
         return fail(VQ_E_BADARG, "vq_ema_update: bad argument");
     hipStream_t s = (hipStream_t)stream;
-    const float weight = 1.0f - decay;
+    const float weight = (float)(1.0 - decay);  // lerp_(.., 1 - decay): the reference subtracts in double and rounds the weight once
     hipLaunchKernelGGL(vq_ema_sizes_kernel, dim3(H), dim3(256), 0, s, cluster_size, counts, K, weight, total_scratch);
     const long long rows = (long long)H * K;
     hipLaunchKernelGGL(vq_ema_codes_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, cluster_size, total_scratch,

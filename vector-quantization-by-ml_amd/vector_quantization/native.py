@@ -129,7 +129,7 @@ def load():
         lib.vq_ema_det_workspace_bytes.argtypes = [ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int]
         lib.vq_ema_det_workspace_bytes.restype = _i64
         lib.vq_ema_update_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_float, ctypes.c_float, ctypes.c_int, _vp]
+                                          ctypes.c_double, ctypes.c_float, ctypes.c_int, _vp]
         lib.vq_ema_update_f32.restype = ctypes.c_int
         lib.vq_similarities_f32.argtypes = [ap, _vp, _i64, _i64, _vp]
         lib.vq_similarities_f32.restype = ctypes.c_int
@@ -671,10 +671,10 @@ def ema_accumulate_residual(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor
     assert Hc == H and Dc == D and (Qc == Q or (stages_share_codebook and Qc == 1))
     if deterministic:
         # atomics-free: one reproducible accumulation per stage on the residual that stage quantized (residual_vq.py:212-233)
-        counts, sums, r = [], [], x
+        counts, sums, r, live = [], [], x, None
         for q in range(Q):
             iq = idx[..., q]
-            live = iq >= 0  # dropped stages (quantize dropout) end a row's chain
+            live = iq >= 0 if live is None else live & (iq >= 0)  # a dropped stage (quantize dropout) ends a row's chain
             c, s_ = ema_accumulate(r, iq, K, None if bool(live.all()) else live, deterministic=True)
             counts.append(c)
             sums.append(s_)
