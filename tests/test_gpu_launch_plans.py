@@ -152,3 +152,73 @@ def test_residual_stacks_per_head_squared_errors_under_both_plans(M, K, D, Q, H,
     s = native.quantize(x, cbs, ste=True, want_sq_err=True)
     assert torch.equal(r["idx"], s["idx"]) and torch.equal(r["out"], s["out"])
     torch.testing.assert_close(r["sq_err"].sum(0), s["sq_err"], rtol=1e-6, atol=0)
+
+
+def _cus() -> int:
+    from vector_quantization import native
+
+    return int(native.device_info().split()[-2])  # "<arch> <n> CUs"
+
+
+def _sq_err_cases():
+    # Each fused kernel kind that carries want_sq_err, at the smallest shape that selects it (H = 2, a ragged 37-row remainder).
+    # The short sweeps keep the K-split and main + tail plans away, so the total and the per-head call run the same kernel.
+    yield "one_block_8_waves", lambda cus: (cus // 2 * 256 + 37, 200, 64)       # H * ceil(M / 256) >= CUs
+    yield "one_block_4_waves", lambda cus: (337, 120, 100)                      # few rows: the 8-wave grid leaves CUs empty
+    yield "wave_pairs", lambda cus: ((cus // 4 + 2) * 128 + 37, 256, 512)       # D = 512, 8 tiles per sweep, more than CUs / 2 workgroups
+    yield "persistent_train", lambda cus: ((cus - 1) * 256 + 37, 1024, 256)     # H * ceil(M / 256) = 2 CUs: the fewest rows it accepts
+
+
+@pytest.mark.parametrize("kind,shape", list(_sq_err_cases()), ids=[k for k, _ in _sq_err_cases()])
+def test_loss_partials_follow_the_chosen_kernel(kind, shape):
+    """The squared-error sum is reduced from the partials of the kernel that ran -- as many per head as that kernel's grid has
+    waves -- so every kind must give the fp64 sum of (codebook[idx] - x)^2 over the rows of the call, in total and per head
+    (rtol 1e-6: fp32 partials of a few thousand terms each, summed in fp64; test_gpu_persistent_kernel.py's bound)."""
+    from vector_quantization import native
+
+    native.load()
+    H = 2
+    M, K, D = shape(_cus())
+    g = torch.Generator(device=DEV).manual_seed(M + K + D)
+    x = torch.randn((H, M, D), device=DEV, generator=g)
+    cb = torch.randn((H, 1, K, D), device=DEV, generator=g)
+    total = native.quantize(x, cb, want_sq_err=True)
+    heads = native.quantize(x, cb, want_sq_err=True, sq_err_per_head=True)
+    assert torch.equal(total["idx"], heads["idx"])
+    hh = torch.arange(H, device=DEV)[:, None]
+    want = (cb[:, 0][hh, heads["idx"][..., 0]] - x).double().pow(2).sum(dim=(1, 2))
+    assert tuple(heads["sq_err"].shape) == (H, 1) and tuple(total["sq_err"].shape) == (1,)
+    torch.testing.assert_close(heads["sq_err"][:, 0], want, rtol=1e-6, atol=0)
+    torch.testing.assert_close(total["sq_err"][0], want.sum(), rtol=1e-6, atol=0)
+    torch.testing.assert_close(heads["sq_err"].sum(), total["sq_err"][0], rtol=1e-6, atol=0)
+
+
+_TWO_BIG_LDS_KERNELS = """
+import sys
+sys.path.insert(0, sys.argv[1])
+import torch
+from vector_quantization import native
+g = torch.Generator().manual_seed(5)
+x = torch.randn((1, 300, 256), generator=g).cuda()
+cb = torch.randn((1, 1, 2048, 256), generator=g).cuda()
+first = [native.quantize(x, cb, metric=m)["idx"] for m in (0, 1)]  # raises on a failed launch
+torch.cuda.synchronize()
+for m in (0, 1):
+    assert torch.equal(first[m], native.quantize(x, cb, metric=m, flags=native.F_FORCE_SIMPLE)["idx"]), m
+print("both searches ok")
+"""
+
+
+def test_lds_limit_is_raised_per_kernel_instantiation():
+    """Two instantiations of one kernel template (same parameter type) that both need more than 64 KiB of dynamic LDS, as the
+    first two searches of a fresh process: each must get its own hipFuncSetAttribute, or the second launch fails."""
+    import os
+    import subprocess
+    import sys
+
+    import vector_quantization
+
+    pkg_parent = os.path.dirname(os.path.dirname(os.path.abspath(vector_quantization.__file__)))
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", _TWO_BIG_LDS_KERNELS, pkg_parent]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "both searches ok" in r.stdout, r.stdout + r.stderr

@@ -1,4 +1,4 @@
-// vq_common.inc -- constants, error strings, padded-dim table, packed (value, index) keys.
+// vq_common.inc -- constants, error strings, the kernel-launch helper, metric / padded-dim dispatch, packed (value, index) keys.
 // Included by vq_kernels.hip inside its anonymous namespace (single translation unit).
 
 constexpr int kTileCodes = 32;
@@ -24,6 +24,51 @@ int fail(int code, const char *msg) {
 int hip_fail(hipError_t e, const char *what) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
     return (int)e;
+}
+
+// The one kernel launch of the library: raise the kernel's dynamic-LDS limit first when the launcher asks for it (BIG_LDS),
+// launch, check.  `what` names the launch in the error string.  hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a
+// per-device property of a kernel, so the "already raised" flags are per kernel (Kern is a template ARGUMENT: kernels of one
+// signature, such as every vq_search_mfma<..>, must not share them), per thread and per device ordinal -- a process that
+// drives several GPUs raises the limit on each of them.
+constexpr int kMaxDevices = 64;
+constexpr bool kBigLds = true;
+
+template <auto Kern, bool BIG_LDS = false, typename... A>
+int launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const char *what, const A &...args) {
+    if constexpr (BIG_LDS) {
+        static thread_local bool raised[kMaxDevices] = {};
+        int dev = -1;
+        if (hipGetDevice(&dev) != hipSuccess) return fail(VQ_E_NODEVICE, "vq: no HIP device");
+        const bool tracked = dev >= 0 && dev < kMaxDevices;
+        if (!tracked || !raised[dev]) {
+            hipError_t e = hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
+            if (tracked) raised[dev] = true;
+        }
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds, s, args...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_fail(e, what);
+}
+
+// run-time value -> template argument: f is called with a std::integral_constant and returns the launch's status
+template <typename F>
+int with_metric(int metric, F f) {
+    if (metric == VQ_METRIC_EUCLID) return f(std::integral_constant<int, VQ_METRIC_EUCLID>{});
+    return f(std::integral_constant<int, VQ_METRIC_DOT>{});
+}
+
+template <typename F, typename U>
+int with_padded_dim(int DP, F f, U on_unsupported) {
+    switch (DP) {
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        case 256: return f(std::integral_constant<int, 256>{});
+        case 512: return f(std::integral_constant<int, 512>{});
+    }
+    return on_unsupported();
 }
 
 inline int padded_dim(int D) {

@@ -224,17 +224,18 @@ int fsq_check(int64_t G, int64_t N, int d, int S, const int32_t *levels, const f
 
 #define FSQ_LAUNCHER(name, kernel)                                                                   \
     template <typename... A>                                                                         \
-    void name(int d, dim3 grid, hipStream_t s, A... args) {                                          \
+    int name(int d, dim3 grid, hipStream_t s, const char *what, A... args) {                         \
         switch (d) {                                                                                 \
             FSQ_CASES(FSQ_CASE_##kernel)                                                             \
         }                                                                                            \
+        return 0;                                                                                    \
     }
 #define FSQ_CASE_fsq_quantize_kernel(D) \
-    case D: hipLaunchKernelGGL(fsq_quantize_kernel<D>, grid, dim3(kFsqThreads), 0, s, args...); break;
+    case D: return launch<fsq_quantize_kernel<D>>(grid, dim3(kFsqThreads), 0, s, what, args...);
 #define FSQ_CASE_fsq_backward_kernel(D) \
-    case D: hipLaunchKernelGGL(fsq_backward_kernel<D>, grid, dim3(kFsqThreads), 0, s, args...); break;
+    case D: return launch<fsq_backward_kernel<D>>(grid, dim3(kFsqThreads), 0, s, what, args...);
 #define FSQ_CASE_fsq_decode_kernel(D) \
-    case D: hipLaunchKernelGGL(fsq_decode_kernel<D>, grid, dim3(kFsqThreads), 0, s, args...); break;
+    case D: return launch<fsq_decode_kernel<D>>(grid, dim3(kFsqThreads), 0, s, what, args...);
 FSQ_LAUNCHER(fsq_launch_quantize, fsq_quantize_kernel)
 FSQ_LAUNCHER(fsq_launch_backward, fsq_backward_kernel)
 FSQ_LAUNCHER(fsq_launch_decode, fsq_decode_kernel)

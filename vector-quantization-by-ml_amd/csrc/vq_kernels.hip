@@ -22,7 +22,7 @@
 //
 // Source layout (ONE source file: the .inc files are included below inside the anonymous namespace, in this order; the file
 // is compiled either whole or once per build part -- see "Build parts"):
-//   vq_common.inc        constants, error strings, padded-dim table, packed (value, index) keys
+//   vq_common.inc        constants, error strings, the kernel-launch helper, metric / padded-dim dispatch, packed (value, index) keys
 //   vq_pack.inc          natural codebook -> packed image
 //   vq_search.inc        the hot kernel (tile geometry, LDS-DMA staging, MFMA fragment pipeline, tie-exact epilogue, finalize)
 //   vq_search_pair.inc   the same search for 256 < D <= 512 with the dims split over a pair of waves (accumulator hand-off)
@@ -46,6 +46,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <initializer_list>
+#include <type_traits>
 
 #include "../../include/vq_mi355x.h"
 
@@ -117,20 +120,100 @@ const DevInfo &dev_info() {
     return info;
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device property of a kernel: one flag per device ordinal
-// (per thread and per instantiation), so a process that drives several GPUs raises the limit on each of them.
-constexpr int kMaxDevices = 64;
+inline int device_cus() {  // compute units of the current device; 256 when the device cannot be asked
+    const DevInfo &di = dev_info();
+    return di.ok && di.cus > 0 ? di.cus : 256;
+}
 
-template <typename K>
-int allow_big_lds(K kern, bool (&done)[kMaxDevices]) {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail(VQ_E_NODEVICE, "vq: no HIP device");
-    const bool tracked = dev >= 0 && dev < kMaxDevices;
-    if (tracked && done[dev]) return 0;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute");
-    if (tracked) done[dev] = true;
-    return 0;
+// ---- which kernel runs a search launch ---------------------------------------------------------------------------------
+// Decided ONCE per launch (choose_search) and handed to everything that depends on it: the set-up of the screened sweep's
+// images, launch_search, and the reduction of the loss partials that the chosen kernel writes.  (The build parts pass the
+// choice to each other, so its type lives in the named namespace.)
+}  // namespace
+namespace vqi {
+enum SearchKind {
+    kResident,  // small codebook resident in LDS (vq_search_resident.inc)
+    kPersist,   // persistent workgroups at Dp = 256 (vq_search_persist.inc)
+    kPair,      // dims split over wave pairs at Dp = 512 (vq_search_pair.inc)
+    kOneBlock,  // one row block per workgroup (vq_search.inc)
+};
+struct SearchChoice {
+    SearchKind kind;
+    int waves;      // waves per workgroup of the chosen kernel
+    bool train;     // kPersist: the deferred copy does the straight-through / squared-error arithmetic
+    bool screened;  // kPersist: the bf16x3 screened sweep + the second pass over its listed rows
+};
+}  // namespace vqi
+namespace {
+using vqi::SearchChoice, vqi::SearchKind, vqi::kResident, vqi::kPersist, vqi::kPair, vqi::kOneBlock;
+
+// workgroups per head (grid.x) of each kernel kind
+inline long long one_block_grid_x(long long M, int waves) { return (M + 32ll * waves - 1) / (32ll * waves); }
+inline long long pair_grid_x(long long M) { return (M + 127) / 128; }  // 8 waves = 4 pairs = 128 rows per workgroup
+inline long long persist_grid_x(long long M, int H, int cus) {  // one 8-wave workgroup per CU, the CUs shared by the heads
+    const long long nblk = (M + 255) / 256;
+    long long gx = cus / H;
+    if (gx < 1) gx = 1;
+    return gx > nblk ? nblk : gx;
+}
+// loss partials per head and stage that the chosen kernel writes: one per wave of every workgroup of the grids above
+// (the resident kernel carries no loss)
+inline long long loss_partials_per_head(const SearchChoice &c, long long M, int H, int cus) {
+    const long long gx = c.kind == kPersist ? persist_grid_x(M, H, cus) : c.kind == kPair ? pair_grid_x(M) : one_block_grid_x(M, c.waves);
+    return gx * c.waves;
+}
+
+// VQ_SINGLE_WAVE_512=1 in the environment selects the one-wave-per-row-block kernel for D > 256 (A/B measurements)
+bool use_pair512() {
+    static const bool off = getenv("VQ_SINGLE_WAVE_512") != nullptr;
+    return !off;
+}
+
+// the screened sweep's share of the workspace: [bf16x3 images][count, 256 B][rows for the second pass: one uint32 per row of the call]
+inline long long screen_bytes(int H, long long M, int ntiles) { return (long long)H * scr_image_bytes(ntiles) + 256 + 4ll * H * M; }
+
+// In order of precedence.  `waves` is the one-block kernel's workgroup size (the caller's plan); `scr_room` the bytes of
+// workspace the screened sweep may use (0: none).  Only a whole fused call (no K split, kModeFused) can be taken by the
+// resident or the persistent kernel: keys-mode searches and the slices of wide rows get wave pairs or one block.
+SearchChoice choose_search(int DP, int waves, const SearchParams &p, int H, int splits, int metric, int cus, long long scr_room = 0) {
+    SearchChoice c = {kOneBlock, waves, false, false};
+    const bool whole_call = splits == 1 && p.mode == kModeFused;
+    // Small codebook whose image fits the LDS beside the row slabs (resident_image_for set p.res_img_floats)
+    if (whole_call && p.res_img_floats > 0 && (DP == 32 || DP == 64 || DP == 128)) {
+        c.kind = kResident;
+        c.waves = 8;
+        return c;
+    }
+    // Plain call at Dp = 256 (one stage, aligned fp32 rows, >= 32 sub-tiles per sweep, several row blocks per CU): persistent
+    // workgroups that copy block b's winners during block b + 1's sweep.  VQ_NO_PERSIST=1 in the environment keeps the
+    // one-block-per-workgroup kernel (A/B measurements); VQ_NO_PERSIST_TRAIN=1 does so for training-mode calls (A/B and
+    // tests; read per call).
+    static const bool no_persist = getenv("VQ_NO_PERSIST") != nullptr;
+    const bool train = p.ste || p.loss_part;
+    const int nsub = p.ntiles * sub_tiles(DP);
+    if (whole_call && !no_persist && DP == 256 && waves == 8 && p.Q == 1 && !p.lse && !p.xt && p.vec_x && p.vec_fin && p.D % 4 == 0 &&
+        (p.out || p.loss_part) &&                                // (else nothing to copy)
+        !(train && getenv("VQ_NO_PERSIST_TRAIN") != nullptr) &&
+        nsub >= 32 && nsub <= 96 &&                              // one row per sub-tile needs 32; beyond ~100 the finalize is < 1 % of a block
+        one_block_grid_x(p.M, waves) * H >= 2ll * cus) {         // at least two blocks per resident workgroup
+        c.kind = kPersist;
+        c.train = train;
+        // The screened sweep (vq_search_persist.inc, SCREEN): Euclid, inference, no winning distances requested, and its
+        // images and row list fit the room.  VQ_NO_SCREEN in the environment keeps the fp32 sweep (read per call: tests
+        // compare both in one process).
+        c.screened = !train && metric == VQ_METRIC_EUCLID && !p.best && getenv("VQ_NO_SCREEN") == nullptr &&
+                     screen_bytes(H, p.M, p.ntiles) <= scr_room && scr_image_bytes(p.ntiles) < (1ll << 31) && (long long)H * p.M < (1ll << 31);
+        return c;
+    }
+    // The wave-pair kernel runs wave B one tile behind wave A: one extra step per sweep.  Worth it from 8 tiles per sweep on.
+    // Residual stacks as long as the winners of every stage fit its LDS (Q <= 26); VQ_PAIR_NO_MULTI=1: one-wave kernel (A/B;
+    // read per call: tests compare both kernels in one process).
+    if (DP == 512 && p.tiles_per_split >= 8 && use_pair512() &&
+        (p.Q == 1 || (getenv("VQ_PAIR_NO_MULTI") == nullptr && p.Q <= PairGeo::max_stages()))) {
+        c.kind = kPair;
+        c.waves = 8;
+    }
+    return c;
 }
 
 template <int DP, int WAVES, int METRIC, int MULTI, bool LSE = false, int XT = 0, int WIDE = 0>
@@ -139,15 +222,8 @@ int launch_search_t(const SearchParams &p, int H, int splits, hipStream_t s) {
     const size_t lds = (size_t)(MULTI ? G::MAIN_FLOATS_M : G::MAIN_FLOATS_S) * 4 + (size_t)WAVES * p.Q * 32 * 4 +
                        ((MULTI && p.loss_part) ? (size_t)WAVES * p.Q * 64 * 4 : 0);
     if (lds > 160 * 1024) return fail(VQ_E_UNSUPPORTED, "vq_search: LDS budget exceeded (too many residual stages)");
-    auto kern = vq_search_mfma<DP, WAVES, METRIC, MULTI, LSE, XT, WIDE>;
-    static thread_local bool attr_done[kMaxDevices] = {};
-    if (int rc = allow_big_lds(kern, attr_done)) return rc;
-    const long long rows_per_wg = 32ll * WAVES;
-    dim3 grid((unsigned)((p.M + rows_per_wg - 1) / rows_per_wg), (unsigned)H, (unsigned)splits);
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, s, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_search_mfma launch");
-    return 0;
+    return launch<vq_search_mfma<DP, WAVES, METRIC, MULTI, LSE, XT, WIDE>, kBigLds>(
+        dim3((unsigned)one_block_grid_x(p.M, WAVES), (unsigned)H, (unsigned)splits), dim3(WAVES * 64), lds, s, "vq_search_mfma launch", p);
 }
 
 // LDS bytes of a residual (multi-stage) launch with Q stages; the budget is the CU's 160 KiB
@@ -165,106 +241,55 @@ int max_stages_t(bool with_loss) {
 
 template <int DP, int WAVES>
 int launch_search_m(const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
-    if (p.Q > 1) {  // residual stages: eval (1) and straight-through (2) arithmetic are separate instantiations
-        if (p.ste) {
-            if (metric == VQ_METRIC_EUCLID) return launch_search_t<DP, WAVES, VQ_METRIC_EUCLID, 2>(p, H, splits, s);
-            return launch_search_t<DP, WAVES, VQ_METRIC_DOT, 2>(p, H, splits, s);
-        }
-        if (metric == VQ_METRIC_EUCLID) return launch_search_t<DP, WAVES, VQ_METRIC_EUCLID, 1>(p, H, splits, s);
-        return launch_search_t<DP, WAVES, VQ_METRIC_DOT, 1>(p, H, splits, s);
-    }
-    if (p.xt == 1) {  // fp16 rows, widened in the prologue (inference)
-        if (metric == VQ_METRIC_EUCLID) return launch_search_t<DP, WAVES, VQ_METRIC_EUCLID, 0, false, 1>(p, H, splits, s);
-        return launch_search_t<DP, WAVES, VQ_METRIC_DOT, 0, false, 1>(p, H, splits, s);
-    }
-    if (p.xt == 2) {  // bf16 rows
-        if (metric == VQ_METRIC_EUCLID) return launch_search_t<DP, WAVES, VQ_METRIC_EUCLID, 0, false, 2>(p, H, splits, s);
-        return launch_search_t<DP, WAVES, VQ_METRIC_DOT, 0, false, 2>(p, H, splits, s);
-    }
-    if (p.lse) {  // search + log-sum-exp in one sweep (cross-entropy commitment loss)
-        if (metric == VQ_METRIC_EUCLID) return launch_search_t<DP, WAVES, VQ_METRIC_EUCLID, 0, true>(p, H, splits, s);
-        return launch_search_t<DP, WAVES, VQ_METRIC_DOT, 0, true>(p, H, splits, s);
-    }
-    if (metric == VQ_METRIC_EUCLID) return launch_search_t<DP, WAVES, VQ_METRIC_EUCLID, 0>(p, H, splits, s);
-    return launch_search_t<DP, WAVES, VQ_METRIC_DOT, 0>(p, H, splits, s);
+    return with_metric(metric, [&](auto m) {
+        constexpr int ME = decltype(m)::value;
+        if (p.Q > 1)  // residual stages: eval (1) and straight-through (2) arithmetic are separate instantiations
+            return p.ste ? launch_search_t<DP, WAVES, ME, 2>(p, H, splits, s) : launch_search_t<DP, WAVES, ME, 1>(p, H, splits, s);
+        if (p.xt == 1) return launch_search_t<DP, WAVES, ME, 0, false, 1>(p, H, splits, s);  // fp16 rows, widened in the prologue (inference)
+        if (p.xt == 2) return launch_search_t<DP, WAVES, ME, 0, false, 2>(p, H, splits, s);  // bf16 rows
+        if (p.lse) return launch_search_t<DP, WAVES, ME, 0, true>(p, H, splits, s);  // search + log-sum-exp in one sweep (cross-entropy commitment loss)
+        return launch_search_t<DP, WAVES, ME, 0>(p, H, splits, s);
+    });
 }
 
-// VQ_SINGLE_WAVE_512=1 in the environment selects the one-wave-per-row-block kernel for D > 256 (A/B measurements)
-bool use_pair512() {
-    static const bool off = getenv("VQ_SINGLE_WAVE_512") != nullptr;
-    return !off;
-}
-
-// The wave-pair kernel runs wave B one tile behind wave A: one extra step per sweep.  Worth it from 8 tiles per sweep on.
-// Residual stacks (round 3) as long as the winners of every stage fit its LDS (Q <= 26); VQ_PAIR_NO_MULTI=1: one-wave kernel (A/B).
-bool pair_selected(int DP, int Q, int tiles_per_sweep) {
-    if (!(DP == 512 && tiles_per_sweep >= 8 && use_pair512())) return false;
-    if (Q == 1) return true;
-    return getenv("VQ_PAIR_NO_MULTI") == nullptr && Q <= PairGeo::max_stages();  // (read per call: tests compare both kernels in one process)
-}
-
-// 256 < D <= 512: dims split over wave pairs (vq_search_pair.inc); 8 waves = 4 pairs = 128 rows per workgroup
+// 256 < D <= 512: dims split over wave pairs (vq_search_pair.inc)
 template <int METRIC, bool LSE = false, int XT = 0, int WIDE = 0, int MULTI = 0>
 int launch_pair_t(const SearchParams &p, int H, int splits, hipStream_t s) {
-    const size_t lds = PairGeo::lds_bytes(MULTI ? p.Q : 1);
-    auto kern = vq_search_pair512<METRIC, LSE, XT, WIDE, MULTI>;
-    static thread_local bool attr_done[kMaxDevices] = {};
-    if (int rc = allow_big_lds(kern, attr_done)) return rc;
-    dim3 grid((unsigned)((p.M + 127) / 128), (unsigned)H, (unsigned)splits);
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_search_pair512 launch");
-    return 0;
+    return launch<vq_search_pair512<METRIC, LSE, XT, WIDE, MULTI>, kBigLds>(dim3((unsigned)pair_grid_x(p.M), (unsigned)H, (unsigned)splits), dim3(512),
+                                                                            PairGeo::lds_bytes(MULTI ? p.Q : 1), s, "vq_search_pair512 launch", p);
 }
 
 #if VQ_OWN(4)  // (not a template: defining it instantiates the wave-pair kernels)
 int launch_pair_any(const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
-    const bool eu = metric == VQ_METRIC_EUCLID;
-    if (p.Q > 1) {  // residual stacks: eval (1) and straight-through (2) arithmetic, as in launch_search_m
-        if (p.ste) return eu ? launch_pair_t<VQ_METRIC_EUCLID, false, 0, 0, 2>(p, H, splits, s) : launch_pair_t<VQ_METRIC_DOT, false, 0, 0, 2>(p, H, splits, s);
-        return eu ? launch_pair_t<VQ_METRIC_EUCLID, false, 0, 0, 1>(p, H, splits, s) : launch_pair_t<VQ_METRIC_DOT, false, 0, 0, 1>(p, H, splits, s);
-    }
-    if (p.xt == 1) return eu ? launch_pair_t<VQ_METRIC_EUCLID, false, 1>(p, H, splits, s) : launch_pair_t<VQ_METRIC_DOT, false, 1>(p, H, splits, s);
-    if (p.xt == 2) return eu ? launch_pair_t<VQ_METRIC_EUCLID, false, 2>(p, H, splits, s) : launch_pair_t<VQ_METRIC_DOT, false, 2>(p, H, splits, s);
-    if (p.lse) return eu ? launch_pair_t<VQ_METRIC_EUCLID, true>(p, H, splits, s) : launch_pair_t<VQ_METRIC_DOT, true>(p, H, splits, s);
-    return eu ? launch_pair_t<VQ_METRIC_EUCLID>(p, H, splits, s) : launch_pair_t<VQ_METRIC_DOT>(p, H, splits, s);
+    return with_metric(metric, [&](auto m) {
+        constexpr int ME = decltype(m)::value;
+        if (p.Q > 1)  // residual stacks: eval (1) and straight-through (2) arithmetic, as in launch_search_m
+            return p.ste ? launch_pair_t<ME, false, 0, 0, 2>(p, H, splits, s) : launch_pair_t<ME, false, 0, 0, 1>(p, H, splits, s);
+        if (p.xt == 1) return launch_pair_t<ME, false, 1>(p, H, splits, s);
+        if (p.xt == 2) return launch_pair_t<ME, false, 2>(p, H, splits, s);
+        if (p.lse) return launch_pair_t<ME, true>(p, H, splits, s);
+        return launch_pair_t<ME>(p, H, splits, s);
+    });
 }
 #endif
-
-// workgroups per head of the persistent kernel: one 8-wave workgroup per CU, the CUs shared by the heads
-inline long long persist_grid_x(long long M, int H, int cus) {
-    const long long nblk = (M + 255) / 256;
-    long long gx = cus / H;
-    if (gx < 1) gx = 1;
-    return gx > nblk ? nblk : gx;
-}
 
 template <int METRIC, bool TRAIN = false, bool SCREEN = false>
 int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s) {
     using G = Geo<256, 8>;
     const size_t lds = (size_t)G::MAIN_FLOATS_S * 4 + 2 * 8 * 32 * 4;
-    auto kern = vq_search_persist<256, 8, METRIC, TRAIN, SCREEN>;
     if constexpr (SCREEN) {  // the bf16x3 images of this call's codebooks, from their fp32 packed images
-        hipLaunchKernelGGL(vq_pack_scr_kernel<256>, dim3((unsigned)p.ntiles, (unsigned)H), dim3(256), 0, s, p.packed, p.pk_hs, p.K,
-                           p.ntiles, (char *)p.scr, p.scr_hs, p.scr_count);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "vq_pack_scr launch");
+        if (int rc = launch<vq_pack_scr_kernel<256>>(dim3((unsigned)p.ntiles, (unsigned)H), dim3(256), 0, s, "vq_pack_scr launch", p.packed, p.pk_hs,
+                                                     p.K, p.ntiles, (char *)p.scr, p.scr_hs, p.scr_count))
+            return rc;
     }
-    static thread_local bool attr_done[kMaxDevices] = {};
-    if (int rc = allow_big_lds(kern, attr_done)) return rc;
-    const long long gx = persist_grid_x(p.M, H, cus);
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)H, 1), dim3(512), lds, s, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_search_persist launch");
+    if (int rc = launch<vq_search_persist<256, 8, METRIC, TRAIN, SCREEN>, kBigLds>(dim3((unsigned)persist_grid_x(p.M, H, cus), (unsigned)H, 1), dim3(512),
+                                                                                   lds, s, "vq_search_persist launch", p))
+        return rc;
     if constexpr (SCREEN) {
         // second pass: the listed rows, in stream order behind the sweep.  One workgroup per CU: the few rows of a usual call
         // (tens) take one round, and a workgroup that finds no entry for itself ends after one load of the count.
-        auto rkern = vq_resolve_rows_kernel<256>;
-        static thread_local bool attr_done_r[kMaxDevices] = {};
-        if (int rc = allow_big_lds(rkern, attr_done_r)) return rc;
-        hipLaunchKernelGGL(rkern, dim3((unsigned)(cus > 0 ? cus : 1)), dim3(kResolveWaves * 64), resolve_lds_bytes<256>(), s, p, H);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "vq_resolve_rows launch");
+        return launch<vq_resolve_rows_kernel<256>, kBigLds>(dim3((unsigned)(cus > 0 ? cus : 1)), dim3(kResolveWaves * 64), resolve_lds_bytes<256>(), s,
+                                                            "vq_resolve_rows launch", p, H);
     }
     return 0;
 }
@@ -277,115 +302,68 @@ int launch_resident_t(const SearchParams &p, int H, int cus, hipStream_t s) {
     long long gx = cus / H;
     if (gx < 1) gx = 1;
     if (gx > (nwb + 7) / 8) gx = (nwb + 7) / 8;
+    auto go = [&](auto multibuf) {
+        return launch<vq_search_resident<DP, METRIC, decltype(multibuf)::value>, kBigLds>(dim3((unsigned)gx, (unsigned)H, 1), dim3(512), lds, s,
+                                                                                          "vq_search_resident launch", p);
+    };
     if constexpr (DP < 128) {
-        if (p.res_nbuf > 1) {  // a slab buffer per slab of a block
-            auto kern = vq_search_resident<DP, METRIC, true>;
-            static thread_local bool attr_done_r[kMaxDevices] = {};
-            if (int rc = allow_big_lds(kern, attr_done_r)) return rc;
-            hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)H, 1), dim3(512), lds, s, p);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return hip_fail(e, "vq_search_resident launch");
-            return 0;
-        }
+        if (p.res_nbuf > 1) return go(std::true_type{});  // a slab buffer per slab of a block
     }
-    auto kern = vq_search_resident<DP, METRIC, false>;
-    static thread_local bool attr_done[kMaxDevices] = {};
-    if (int rc = allow_big_lds(kern, attr_done)) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)H, 1), dim3(512), lds, s, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_search_resident launch");
-    return 0;
+    return go(std::false_type{});
 }
 
 template <int DP>
 int launch_resident_m(const SearchParams &p, int H, int cus, int metric, hipStream_t s) {
-    return metric == VQ_METRIC_EUCLID ? launch_resident_t<DP, VQ_METRIC_EUCLID>(p, H, cus, s) : launch_resident_t<DP, VQ_METRIC_DOT>(p, H, cus, s);
+    return with_metric(metric, [&](auto m) { return launch_resident_t<DP, decltype(m)::value>(p, H, cus, s); });
 }
 
 template <int DP, int WAVES, int METRIC, int MODE>
 int launch_aux_t(const AuxParams &p, int H, hipStream_t s) {
-    using G = Geo<DP, WAVES>;
-    const size_t lds = (size_t)G::MAIN_FLOATS * 4;
-    auto kern = vq_sweep_aux<DP, WAVES, METRIC, MODE>;
-    static thread_local bool attr_done[kMaxDevices] = {};
-    if (int rc = allow_big_lds(kern, attr_done)) return rc;
-    const long long rows_per_wg = 32ll * WAVES;
-    dim3 grid((unsigned)((p.M + rows_per_wg - 1) / rows_per_wg), (unsigned)H, 1);
-    hipLaunchKernelGGL(kern, grid, dim3(WAVES * 64), lds, s, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_sweep_aux launch");
-    return 0;
+    return launch<vq_sweep_aux<DP, WAVES, METRIC, MODE>, kBigLds>(dim3((unsigned)one_block_grid_x(p.M, WAVES), (unsigned)H, 1), dim3(WAVES * 64),
+                                                                  (size_t)Geo<DP, WAVES>::MAIN_FLOATS * 4, s, "vq_sweep_aux launch", p);
 }
 
 template <int DP, int WAVES>
 int launch_aux_m(const AuxParams &p, int H, int metric, int mode, hipStream_t s) {
-    if (mode == kAuxSims) {
-        if (metric == VQ_METRIC_EUCLID) return launch_aux_t<DP, WAVES, VQ_METRIC_EUCLID, kAuxSims>(p, H, s);
-        return launch_aux_t<DP, WAVES, VQ_METRIC_DOT, kAuxSims>(p, H, s);
-    }
-    if (metric == VQ_METRIC_EUCLID) return launch_aux_t<DP, WAVES, VQ_METRIC_EUCLID, kAuxStats>(p, H, s);
-    return launch_aux_t<DP, WAVES, VQ_METRIC_DOT, kAuxStats>(p, H, s);
+    return with_metric(metric, [&](auto m) {
+        constexpr int ME = decltype(m)::value;
+        return mode == kAuxSims ? launch_aux_t<DP, WAVES, ME, kAuxSims>(p, H, s) : launch_aux_t<DP, WAVES, ME, kAuxStats>(p, H, s);
+    });
 }
 
 template <int DP, int METRIC>
 int launch_ce_bwd_t(const CeBwdParams &p, int H, hipStream_t s) {
-    using G = Geo<DP, 4>;
-    const size_t stage_floats = (size_t)4 * (32 * CeGeo<DP>::GS + 96);
-    const size_t lds = 4 * ((size_t)G::MAIN_FLOATS > stage_floats ? (size_t)G::MAIN_FLOATS : stage_floats);
-    auto kern = vq_ce_backward<DP, METRIC>;
-    static thread_local bool attr_done[kMaxDevices] = {};
-    if (int rc = allow_big_lds(kern, attr_done)) return rc;
-    dim3 grid((unsigned)((p.M + 127) / 128), (unsigned)H, (unsigned)CeGeo<DP>::NH);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_ce_backward launch");
-    return 0;
+    const size_t stage_floats = (size_t)4 * (32 * CeGeo<DP>::GS + 96), main_floats = (size_t)Geo<DP, 4>::MAIN_FLOATS;
+    return launch<vq_ce_backward<DP, METRIC>, kBigLds>(dim3((unsigned)((p.M + 127) / 128), (unsigned)H, (unsigned)CeGeo<DP>::NH), dim3(256),
+                                                       4 * (main_floats > stage_floats ? main_floats : stage_floats), s, "vq_ce_backward launch", p);
 }
 
 // Dp = 256: the two contractions on a pair of waves (two waves per SIMD); VQ_CE_NO_ROLES=1 keeps the one-wave kernel (A/B runs)
 template <int METRIC>
 int launch_ce_bwd_roles_t(const CeBwdParams &p, int H, hipStream_t s) {
-    const size_t lds = (size_t)CeRolesGeo::LDS_F * 4;
-    auto kern = vq_ce_backward_roles<METRIC>;
-    static thread_local bool attr_done[kMaxDevices] = {};
-    if (int rc = allow_big_lds(kern, attr_done)) return rc;
-    dim3 grid((unsigned)((p.M + 32 * CeRolesGeo::NB - 1) / (32 * CeRolesGeo::NB)), (unsigned)H, 1);
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_ce_backward_roles launch");
-    return 0;
+    return launch<vq_ce_backward_roles<METRIC>, kBigLds>(dim3((unsigned)((p.M + 32 * CeRolesGeo::NB - 1) / (32 * CeRolesGeo::NB)), (unsigned)H, 1),
+                                                         dim3(512), (size_t)CeRolesGeo::LDS_F * 4, s, "vq_ce_backward_roles launch", p);
 }
 
 // Dp = 512: four roles per row block (S cut in two, G in two halves of the positions), 64 rows per workgroup
 template <int METRIC>
 int launch_ce_bwd_roles512_t(const CeBwdParams &p, int H, hipStream_t s) {
-    const size_t lds = (size_t)CeRoles512Geo::LDS_F * 4;
-    auto kern = vq_ce_backward_roles512<METRIC>;
-    static thread_local bool attr_done[kMaxDevices] = {};
-    if (int rc = allow_big_lds(kern, attr_done)) return rc;
-    dim3 grid((unsigned)((p.M + 32 * CeRoles512Geo::NQ - 1) / (32 * CeRoles512Geo::NQ)), (unsigned)H, 1);
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_ce_backward_roles512 launch");
-    return 0;
+    return launch<vq_ce_backward_roles512<METRIC>, kBigLds>(dim3((unsigned)((p.M + 32 * CeRoles512Geo::NQ - 1) / (32 * CeRoles512Geo::NQ)), (unsigned)H, 1),
+                                                            dim3(512), (size_t)CeRoles512Geo::LDS_F * 4, s, "vq_ce_backward_roles512 launch", p);
 }
 
 template <int DP>
 int launch_ce_bwd_m(const CeBwdParams &p, int H, int metric, hipStream_t s) {
-    if constexpr (DP == 512) {
-        if (getenv("VQ_CE_NO_ROLES") == nullptr) {
-            if (metric == VQ_METRIC_EUCLID) return launch_ce_bwd_roles512_t<VQ_METRIC_EUCLID>(p, H, s);
-            return launch_ce_bwd_roles512_t<VQ_METRIC_DOT>(p, H, s);
+    return with_metric(metric, [&](auto m) {
+        constexpr int ME = decltype(m)::value;
+        if constexpr (DP == 256 || DP == 512) {
+            if (getenv("VQ_CE_NO_ROLES") == nullptr) {  // (read per call: tests switch between the two kernels in one process)
+                if constexpr (DP == 512) return launch_ce_bwd_roles512_t<ME>(p, H, s);
+                else return launch_ce_bwd_roles_t<ME>(p, H, s);
+            }
         }
-    }
-    if constexpr (DP == 256) {
-        if (getenv("VQ_CE_NO_ROLES") == nullptr) {  // (read per call: tests switch between the two kernels in one process)
-            if (metric == VQ_METRIC_EUCLID) return launch_ce_bwd_roles_t<VQ_METRIC_EUCLID>(p, H, s);
-            return launch_ce_bwd_roles_t<VQ_METRIC_DOT>(p, H, s);
-        }
-    }
-    if (metric == VQ_METRIC_EUCLID) return launch_ce_bwd_t<DP, VQ_METRIC_EUCLID>(p, H, s);
-    return launch_ce_bwd_t<DP, VQ_METRIC_DOT>(p, H, s);
+        return launch_ce_bwd_t<DP, ME>(p, H, s);
+    });
 }
 
 #ifndef VQ_EXP_RESIDENT_MIN_ROWS_PER_CU
@@ -403,20 +381,18 @@ constexpr int kWideRows = 32 * kWideWaves;                   // rows per workgro
 constexpr long long kWideChunkBytes = (long long)VQ_EXP_WIDE_CHUNK_MB << 20;  // accumulator workspace per (row chunk, code chunk)
 constexpr int kWideCodes = 4096;                    // codes per chunk
 
-template <int DP, int WIDE>
-int launch_wide_t(const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
-    if (metric == VQ_METRIC_EUCLID) return launch_search_t<DP, kWideWaves, VQ_METRIC_EUCLID, 0, false, 0, WIDE>(p, H, splits, s);
-    return launch_search_t<DP, kWideWaves, VQ_METRIC_DOT, 0, false, 0, WIDE>(p, H, splits, s);
-}
-
 // one slice of rows wider than 512 dims: WIDE = 1 a full slice (Dp = the slice width only), 2 / 3 the last slice
 template <int DP>
 int launch_wide_any(int wide, const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
-    if (wide == 1) {
-        if constexpr (DP >= 256) return launch_wide_t<DP, 1>(p, H, splits, metric, s);
-        return fail(VQ_E_UNSUPPORTED, "vq_search: a full slice of wide rows is 256 (or 512) dims");
-    }
-    return wide == 3 ? launch_wide_t<DP, 3>(p, H, splits, metric, s) : launch_wide_t<DP, 2>(p, H, splits, metric, s);
+    return with_metric(metric, [&](auto m) {
+        constexpr int ME = decltype(m)::value;
+        if (wide == 1) {
+            if constexpr (DP >= 256) return launch_search_t<DP, kWideWaves, ME, 0, false, 0, 1>(p, H, splits, s);
+            else return fail(VQ_E_UNSUPPORTED, "vq_search: a full slice of wide rows is 256 (or 512) dims");
+        }
+        return wide == 3 ? launch_search_t<DP, kWideWaves, ME, 0, false, 0, 3>(p, H, splits, s)
+                         : launch_search_t<DP, kWideWaves, ME, 0, false, 0, 2>(p, H, splits, s);
+    });
 }
 
 }  // namespace
@@ -431,7 +407,7 @@ template <int DP> int part_resident(const SearchParams &p, int H, int cus, int m
 template <int DP> int part_aux(const AuxParams &p, int H, int metric, int mode, hipStream_t s);
 template <int DP> int part_ce_bwd(const CeBwdParams &p, int H, int metric, hipStream_t s);
 int part_pair(const SearchParams &p, int H, int splits, int metric, hipStream_t s);
-int part_persist(const SearchParams &p, int H, int cus, int metric, hipStream_t s);
+int part_persist(const SearchChoice &c, const SearchParams &p, int H, int cus, int metric, hipStream_t s);
 #define VQ_DECLARE_PARTS(DP)                                                                                         \
     template <> int part_search<DP>(int waves, const SearchParams &p, int H, int splits, int metric, hipStream_t s); \
     template <> int part_wide<DP>(int wide, const SearchParams &p, int H, int splits, int metric, hipStream_t s);    \
@@ -469,11 +445,12 @@ VQ_DEFINE_RESIDENT_PART(128)
 #undef VQ_DEFINE_RESIDENT_PART
 #if VQ_OWN(3)
 VQ_DEFINE_SEARCH_PART(256, 4)
-int part_persist(const SearchParams &p, int H, int cus, int metric, hipStream_t s) {
-    if (p.scr) return launch_persist_t<VQ_METRIC_EUCLID, false, true>(p, H, cus, s);  // (screen_image_for: Euclid inference calls)
-    if (p.ste || p.loss_part)  // training-mode call: the deferred copy does the straight-through / squared-error arithmetic
-        return metric == VQ_METRIC_EUCLID ? launch_persist_t<VQ_METRIC_EUCLID, true>(p, H, cus, s) : launch_persist_t<VQ_METRIC_DOT, true>(p, H, cus, s);
-    return metric == VQ_METRIC_EUCLID ? launch_persist_t<VQ_METRIC_EUCLID>(p, H, cus, s) : launch_persist_t<VQ_METRIC_DOT>(p, H, cus, s);
+int part_persist(const SearchChoice &c, const SearchParams &p, int H, int cus, int metric, hipStream_t s) {
+    if (c.screened) return launch_persist_t<VQ_METRIC_EUCLID, false, true>(p, H, cus, s);  // (choose_search: Euclid inference calls)
+    return with_metric(metric, [&](auto m) {
+        constexpr int ME = decltype(m)::value;
+        return c.train ? launch_persist_t<ME, true>(p, H, cus, s) : launch_persist_t<ME>(p, H, cus, s);
+    });
 }
 #endif
 #if VQ_OWN(4)
@@ -484,12 +461,14 @@ template <> int part_wide<512>(int wide, const SearchParams &p, int H, int split
 #if VQ_EXP_WIDE_SLICE == 512
     // a 512-dim slice of wider rows: the wave-pair kernel (two waves per SIMD, accumulator hand-off) when the sweep is long
     // enough for its extra pipeline step, else the one-wave kernel
-    if (pair_selected(512, 1, p.tiles_per_split)) {
-        const bool eu = metric == VQ_METRIC_EUCLID;
-        if (wide == 1) return eu ? launch_pair_t<VQ_METRIC_EUCLID, false, 0, 1>(p, H, splits, s) : launch_pair_t<VQ_METRIC_DOT, false, 0, 1>(p, H, splits, s);
-        if (wide == 3) return eu ? launch_pair_t<VQ_METRIC_EUCLID, false, 0, 3>(p, H, splits, s) : launch_pair_t<VQ_METRIC_DOT, false, 0, 3>(p, H, splits, s);
-        return eu ? launch_pair_t<VQ_METRIC_EUCLID, false, 0, 2>(p, H, splits, s) : launch_pair_t<VQ_METRIC_DOT, false, 0, 2>(p, H, splits, s);
-    }
+    // (a slice is one stage at Dp = 512, so the choice is wave pairs or one block whatever the device: no CU count needed)
+    if (choose_search(512, kWideWaves, p, H, splits, metric, 0).kind == kPair)
+        return with_metric(metric, [&](auto m) {
+            constexpr int ME = decltype(m)::value;
+            if (wide == 1) return launch_pair_t<ME, false, 0, 1>(p, H, splits, s);
+            if (wide == 3) return launch_pair_t<ME, false, 0, 3>(p, H, splits, s);
+            return launch_pair_t<ME, false, 0, 2>(p, H, splits, s);
+        });
     return launch_wide_any<512>(wide, p, H, splits, metric, s);
 #else
     (void)wide; (void)p; (void)H; (void)splits; (void)metric; (void)s;
@@ -527,36 +506,20 @@ thread_local char g_err[512] = "";
 }
 namespace {
 
-// Plain inference call at Dp = 256 (one stage, no straight-through, no loss, aligned fp32 rows, >= 32 sub-tiles per sweep,
-// several row blocks per CU): persistent workgroups that copy block b's winners during block b + 1's sweep.
-// VQ_NO_PERSIST=1 in the environment keeps the one-block-per-workgroup kernel (A/B measurements).
-bool persist_selected(int DP, int waves, const SearchParams &p, int H, int splits, int cus) {
-    static const bool off = getenv("VQ_NO_PERSIST") != nullptr;
-    if (off || DP != 256 || waves != 8 || splits != 1 || p.Q != 1 || p.mode != kModeFused) return false;
-    if (p.lse || p.xt || !p.vec_x || !p.vec_fin || p.D % 4) return false;
-    if (!p.out && !p.loss_part) return false;  // (nothing to copy)
-    if ((p.ste || p.loss_part) && getenv("VQ_NO_PERSIST_TRAIN") != nullptr) return false;  // (A/B and tests: training-mode calls on the one-block kernel; read per call)
-    const int nsub = p.ntiles * sub_tiles(DP);
-    if (nsub < 32 || nsub > 96) return false;  // one row per sub-tile needs 32; beyond ~100 the finalize is < 1 % of a block
-    const long long nblk = (p.M + 32 * waves - 1) / (32 * waves);
-    return nblk * H >= 2ll * cus;  // at least two blocks per resident workgroup
-}
-
 bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
-// The screened sweep (vq_search_persist.inc, SCREEN) for a call the persistent kernel takes: Euclid, fp32 rows, inference
-// (no straight-through / loss), no winning distances requested.  Its bf16x3 images are built per call into the key area of
-// the workspace, which a fused call does not use, and behind them the list of rows that the second pass searches in full
-// (vq_resolve_rows_kernel); a call whose images and list do not fit there keeps the fp32 sweep.  Sets p.scr (or leaves it NULL).  VQ_NO_SCREEN in the environment keeps the fp32 sweep (read per call: tests compare both in one process).
-long long ws_keys_bytes(int H, long long M);
-void screen_image_for(SearchParams &p, const vq_args *a, int DP, int waves, int cus) {
-    p.scr = nullptr;
-    if (getenv("VQ_NO_SCREEN") != nullptr) return;
-    if (a->metric != VQ_METRIC_EUCLID || p.xt || p.ste || p.loss_part || p.best || p.lse) return;
-    if (!persist_selected(DP, waves, p, a->H, 1, cus)) return;
-    const long long img = scr_image_bytes(p.ntiles), rows = (long long)a->H * a->M;
-    // [images][count, 256 B][list of rows for the second pass: one uint32 per row of the call]
-    if (!a->workspace || (long long)a->H * img + 256 + 4 * rows > ws_keys_bytes(a->H, a->M) || img >= (1ll << 31) || rows >= (1ll << 31)) return;
+// 16-byte (float4) accesses: the pointer aligned to `align` bytes (16; 8 for 2-byte rows) and every stride -- or extent that
+// acts as one -- a multiple of 4 elements
+bool vec4_ok(const void *p, std::initializer_list<long long> strides, unsigned align = 16) {
+    for (const long long st : strides)
+        if (st % 4) return false;
+    return ((uintptr_t)p & (align - 1)) == 0;
+}
+
+// The screened sweep's bf16x3 images are built per call into the key area of the workspace, which a fused call does not use,
+// and behind them the list of rows that the second pass searches in full (vq_resolve_rows_kernel): the layout of screen_bytes.
+void set_screen_image(SearchParams &p, const vq_args *a) {
+    const long long img = scr_image_bytes(p.ntiles);
     p.scr = (const float *)a->workspace;
     p.scr_hs = img;
     p.scr_bytes = (unsigned)img;
@@ -571,8 +534,8 @@ int resident_image_for(const vq_args *a, int DP, bool lse, int cus) {
     static const bool off = getenv("VQ_NO_RESIDENT") != nullptr;
     if (off || DP == 0 || DP > 128 || a->Q != 1 || lse || a->sq_err || !a->out || !a->idx || !a->cb || !a->packed) return 0;
     if (a->flags & (VQ_F_STE | VQ_F_FORCE_SIMPLE | VQ_F_FORCE_SPLIT | VQ_F_X_F16 | VQ_F_X_BF16)) return 0;
-    if (a->D % 16 || a->x_rs % 4 || a->x_hs % 4 || !aligned16(a->x)) return 0;
-    if (a->out_rs % 4 || a->out_hs % 4 || !aligned16(a->out) || a->cb_hs % 4 || !aligned16(a->cb)) return 0;
+    if (a->D % 16 || !vec4_ok(a->x, {a->x_rs, a->x_hs})) return 0;
+    if (!vec4_ok(a->out, {a->out_rs, a->out_hs}) || !vec4_ok(a->cb, {a->cb_hs})) return 0;
     const int nsub_k = (a->K + kTileCodes - 1) / kTileCodes;
     if (nsub_k < DP / 16) return 0;  // (the sweep's first Dp / 16 sub-tiles carry the next block's slabs)
     if (nsub_k > 8) return 0;        // measured (gpurun_out/r3/t5_res_ab.log): from K = 512 on the tile-streaming kernels are ahead again
@@ -583,54 +546,32 @@ int resident_image_for(const vq_args *a, int DP, bool lse, int cus) {
     return img;
 }
 
-int launch_search(int DP, int waves, const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
-    {
-        const DevInfo &di = dev_info();
-        const int cus = di.ok && di.cus > 0 ? di.cus : 256;
-        if (p.res_img_floats > 0 && splits == 1 && p.mode == kModeFused) {
-            switch (DP) {
-                case 32: return vqi::part_resident<32>(p, H, cus, metric, s);
-                case 64: return vqi::part_resident<64>(p, H, cus, metric, s);
-                case 128: return vqi::part_resident<128>(p, H, cus, metric, s);
-            }
-        }
-        if (persist_selected(DP, waves, p, H, splits, cus))
-            return vqi::part_persist(p, H, cus, metric, s);
-    }
-    if (pair_selected(DP, p.Q, p.tiles_per_split)) return vqi::part_pair(p, H, splits, metric, s);  // single stage: wave pairs
-    switch (DP) {
-        case 32: return vqi::part_search<32>(waves, p, H, splits, metric, s);
-        case 64: return vqi::part_search<64>(waves, p, H, splits, metric, s);
-        case 128: return vqi::part_search<128>(waves, p, H, splits, metric, s);
-        case 256: return vqi::part_search<256>(waves, p, H, splits, metric, s);
-        case 512: return vqi::part_search<512>(waves, p, H, splits, metric, s);
+// launches the kernel that choose_search picked for (DP, p, H, splits)
+int launch_search(const SearchChoice &c, int DP, const SearchParams &p, int H, int splits, int metric, int cus, hipStream_t s) {
+    switch (c.kind) {
+        case kResident:  // (resident images exist for Dp <= 128 only)
+            if (DP == 32) return vqi::part_resident<32>(p, H, cus, metric, s);
+            if (DP == 64) return vqi::part_resident<64>(p, H, cus, metric, s);
+            if (DP == 128) return vqi::part_resident<128>(p, H, cus, metric, s);
+            break;
+        case kPersist: return vqi::part_persist(c, p, H, cus, metric, s);
+        case kPair: return vqi::part_pair(p, H, splits, metric, s);
+        case kOneBlock:
+            return with_padded_dim(DP, [&](auto dp) { return vqi::part_search<decltype(dp)::value>(c.waves, p, H, splits, metric, s); },
+                                   [] { return fail(VQ_E_UNSUPPORTED, "vq_search: unsupported padded dim"); });
     }
     return fail(VQ_E_UNSUPPORTED, "vq_search: unsupported padded dim");
 }
 
-
 int launch_aux(int DP, const AuxParams &p, int H, int metric, int mode, hipStream_t s) {
-    switch (DP) {
-        case 32: return vqi::part_aux<32>(p, H, metric, mode, s);
-        case 64: return vqi::part_aux<64>(p, H, metric, mode, s);
-        case 128: return vqi::part_aux<128>(p, H, metric, mode, s);
-        case 256: return vqi::part_aux<256>(p, H, metric, mode, s);
-        case 512: return vqi::part_aux<512>(p, H, metric, mode, s);
-    }
-    return fail(VQ_E_UNSUPPORTED, "vq_sweep_aux: unsupported padded dim");
+    return with_padded_dim(DP, [&](auto dp) { return vqi::part_aux<decltype(dp)::value>(p, H, metric, mode, s); },
+                           [] { return fail(VQ_E_UNSUPPORTED, "vq_sweep_aux: unsupported padded dim"); });
 }
-
 
 // one slice of a wide-row sweep, by the padded width of the slice
 int launch_wide(int wide, int DP, const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
-    switch (DP) {
-        case 32: return vqi::part_wide<32>(wide, p, H, splits, metric, s);
-        case 64: return vqi::part_wide<64>(wide, p, H, splits, metric, s);
-        case 128: return vqi::part_wide<128>(wide, p, H, splits, metric, s);
-        case 256: return vqi::part_wide<256>(wide, p, H, splits, metric, s);
-        case 512: return vqi::part_wide<512>(wide, p, H, splits, metric, s);
-    }
-    return fail(VQ_E_UNSUPPORTED, "vq_search: unsupported padded dim");
+    return with_padded_dim(DP, [&](auto dp) { return vqi::part_wide<decltype(dp)::value>(wide, p, H, splits, metric, s); },
+                           [] { return fail(VQ_E_UNSUPPORTED, "vq_search: unsupported padded dim"); });
 }
 
 int check_common(const vq_args *a) {
@@ -678,10 +619,8 @@ void fill_search_params(SearchParams &p, const vq_args *a) {
 
     p.ste = (a->flags & VQ_F_STE) ? 1 : 0;
     p.xt = (a->flags & VQ_F_X_F16) ? 1 : ((a->flags & VQ_F_X_BF16) ? 2 : 0);
-    p.vec_x = (a->D % 4 == 0 && a->x_rs % 4 == 0 && a->x_hs % 4 == 0 &&
-               (p.xt ? (((uintptr_t)a->x & 7) == 0) : aligned16(a->x))) ? 1 : 0;
-    p.vec_fin = (p.vec_x && (!a->out || (a->out_rs % 4 == 0 && a->out_hs % 4 == 0 && aligned16(a->out))) &&
-                 (!a->cb || (a->cb_hs % 4 == 0 && a->cb_qs % 4 == 0 && aligned16(a->cb)))) ? 1 : 0;
+    p.vec_x = vec4_ok(a->x, {a->D, a->x_rs, a->x_hs}, p.xt ? 8 : 16) ? 1 : 0;  // (2-byte rows: four of them are 8 bytes)
+    p.vec_fin = (p.vec_x && (!a->out || vec4_ok(a->out, {a->out_rs, a->out_hs})) && (!a->cb || vec4_ok(a->cb, {a->cb_hs, a->cb_qs}))) ? 1 : 0;
 }
 
 // one stage of a residual stack run stage by stage (residual_tail_staged): where the next residual goes, whether `out` accumulates
@@ -709,18 +648,30 @@ int run_finalize(const vq_args *a, const long long *keys, float *loss_part, hipS
     f.best = a->best;
     f.loss_part = loss_part;
     f.M = a->M; f.D = a->D; f.metric = a->metric; f.ste = (a->flags & VQ_F_STE) ? 1 : 0;
-    f.vec = (a->D % 4 == 0 && a->cb_hs % 4 == 0 && aligned16(a->cb) && (!a->out || (a->out_rs % 4 == 0 && a->out_hs % 4 == 0 && aligned16(a->out))) &&
-             (!(f.ste || loss_part || f.res_next) || (a->x_rs % 4 == 0 && a->x_hs % 4 == 0 && aligned16(a->x))) &&
+    f.vec = (vec4_ok(a->cb, {a->D, a->cb_hs}) && (!a->out || vec4_ok(a->out, {a->out_rs, a->out_hs})) &&
+             (!(f.ste || loss_part || f.res_next) || vec4_ok(a->x, {a->x_rs, a->x_hs})) &&  // (x is read for these only)
              (!f.res_next || aligned16(f.res_next))) ? 1 : 0;
     long long blocks = (a->M + 3) / 4;
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
-    if (rst) hipLaunchKernelGGL(vq_finalize_kernel<true>, dim3((unsigned)blocks, (unsigned)a->H), dim3(256), 0, s, f);
-    else hipLaunchKernelGGL(vq_finalize_kernel<false>, dim3((unsigned)blocks, (unsigned)a->H), dim3(256), 0, s, f);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_finalize launch");
+    const dim3 grid((unsigned)blocks, (unsigned)a->H);
+    const int rc = rst ? launch<vq_finalize_kernel<true>>(grid, dim3(256), 0, s, "vq_finalize launch", f)
+                       : launch<vq_finalize_kernel<false>>(grid, dim3(256), 0, s, "vq_finalize launch", f);
+    if (rc) return rc;
     if (nparts_out) *nparts_out = (int)(blocks * 4 * a->H);
     return 0;
+}
+
+// sums the loss partials of a launch: grid = (stages, heads or 1); `sq_err_hs` > 0: the heads' sums that many doubles apart
+int reduce_loss(dim3 grid, hipStream_t s, const float *part, long long nparts, int Q, double *sq_err, int acc, int sq_err_hs = -1) {
+    return launch<vq_loss_reduce_kernel>(grid, dim3(256), 0, s, "vq_loss_reduce launch", part, nparts, Q, sq_err, acc, sq_err_hs);
+}
+
+// squared-error sums of a call: one per stage, per head with VQ_F_SQERR_PER_HEAD
+inline size_t sq_err_count(const vq_args *a) { return (size_t)a->Q * ((a->flags & VQ_F_SQERR_PER_HEAD) ? a->H : 1); }
+int clear_sq_err(double *sq_err, size_t n, hipStream_t s, const char *what) {
+    const hipError_t e = hipMemsetAsync(sq_err, 0, sizeof(double) * n, s);
+    return e == hipSuccess ? 0 : hip_fail(e, what);
 }
 
 // Rows per workgroup of the fused single-stage launch: 256 (8 waves x 32), 128 (4 wave pairs / 4 waves) at Dp = 512.
@@ -768,15 +719,23 @@ int plan_k_split(int DP, int H, long long M, int K, int D, int cus, double *cost
     return best_s;
 }
 
+// The cut of a grid of `nblk_h` row blocks per head into whole rounds of `cus` workgroups that are also whole row blocks of
+// every head (every head gets the same cut), and the workgroups left for a last, partly filled round.
+struct RoundsCut {
+    long long full, rem;
+};
+inline RoundsCut whole_rounds(long long nblk_h, int H, int cus) {
+    long long full = nblk_h * H / cus;
+    while (full > 0 && (full * cus) % H) --full;
+    return {full, nblk_h * H - full * cus};
+}
+
 // Third remedy for the same quantisation: the row blocks that fill whole rounds run fused, the
 // remainder (fewer blocks than CUs) is searched by a second call, which splits K until the chip is full -- a short round
 // instead of a whole one.  Returns the rows of the fused part, 0 when the model does not predict >= 5 % over both alternatives.
 long long plan_main_tail(int DP, int H, long long M, int K, int D, int cus) {
     const int rpw = fused_rows_per_wg(DP);
-    const long long nblk_h = (M + rpw - 1) / rpw;  // row blocks per head; every head gets the same cut
-    long long full = nblk_h * H / cus;
-    while (full > 0 && (full * cus) % H) --full;   // whole rounds that are also whole row blocks of every head
-    const long long rem = nblk_h * H - full * cus;
+    const auto [full, rem] = whole_rounds((M + rpw - 1) / rpw, H, cus);
     const int nsub = (K + kTileCodes - 1) / kTileCodes;
     if (full < 1 || rem == 0 || rem >= cus || nsub < 8) return 0;
     double plan_cost = 0.0, fused_cost = 0.0;
@@ -839,10 +798,9 @@ bool wide_workspace_ok(const vq_args *a) {
 bool wide_fusable(const vq_args *a) {
     if (a->Q != 1 || (a->flags & (VQ_F_STE | VQ_F_FORCE_SPLIT | VQ_F_FORCE_SIMPLE)) || a->sq_err || !a->out || !a->idx || !a->cb)
         return false;
-    if (a->D % 4 || a->out_rs % 4 || a->out_hs % 4 || !aligned16(a->out) || a->cb_hs % 4 || !aligned16(a->cb)) return false;
+    if (!vec4_ok(a->out, {a->D, a->out_rs, a->out_hs}) || !vec4_ok(a->cb, {a->cb_hs})) return false;
     if (round_up(a->K, kTileCodes) > kWideCodes) return false;
-    const DevInfo &di = dev_info();
-    const int cus = di.ok && di.cus > 0 ? di.cus : 256;
+    const int cus = device_cus();
     const WidePlan w = wide_plan(a->H, a->M, a->K, a->D);
     const long long last_rows = a->M % w.mc ? a->M % w.mc : w.mc;  // the smallest row chunk
     if (((last_rows + kWideRows - 1) / kWideRows) * a->H < cus) return false;
@@ -863,8 +821,7 @@ int run_wide(const vq_args *a, long long idx_offset, long long *keys, float *sim
         return fail(VQ_E_BADARG, "vq: workspace too small for rows wider than 512 dims (see vq_workspace_bytes_wide)");
     float *acc_ws = (float *)((char *)a->workspace + base);
     float *xn_ws = (float *)((char *)a->workspace + base + w.acc_bytes);
-    const DevInfo &di = dev_info();
-    const int cus = di.ok && di.cus > 0 ? di.cus : 256;
+    const int cus = device_cus();
     const int Kp = round_up(a->K, kTileCodes);
     const int d_last = wide_last_dims(a->D), dp_last = padded_dim(d_last);
     for (long long m0 = 0; m0 < a->M; m0 += w.mc) {
@@ -913,7 +870,7 @@ int run_wide(const vq_args *a, long long idx_offset, long long *keys, float *sim
                 p.keys = keys ? keys + m0 : nullptr;
                 p.key_hs = a->M;
                 p.idx_offset = idx_offset + k0;
-                p.vec_x = (p.D % 4 == 0 && a->x_rs % 4 == 0 && a->x_hs % 4 == 0 && aligned16(a->x)) ? 1 : 0;
+                p.vec_x = vec4_ok(a->x, {p.D, a->x_rs, a->x_hs}) ? 1 : 0;
                 p.acc_ws = acc_ws;
                 p.ws_hs = nblk * kWideWaves * (long long)nsub * 256;
                 p.ws_nsub = nsub;
@@ -924,7 +881,7 @@ int run_wide(const vq_args *a, long long idx_offset, long long *keys, float *sim
                 if (sims) {
                     p.sims = sims + m0 * sims_rs + k0;
                     p.sims_rs = sims_rs; p.sims_hs = sims_hs;
-                    p.vec_s = (a->K % 4 == 0 && sims_rs % 4 == 0 && sims_hs % 4 == 0 && aligned16(sims)) ? 1 : 0;
+                    p.vec_s = vec4_ok(sims, {a->K, sims_rs, sims_hs}) ? 1 : 0;
                 }
                 const int rc = launch_wide(!last ? 1 : (sims ? 3 : 2), DP, p, a->H, splits, a->metric, s);
                 if (rc) return rc;
@@ -936,6 +893,19 @@ int run_wide(const vq_args *a, long long idx_offset, long long *keys, float *sim
 
 // How a keys-mode search of `a` is launched on this device: workgroup size and the number of K splits (= key planes when the
 // splits store into planes of their own instead of combining with atomic MIN).
+// Workgroup size of the one-block kernel and the workgroups of its grid: 8 waves (4 at Dp = 512: LDS), or 4 when the 8-wave
+// grid leaves CUs empty.
+struct WaveGrid {
+    int waves;
+    long long wgs;
+};
+inline WaveGrid wave_grid(int DP, int H, long long M, int cus, bool may_halve = true) {
+    WaveGrid g = {DP == 512 ? 4 : 8, 0};
+    g.wgs = H * one_block_grid_x(M, g.waves);
+    if (may_halve && g.waves == 8 && g.wgs < cus) g = {4, H * one_block_grid_x(M, 4)};
+    return g;
+}
+
 struct KeysPlan {
     int DP, waves, splits, tiles_per_split;
     bool mfma;  // false: the one-thread-per-row kernel / the sliced sweep of wide rows (one plane, atomic MIN)
@@ -949,16 +919,12 @@ KeysPlan plan_keys(const vq_args *a, int planned_splits) {
     k.splits = 1;
     k.tiles_per_split = 1;
     if (!k.mfma) return k;
-    const DevInfo &di = dev_info();
-    const int cus = di.ok && di.cus > 0 ? di.cus : 256;
+    const int cus = device_cus();
     const int tc = kTileCodes * sub_tiles(k.DP);
     const int ntiles = (a->K + tc - 1) / tc;
-    k.waves = (k.DP == 512) ? 4 : 8;
-    long long wgs = (long long)a->H * ((a->M + 32 * k.waves - 1) / (32 * k.waves));
-    if (k.waves == 8 && wgs < cus && planned_splits == 0) {
-        k.waves = 4;
-        wgs = (long long)a->H * ((a->M + 127) / 128);
-    }
+    const WaveGrid g = wave_grid(k.DP, a->H, a->M, cus, /*may_halve=*/planned_splits == 0);  // (plan_k_split: full-size workgroups)
+    k.waves = g.waves;
+    const long long wgs = g.wgs;
     // K is split until the chip is full: two 4-wave workgroups fit a CU at Dp <= 256, one (LDS) at Dp = 512 -- splitting
     // further only repeats the prologue and, in the wave-pair kernel, the extra pipeline step
     const long long fill = (long long)cus * (k.DP == 512 ? 1 : 2);
@@ -984,16 +950,10 @@ int run_search_keys(const vq_args *a, long long idx_offset, long long *keys, hip
     if (kp.DP == 0 && !(a->flags & VQ_F_FORCE_SIMPLE)) return run_wide(a, idx_offset, keys, nullptr, 0, 0, s);
     if (!kp.mfma) {
         if (!a->cb) return fail(VQ_E_BADARG, "vq: natural codebook required for the scalar kernel");
-        dim3 grid((unsigned)((a->M + 63) / 64), (unsigned)a->H);
-        if (a->metric == VQ_METRIC_EUCLID)
-            hipLaunchKernelGGL(vq_search_simple<VQ_METRIC_EUCLID>, grid, dim3(64), 0, s, a->x, a->x_rs, a->x_hs, a->cb,
-                               a->cb_hs, a->M, a->K, a->D, idx_offset, keys);
-        else
-            hipLaunchKernelGGL(vq_search_simple<VQ_METRIC_DOT>, grid, dim3(64), 0, s, a->x, a->x_rs, a->x_hs, a->cb,
-                               a->cb_hs, a->M, a->K, a->D, idx_offset, keys);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "vq_search_simple launch");
-        return 0;
+        return with_metric(a->metric, [&](auto m) {
+            return launch<vq_search_simple<decltype(m)::value>>(dim3((unsigned)((a->M + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_search_simple launch",
+                                                                a->x, a->x_rs, a->x_hs, a->cb, a->cb_hs, a->M, a->K, a->D, idx_offset, keys);
+        });
     }
     if (!a->packed) return fail(VQ_E_BADARG, "vq: packed codebook is null");
     if (vq_packed_floats(a->K, a->D) * 4 >= (1ll << 31))
@@ -1008,7 +968,8 @@ int run_search_keys(const vq_args *a, long long idx_offset, long long *keys, hip
     p.out = nullptr;
     p.loss_part = nullptr;
     p.tiles_per_split = kp.tiles_per_split;
-    return launch_search(kp.DP, kp.waves, p, a->H, kp.splits, a->metric, s);
+    const int cus = device_cus();  // (a keys-mode search is never a whole fused call: wave pairs or one block)
+    return launch_search(choose_search(kp.DP, kp.waves, p, a->H, kp.splits, a->metric, cus), kp.DP, p, a->H, kp.splits, a->metric, cus, s);
 }
 
 }  // namespace
@@ -1079,34 +1040,27 @@ int vq_pack_codebooks_f32(const float *cb, int n_codebooks, int64_t cb_stride, i
         for (int j = 0; j < nd; ++j) {
             const int dp = (j + 1 == nd) ? padded_dim(wide_last_dims(D)) : kWideSlice;
             const int Kp = round_up(K, kTileCodes * sub_tiles(dp));
-            hipLaunchKernelGGL(vq_pack_kernel, dim3(Kp / 64 + 1, n_codebooks), dim3(64), 0, s, cb, (long long)cb_stride, K, Kp,
-                               D, j * kWideSlice, dp, metric, packed + (long long)j * wide_image_floats(K), pk_stride);
+            if (int rc = launch<vq_pack_kernel>(dim3(Kp / 64 + 1, n_codebooks), dim3(64), 0, s, "vq_pack launch", cb, (long long)cb_stride, K, Kp, D,
+                                                j * kWideSlice, dp, metric, packed + (long long)j * wide_image_floats(K), pk_stride))
+                return rc;
         }
-        hipLaunchKernelGGL(vq_pack_flag_kernel, dim3(n_codebooks), dim3(256), 0, s, packed, pk_stride, K, kWideSlice + 4, kWideSlice,
-                           nd, wide_image_floats(K), wide_last_image_floats(K, D));
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "vq_pack launch");
-        return 0;
+        return launch<vq_pack_flag_kernel>(dim3(n_codebooks), dim3(256), 0, s, "vq_pack launch", packed, pk_stride, K, kWideSlice + 4, kWideSlice, nd,
+                                           wide_image_floats(K), wide_last_image_floats(K, D));
     }
     const int Kp = round_up(K, kTileCodes * sub_tiles(DP));
     // grid covers Kp rows plus at least one extra block whose threads zero the over-copy slack
-    hipLaunchKernelGGL(vq_pack_kernel, dim3(Kp / 64 + 1, n_codebooks), dim3(64), 0, s, cb, (long long)cb_stride, K, Kp,
-                       D, 0, DP, metric, packed, pk_stride);
-    hipLaunchKernelGGL(vq_pack_flag_kernel, dim3(n_codebooks), dim3(256), 0, s, packed, pk_stride, K, DP + 4, DP, 1, pk_stride,
-                       (long long)vq_packed_floats(K, D));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_pack launch");
-    return 0;
+    if (int rc = launch<vq_pack_kernel>(dim3(Kp / 64 + 1, n_codebooks), dim3(64), 0, s, "vq_pack launch", cb, (long long)cb_stride, K, Kp, D, 0, DP,
+                                        metric, packed, pk_stride))
+        return rc;
+    return launch<vq_pack_flag_kernel>(dim3(n_codebooks), dim3(256), 0, s, "vq_pack launch", packed, pk_stride, K, DP + 4, DP, 1, pk_stride,
+                                       (long long)vq_packed_floats(K, D));
 }
 
 int vq_keys_init(int64_t *keys, int64_t n, void *stream) {
     if (!keys || n < 0) return fail(VQ_E_BADARG, "vq_keys_init: bad argument");
     if (n == 0) return 0;
-    hipLaunchKernelGGL(vq_keys_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (long long *)keys, (long long)n);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_keys_init launch");
-    return 0;
+    return launch<vq_keys_init_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, "vq_keys_init launch", (long long *)keys,
+                                       (long long)n);
 }
 
 int vq_search_keys_f32(const vq_args *a, int64_t idx_offset, int64_t *keys, void *stream) {
@@ -1152,8 +1106,7 @@ int vq_finalize_key_planes_f32(const vq_args *a, const int64_t *keys, int n_plan
     if (a->Q != 1) return fail(VQ_E_BADARG, "vq_finalize_keys: Q must be 1");
     if (!keys || !a->cb) return fail(VQ_E_BADARG, "vq_finalize_keys: keys / cb is null");
     if (a->M == 0) {
-        if (a->sq_err) hipMemsetAsync(a->sq_err, 0, sizeof(double), (hipStream_t)stream);
-        return 0;
+        return a->sq_err ? clear_sq_err(a->sq_err, 1, (hipStream_t)stream, "vq_finalize_keys: clearing sq_err") : 0;
     }
     hipStream_t s = (hipStream_t)stream;
     float *loss_part = nullptr;
@@ -1165,15 +1118,10 @@ int vq_finalize_key_planes_f32(const vq_args *a, const int64_t *keys, int n_plan
     int nparts = 0;
     rc = run_finalize(a, (const long long *)keys, loss_part, s, &nparts, n_planes);
     if (rc) return rc;
-    if (a->sq_err) {
-        hipLaunchKernelGGL(vq_loss_reduce_kernel, dim3(1), dim3(256), 0, s, loss_part, (long long)nparts, 1, a->sq_err);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "vq_loss_reduce launch");
-    }
-    return 0;
+    return a->sq_err ? reduce_loss(dim3(1), s, loss_part, nparts, 1, a->sq_err, 0) : 0;
 }
 
-constexpr uint32_t kFlagAccumulateSqErr = 0x80000000u;  // never set by callers: vq_quantize_f32 masks it off
+constexpr uint32_t kFlagAccumulateSqErr = 0x80000000u;  // never set by callers: quantize_entry masks it off
 
 // A single stage as  search into key planes (K split over workgroups: every split stores its winners into a plane of its own, no
 // init launch, no atomics; one plane + atomic MIN if the planes do not fit the workspace)  +  finalize (MIN over the planes,
@@ -1197,15 +1145,10 @@ static int split_stage(const vq_args *a, int planned_splits, int acc, void *stre
     int nparts = 0;
     rc = run_finalize(a, keys, a->sq_err ? loss_part : nullptr, s, &nparts, planes, rst);
     if (rc) return rc;
-    if (a->sq_err) {
-        if (sq_err_hs > 0)  // the finalize's partials are [head][nparts / H]
-            hipLaunchKernelGGL(vq_loss_reduce_kernel, dim3(1, a->H), dim3(256), 0, s, loss_part, (long long)(nparts / a->H), 1, a->sq_err, acc, sq_err_hs);
-        else
-            hipLaunchKernelGGL(vq_loss_reduce_kernel, dim3(1), dim3(256), 0, s, loss_part, (long long)nparts, 1, a->sq_err, acc);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "vq_loss_reduce launch");
-    }
-    return 0;
+    if (!a->sq_err) return 0;
+    if (sq_err_hs > 0)  // the finalize's partials are [head][nparts / H]
+        return reduce_loss(dim3(1, a->H), s, loss_part, nparts / a->H, 1, a->sq_err, acc, sq_err_hs);
+    return reduce_loss(dim3(1), s, loss_part, nparts, 1, a->sq_err, acc);
 }
 
 // ---- residual stacks whose row count leaves the last round of workgroups mostly empty -------------------------------------
@@ -1221,10 +1164,7 @@ static long long plan_residual_tail(const vq_args *a, int DP, int cus) {
     if (a->Q < 2 || DP == 0 || (a->flags & (VQ_F_FORCE_SIMPLE | VQ_F_FORCE_SPLIT))) return -1;
     if (getenv("VQ_NO_RESIDUAL_TAIL") != nullptr) return -1;  // (read per call: tests run both plans in one process)
     const int rpw = fused_rows_per_wg(DP);  // 256 (128 at Dp = 512)
-    const long long nblk_h = (a->M + rpw - 1) / rpw;
-    long long full = nblk_h * a->H / cus;
-    while (full > 0 && (full * cus) % a->H) --full;  // whole rounds that are whole row blocks of every head
-    const long long rem = nblk_h * a->H - full * cus;  // workgroups of the last, partly filled round
+    const auto [full, rem] = whole_rounds((a->M + rpw - 1) / rpw, a->H, cus);
     if (rem == 0) return -1;
     const long long m1 = full * cus / a->H * rpw, mt = a->M - m1;
     if (mt <= 0 || (long long)a->H * mt * a->D * 4 > residual_tail_room(a->H, a->M, a->Q)) return -1;  // (no room for the residual rows)
@@ -1285,10 +1225,7 @@ static int quantize_impl(const vq_args *a, void *stream, float *lse) {
         return fail(VQ_E_UNSUPPORTED, "vq_quantize: 2-byte rows are inference only (Q == 1, D <= 512, no STE / sq_err / lse)");
     if (a->M > 0 && !a->idx) return fail(VQ_E_BADARG, "vq_quantize: idx is null");
     if (a->M > 0 && !a->cb) return fail(VQ_E_BADARG, "vq_quantize: natural codebook is null");
-    if (a->M == 0) {
-        if (a->sq_err) hipMemsetAsync(a->sq_err, 0, sizeof(double) * a->Q * ((a->flags & VQ_F_SQERR_PER_HEAD) ? a->H : 1), s);
-        return 0;
-    }
+    if (a->M == 0) return a->sq_err ? clear_sq_err(a->sq_err, sq_err_count(a), s, "vq_quantize: clearing sq_err") : 0;
     if (!a->workspace || a->workspace_bytes < vq_workspace_bytes(a->H, a->M, a->Q))
         return fail(VQ_E_BADARG, "vq_quantize: workspace too small (see vq_workspace_bytes)");
     long long *keys = (long long *)a->workspace;
@@ -1296,8 +1233,7 @@ static int quantize_impl(const vq_args *a, void *stream, float *lse) {
 
     const int DP = padded_dim(a->D);
     const bool simple = (a->flags & VQ_F_FORCE_SIMPLE) || DP == 0;
-    const DevInfo &di = dev_info();
-    const int cus = di.ok && di.cus > 0 ? di.cus : 256;
+    const int cus = device_cus();
 
     const int acc = (a->flags & kFlagAccumulateSqErr) ? 1 : 0;  // (internal: second call of a two-call plan adds its sum)
     const int res_img = (simple || acc) ? 0 : resident_image_for(a, DP, lse != nullptr, cus);
@@ -1328,8 +1264,8 @@ static int quantize_impl(const vq_args *a, void *stream, float *lse) {
                 rc = quantize_impl(&a1, stream, nullptr);
                 if (rc) return rc;
             } else if (a->sq_err) {  // (no fused part: the stages ADD their sums)
-                hipError_t e = hipMemsetAsync(a->sq_err, 0, sizeof(double) * a->Q * ((a->flags & VQ_F_SQERR_PER_HEAD) ? a->H : 1), s);
-                if (e != hipSuccess) return hip_fail(e, "vq_quantize: clearing sq_err");
+                rc = clear_sq_err(a->sq_err, sq_err_count(a), s, "vq_quantize: clearing sq_err");
+                if (rc) return rc;
             }
             return residual_tail_staged(a, m1, stream);
         }
@@ -1340,11 +1276,9 @@ static int quantize_impl(const vq_args *a, void *stream, float *lse) {
     int planned_splits = 0;
     int waves = (DP == 512) ? 4 : 8;
     if (fused) {
-        long long wgs = (long long)a->H * ((a->M + 32 * waves - 1) / (32 * waves));
-        if (waves == 8 && wgs < cus) {
-            waves = 4;
-            wgs = (long long)a->H * ((a->M + 127) / 128);
-        }
+        const WaveGrid g = wave_grid(DP, a->H, a->M, cus);
+        waves = g.waves;
+        long long wgs = g.wgs;
         // Residual stacks cannot split K (every stage needs the whole codebook per row), so a row count just above a multiple of
         // cus x 256 used to pay a whole extra round of 8-wave workgroups.  Two 4-wave workgroups share a CU at the pace of one
         // 8-wave workgroup, and a LONE 4-wave workgroup (one wave per SIMD: the matrix pipe to itself) finishes its 128 rows in
@@ -1392,21 +1326,14 @@ static int quantize_impl(const vq_args *a, void *stream, float *lse) {
             const size_t full = ((size_t)res_img + 8 * (DP / 16) * 512) * 4 + 2 * 8 * 32 * 4;  // a slab buffer per slab of a block
             p.res_nbuf = (DP < 128 && full <= 160 * 1024) ? DP / 16 : 1;
         }
-        if (!res_img) screen_image_for(p, a, DP, waves, cus);
-        rc = launch_search(DP, waves, p, a->H, 1, a->metric, s);
-        if (rc) return rc;
-        if (a->sq_err) {
-            const bool pair = pair_selected(DP, a->Q, p.tiles_per_split);  // 8 waves (4 pairs) per 128 rows, one partial per wave
-            const bool pers = !res_img && persist_selected(DP, waves, p, a->H, 1, cus);  // one partial per wave of the resident workgroups
-            const long long rows_per_wg = pair ? 128 : 32ll * waves;
-            const long long per_head = pers ? persist_grid_x(a->M, a->H, cus) * 8 : ((a->M + rows_per_wg - 1) / rows_per_wg) * (pair ? 8 : waves);
-            const bool by_head = (a->flags & VQ_F_SQERR_PER_HEAD) != 0;
-            hipLaunchKernelGGL(vq_loss_reduce_kernel, dim3(a->Q, by_head ? a->H : 1), dim3(256), 0, s, loss_part,
-                               by_head ? per_head : per_head * a->H, a->Q, a->sq_err, acc);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return hip_fail(e, "vq_loss_reduce launch");
-        }
-        return 0;
+        // the one decision which kernel runs this call: the screen images, the launch and the partials' count all follow it
+        const SearchChoice c = choose_search(DP, waves, p, a->H, 1, a->metric, cus, /*scr_room=*/ws_keys_bytes(a->H, a->M));
+        if (c.screened) set_screen_image(p, a);
+        rc = launch_search(c, DP, p, a->H, 1, a->metric, cus, s);
+        if (rc || !a->sq_err) return rc;
+        const long long per_head = loss_partials_per_head(c, a->M, a->H, cus);
+        const bool by_head = (a->flags & VQ_F_SQERR_PER_HEAD) != 0;
+        return reduce_loss(dim3(a->Q, by_head ? a->H : 1), s, loss_part, by_head ? per_head : per_head * a->H, a->Q, a->sq_err, acc);
     }
 
     if (DP == 0 && wide_fusable(a)) return run_wide(a, 0, nullptr, nullptr, 0, 0, s, true);
@@ -1416,23 +1343,21 @@ static int quantize_impl(const vq_args *a, void *stream, float *lse) {
     return split_stage(a, fused ? 0 : planned_splits, acc, stream, nullptr);
 }
 
-int vq_quantize_f32(const vq_args *a, void *stream) {
-    if (a && (a->flags & kFlagAccumulateSqErr)) {
-        vq_args b = *a;
-        b.flags &= ~kFlagAccumulateSqErr;
-        return quantize_impl(&b, stream, nullptr);
-    }
-    return quantize_impl(a, stream, nullptr);
-}
-
-int vq_quantize_lse_f32(const vq_args *a, float *lse, void *stream) {
-    if (!lse && a && a->M > 0) return fail(VQ_E_BADARG, "vq_quantize_lse: lse is null");
+// the public entries: kFlagAccumulateSqErr is internal, a caller's copy of the bit is dropped
+static int quantize_entry(const vq_args *a, void *stream, float *lse) {
     if (a && (a->flags & kFlagAccumulateSqErr)) {
         vq_args b = *a;
         b.flags &= ~kFlagAccumulateSqErr;
         return quantize_impl(&b, stream, lse);
     }
     return quantize_impl(a, stream, lse);
+}
+
+int vq_quantize_f32(const vq_args *a, void *stream) { return quantize_entry(a, stream, nullptr); }
+
+int vq_quantize_lse_f32(const vq_args *a, float *lse, void *stream) {
+    if (!lse && a && a->M > 0) return fail(VQ_E_BADARG, "vq_quantize_lse: lse is null");
+    return quantize_entry(a, stream, lse);
 }
 
 int vq_quantize_backward_f32(const vq_args *a, const float *grad_out, int64_t go_rs, int64_t go_hs, const double *grad_sq_err,
@@ -1451,15 +1376,11 @@ int vq_quantize_backward_f32(const vq_args *a, const float *grad_out, int64_t go
     p.g_err_hs = (a->flags & VQ_F_SQERR_PER_HEAD) ? a->Q : 0;
     p.gx = grad_x; p.gx_rs = gx_rs; p.gx_hs = gx_hs;
     p.M = a->M; p.D = a->D; p.Q = a->Q; p.ste = (a->flags & VQ_F_STE) ? 1 : 0;
-    p.vec = (a->D % 4 == 0 && a->x_rs % 4 == 0 && a->x_hs % 4 == 0 && aligned16(a->x) && gx_rs % 4 == 0 && gx_hs % 4 == 0 &&
-             aligned16(grad_x) && a->cb_hs % 4 == 0 && a->cb_qs % 4 == 0 && aligned16(a->cb) &&
-             (!grad_out || (go_rs % 4 == 0 && go_hs % 4 == 0 && aligned16(grad_out)))) ? 1 : 0;
+    p.vec = (vec4_ok(a->x, {a->D, a->x_rs, a->x_hs}) && vec4_ok(grad_x, {gx_rs, gx_hs}) && vec4_ok(a->cb, {a->cb_hs, a->cb_qs}) &&
+             (!grad_out || vec4_ok(grad_out, {go_rs, go_hs}))) ? 1 : 0;
     long long blocks = (a->M + 3) / 4;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(vq_quantize_backward_kernel, dim3((unsigned)blocks, (unsigned)a->H), dim3(256), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_quantize_backward launch");
-    return 0;
+    return launch<vq_quantize_backward_kernel>(dim3((unsigned)blocks, (unsigned)a->H), dim3(256), 0, (hipStream_t)stream, "vq_quantize_backward launch", p);
 }
 
 // Owner-computes launch plan: a wave owns cw codes (8 KiB of partial sums) and one of row_blocks contiguous row ranges
@@ -1477,9 +1398,7 @@ static bool ema_owner_plan(int H, long long M, int K, int D, EmaOwnerPlan &pl) {
     if (cw > K) cw = K;
     pl.cw = cw;
     pl.owners = (K + cw - 1) / cw;
-    const DevInfo &di = dev_info();
-    const int cus = di.ok && di.cus > 0 ? di.cus : 256;
-    long long row_blocks = (16ll * cus) / (pl.owners * H);  // ~16 waves per CU in total
+    long long row_blocks = (16ll * device_cus()) / (pl.owners * H);  // ~16 waves per CU in total
     if (row_blocks < 1) row_blocks = 1;
     long long rows_per_block = (M + row_blocks - 1) / row_blocks;
     if (rows_per_block < 2048) rows_per_block = 2048;
@@ -1494,14 +1413,10 @@ static bool ema_owner_plan(int H, long long M, int K, int D, EmaOwnerPlan &pl) {
 static int launch_ema_owner(const EmaOwnerPlan &pl, const float *x, int64_t x_rs, int64_t x_hs, const int64_t *idx, int64_t idx_rs,
                             int64_t idx_hs, const uint8_t *mask, int H, int64_t M, int K, int D, float *counts, float *sums,
                             float *part_sums, float *part_counts, hipStream_t s) {
-    static thread_local bool attr_done[kMaxDevices] = {};
-    if (int arc = allow_big_lds(vq_ema_accumulate_owner_kernel, attr_done)) return arc;
-    hipLaunchKernelGGL(vq_ema_accumulate_owner_kernel, dim3((unsigned)((pl.owners + 3) / 4), (unsigned)pl.row_blocks, (unsigned)H),
-                       dim3(256), pl.lds, s, x, (long long)x_rs, (long long)x_hs, (const long long *)idx, (long long)idx_rs,
-                       (long long)idx_hs, mask, (long long)M, pl.rows_per_block, K, pl.cw, D, counts, sums, part_sums, part_counts);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_ema_accumulate_owner launch");
-    return 0;
+    return launch<vq_ema_accumulate_owner_kernel, kBigLds>(dim3((unsigned)((pl.owners + 3) / 4), (unsigned)pl.row_blocks, (unsigned)H), dim3(256), pl.lds, s,
+                                                           "vq_ema_accumulate_owner launch", x, (long long)x_rs, (long long)x_hs, (const long long *)idx,
+                                                           (long long)idx_rs, (long long)idx_hs, mask, (long long)M, pl.rows_per_block, K, pl.cw, D, counts,
+                                                           sums, part_sums, part_counts);
 }
 
 int vq_ema_accumulate_f32(const float *x, int64_t x_rs, int64_t x_hs, const int64_t *idx, int64_t idx_rs, int64_t idx_hs,
@@ -1516,12 +1431,9 @@ int vq_ema_accumulate_f32(const float *x, int64_t x_rs, int64_t x_hs, const int6
         return launch_ema_owner(pl, x, x_rs, x_hs, idx, idx_rs, idx_hs, mask, H, M, K, D, counts, sums, nullptr, nullptr, s);
     long long blocks = (M + 3) / 4;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(vq_ema_accumulate_kernel, dim3((unsigned)blocks, (unsigned)H), dim3(256), 0, s, x,
-                       (long long)x_rs, (long long)x_hs, (const long long *)idx, (long long)idx_rs, (long long)idx_hs, mask,
-                       (long long)M, K, D, counts, sums);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_ema_accumulate launch");
-    return 0;
+    return launch<vq_ema_accumulate_kernel>(dim3((unsigned)blocks, (unsigned)H), dim3(256), 0, s, "vq_ema_accumulate launch", x, (long long)x_rs,
+                                            (long long)x_hs, (const long long *)idx, (long long)idx_rs, (long long)idx_hs, mask, (long long)M, K, D, counts,
+                                            sums);
 }
 
 int64_t vq_ema_det_workspace_bytes(int H, int64_t M, int K, int D) {
@@ -1546,13 +1458,11 @@ int vq_ema_accumulate_det_f32(const float *x, int64_t x_rs, int64_t x_hs, const 
     if (int rc = launch_ema_owner(pl, x, x_rs, x_hs, idx, idx_rs, idx_hs, mask, H, M, K, D, counts, sums, part_sums, part_counts, s))
         return rc;
     const long long n_s = (long long)H * K * D, n_c = (long long)H * K;
-    hipLaunchKernelGGL(vq_ema_reduce_parts_kernel, dim3((unsigned)((n_s + 255) / 256)), dim3(256), 0, s, part_sums,
-                       (int)pl.row_blocks, n_s, sums);
-    hipLaunchKernelGGL(vq_ema_reduce_parts_kernel, dim3((unsigned)((n_c + 255) / 256)), dim3(256), 0, s, part_counts,
-                       (int)pl.row_blocks, n_c, counts);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_ema_reduce_parts launch");
-    return 0;
+    if (int rc = launch<vq_ema_reduce_parts_kernel>(dim3((unsigned)((n_s + 255) / 256)), dim3(256), 0, s, "vq_ema_reduce_parts launch", part_sums,
+                                                    (int)pl.row_blocks, n_s, sums))
+        return rc;
+    return launch<vq_ema_reduce_parts_kernel>(dim3((unsigned)((n_c + 255) / 256)), dim3(256), 0, s, "vq_ema_reduce_parts launch", part_counts,
+                                              (int)pl.row_blocks, n_c, counts);
 }
 
 int vq_ema_accumulate_residual_f32(const vq_args *a, float *counts, float *sums, void *stream) {
@@ -1562,13 +1472,11 @@ int vq_ema_accumulate_residual_f32(const vq_args *a, float *counts, float *sums,
     if (!a->cb || !a->idx || !counts || !sums) return fail(VQ_E_BADARG, "vq_ema_accumulate_residual: cb / idx / counts / sums is null");
     long long blocks = (a->M + 3) / 4;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(vq_ema_accumulate_residual_kernel, dim3((unsigned)blocks, (unsigned)a->H), dim3(256), 0,
-                       (hipStream_t)stream, a->x, (long long)a->x_rs, (long long)a->x_hs, a->cb, (long long)a->cb_hs,
-                       (long long)a->cb_qs, (const long long *)a->idx, (long long)a->idx_rs, (long long)a->idx_hs,
-                       (long long)a->idx_qs, (long long)a->M, a->K, a->D, a->Q, (a->flags & VQ_F_STE) ? 1 : 0, counts, sums);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_ema_accumulate_residual launch");
-    return 0;
+    return launch<vq_ema_accumulate_residual_kernel>(dim3((unsigned)blocks, (unsigned)a->H), dim3(256), 0, (hipStream_t)stream,
+                                                     "vq_ema_accumulate_residual launch", a->x, (long long)a->x_rs, (long long)a->x_hs, a->cb,
+                                                     (long long)a->cb_hs, (long long)a->cb_qs, (const long long *)a->idx, (long long)a->idx_rs,
+                                                     (long long)a->idx_hs, (long long)a->idx_qs, (long long)a->M, a->K, a->D, a->Q,
+                                                     (a->flags & VQ_F_STE) ? 1 : 0, counts, sums);
 }
 
 int vq_ema_update_f32(float *cluster_size, float *embed_avg, float *embeddings, const float *counts, const float *sums,
@@ -1577,28 +1485,24 @@ int vq_ema_update_f32(float *cluster_size, float *embed_avg, float *embeddings, 
         return fail(VQ_E_BADARG, "vq_ema_update: bad argument");
     hipStream_t s = (hipStream_t)stream;
     const float weight = (float)(1.0 - decay);  // lerp_(.., 1 - decay): the reference subtracts in double and rounds the weight once
-    hipLaunchKernelGGL(vq_ema_sizes_kernel, dim3(H), dim3(256), 0, s, cluster_size, counts, K, weight, total_scratch);
+    if (int rc = launch<vq_ema_sizes_kernel>(dim3(H), dim3(256), 0, s, "vq_ema_update launch", cluster_size, counts, K, weight, total_scratch)) return rc;
     const long long rows = (long long)H * K;
-    hipLaunchKernelGGL(vq_ema_codes_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, cluster_size, total_scratch,
-                       embed_avg, sums, embeddings, H, K, D, weight, eps, l2norm);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_ema_update launch");
-    return 0;
+    return launch<vq_ema_codes_kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, "vq_ema_update launch", cluster_size, total_scratch, embed_avg,
+                                       sums, embeddings, H, K, D, weight, eps, l2norm);
 }
 
-static int fill_aux_params(AuxParams &p, const vq_args *a, const char *who) {
+static int fill_aux_params(AuxParams &p, const vq_args *a) {
     memset(&p, 0, sizeof(p));
     if (!a->packed) return fail(VQ_E_BADARG, "vq: packed codebook is null");
     if (vq_packed_floats(a->K, a->D) * 4 >= (1ll << 31))
         return fail(VQ_E_UNSUPPORTED, "vq: packed codebook image >= 2 GiB (shard the codebook)");
-    (void)who;
     p.x = a->x; p.x_rs = a->x_rs; p.x_hs = a->x_hs;
     p.packed = a->packed; p.pk_hs = a->pk_hs;
     p.pk_bytes = (unsigned)(vq_packed_floats(a->K, a->D) * 4);
     p.M = a->M; p.K = a->K; p.D = a->D;
     const int tc = kTileCodes * sub_tiles(padded_dim(a->D));
     p.ntiles = (a->K + tc - 1) / tc;
-    p.vec_x = (a->D % 4 == 0 && a->x_rs % 4 == 0 && a->x_hs % 4 == 0 && aligned16(a->x)) ? 1 : 0;
+    p.vec_x = vec4_ok(a->x, {a->D, a->x_rs, a->x_hs}) ? 1 : 0;
     return 0;
 }
 
@@ -1617,22 +1521,16 @@ int vq_similarities_f32(const vq_args *a, float *sims, int64_t sims_rs, int64_t 
         if (!a->cb) return fail(VQ_E_BADARG, "vq_similarities: natural codebook required for the scalar kernel");
         const long long n = a->M * (long long)a->K;
         if ((n + 255) / 256 > 0x7FFFFFFFll) return fail(VQ_E_UNSUPPORTED, "vq_similarities: chunk too large for the scalar kernel");
-        dim3 grid((unsigned)((n + 255) / 256), (unsigned)a->H);
-        if (a->metric == VQ_METRIC_EUCLID)
-            hipLaunchKernelGGL(vq_sims_simple<VQ_METRIC_EUCLID>, grid, dim3(256), 0, s, a->x, a->x_rs, a->x_hs, a->cb,
-                               a->cb_hs, a->M, a->K, a->D, sims, (long long)sims_rs, (long long)sims_hs);
-        else
-            hipLaunchKernelGGL(vq_sims_simple<VQ_METRIC_DOT>, grid, dim3(256), 0, s, a->x, a->x_rs, a->x_hs, a->cb,
-                               a->cb_hs, a->M, a->K, a->D, sims, (long long)sims_rs, (long long)sims_hs);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "vq_sims_simple launch");
-        return 0;
+        return with_metric(a->metric, [&](auto m) {
+            return launch<vq_sims_simple<decltype(m)::value>>(dim3((unsigned)((n + 255) / 256), (unsigned)a->H), dim3(256), 0, s, "vq_sims_simple launch", a->x,
+                                                              a->x_rs, a->x_hs, a->cb, a->cb_hs, a->M, a->K, a->D, sims, (long long)sims_rs, (long long)sims_hs);
+        });
     }
     AuxParams p;
-    rc = fill_aux_params(p, a, "vq_similarities");
+    rc = fill_aux_params(p, a);
     if (rc) return rc;
     p.sims = sims; p.sims_rs = sims_rs; p.sims_hs = sims_hs;
-    p.vec_s = (a->K % 4 == 0 && sims_rs % 4 == 0 && sims_hs % 4 == 0 && aligned16(sims)) ? 1 : 0;
+    p.vec_s = vec4_ok(sims, {a->K, sims_rs, sims_hs}) ? 1 : 0;
     return launch_aux(DP, p, a->H, a->metric, kAuxSims, s);
 }
 
@@ -1646,7 +1544,7 @@ int vq_softmax_stats_f32(const vq_args *a, float scale, const int64_t *target, i
     const int DP = padded_dim(a->D);
     if (DP == 0) return fail(VQ_E_UNSUPPORTED, "vq_softmax_stats: D > 512 is not supported (use vq_similarities_f32 chunks)");
     AuxParams p;
-    rc = fill_aux_params(p, a, "vq_softmax_stats");
+    rc = fill_aux_params(p, a);
     if (rc) return rc;
     p.scale = scale;
     p.target = (const long long *)target; p.tgt_rs = tgt_rs; p.tgt_hs = tgt_hs;
@@ -1664,7 +1562,7 @@ int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_l
     const int DP = padded_dim(a->D);
     if (DP == 0) return fail(VQ_E_UNSUPPORTED, "vq_ce_backward: D > 512 (use vq_similarities_f32 row chunks)");
     AuxParams ap;
-    rc = fill_aux_params(ap, a, "vq_ce_backward");
+    rc = fill_aux_params(ap, a);
     if (rc) return rc;
     CeBwdParams p;
     memset(&p, 0, sizeof(p));
@@ -1678,26 +1576,14 @@ int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_l
     p.tgt_logit = target_logit;
     p.gx = grad_x; p.gx_rs = gx_rs; p.gx_hs = gx_hs;
     hipStream_t s = (hipStream_t)stream;
-    switch (DP) {
-        case 32: return vqi::part_ce_bwd<32>(p, a->H, a->metric, s);
-        case 64: return vqi::part_ce_bwd<64>(p, a->H, a->metric, s);
-        case 128: return vqi::part_ce_bwd<128>(p, a->H, a->metric, s);
-        case 256: return vqi::part_ce_bwd<256>(p, a->H, a->metric, s);
-        case 512: return vqi::part_ce_bwd<512>(p, a->H, a->metric, s);
-    }
-    return fail(VQ_E_UNSUPPORTED, "vq_ce_backward: unsupported padded dim");
+    return with_padded_dim(DP, [&](auto dp) { return vqi::part_ce_bwd<decltype(dp)::value>(p, a->H, a->metric, s); },
+                           [] { return fail(VQ_E_UNSUPPORTED, "vq_ce_backward: unsupported padded dim"); });
 }
 
 int vq_max_fused_stages(int D, int want_sq_err) {
     // largest Q one residual launch can hold (winner indices and loss partials of every stage live in LDS); 0: no fused residual launch (D > 512)
-    switch (padded_dim(D)) {
-        case 32: return max_stages_t<32, 8>(want_sq_err != 0);
-        case 64: return max_stages_t<64, 8>(want_sq_err != 0);
-        case 128: return max_stages_t<128, 8>(want_sq_err != 0);
-        case 256: return max_stages_t<256, 8>(want_sq_err != 0);
-        case 512: return max_stages_t<512, 4>(want_sq_err != 0);
-    }
-    return 0;
+    return with_padded_dim(padded_dim(D), [&](auto dp) { return max_stages_t<decltype(dp)::value, decltype(dp)::value == 512 ? 4 : 8>(want_sq_err != 0); },
+                           [] { return 0; });
 }
 
 int vq_nearest_f32(const vq_args *a, void *stream) {
@@ -1725,13 +1611,10 @@ int vq_lfq_quantize_f32(const float *v, int64_t v_rs, const float *xa, int64_t x
     const int64_t blocks = lfq_quant_blocks(N, C);
     double *part = commit_sum ? (double *)((char *)workspace + ws.commit) : nullptr;
     if (blocks > 0)
-        hipLaunchKernelGGL(lfq_quantize_kernel, dim3((unsigned)blocks), dim3(kLfqQuantThreads), 0, s, v, v_rs, xa, xa_rs, N, C, d,
-                           qmag, mask, q, out, idx, part);
-    if (commit_sum)
-        hipLaunchKernelGGL(lfq_sum_kernel<double>, dim3(1), dim3(kLfqSumThreads), 0, s, part, blocks, commit_sum, (int64_t)0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_lfq_quantize launch");
-    return 0;
+        rc = launch<lfq_quantize_kernel>(dim3((unsigned)blocks), dim3(kLfqQuantThreads), 0, s, "vq_lfq_quantize launch", v, v_rs, xa, xa_rs, N, C, d, qmag,
+                                         mask, q, out, idx, part);
+    if (rc || !commit_sum) return rc;
+    return launch<lfq_sum_kernel<double>>(dim3(1), dim3(kLfqSumThreads), 0, s, "vq_lfq_quantize launch", part, blocks, commit_sum, (int64_t)0);
 }
 
 int vq_lfq_entropy_fwd_f32(const float *v, int64_t v_rs, const int64_t *rows, int64_t R, int C, int d, float code_scale,
@@ -1784,14 +1667,10 @@ int vq_rlfq_quantize_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, 
     hipStream_t s = (hipStream_t)stream;
     const int64_t blocks = rlfq_blocks(N);
     double *part = commit_sum ? (double *)workspace : nullptr;
-    rlfq_launch_quantize(d, dim3((unsigned)blocks, (unsigned)G), s, x, x_gs, x_rs, N, S, stage_consts, spherical != 0, ste != 0, mask,
-                         out, out_gs, out_rs, idx, v_all, part);
-    if (commit_sum)
-        hipLaunchKernelGGL(lfq_sum_kernel<double>, dim3((unsigned)(G * S)), dim3(kLfqSumThreads), 0, s, part, blocks, commit_sum,
-                           blocks);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_rlfq_quantize launch");
-    return 0;
+    rc = rlfq_launch_quantize(d, dim3((unsigned)blocks, (unsigned)G), s, "vq_rlfq_quantize launch", x, x_gs, x_rs, N, S, stage_consts, spherical != 0,
+                              ste != 0, mask, out, out_gs, out_rs, idx, v_all, part);
+    if (rc || !commit_sum) return rc;
+    return launch<lfq_sum_kernel<double>>(dim3((unsigned)(G * S)), dim3(kLfqSumThreads), 0, s, "vq_rlfq_quantize launch", part, blocks, commit_sum, blocks);
 }
 
 int vq_rlfq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, int S, const float *stage_consts,
@@ -1802,11 +1681,8 @@ int vq_rlfq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, 
     if (!x || !grad_x) return fail(VQ_E_BADARG, "vq_rlfq_backward: null pointer");
     if (N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    rlfq_launch_backward(d, dim3((unsigned)rlfq_blocks(N), (unsigned)G), s, x, x_gs, x_rs, N, S, stage_consts, spherical != 0, mask,
-                         g_out, g_gs, g_rs, w_commit, g_ent, grad_x, gx_gs, gx_rs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_rlfq_backward launch");
-    return 0;
+    return rlfq_launch_backward(d, dim3((unsigned)rlfq_blocks(N), (unsigned)G), s, "vq_rlfq_backward launch", x, x_gs, x_rs, N, S, stage_consts,
+                                spherical != 0, mask, g_out, g_gs, g_rs, w_commit, g_ent, grad_x, gx_gs, gx_rs);
 }
 
 int vq_fsq_quantize_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, const int32_t *levels, int S,
@@ -1817,11 +1693,8 @@ int vq_fsq_quantize_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, i
     if (rc) return rc;
     if (!x || !out) return fail(VQ_E_BADARG, "vq_fsq_quantize: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    fsq_launch_quantize(d, dim3((unsigned)fsq_blocks(N), (unsigned)G), s, x, x_gs, x_rs, N, S, lv, consts, prebound != 0, out,
-                        out_gs, out_rs, idx);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_fsq_quantize launch");
-    return 0;
+    return fsq_launch_quantize(d, dim3((unsigned)fsq_blocks(N), (unsigned)G), s, "vq_fsq_quantize launch", x, x_gs, x_rs, N, S, lv, consts, prebound != 0,
+                               out, out_gs, out_rs, idx);
 }
 
 int vq_fsq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, int64_t N, int d, const int32_t *levels, int S,
@@ -1832,11 +1705,8 @@ int vq_fsq_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, int64_t G, i
     if (rc) return rc;
     if (!x || !g_out || !grad_x) return fail(VQ_E_BADARG, "vq_fsq_backward: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    fsq_launch_backward(d, dim3((unsigned)fsq_blocks(N), (unsigned)G), s, x, x_gs, x_rs, N, S, lv, consts, prebound != 0, g_out,
-                        g_gs, g_rs, grad_x, gx_gs, gx_rs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_fsq_backward launch");
-    return 0;
+    return fsq_launch_backward(d, dim3((unsigned)fsq_blocks(N), (unsigned)G), s, "vq_fsq_backward launch", x, x_gs, x_rs, N, S, lv, consts, prebound != 0,
+                               g_out, g_gs, g_rs, grad_x, gx_gs, gx_rs);
 }
 
 int vq_fsq_decode_f32(const void *idx, int idx_64, int64_t N, int Q, int d, const int32_t *levels, const float *scales,
@@ -1846,11 +1716,8 @@ int vq_fsq_decode_f32(const void *idx, int idx_64, int64_t N, int Q, int d, cons
     if (rc) return rc;
     if (!idx || (!codes_sum && !all_codes)) return fail(VQ_E_BADARG, "vq_fsq_decode: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    fsq_launch_decode(d, dim3((unsigned)fsq_blocks(N)), s, idx, idx_64 != 0, N, Q, lv, scales, drop_null != 0, codes_sum,
-                      all_codes);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_fsq_decode launch");
-    return 0;
+    return fsq_launch_decode(d, dim3((unsigned)fsq_blocks(N)), s, "vq_fsq_decode launch", idx, idx_64 != 0, N, Q, lv, scales, drop_null != 0, codes_sum,
+                             all_codes);
 }
 
 int64_t vq_lq_workspace_bytes(int64_t B, int64_t P, int C) {
@@ -1875,14 +1742,10 @@ int vq_lq_quantize_f32(const float *z, int64_t z_bs, int64_t z_ps, int64_t z_cs,
         return fail(VQ_E_BADARG, "vq_lq_quantize: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     float *part = loss ? (float *)workspace : nullptr;
-    lq_launch_quantize(d, dim3((unsigned)blocks), s, z, LqStrides{z_bs, z_ps, z_cs}, P, C, N, lv, tables, n_table, codes,
-                       LqStrides{c_bs, c_ps, c_cs}, idx, part);
-    if (loss)
-        hipLaunchKernelGGL(lq_loss_kernel, dim3(1), dim3(kLqLossThreads), 0, s, part, blocks, (double)N * (double)d, w_c, w_q,
-                           loss);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_lq_quantize launch");
-    return 0;
+    rc = lq_launch_quantize(d, dim3((unsigned)blocks), s, "vq_lq_quantize launch", z, LqStrides{z_bs, z_ps, z_cs}, P, C, N, lv, tables, n_table, codes,
+                            LqStrides{c_bs, c_ps, c_cs}, idx, part);
+    if (rc || !loss) return rc;
+    return launch<lq_loss_kernel>(dim3(1), dim3(kLqLossThreads), 0, s, "vq_lq_quantize launch", part, blocks, (double)N * (double)d, w_c, w_q, loss);
 }
 
 int vq_lq_backward_f32(const float *x, int64_t x_bs, int64_t x_ps, int64_t x_cs, const float *out, int64_t o_bs, int64_t o_ps,
@@ -1895,12 +1758,9 @@ int vq_lq_backward_f32(const float *x, int64_t x_bs, int64_t x_ps, int64_t x_cs,
         return fail(VQ_E_BADARG, "vq_lq_backward: too many elements");
     const int64_t N = B * P * W;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(lq_backward_kernel, dim3((unsigned)lq_blocks(N)), dim3(kLqThreads), 0, s, x, LqStrides{x_bs, x_ps, x_cs},
-                       out, LqStrides{o_bs, o_ps, o_cs}, g_out, LqStrides{g_bs, g_ps, g_cs}, g_loss, coef, P, W, N, grad_x,
-                       LqStrides{gx_bs, gx_ps, gx_cs});
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "vq_lq_backward launch");
-    return 0;
+    return launch<lq_backward_kernel>(dim3((unsigned)lq_blocks(N)), dim3(kLqThreads), 0, s, "vq_lq_backward launch", x, LqStrides{x_bs, x_ps, x_cs}, out,
+                                      LqStrides{o_bs, o_ps, o_cs}, g_out, LqStrides{g_bs, g_ps, g_cs}, g_loss, coef, P, W, N, grad_x,
+                                      LqStrides{gx_bs, gx_ps, gx_cs});
 }
 
 }  // extern "C"

@@ -471,21 +471,20 @@ int lfq_entropy_fwd_run(const float *v, int64_t v_rs, int64_t v_ss, const int64_
     const LfqCoef coefs = lfq_coef_args(code_scale, code_scale_dev, period, inv_temperature);
     const int waves = lfq_task_waves(d);
     const int64_t tasks = R * C;
-    hipLaunchKernelGGL(lfq_entropy_fwd_kernel, dim3((unsigned)((tasks + waves - 1) / waves), (unsigned)T), dim3(waves * 64),
-                       lfq_block_lds_bytes(d), s, v, v_rs, v_ss, rows, rows_ss, R, C, d, coefs, ent, tabA, tabB);
-    hipLaunchKernelGGL(lfq_sum_kernel<float>, dim3((unsigned)T), dim3(kLfqSumThreads), 0, s, ent, tasks, per_sample_sum, tasks);
+    rc = launch<lfq_entropy_fwd_kernel>(dim3((unsigned)((tasks + waves - 1) / waves), (unsigned)T), dim3(waves * 64),
+                                        lfq_block_lds_bytes(d), s, who, v, v_rs, v_ss, rows, rows_ss, R, C, d, coefs, ent, tabA, tabB);
+    if (rc) return rc;
+    rc = launch<lfq_sum_kernel<float>>(dim3((unsigned)T), dim3(kLfqSumThreads), 0, s, who, ent, tasks, per_sample_sum, tasks);
+    if (rc) return rc;
     const int64_t rps = lfq_rows_per_split(R, C, d);
     const int64_t splits = (R + rps - 1) / rps;
     const int P = 1 << d;
-    hipLaunchKernelGGL(lfq_avg_prob_kernel,
-                       dim3((unsigned)((P + kLfqAvgCodes - 1) / kLfqAvgCodes), (unsigned)splits, (unsigned)(C * T)),
-                       dim3(kLfqAvgCodes), 0, s, tabA, tabB, R, C, d, rps, splits, part);
+    rc = launch<lfq_avg_prob_kernel>(dim3((unsigned)((P + kLfqAvgCodes - 1) / kLfqAvgCodes), (unsigned)splits, (unsigned)(C * T)),
+                                     dim3(kLfqAvgCodes), 0, s, who, tabA, tabB, R, C, d, rps, splits, part);
+    if (rc) return rc;
     const int64_t CP = (int64_t)C * P;
-    hipLaunchKernelGGL(lfq_avg_reduce_kernel, dim3((unsigned)((CP + 255) / 256), (unsigned)T), dim3(256), 0, s, part, (int)splits,
-                       CP, 1.0 / (double)R, avg_prob);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, who);
-    return 0;
+    return launch<lfq_avg_reduce_kernel>(dim3((unsigned)((CP + 255) / 256), (unsigned)T), dim3(256), 0, s, who, part, (int)splits,
+                                         CP, 1.0 / (double)R, avg_prob);
 }
 
 // The entropy backward of T stages (T = 1: vq_lfq_entropy_bwd_f32).
@@ -502,9 +501,7 @@ int lfq_entropy_bwd_run(const float *v, int64_t v_rs, int64_t v_ss, const int64_
     const LfqCoef coefs = lfq_coef_args(code_scale, code_scale_dev, period, inv_temperature);
     const int waves = lfq_task_waves(d);
     const int64_t tasks = R * C;
-    hipLaunchKernelGGL(lfq_entropy_bwd_kernel, dim3((unsigned)((tasks + waves - 1) / waves), (unsigned)T), dim3(waves * 64),
-                       lfq_block_lds_bytes(d), s, v, v_rs, v_ss, rows, rows_ss, R, C, d, coefs, w_ps, w_cb, grad_v, gv_rs, gv_ss);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, who);
-    return 0;
+    return launch<lfq_entropy_bwd_kernel>(dim3((unsigned)((tasks + waves - 1) / waves), (unsigned)T), dim3(waves * 64),
+                                          lfq_block_lds_bytes(d), s, who, v, v_rs, v_ss, rows, rows_ss, R, C, d, coefs, w_ps, w_cb, grad_v,
+                                          gv_rs, gv_ss);
 }

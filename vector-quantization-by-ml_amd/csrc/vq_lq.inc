@@ -161,9 +161,10 @@ int lq_check(int64_t B, int64_t P, int C, int d, const int32_t *levels, int &n_t
 }
 
 #define LQ_CASE(D) \
-    case D: hipLaunchKernelGGL(lq_quantize_kernel<D>, grid, dim3(kLqThreads), 0, s, args...); break;
+    case D: return launch<lq_quantize_kernel<D>>(grid, dim3(kLqThreads), 0, s, what, args...);
 template <typename... A>
-void lq_launch_quantize(int d, dim3 grid, hipStream_t s, A... args) {
+int lq_launch_quantize(int d, dim3 grid, hipStream_t s, const char *what, A... args) {
     switch (d) { FSQ_CASES(LQ_CASE) }
+    return 0;
 }
 #undef LQ_CASE

@@ -183,21 +183,23 @@ int rlfq_check(int64_t G, int64_t N, int d, int S, const float *stage_consts, co
 #define RLFQ_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20)
 
 template <typename... A>
-void rlfq_launch_quantize(int d, dim3 grid, hipStream_t s, A... args) {
+int rlfq_launch_quantize(int d, dim3 grid, hipStream_t s, const char *what, A... args) {
     switch (d) {
 #define RLFQ_Q(D) \
-    case D: hipLaunchKernelGGL(rlfq_quantize_kernel<D>, grid, dim3(kRlfqThreads), 0, s, args...); break;
+    case D: return launch<rlfq_quantize_kernel<D>>(grid, dim3(kRlfqThreads), 0, s, what, args...);
         RLFQ_CASES(RLFQ_Q)
 #undef RLFQ_Q
     }
+    return 0;
 }
 
 template <typename... A>
-void rlfq_launch_backward(int d, dim3 grid, hipStream_t s, A... args) {
+int rlfq_launch_backward(int d, dim3 grid, hipStream_t s, const char *what, A... args) {
     switch (d) {
 #define RLFQ_B(D) \
-    case D: hipLaunchKernelGGL(rlfq_backward_kernel<D>, grid, dim3(kRlfqThreads), 0, s, args...); break;
+    case D: return launch<rlfq_backward_kernel<D>>(grid, dim3(kRlfqThreads), 0, s, what, args...);
         RLFQ_CASES(RLFQ_B)
 #undef RLFQ_B
     }
+    return 0;
 }

@@ -227,7 +227,7 @@ constexpr size_t resolve_lds_bytes() { return ((size_t)DP + kResolveWaves * kExC
 template <int DP>
 __global__ void __launch_bounds__(kResolveWaves * 64) vq_resolve_rows_kernel(const SearchParams p, int H) {
     constexpr int WAVES = kResolveWaves;
-    const unsigned cap = (unsigned)((long long)H * p.M);  // (screen_image_for: H M < 2^31, the list holds them all)
+    const unsigned cap = (unsigned)((long long)H * p.M);  // (choose_search: H M < 2^31, the list holds them all)
     unsigned count = *p.scr_count;
     if (count > cap) count = cap;
     if (blockIdx.x >= count) return;
