@@ -169,7 +169,8 @@ bool use_pair512() {
     return !off;
 }
 
-// the screened sweep's share of the workspace: [bf16x3 images][count, 256 B][rows for the second pass: one uint32 per row of the call]
+// the screened sweep's share of the workspace: [bf16x3 images][two counts, 256 B][rows for the second pass: one uint32 per row of the
+// call, the full-search list from the front and the rescore list from the back]
 inline long long screen_bytes(int H, long long M, int ntiles) { return (long long)H * scr_image_bytes(ntiles) + 256 + 4ll * H * M; }
 
 // In order of precedence.  `waves` is the one-block kernel's workgroup size (the caller's plan); `scr_room` the bytes of
@@ -286,8 +287,9 @@ int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s) {
                                                                                    lds, s, "vq_search_persist launch", p))
         return rc;
     if constexpr (SCREEN) {
-        // second pass: the listed rows, in stream order behind the sweep.  One workgroup per CU: the few rows of a usual call
-        // (tens) take one round, and a workgroup that finds no entry for itself ends after one load of the count.
+        // second pass: the rows of both lists, in stream order behind the sweep.  One workgroup per CU: the few full searches
+        // of a usual call (tens) take one round, the other workgroups share the rescore batches, and a workgroup that finds
+        // nothing for itself ends after one load of the counts.
         return launch<vq_resolve_rows_kernel<256>, kBigLds>(dim3((unsigned)(cus > 0 ? cus : 1)), dim3(kResolveWaves * 64), resolve_lds_bytes<256>(), s,
                                                             "vq_resolve_rows launch", p, H);
     }
@@ -517,7 +519,7 @@ bool vec4_ok(const void *p, std::initializer_list<long long> strides, unsigned a
 }
 
 // The screened sweep's bf16x3 images are built per call into the key area of the workspace, which a fused call does not use,
-// and behind them the list of rows that the second pass searches in full (vq_resolve_rows_kernel): the layout of screen_bytes.
+// and behind them the two lists of rows for the second pass (vq_resolve_rows_kernel): the layout of screen_bytes.
 void set_screen_image(SearchParams &p, const vq_args *a) {
     const long long img = scr_image_bytes(p.ntiles);
     p.scr = (const float *)a->workspace;

@@ -52,8 +52,9 @@ struct SearchParams {
     const float *scr;
     long long scr_hs;
     unsigned scr_bytes;
-    // rows the screen cannot bound: `*scr_count` entries head * M + row in `scr_list` (room for all H M rows), behind the
-    // images; the count is zeroed by vq_pack_scr_kernel, the entries are searched in full by vq_resolve_rows_kernel
+    // rows the screen cannot bound, as entries head * M + row in `scr_list` (room for all H M rows), behind the images:
+    // scr_count[0] rows to search in full from the front, scr_count[1] rows to rescore (candidate codes in their idx element)
+    // from the back; both counts are zeroed by vq_pack_scr_kernel, the entries are decided by vq_resolve_rows_kernel
     unsigned *scr_count;
     unsigned *scr_list;
 };

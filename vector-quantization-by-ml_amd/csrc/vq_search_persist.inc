@@ -22,10 +22,19 @@
 // accumulates hi_c * hi_x + lo_c * hi_x + hi_c * lo_x (3 bf16 MFMAs per 16 dims: 48 per 32 x 32 sub-tile instead of 129 fp32
 // ones), starting from |c|^2 (the fp32 chain of the packed image) in the accumulator.  Each lane keeps the three lowest
 // screened values of its codes over distinct codes, and the codes of the two lowest.  A row whose two lowest screened values
-// are further apart than the bound below can only have the screened winner as its exact winner.  The other rows rescore
-// their few candidates by the exact chain (exact_pair_euclid), or, when a lane half holds more candidates than it tracks,
-// are put on a list and searched again in full by a second kernel on the same stream (vq_resolve_rows_kernel, which runs
-// exact_row_euclid).  Results are those of the fp32 kernel bit for bit.
+// are further apart than the bound below can only have the screened winner as its exact winner.  The other rows are decided
+// by a second kernel on the same stream (vq_resolve_rows_kernel), none of them inside the sweep kernel, where one wave's
+// exact chains would hold the other seven at the next tile barrier.  The sweep puts them on one of two lists, which share one
+// array of H M uint32 entries head * M + row in the workspace (counts: scr_count[0], scr_count[1], zeroed by
+// vq_pack_scr_kernel):
+//  * rescore list, filled from the BACK of the array: the row's candidates are among the <= 4 codes its two lane halves
+//    track.  Between the two kernels the row's idx element (an int64 the second pass overwrites) holds them as four 16-bit
+//    codes, 0xFFFF for an empty slot (the persistent kernel is chosen for K <= 3072); the second pass runs the exact chain for
+//    each (rescore_batch);
+//  * full-search list, filled from the FRONT: a lane half holds more candidates than it tracks, or the row is not eligible;
+//    the second pass searches all K codes again (exact_row_euclid).  idx holds the screened argmin meanwhile.
+// A row is on one list at most, so the two ends never meet and the array needs no more room than one list did.  Results
+// are those of the fp32 kernel bit for bit.
 //
 // The bound.  u = 2^-24; for a row x (fp32 chain xn = d-ordered sum of squares) and code c (fp32 chain cn), c' = -2c as
 // packed (exact), Q = sum_k x_k c'_k in real arithmetic, nx = sqrt(xn), nc = sqrt(max cn) over the codebook, L = 2 nx nc.
@@ -75,13 +84,13 @@ __device__ __forceinline__ void split_bf16x2(const f32x8 &v, bf16x8 &hi, bf16x8 
 // the padding rows).  Per 32-code tile: row c at c * 1040 bytes, for each group s of 16 dims hi[16s .. 16s+7], hi[16s+8 ..
 // 16s+15], lo[16s ..], lo[16s+8 ..] (16 B each: one ds_read_b128 is one MFMA's A fragment), then the 32 |c|^2 of the tile;
 // behind the tiles the maximum |c|^2 of each tile's real codes.  Grid (tiles, heads), 256 threads: 8 per code.
-// One thread also zeroes the count of the call's list of rows for the second pass (vq_resolve_rows_kernel).
+// One thread also zeroes the counts of the call's two lists of rows for the second pass (vq_resolve_rows_kernel).
 template <int DP>
 __global__ void __launch_bounds__(256) vq_pack_scr_kernel(const float *__restrict__ packed, long long pk_hs, int K, int ntiles,
                                                           char *__restrict__ img, long long img_hs, unsigned *__restrict__ list_count) {
     static_assert(DP == 256, "the screened sweep is built for Dp = 256");
-    // first on the stream in every screened call: the list of rows for the second pass starts empty
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *list_count = 0u;
+    // first on the stream in every screened call: both lists of rows for the second pass start empty
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) list_count[0] = list_count[1] = 0u;
     constexpr int RS = DP + 4;
     const int t = blockIdx.x, c = threadIdx.x >> 3, part = threadIdx.x & 7;
     const int k = t * kTileCodes + c;
@@ -133,6 +142,26 @@ __global__ void __launch_bounds__(256) vq_pack_scr_kernel(const float *__restric
 constexpr int kExChunk = 32;                // dims per staged chunk
 constexpr int kExStageRow = kExChunk + 4;   // floats per staged code (144 B: 16 lanes' ds_read_b128 cover the 64 banks once)
 constexpr int kExCodes = 64;                // codes per wave and pass
+// 8 dims of the k-ordered fmaf chain: `xa`, `xb` = dims 8 q .. 8 q + 7 of the row, `ce`, `co` = the even and the odd dims of
+// that group of the packed image (values -2c)
+__device__ __forceinline__ float exact_chain8(float acc, const f32x4 &xa, const f32x4 &xb, const f32x4 &ce, const f32x4 &co) {
+    acc = fmaf(xa.x, ce.x, acc);
+    acc = fmaf(xa.y, co.x, acc);
+    acc = fmaf(xa.z, ce.y, acc);
+    acc = fmaf(xa.w, co.y, acc);
+    acc = fmaf(xb.x, ce.z, acc);
+    acc = fmaf(xb.y, co.z, acc);
+    acc = fmaf(xb.z, ce.w, acc);
+    acc = fmaf(xb.w, co.w, acc);
+    return acc;
+}
+// the chain's end: + |x|^2, + |c|^2, clamp_min_(0) (keeps NaN), correctly rounded sqrt
+__device__ __forceinline__ float exact_dist(float acc, float xn, float cn) {
+    float tt = fmaf(1.0f, xn, acc);
+    tt = fmaf(cn, 1.0f, tt);
+    tt = (tt < 0.0f) ? 0.0f : tt;
+    return sqrtf(tt);
+}
 __device__ __forceinline__ bool better_euclid(bool on, float ov, int oi, bool bn, float bv, int bi) {
     if (on != bn) return on;
     if (bn) return oi < bi;
@@ -175,21 +204,11 @@ __device__ __forceinline__ void exact_row_euclid(const float *rowbuf, float *sta
             for (int q = 0; q < CD / 8; ++q) {
                 const f32x4 ce = *(const f32x4 *)(cr + 8 * q), co = *(const f32x4 *)(cr + 8 * q + 4);
                 const f32x4 xa = *(const f32x4 *)(rowbuf + ch * CD + 8 * q), xb = *(const f32x4 *)(rowbuf + ch * CD + 8 * q + 4);
-                acc = fmaf(xa.x, ce.x, acc);
-                acc = fmaf(xa.y, co.x, acc);
-                acc = fmaf(xa.z, ce.y, acc);
-                acc = fmaf(xa.w, co.y, acc);
-                acc = fmaf(xb.x, ce.z, acc);
-                acc = fmaf(xb.y, co.z, acc);
-                acc = fmaf(xb.z, ce.w, acc);
-                acc = fmaf(xb.w, co.w, acc);
+                acc = exact_chain8(acc, xa, xb, ce, co);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the chunk has been read: the next one may overwrite it
         }
-        float tt = fmaf(1.0f, xn, acc);
-        tt = fmaf(cn, 1.0f, tt);
-        tt = (tt < 0.0f) ? 0.0f : tt;  // clamp_min_(0): keeps NaN
-        const float s = sqrtf(tt);
+        const float s = exact_dist(acc, xn, cn);
         if (ok && !bn) {
             if (s != s) {
                 bn = true;
@@ -214,30 +233,141 @@ __device__ __forceinline__ void exact_row_euclid(const float *rowbuf, float *sta
     }
 }
 
-// Second pass of the screened sweep: the rows it could not bound (list entries head * M + row, `*p.scr_count` of them, written
-// by vq_search_persist<.., SCREEN> earlier on the stream) searched again in full by the exact rule.  Grid-stride over the
-// entries, one 8-wave workgroup per entry at a time: the row staged in LDS once, its |x|^2 chain recomputed in the prologue's
-// order (d-ordered fmaf from 0), the waves split the K codes in runs of 64 (exact_row_euclid), the winner reduced over the
-// waves through LDS in the order of the rule; then idx and the quantized row are stored over the provisional ones.
+// Rescore list of the screened sweep, one wave and kRsEntries entries `first` .. of it (entry i is scr_list[cap - 1 - i]): a
+// lane per (entry, candidate) pair.  The entry's <= 4 candidate codes are the 16-bit fields of its idx element (0xFFFF: none;
+// written by vq_search_persist<.., SCREEN>).  Each lane runs the oracle's chain for its pair -- what exact_row_euclid does for
+// a code -- and, in the same pass over the row, the d-ordered |x|^2 chain of the prologue; the four lanes of an entry then
+// take the lowest distance, then the lowest code, and idx and the quantized row are stored over the provisional ones.
+// As in exact_row_euclid nothing walks a row of its own: 8 lanes load the 128 B of one code (of one row) per chunk of 32 dims,
+// one chunk ahead, into `cstage` (64 pairs) and `xstage` (16 rows), kExStageRow floats each, both private to the wave.
+constexpr int kRsEntries = 16;
+template <int DP>
+__device__ __forceinline__ void rescore_batch(const SearchParams &p, unsigned cap, unsigned first, unsigned n1, float *cstage, float *xstage,
+                                              int lane) {
+    constexpr int RS = DP + 4, CD = kExChunk, SR = kExStageRow, NCH = DP / CD, NLC = 64 / 8, NLX = kRsEntries / 8;
+    const int e = lane >> 2, j = lane & 3;
+    const bool in_list = first + (unsigned)e < n1;
+    unsigned ent = p.scr_list[cap - 1u - (in_list ? first + (unsigned)e : first)];
+    const bool ok = in_list && ent < cap;  // (ent < cap: always, for a list the sweep wrote)
+    if (!ok) ent = 0u;
+    const int head = (int)(ent / (unsigned long long)p.M);
+    const int row = (int)((long long)ent - (long long)head * p.M);  // (H M < 2^31)
+    const long long io = (long long)head * p.idx_hs + (long long)row * p.idx_rs;
+    const unsigned code = (unsigned)((unsigned long long)p.idx[io] >> (16 * j)) & 0xFFFFu;
+    const bool valid = ok && code < (unsigned)p.K;
+    const int kc = valid ? (int)code : 0;
+    const int piece = lane & 7, sub = lane >> 3;  // this lane loads float4 `piece` of the chunk of pairs (rows) sub + 8 i
+    const float *csrc[NLC], *xsrc[NLX];
+#pragma unroll
+    for (int i = 0; i < NLC; ++i) {
+        const int q = sub + 8 * i;
+        csrc[i] = p.packed + (long long)__shfl(head, q) * p.pk_hs + (long long)__shfl(kc, q) * RS + 4 * piece;
+    }
+#pragma unroll
+    for (int i = 0; i < NLX; ++i) {
+        const int q = 4 * (sub + 8 * i);
+        xsrc[i] = p.x + (long long)__shfl(head, q) * p.x_hs + (long long)__shfl(row, q) * p.x_rs + 4 * piece;
+    }
+    f32x4 g[NLC], gx[NLX];
+    auto load = [&](int ch) {
+#pragma unroll
+        for (int i = 0; i < NLC; ++i) g[i] = *(const f32x4 *)(csrc[i] + ch * CD);
+#pragma unroll
+        for (int i = 0; i < NLX; ++i)  // (natural rows: zeros behind D; D % 4 == 0)
+            gx[i] = (ch * CD + 4 * piece < p.D) ? *(const f32x4 *)(xsrc[i] + ch * CD) : (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+    };
+    load(0);
+    const float cn = p.packed[(long long)head * p.pk_hs + (long long)kc * RS + DP];
+    const float *cr = cstage + lane * SR, *xr = xstage + e * SR;
+    float acc = 0.0f, xn = 0.0f;
+#pragma clang loop unroll(disable)
+    for (int ch = 0; ch < NCH; ++ch) {
+#pragma unroll
+        for (int i = 0; i < NLC; ++i) *(f32x4 *)(cstage + (sub + 8 * i) * SR + 4 * piece) = g[i];
+#pragma unroll
+        for (int i = 0; i < NLX; ++i) *(f32x4 *)(xstage + (sub + 8 * i) * SR + 4 * piece) = gx[i];
+        if (ch + 1 < NCH) load(ch + 1);
+#pragma unroll
+        for (int q = 0; q < CD / 8; ++q) {
+            const f32x4 ce = *(const f32x4 *)(cr + 8 * q), co = *(const f32x4 *)(cr + 8 * q + 4);
+            const f32x4 xa = *(const f32x4 *)(xr + 8 * q), xb = *(const f32x4 *)(xr + 8 * q + 4);
+            xn = fmaf(xa.x, xa.x, xn);
+            xn = fmaf(xa.y, xa.y, xn);
+            xn = fmaf(xa.z, xa.z, xn);
+            xn = fmaf(xa.w, xa.w, xn);
+            xn = fmaf(xb.x, xb.x, xn);
+            xn = fmaf(xb.y, xb.y, xn);
+            xn = fmaf(xb.z, xb.z, xn);
+            xn = fmaf(xb.w, xb.w, xn);
+            acc = exact_chain8(acc, xa, xb, ce, co);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the chunk has been read: the next one may overwrite it
+    }
+    const float s = exact_dist(acc, xn, cn);
+    float bv = valid ? s : __builtin_inff();
+    int bk = valid ? kc : 0x7FFFFFFF;
+#pragma unroll
+    for (int o = 1; o < 4; o <<= 1) {
+        const float ov = __shfl_xor(bv, o);
+        const int oi = __shfl_xor(bk, o);
+        if (ov < bv || (ov == bv && oi < bk)) {
+            bv = ov;
+            bk = oi;
+        }
+    }
+    const bool store = ok && bk < p.K;  // (an entry always holds the screened argmin, a valid code)
+    if (j == 0 && store) p.idx[io] = bk;
+    if (p.out) {
+        const int dl = 4 * lane;
+#pragma unroll 4
+        for (int r = 0; r < kRsEntries; ++r) {  // one row per step: 64 lanes x float4
+            const int q = 4 * r;
+            const int wk = __shfl(bk, q), hq = __shfl(head, q), rq = __shfl(row, q);
+            if (__shfl((int)store, q) != 0 && dl < p.D)
+                *(f32x4 *)(p.out + (long long)hq * p.out_hs + (long long)rq * p.out_rs + dl) =
+                    *(const f32x4 *)(p.cb + (long long)hq * p.cb_hs + (long long)wk * p.D + dl);
+        }
+    }
+}
+
+// Second pass of the screened sweep: the rows it could not decide, on two lists that share one array of H M entries
+// head * M + row (written by vq_search_persist<.., SCREEN> earlier on the stream; counts p.scr_count[0] and [1]).
+//  * From the front, rows to search again in full by the exact rule.  Grid-stride over the entries, one 8-wave workgroup
+//    per entry at a time: the row staged in LDS once, its |x|^2 chain recomputed in the prologue's order (d-ordered fmaf from
+//    0), the waves split the K codes in runs of 64 (exact_row_euclid), the winner reduced over the waves through LDS in the
+//    order of the rule; then idx and the quantized row are stored over the provisional ones.
+//  * From the back, rows whose <= 4 candidates are known (their idx element holds the codes): rescore_batch, kRsEntries
+//    entries per wave.  A full search keeps a workgroup busy for ~20 us, a batch a wave for a few, so the batches are dealt
+//    to the workgroups that have no full-search entry: from the last workgroup downwards, one batch for every such workgroup
+//    before a second wave of any of them gets one.  When every workgroup has a full search to do, all of them share.
 // Dynamic LDS only (the launcher raises the kernel's dynamic limit to the CU's 160 KiB, which leaves no room for static
-// arrays): [row, Dp floats][8 waves x 64 x kExStageRow floats of code staging][the waves' winners: 3 x 8 words].
+// arrays): [row, Dp floats][8 waves x 64 x kExStageRow floats of code staging][8 waves x kRsEntries x kExStageRow floats of
+// row staging][the waves' winners: 3 x 8 words].
 constexpr int kResolveWaves = 8;
 template <int DP>
-constexpr size_t resolve_lds_bytes() { return ((size_t)DP + kResolveWaves * kExCodes * kExStageRow + 3 * kResolveWaves) * 4; }
+constexpr size_t resolve_lds_bytes() {
+    return ((size_t)DP + kResolveWaves * (kExCodes + kRsEntries) * kExStageRow + 3 * kResolveWaves) * 4;
+}
 template <int DP>
 __global__ void __launch_bounds__(kResolveWaves * 64) vq_resolve_rows_kernel(const SearchParams p, int H) {
     constexpr int WAVES = kResolveWaves;
-    const unsigned cap = (unsigned)((long long)H * p.M);  // (choose_search: H M < 2^31, the list holds them all)
-    unsigned count = *p.scr_count;
+    const unsigned cap = (unsigned)((long long)H * p.M);  // (choose_search: H M < 2^31, the array holds them all)
+    unsigned count = p.scr_count[0], n1 = p.scr_count[1];
     if (count > cap) count = cap;
-    if (blockIdx.x >= count) return;
+    if (n1 > cap - count) n1 = cap - count;
+    // workgroups without a full-search entry, counted from the last one: they share the rescore batches
+    const unsigned nfree = gridDim.x > count ? gridDim.x - count : 0u;
+    const unsigned sharers = nfree ? nfree : gridDim.x, from_last = gridDim.x - 1u - blockIdx.x;
+    const unsigned nbatch = (n1 + kRsEntries - 1) / kRsEntries;
+    if (blockIdx.x >= count && (from_last >= sharers || from_last >= nbatch)) return;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *rowbuf = smem;
-    float *red_v = smem + DP + WAVES * kExCodes * kExStageRow;
+    float *red_v = smem + DP + WAVES * (kExCodes + kRsEntries) * kExStageRow;
     int *red_i = (int *)(red_v + WAVES), *red_n = red_i + WAVES;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float *stage = smem + DP + wave * (kExCodes * kExStageRow);
+    float *xstage = smem + DP + WAVES * (kExCodes * kExStageRow) + wave * (kRsEntries * kExStageRow);
     const int per = ((p.K + WAVES - 1) / WAVES + kExCodes - 1) / kExCodes * kExCodes;  // codes per wave: whole passes
     const int kbeg = wave * per < p.K ? wave * per : p.K, kend = kbeg + per < p.K ? kbeg + per : p.K;
     for (unsigned e = blockIdx.x; e < count; e += gridDim.x) {
@@ -289,61 +419,12 @@ __global__ void __launch_bounds__(kResolveWaves * 64) vq_resolve_rows_kernel(con
                     *(const f32x4 *)(p.cb + (long long)head * p.cb_hs + (long long)bi * p.D + dl);
         }
     }
+    // the rescore batches of this wave (no barrier from here on: the staging regions are the wave's own)
+    if (from_last < sharers)
+        for (unsigned b = from_last + (unsigned)wave * sharers; b < nbatch; b += sharers * WAVES)
+            rescore_batch<DP>(p, cap, b * kRsEntries, n1, stage, xstage, lane);
 }
 
-
-// The exact distances (oracle/vq_oracle.c's chain: k-ordered fmaf over the dims, + |x|^2, + |c|^2, clamp_min(0), correctly
-// rounded sqrt) of one row and TWO codes of the fp32 packed image at once: the two chains run in one v_pk_fma_f32, bit for bit
-// the scalar chains.  `xr` = the natural fp32 row (D % 4 == 0, 16-B aligned), `xn` = its d-ordered |x|^2 chain.  Loads run
-// one chunk of 16 dims ahead of the arithmetic.
-template <int DP>
-__device__ __forceinline__ f32x2 exact_pair_euclid(const float *xr, int D, const float *p0, const float *p1, float xn) {
-    constexpr int GC = 2, NCH = DP / (8 * GC);
-    f32x2 acc = {0.0f, 0.0f};
-    f32x4 e0[GC], o0[GC], e1[GC], o1[GC], xa[GC], xb[GC];
-    auto load = [&](int ch) {
-#pragma unroll
-        for (int g = 0; g < GC; ++g) {
-            const int gg = ch * GC + g;
-            e0[g] = *(const f32x4 *)(p0 + 8 * gg); o0[g] = *(const f32x4 *)(p0 + 8 * gg + 4);
-            e1[g] = *(const f32x4 *)(p1 + 8 * gg); o1[g] = *(const f32x4 *)(p1 + 8 * gg + 4);
-            const f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-            xa[g] = (8 * gg < D) ? *(const f32x4 *)(xr + 8 * gg) : z;
-            xb[g] = (8 * gg + 4 < D) ? *(const f32x4 *)(xr + 8 * gg + 4) : z;
-        }
-    };
-    load(0);
-#pragma clang loop unroll(disable)
-    for (int ch = 0; ch < NCH; ++ch) {
-        f32x4 ce0[GC], co0[GC], ce1[GC], co1[GC], cxa[GC], cxb[GC];
-#pragma unroll
-        for (int g = 0; g < GC; ++g) {
-            ce0[g] = e0[g]; co0[g] = o0[g]; ce1[g] = e1[g]; co1[g] = o1[g]; cxa[g] = xa[g]; cxb[g] = xb[g];
-        }
-        if (ch + 1 < NCH) load(ch + 1);
-#pragma unroll
-        for (int g = 0; g < GC; ++g) {
-            const f32x4 a = cxa[g], b = cxb[g];
-            acc = __builtin_elementwise_fma((f32x2){a.x, a.x}, (f32x2){ce0[g].x, ce1[g].x}, acc);
-            acc = __builtin_elementwise_fma((f32x2){a.y, a.y}, (f32x2){co0[g].x, co1[g].x}, acc);
-            acc = __builtin_elementwise_fma((f32x2){a.z, a.z}, (f32x2){ce0[g].y, ce1[g].y}, acc);
-            acc = __builtin_elementwise_fma((f32x2){a.w, a.w}, (f32x2){co0[g].y, co1[g].y}, acc);
-            acc = __builtin_elementwise_fma((f32x2){b.x, b.x}, (f32x2){ce0[g].z, ce1[g].z}, acc);
-            acc = __builtin_elementwise_fma((f32x2){b.y, b.y}, (f32x2){co0[g].z, co1[g].z}, acc);
-            acc = __builtin_elementwise_fma((f32x2){b.z, b.z}, (f32x2){ce0[g].w, ce1[g].w}, acc);
-            acc = __builtin_elementwise_fma((f32x2){b.w, b.w}, (f32x2){co0[g].w, co1[g].w}, acc);
-        }
-    }
-    f32x2 r;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        float tt = fmaf(1.0f, xn, acc[j]);
-        tt = fmaf((j ? p1 : p0)[DP], 1.0f, tt);
-        tt = (tt < 0.0f) ? 0.0f : tt;
-        r[j] = sqrtf(tt);
-    }
-    return r;
-}
 
 #ifdef VQ_EXP_SCREEN_COUNT
 __device__ unsigned long long g_scr_rows[3];  // [0] rows listed for the second pass, [1] rows screened, [2] rows rescored
@@ -691,6 +772,8 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
 
         float best_s;
         int best_i;
+        long long cand = 0;     // SCREEN: the candidate codes of a row on the rescore list (lane h == 0), stored as its idx
+        bool has_cand = false;
         if constexpr (SCREEN) {
             // the screened argmin of this lane (lowest code holding the lowest value), then both lane halves of the row
             const float l1 = lb.best_t, l2 = scr_b2;  // this lane's two lowest (codes lb.pend_u, scr_i2)
@@ -714,8 +797,8 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             // Uncertain rows.  Only a code with S <= thr = b1 + 2 delta + w can beat or tie the exact winner (its D would
             // otherwise exceed the winner's by more than the sqrt rounding window, and `eligible` excludes clamping).  When
             // the third lowest value of BOTH lane halves is above thr, the row's candidates are among the <= 4 codes the
-            // halves hold: they are rescored by the exact chain (rescore), every other row goes onto the list of rows that the
-            // second pass searches again in full (candidate overflow, NaN / inf rows, ineligible magnitudes, flagged codebooks).
+            // halves hold: the second pass rescores those by the exact chain (rescore); every other row goes onto the list of
+            // rows that it searches again in full (candidate overflow, NaN / inf rows, ineligible magnitudes, flagged codebooks).
             const float thr = b1 + 2.0f * delta + w;
             const bool complete = eligible && scr_b3 > thr && ob3 > thr;
             const unsigned rescore = (unsigned)__ballot(row_ok && !certain && complete);
@@ -728,28 +811,26 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
                 atomicAdd(&g_scr_rows[2], (unsigned long long)__builtin_popcount(rescore));
             }
 #endif
+            // Both kinds of uncertain row are decided by vq_resolve_rows_kernel after this kernel, which stores their idx and
+            // quantized rows; until then they keep the screened argmin in sidx (best_i < K: the deferred copy gathers a valid
+            // code row).  One array of H M entries head * M + row holds both lists: rows to search in full from the front,
+            // rows to rescore from the back (a row is on one list at most, so the ends never meet).
             if (rescore != 0u) {
-                // lane (c, h): the exact chains of its own candidates for row c (two k-ordered fmaf chains in one v_pk_fma_f32)
-                const bool mine = (rescore >> c) & 1u;
-                const bool u1 = mine && l1 <= thr, u2 = mine && l2 <= thr;
-                const int k1 = u1 ? li1 : 0, k2 = u2 ? li2 : k1;
-                const f32x2 sd = exact_pair_euclid<DP>(xh + (row_ok ? row : p.M - 1) * p.x_rs, p.D, pk + (long long)k1 * (DP + 4),
-                                                       pk + (long long)k2 * (DP + 4), xn0);
-                // lowest distance, then lowest code, over the lane's candidates and then over both halves of the row
-                float bv = u1 ? sd.x : INF;
-                int bk = u1 ? k1 : 0x7FFFFFFF;
-                if (u2 && (sd.y < bv || (sd.y == bv && k2 < bk))) {
-                    bv = sd.y;
-                    bk = k2;
+                // the row's candidates = the codes of both lane halves with S <= thr, as four 16-bit codes (0xFFFF: none;
+                // K <= 3072 here) in the row's own idx element, which the second pass reads and overwrites
+                const unsigned my = ((l1 <= thr) ? (unsigned)li1 : 0xFFFFu) | (((l2 <= thr) ? (unsigned)li2 : 0xFFFFu) << 16);
+                const unsigned other = (unsigned)__shfl_xor((int)my, 32);
+                unsigned at = 0u;
+                if (lane == 0) at = atomicAdd(p.scr_count + 1, (unsigned)__builtin_popcount(rescore));
+                at = __builtin_amdgcn_readfirstlane(at);
+                if (h == 0 && ((rescore >> c) & 1u)) {
+                    const unsigned cap = (unsigned)((long long)gridDim.y * p.M);
+                    p.scr_list[cap - 1u - (at + __builtin_popcount(rescore & ((1u << c) - 1u)))] = (unsigned)((long long)head * p.M + row);
+                    cand = (long long)(((unsigned long long)other << 32) | my);
+                    has_cand = true;
                 }
-                const float ov = __shfl_xor(bv, 32);
-                const int ok = __shfl_xor(bk, 32);
-                if (ov < bv || (ov == bv && ok < bk)) bk = ok;
-                if (mine) best_i = bk;
             }
             if (todo != 0u) {
-                // onto the list of vq_resolve_rows_kernel, which stores their idx and quantized rows after this kernel; until
-                // then they keep the screened argmin (best_i < K: the deferred copy gathers a valid code row)
                 unsigned at = 0u;
                 if (lane == 0) at = atomicAdd(p.scr_count, (unsigned)__builtin_popcount(todo));
                 at = __builtin_amdgcn_readfirstlane(at);
@@ -783,7 +864,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         PSTAMP(3);
         if (h == 0 && row_ok) {
             const long long o = (long long)head * p.idx_hs + row * p.idx_rs;
-            p.idx[o] = best_i;
+            p.idx[o] = has_cand ? cand : (long long)best_i;
             if (p.best) p.best[o] = best_s;
         }
         int *mine = sidx + ((it & 1) * WAVES + wave) * 32;
