@@ -234,6 +234,29 @@ int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_l
                        int64_t tgt_hs, const float *coef, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream);
 
 /*
+ * Backward of the straight-through Gumbel softmax over the similarities (utils/general.py:147-149 with
+ * codebooks.py:386-395), nothing of [M, K] in memory.  With s = similarities, g = dL/dquantize, a = g c^T, tau = 1 / temperature:
+ *   p = softmax_k(tau s), delta_m = sum_k p_mk a_mk, w = tau p (a - delta) = dL/ds, and through the similarities
+ *   dot: gx = w c, gc = w^T x;   Euclid: r = w / s (0 at s == 0), gx = x rowsum(r) - r c, gc = c colsum(r) - r^T x.
+ * All three use a->x, H, M, K, D (<= 256: VQ_E_UNSUPPORTED beyond), metric and the rows g (h, m, d) at g[h*g_hs + m*g_rs + d].
+ * lse2 / delta: [H][vq_gumbel_row_stride(M)] floats, 16-byte aligned.
+ * vq_gumbel_stats_f32 (a->packed): writes lse2[h][m] = log2 sum_k exp2(tau s log2 e) and delta[h][m].
+ * vq_gumbel_backward_x_f32 (a->packed): grad_x (h, m, d) at grad_x[h*gx_hs + m*gx_rs + d].
+ * vq_gumbel_backward_codes_f32 (a->cb, the natural codebook): grad_codes [H][K][D] contiguous -- the part through the
+ *   similarities only; the gradient of the gather itself is vq_ema_accumulate_f32 of g.  The rows are packed into the
+ *   workspace (>= vq_gumbel_workspace_bytes bytes, 16-byte aligned; 0 = unsupported shape), split over workgroups, and the
+ *   splits' partial sums are added in a fixed order: no float atomics, bit-identical results from run to run on one device.
+ */
+int64_t vq_gumbel_row_stride(int64_t M);
+int64_t vq_gumbel_workspace_bytes(int H, int64_t M, int K, int D);
+int vq_gumbel_stats_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, float *lse2, float *delta,
+                        void *stream);
+int vq_gumbel_backward_x_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2,
+                             const float *delta, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream);
+int vq_gumbel_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2,
+                                 const float *delta, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * Lookup-free quantization (LFQ) over C codebooks of d sign bits each, 1 <= d <= 20 (implicit codebook {-a, +a}^d).
  * v: [N][C][d] fp32, element (m, c, i) at v[m * v_rs + c * d + i] (rows may be strided, each row's C * d values contiguous).
  *

@@ -1,0 +1,65 @@
+"""Timings of the Gumbel straight-through backward: the three fused sweeps (row statistics, d/dx, d/dcodes) and the chunked
+path on the same inputs, beside vq_ce_backward_f32 on the same shapes (diagnostic; DESIGN.md quotes these).
+
+    python tools/gumbel_bench.py            # on the GPU box
+"""
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "vector-quantization-by-ml_amd"))
+
+from vector_quantization import gumbel, native  # noqa: E402
+
+PEAK = 157.3  # fp32 MFMA, TFLOP/s
+
+
+def timed(fn, n=5, warm=2):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def line(name, t, flops):
+    print(f"  {name:42s} {t:9.3f} ms  {flops / t / 1e9:7.1f} TFLOP/s ({flops / t / 1e9 / PEAK:.3f} of peak)")
+
+
+def shape(M, K, D, metric=native.EUCLID, tau=1.0):
+    dev = "cuda:0"
+    gen = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn((1, M, D), device=dev, generator=gen)
+    cb = torch.randn((1, K, D), device=dev, generator=gen)
+    g = torch.randn((1, M, D), device=dev, generator=gen)
+    tgt = torch.randint(0, K, (1, M), device=dev, generator=gen)
+    packed = native.pack_codebooks(cb, metric)
+    mkd = 2.0 * M * K * D  # one contraction
+    print(f"M={M} K={K} D={D} {'Euclid' if metric == native.EUCLID else 'dot'}")
+    lse, tl = native.softmax_stats(x, cb, target=tgt, packed=packed)
+    coef = torch.tensor([1.0 / M], device=dev)
+    line("vq_ce_backward_f32 (2 contractions)", timed(lambda: native.ce_backward(x, cb, lse, tl, tgt, coef, packed=packed)),
+         2 * mkd)
+    line("vq_softmax_stats_f32 (1 contraction)", timed(lambda: native.softmax_stats(x, cb, packed=packed)), mkd)
+    line("vq_gumbel_stats_f32 (2 contractions)",
+         timed(lambda: native.gumbel_stats(x, cb, g, metric=metric, tau=tau, packed=packed)), 2 * mkd)
+    lse2, delta = native.gumbel_stats(x, cb, g, metric=metric, tau=tau, packed=packed)
+    line("vq_gumbel_backward_x_f32 (3 contractions)",
+         timed(lambda: native.gumbel_backward_x(x, cb, g, lse2, delta, metric=metric, tau=tau, packed=packed)), 3 * mkd)
+    line("vq_gumbel_backward_codes_f32 (3 contractions)",
+         timed(lambda: native.gumbel_backward_codes(x, cb, g, lse2, delta, metric=metric, tau=tau)), 3 * mkd)
+    ind = tgt
+    line("chunked path, gx and gc (8 contractions)",
+         timed(lambda: gumbel._chunked_backward(x, cb, None, ind, g, metric, tau, False, True, True), n=2, warm=1), 8 * mkd)
+
+
+if __name__ == "__main__":
+    shape(262144, 1024, 256)
+    shape(65536, 8192, 64)

@@ -1,0 +1,380 @@
+// vq_gumbel.inc -- backward of the straight-through Gumbel softmax over the similarities (utils/general.py:147-149,
+// codebooks.py:386-395), nothing of [M, K] in memory.  Included by vq_kernels.hip (after vq_similarity.inc: shares its row
+// prologue, the tile geometry and the fragment pipeline of the search).
+// ------------------------------------------------------------------------------------------------
+//   s = similarities [M, K]   g = dL/dquantize [M, D]   a = g c^T [M, K]   tau = 1 / temperature
+//   p = softmax_k(tau s)      delta_m = sum_k p_mk a_mk      w = tau p (a - delta) = dL/ds
+//   dot     gx = w c                    gc = w^T x
+//   Euclid  r = w / s (0 at s == 0)     gx = x rowsum(r) - r c      gc = c colsum(r) - r^T x
+// One kernel, three roles.  "Resident" rows become MFMA B fragments of a wave (32 rows per wave), "streamed" rows pass
+// through LDS as packed images (vq_pack.inc layout) and are the A operands:
+//   kGumStats  resident x and g rows, streamed codes: two products per tile (s and a), online softmax in the log2 domain
+//              -> lse2[m] = log2 sum_k exp2(tau s log2 e) and delta[m]
+//   kGumX      the same two products, w (or r) in place in the accumulator of s, then the contraction with the SAME
+//              codebook tile (vq_ce_backward's G sweep: the accumulator registers are valid B operands as they stand)
+//   kGumC      the roles swapped: a wave owns 32 codes (one fragment set serves both products), tiles of the packed x rows
+//              and of the packed g rows are streamed, lse2 / delta are read per streamed row (= per accumulator register),
+//              the contraction runs onto the streamed x tile.  The rows are split over blockIdx.z; every split STORES its
+//              partial [K, D] (rank-one term included: it is linear in the split) and vq_gumbel_reduce_parts adds the
+//              splits in a fixed order: no atomics, bit-identical from run to run.
+// Registers at Dp = 256: kGumX holds x fragments + g fragments + gradient accumulators (3 x 128) and compiles to 472 of the
+// 512 entries without scratch, so the dims are NOT split over workgroups (a split would repeat the two products per part);
+// kGumC holds 128 + 128.  One wave per SIMD from Dp = 128 on.
+// ------------------------------------------------------------------------------------------------
+constexpr int kGumStats = 0;
+constexpr int kGumX = 1;
+constexpr int kGumC = 2;
+
+}  // namespace
+namespace vqi {
+struct GumbelParams {
+    const float *res;  // resident rows: x (kGumStats, kGumX) / the natural codebook (kGumC)
+    long long res_rs, res_hs;
+    const float *g;  // upstream gradient rows (kGumStats, kGumX)
+    long long g_rs, g_hs;
+    const float *img;  // streamed image of the two sweeps over s: packed codes / packed x rows (kGumC)
+    long long img_hs;
+    unsigned img_bytes;
+    const float *gimg;  // kGumC: packed g rows (plain values)
+    long long NR, NS;   // resident / streamed rows per head
+    int D, ntiles, vec_res, vec_g;
+    float tau;
+    float *lse, *delta;  // [H][st_hs]: log2-domain log-sum-exp and delta per row m (written by kGumStats)
+    long long st_hs;
+    float *out;  // gx (kGumX) / the partials of gc (kGumC)
+    long long out_rs, out_hs, out_zs;
+    int tiles_per_split;  // kGumC: streamed tiles per blockIdx.z
+};
+}  // namespace vqi
+namespace {
+using vqi::GumbelParams;
+
+template <int DP>
+struct GumGeo {
+    static constexpr int V = DP >= 128 ? 4 : DP / 32;  // floats per A-fragment read of the contraction (positions V i + e)
+    static constexpr int NJ = DP / (32 * V);           // 128-wide (V = 4) position blocks
+    static constexpr int NACC = DP / 32;               // 32x32 accumulators of the gradient
+    static constexpr int GS = DP + 4;                  // staging row stride (floats)
+};
+
+// both products over one staged tile: every fragment read feeds the s and the a accumulator
+template <int DP>
+__device__ __forceinline__ void mfma_range2(f32x16 &acc, f32x16 &acc2, f32x4 (&a)[DP / 8], const f32x4 *ta,
+                                            const float (&xf)[DP / 2], const float (&gf)[DP / 2]) {
+    constexpr int NG = FragPipe<DP>::NG, PF = FragPipe<DP>::PF;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        if (g + PF < NG) a[g + PF] = ta[2 * (g + PF)];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].x, xf[4 * g + 0], acc, 0, 0, 0);
+        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].x, gf[4 * g + 0], acc2, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].y, xf[4 * g + 1], acc, 0, 0, 0);
+        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].y, gf[4 * g + 1], acc2, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].z, xf[4 * g + 2], acc, 0, 0, 0);
+        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].z, gf[4 * g + 2], acc2, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].w, xf[4 * g + 3], acc, 0, 0, 0);
+        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g].w, gf[4 * g + 3], acc2, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+template <int DP, int METRIC, int ROLE>
+__global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const GumbelParams p) {
+    constexpr int WAVES = 4;
+    using G = Geo<DP, WAVES>;
+    using GG = GumGeo<DP>;
+    constexpr int RS = G::RS, RS4 = G::RS4, SUB = G::SUB, NG = DP / 8, V = GG::V, NJ = GG::NJ, NACC = GG::NACC;
+    constexpr bool EUCLID = (METRIC == VQ_METRIC_EUCLID);
+    constexpr bool CODES = (ROLE == kGumC);
+    constexpr bool STATS = (ROLE == kGumStats);
+    constexpr int IMG_F4 = 2 * G::BUF_F4;  // the two tile buffers of one image
+    constexpr float LOG2E = 1.4426950408889634f;
+    const float INF = __builtin_inff();
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    f32x4 *tile4 = (f32x4 *)smem;
+    lds_f32x4 *tile4_lds = (lds_f32x4 *)smem;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    const int head = blockIdx.y;
+    const long long row0 = ((long long)blockIdx.x * WAVES + wave) * 32;
+    const float *rh = p.res + (long long)head * p.res_hs;
+
+    float rf[DP / 2];
+    float rn0;
+    load_x_fragments<DP, WAVES, EUCLID>(rh, p.res_rs, p.NR, p.D, p.vec_res, row0, smem, wave, lane, rf, rn0);
+    float gf[CODES ? 1 : DP / 2];
+    if constexpr (!CODES) {
+        float unused;
+        load_x_fragments<DP, WAVES, false>(p.g + (long long)head * p.g_hs, p.g_rs, p.NR, p.D, p.vec_g, row0, smem, wave, lane, gf,
+                                           unused);
+    }
+
+    const long long row = row0 + c;
+    const bool row_ok = row < p.NR;
+    const float *img = p.img + (long long)head * p.img_hs;
+    const float *gimg = CODES ? p.gimg + (long long)head * p.img_hs : nullptr;
+    const float b_aug = h ? 1.0f : rn0;
+    const float tau2 = p.tau * LOG2E;
+    const long long st0 = (long long)head * p.st_hs;
+
+    // per resident row (kGumX): the statistics of this lane's row
+    float lse_row = 0.0f, delta_row = 0.0f;
+    if (ROLE == kGumX && row_ok) {
+        lse_row = p.lse[st0 + row];
+        delta_row = p.delta[st0 + row];
+    }
+    // kGumStats: running max / sum of exp2 / sum of exp2 * a over the codes this lane has seen
+    float run_m = -INF, run_s = 0.0f, run_d = 0.0f;
+
+    f32x16 gacc[STATS ? 1 : NACC];
+#pragma unroll
+    for (int j = 0; j < (STATS ? 1 : NACC); ++j) gacc[j] = (f32x16){0};
+    float sum_ratio = 0.0f;
+
+    auto stage = [&](int tile, int buf) {
+#pragma unroll
+        for (int i = 0; i < (G::TILE_CHUNKS + WAVES - 1) / WAVES; ++i) {
+            const int ck = i * WAVES + wave;
+            if (ck < G::TILE_CHUNKS) {
+                lds_dma16(img, p.img_bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16, tile4_lds + buf * G::BUF_F4 + ck * 64);
+                if constexpr (CODES)
+                    lds_dma16(gimg, p.img_bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16,
+                              tile4_lds + IMG_F4 + buf * G::BUF_F4 + ck * 64);
+            }
+        }
+    };
+
+    int t_begin = 0, t_end = p.ntiles;
+    if constexpr (CODES) {
+        t_begin = (int)blockIdx.z * p.tiles_per_split;
+        t_end = t_begin + p.tiles_per_split < p.ntiles ? t_begin + p.tiles_per_split : p.ntiles;
+    }
+    stage(t_begin, 0);
+    __syncthreads();
+    for (int t = t_begin; t < t_end; ++t) {
+        const int cur = (t - t_begin) & 1;
+        if (t + 1 < t_end) stage(t + 1, cur ^ 1);
+#pragma unroll 1
+        for (int st = 0; st < SUB; ++st) {
+            const int u = t * SUB + st;
+            if ((long long)u * kTileCodes >= p.NS) break;  // workgroup-uniform: nothing but padding from here on
+            const f32x4 *tb = tile4 + cur * G::BUF_F4 + st * (kTileCodes * RS4);
+            const long long sbase = (long long)u * kTileCodes + 4 * h;  // streamed row of this lane's register 0
+            // kGumC: the statistics of the 16 streamed rows this lane's registers stand for (rows 8 g + 4 h + 0..3 of the sub-tile)
+            f32x4 l4[4], d4[4];
+            if constexpr (CODES) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    l4[g] = *(const f32x4 *)(p.lse + st0 + sbase + 8 * g);
+                    d4[g] = *(const f32x4 *)(p.delta + st0 + sbase + 8 * g);
+                }
+            }
+            // ---- the two products: acc = t (squared distance / dot product), acca = the image's multiple of a
+            f32x16 acc = {0}, acca = {0};
+            {
+                const f32x4 *ta = tb + c * RS4 + h;
+                f32x4 a[NG];
+                const float cnv = EUCLID ? ((const float *)tb)[c * RS + DP] : 0.0f;
+                mfma_prefetch<DP>(a, ta);
+                if constexpr (CODES) mfma_range<DP, 0, NG>(acc, a, ta, rf);
+                else mfma_range2<DP>(acc, acca, a, ta, rf, gf);
+                if (EUCLID) {
+                    const float a_aug = h ? cnv : 1.0f;
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a_aug, b_aug, acc, 0, 0, 0);
+                }
+            }
+            if constexpr (CODES) {
+                const f32x4 *ta = tb + IMG_F4 + c * RS4 + h;
+                f32x4 a[NG];
+                mfma_prefetch<DP>(a, ta);
+                mfma_range<DP, 0, NG>(acca, a, ta, rf);
+            }
+            // (the codebook image of the Euclid metric holds -2 c; the image of the g rows holds g)
+            const float a_scale = (EUCLID && !CODES) ? -0.5f : 1.0f;
+            if constexpr (STATS) {
+                float l[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float tv = acc[r];
+                    l[r] = EUCLID ? -tau2 * __builtin_amdgcn_sqrtf(fmaxf(tv, 0.0f)) : tau2 * tv;
+                    if (sbase + (r & 3) + 8 * (r >> 2) >= p.NS) l[r] = -INF;
+                }
+                float tm = l[0];
+#pragma unroll
+                for (int r = 1; r < 16; ++r) tm = fmaxf(tm, l[r]);
+                if (tm > run_m) {
+                    const float sc = __builtin_amdgcn_exp2f(run_m - tm);  // exp2(-inf) = 0 on the first visit
+                    run_s *= sc;
+                    run_d *= sc;
+                    run_m = tm;
+                }
+                if (run_m > -INF) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float e = __builtin_amdgcn_exp2f(l[r] - run_m);
+                        run_s += e;
+                        run_d = fmaf(e, a_scale * acca[r], run_d);
+                    }
+                }
+            } else {
+                // ---- acc[r] <- w (dot) / r = w / s (Euclid) of (streamed row sbase + (r&3) + 8(r>>2), this lane's resident row)
+                float sum_u = 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float lse2 = CODES ? l4[r >> 2][r & 3] : lse_row;
+                    const float dl = CODES ? d4[r >> 2][r & 3] : delta_row;
+                    const float tv = acc[r];
+                    const float av = a_scale * acca[r];
+                    float v;
+                    if (EUCLID) {
+                        const float tc = fmaxf(tv, 0.0f);
+                        const float dist = __builtin_amdgcn_sqrtf(tc), rs = __builtin_amdgcn_rsqf(tc);
+                        const float pr = __builtin_amdgcn_exp2f(fmaf(dist, -tau2, -lse2));
+                        v = -((p.tau * pr) * (av - dl)) * rs;  // w / s with s = -dist; inf / nan at dist == 0 (fixed below)
+                    } else {
+                        const float pr = __builtin_amdgcn_exp2f(fmaf(tv, tau2, -lse2));
+                        v = (p.tau * pr) * (av - dl);
+                    }
+                    if (!(__builtin_fabsf(v) < INF)) v = 0.0f;                  // 1 / 0: ATen's subgradient 0
+                    if (sbase + (r & 3) + 8 * (r >> 2) >= p.NS) v = 0.0f;       // padding rows of the streamed image
+                    acc[r] = v;
+                    sum_u += v;
+                }
+                sum_ratio += sum_u;
+                // ---- contraction: gacc[J*V + e][position i, resident row] += img[streamed row (r, half)][128 J + V i + e] * acc[r]
+                const float *trow = (const float *)tb + (4 * h) * RS + V * c;
+                if constexpr (V == 4) {
+                    constexpr int NSEQ = NJ * 16, PF = 4;
+                    auto frag = [&](int n) -> f32x4 {
+                        const int J = n >> 4, r = n & 15;
+                        return *(const f32x4 *)(trow + ((r & 3) + 8 * (r >> 2)) * RS + 128 * J);
+                    };
+                    f32x4 af[NSEQ];
+#pragma unroll
+                    for (int n = 0; n < PF; ++n) af[n] = frag(n);
+#pragma unroll
+                    for (int n = 0; n < NSEQ; ++n) {
+                        if (n + PF < NSEQ) af[n + PF] = frag(n + PF);
+                        const int J = n >> 4, r = n & 15;
+                        gacc[J * 4 + 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[n].x, acc[r], gacc[J * 4 + 0], 0, 0, 0);
+                        gacc[J * 4 + 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[n].y, acc[r], gacc[J * 4 + 1], 0, 0, 0);
+                        gacc[J * 4 + 2] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[n].z, acc[r], gacc[J * 4 + 2], 0, 0, 0);
+                        gacc[J * 4 + 3] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[n].w, acc[r], gacc[J * 4 + 3], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float *ap = trow + ((r & 3) + 8 * (r >> 2)) * RS;
+                        if (V == 2) {
+                            const float a0 = ap[0], a1 = ap[1];
+                            gacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, acc[r], gacc[0], 0, 0, 0);
+                            gacc[NACC > 1 ? 1 : 0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, acc[r], gacc[NACC > 1 ? 1 : 0], 0, 0, 0);
+                        } else {
+                            gacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[0], acc[r], gacc[0], 0, 0, 0);
+                        }
+                        if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // bound the fragment reads in flight
+                    }
+                }
+            }
+        }
+        __syncthreads();  // next tile landed, everybody is done reading this one
+    }
+
+    if constexpr (STATS) {
+        const float om = __shfl_xor(run_m, 32), os = __shfl_xor(run_s, 32), od = __shfl_xor(run_d, 32);
+        const float mm = fmaxf(run_m, om);  // lane half 0 always saw streamed row 0, so mm is finite
+        const float w0 = run_m > -INF ? __builtin_amdgcn_exp2f(run_m - mm) : 0.0f;
+        const float w1 = om > -INF ? __builtin_amdgcn_exp2f(om - mm) : 0.0f;
+        const float s = run_s * w0 + os * w1;
+        const float d = run_d * w0 + od * w1;
+        if (h == 0 && row_ok) {
+            p.lse[st0 + row] = mm + __builtin_amdgcn_logf(s);
+            p.delta[st0 + row] = d / s;
+        }
+    } else {
+        // ---------------- finalize: fragment layout -> natural rows through LDS ----------------
+        // (the loop's last barrier guarantees nobody reads the tile buffers any more; the region is wave-private)
+        constexpr int GS = GG::GS;
+        float *stg = smem + wave * (32 * GS + 32);
+        float *srs = stg + 32 * GS;
+        sum_ratio += __shfl_xor(sum_ratio, 32);
+        if (h == 0) srs[c] = sum_ratio;
+#pragma unroll
+        for (int a = 0; a < NACC; ++a) {
+            const int J = a / V, e = a % V;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int i = 8 * (r >> 2) + 4 * h + (r & 3);  // MFMA i index held by this lane's register r
+                const int pos = 32 * V * J + V * i + e;        // position in the packed row
+                const int p8 = pos & 7;
+                const int dim = (pos & ~7) + (p8 < 4 ? 2 * p8 : 2 * (p8 - 4) + 1);
+                stg[c * GS + dim] = gacc[a][r];
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private region: in-order LDS, no barrier needed
+        const long long left = p.NR - row0;
+        const int nrows = left >= 32 ? 32 : (left > 0 ? (int)left : 0);
+        float *oh = p.out + (CODES ? (long long)blockIdx.z * p.out_zs : 0) + (long long)head * p.out_hs;
+        for (int rr = 0; rr < nrows; ++rr) {
+            const float sr = srs[rr];
+            const float *xr = rh + (row0 + rr) * p.res_rs;
+            float *orow = oh + (row0 + rr) * p.out_rs;
+            for (int d = lane; d < p.D; d += 64) {
+                const float gv = stg[rr * GS + d];
+                // Euclid: x rowsum(r) - r c  with the image holding -2 c (kGumC: c colsum(r) - r^T x, image -2 x)
+                orow[d] = EUCLID ? fmaf(xr[d], sr, 0.5f * gv) : gv;
+            }
+        }
+    }
+}
+
+// packed images of the x rows (metric-scaled, |x|^2 behind every row: vq_pack.inc layout) and of the g rows (plain) for
+// kGumC; rows may be strided.  One thread per packed row; rows past M are zero (|x|^2 = +inf under Euclid, as for padding codes).
+__global__ void __launch_bounds__(64) vq_gumbel_pack_rows(const float *__restrict__ x, long long x_rs, long long x_hs,
+                                                          const float *__restrict__ g, long long g_rs, long long g_hs, long long M,
+                                                          long long Mp, int D, int DP, int metric, float *__restrict__ ximg,
+                                                          float *__restrict__ gimg, long long img_hs) {
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= Mp) return;
+    const int RS = DP + 4;
+    const bool real = m < M;
+    const float *xs = x + (long long)blockIdx.y * x_hs + (real ? m : 0) * x_rs;
+    const float *gs = g + (long long)blockIdx.y * g_hs + (real ? m : 0) * g_rs;
+    float *xd = ximg + (long long)blockIdx.y * img_hs + m * RS;
+    float *gd = gimg + (long long)blockIdx.y * img_hs + m * RS;
+    const float scale = (metric == VQ_METRIC_EUCLID) ? -2.0f : 1.0f;
+    float cn = 0.0f;
+    for (int g8 = 0; g8 < DP / 8; ++g8) {
+        float v[8], w[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int d = 8 * g8 + e;
+            const bool in = real && d < D;
+            v[e] = in ? xs[d] : 0.0f;
+            w[e] = in ? gs[d] : 0.0f;
+            cn = fmaf(v[e], v[e], cn);  // d-ordered chain; padded zeros leave it unchanged
+        }
+        *(f32x4 *)(xd + 8 * g8) = (f32x4){scale * v[0], scale * v[2], scale * v[4], scale * v[6]};
+        *(f32x4 *)(xd + 8 * g8 + 4) = (f32x4){scale * v[1], scale * v[3], scale * v[5], scale * v[7]};
+        *(f32x4 *)(gd + 8 * g8) = (f32x4){w[0], w[2], w[4], w[6]};
+        *(f32x4 *)(gd + 8 * g8 + 4) = (f32x4){w[1], w[3], w[5], w[7]};
+    }
+    const float chain = real ? cn : 0.0f;
+    if (!real) cn = __builtin_inff();
+    *(f32x4 *)(xd + DP) = (f32x4){(metric == VQ_METRIC_EUCLID) ? cn : 0.0f, 1.0f, chain, 0.0f};
+    *(f32x4 *)(gd + DP) = (f32x4){0.0f, 1.0f, 0.0f, 0.0f};
+}
+
+// gc[i] = parts[0][i] + parts[1][i] + ... in this order, i over [H, K, D]
+__global__ void __launch_bounds__(256) vq_gumbel_reduce_parts(const float *__restrict__ parts, long long n, int splits,
+                                                              float *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = parts[i];
+    for (int z = 1; z < splits; ++z) s += parts[(long long)z * n + i];
+    out[i] = s;
+}

@@ -59,6 +59,7 @@
 //   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward
+//   7 Gumbel straight-through backward sweeps
 #ifndef VQ_PART
 #define VQ_PART -1
 #endif
@@ -79,6 +80,7 @@ namespace {
 #include "vq_search_persist.inc"
 #include "vq_search_resident.inc"
 #include "vq_similarity.inc"
+#include "vq_gumbel.inc"
 #if VQ_OWN(0)
 #include "vq_finalize_ema.inc"
 #include "vq_lfq.inc"
@@ -368,6 +370,29 @@ int launch_ce_bwd_m(const CeBwdParams &p, int H, int metric, hipStream_t s) {
     });
 }
 
+// the Gumbel backward sweeps: `gz` = row splits of kGumC
+template <int DP, int METRIC, int ROLE>
+int launch_gumbel_t(const GumbelParams &p, int H, int gz, hipStream_t s) {
+    using G = Geo<DP, 4>;
+    using GG = GumGeo<DP>;
+    const size_t tile_floats = (size_t)(ROLE == kGumC ? 2 : 1) * 2 * G::BUF_F4 * 4, rows_floats = (size_t)4 * 32 * G::XS;
+    const size_t stage_floats = ROLE == kGumStats ? 0 : (size_t)4 * (32 * GG::GS + 32);
+    size_t floats = tile_floats > rows_floats ? tile_floats : rows_floats;
+    if (stage_floats > floats) floats = stage_floats;
+    return launch<vq_gumbel_sweep<DP, METRIC, ROLE>, kBigLds>(dim3((unsigned)((p.NR + 127) / 128), (unsigned)H, (unsigned)gz),
+                                                              dim3(256), floats * 4, s, "vq_gumbel_sweep launch", p);
+}
+
+template <int DP>
+int launch_gumbel_m(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s) {
+    return with_metric(metric, [&](auto m) {
+        constexpr int ME = decltype(m)::value;
+        if (role == kGumStats) return launch_gumbel_t<DP, ME, kGumStats>(p, H, 1, s);
+        if (role == kGumX) return launch_gumbel_t<DP, ME, kGumX>(p, H, 1, s);
+        return launch_gumbel_t<DP, ME, kGumC>(p, H, gz, s);
+    });
+}
+
 #ifndef VQ_EXP_RESIDENT_MIN_ROWS_PER_CU
 #define VQ_EXP_RESIDENT_MIN_ROWS_PER_CU 512  // rows per CU from which the resident-codebook kernel takes a small codebook
 #endif
@@ -408,6 +433,11 @@ template <int DP> int part_wide(int wide, const SearchParams &p, int H, int spli
 template <int DP> int part_resident(const SearchParams &p, int H, int cus, int metric, hipStream_t s);
 template <int DP> int part_aux(const AuxParams &p, int H, int metric, int mode, hipStream_t s);
 template <int DP> int part_ce_bwd(const CeBwdParams &p, int H, int metric, hipStream_t s);
+template <int DP> int part_gumbel(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <> int part_gumbel<32>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <> int part_gumbel<64>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <> int part_gumbel<128>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <> int part_gumbel<256>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 int part_pair(const SearchParams &p, int H, int splits, int metric, hipStream_t s);
 int part_persist(const SearchChoice &c, const SearchParams &p, int H, int cus, int metric, hipStream_t s);
 #define VQ_DECLARE_PARTS(DP)                                                                                         \
@@ -499,6 +529,15 @@ VQ_DEFINE_CE_PART(128)
 VQ_DEFINE_CE_PART(256)
 VQ_DEFINE_CE_PART(512)
 #undef VQ_DEFINE_CE_PART
+#endif
+#if VQ_OWN(7)
+#define VQ_DEFINE_GUMBEL_PART(DP) \
+    template <> int part_gumbel<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s) { return launch_gumbel_m<DP>(role, p, H, gz, metric, s); }
+VQ_DEFINE_GUMBEL_PART(32)
+VQ_DEFINE_GUMBEL_PART(64)
+VQ_DEFINE_GUMBEL_PART(128)
+VQ_DEFINE_GUMBEL_PART(256)
+#undef VQ_DEFINE_GUMBEL_PART
 #endif
 }  // namespace vqi
 
@@ -972,6 +1011,28 @@ int run_search_keys(const vq_args *a, long long idx_offset, long long *keys, hip
     p.tiles_per_split = kp.tiles_per_split;
     const int cus = device_cus();  // (a keys-mode search is never a whole fused call: wave pairs or one block)
     return launch_search(choose_search(kp.DP, kp.waves, p, a->H, kp.splits, a->metric, cus), kp.DP, p, a->H, kp.splits, a->metric, cus, s);
+}
+
+// vq_gumbel_backward_codes_f32: the rows are streamed as packed images (vq_packed_floats layout) and split over
+// workgroups so that every CU has one (a workgroup owns 128 codes of one head); every split is at least one staged tile
+struct GumbelCodesPlan {
+    long long Mp, img_floats;
+    int ntiles, tiles_per_split, splits;
+};
+GumbelCodesPlan plan_gumbel_codes(int H, long long M, int K, int D) {
+    GumbelCodesPlan pl;
+    const int tile = kTileCodes * sub_tiles(padded_dim(D));
+    pl.Mp = (M + tile - 1) / tile * tile;
+    pl.img_floats = pl.Mp * (padded_dim(D) + 4) + kPackSlack;
+    pl.ntiles = (int)(pl.Mp / tile);
+    const long long blocks = (long long)((K + 127) / 128) * H;
+    long long want = (device_cus() + blocks - 1) / blocks;
+    if (want > 64) want = 64;
+    if (want > pl.ntiles) want = pl.ntiles;
+    if (want < 1) want = 1;
+    pl.tiles_per_split = (int)((pl.ntiles + want - 1) / want);
+    pl.splits = (pl.ntiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
+    return pl;
 }
 
 }  // namespace
@@ -1580,6 +1641,127 @@ int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_l
     hipStream_t s = (hipStream_t)stream;
     return with_padded_dim(DP, [&](auto dp) { return vqi::part_ce_bwd<decltype(dp)::value>(p, a->H, a->metric, s); },
                            [] { return fail(VQ_E_UNSUPPORTED, "vq_ce_backward: unsupported padded dim"); });
+}
+
+// ---- Gumbel straight-through backward (vq_gumbel.inc) -----------------------------------------------------------------
+int64_t vq_gumbel_row_stride(int64_t M) { return M <= 0 ? 0 : (M + 255) / 256 * 256; }
+
+int64_t vq_gumbel_workspace_bytes(int H, int64_t M, int K, int D) {
+    if (H <= 0 || M <= 0 || K <= 0 || D <= 0 || D > 256 || M > 0x7FFFFFFFll) return 0;
+    const GumbelCodesPlan pl = plan_gumbel_codes(H, M, K, D);
+    return 4 * (2 * (int64_t)H * pl.img_floats + (pl.splits > 1 ? (int64_t)pl.splits * H * K * D : 0));
+}
+
+static int fill_gumbel_params(GumbelParams &p, const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau,
+                              const float *lse2, const float *delta) {
+    memset(&p, 0, sizeof(p));
+    if (!g || !lse2 || !delta) return fail(VQ_E_BADARG, "vq_gumbel: null argument (g / lse2 / delta)");
+    if (!(tau > 0.0f)) return fail(VQ_E_BADARG, "vq_gumbel: tau must be positive");
+    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, "vq_gumbel: D > 256 (use row chunks of vq_similarities_f32)");
+    if (!aligned16(lse2) || !aligned16(delta)) return fail(VQ_E_BADARG, "vq_gumbel: lse2 / delta must be 16-byte aligned");
+    p.D = a->D;
+    p.tau = tau;
+    p.lse = (float *)lse2;
+    p.delta = (float *)delta;
+    p.st_hs = vq_gumbel_row_stride(a->M);
+    p.g = g; p.g_rs = g_rs; p.g_hs = g_hs;
+    p.vec_g = vec4_ok(g, {a->D, g_rs, g_hs}) ? 1 : 0;
+    return 0;
+}
+
+// kGumStats / kGumX: the rows are resident, the packed codebook is streamed
+static int fill_gumbel_rows(GumbelParams &p, const vq_args *a) {
+    AuxParams ap;
+    if (int rc = fill_aux_params(ap, a)) return rc;
+    p.res = a->x; p.res_rs = a->x_rs; p.res_hs = a->x_hs;
+    p.vec_res = ap.vec_x;
+    p.img = ap.packed; p.img_hs = ap.pk_hs; p.img_bytes = ap.pk_bytes;
+    p.NR = a->M; p.NS = a->K;
+    p.ntiles = ap.ntiles;
+    return 0;
+}
+
+int vq_gumbel_stats_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, float *lse2, float *delta,
+                        void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    if (a->M == 0) return 0;
+    GumbelParams p;
+    if ((rc = fill_gumbel_params(p, a, g, g_rs, g_hs, tau, lse2, delta))) return rc;
+    if ((rc = fill_gumbel_rows(p, a))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    return with_padded_dim(padded_dim(a->D) == 512 ? 0 : padded_dim(a->D),
+                           [&](auto dp) {
+                               constexpr int DP = decltype(dp)::value;
+                               if constexpr (DP <= 256) return vqi::part_gumbel<DP>(kGumStats, p, a->H, 1, a->metric, s);
+                               else return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
+                           },
+                           [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim"); });
+}
+
+int vq_gumbel_backward_x_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2,
+                             const float *delta, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    if (a->M == 0) return 0;
+    if (!grad_x) return fail(VQ_E_BADARG, "vq_gumbel_backward_x: grad_x is null");
+    GumbelParams p;
+    if ((rc = fill_gumbel_params(p, a, g, g_rs, g_hs, tau, lse2, delta))) return rc;
+    if ((rc = fill_gumbel_rows(p, a))) return rc;
+    p.out = grad_x; p.out_rs = gx_rs; p.out_hs = gx_hs;
+    hipStream_t s = (hipStream_t)stream;
+    return with_padded_dim(padded_dim(a->D) == 512 ? 0 : padded_dim(a->D),
+                           [&](auto dp) {
+                               constexpr int DP = decltype(dp)::value;
+                               if constexpr (DP <= 256) return vqi::part_gumbel<DP>(kGumX, p, a->H, 1, a->metric, s);
+                               else return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
+                           },
+                           [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim"); });
+}
+
+int vq_gumbel_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2,
+                                 const float *delta, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    if (!grad_codes || !a->cb) return fail(VQ_E_BADARG, "vq_gumbel_backward_codes: null argument (grad_codes / cb)");
+    hipStream_t s = (hipStream_t)stream;
+    const long long n = (long long)a->H * a->K * a->D;
+    if (a->M == 0) {
+        const hipError_t e = hipMemsetAsync(grad_codes, 0, (size_t)n * 4, s);
+        return e == hipSuccess ? 0 : hip_fail(e, "vq_gumbel_backward_codes memset");
+    }
+    GumbelParams p;
+    if ((rc = fill_gumbel_params(p, a, g, g_rs, g_hs, tau, lse2, delta))) return rc;
+    if (a->M > 0x7FFFFFFFll) return fail(VQ_E_UNSUPPORTED, "vq_gumbel_backward_codes: too many rows (use row chunks)");
+    const GumbelCodesPlan pl = plan_gumbel_codes(a->H, a->M, a->K, a->D);
+    if (pl.img_floats * 4 >= (1ll << 31))
+        return fail(VQ_E_UNSUPPORTED, "vq_gumbel_backward_codes: packed row image >= 2 GiB (use row chunks)");
+    if (!workspace || !aligned16(workspace) || workspace_bytes < vq_gumbel_workspace_bytes(a->H, a->M, a->K, a->D))
+        return fail(VQ_E_BADARG, "vq_gumbel_backward_codes: workspace too small or misaligned (see vq_gumbel_workspace_bytes)");
+    const int DP = padded_dim(a->D);
+    float *ximg = (float *)workspace, *gimg = ximg + (long long)a->H * pl.img_floats, *parts = gimg + (long long)a->H * pl.img_floats;
+    if ((rc = launch<vq_gumbel_pack_rows>(dim3((unsigned)((pl.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
+                                          (long long)a->x_rs, (long long)a->x_hs, g, (long long)g_rs, (long long)g_hs, (long long)a->M, pl.Mp,
+                                          a->D, DP, a->metric, ximg, gimg, pl.img_floats)))
+        return rc;
+    p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
+    p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
+    p.img = ximg; p.gimg = gimg; p.img_hs = pl.img_floats; p.img_bytes = (unsigned)(pl.img_floats * 4);
+    p.NR = a->K; p.NS = a->M;
+    p.ntiles = pl.ntiles;
+    p.tiles_per_split = pl.tiles_per_split;
+    p.out = pl.splits > 1 ? parts : grad_codes;
+    p.out_rs = a->D; p.out_hs = (long long)a->K * a->D; p.out_zs = n;
+    rc = with_padded_dim(DP == 512 ? 0 : DP,
+                         [&](auto dp) {
+                             constexpr int DPC = decltype(dp)::value;
+                             if constexpr (DPC <= 256) return vqi::part_gumbel<DPC>(kGumC, p, a->H, pl.splits, a->metric, s);
+                             else return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
+                         },
+                         [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim"); });
+    if (rc || pl.splits == 1) return rc;
+    return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
+                                          pl.splits, grad_codes);
 }
 
 int vq_max_fused_stages(int D, int want_sq_err) {

@@ -142,6 +142,9 @@ class Codebook(nn.Module):
         if gumbel_params is None:
             gumbel_params = GumbelParams()
         self.gumbel_params = asdict(gumbel_params) if is_dataclass(gumbel_params) else dict(gumbel_params)
+        assert not (self.gumbel_params.get("reinmax", False) and not self.gumbel_params.get("straight_through", False)), (
+            "reinmax can only be turned on if using straight through gumbel softmax"
+        )
 
         assert not (use_ddp and num_codebooks > 1 and initialization_by_kmeans), (
             "kmeans init is not compatible with multiple codebooks in distributed environment for now"
@@ -168,6 +171,14 @@ class Codebook(nn.Module):
         GumbelParams.training (default True) -- NOT the module's train / eval state."""
         g = self.gumbel_params
         return bool(g.get("training", True) and g.get("stochastic", False) and g.get("temperature", 1.0) > 0)
+
+    def _relaxation_active(self) -> bool:
+        """The selection is differentiated through softmax(similarities / temperature) (utils/general.py:135): asked for,
+        at a positive temperature, with GumbelParams.training, and -- the reference gathers by index in eval mode
+        (codebooks.py:393-397) -- only while the module trains."""
+        g = self.gumbel_params
+        return bool(self.training and g.get("straight_through", False) and g.get("training", True)
+                    and g.get("temperature", 1.0) > 0)
 
     def _sync_sum(self, t: torch.Tensor) -> torch.Tensor:
         if self.use_ddp and dist.is_available() and dist.is_initialized():
@@ -220,6 +231,13 @@ class Codebook(nn.Module):
             return (*res, None) if want_lse else res
         codes = self.current_codes()
         packed = self.packed_codes()
+        if (self._relaxation_active() and torch.is_grad_enabled() and (flat.requires_grad or codes.requires_grad)
+                and (not ste or (want_sq_err and codebook_grad_from_err))):
+            # (with the straight-through output and a detached squared error nothing consumes the relaxation's gradient:
+            # the single launch below stays -- VectorQuantize with an EMA codebook, where the reference discards it too)
+            res = self._quantize_relaxed(flat, codes, packed, ste=ste, want_sq_err=want_sq_err,
+                                         codebook_grad_from_err=codebook_grad_from_err, idx=idx, frozen=frozen)
+            return (*res, None) if want_lse else res
         if (torch.is_grad_enabled() and flat.requires_grad and not codes.requires_grad and self.training and self.ema_update
                 and not frozen):
             # the EMA step that follows rewrites the codebook in place; the backward pass (commitment loss: 2 (x - c))
@@ -238,17 +256,42 @@ class Codebook(nn.Module):
             return out, idx[..., 0], sq_err, (res[3]["lse"], best if self.use_cosine_sim else -best)
         return out, idx[..., 0], sq_err
 
+    def _quantize_relaxed(self, flat, codes, packed, *, ste, want_sq_err, codebook_grad_from_err, idx, frozen):
+        """Argmax selection with the straight-through / reinmax Gumbel gradient: the search runs as always (indices stay
+        bit-exact), the gathered rows go through gumbel.relaxed_gather, the rest is tensor ops on its output."""
+        from . import gumbel
+
+        g = self.gumbel_params
+        with torch.no_grad():
+            _, ind, _ = search.quantize_rows(flat.detach(), codes.detach()[:, None], metric=self.metric, idx=idx,
+                                             packed=packed)
+        ind = ind[..., 0]
+        live = None
+        if self.ema_update and not frozen:
+            # the EMA step that follows rewrites the codes behind autograd's back: the reference's backward takes the
+            # softmax and the distances from the codes of this forward and multiplies with the updated ones
+            codes, live = codes.clone(), self.embeddings
+        x = flat.float()
+        picked = gumbel.relaxed_gather(x, codes, ind, self.metric, g.get("temperature", 1.0), g.get("reinmax", False), live)
+        sq_err = None
+        if want_sq_err:
+            target = picked if codebook_grad_from_err else picked.detach()
+            sq_err = ((target - x) ** 2).sum(dtype=torch.float64).reshape(1)
+        out = x + (picked - x).detach() if ste else picked
+        return out, ind, sq_err
+
     def _quantize_stochastic(self, flat, *, ste, want_sq_err, codebook_grad_from_err, idx=None):
         """Gumbel-max sampling of the code (utils/general.py:106-129): ind = argmax(similarities / temperature + g),
         g = -log(-log(u)).  RNG-dependent, so no parity with the reference's draws is possible; the similarities come
         from the native kernel in bounded row chunks and the noise from torch's generator on the tensor's device.
-        Straight-through / reinmax relaxations (gradients through the softmax) are not provided."""
+        The straight-through / reinmax relaxations are provided for the argmax selection (_quantize_relaxed), not for
+        sampled codes."""
         from . import losses
 
         g = self.gumbel_params
         if g.get("straight_through", False) or g.get("reinmax", False):
-            raise NotImplementedError("straight-through / reinmax Gumbel relaxations are outside the MI355X hot-path "
-                                      "build (SURVEY 2, #4); plain stochastic sampling is supported")
+            raise NotImplementedError("straight-through / reinmax Gumbel relaxations are provided for the argmax selection "
+                                      "only; plain stochastic sampling is supported")
         codes = self.current_codes()
         h, m, _ = flat.shape
         x = flat.float()

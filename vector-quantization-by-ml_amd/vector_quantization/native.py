@@ -137,6 +137,16 @@ def load():
         lib.vq_softmax_stats_f32.restype = ctypes.c_int
         lib.vq_ce_backward_f32.argtypes = [ap, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]
         lib.vq_ce_backward_f32.restype = ctypes.c_int
+        lib.vq_gumbel_row_stride.argtypes = [_i64]
+        lib.vq_gumbel_row_stride.restype = _i64
+        lib.vq_gumbel_workspace_bytes.argtypes = [ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int]
+        lib.vq_gumbel_workspace_bytes.restype = _i64
+        lib.vq_gumbel_stats_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp]
+        lib.vq_gumbel_stats_f32.restype = ctypes.c_int
+        lib.vq_gumbel_backward_x_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _vp]
+        lib.vq_gumbel_backward_x_f32.restype = ctypes.c_int
+        lib.vq_gumbel_backward_codes_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _vp]
+        lib.vq_gumbel_backward_codes_f32.restype = ctypes.c_int
         lib.vq_quantize_backward_f32.argtypes = [ap, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]
         lib.vq_quantize_backward_f32.restype = ctypes.c_int
         lib.vq_ema_accumulate_residual_f32.argtypes = [ap, _vp, _vp, _vp]
@@ -205,6 +215,8 @@ EXPORTED_SYMBOLS = (
     "vq_rlfq_workspace_bytes", "vq_rlfq_quantize_f32", "vq_rlfq_backward_f32",
     "vq_fsq_quantize_f32", "vq_fsq_backward_f32", "vq_fsq_decode_f32",
     "vq_lq_workspace_bytes", "vq_lq_quantize_f32", "vq_lq_backward_f32",
+    "vq_gumbel_row_stride", "vq_gumbel_workspace_bytes", "vq_gumbel_stats_f32", "vq_gumbel_backward_x_f32",
+    "vq_gumbel_backward_codes_f32",
 )
 
 
@@ -620,6 +632,87 @@ def ce_backward(x: torch.Tensor, cb: torch.Tensor, lse: torch.Tensor, target_log
                                          int(target.stride(0)), coef.data_ptr(), gx.data_ptr(), D, M * D,
                                          _stream_ptr(x.device)), "vq_ce_backward_f32")
     return gx
+
+
+GUMBEL_MAX_DIM = 256  # vq_gumbel_*_f32: rows of one launch
+
+
+def _gumbel_args(x, cb, g, metric, packed):
+    a, packed = _aux_args(x, cb, metric, packed, 0)
+    _require_gpu(g)
+    assert a.D <= GUMBEL_MAX_DIM and g.dtype == torch.float32 and tuple(g.shape) == tuple(x.shape)
+    g_rs, g_hs = _row_strides(g)
+    return a, packed, g_rs, g_hs
+
+
+def gumbel_stats(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, *, metric: int = EUCLID, tau: float = 1.0,
+                 packed: torch.Tensor | None = None):
+    """Row statistics of the straight-through Gumbel backward: x, g [H, M, D] (strided rows ok), cb [H, K, D] ->
+    (lse2, delta), both [H, vq_gumbel_row_stride(M)] (columns past M unused): lse2 = log2 sum_k exp2(tau * sim * log2 e),
+    delta = sum_k softmax_k(tau * sim) * (g . c_k).  The pair is what gumbel_backward_x / gumbel_backward_codes take."""
+    a, packed, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
+    stride = int(load().vq_gumbel_row_stride(a.M))
+    lse2 = torch.empty((a.H, stride), dtype=torch.float32, device=x.device)
+    delta = torch.empty((a.H, stride), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(load().vq_gumbel_stats_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(),
+                                          delta.data_ptr(), _stream_ptr(x.device)), "vq_gumbel_stats_f32")
+    return lse2, delta
+
+
+def gumbel_backward_x(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, lse2: torch.Tensor, delta: torch.Tensor, *,
+                      metric: int = EUCLID, tau: float = 1.0, packed: torch.Tensor | None = None,
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+    """d/dx of the straight-through Gumbel softmax through the similarities, one fused sweep -> gx [H, M, D]
+    (``out``: a destination with strided rows)."""
+    a, packed, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
+    H, M, D = x.shape
+    stride = int(load().vq_gumbel_row_stride(M))
+    for t in (lse2, delta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (H, stride) and t.device == x.device
+    if out is None:
+        out = torch.empty((H, M, D), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (H, M, D) and out.device == x.device
+    o_rs, o_hs = _row_strides(out)
+    with torch.cuda.device(x.device):
+        _check(load().vq_gumbel_backward_x_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(),
+                                               delta.data_ptr(), out.data_ptr(), o_rs, o_hs, _stream_ptr(x.device)),
+               "vq_gumbel_backward_x_f32")
+    return out
+
+
+def gumbel_codes_supported(H: int, M: int, K: int, D: int) -> bool:
+    """vq_gumbel_backward_codes_f32 streams the rows as one packed image per head (< 2 GiB)."""
+    return D <= GUMBEL_MAX_DIM and 0 < M < (1 << 31) and 0 < packed_floats(M, D) * 4 < (1 << 31)
+
+
+def gumbel_backward_codes(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, lse2: torch.Tensor, delta: torch.Tensor, *,
+                          metric: int = EUCLID, tau: float = 1.0) -> torch.Tensor:
+    """d/dcodes of the straight-through Gumbel softmax through the similarities -> [H, K, D] (the gather's own scatter
+    term is ema_accumulate of g).  Atomics-free: bit-identical from run to run on one device."""
+    _require_gpu(x, cb, g)
+    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and g.dtype == torch.float32
+    assert x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous() and tuple(g.shape) == tuple(x.shape)
+    H, M, D = x.shape
+    K = cb.shape[1]
+    assert cb.shape[0] == H and cb.shape[2] == D and gumbel_codes_supported(H, M, K, D)
+    stride = int(load().vq_gumbel_row_stride(M))
+    for t in (lse2, delta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (H, stride) and t.device == x.device
+    x_rs, x_hs = _row_strides(x)
+    g_rs, g_hs = _row_strides(g)
+    a = VqArgs()
+    a.H, a.Q, a.M, a.K, a.D, a.metric, a.flags = H, 1, M, K, D, metric, 0
+    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
+    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), K * D, 0
+    gc = torch.empty((H, K, D), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        nbytes = int(load().vq_gumbel_workspace_bytes(H, M, K, D))
+        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=x.device)
+        _check(load().vq_gumbel_backward_codes_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(),
+                                                   delta.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                                   _stream_ptr(x.device)), "vq_gumbel_backward_codes_f32")
+    return gc
 
 
 def quantize_backward(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor, grad_out: torch.Tensor | None,

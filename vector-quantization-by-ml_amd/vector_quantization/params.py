@@ -29,8 +29,11 @@ class KmeansParameters:
 
 @dataclass
 class GumbelParams:
-    """Sampling options of the code selection: deterministic argmax (native, bit-exact) or stochastic Gumbel-max sampling
-    (native similarities + device RNG); the straight-through / reinmax relaxations are not provided."""
+    """Options of the code selection: deterministic argmax (native, bit-exact) or stochastic Gumbel-max sampling (native
+    similarities + device RNG).  ``straight_through`` (optionally with ``reinmax``) keeps the argmax selection and its value
+    and adds the reference's gradient through ``softmax(similarities / temperature)`` to the encoder and to a learnable
+    codebook; it is active at ``temperature > 0`` with ``training`` while the module is in train mode (gumbel.py).
+    ``reinmax`` needs ``straight_through``; ``stochastic`` together with ``straight_through`` raises NotImplementedError."""
 
     temperature: float = 1.0
     stochastic: bool = False

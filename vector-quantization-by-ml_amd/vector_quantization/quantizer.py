@@ -44,6 +44,21 @@ def _cached_zeros(module, attr: str, shape, device) -> torch.Tensor:
     return entry[0]
 
 
+class _AddGradFn(torch.autograd.Function):
+    """Identity whose backward adds a ready gradient: how d(in-place optimizer loss)/dx, which the reference's
+    ``loss.backward()`` in the middle of its forward leaves in the graph of ``x``, reaches ``x`` here (with the caller's
+    own backward; the graph upstream of the codebook is not walked inside the forward)."""
+
+    @staticmethod
+    def forward(ctx, x, extra):
+        ctx.save_for_backward(extra)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g + ctx.saved_tensors[0], None
+
+
 def _stochastic_sampling_requested(params: CodebookParams) -> bool:
     """Gumbel-max code sampling asked for (the rule of Codebook._stochastic_requested, on the config before it is built)."""
     g = params.gumbel_params
@@ -344,15 +359,27 @@ class VectorQuantize(nn.Module):
         if self.in_place_codebook_optimizer is not None and training and not freeze_codebook:
             # vector_quantize_pytorch.py:234-259: one optimizer step on mse(quantize, x) with respect to the codebook,
             # then the codebook is searched again.  Only the search is needed from the first pass.
-            with torch.no_grad():
-                _, first_idx, _ = cb.quantize_flat(flat.detach())
-            picked = cb.current_codes()[torch.arange(flat.shape[0], device=flat.device)[:, None], first_idx]
+            relaxed = cb._relaxation_active()
+            if relaxed:
+                # the differentiable selection: the codebook also receives the gradient through the softmax of the
+                # similarities.  The reference's first Codebook.forward runs its EMA step BEFORE this loss is differentiated.
+                # There the loss is differentiated with respect to x as well (only x.detach() is the target).
+                leaf = flat.detach().requires_grad_(torch.is_grad_enabled() and flat.requires_grad)
+                picked, first_idx, _ = cb.quantize_flat(leaf, frozen=freeze_codebook)
+                if will_update:
+                    cb.ema_step(flat.detach(), first_idx, flat_mask, sample_pool=sampling_rows)
+            else:
+                with torch.no_grad():
+                    _, first_idx, _ = cb.quantize_flat(flat.detach())
+                picked = cb.current_codes()[torch.arange(flat.shape[0], device=flat.device)[:, None], first_idx]
             err = (picked - flat.detach()) ** 2
             inplace_loss = err[flat_mask].mean() if flat_mask is not None else err.mean()
             inplace_loss.backward()
             self.in_place_codebook_optimizer.step()
             self.in_place_codebook_optimizer.zero_grad()
-            if will_update:  # the reference's first Codebook.forward already ran its EMA step
+            if relaxed and leaf.grad is not None:
+                flat = _AddGradFn.apply(flat, leaf.grad)
+            if will_update and not relaxed:  # the reference's first Codebook.forward already ran its EMA step
                 cb.ema_step(flat.detach(), first_idx, flat_mask, sample_pool=sampling_rows)
         # cross-entropy commitment: the search sweep also emits the row's log-sum-exp (no second sweep for the loss)
         ce_from_search = training and want_loss and use_ce

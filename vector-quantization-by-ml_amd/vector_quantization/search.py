@@ -139,6 +139,25 @@ class _NativeBackend:
         return native.ce_backward(x, cb.contiguous(), lse, target_logit, target, coef, metric=metric)
 
 
+    @staticmethod
+    def gumbel_backward(x, cb, g, *, metric, tau, need_x=True, need_codes=True):
+        """Fused backward of the straight-through Gumbel softmax through the similarities: (gx | None, gc_sim | None) from
+        vq_gumbel_stats_f32 + vq_gumbel_backward_x_f32 / vq_gumbel_backward_codes_f32; None when the shape is outside the
+        kernels' range (the caller then works on row chunks)."""
+        H, M, D = x.shape
+        K = cb.shape[1]
+        if D > native.GUMBEL_MAX_DIM or M == 0 or (need_codes and not native.gumbel_codes_supported(H, M, K, D)):
+            return None
+        cb = cb.contiguous()
+        if g.stride(-1) != 1 and g.shape[-1] != 1:
+            g = g.contiguous()
+        packed = native.pack_codebooks(cb, metric)
+        lse2, delta = native.gumbel_stats(x, cb, g, metric=metric, tau=tau, packed=packed)
+        gx = native.gumbel_backward_x(x, cb, g, lse2, delta, metric=metric, tau=tau, packed=packed) if need_x else None
+        gc = native.gumbel_backward_codes(x, cb, g, lse2, delta, metric=metric, tau=tau) if need_codes else None
+        return gx, gc
+
+
 _backend = _NativeBackend
 
 
