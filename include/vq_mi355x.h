@@ -257,6 +257,25 @@ int vq_gumbel_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs,
                                  const float *delta, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * Gumbel-max sampling of the code, utils/general.py:112-129 (ind = argmax(similarities / temperature + gumbel_noise)) with
+ * the noise of utils/general.py:25-30, as an epilogue of the similarity sweep: nothing of [M, K] in memory, one launch.
+ *   idx[h*idx_hs + m*idx_rs] = first index of the maximum over k < K of  key = fl(fl(s * tau) + g)
+ * with s the value vq_similarities_f32 writes (bit for bit), tau = 1 / temperature in fp32 and g the noise below; a NaN key
+ * is the maximum and the lowest code wins among equal maxima (ATen's argmax).  Uses a->x, a->packed, a->idx (idx_rs, idx_hs),
+ * H, M, K, D (<= 512: VQ_E_UNSUPPORTED beyond), metric; Q is ignored.  tau must be finite.
+ * seed: TWO 64-bit words on the DEVICE (no host synchronisation; capturable in a hipGraph).
+ *
+ * The noise of entry (h, m, k) depends on (seed, h, m, k) only, never on the launch geometry: Philox4x32-10 with
+ *   key      k0 = seed[0] bits 31..0, k1 = seed[0] bits 63..32
+ *   counter  c0 = m bits 31..0, c1 = m bits 63..32, (c3 : c2) = ((h << 32) | (k >> 2)) + seed[1]  (mod 2^64, c2 the low word)
+ * yields four 32-bit words; word k & 3 gives u = (word >> 8) * 2^-24 in [0, 1) and g = -log(max(-log(max(u, 1e-5)), 1e-5)).
+ * vq_gumbel_noise_f32 writes exactly that g to noise[(h*M + m)*K + k] and, when bits is not NULL, the word to
+ * bits[(h*M + m)*K + k] -- the hook that makes vq_gumbel_sample_f32 checkable entry by entry; no product path uses it.
+ */
+int vq_gumbel_sample_f32(const vq_args *a, float tau, const int64_t *seed /* 2 words, device */, void *stream);
+int vq_gumbel_noise_f32(const int64_t *seed, int H, int64_t M, int K, float *noise, uint32_t *bits /* may be NULL */, void *stream);
+
+/*
  * Lookup-free quantization (LFQ) over C codebooks of d sign bits each, 1 <= d <= 20 (implicit codebook {-a, +a}^d).
  * v: [N][C][d] fp32, element (m, c, i) at v[m * v_rs + c * d + i] (rows may be strided, each row's C * d values contiguous).
  *

@@ -28,7 +28,9 @@
 //   vq_search_pair.inc   the same search for 256 < D <= 512 with the dims split over a pair of waves (accumulator hand-off)
 //   vq_search_persist.inc  inference search at Dp = 256 with block b's gather hidden inside block b + 1's sweep
 //   vq_search_resident.inc small codebooks: the packed image stays in LDS, no barriers, rows streamed past it by LDS-DMA slabs
-//   vq_similarity.inc    the same sweep with the similarity / online-softmax epilogues, fused cross-entropy backward
+//   vq_sample.inc        counter-based Gumbel noise (Philox4x32-10) for Gumbel-max code sampling, its test-hook kernel
+//   vq_similarity.inc    the same sweep with the similarity / online-softmax / Gumbel-max sampling epilogues, fused
+//                        cross-entropy backward
 //   vq_finalize_ema.inc  scalar fallback search, finalize-from-keys, loss reduction, EMA codebook update
 //   vq_lfq.inc           lookup-free quantization: sign quantizer, factorised entropy loss forward / backward (stage axis)
 //   vq_rlfq.inc          residual LFQ: every stage's quantize step in one pass (residual in registers), its backward
@@ -59,7 +61,7 @@
 //   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward
-//   7 Gumbel straight-through backward sweeps
+//   7 Gumbel straight-through backward sweeps                                    8 Gumbel-max sampling sweeps
 #ifndef VQ_PART
 #define VQ_PART -1
 #endif
@@ -79,6 +81,7 @@ namespace {
 #include "vq_search_pair.inc"
 #include "vq_search_persist.inc"
 #include "vq_search_resident.inc"
+#include "vq_sample.inc"
 #include "vq_similarity.inc"
 #include "vq_gumbel.inc"
 #if VQ_OWN(0)
@@ -370,6 +373,12 @@ int launch_ce_bwd_m(const CeBwdParams &p, int H, int metric, hipStream_t s) {
     });
 }
 
+// Gumbel-max sampling: the kAuxSample epilogue, a build part of its own
+template <int DP>
+int launch_sample_m(const AuxParams &p, int H, int metric, hipStream_t s) {
+    return with_metric(metric, [&](auto m) { return launch_aux_t<DP, 4, decltype(m)::value, kAuxSample>(p, H, s); });
+}
+
 // the Gumbel backward sweeps: `gz` = row splits of kGumC
 template <int DP, int METRIC, int ROLE>
 int launch_gumbel_t(const GumbelParams &p, int H, int gz, hipStream_t s) {
@@ -433,6 +442,7 @@ template <int DP> int part_wide(int wide, const SearchParams &p, int H, int spli
 template <int DP> int part_resident(const SearchParams &p, int H, int cus, int metric, hipStream_t s);
 template <int DP> int part_aux(const AuxParams &p, int H, int metric, int mode, hipStream_t s);
 template <int DP> int part_ce_bwd(const CeBwdParams &p, int H, int metric, hipStream_t s);
+template <int DP> int part_sample(const AuxParams &p, int H, int metric, hipStream_t s);
 template <int DP> int part_gumbel(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <> int part_gumbel<32>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <> int part_gumbel<64>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
@@ -444,7 +454,8 @@ int part_persist(const SearchChoice &c, const SearchParams &p, int H, int cus, i
     template <> int part_search<DP>(int waves, const SearchParams &p, int H, int splits, int metric, hipStream_t s); \
     template <> int part_wide<DP>(int wide, const SearchParams &p, int H, int splits, int metric, hipStream_t s);    \
     template <> int part_aux<DP>(const AuxParams &p, int H, int metric, int mode, hipStream_t s);                    \
-    template <> int part_ce_bwd<DP>(const CeBwdParams &p, int H, int metric, hipStream_t s);
+    template <> int part_ce_bwd<DP>(const CeBwdParams &p, int H, int metric, hipStream_t s);                          \
+    template <> int part_sample<DP>(const AuxParams &p, int H, int metric, hipStream_t s);
 template <> int part_resident<32>(const SearchParams &p, int H, int cus, int metric, hipStream_t s);
 template <> int part_resident<64>(const SearchParams &p, int H, int cus, int metric, hipStream_t s);
 template <> int part_resident<128>(const SearchParams &p, int H, int cus, int metric, hipStream_t s);
@@ -538,6 +549,16 @@ VQ_DEFINE_GUMBEL_PART(64)
 VQ_DEFINE_GUMBEL_PART(128)
 VQ_DEFINE_GUMBEL_PART(256)
 #undef VQ_DEFINE_GUMBEL_PART
+#endif
+#if VQ_OWN(8)
+#define VQ_DEFINE_SAMPLE_PART(DP) \
+    template <> int part_sample<DP>(const AuxParams &p, int H, int metric, hipStream_t s) { return launch_sample_m<DP>(p, H, metric, s); }
+VQ_DEFINE_SAMPLE_PART(32)
+VQ_DEFINE_SAMPLE_PART(64)
+VQ_DEFINE_SAMPLE_PART(128)
+VQ_DEFINE_SAMPLE_PART(256)
+VQ_DEFINE_SAMPLE_PART(512)
+#undef VQ_DEFINE_SAMPLE_PART
 #endif
 }  // namespace vqi
 
@@ -1641,6 +1662,38 @@ int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_l
     hipStream_t s = (hipStream_t)stream;
     return with_padded_dim(DP, [&](auto dp) { return vqi::part_ce_bwd<decltype(dp)::value>(p, a->H, a->metric, s); },
                            [] { return fail(VQ_E_UNSUPPORTED, "vq_ce_backward: unsupported padded dim"); });
+}
+
+// ---- Gumbel-max code sampling (vq_sample.inc, kAuxSample in vq_similarity.inc) -----------------------------------------
+int vq_gumbel_sample_f32(const vq_args *a, float tau, const int64_t *seed, void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    if (!(__builtin_fabsf(tau) < __builtin_inff())) return fail(VQ_E_BADARG, "vq_gumbel_sample: tau is not finite");
+    if (!seed) return fail(VQ_E_BADARG, "vq_gumbel_sample: seed is null");
+    if (a->M == 0) return 0;
+    if (!a->idx) return fail(VQ_E_BADARG, "vq_gumbel_sample: idx is null");
+    const int DP = padded_dim(a->D);
+    if (DP == 0) return fail(VQ_E_UNSUPPORTED, "vq_gumbel_sample: D > 512 is not supported (use vq_similarities_f32 chunks)");
+    AuxParams p;
+    rc = fill_aux_params(p, a);
+    if (rc) return rc;
+    p.tau = tau;
+    p.seed = (const long long *)seed;
+    p.idx = (long long *)a->idx; p.idx_rs = a->idx_rs; p.idx_hs = a->idx_hs;
+    hipStream_t s = (hipStream_t)stream;
+    return with_padded_dim(DP, [&](auto dp) { return vqi::part_sample<decltype(dp)::value>(p, a->H, a->metric, s); },
+                           [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel_sample: unsupported padded dim"); });
+}
+
+int vq_gumbel_noise_f32(const int64_t *seed, int H, int64_t M, int K, float *noise, uint32_t *bits, void *stream) {
+    if (!seed || !noise) return fail(VQ_E_BADARG, "vq_gumbel_noise: null argument (seed / noise)");
+    if (H <= 0 || M < 0 || K <= 0) return fail(VQ_E_BADARG, "vq_gumbel_noise: non-positive size");
+    if (M == 0) return 0;
+    const long long n = (long long)H * M * K;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 65536) blocks = 65536;  // (the kernel strides over the rest)
+    return launch<vq_gumbel_noise_kernel>(dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, "vq_gumbel_noise launch",
+                                          (const long long *)seed, H, (long long)M, K, noise, (unsigned *)bits);
 }
 
 // ---- Gumbel straight-through backward (vq_gumbel.inc) -----------------------------------------------------------------

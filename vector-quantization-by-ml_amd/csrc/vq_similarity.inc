@@ -1,15 +1,18 @@
 // vq_similarity.inc -- consumers of the similarity matrix on the same sweep: emission, online-softmax statistics,
-// fused cross-entropy backward.  Included by vq_kernels.hip (after vq_search.inc: shares its tile geometry and fragment pipeline).
+// Gumbel-max sampling, fused cross-entropy backward.  Included by vq_kernels.hip (after vq_search.inc: shares its tile geometry and fragment pipeline).
 // ------------------------------------------------------------------------------------------------
-// similarity consumers (SURVEY 8f rank 3): the same MFMA sweep with two other epilogues.
+// similarity consumers (SURVEY 8f rank 3): the same MFMA sweep with three other epilogues.
 //   kAuxSims   write sim[h, m, k] = -sqrt(max(0, t)) (Euclid) / x.c (dot) -- the third return value of
 //              Codebook.forward (codebooks.py:386,435), bit-identical to the values the search compares.
 //   kAuxStats  online softmax over logits = scale * sim: per row log-sum-exp and the logit of a given target code
 //              (F.cross_entropy(distances, codes) -- vector_quantize_pytorch.py:287-297 -- without [M, K] in memory).
+//   kAuxSample Gumbel-max sampling (utils/general.py:112-129): key = sim * tau + gumbel noise (counter-based, made in
+//              registers: vq_sample.inc), running first-index argmax per row -- no [M, K] tensor, no noise tensor.
 // Performance is secondary here (training-only losses): plain loop, no in-wave software pipeline.
 // ------------------------------------------------------------------------------------------------
 constexpr int kAuxSims = 0;
 constexpr int kAuxStats = 1;
+constexpr int kAuxSample = 2;
 
 }  // namespace
 namespace vqi {
@@ -28,6 +31,10 @@ struct AuxParams {
     const long long *target;
     long long tgt_rs, tgt_hs;
     float *lse, *tgt_logit;  // [H * M]
+    float tau;  // kAuxSample: 1 / temperature
+    const long long *seed;  // two words on the device
+    long long *idx;
+    long long idx_rs, idx_hs;
 };
 }  // namespace vqi
 namespace {
@@ -143,6 +150,16 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_sweep_aux(
         const long long tv = p.target[(long long)head * p.tgt_hs + row * p.tgt_rs];
         tgt = (tv >= 0 && tv < p.K) ? (int)tv : (tv < 0 ? -1 : -2);  // -2: out of range -> logit stays -inf
     }
+    // kAuxSample state: the best key this lane has seen and its code.  ATen's argmax rule: a NaN key is the maximum, among equal
+    // maxima the first code wins -- a lane sees its codes in ascending order, so only a strictly better key replaces the record.
+    // (A lane half whose first code 4h is past K never updates: its -inf loses every tie against lane half 0's lower code.)
+    float best_key = -INF;
+    int best_code = 4 * h;
+    unsigned long long seed0 = 0, seed1 = 0;
+    if (MODE == kAuxSample) {
+        seed0 = (unsigned long long)p.seed[0];
+        seed1 = (unsigned long long)p.seed[1];
+    }
     // sub-tile and register that hold the target for THIS lane (-1: never)
     const int tgt_u = (tgt >= 0 && ((tgt >> 2) & 1) == h) ? (tgt >> 5) : -1;
     const int tgt_r = (tgt & 3) + 4 * ((tgt >> 3) & 3);
@@ -179,6 +196,23 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_sweep_aux(
                         for (int e = 0; e < 4; ++e)
                             if (code + e < p.K) srow[code + e] = v[e];
                     }
+                }
+            }
+        } else if (MODE == kAuxSample) {
+            const bool tail = u * kTileCodes + kTileCodes > p.K;  // wave-uniform
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int code = cbase + 8 * g;
+                const f32x4 nz = gumbel_noise4(seed0, seed1, head, row, code >> 2);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float tv = acc[4 * g + e];
+                    const float s = EUCLID ? -sqrtf(tv < 0.0f ? 0.0f : tv) : tv;  // the value kAuxSims writes
+                    const float key = __fadd_rn(__fmul_rn(s, p.tau), nz[e]);      // two roundings, like ATen's mul and add
+                    bool better = !(key <= best_key) && best_key == best_key;     // greater, or the first NaN
+                    if (tail) better = better && code + e < p.K;                  // padding codes never compete
+                    best_key = better ? key : best_key;
+                    best_code = better ? code + e : best_code;
                 }
             }
         } else {
@@ -255,6 +289,14 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_sweep_aux(
         else epilogue(acc1, last_u);
     }
 
+    if (MODE == kAuxSample) {
+        const float ok = __shfl_xor(best_key, 32);
+        const int oc = __shfl_xor(best_code, 32);
+        const bool other_better = !(ok <= best_key) && best_key == best_key;
+        const bool mine_better = !(best_key <= ok) && ok == ok;
+        const bool take = other_better || (!mine_better && oc < best_code);  // equal keys, or both NaN: the lower code
+        if (h == 0 && row_ok) p.idx[(long long)head * p.idx_hs + row * p.idx_rs] = take ? oc : best_code;
+    }
     if (MODE == kAuxStats) {
         const float om = __shfl_xor(run_m, 32), os = __shfl_xor(run_s, 32), ot = __shfl_xor(tgt_l, 32);
         const float mm = fmaxf(run_m, om);  // lane half 0 always saw code 0, so mm is finite

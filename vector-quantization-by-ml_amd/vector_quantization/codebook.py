@@ -282,10 +282,15 @@ class Codebook(nn.Module):
 
     def _quantize_stochastic(self, flat, *, ste, want_sq_err, codebook_grad_from_err, idx=None):
         """Gumbel-max sampling of the code (utils/general.py:106-129): ind = argmax(similarities / temperature + g),
-        g = -log(-log(u)).  RNG-dependent, so no parity with the reference's draws is possible; the similarities come
-        from the native kernel in bounded row chunks and the noise from torch's generator on the tensor's device.
+        g = -log(-log(u)).  RNG-dependent, so no parity with the reference's draws is possible.  Rows of up to 512 dims:
+        ONE native sweep (vq_gumbel_sample_f32) that makes the noise in registers from a seed drawn on the device from torch's
+        generator -- nothing of [h, M, K] exists.  Wider rows, backends without the sweep and VQ_NO_FUSED_SAMPLE=1 in the
+        environment (A/B measurements): similarities from the native kernel in bounded row chunks, noise from torch's generator.
         The straight-through / reinmax relaxations are provided for the argmax selection (_quantize_relaxed), not for
         sampled codes."""
+        import os
+
+        from . import gumbel as gumbel_mod
         from . import losses
 
         g = self.gumbel_params
@@ -295,15 +300,24 @@ class Codebook(nn.Module):
         codes = self.current_codes()
         h, m, _ = flat.shape
         x = flat.float()
-        step = losses._rows_per_chunk(h, self.codebook_size)
-        ind = torch.empty((h, m), dtype=torch.int64, device=flat.device)
-        eps = 1e-5  # the reference's log(t) clamps at 1e-5 (utils/general.py:25-26)
-        with torch.no_grad():
-            for r0 in range(0, m, step):
-                sims = losses.similarity_matrix(x[:, r0:r0 + step].detach(), codes.detach(), self.metric)
-                noise = torch.zeros_like(sims).uniform_(0, 1)
-                gumbel = -(-noise.clamp(min=eps).log()).clamp(min=eps).log()
-                ind[:, r0:r0 + step] = (sims / g.get("temperature", 1.0) + gumbel).argmax(dim=-1)
+        temperature = g.get("temperature", 1.0)
+        seed = gumbel_mod.draw_seed(flat.device)  # once per call, whichever path runs
+        ind = None
+        fused = getattr(search.get_backend(), "sample_codes", None)
+        if fused is not None and not os.environ.get("VQ_NO_FUSED_SAMPLE"):  # (read per call: tests compare both paths)
+            packed = self.packed_codes()
+            ind = fused(x.detach(), codes.detach(), metric=self.metric, tau=1.0 / temperature, seed=seed,
+                        **({"packed": packed} if packed is not None else {}))
+        if ind is None:  # rows wider than 512 dims, a backend without the sweep, or the switch
+            step = losses._rows_per_chunk(h, self.codebook_size)
+            ind = torch.empty((h, m), dtype=torch.int64, device=flat.device)
+            eps = 1e-5  # the reference's log(t) clamps at 1e-5 (utils/general.py:25-26)
+            with torch.no_grad():
+                for r0 in range(0, m, step):
+                    sims = losses.similarity_matrix(x[:, r0:r0 + step].detach(), codes.detach(), self.metric)
+                    noise = torch.zeros_like(sims).uniform_(0, 1)
+                    gumbel = -(-noise.clamp(min=eps).log()).clamp(min=eps).log()
+                    ind[:, r0:r0 + step] = (sims / temperature + gumbel).argmax(dim=-1)
         if idx is not None:
             idx.copy_(ind[..., None])
         picked = codes[torch.arange(h, device=flat.device)[:, None], ind]  # [h, m, d]; differentiable w.r.t. a learnable codebook

@@ -29,6 +29,12 @@ import torch
 from . import losses, search
 
 
+def draw_seed(device) -> torch.Tensor:
+    """The seed of one Gumbel-max sampling call (native.sample_codes): two int64 words drawn on ``device`` from its default
+    generator, so ``torch.manual_seed`` governs the sampled codes; they stay on the device (no host synchronisation)."""
+    return torch.randint(-(2 ** 63), 2 ** 63 - 1, (2,), dtype=torch.int64, device=device)
+
+
 def _harange(t):
     return torch.arange(t.shape[0], device=t.device)[:, None]
 

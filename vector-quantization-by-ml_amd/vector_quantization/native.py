@@ -147,6 +147,10 @@ def load():
         lib.vq_gumbel_backward_x_f32.restype = ctypes.c_int
         lib.vq_gumbel_backward_codes_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _vp]
         lib.vq_gumbel_backward_codes_f32.restype = ctypes.c_int
+        lib.vq_gumbel_sample_f32.argtypes = [ap, ctypes.c_float, _vp, _vp]
+        lib.vq_gumbel_sample_f32.restype = ctypes.c_int
+        lib.vq_gumbel_noise_f32.argtypes = [_vp, ctypes.c_int, _i64, ctypes.c_int, _vp, _vp, _vp]
+        lib.vq_gumbel_noise_f32.restype = ctypes.c_int
         lib.vq_quantize_backward_f32.argtypes = [ap, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]
         lib.vq_quantize_backward_f32.restype = ctypes.c_int
         lib.vq_ema_accumulate_residual_f32.argtypes = [ap, _vp, _vp, _vp]
@@ -216,7 +220,7 @@ EXPORTED_SYMBOLS = (
     "vq_fsq_quantize_f32", "vq_fsq_backward_f32", "vq_fsq_decode_f32",
     "vq_lq_workspace_bytes", "vq_lq_quantize_f32", "vq_lq_backward_f32",
     "vq_gumbel_row_stride", "vq_gumbel_workspace_bytes", "vq_gumbel_stats_f32", "vq_gumbel_backward_x_f32",
-    "vq_gumbel_backward_codes_f32",
+    "vq_gumbel_backward_codes_f32", "vq_gumbel_sample_f32", "vq_gumbel_noise_f32",
 )
 
 
@@ -713,6 +717,47 @@ def gumbel_backward_codes(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, ls
                                                    delta.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws.numel() * 8,
                                                    _stream_ptr(x.device)), "vq_gumbel_backward_codes_f32")
     return gc
+
+
+E_UNSUPPORTED = -2  # VQ_E_UNSUPPORTED
+SAMPLE_MAX_DIM = 512  # vq_gumbel_sample_f32: rows of one launch
+
+
+def _check_seed(seed: torch.Tensor, device) -> None:
+    _require_gpu(seed)
+    assert seed.dtype == torch.int64 and seed.numel() == 2 and seed.is_contiguous() and seed.device == device, \
+        "seed: two int64 words on the tensors' device (gumbel.draw_seed)"
+
+
+def sample_codes(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, tau: float = 1.0, seed: torch.Tensor,
+                 packed: torch.Tensor | None = None):
+    """Gumbel-max sampling in one sweep (vq_gumbel_sample_f32): x [H, M, D] (strided rows ok), cb [H, K, D], tau =
+    1 / temperature, seed = two int64 words on the device -> idx [H, M] int64 = first argmax_k of sim * tau + noise, the noise
+    a function of (seed, head, row, code) only (gumbel_noise returns it).  Nothing of [M, K] is written.  None where the
+    library answers VQ_E_UNSUPPORTED (D > 512)."""
+    a, packed = _aux_args(x, cb, metric, packed, 0)
+    _check_seed(seed, x.device)
+    H, M = a.H, a.M
+    out = torch.empty((H, M), dtype=torch.int64, device=x.device)
+    a.idx, a.idx_rs, a.idx_hs, a.idx_qs = out.data_ptr(), 1, M, 0
+    with torch.cuda.device(x.device):
+        rc = load().vq_gumbel_sample_f32(ctypes.byref(a), float(tau), seed.data_ptr(), _stream_ptr(x.device))
+    if rc == E_UNSUPPORTED:
+        return None
+    _check(rc, "vq_gumbel_sample_f32")
+    return out
+
+
+def gumbel_noise(seed: torch.Tensor, H: int, M: int, K: int, want_bits: bool = False):
+    """The noise sample_codes adds, written out (vq_gumbel_noise_f32; tests): -> noise [H, M, K] fp32, and with ``want_bits``
+    (noise, bits [H, M, K] int32 holding the raw 32-bit Philox word of every entry)."""
+    _check_seed(seed, seed.device)
+    noise = torch.empty((H, M, K), dtype=torch.float32, device=seed.device)
+    bits = torch.empty((H, M, K), dtype=torch.int32, device=seed.device) if want_bits else None
+    with torch.cuda.device(seed.device):
+        _check(load().vq_gumbel_noise_f32(seed.data_ptr(), H, M, K, noise.data_ptr(), bits.data_ptr() if want_bits else None,
+                                          _stream_ptr(seed.device)), "vq_gumbel_noise_f32")
+    return (noise, bits) if want_bits else noise
 
 
 def quantize_backward(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor, grad_out: torch.Tensor | None,

@@ -7,6 +7,7 @@ instead of breaking the graph at an opaque Python call:
     torch.ops.vq_mi355x.pack(cb, metric) -> packed images
     torch.ops.vq_mi355x.quantize_into(x, cb, packed, out, idx, metric, ste, want_sq_err, share, per_head) -> sq_err
         (writes the quantized rows and the indices into the caller's -- possibly strided -- ``out`` / ``idx`` views)
+    torch.ops.vq_mi355x.gumbel_sample(x, cb, packed, seed, metric, tau) -> idx [H, M]   (Gumbel-max sampling, native.sample_codes)
     torch.ops.vq_mi355x.lfq_quantize / lfq_entropy_fwd / lfq_entropy_bwd   (lookup-free quantization, native.lfq_*)
     torch.ops.vq_mi355x.rlfq_quantize / rlfq_backward / lfq_entropy_staged_fwd / lfq_entropy_staged_bwd
         (residual LFQ, native.rlfq_* and native.lfq_entropy_staged_*)
@@ -57,6 +58,21 @@ def quantize_into(x: torch.Tensor, cb: torch.Tensor, packed: Optional[torch.Tens
 def _(x, cb, packed, out, idx, metric, ste, want_sq_err, share, per_head):
     q = idx.shape[-1]
     return x.new_empty((x.shape[0], q) if per_head else (q,), dtype=torch.float64)
+
+
+@torch.library.custom_op(f"{_LIB_NS}::gumbel_sample", mutates_args=())
+def gumbel_sample(x: torch.Tensor, cb: torch.Tensor, packed: Optional[torch.Tensor], seed: torch.Tensor, metric: int,
+                  tau: float) -> torch.Tensor:
+    """x [H, M, D] (D <= 512), cb [H, K, D], seed [2] int64 -> idx [H, M] int64: argmax_k of similarity * tau + Gumbel noise."""
+    idx = native.sample_codes(x, cb, metric=metric, tau=tau, seed=seed, packed=packed)
+    if idx is None:
+        raise RuntimeError("vq_gumbel_sample_f32: rows wider than 512 dims are not supported")
+    return idx
+
+
+@gumbel_sample.register_fake
+def _(x, cb, packed, seed, metric, tau):
+    return x.new_empty((x.shape[0], x.shape[1]), dtype=torch.int64)
 
 
 # lookup-free quantization (native.lfq_*): the same calls with a dispatcher identity and fake implementations

@@ -140,6 +140,19 @@ class _NativeBackend:
 
 
     @staticmethod
+    def sample_codes(x, cb, *, metric, tau, seed, packed=None):
+        """Gumbel-max sampling of the code in one sweep (vq_gumbel_sample_f32): -> idx [H, M] int64 = argmax_k of
+        similarity * tau + Gumbel noise, the noise counter-based from ``seed`` (two int64 words on the device,
+        gumbel.draw_seed); None when the shape is outside the kernel's range (D > 512: the caller works on row chunks)."""
+        if x.shape[-1] > native.SAMPLE_MAX_DIM:
+            return None
+        if torch.compiler.is_compiling():
+            from . import ops
+
+            return ops.gumbel_sample(x, cb.contiguous(), packed, seed, metric, float(tau))
+        return native.sample_codes(x, cb.contiguous(), metric=metric, tau=tau, seed=seed, packed=packed)
+
+    @staticmethod
     def gumbel_backward(x, cb, g, *, metric, tau, need_x=True, need_codes=True):
         """Fused backward of the straight-through Gumbel softmax through the similarities: (gx | None, gc_sim | None) from
         vq_gumbel_stats_f32 + vq_gumbel_backward_x_f32 / vq_gumbel_backward_codes_f32; None when the shape is outside the
