@@ -205,6 +205,37 @@ int vq_ema_update_f32(float *cluster_size, float *embed_avg, float *embeddings, 
                       float *total_scratch, int H, int K, int D, double decay, float eps, int l2norm, void *stream);
 
 /*
+ * Affine re-parameterisation of a codebook (codebooks.py:275-348, 379-384, 400-403).
+ *
+ * vq_affine_stats_f32: per-column statistics of the rows (h, m, :) at x[h*x_hs + m*x_rs + d] in ONE read of x:
+ *   count[h] = rows kept by the mask (all M without one), mean[h][d] their mean, m2[h][d] = sum (x - mean)^2 (the biased
+ *   variance is m2 / count; both 0 when count is 0).  mask: NULL or uint8 (h, m) at mask[h*mask_hs + m*mask_rs], non-zero =
+ *   keep.  The same entry point serves the codebook's own statistics (x = the codes, M = K).
+ *   No atomics and a fixed summation order (bit-identical from run to run); the raw sum of squares is never formed.
+ *   Geometry: VEC = 4 columns per thread (float4 loads) when x, x_rs, x_hs are 16-byte aligned and D % 4 == 0, else VEC = 1;
+ *   TC = min(64, next power of two >= ceil(D / VEC)) threads across the columns, TR = 256 / TC row lanes, CG = ceil(D / (TC VEC))
+ *   column groups, nblk = clamp(ceil(M / (16 TR)), 1, max(1, 1024 / (H CG))) row blocks.  Row lane r of block b folds the rows
+ *   b TR + r + i nblk TR, i = 0, 1, ..., in that order (Welford in fp32 on x minus the lane's first kept row); the TR lanes are
+ *   merged pairwise (lane r takes lane r + s, s = TR / 2 .. 1); then 64 lanes per column fold the nblk partials (lane j:
+ *   b = j, j + 64, ... in that order) and are merged pairwise (lane j takes lane j + s, s = 32 .. 1).  Every merge is Chan's
+ *   formula in fp64.
+ *   workspace: >= vq_affine_stats_workspace_bytes(H, M, D) bytes, 16-byte aligned.  VQ_E_UNSUPPORTED: M / nblk >= 2^24.
+ *
+ * vq_affine_apply_f32: elementwise over in / out [H][K][D] contiguous (in == out allowed), the four statistics [H][D],
+ *   std = sqrt(clamp(variance, min = 1e-5)) computed in the kernel:
+ *   mode 0 (codes -> batch space)             out = (in - codebook_mean) * (batch_std / codebook_std) + batch_mean
+ *   mode 1 (accumulated sums -> codebook space) out = in * r + hits[h][k] * (codebook_mean - batch_mean * r), r = codebook_std / batch_std
+ *          = the per-code sums of (x - batch_mean) * r + codebook_mean from the sums of the raw rows (vq_ema_accumulate_f32).
+ */
+int64_t vq_affine_stats_workspace_bytes(int H, int64_t M, int D);
+int vq_affine_stats_f32(const float *x, int64_t x_rs, int64_t x_hs, const uint8_t *mask, int64_t mask_rs, int64_t mask_hs, int H,
+                        int64_t M, int D, int64_t *count, float *mean, float *m2, void *workspace, int64_t workspace_bytes,
+                        void *stream);
+int vq_affine_apply_f32(const float *in, float *out, const float *hits /* mode 1 */, const float *codebook_mean,
+                        const float *codebook_variance, const float *batch_mean, const float *batch_variance, int H, int K, int D,
+                        int mode, void *stream);
+
+/*
  * Consumers of the similarity matrix.  Both use a->x, a->packed (a->cb for D > 512 / VQ_F_FORCE_SIMPLE),
  * H, M, K, D, metric; Q is ignored.
  * vq_similarities_f32: sims[h*sims_hs + m*sims_rs + k] = -cdist(x, c) (Euclid) or x.c (dot): the third return value of

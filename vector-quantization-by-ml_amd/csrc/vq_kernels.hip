@@ -38,6 +38,8 @@
 //                        backward, index -> code decode
 //   vq_lq.inc            latent quantization: per-dimension level search against learnable value tables (in LDS), index,
 //                        fused squared-error loss and its backward
+//   vq_affine.inc        affine re-parameterisation: one-read column mean / squared deviations (Welford lanes, Chan merges),
+//                        the moment-matching transform of the codes and of the accumulated EMA sums
 //   this file            host-side dispatch and the C ABI (include/vq_mi355x.h)
 //
 // Reference lines replaced (relative to the reference root): vector_quantization/codebooks.py:386-397,
@@ -58,7 +60,7 @@
 // the same file once per part (-DVQ_PART=n, in parallel) and links the objects: every part sees the same templates, but only
 // its own launchers are defined -- and with them instantiated -- there; the other parts call them through the
 // vqi::part_* entry points declared below.
-//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ) 4 search Dp = 512 + wave-pair kernel
+//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ, affine) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward
 //   7 Gumbel straight-through backward sweeps                                    8 Gumbel-max sampling sweeps
@@ -90,6 +92,7 @@ namespace {
 #include "vq_rlfq.inc"
 #include "vq_fsq.inc"
 #include "vq_lq.inc"
+#include "vq_affine.inc"
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1573,6 +1576,56 @@ int vq_ema_update_f32(float *cluster_size, float *embed_avg, float *embeddings, 
     const long long rows = (long long)H * K;
     return launch<vq_ema_codes_kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, "vq_ema_update launch", cluster_size, total_scratch, embed_avg,
                                        sums, embeddings, H, K, D, weight, eps, l2norm);
+}
+
+int64_t vq_affine_stats_workspace_bytes(int H, int64_t M, int D) {
+    if (H <= 0 || M < 0 || D <= 0) return 0;
+    // (the geometry depends on the alignment of the call: the larger of the two)
+    const AffineGeo a = affine_geo(H, M, D, true), b = affine_geo(H, M, D, false);
+    const int nblk = a.nblk > b.nblk ? a.nblk : b.nblk;
+    return affine_ws_counts(H, nblk) * 4 + 2ll * H * nblk * D * 8 + 256;
+}
+
+int vq_affine_stats_f32(const float *x, int64_t x_rs, int64_t x_hs, const uint8_t *mask, int64_t mask_rs, int64_t mask_hs, int H,
+                        int64_t M, int D, int64_t *count, float *mean, float *m2, void *workspace, int64_t workspace_bytes,
+                        void *stream) {
+    if (H <= 0 || M < 0 || D <= 0 || H > 65535) return fail(VQ_E_BADARG, "vq_affine_stats: bad size");
+    if (!count || !mean || !m2) return fail(VQ_E_BADARG, "vq_affine_stats: count / mean / m2 is null");
+    if (!x && M > 0) return fail(VQ_E_BADARG, "vq_affine_stats: x is null");
+    if (M > 1 && x_rs < D) return fail(VQ_E_BADARG, "vq_affine_stats: row stride smaller than D");
+    if (!workspace || workspace_bytes < vq_affine_stats_workspace_bytes(H, M, D) || ((uintptr_t)workspace & 15))
+        return fail(VQ_E_BADARG, "vq_affine_stats: workspace too small or misaligned (see vq_affine_stats_workspace_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = D % 4 == 0 && vec4_ok(x, {x_rs, x_hs});
+    const AffineGeo g = affine_geo(H, M, D, vec);
+    if (M / g.nblk >= (1ll << 24)) return fail(VQ_E_UNSUPPORTED, "vq_affine_stats: more than 2^24 rows per partial");
+    unsigned *part_n = (unsigned *)workspace;
+    double *part_mean = (double *)((unsigned *)workspace + affine_ws_counts(H, g.nblk));  // (a multiple of 256 bytes in)
+    double *part_m2 = part_mean + (long long)H * g.nblk * D;
+    const int nblk = M > 0 ? g.nblk : 0;
+    if (nblk > 0) {
+        const dim3 grid((unsigned)g.nblk, (unsigned)g.cg, (unsigned)H);
+        const int rc = vec ? launch<vq_affine_stats_kernel<4>>(grid, dim3(256), 0, s, "vq_affine_stats launch", x, (long long)x_rs, (long long)x_hs, mask,
+                                                               (long long)mask_rs, (long long)mask_hs, (long long)M, D, g.tc, g.nblk, part_n, part_mean, part_m2)
+                           : launch<vq_affine_stats_kernel<1>>(grid, dim3(256), 0, s, "vq_affine_stats launch", x, (long long)x_rs, (long long)x_hs, mask,
+                                                               (long long)mask_rs, (long long)mask_hs, (long long)M, D, g.tc, g.nblk, part_n, part_mean, part_m2);
+        if (rc) return rc;
+    }
+    return launch<vq_affine_merge_kernel>(dim3((unsigned)((D + 3) / 4), (unsigned)H), dim3(256), 0, s, "vq_affine_merge launch", (const unsigned *)part_n,
+                                          (const double *)part_mean, (const double *)part_m2, H, D, nblk, (long long *)count, mean, m2);
+}
+
+int vq_affine_apply_f32(const float *in, float *out, const float *hits, const float *codebook_mean, const float *codebook_variance,
+                        const float *batch_mean, const float *batch_variance, int H, int K, int D, int mode, void *stream) {
+    if (H <= 0 || K <= 0 || D <= 0) return fail(VQ_E_BADARG, "vq_affine_apply: non-positive size");
+    if (mode != 0 && mode != 1) return fail(VQ_E_BADARG, "vq_affine_apply: mode must be 0 (codes) or 1 (accumulated sums)");
+    if (!in || !out || !codebook_mean || !codebook_variance || !batch_mean || !batch_variance)
+        return fail(VQ_E_BADARG, "vq_affine_apply: null argument");
+    if (mode == 1 && !hits) return fail(VQ_E_BADARG, "vq_affine_apply: mode 1 needs hits");
+    const long long total = (long long)H * K * D;
+    if ((total + 255) / 256 >= (1ll << 31)) return fail(VQ_E_UNSUPPORTED, "vq_affine_apply: too many elements for one launch");
+    return launch<vq_affine_apply_kernel>(dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, "vq_affine_apply launch", in, out,
+                                          hits, codebook_mean, codebook_variance, batch_mean, batch_variance, K, D, total, mode);
 }
 
 static int fill_aux_params(AuxParams &p, const vq_args *a) {

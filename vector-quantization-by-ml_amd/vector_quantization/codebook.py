@@ -92,6 +92,31 @@ def _pick_rows_all_ranks(rows: torch.Tensor, count: int) -> torch.Tensor:
     return torch.cat(parts, dim=0)
 
 
+def _affine_std(variance: torch.Tensor) -> torch.Tensor:
+    return variance.clamp(min=1e-5).sqrt()
+
+
+class _AffineCodes(torch.autograd.Function):
+    """codes [h, K, D] -> (codes - codebook_mean) * (batch_std / codebook_std) + batch_mean, natively (vq_affine_apply_f32,
+    mode 0) when ``fused`` is the backend's hook, else with the reference's own op sequence.  Backward: g * scale; the scale
+    is made (and kept: the statistics move in place with the next forward) only when the codes ask for a gradient."""
+
+    @staticmethod
+    def forward(ctx, codes, fused, codebook_mean, codebook_variance, batch_mean, batch_variance):
+        scale = None
+        if ctx.needs_input_grad[0] or fused is None:
+            scale = _affine_std(batch_variance) / _affine_std(codebook_variance)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(scale)
+        if fused is not None:
+            return fused(codes.detach().contiguous(), codebook_mean, codebook_variance, batch_mean, batch_variance, mode=0)
+        return (codes - codebook_mean) * scale + batch_mean
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * ctx.saved_tensors[0], None, None, None, None, None
+
+
 class Codebook(nn.Module):
     def __init__(
         self,
@@ -118,8 +143,9 @@ class Codebook(nn.Module):
         super().__init__()
         self.transform_input = _row_transform(transform_input, "transform input function")
         self.weights_regularization = _row_transform(weights_regularization, "weights regularization")
-        if use_affine:
-            raise NotImplementedError("affine re-parameterisation is outside the MI355X hot-path build (SURVEY 2, #6)")
+        if use_affine and affine_params is None:
+            # (the reference accepts this and fails with AttributeError on its first forward, codebooks.py:288)
+            raise ValueError("use_affine=True needs affine_params (AffineParameters, or the dict dataclasses.asdict makes of it)")
 
         self.dim = dim
         self.codebook_size = codebook_size
@@ -134,7 +160,10 @@ class Codebook(nn.Module):
         self.use_ddp = use_ddp
         self.distributed_replace_codes = distributed_replace_codes
         self.learnable_codebook = learnable_codebook
-        self.use_affine = False
+        self.use_affine = bool(use_affine)
+        self.affine_params = None
+        if use_affine:
+            self.affine_params = asdict(affine_params) if is_dataclass(affine_params) else dict(affine_params)
 
         if kmeans_params is None:
             kmeans_params = KmeansParameters() if initialization_by_kmeans else None
@@ -160,6 +189,23 @@ class Codebook(nn.Module):
             self.embeddings = nn.Parameter(start)
         else:
             self.register_buffer("embeddings", start)
+        if use_affine:
+            if self.gumbel_params.get("straight_through", False):
+                raise NotImplementedError("use_affine together with GumbelParams(straight_through=True) is not supported: "
+                                          "the relaxation's gradient is provided for untransformed codes only")
+            # codebooks.py:192-206: names, shapes and dtypes are the checkpoint format.  The two batch buffers stay None until
+            # the first forward; afterwards every statistic is updated IN PLACE (the reference re-registers new tensors)
+            self.register_buffer("batch_mean", None)
+            self.register_buffer("batch_variance", None)
+            self.register_buffer("codebook_mean_needs_init", torch.Tensor([True]))
+            self.register_buffer("codebook_mean", torch.zeros(num_codebooks, 1, dim))
+            self.register_buffer("codebook_variance_needs_init", torch.Tensor([True]))
+            self.register_buffer("codebook_variance", torch.zeros(num_codebooks, 1, dim))
+        # host-side mirror of the two *_needs_init flags (no device read in steady state; refreshed by load_state_dict)
+        self._codebook_stats_need_init = True
+        # the statistics the current forward uses (update_affine) and the effective codes made from them
+        self._affine_now = None
+        self._effective = None
         # packed image of `embeddings` for the native search, rebuilt only when the codes change (see packed_codes)
         self._packed = None
         self._packed_key = None
@@ -199,6 +245,7 @@ class Codebook(nn.Module):
     def invalidate_packed(self):
         """Call after changing ``embeddings`` through ``.data`` or a raw pointer (every writer in this package does)."""
         self._packed_epoch += 1
+        self._effective = None
 
     def packed_codes(self):
         """Packed image [h, packed_floats] of the codes for the native search (None for backends without one), cached:
@@ -206,6 +253,13 @@ class Codebook(nn.Module):
         backend = search.get_backend()
         if not getattr(backend, "uses_packed", False):
             return None
+        if self.use_affine:
+            # the effective codes change with every forward's statistics: an image is packed per call, never cached
+            codes = self.effective_codes().detach()
+            if not codes.is_cuda and not torch.compiler.is_compiling():
+                return None
+            with torch.no_grad():
+                return backend.pack(codes.contiguous(), self.metric)
         if torch.compiler.is_compiling():  # traced: the pack is a node of the graph (no identity-keyed cache inside a trace)
             return backend.pack(self.embeddings.detach().contiguous(), self.metric)
         if not self.embeddings.is_cuda:
@@ -216,6 +270,125 @@ class Codebook(nn.Module):
                 self._packed = backend.pack(self.embeddings.detach().contiguous(), self.metric)
             self._packed_key = key
         return self._packed
+
+    # ------------------------------------------------------------------ affine re-parameterisation
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        if self.use_affine:
+            for name in ("batch_mean", "batch_variance"):  # absent (None) until the first forward: make room for saved ones
+                saved = state_dict.get(prefix + name)
+                if saved is not None and getattr(self, name) is None:
+                    setattr(self, name, torch.empty_like(saved, device=self.embeddings.device))
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if self.use_affine:
+            self._codebook_stats_need_init = bool(self.codebook_mean_needs_init.item() != 0
+                                                  or self.codebook_variance_needs_init.item() != 0)
+            self._affine_now = None
+            self._effective = None
+
+    @staticmethod
+    def _fused_affine(name: str):
+        """The backend's native affine hook (``column_stats`` / ``affine_apply``), or None: backends without it, traced
+        forwards (torch.compile runs the step as tensor ops) and VQ_NO_FUSED_AFFINE=1 in the environment (A/B measurements;
+        read per call: tests compare both paths in one process) take the tensor-op path."""
+        import os
+
+        if torch.compiler.is_compiling() or os.environ.get("VQ_NO_FUSED_AFFINE"):
+            return None
+        return getattr(search.get_backend(), name, None)
+
+    def _moments(self, rows: torch.Tensor, flat_mask=None):
+        """rows [h, M, D] -> (count [h] (int64 from the kernel), mean [h, 1, D], m2 [h, 1, D]) over the kept rows."""
+        fused = self._fused_affine("column_stats")
+        if fused is not None:
+            count, mean, m2 = fused(rows, flat_mask)
+            return count, mean[:, None], m2[:, None]
+        if flat_mask is not None:
+            rows = rows[flat_mask].reshape(rows.shape[0], -1, rows.shape[-1])  # (the same rows are kept in every head)
+        mean = rows.mean(dim=1, keepdim=True)
+        m2 = torch.var(rows, dim=1, unbiased=False, keepdim=True) * rows.shape[1]
+        return torch.full((rows.shape[0],), float(rows.shape[1]), device=rows.device), mean, m2
+
+    def _mean_and_variance(self, rows: torch.Tensor, flat_mask=None, sync: bool = False):
+        """Per-column mean and biased variance [h, 1, D] of the kept rows (codebooks.py:287-292, 309-314); with ``sync`` over
+        the rows of every rank (codebooks.py:319-348) from each rank's (n, mean, M2) alone.  A head whose mask keeps no row
+        gets NaN statistics (0 / 0), as the reference's mean over no rows does."""
+        if not sync and self._fused_affine("column_stats") is None:  # the reference's own two reductions
+            if flat_mask is not None:
+                rows = rows[flat_mask].reshape(rows.shape[0], -1, rows.shape[-1])
+            return rows.mean(dim=1, keepdim=True), torch.var(rows, dim=1, unbiased=False, keepdim=True)
+        count, mean, m2 = self._moments(rows, flat_mask)
+        n = count[:, None, None]
+        if not sync:
+            return mean, m2 / n
+        n = n.to(mean.dtype)
+        total = n.clone()
+        dist.all_reduce(total)
+        column_sum = mean * n
+        dist.all_reduce(column_sum)
+        global_mean = column_sum / total
+        # sum of squared deviations about the GLOBAL mean from the local ones: no second pass over the rows
+        about_global = m2 + n * (mean - global_mean) ** 2
+        dist.all_reduce(about_global)
+        return global_mean, about_global / total
+
+    @staticmethod
+    def _decay_into(buffers, fresh, decay: float):
+        """buffers <- buffers * decay + fresh * (1 - decay), in place, two launches for the pair (codebooks.py:271)."""
+        torch._foreach_mul_(buffers, decay)
+        torch._foreach_add_(buffers, fresh, alpha=1 - decay)
+
+    @torch.no_grad()
+    def update_affine(self, flat: torch.Tensor, flat_mask=None):
+        """codebooks.py:275-348, at the top of every search (train AND eval): running column statistics of the codes (moved
+        only while training) and of the batch (always), updated in place.  flat [h, M, D] (strided views are not copied)."""
+        assert self.use_affine
+        p = self.affine_params
+        flat = flat.detach()
+        if flat.dtype != torch.float32:
+            flat = flat.float()
+        self._effective = None
+        codebook_mean, codebook_variance = self.codebook_mean, self.codebook_variance
+        if self.training or self._codebook_stats_need_init:
+            mean, var = self._mean_and_variance(self.embeddings.detach())
+            if not self.training:
+                # eval before any training forward: the reference searches against torch.empty garbage; here the statistics
+                # of the current codes serve this forward and are not stored
+                codebook_mean, codebook_variance = mean, var
+            elif self._codebook_stats_need_init:
+                self.codebook_mean.copy_(mean)
+                self.codebook_variance.copy_(var)
+                self.codebook_mean_needs_init.zero_()
+                self.codebook_variance_needs_init.zero_()
+                self._codebook_stats_need_init = False
+            else:
+                self._decay_into([self.codebook_mean, self.codebook_variance], [mean, var], p["codebook_decay"])
+        sync = bool(p["sync"]) and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        mean, var = self._mean_and_variance(flat, flat_mask, sync=sync)
+        if self.batch_mean is None:
+            self.batch_mean, self.batch_variance = mean.clone(), var.clone()
+        else:
+            self._decay_into([self.batch_mean, self.batch_variance], [mean, var], p["batch_decay"])
+        self._affine_now = (codebook_mean, codebook_variance, self.batch_mean, self.batch_variance)
+
+    def effective_codes(self) -> torch.Tensor:
+        """The codes the forward consumes: ``current_codes()``, under affine moved to the batch's moments (codebooks.py:379-384):
+        (embeddings - codebook_mean) * (batch_std / codebook_std) + batch_mean.  Differentiable with respect to a learnable
+        codebook (the statistics are constants).  Without a gradient they are made once per forward (update_affine drops the
+        previous ones); a tensor that carries an autograd graph is never kept on the module (it would keep the graph alive
+        between steps and make the module impossible to deep-copy): a learnable codebook makes them per consumer."""
+        codes = self.current_codes()
+        if not self.use_affine:
+            return codes
+        if self._affine_now is None:
+            raise RuntimeError("an affine codebook has no statistics yet: update_affine() runs at the top of every forward")
+        if codes.requires_grad and torch.is_grad_enabled():
+            return _AffineCodes.apply(codes, self._fused_affine("affine_apply"), *self._affine_now)
+        key = self.codes_state()
+        if self._effective is None or self._effective[0] != key:
+            with torch.no_grad():
+                made = _AffineCodes.apply(codes.detach(), self._fused_affine("affine_apply"), *self._affine_now)
+            self._effective = (key, made)
+        return self._effective[1]
 
     # ------------------------------------------------------------------ the hot path
     def quantize_flat(self, flat: torch.Tensor, *, ste: bool = False, want_sq_err: bool = False,
@@ -229,7 +402,7 @@ class Codebook(nn.Module):
             res = self._quantize_stochastic(flat, ste=ste, want_sq_err=want_sq_err,
                                             codebook_grad_from_err=codebook_grad_from_err, idx=idx)
             return (*res, None) if want_lse else res
-        codes = self.current_codes()
+        codes = self.effective_codes()
         packed = self.packed_codes()
         if (self._relaxation_active() and torch.is_grad_enabled() and (flat.requires_grad or codes.requires_grad)
                 and (not ste or (want_sq_err and codebook_grad_from_err))):
@@ -239,7 +412,7 @@ class Codebook(nn.Module):
                                          codebook_grad_from_err=codebook_grad_from_err, idx=idx, frozen=frozen)
             return (*res, None) if want_lse else res
         if (torch.is_grad_enabled() and flat.requires_grad and not codes.requires_grad and self.training and self.ema_update
-                and not frozen):
+                and not frozen and not self.use_affine):  # (effective codes are a tensor of this forward already)
             # the EMA step that follows rewrites the codebook in place; the backward pass (commitment loss: 2 (x - c))
             # must see the codes this forward used, as the reference's autograd graph does (it holds `quantize` by value)
             codes = codes.clone()
@@ -297,7 +470,7 @@ class Codebook(nn.Module):
         if g.get("straight_through", False) or g.get("reinmax", False):
             raise NotImplementedError("straight-through / reinmax Gumbel relaxations are provided for the argmax selection "
                                       "only; plain stochastic sampling is supported")
-        codes = self.current_codes()
+        codes = self.effective_codes()
         h, m, _ = flat.shape
         x = flat.float()
         temperature = g.get("temperature", 1.0)
@@ -334,7 +507,7 @@ class Codebook(nn.Module):
         whole matrix -- see losses.py."""
         from . import losses
 
-        return losses.similarity_matrix(flat, self.current_codes(), self.metric)
+        return losses.similarity_matrix(flat, self.effective_codes(), self.metric)
 
     def forward(self, x, mask=None, freeze_codebook=False, return_similarities=True):
         """(quantize, embed_ind, similarities) like the reference (codebooks.py:351,435).  A direct caller gets the full
@@ -356,6 +529,9 @@ class Codebook(nn.Module):
             self.seed_with_kmeans(flat, flat_mask)
             self.is_initialized = True
 
+        if self.use_affine:
+            self.update_affine(flat, flat_mask)
+
         out, idx, _ = self.quantize_flat(flat, frozen=freeze_codebook)
         sims = self.similarities(flat).reshape(h, *lead, self.codebook_size) if return_similarities else None
 
@@ -376,6 +552,18 @@ class Codebook(nn.Module):
         ``sample_pool``: the rows re-seeding draws from, in the REFERENCE's row order (a tensor or a callable returning it;
         default ``flat``) -- the draw is an index into them, so the order matters (shared codebook with several heads)."""
         hits, sums = search.get_backend().ema_accumulate(flat, idx, self.codebook_size, flat_mask)
+        if self.use_affine:
+            # codebooks.py:400-403 sums the rows moved to the codebook's moments, (x - batch_mean) * r + codebook_mean with
+            # r = codebook_std / batch_std.  Per code that is r * sum(x) + hits * (codebook_mean - batch_mean * r): the raw
+            # rows are accumulated as always and the [h, K, D] result is corrected -- no transformed copy of [M, D]
+            hits, sums = hits.contiguous(), sums.contiguous()
+            fused = self._fused_affine("affine_apply")
+            codebook_mean, codebook_variance, batch_mean, batch_variance = self._affine_now
+            if fused is not None:
+                sums = fused(sums, codebook_mean, codebook_variance, batch_mean, batch_variance, mode=1, hits=hits, out=sums)
+            else:
+                r = _affine_std(codebook_variance) / _affine_std(batch_variance)
+                sums = sums * r + hits[..., None] * (codebook_mean - batch_mean * r)
         self.ema_apply(hits, sums)
         self.reseed_dead_codes(sample_pool if sample_pool is not None else flat)
 

@@ -131,6 +131,14 @@ def load():
         lib.vq_ema_update_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_double, ctypes.c_float, ctypes.c_int, _vp]
         lib.vq_ema_update_f32.restype = ctypes.c_int
+        lib.vq_affine_stats_workspace_bytes.argtypes = [ctypes.c_int, _i64, ctypes.c_int]
+        lib.vq_affine_stats_workspace_bytes.restype = _i64
+        lib.vq_affine_stats_f32.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, ctypes.c_int, _i64, ctypes.c_int, _vp, _vp, _vp,
+                                            _vp, _i64, _vp]
+        lib.vq_affine_stats_f32.restype = ctypes.c_int
+        lib.vq_affine_apply_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, _vp]
+        lib.vq_affine_apply_f32.restype = ctypes.c_int
         lib.vq_similarities_f32.argtypes = [ap, _vp, _i64, _i64, _vp]
         lib.vq_similarities_f32.restype = ctypes.c_int
         lib.vq_softmax_stats_f32.argtypes = [ap, ctypes.c_float, _vp, _i64, _i64, _vp, _vp, _vp]
@@ -221,6 +229,7 @@ EXPORTED_SYMBOLS = (
     "vq_lq_workspace_bytes", "vq_lq_quantize_f32", "vq_lq_backward_f32",
     "vq_gumbel_row_stride", "vq_gumbel_workspace_bytes", "vq_gumbel_stats_f32", "vq_gumbel_backward_x_f32",
     "vq_gumbel_backward_codes_f32", "vq_gumbel_sample_f32", "vq_gumbel_noise_f32",
+    "vq_affine_stats_workspace_bytes", "vq_affine_stats_f32", "vq_affine_apply_f32",
 )
 
 
@@ -527,6 +536,57 @@ def ema_update(cluster_size: torch.Tensor, embed_avg: torch.Tensor, embeddings: 
         _check(load().vq_ema_update_f32(cluster_size.data_ptr(), embed_avg.data_ptr(), embeddings.data_ptr(),
                                         counts.data_ptr(), sums.data_ptr(), total.data_ptr(), H, K, D, float(decay),
                                         float(eps), 1 if l2norm else 0, _stream_ptr(dev)), "vq_ema_update_f32")
+
+
+def column_stats(x: torch.Tensor, mask: torch.Tensor | None = None):
+    """x [H, M, D] fp32 (strided rows / heads ok, never copied), mask [H, M] bool / uint8 (any strides) or None ->
+    (count [H] int64, mean [H, D], m2 [H, D]): rows kept, their per-column mean and sum of squared deviations about it
+    (vq_affine_stats_f32: one read of x, no atomics, bit-identical from run to run)."""
+    _require_gpu(x, mask)
+    assert x.dtype == torch.float32 and x.dim() == 3
+    H, M, D = x.shape
+    dev = x.device
+    x_rs, x_hs = _row_strides(x)
+    m8, m_rs, m_hs = None, 0, 0
+    if mask is not None:
+        assert tuple(mask.shape) == (H, M)
+        m8 = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+        assert m8.dtype == torch.uint8
+        m_rs, m_hs = int(m8.stride(1)), int(m8.stride(0))
+    count = torch.empty((H,), dtype=torch.int64, device=dev)
+    mean = torch.empty((H, D), dtype=torch.float32, device=dev)
+    m2 = torch.empty((H, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = int(load().vq_affine_stats_workspace_bytes(H, M, D))
+        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+        _check(load().vq_affine_stats_f32(x.data_ptr(), x_rs, x_hs, m8.data_ptr() if m8 is not None else None, m_rs, m_hs,
+                                          H, M, D, count.data_ptr(), mean.data_ptr(), m2.data_ptr(), ws.data_ptr(),
+                                          ws.numel() * 8, _stream_ptr(dev)), "vq_affine_stats_f32")
+    return count, mean, m2
+
+
+def affine_apply(src: torch.Tensor, codebook_mean: torch.Tensor, codebook_variance: torch.Tensor, batch_mean: torch.Tensor,
+                 batch_variance: torch.Tensor, *, mode: int = 0, hits: torch.Tensor | None = None,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """The moment-matching transform over src [H, K, D] with the statistics [H, 1, D] (or [H, D]), vq_affine_apply_f32:
+    mode 0 codes -> batch space, mode 1 accumulated sums (with ``hits`` [H, K]) -> codebook space.  ``out`` may be ``src``."""
+    stats = (codebook_mean, codebook_variance, batch_mean, batch_variance)
+    _require_gpu(src, hits, out, *stats)
+    assert src.dtype == torch.float32 and src.dim() == 3 and src.is_contiguous()
+    H, K, D = src.shape
+    for t in stats:
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == H * D
+    if mode == 1:
+        assert hits is not None and hits.dtype == torch.float32 and hits.is_contiguous() and tuple(hits.shape) == (H, K)
+    if out is None:
+        out = torch.empty_like(src)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == src.shape
+    dev = src.device
+    with torch.cuda.device(dev):
+        _check(load().vq_affine_apply_f32(src.data_ptr(), out.data_ptr(), hits.data_ptr() if hits is not None else None,
+                                          *(t.data_ptr() for t in stats), H, K, D, int(mode), _stream_ptr(dev)),
+               "vq_affine_apply_f32")
+    return out
 
 
 def _aux_args(x: torch.Tensor, cb: torch.Tensor, metric: int, packed, flags: int):

@@ -12,7 +12,13 @@ from typing import Optional
 
 @dataclass
 class AffineParameters:
-    """Running-statistics affine re-parameterisation (training-time; not on the search path)."""
+    """Affine re-parameterisation of a codebook (``use_affine=True``): the codes are searched after being moved to the
+    running per-column mean / variance of the batch, ``(codes - codebook_mean) * (batch_std / codebook_std) + batch_mean``,
+    and the EMA step sees the rows moved the other way.  ``batch_decay`` / ``codebook_decay`` are the weights of the OLD
+    running value (the first forward assigns); the codebook's statistics move only in train mode, the batch's in eval mode
+    too.  ``sync``: in a distributed world the batch statistics are those of every rank's rows.  Native column statistics
+    and transform kernels.  Not available with a sharded codebook, ``in_place_codebook_optimizer``
+    or ``GumbelParams(straight_through=True)`` (NotImplementedError at construction)."""
 
     sync: bool
     batch_decay: float = 0.99

@@ -154,7 +154,8 @@ class VectorQuantize(nn.Module):
                                in_place_codebook_optimizer=in_place_codebook_optimizer is not None,
                                learnable_codebook=codebook_params.learnable_codebook,
                                initialization_by_kmeans=codebook_params.initialization_by_kmeans,
-                               stochastic_sampling=_stochastic_sampling_requested(codebook_params))
+                               stochastic_sampling=_stochastic_sampling_requested(codebook_params),
+                               use_affine=codebook_params.use_affine)
             bad = [k for k, v in unsupported.items() if v]
             if bad:
                 raise NotImplementedError(f"a sharded codebook supports the search / quantize step / EMA update only, not {bad}")
@@ -165,6 +166,9 @@ class VectorQuantize(nn.Module):
         self.shard_gather = codebook_shard_gather
         self._shard_table = None
 
+        if codebook_params.use_affine and in_place_codebook_optimizer is not None:
+            # (the reference searches twice there, vector_quantize_pytorch.py:234-259: its statistics would move twice a step)
+            raise NotImplementedError("use_affine together with in_place_codebook_optimizer is not supported")
         if sync_codebook is None:
             sync_codebook = _world_is_distributed()
         self.codebook_params = replace(
@@ -304,7 +308,7 @@ class VectorQuantize(nn.Module):
         x4 = x.reshape(batch, n, heads, head_dim)
         x4 = cb.transform_input(x4)
         wide_input = x4.dtype == torch.float64  # the reference's straight-through sum x + (q - x) promotes to the input's width
-        plain_inference = not self.training and indices is None and mask is None and cb.is_initialized
+        plain_inference = not self.training and indices is None and mask is None and cb.is_initialized and not cb.use_affine
         if x4.dtype != torch.float32 and not (plain_inference and x4.dtype in (torch.float16, torch.bfloat16)):
             x4 = x4.float()  # (2-byte rows of a plain inference forward are widened inside the search kernel instead)
         if not x4.is_contiguous():
@@ -347,6 +351,10 @@ class VectorQuantize(nn.Module):
                 seed_mask = mask.reshape(batch, 1, n).expand(batch, heads, n).reshape(1, rows * heads)
             cb.seed_with_kmeans(sampling_rows(), seed_mask)
             cb.is_initialized = True
+
+        if cb.use_affine:
+            # codebooks.py:372-373: after the seeding, before anything reads the codes -- in eval mode too
+            cb.update_affine(flat, flat_mask)
 
         if training or return_loss:
             loss = torch.zeros(1, device=x.device, dtype=torch.float32)
@@ -423,8 +431,8 @@ class VectorQuantize(nn.Module):
         #      used, i.e. BEFORE the EMA step below rewrites it
         needs_sims = return_loss or (training and ((want_loss and use_ce) or self.has_codebook_diversity_loss))
         if needs_sims:
-            codes, live = cb.current_codes(), None
-            if will_update:
+            codes, live = cb.effective_codes(), None
+            if will_update and not cb.use_affine:  # (affine: the codes of this forward are a tensor of their own already)
                 # the backward pass recomputes similarities from the pre-update codebook; the reference's autograd then
                 # multiplies with the codebook as it is at backward time (losses.similarity_matrix: live_codes)
                 codes, live = codes.detach().clone().requires_grad_(codes.requires_grad), cb.embeddings

@@ -126,6 +126,17 @@ class _NativeBackend:
         native.ema_update(cluster_size, embed_avg, embeddings, hits, sums, decay, eps, l2norm)
 
     @staticmethod
+    def column_stats(x, mask=None):
+        """-> (count [H] int64, mean [H, D], m2 [H, D]) of the kept rows of x [H, M, D] in one read (vq_affine_stats_f32)."""
+        return native.column_stats(x, mask)
+
+    @staticmethod
+    def affine_apply(src, codebook_mean, codebook_variance, batch_mean, batch_variance, *, mode, hits=None, out=None):
+        """The affine codebook's moment-matching transform of codes (mode 0) or accumulated sums (mode 1), vq_affine_apply_f32."""
+        return native.affine_apply(src, codebook_mean, codebook_variance, batch_mean, batch_variance, mode=mode, hits=hits,
+                                   out=out)
+
+    @staticmethod
     def quantize_backward(x, cb, idx, grad_out, grad_sq_err, *, ste, share, sq_err_per_head=False):
         """d/dx of the quantize step in one native pass (vq_quantize_backward_f32)."""
         return native.quantize_backward(x, cb, idx, grad_out, grad_sq_err, ste=ste, stages_share_codebook=share,
