@@ -89,6 +89,11 @@ def similarities64(x, c, metric_dot):
     return x @ c.transpose(-1, -2) if metric_dot else -torch.cdist(x, c)
 
 
+def logsumexp64(x, c, tau, metric_dot, dtype=torch.float64):
+    """Natural-log logsumexp_k(tau s) [H, M] in ``dtype`` (what vq_gumbel_stats_f32 returns as lse2, times log 2)."""
+    return (similarities64(x.to(dtype), c.to(dtype), metric_dot) * tau).logsumexp(-1)
+
+
 def closed_form64(x, c, g, ind, tau, metric_dot, reinmax=False, dtype=torch.float64):
     """(delta, gx, gc_sim, gc) of the module docstring of vector_quantization.gumbel, dense, in ``dtype``: x [H, M, D],
     c [H, K, D], g [H, M, D], ind [H, M].  ``dtype=torch.float32`` is the reference's own op sequence at its precision."""
