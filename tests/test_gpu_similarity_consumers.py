@@ -168,6 +168,36 @@ def test_fused_cross_entropy_backward(H, M, K, D, metric):
     assert bool((got[:, ::5] == 0).all()), "ignored rows must get exactly zero gradient"
 
 
+@pytest.mark.parametrize("H,M,K,D,offset_view", [(2, 33, 40, 30, False), (1, 130, 70, 250, True), (1, 65, 70, 300, True)])
+@pytest.mark.parametrize("metric", [0, 1])
+def test_fused_cross_entropy_backward_scalar_row_loads(H, M, K, D, offset_view, metric):
+    """Rows that cannot be read four floats at a time (D % 4 != 0, or a view that starts one float into a wider buffer, which
+    also makes the rows strided) in the one-wave kernel (Dp = 32), the role-split kernel (Dp = 256) and the four-role kernel
+    (Dp = 512, M % 64 != 0), with a partly filled last row block each: float64 autograd, the tolerance of
+    test_fused_cross_entropy_backward."""
+    native = _native()
+    x, cb = make_x((H, M, D), "S"), make_codebook(H, K, D, "S")
+    if metric == 1:
+        x = x * 0.25
+    g = torch.Generator().manual_seed(13)
+    target = torch.randint(0, K, (H, M), generator=g)
+    target[:, ::5] = -1
+    coef = 0.37
+    want = _ce_grad_reference(x, cb, target, metric, coef)
+    xs, cbs, ts = x.cuda(), cb.cuda(), target.cuda()
+    if offset_view:
+        wide = torch.full((H, M, D + 1), 9.0, device="cuda")
+        wide[:, :, 1:] = xs
+        xs = wide[:, :, 1:]  # row stride D + 1, base 4 bytes past a 16-byte boundary
+        assert xs.data_ptr() % 16 == 4 and not xs.is_contiguous()
+    lse, tl = native.softmax_stats(xs, cbs, metric=metric, target=ts)
+    got = native.ce_backward(xs, cbs, lse, tl, ts, torch.tensor([coef], device="cuda"), metric=metric)
+    torch.cuda.synchronize()
+    scale = max(float(want.abs().max()), coef)
+    np.testing.assert_allclose(got.cpu().double().numpy(), want.numpy(), atol=2e-5 * scale, rtol=2e-4)
+    assert bool((got[:, ::5] == 0).all()), "ignored rows must get exactly zero gradient"
+
+
 @pytest.mark.parametrize("H,M,K,D", [(1, 128, 32, 256), (1, 1000, 1000, 256), (2, 333, 1030, 200), (1, 4097, 64, 132),
                                      (3, 129, 7, 256), (1, 70000, 96, 256),
                                      # Dp = 512: four roles per row block (S1, S2, G1, G2), 64 rows per workgroup

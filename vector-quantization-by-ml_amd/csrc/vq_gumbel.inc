@@ -103,13 +103,15 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     const float *rh = p.res + (long long)head * p.res_hs;
 
     float rf[DP / 2];
-    float rn0;
-    load_x_fragments<DP, WAVES, EUCLID>(rh, p.res_rs, p.NR, p.D, p.vec_res, row0, smem, wave, lane, rf, rn0);
+    float rn0 = 0.0f;
+    load_x_fragments<G::CH, G::XS, DP / G::CH, EUCLID>(rh, p.res_rs, p.NR, p.D, p.vec_res, row0, true, smem, wave, lane, rf, rn0);
+    __syncthreads();  // (the staging regions are reused: by the second pass, then as tile buffers)
     float gf[CODES ? 1 : DP / 2];
     if constexpr (!CODES) {
-        float unused;
-        load_x_fragments<DP, WAVES, false>(p.g + (long long)head * p.g_hs, p.g_rs, p.NR, p.D, p.vec_g, row0, smem, wave, lane, gf,
-                                           unused);
+        float unused = 0.0f;
+        load_x_fragments<G::CH, G::XS, DP / G::CH, false>(p.g + (long long)head * p.g_hs, p.g_rs, p.NR, p.D, p.vec_g, row0, true, smem,
+                                                          wave, lane, gf, unused);
+        __syncthreads();
     }
 
     const long long row = row0 + c;

@@ -25,6 +25,8 @@
 //   vq_common.inc        constants, error strings, the kernel-launch helper, metric / padded-dim dispatch, packed (value, index) keys
 //   vq_pack.inc          natural codebook -> packed image
 //   vq_search.inc        the hot kernel (tile geometry, LDS-DMA staging, MFMA fragment pipeline, tie-exact epilogue, finalize)
+//                        and what other sweep kernels share with it: load_x_fragments (a wave's rows -> B fragments + the
+//                        |x|^2 chain, for the training-side sweeps), stage_tile, lane_best_start, store_sims_subtile
 //   vq_search_pair.inc   the same search for 256 < D <= 512 with the dims split over a pair of waves (accumulator hand-off)
 //   vq_search_persist.inc  inference search at Dp = 256 with block b's gather hidden inside block b + 1's sweep
 //   vq_search_resident.inc small codebooks: the packed image stays in LDS, no barriers, rows streamed past it by LDS-DMA slabs

@@ -120,6 +120,106 @@ struct Geo {
     static constexpr int MAIN_FLOATS_S = SEP_STAGE ? NBUF * BUF_F4 * 4 + WAVES * 32 * XS : MAIN_FLOATS;  // MULTI == 0 kernels
 };
 
+// LDS-DMA of one packed tile image into the tile buffer `dst`: buffer_load ... lds with the per-lane part (lane * 16 B) in
+// voffset and the tile / chunk position in the SCALAR offset -> no vector instructions at all per issue (on gfx950 VALU
+// work is not free beside f32 MFMA: it executes on the same lanes).  The 1-KiB chunks go round the workgroup's waves.
+// Used by the kernels whose register allocation it leaves as it was (vq_search_persist, vq_ce_backward_roles); the other
+// sweeps spell the same loop out in a `stage` lambda (profiles/prologue_refactor_codegen.md has the figures).
+template <typename G, int WAVES>
+__device__ __forceinline__ void stage_tile(const float *img, unsigned bytes, int tile, lds_f32x4 *dst, int wave, int lane) {
+#pragma unroll
+    for (int i = 0; i < (G::TILE_CHUNKS + WAVES - 1) / WAVES; ++i) {
+        const int ck = i * WAVES + wave;
+        if (ck < G::TILE_CHUNKS) lds_dma16(img, bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16, dst + ck * 64);
+    }
+}
+
+// ---- prologue of the fp32 MFMA sweeps: a wave's 32 rows -> B fragments in registers --------------------------------------
+// xf[s] = x[row0 + c][2 s + h] for the NCHUNK * CH dims from `x` on: lane half h holds the k = h operand of MFMA step s of
+// v_mfma_f32_32x32x2_f32.  Rows past M repeat row M - 1, dims past D are zeros.  The rows go through the wave-private LDS
+// region number `region` of `stage` ([32][XS] floats each; no workgroup barriers: a wave's LDS operations execute in order)
+// CH dims at a time, the global loads of chunk i + 1 in flight while chunk i goes through LDS.  On the way every lane extends
+// xn0 = |x|^2 of its row c (both lane halves read the same row): the d-ordered fmaf chain of oracle/vq_oracle.c
+// (sumsq_chain), continued from the value the caller passes in (0, or the chain over the dims in front of these) -- when
+// EUCLID and `walk_chain`.
+// `x` points at dim 0 of the head's first row -- a wave that owns the dims from d on passes x + d and D - d; `vec_x`: rows may
+// be read as float4.  No barrier at the end: the caller knows whether the region is about to be reused by other waves.
+// Shared by the similarity / softmax-statistics / sampling sweeps, the cross-entropy backward kernels and the Gumbel sweeps.
+// The three inference search kernels (vq_search_mfma below, vq_search_pair512, vq_search_persist) keep this body written out
+// in place, with their own variations (fp16 / bf16 rows, non-temporal loads, the screened sweep's bf16 pairing): routed
+// through this function their VGPR / AGPR counts move (profiles/prologue_refactor_codegen.md), and those kernels are tuned
+// to their register budgets.  A change to the chain or the swaps has to be made in all four places.
+template <int CH, int XS, int NCHUNK, bool EUCLID>
+__device__ __forceinline__ void load_x_fragments(const float *x, long long x_rs, long long M, int D, int vec_x, long long row0,
+                                                 bool walk_chain, float *stage, int region, int lane,
+                                                 float (&xf)[NCHUNK * CH / 2], float &xn0) {
+    constexpr int LPL = CH / 8;  // float4 loads per lane per chunk
+    const int c = lane & 31, h = lane >> 5;
+    float *xs = stage + region * (32 * XS);
+    f32x4 v[2][LPL];
+    auto load_chunk = [&](int ch, f32x4 (&dst)[LPL]) {
+#pragma unroll
+        for (int it = 0; it < LPL; ++it) {
+            const int f = it * 64 + lane;
+            const int r = f / (CH / 4), c4 = f % (CH / 4);
+            long long grow = row0 + r;
+            if (grow >= M) grow = M - 1;
+            const int d0 = ch * CH + c4 * 4;
+            f32x4 t = {0.0f, 0.0f, 0.0f, 0.0f};
+            const float *src = x + grow * x_rs + d0;
+            if (vec_x) {
+                if (d0 < D) t = *(const f32x4 *)src;
+            } else {
+                if (d0 + 0 < D) t.x = src[0];
+                if (d0 + 1 < D) t.y = src[1];
+                if (d0 + 2 < D) t.z = src[2];
+                if (d0 + 3 < D) t.w = src[3];
+            }
+            dst[it] = t;
+        }
+    };
+    load_chunk(0, v[0]);
+#pragma unroll
+    for (int ch = 0; ch < NCHUNK; ++ch) {
+        if (ch + 1 < NCHUNK) load_chunk(ch + 1, v[(ch + 1) & 1]);
+#pragma unroll
+        for (int it = 0; it < LPL; ++it) {
+            const int f = it * 64 + lane;
+            const int r = f / (CH / 4), c4 = f % (CH / 4);
+            *(f32x4 *)(xs + r * XS + c4 * 4) = v[ch & 1][it];  // XS = 4 mod 8: b128 accesses conflict-free
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const float *rp = xs + c * XS;  // this lane's row
+#pragma unroll
+        for (int j = 0; j < CH / 8; ++j) {
+            const f32x4 lo = *(const f32x4 *)(rp + 8 * j);
+            const f32x4 hi = *(const f32x4 *)(rp + 8 * j + 4);
+            if (EUCLID && walk_chain) {
+                xn0 = fmaf(lo.x, lo.x, xn0);
+                xn0 = fmaf(lo.y, lo.y, xn0);
+                xn0 = fmaf(lo.z, lo.z, xn0);
+                xn0 = fmaf(lo.w, lo.w, xn0);
+                xn0 = fmaf(hi.x, hi.x, xn0);
+                xn0 = fmaf(hi.y, hi.y, xn0);
+                xn0 = fmaf(hi.z, hi.z, xn0);
+                xn0 = fmaf(hi.w, hi.w, xn0);
+                asm volatile("" : "+v"(xn0));  // pin the chain here: do not keep lo/hi alive to finish it later
+            }
+            // lower half-wave keeps dims 8j..8j+3, upper 8j+4..8j+7; two half-wave exchanges de-interleave
+            // them into the MFMA k-parity layout: lower gets the even dims, upper the odd dims.
+            const f32x4 m = h ? hi : lo;
+            const auto xy = __builtin_amdgcn_permlane32_swap(__float_as_uint(m.x), __float_as_uint(m.y), false, false);
+            const auto zw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m.z), __float_as_uint(m.w), false, false);
+            const int sb = ch * (CH / 2) + 4 * j;
+            xf[sb + 0] = __uint_as_float(xy[0]);  // dim 8j + 0 + h
+            xf[sb + 1] = __uint_as_float(zw[0]);  // dim 8j + 2 + h
+            xf[sb + 2] = __uint_as_float(xy[1]);  // dim 8j + 4 + h
+            xf[sb + 3] = __uint_as_float(zw[1]);  // dim 8j + 6 + h
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads done before the next chunk overwrites
+    }
+}
+
 // code fragments: one ds_read_b128 feeds 4 MFMAs (256 cycles of matrix pipe).  `a` is the whole tile's fragment
 // array (compile-time indexed -> registers); reads run PF groups ahead of the MFMAs and the order is pinned so the
 // scheduler cannot hoist every read to the top (register pressure).  Groups [G0, G1) of 8 dims.
@@ -425,6 +525,48 @@ __device__ __forceinline__ float sweep_start_value(unsigned cb_flag) {
     return cb_flag ? INF : -INF;
 }
 
+// A lane's state at the start of a sweep: nothing parked yet (Euclid: pend[0] <= +inf still selects code 0), `best_t` = the
+// record every candidate has to beat (sweep_start_value, or +inf for the screened sweep)
+template <int METRIC>
+__device__ __forceinline__ LaneBest lane_best_start(float best_t) {
+    const float INF = __builtin_inff();
+    LaneBest lb;
+    lb.best_t = best_t;
+    lb.pend_u = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) lb.pend[r] = (METRIC == VQ_METRIC_EUCLID) ? INF : -INF;
+    lb.run_m = -INF;
+    lb.run_s = 0.0f;
+    return lb;
+}
+
+// Similarities of sub-tile u leave for memory (the WIDE = 3 variants of vq_search_mfma and vq_search_pair512): a lane holds
+// codes u*32 + 4h + 8g + (0..3) of ITS row (`srow`) -> one float4 per g.  sim = -sqrt(max(0, t)) (Euclid; correctly rounded,
+// like the values the search compares, and it keeps NaN) / x.c (dot): codebooks.py:386,435.  `vec_s`: float4 stores are
+// aligned (then K % 4 == 0).
+// (Scalar arguments by reference, as the lambdas this replaces captured them: by value the allocator packs these kernels
+//  tighter -- vq_search_mfma<32, 4, EUCLID, .., WIDE 3> 118 -> 87 VGPRs, <256, 4, ..> 206 -> 198, <512, 4, ..> 104 -> 96 AGPRs --
+//  a change of its own to measure, not part of sharing the code.)
+template <bool EUCLID>
+__device__ __forceinline__ void store_sims_subtile(const f32x16 &acc, const int &u, const int &h, const bool &row_ok, float *const &srow,
+                                                   const int &K, const int &vec_s) {
+    if (!row_ok) return;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = EUCLID ? -sqrtf(acc[4 * g + e] < 0.0f ? 0.0f : acc[4 * g + e]) : acc[4 * g + e];
+        const int code = u * kTileCodes + 4 * h + 8 * g;
+        if (vec_s) {
+            if (code < K) *(f32x4 *)(srow + code) = o;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (code + e < K) srow[code + e] = o[e];
+        }
+    }
+}
+
 // which rows of this wave take the repair: bit r = row r (lanes r and r + 32 agree on `best_s` after the merge)
 __device__ __forceinline__ unsigned nonfinite_rows(float best_s, bool row_ok) {
     return (unsigned)__ballot(row_ok && !(__builtin_fabsf(best_s) < __builtin_inff()));
@@ -491,6 +633,7 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_search_mfm
 
     // ---------------- prologue: this wave's 32 rows -> MFMA fragments in registers ----------------
     // xf[s] = x[row0 + c][2 s + h]   (lane half h holds the k = h operand of MFMA step s)
+    // (load_x_fragments written out in place, with fp16 / bf16 rows and non-temporal loads: see there)
     STAMP(0);
     STAMP_RT(60);
     // Memory-bound phases (prologue, finalize) run at raised priority: when another workgroup's wave is streaming
@@ -622,24 +765,7 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_search_mfm
     };
     auto ws_store = [&](const f32x16 &v, int u) {
         if constexpr (WIDE == 3) {
-            // similarities of sub-tile u: a lane holds codes u*32 + 4h + 8g + (0..3) of ITS row -> one float4 per g
-            // (-sqrt correctly rounded, like the values the search compares; codebooks.py:386,435)
-            if (!row_ok) return;
-            float *srow = p.sims + (long long)head * p.sims_hs + row * p.sims_rs;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                f32x4 o;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = EUCLID ? -sqrtf(v[4 * g + e] < 0.0f ? 0.0f : v[4 * g + e]) : v[4 * g + e];  // (keeps NaN)
-                const int code = u * kTileCodes + 4 * h + 8 * g;
-                if (p.vec_s) {
-                    if (code < p.K) *(f32x4 *)(srow + code) = o;  // K % 4 == 0 with vec_s
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (code + e < p.K) srow[code + e] = o[e];
-                }
-            }
+            store_sims_subtile<EUCLID>(v, u, h, row_ok, p.sims + (long long)head * p.sims_hs + row * p.sims_rs, p.K, p.vec_s);
         } else {
             f32x4 *s4 = wsw + (long long)u * 256;
 #pragma unroll
@@ -655,19 +781,7 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_search_mfm
         // later stages from the residual update at the end of the previous stage (`xn0` is carried in the lower lane half)
         const float b_aug = EUCLID ? (h ? 1.0f : xn0) : 1.0f;  // B[k=0][row] = |x|^2, B[k=1][row] = 1
         STAMP(4 + 5 * q + 0);
-        LaneBest lb;
-        lb.best_t = sweep_start_value<METRIC>(codebook_flag(pk, p.pk_bytes));
-        lb.pend_u = 0;
-        lb.pend = (f32x16){0};
-        lb.run_m = -INF;
-        lb.run_s = 0.0f;
-        if (EUCLID) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) lb.pend[r] = INF;  // nothing parked yet (pend[0] <= +inf still selects code 0)
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) lb.pend[r] = -INF;
-        }
+        LaneBest lb = lane_best_start<METRIC>(sweep_start_value<METRIC>(codebook_flag(pk, p.pk_bytes)));
 
         const int t0 = blockIdx.z * p.tiles_per_split;
         const int t1 = (t0 + p.tiles_per_split < p.ntiles) ? t0 + p.tiles_per_split : p.ntiles;

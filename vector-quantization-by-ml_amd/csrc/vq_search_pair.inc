@@ -89,7 +89,7 @@ __global__ void __launch_bounds__(512, 2) vq_search_pair512(const SearchParams p
             xn0 = p.xn_ws[(long long)head * p.xn_hs + grow];
         }
     }
-    {
+    {  // (load_x_fragments of vq_search.inc written out in place for this wave's half of the dims: see there)
         float *xs = smem + wave * (32 * XS);
         constexpr int NCHUNK = HD / CH;
         constexpr int LPL = CH / 8;
@@ -281,36 +281,15 @@ __global__ void __launch_bounds__(512, 2) vq_search_pair512(const SearchParams p
         // where the accumulators leave the wave instead of entering the argmin (WIDE = 1: the workspace; 3: the similarities)
         auto ws_store = [&](const f32x16 &v, int tile) {
             if constexpr (WIDE == 3) {
-                if (!row_ok) return;
-                float *srow = p.sims + (long long)head * p.sims_hs + row * p.sims_rs;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f32x4 o;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = EUCLID ? -sqrtf(v[4 * g + e] < 0.0f ? 0.0f : v[4 * g + e]) : v[4 * g + e];
-                    const int code = tile * kTileCodes + 4 * h + 8 * g;
-                    if (p.vec_s) {
-                        if (code < p.K) *(f32x4 *)(srow + code) = o;
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (code + e < p.K) srow[code + e] = o[e];
-                    }
-                }
+                store_sims_subtile<EUCLID>(v, tile, h, row_ok, p.sims + (long long)head * p.sims_hs + row * p.sims_rs, p.K, p.vec_s);
             } else {
                 f32x4 *s4 = wsw + (long long)tile * 256;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) s4[g * 64] = (f32x4){v[4 * g + 0], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
             }
         };
-        LaneBest lb;  // (declared after the chain: its 16 parked registers would be live across it otherwise)
-        lb.best_t = sweep_start_value<METRIC>(codebook_flag(pk, p.pk_bytes));
-        lb.pend_u = 0;
-        lb.pend = (f32x16){0};
-        lb.run_m = -INF;
-        lb.run_s = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) lb.pend[r] = EUCLID ? INF : -INF;
+        // (declared after the chain: its 16 parked registers would be live across it otherwise)
+        LaneBest lb = lane_best_start<METRIC>(sweep_start_value<METRIC>(codebook_flag(pk, p.pk_bytes)));
         f32x16 acc;
         // One step of B.  The previous tile's 32 x 32 result is reduced FIRST and its registers are then reloaded from the
         // hand-off slot: B keeps ONE accumulator (two would not fit beside 128 row registers without spilling in the loop).

@@ -515,16 +515,16 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
     };
 
     auto stage = [&](int tile, int buf) {
+        if constexpr (SCREEN) {  // a bf16x3 tile: its own length, whole KiB
+            static_assert(kScrTileBytes <= G::BUF_F4 * 16, "a bf16x3 tile fits the fp32 tile's buffer");
 #pragma unroll
-        for (int i2 = 0; i2 < (G::TILE_CHUNKS + WAVES - 1) / WAVES; ++i2) {
-            const int ck = i2 * WAVES + wave;
-            if constexpr (SCREEN) {
-                static_assert(kScrTileBytes <= G::BUF_F4 * 16, "a bf16x3 tile fits the fp32 tile's buffer");
+            for (int i2 = 0; i2 < (G::TILE_CHUNKS + WAVES - 1) / WAVES; ++i2) {
+                const int ck = i2 * WAVES + wave;
                 if (ck < (kScrTileBytes + 1023) / 1024)
                     lds_dma16(scrh, p.scr_bytes, lane * 16, tile * kScrTileBytes + ck * 1024, tile4_lds + buf * G::BUF_F4 + ck * 64);
-            } else if (ck < G::TILE_CHUNKS) {
-                lds_dma16(pk, p.pk_bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16, tile4_lds + buf * G::BUF_F4 + ck * 64);
             }
+        } else {
+            stage_tile<G, WAVES>(pk, p.pk_bytes, tile, tile4_lds + buf * G::BUF_F4, wave, lane);
         }
     };
     // Diagnostic build (-DVQ_EXP_STAMPS; tools/stamps_persist.py): per wave and row block `it` < 14 the shader-clock time of
@@ -540,7 +540,9 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         // the sweep's first tile goes out before the rows are loaded: the tile buffers are free (the previous sweep ended with a
         // barrier) and the rows are staged behind them
         stage(0, 0);
-        // ---------------- prologue: this wave's 32 rows -> MFMA fragments in registers (vq_search_mfma's) ----------------
+        // ---------------- prologue: this wave's 32 rows -> MFMA fragments in registers ----------------
+        // (load_x_fragments of vq_search.inc written out in place: vector loads only, and SCREEN pairs the groups of 8 dims
+        //  into bf16 fragments instead of swapping them -- see there)
         __builtin_amdgcn_s_setprio(2);
         float xf[NS];  // (unused by SCREEN)
         bf16x8 xhf[SCREEN ? DP / 16 : 1], xlf[SCREEN ? DP / 16 : 1];  // SCREEN: B fragments of group s = 16 dims (hi, lo)
@@ -621,17 +623,9 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         const bool row_ok = row < p.M;
         const float b_aug = EUCLID ? (h ? 1.0f : xn0) : 1.0f;
 
-        LaneBest lb;
-        lb.best_t = sweep_start_value<METRIC>(codebook_flag(pk, p.pk_bytes));  // (SCREEN: reset below)
-        lb.pend_u = 0;
-        lb.pend = (f32x16){0};
-        lb.run_m = -INF;
-        lb.run_s = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) lb.pend[r] = EUCLID ? INF : -INF;
-
         const unsigned cb_flag = codebook_flag(pk, p.pk_bytes);
-        if constexpr (SCREEN) lb.best_t = INF;  // (a flagged codebook makes every row uncertain instead, below)
+        // (SCREEN starts from +inf: a flagged codebook makes every row uncertain instead, below)
+        LaneBest lb = lane_best_start<METRIC>(SCREEN ? INF : sweep_start_value<METRIC>(cb_flag));
         // SCREEN, per lane over its codes: lowest value b1 (lb.best_t, its code lb.pend_u), second lowest b2 (code scr_i2) and
         // third lowest b3 over distinct codes.  Per value v: b3 = med3(b2, b3, v), b2 = med3(b1, b2, v), b1 = min(b1, v) (each
         // med3 is the new k-th lowest because b1 <= b2 <= b3); the codes are looked up only when the two lowest change.

@@ -229,14 +229,7 @@ __global__ void __launch_bounds__(512, 2) vq_search_resident(const SearchParams 
         const bool row_ok = row < p.M;
         const float b_aug = EUCLID ? (h ? 1.0f : xn0) : 1.0f;
 
-        LaneBest lb;
-        lb.best_t = start_value;
-        lb.pend_u = 0;
-        lb.pend = (f32x16){0};
-        lb.run_m = -INF;
-        lb.run_s = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) lb.pend[r] = EUCLID ? INF : -INF;
+        LaneBest lb = lane_best_start<METRIC>(start_value);
         xnn = 0.0f;
         RSTAMP_BEGIN();
 

@@ -40,81 +40,6 @@ struct AuxParams {
 namespace {
 using vqi::AuxParams;
 
-// x rows of one wave -> MFMA B fragments (same layout and |x|^2 chain as the search kernel's prologue)
-template <int DP, int WAVES, bool EUCLID>
-__device__ __forceinline__ void load_x_fragments(const float *xh, long long x_rs, long long M, int D, int vec_x,
-                                                 long long row0, float *smem, int wave, int lane,
-                                                 float (&xf)[DP / 2], float &xn0) {
-    using G = Geo<DP, WAVES>;
-    constexpr int CH = G::CH, XS = G::XS;
-    const int c = lane & 31, h = lane >> 5;
-    float *xs = smem + wave * (32 * XS);
-    constexpr int NCHUNK = DP / CH;
-    constexpr int LPL = CH / 8;
-    xn0 = 0.0f;
-    f32x4 v[2][LPL];  // global loads of chunk i+1 are in flight while chunk i goes through LDS
-    auto load_chunk = [&](int ch, f32x4 (&dst)[LPL]) {
-#pragma unroll
-        for (int it = 0; it < LPL; ++it) {
-            const int f = it * 64 + lane;
-            const int r = f / (CH / 4), c4 = f % (CH / 4);
-            long long grow = row0 + r;
-            if (grow >= M) grow = M - 1;
-            const int d0 = ch * CH + c4 * 4;
-            const float *src = xh + grow * x_rs + d0;
-            f32x4 t = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (vec_x) {
-                if (d0 < D) t = *(const f32x4 *)src;
-            } else {
-                if (d0 + 0 < D) t.x = src[0];
-                if (d0 + 1 < D) t.y = src[1];
-                if (d0 + 2 < D) t.z = src[2];
-                if (d0 + 3 < D) t.w = src[3];
-            }
-            dst[it] = t;
-        }
-    };
-    load_chunk(0, v[0]);
-#pragma unroll
-    for (int ch = 0; ch < NCHUNK; ++ch) {
-        if (ch + 1 < NCHUNK) load_chunk(ch + 1, v[(ch + 1) & 1]);
-#pragma unroll
-        for (int it = 0; it < LPL; ++it) {
-            const int f = it * 64 + lane;
-            const int r = f / (CH / 4), c4 = f % (CH / 4);
-            *(f32x4 *)(xs + r * XS + c4 * 4) = v[ch & 1][it];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const float *rp = xs + c * XS;
-#pragma unroll
-        for (int j = 0; j < CH / 8; ++j) {
-            const f32x4 lo = *(const f32x4 *)(rp + 8 * j);
-            const f32x4 hi = *(const f32x4 *)(rp + 8 * j + 4);
-            if (EUCLID) {
-                xn0 = fmaf(lo.x, lo.x, xn0);
-                xn0 = fmaf(lo.y, lo.y, xn0);
-                xn0 = fmaf(lo.z, lo.z, xn0);
-                xn0 = fmaf(lo.w, lo.w, xn0);
-                xn0 = fmaf(hi.x, hi.x, xn0);
-                xn0 = fmaf(hi.y, hi.y, xn0);
-                xn0 = fmaf(hi.z, hi.z, xn0);
-                xn0 = fmaf(hi.w, hi.w, xn0);
-                asm volatile("" : "+v"(xn0));
-            }
-            const f32x4 m = h ? hi : lo;
-            const auto xy = __builtin_amdgcn_permlane32_swap(__float_as_uint(m.x), __float_as_uint(m.y), false, false);
-            const auto zw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m.z), __float_as_uint(m.w), false, false);
-            const int sb = ch * (CH / 2) + 4 * j;
-            xf[sb + 0] = __uint_as_float(xy[0]);
-            xf[sb + 1] = __uint_as_float(zw[0]);
-            xf[sb + 2] = __uint_as_float(xy[1]);
-            xf[sb + 3] = __uint_as_float(zw[1]);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-}
-
 template <int DP, int WAVES, int METRIC, int MODE>
 __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_sweep_aux(const AuxParams p) {
     using G = Geo<DP, WAVES>;
@@ -135,8 +60,9 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_sweep_aux(
     const float INF = __builtin_inff();
 
     float xf[DP / 2];
-    float xn0;
-    load_x_fragments<DP, WAVES, EUCLID>(xh, p.x_rs, p.M, p.D, p.vec_x, row0, smem, wave, lane, xf, xn0);
+    float xn0 = 0.0f;
+    load_x_fragments<G::CH, G::XS, DP / G::CH, EUCLID>(xh, p.x_rs, p.M, p.D, p.vec_x, row0, true, smem, wave, lane, xf, xn0);
+    __syncthreads();  // the staging region is about to be reused as codebook tile buffers
 
     const long long row = row0 + c;
     const bool row_ok = row < p.M;
@@ -461,8 +387,9 @@ __global__ void __launch_bounds__(256, (DP <= 128 ? 2 : 1)) vq_ce_backward(const
 
     STAMP(0);
     float xf[DP / 2];
-    float xn0;
-    load_x_fragments<DP, WAVES, EUCLID>(xh, p.x_rs, p.M, p.D, p.vec_x, row0, smem, wave, lane, xf, xn0);
+    float xn0 = 0.0f;
+    load_x_fragments<G::CH, G::XS, DP / G::CH, EUCLID>(xh, p.x_rs, p.M, p.D, p.vec_x, row0, true, smem, wave, lane, xf, xn0);
+    __syncthreads();  // the staging region is about to be reused as codebook tile buffers
     STAMP(1);
 
     const long long row = row0 + c;
@@ -720,14 +647,7 @@ __global__ void __launch_bounds__(512, 1) vq_ce_backward_roles(const CeBwdParams
     const int T = p.ntiles;
     f32x4 *slot4 = (f32x4 *)(smem + RG::TILES_F + blk * 2 * RG::SLOT_F) + lane;  // this pair's two slots, this lane's float4 column
 
-    auto stage = [&](int tile, int buf) {
-#pragma unroll
-        for (int i = 0; i < (G::TILE_CHUNKS + WAVES - 1) / WAVES; ++i) {
-            const int ck = i * WAVES + wave;
-            if (ck < G::TILE_CHUNKS)
-                lds_dma16(pk, p.pk_bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16, tile4_lds + buf * G::BUF_F4 + ck * 64);
-        }
-    };
+    auto stage = [&](int tile, int buf) { stage_tile<G, WAVES>(pk, p.pk_bytes, tile, tile4_lds + buf * G::BUF_F4, wave, lane); };
     // finalize staging of this pair's row block (aliases the tile buffers / slots once the sweep is over)
     float *stg = smem + blk * RG::STG_F;
     float *srs = stg + 32 * CG::GS;
@@ -738,8 +658,10 @@ __global__ void __launch_bounds__(512, 1) vq_ce_backward_roles(const CeBwdParams
     if (!role_g) {
         // ================= wave S: x fragments, S sweep, softmax weights =================
         float xf[DP / 2];
-        float xn0;
-        load_x_fragments<DP, 4, EUCLID>(xh, p.x_rs, p.M, p.D, p.vec_x, row0, smem + 2 * G::BUF_F4 * 4, blk, lane, xf, xn0);  // (ends in a workgroup barrier)
+        float xn0 = 0.0f;
+        load_x_fragments<G::CH, G::XS, DP / G::CH, EUCLID>(xh, p.x_rs, p.M, p.D, p.vec_x, row0, true, smem + 2 * G::BUF_F4 * 4, blk,
+                                                           lane, xf, xn0);
+        __syncthreads();
         const long long row = row0 + c;
         const bool row_ok = row < p.M;
         const float b_aug = h ? 1.0f : xn0;
@@ -994,74 +916,14 @@ __global__ void __launch_bounds__(512, 1) vq_ce_backward_roles512(const CeBwdPar
     float *stg_f = rowt + 64;
 
     if (role < 2) {
-        // ================= S1 / S2: this wave's half of the rows -> fragments (the wave-pair search kernel's prologue) =================
+        // ================= S1 / S2: this wave's half of the rows -> fragments =================
         const int dbase = role * HD;
         float xf[NS];
         float xn0 = 0.0f;
         {
+            // S1 walks its part of the d-ordered |x|^2 chain, S2 continues it below (row chunks of 32 dims, as in vq_search_pair512)
             constexpr int CH = 32, XS = 64 + 4;
-            float *xs = smem + sw * (32 * XS);
-            constexpr int NCHUNK = HD / CH, LPL = CH / 8;
-            f32x4 v[2][LPL];
-            auto load_chunk = [&](int ch, f32x4 (&dst)[LPL]) {
-#pragma unroll
-                for (int it = 0; it < LPL; ++it) {
-                    const int f = it * 64 + lane;
-                    const int r = f / (CH / 4), c4 = f % (CH / 4);
-                    long long grow = row0 + r;
-                    if (grow >= p.M) grow = p.M - 1;
-                    const int d0 = dbase + ch * CH + c4 * 4;
-                    const float *src = xh + grow * p.x_rs + d0;
-                    f32x4 t = {0.0f, 0.0f, 0.0f, 0.0f};
-                    if (p.vec_x) {
-                        if (d0 < p.D) t = *(const f32x4 *)src;
-                    } else {
-                        if (d0 + 0 < p.D) t.x = src[0];
-                        if (d0 + 1 < p.D) t.y = src[1];
-                        if (d0 + 2 < p.D) t.z = src[2];
-                        if (d0 + 3 < p.D) t.w = src[3];
-                    }
-                    dst[it] = t;
-                }
-            };
-            load_chunk(0, v[0]);
-#pragma unroll
-            for (int ch = 0; ch < NCHUNK; ++ch) {
-                if (ch + 1 < NCHUNK) load_chunk(ch + 1, v[(ch + 1) & 1]);
-#pragma unroll
-                for (int it = 0; it < LPL; ++it) {
-                    const int f = it * 64 + lane;
-                    const int r = f / (CH / 4), c4 = f % (CH / 4);
-                    *(f32x4 *)(xs + r * XS + c4 * 4) = v[ch & 1][it];
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                const float *rp = xs + c * XS;
-#pragma unroll
-                for (int j = 0; j < CH / 8; ++j) {
-                    const f32x4 lo = *(const f32x4 *)(rp + 8 * j);
-                    const f32x4 hi = *(const f32x4 *)(rp + 8 * j + 4);
-                    if (EUCLID && role == 0) {  // S1's part of the d-ordered |x|^2 chain (S2 continues it below)
-                        xn0 = fmaf(lo.x, lo.x, xn0);
-                        xn0 = fmaf(lo.y, lo.y, xn0);
-                        xn0 = fmaf(lo.z, lo.z, xn0);
-                        xn0 = fmaf(lo.w, lo.w, xn0);
-                        xn0 = fmaf(hi.x, hi.x, xn0);
-                        xn0 = fmaf(hi.y, hi.y, xn0);
-                        xn0 = fmaf(hi.z, hi.z, xn0);
-                        xn0 = fmaf(hi.w, hi.w, xn0);
-                        asm volatile("" : "+v"(xn0));
-                    }
-                    const f32x4 m = h ? hi : lo;
-                    const auto xy = __builtin_amdgcn_permlane32_swap(__float_as_uint(m.x), __float_as_uint(m.y), false, false);
-                    const auto zw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m.z), __float_as_uint(m.w), false, false);
-                    const int sb = ch * (CH / 2) + 4 * j;
-                    xf[sb + 0] = __uint_as_float(xy[0]);
-                    xf[sb + 1] = __uint_as_float(zw[0]);
-                    xf[sb + 2] = __uint_as_float(xy[1]);
-                    xf[sb + 3] = __uint_as_float(zw[1]);
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            }
+            load_x_fragments<CH, XS, HD / CH, EUCLID>(xh + dbase, p.x_rs, p.M, p.D - dbase, p.vec_x, row0, role == 0, smem, sw, lane, xf, xn0);
             if (EUCLID && role == 0 && h == 0) xn_a[quad * 32 + c] = xn0;
         }
         if (tid < 8) flags[tid] = 0;  // (wave 0 is quad 0's S1; before the barrier)
