@@ -288,6 +288,47 @@ int vq_gumbel_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs,
                                  const float *delta, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * Backward of the reinmax Gumbel softmax over the similarities (utils/general.py:131-146 with codebooks.py:386-395), nothing
+ * of [M, K] in memory.  With s, g, a, tau as above and ind the selected code of every row:
+ *   p0 = softmax_k(s)                      delta0_m = sum_k p0_mk a_mk
+ *   ptau = softmax_k(tau s)                p1_mk = max((onehot(ind_m)_k + ptau_mk) / 2, 1e-5)
+ *   col_k = sum_m p1_mk                    e_k = (sum_m p1_mk a_mk) / col_k        (sums over the rows of the head)
+ *   w_mk = 2 (p1_mk / col_k)(a_mk - e_k) - 0.5 p0_mk (a_mk - delta0_m) = dL/ds, and through the similarities as above.
+ * All four use a->x, H, M, K, D (<= 256: VQ_E_UNSUPPORTED beyond), metric and the rows g; tau must be positive and finite
+ * (VQ_E_BADARG).  M == 0: nothing is launched (backward_codes zeroes grad_codes).
+ * Per-row arrays lse2_tau / lse2_one / delta0: [H][vq_gumbel_row_stride(M)] floats; per-code arrays col / e:
+ * [H][vq_gumbel_row_stride(K)] floats (entries past K are written as col = 1, e = 0); all 16-byte aligned.
+ * ind: int64, element (h, m) at ind[h*ind_hs + m*ind_rs].  It is only ever COMPARED with a code index: a value outside
+ * [0, K) selects nothing.  It need not be the argmax of the similarities.
+ * vq_gumbel_reinmax_stats_f32 (a->packed): lse2_tau[h][m] = log2 sum_k exp2(tau s log2 e), lse2_one the same at tau = 1, delta0.
+ * vq_gumbel_reinmax_columns_f32 (a->cb): writes col and e.  It packs the x rows and the g rows into the workspace, converts
+ *   ind to int32 there, sweeps the rows in splits and adds the splits' partial sums in split order.
+ * vq_gumbel_reinmax_backward_x_f32 (a->packed): grad_x (h, m, d) at grad_x[h*gx_hs + m*gx_rs + d].
+ * vq_gumbel_reinmax_backward_codes_f32 (a->cb): grad_codes [H][K][D] contiguous, the part through the similarities only.
+ *   CONTRACT: it must be given the workspace that vq_gumbel_reinmax_columns_f32 filled for the same a->x, g, ind and shape
+ *   on the same stream order -- it reuses the packed row images and the int32 ind found there and does not pack again.
+ * No float atomics anywhere: results are bit-identical from run to run on one device.
+ * Workspace (>= vq_gumbel_reinmax_workspace_bytes bytes, 16-byte aligned; 0 = unsupported shape), in 4-byte units, with
+ * img = vq_packed_floats(M, D), rsM = vq_gumbel_row_stride(M), rsK = vq_gumbel_row_stride(K), splits = the row splits of
+ * the plan vq_gumbel_backward_codes_f32 uses:
+ *   [x image: H*img][g image: H*img][ind int32: H*rsM (-1 past M)][col partials: splits*H*rsK][e partials: splits*H*rsK]
+ *   [grad_codes partials: splits*H*K*D, only when splits > 1]
+ * More than 2^31 - 1 rows or a packed row image of 2 GiB or more: VQ_E_UNSUPPORTED (use row chunks).
+ */
+int64_t vq_gumbel_reinmax_workspace_bytes(int H, int64_t M, int K, int D);
+int vq_gumbel_reinmax_stats_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, float *lse2_tau,
+                                float *lse2_one, float *delta0, void *stream);
+int vq_gumbel_reinmax_columns_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
+                                  const int64_t *ind, int64_t ind_rs, int64_t ind_hs, float *col, float *e, void *workspace,
+                                  int64_t workspace_bytes, void *stream);
+int vq_gumbel_reinmax_backward_x_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
+                                     const float *lse2_one, const float *delta0, const int64_t *ind, int64_t ind_rs, int64_t ind_hs,
+                                     const float *col, const float *e, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream);
+int vq_gumbel_reinmax_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
+                                         const float *lse2_one, const float *delta0, const float *col, const float *e,
+                                         float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * Gumbel-max sampling of the code, utils/general.py:112-129 (ind = argmax(similarities / temperature + gumbel_noise)) with
  * the noise of utils/general.py:25-30, as an epilogue of the similarity sweep: nothing of [M, K] in memory, one launch.
  *   idx[h*idx_hs + m*idx_rs] = first index of the maximum over k < K of  key = fl(fl(s * tau) + g)

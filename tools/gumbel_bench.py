@@ -1,7 +1,9 @@
 """Timings of the Gumbel straight-through backward: the three fused sweeps (row statistics, d/dx, d/dcodes) and the chunked
-path on the same inputs, beside vq_ce_backward_f32 on the same shapes (diagnostic; DESIGN.md quotes these).
+path on the same inputs, beside vq_ce_backward_f32 on the same shapes; then the four fused sweeps of the reinmax backward
+(row statistics, column statistics, d/dx, d/dcodes), their sum, and the chunked reinmax path on the same inputs, alternating
+over ``--rounds`` (diagnostic; DESIGN.md quotes these).
 
-    python tools/gumbel_bench.py            # on the GPU box
+    python tools/gumbel_bench.py [--rounds N]           # on the GPU box
 """
 import os
 import sys
@@ -33,7 +35,7 @@ def line(name, t, flops):
     print(f"  {name:42s} {t:9.3f} ms  {flops / t / 1e9:7.1f} TFLOP/s ({flops / t / 1e9 / PEAK:.3f} of peak)")
 
 
-def shape(M, K, D, metric=native.EUCLID, tau=1.0):
+def shape(M, K, D, metric=native.EUCLID, tau=1.0, rounds=2):
     dev = "cuda:0"
     gen = torch.Generator(device=dev).manual_seed(0)
     x = torch.randn((1, M, D), device=dev, generator=gen)
@@ -58,8 +60,29 @@ def shape(M, K, D, metric=native.EUCLID, tau=1.0):
     ind = tgt
     line("chunked path, gx and gc (8 contractions)",
          timed(lambda: gumbel._chunked_backward(x, cb, None, ind, g, metric, tau, False, True, True), n=2, warm=1), 8 * mkd)
+    # reinmax: the fused sweeps and the chunked path in turns, so that drift of the device shows in both
+    for rnd in range(rounds):
+        print(f" reinmax, round {rnd + 1}")
+        stats = native.gumbel_reinmax_stats(x, cb, g, metric=metric, tau=tau, packed=packed)
+        col, e, ws = native.gumbel_reinmax_columns(x, cb, g, stats[0], ind, metric=metric, tau=tau)
+        ts = [timed(lambda: native.gumbel_reinmax_stats(x, cb, g, metric=metric, tau=tau, packed=packed)),
+              timed(lambda: native.gumbel_reinmax_columns(x, cb, g, stats[0], ind, metric=metric, tau=tau, workspace=ws)),
+              timed(lambda: native.gumbel_reinmax_backward_x(x, cb, g, stats, ind, col, e, metric=metric, tau=tau, packed=packed)),
+              timed(lambda: native.gumbel_reinmax_backward_codes(x, cb, g, stats, col, e, ws, metric=metric, tau=tau))]
+        line("vq_gumbel_reinmax_stats_f32 (2 contractions)", ts[0], 2 * mkd)
+        line("vq_gumbel_reinmax_columns_f32 (2 contractions)", ts[1], 2 * mkd)
+        line("vq_gumbel_reinmax_backward_x_f32 (3 contr.)", ts[2], 3 * mkd)
+        line("vq_gumbel_reinmax_backward_codes_f32 (3 c.)", ts[3], 3 * mkd)
+        line("the four reinmax sweeps (10 contractions)", sum(ts), 10 * mkd)
+        line("chunked path, reinmax, gx and gc (7 contr.)",
+             timed(lambda: gumbel._chunked_backward(x, cb, None, ind, g, metric, tau, True, True, True), n=2, warm=1), 7 * mkd)
 
 
 if __name__ == "__main__":
-    shape(262144, 1024, 256)
-    shape(65536, 8192, 64)
+    import argparse
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=2, help="rounds of (fused reinmax sweeps, chunked reinmax path)")
+    args = ap.parse_args()
+    shape(262144, 1024, 256, rounds=args.rounds)
+    shape(65536, 8192, 64, rounds=args.rounds)

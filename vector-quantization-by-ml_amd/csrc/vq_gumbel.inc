@@ -1,5 +1,5 @@
-// vq_gumbel.inc -- backward of the straight-through Gumbel softmax over the similarities (utils/general.py:147-149,
-// codebooks.py:386-395), nothing of [M, K] in memory.  Included by vq_kernels.hip (after vq_similarity.inc: shares its row
+// vq_gumbel.inc -- backward of the straight-through and of the reinmax Gumbel softmax over the similarities
+// (utils/general.py:131-149, codebooks.py:386-395), nothing of [M, K] in memory.  Included by vq_kernels.hip (after vq_similarity.inc: shares its row
 // prologue, the tile geometry and the fragment pipeline of the search).
 // ------------------------------------------------------------------------------------------------
 //   s = similarities [M, K]   g = dL/dquantize [M, D]   a = g c^T [M, K]   tau = 1 / temperature
@@ -20,10 +20,27 @@
 // Registers at Dp = 256: kGumX holds x fragments + g fragments + gradient accumulators (3 x 128) and compiles to 472 of the
 // 512 entries without scratch, so the dims are NOT split over workgroups (a split would repeat the two products per part);
 // kGumC holds 128 + 128.  One wave per SIMD from Dp = 128 on.
+//
+// Reinmax (utils/general.py:131-146) through the same sweep, four more roles.  With p0 = softmax_k(s),
+// p1 = max((onehot(ind) + softmax_k(tau s)) / 2, 1e-5), col_k = sum_m p1_mk, e_k = (sum_m p1_mk a_mk) / col_k and
+// delta0_m = sum_k p0_mk a_mk:   w = 2 (p1 / col)(a - e) - 0.5 p0 (a - delta0)
+//   kRmStats   as kGumStats with two online softmaxes over one running maximum (log2 e s; tau > 0 keeps the order of the
+//              logits) -> lse (at tau), lse1 (at 1) and delta = delta0
+//   kRmCol     the orientation of kGumC, the two products only: p1 from lse and the int32 copy of ind of the streamed row,
+//              per-lane sums of p1 and p1 a over the rows of the split -> partial col / e per blockIdx.z, added in split
+//              order by vq_gumbel_reduce_cols
+//   kRmX       as kGumX: the statistics and ind of the lane's row, col / e of the streamed codes read four at a time
+//   kRmC       as kGumC: the statistics and ind of the streamed rows read four at a time, col / e of the lane's code
+// ind is only ever compared with a code index.  Streamed padding is masked AFTER the clamp (p1 = 1e-5 there, not 0).
 // ------------------------------------------------------------------------------------------------
 constexpr int kGumStats = 0;
 constexpr int kGumX = 1;
 constexpr int kGumC = 2;
+constexpr int kRmStats = 3;
+constexpr int kRmCol = 4;
+constexpr int kRmX = 5;
+constexpr int kRmC = 6;
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 }  // namespace
 namespace vqi {
@@ -44,6 +61,15 @@ struct GumbelParams {
     float *out;  // gx (kGumX) / the partials of gc (kGumC)
     long long out_rs, out_hs, out_zs;
     int tiles_per_split;  // kGumC: streamed tiles per blockIdx.z
+    // reinmax roles (lse / delta above: the log-sum-exp at tau and delta0)
+    float *lse1;                   // [H][st_hs]: log2-domain log-sum-exp at temperature 1
+    const long long *ind;          // kRmX: the caller's selection, (h, m) at ind[h*ind_hs + m*ind_rs]
+    long long ind_rs, ind_hs;
+    const int *ind32;              // kRmCol / kRmC: [H][st_hs] int32 copy, -1 past M
+    float *col, *e;                // [H][ck_hs] per code (read by kRmX / kRmC)
+    long long ck_hs;
+    float *colp, *ep;              // kRmCol: partials [splits][H][ck_hs]
+    long long cp_zs;
 };
 }  // namespace vqi
 namespace {
@@ -84,8 +110,10 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     using GG = GumGeo<DP>;
     constexpr int RS = G::RS, RS4 = G::RS4, SUB = G::SUB, NG = DP / 8, V = GG::V, NJ = GG::NJ, NACC = GG::NACC;
     constexpr bool EUCLID = (METRIC == VQ_METRIC_EUCLID);
-    constexpr bool CODES = (ROLE == kGumC);
-    constexpr bool STATS = (ROLE == kGumStats);
+    constexpr bool CODES = (ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC);
+    constexpr bool RM = (ROLE >= kRmStats);
+    constexpr bool COLS = (ROLE == kRmCol);
+    constexpr bool STATS = (ROLE == kGumStats || ROLE == kRmStats || COLS);  // no contraction: no gradient accumulators
     constexpr int IMG_F4 = 2 * G::BUF_F4;  // the two tile buffers of one image
     constexpr float LOG2E = 1.4426950408889634f;
     const float INF = __builtin_inff();
@@ -124,12 +152,24 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
 
     // per resident row (kGumX): the statistics of this lane's row
     float lse_row = 0.0f, delta_row = 0.0f;
-    if (ROLE == kGumX && row_ok) {
+    if ((ROLE == kGumX || ROLE == kRmX) && row_ok) {
         lse_row = p.lse[st0 + row];
         delta_row = p.delta[st0 + row];
     }
+    // reinmax: kRmX the rest of the row's statistics and its selected code; kRmC the lane's own code's 1 / col and e
+    float lse1_row = 0.0f, rcol_own = 0.0f, e_own = 0.0f;
+    long long ind_row = -1;
+    if (ROLE == kRmX && row_ok) {
+        lse1_row = p.lse1[st0 + row];
+        ind_row = p.ind[(long long)head * p.ind_hs + row * p.ind_rs];
+    }
+    if (ROLE == kRmC && row_ok) {
+        rcol_own = __builtin_amdgcn_rcpf(p.col[(long long)head * p.ck_hs + row]);
+        e_own = p.e[(long long)head * p.ck_hs + row];
+    }
     // kGumStats: running max / sum of exp2 / sum of exp2 * a over the codes this lane has seen
-    float run_m = -INF, run_s = 0.0f, run_d = 0.0f;
+    // (kRmStats: run_m in units of log2 e s, run_s at tau, run_s1 and run_d at temperature 1; kRmCol: run_s = sum p1, run_d = sum p1 a)
+    float run_m = -INF, run_s = 0.0f, run_d = 0.0f, run_s1 = 0.0f;
 
     f32x16 gacc[STATS ? 1 : NACC];
 #pragma unroll
@@ -167,7 +207,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
             const long long sbase = (long long)u * kTileCodes + 4 * h;  // streamed row of this lane's register 0
             // kGumC: the statistics of the 16 streamed rows this lane's registers stand for (rows 8 g + 4 h + 0..3 of the sub-tile)
             f32x4 l4[4], d4[4];
-            if constexpr (CODES) {
+            if constexpr (CODES && !RM) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     l4[g] = *(const f32x4 *)(p.lse + st0 + sbase + 8 * g);
@@ -196,7 +236,88 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
             }
             // (the codebook image of the Euclid metric holds -2 c; the image of the g rows holds g)
             const float a_scale = (EUCLID && !CODES) ? -0.5f : 1.0f;
-            if constexpr (STATS) {
+            if constexpr (ROLE == kRmStats) {
+                float b[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float tv = acc[r];
+                    b[r] = EUCLID ? -LOG2E * __builtin_amdgcn_sqrtf(fmaxf(tv, 0.0f)) : LOG2E * tv;
+                    if (sbase + (r & 3) + 8 * (r >> 2) >= p.NS) b[r] = -INF;
+                }
+                float tm = b[0];
+#pragma unroll
+                for (int r = 1; r < 16; ++r) tm = fmaxf(tm, b[r]);
+                if (tm > run_m) {
+                    const float df = run_m - tm;  // -inf on the first visit: both factors 0
+                    const float sc1 = __builtin_amdgcn_exp2f(df);
+                    run_s *= __builtin_amdgcn_exp2f(p.tau * df);
+                    run_s1 *= sc1;
+                    run_d *= sc1;
+                    run_m = tm;
+                }
+                if (run_m > -INF) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float df = b[r] - run_m;
+                        const float e1 = __builtin_amdgcn_exp2f(df);
+                        run_s += __builtin_amdgcn_exp2f(p.tau * df);
+                        run_s1 += e1;
+                        run_d = fmaf(e1, a_scale * acca[r], run_d);
+                    }
+                }
+            } else if constexpr (RM) {
+                // ---- reinmax: p1, then the column sums (kRmCol) or acc[r] <- w / r in place (kRmX, kRmC); the per-streamed
+                // arrays are read four registers' worth at a time (rows / codes sbase + 8 g + 0..3)
+                float sum_u = 0.0f;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    f32x4 lt4 = {0}, l14 = {0}, dl4 = {0}, c4 = {0}, e4 = {0};
+                    i32x4 i4 = {0};
+                    if constexpr (CODES) {
+                        lt4 = *(const f32x4 *)(p.lse + st0 + sbase + 8 * g);
+                        i4 = *(const i32x4 *)(p.ind32 + st0 + sbase + 8 * g);
+                        if constexpr (!COLS) {
+                            l14 = *(const f32x4 *)(p.lse1 + st0 + sbase + 8 * g);
+                            dl4 = *(const f32x4 *)(p.delta + st0 + sbase + 8 * g);
+                        }
+                    } else {
+                        c4 = *(const f32x4 *)(p.col + (long long)head * p.ck_hs + sbase + 8 * g);
+                        e4 = *(const f32x4 *)(p.e + (long long)head * p.ck_hs + sbase + 8 * g);
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int r = 4 * g + q;
+                        const long long sidx = sbase + 8 * g + q;
+                        const bool pad = sidx >= p.NS;  // padding rows / codes of the streamed image
+                        const float tv = acc[r];
+                        const float av = a_scale * acca[r];
+                        const float tc = fmaxf(tv, 0.0f);
+                        const float dist = __builtin_amdgcn_sqrtf(tc);
+                        const float lse2 = CODES ? lt4[q] : lse_row;
+                        const float pt = __builtin_amdgcn_exp2f(EUCLID ? fmaf(dist, -tau2, -lse2) : fmaf(tv, tau2, -lse2));
+                        const bool hot = CODES ? ((long long)i4[q] == row) : (ind_row == sidx);
+                        const float p1 = fmaxf(0.5f * ((hot ? 1.0f : 0.0f) + pt), 1e-5f);
+                        if constexpr (COLS) {
+                            const float pm = pad ? 0.0f : p1;  // (the clamp made 1e-5 of a padding row)
+                            run_s += pm;
+                            run_d = fmaf(pm, pad ? 0.0f : av, run_d);
+                        } else {
+                            const float lse1 = CODES ? l14[q] : lse1_row;
+                            const float dl = CODES ? dl4[q] : delta_row;
+                            const float rc = CODES ? rcol_own : __builtin_amdgcn_rcpf(c4[q]);
+                            const float ek = CODES ? e_own : e4[q];
+                            const float p0 = __builtin_amdgcn_exp2f(EUCLID ? fmaf(dist, -LOG2E, -lse1) : fmaf(tv, LOG2E, -lse1));
+                            float v = (2.0f * p1 * rc) * (av - ek) - (0.5f * p0) * (av - dl);
+                            if (EUCLID) v = -v * __builtin_amdgcn_rsqf(tc);  // w / s with s = -dist; inf / nan at dist == 0
+                            if (!(__builtin_fabsf(v) < INF)) v = 0.0f;       // 1 / 0: ATen's subgradient 0
+                            if (pad) v = 0.0f;
+                            acc[r] = v;
+                            sum_u += v;
+                        }
+                    }
+                }
+                sum_ratio += sum_u;
+            } else if constexpr (STATS) {
                 float l[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -246,6 +367,8 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                     sum_u += v;
                 }
                 sum_ratio += sum_u;
+            }
+            if constexpr (!STATS) {
                 // ---- contraction: gacc[J*V + e][position i, resident row] += img[streamed row (r, half)][128 J + V i + e] * acc[r]
                 const float *trow = (const float *)tb + (4 * h) * RS + V * c;
                 if constexpr (V == 4) {
@@ -286,7 +409,31 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
         __syncthreads();  // next tile landed, everybody is done reading this one
     }
 
-    if constexpr (STATS) {
+    if constexpr (COLS) {
+        // the two lane halves hold the two halves of every sub-tile's rows; one partial per (split, code)
+        run_s += __shfl_xor(run_s, 32);
+        run_d += __shfl_xor(run_d, 32);
+        if (h == 0 && row_ok) {
+            const long long o = (long long)blockIdx.z * p.cp_zs + (long long)head * p.ck_hs + row;
+            p.colp[o] = run_s;
+            p.ep[o] = run_d;
+        }
+    } else if constexpr (ROLE == kRmStats) {
+        const float om = __shfl_xor(run_m, 32), os = __shfl_xor(run_s, 32), os1 = __shfl_xor(run_s1, 32), od = __shfl_xor(run_d, 32);
+        const float mm = fmaxf(run_m, om);  // lane half 0 always saw streamed row 0, so mm is finite
+        const bool mine = run_m > -INF, other = om > -INF;
+        const float w0 = mine ? __builtin_amdgcn_exp2f(run_m - mm) : 0.0f, w1 = other ? __builtin_amdgcn_exp2f(om - mm) : 0.0f;
+        const float t0 = mine ? __builtin_amdgcn_exp2f(p.tau * (run_m - mm)) : 0.0f;
+        const float t1 = other ? __builtin_amdgcn_exp2f(p.tau * (om - mm)) : 0.0f;
+        const float st = run_s * t0 + os * t1;
+        const float s1 = run_s1 * w0 + os1 * w1;
+        const float d = run_d * w0 + od * w1;
+        if (h == 0 && row_ok) {
+            p.lse[st0 + row] = fmaf(p.tau, mm, __builtin_amdgcn_logf(st));
+            p.lse1[st0 + row] = mm + __builtin_amdgcn_logf(s1);
+            p.delta[st0 + row] = d / s1;
+        }
+    } else if constexpr (STATS) {
         const float om = __shfl_xor(run_m, 32), os = __shfl_xor(run_s, 32), od = __shfl_xor(run_d, 32);
         const float mm = fmaxf(run_m, om);  // lane half 0 always saw streamed row 0, so mm is finite
         const float w0 = run_m > -INF ? __builtin_amdgcn_exp2f(run_m - mm) : 0.0f;
@@ -379,4 +526,38 @@ __global__ void __launch_bounds__(256) vq_gumbel_reduce_parts(const float *__res
     float s = parts[i];
     for (int z = 1; z < splits; ++z) s += parts[(long long)z * n + i];
     out[i] = s;
+}
+
+// the int32 copy of ind the codes-resident reinmax roles read 16 bytes at a time: [H][stride], -1 past M and for values no
+// code index can equal (the copy is only ever compared)
+__global__ void __launch_bounds__(256) vq_gumbel_pack_ind(const long long *__restrict__ ind, long long ind_rs, long long ind_hs, long long M,
+                                                          long long stride, int *__restrict__ out) {
+    const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (m >= stride) return;
+    int v = -1;
+    if (m < M) {
+        const long long i = ind[(long long)blockIdx.y * ind_hs + m * ind_rs];
+        if (i >= 0 && i <= 0x7FFFFFFFll) v = (int)i;
+    }
+    out[(long long)blockIdx.y * stride + m] = v;
+}
+
+// col[h][k] = colp[0] + colp[1] + ... and e[h][k] = (ep[0] + ep[1] + ...) / col in this order; 1 / 0 in the padding past K
+__global__ void __launch_bounds__(256) vq_gumbel_reduce_cols(const float *__restrict__ colp, const float *__restrict__ ep, long long n,
+                                                             long long stride, int K, int splits, float *__restrict__ col,
+                                                             float *__restrict__ e) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (i % stride >= K) {
+        col[i] = 1.0f;
+        e[i] = 0.0f;
+        return;
+    }
+    float cs = colp[i], es = ep[i];
+    for (int z = 1; z < splits; ++z) {
+        cs += colp[(long long)z * n + i];
+        es += ep[(long long)z * n + i];
+    }
+    col[i] = cs;
+    e[i] = es / cs;
 }

@@ -65,7 +65,7 @@
 //   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ, affine) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward
-//   7 Gumbel straight-through backward sweeps                                    8 Gumbel-max sampling sweeps
+//   7 Gumbel straight-through backward sweeps               8 Gumbel-max sampling sweeps + Gumbel reinmax backward sweeps
 #ifndef VQ_PART
 #define VQ_PART -1
 #endif
@@ -389,8 +389,10 @@ template <int DP, int METRIC, int ROLE>
 int launch_gumbel_t(const GumbelParams &p, int H, int gz, hipStream_t s) {
     using G = Geo<DP, 4>;
     using GG = GumGeo<DP>;
-    const size_t tile_floats = (size_t)(ROLE == kGumC ? 2 : 1) * 2 * G::BUF_F4 * 4, rows_floats = (size_t)4 * 32 * G::XS;
-    const size_t stage_floats = ROLE == kGumStats ? 0 : (size_t)4 * (32 * GG::GS + 32);
+    constexpr bool two_images = ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC;  // packed x rows and packed g rows
+    constexpr bool no_gradient = ROLE == kGumStats || ROLE == kRmStats || ROLE == kRmCol;
+    const size_t tile_floats = (size_t)(two_images ? 2 : 1) * 2 * G::BUF_F4 * 4, rows_floats = (size_t)4 * 32 * G::XS;
+    const size_t stage_floats = no_gradient ? 0 : (size_t)4 * (32 * GG::GS + 32);
     size_t floats = tile_floats > rows_floats ? tile_floats : rows_floats;
     if (stage_floats > floats) floats = stage_floats;
     return launch<vq_gumbel_sweep<DP, METRIC, ROLE>, kBigLds>(dim3((unsigned)((p.NR + 127) / 128), (unsigned)H, (unsigned)gz),
@@ -404,6 +406,18 @@ int launch_gumbel_m(int role, const GumbelParams &p, int H, int gz, int metric, 
         if (role == kGumStats) return launch_gumbel_t<DP, ME, kGumStats>(p, H, 1, s);
         if (role == kGumX) return launch_gumbel_t<DP, ME, kGumX>(p, H, 1, s);
         return launch_gumbel_t<DP, ME, kGumC>(p, H, gz, s);
+    });
+}
+
+// the reinmax roles of the same sweep: a build part of their own entry point
+template <int DP>
+int launch_reinmax_m(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s) {
+    return with_metric(metric, [&](auto m) {
+        constexpr int ME = decltype(m)::value;
+        if (role == kRmStats) return launch_gumbel_t<DP, ME, kRmStats>(p, H, 1, s);
+        if (role == kRmCol) return launch_gumbel_t<DP, ME, kRmCol>(p, H, gz, s);
+        if (role == kRmX) return launch_gumbel_t<DP, ME, kRmX>(p, H, 1, s);
+        return launch_gumbel_t<DP, ME, kRmC>(p, H, gz, s);
     });
 }
 
@@ -453,6 +467,11 @@ template <> int part_gumbel<32>(int role, const GumbelParams &p, int H, int gz, 
 template <> int part_gumbel<64>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <> int part_gumbel<128>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <> int part_gumbel<256>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <int DP> int part_reinmax(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <> int part_reinmax<32>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <> int part_reinmax<64>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <> int part_reinmax<128>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <> int part_reinmax<256>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 int part_pair(const SearchParams &p, int H, int splits, int metric, hipStream_t s);
 int part_persist(const SearchChoice &c, const SearchParams &p, int H, int cus, int metric, hipStream_t s);
 #define VQ_DECLARE_PARTS(DP)                                                                                         \
@@ -564,6 +583,13 @@ VQ_DEFINE_SAMPLE_PART(128)
 VQ_DEFINE_SAMPLE_PART(256)
 VQ_DEFINE_SAMPLE_PART(512)
 #undef VQ_DEFINE_SAMPLE_PART
+#define VQ_DEFINE_REINMAX_PART(DP) \
+    template <> int part_reinmax<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s) { return launch_reinmax_m<DP>(role, p, H, gz, metric, s); }
+VQ_DEFINE_REINMAX_PART(32)
+VQ_DEFINE_REINMAX_PART(64)
+VQ_DEFINE_REINMAX_PART(128)
+VQ_DEFINE_REINMAX_PART(256)
+#undef VQ_DEFINE_REINMAX_PART
 #endif
 }  // namespace vqi
 
@@ -1870,6 +1896,163 @@ int vq_gumbel_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs,
     if (rc || pl.splits == 1) return rc;
     return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
                                           pl.splits, grad_codes);
+}
+
+// ---- Gumbel reinmax backward (the kRm* roles of vq_gumbel.inc) --------------------------------------------------------
+// workspace: [x image H x img_floats][g image H x img_floats][ind int32 H x row_stride(M)]
+//            [col partials splits x H x row_stride(K)][e partials splits x H x row_stride(K)][gc partials splits x H x K x D, splits > 1]
+struct ReinmaxWorkspace {
+    GumbelCodesPlan pl;
+    long long ind_off, colp_off, ep_off, parts_off, floats;  // offsets in 4-byte units
+};
+static ReinmaxWorkspace reinmax_workspace(int H, long long M, int K, int D) {
+    ReinmaxWorkspace w;
+    w.pl = plan_gumbel_codes(H, M, K, D);
+    const long long ck = (long long)H * vq_gumbel_row_stride(K);
+    w.ind_off = 2 * (long long)H * w.pl.img_floats;
+    w.colp_off = w.ind_off + (long long)H * vq_gumbel_row_stride(M);
+    w.ep_off = w.colp_off + w.pl.splits * ck;
+    w.parts_off = w.ep_off + w.pl.splits * ck;
+    w.floats = w.parts_off + (w.pl.splits > 1 ? (long long)w.pl.splits * H * K * D : 0);
+    return w;
+}
+
+int64_t vq_gumbel_reinmax_workspace_bytes(int H, int64_t M, int K, int D) {
+    if (H <= 0 || M <= 0 || K <= 0 || D <= 0 || D > 256 || M > 0x7FFFFFFFll) return 0;
+    return 4 * reinmax_workspace(H, M, K, D).floats;
+}
+
+// what every reinmax entry checks and fills; `arrays`: the per-row and per-code arrays the entry uses (non-null, 16-byte aligned)
+static int fill_reinmax_params(GumbelParams &p, const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau,
+                               std::initializer_list<const void *> arrays) {
+    memset(&p, 0, sizeof(p));
+    if (!g) return fail(VQ_E_BADARG, "vq_gumbel_reinmax: g is null");
+    if (!(tau > 0.0f) || !(tau < __builtin_inff())) return fail(VQ_E_BADARG, "vq_gumbel_reinmax: tau must be positive and finite");
+    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, "vq_gumbel_reinmax: D > 256 (use row chunks of vq_similarities_f32)");
+    for (const void *q : arrays)  // (M == 0: no launch, the per-row arrays are empty)
+        if (a->M > 0 && (!q || !aligned16(q))) return fail(VQ_E_BADARG, "vq_gumbel_reinmax: a statistics array is null or not 16-byte aligned");
+    p.D = a->D;
+    p.tau = tau;
+    p.st_hs = vq_gumbel_row_stride(a->M);
+    p.ck_hs = vq_gumbel_row_stride(a->K);
+    p.g = g; p.g_rs = g_rs; p.g_hs = g_hs;
+    p.vec_g = vec4_ok(g, {a->D, g_rs, g_hs}) ? 1 : 0;
+    return 0;
+}
+
+static int launch_reinmax(int role, const GumbelParams &p, const vq_args *a, int gz, hipStream_t s) {
+    const int DP = padded_dim(a->D);
+    return with_padded_dim(DP == 512 ? 0 : DP,
+                           [&](auto dp) {
+                               constexpr int DPC = decltype(dp)::value;
+                               if constexpr (DPC <= 256) return vqi::part_reinmax<DPC>(role, p, a->H, gz, a->metric, s);
+                               else return fail(VQ_E_UNSUPPORTED, "vq_gumbel_reinmax: unsupported padded dim");
+                           },
+                           [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel_reinmax: unsupported padded dim"); });
+}
+
+// the codes-resident roles: the plan, the workspace and the images in it
+static int fill_reinmax_codes(GumbelParams &p, const vq_args *a, void *workspace, int64_t workspace_bytes, ReinmaxWorkspace &w) {
+    if (!a->cb) return fail(VQ_E_BADARG, "vq_gumbel_reinmax: cb is null");
+    if (a->M > 0x7FFFFFFFll) return fail(VQ_E_UNSUPPORTED, "vq_gumbel_reinmax: too many rows (use row chunks)");
+    w = reinmax_workspace(a->H, a->M, a->K, a->D);
+    if (w.pl.img_floats * 4 >= (1ll << 31)) return fail(VQ_E_UNSUPPORTED, "vq_gumbel_reinmax: packed row image >= 2 GiB (use row chunks)");
+    if (!workspace || !aligned16(workspace) || workspace_bytes < 4 * w.floats)
+        return fail(VQ_E_BADARG, "vq_gumbel_reinmax: workspace too small or misaligned (see vq_gumbel_reinmax_workspace_bytes)");
+    float *ws = (float *)workspace;
+    p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
+    p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
+    p.img = ws; p.gimg = ws + (long long)a->H * w.pl.img_floats;
+    p.img_hs = w.pl.img_floats; p.img_bytes = (unsigned)(w.pl.img_floats * 4);
+    p.ind32 = (const int *)(ws + w.ind_off);
+    p.NR = a->K; p.NS = a->M;
+    p.ntiles = w.pl.ntiles;
+    p.tiles_per_split = w.pl.tiles_per_split;
+    return 0;
+}
+
+int vq_gumbel_reinmax_stats_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, float *lse2_tau,
+                                float *lse2_one, float *delta0, void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    GumbelParams p;
+    if ((rc = fill_reinmax_params(p, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0}))) return rc;
+    if (a->M == 0) return 0;
+    if ((rc = fill_gumbel_rows(p, a))) return rc;
+    p.lse = lse2_tau; p.lse1 = lse2_one; p.delta = delta0;
+    return launch_reinmax(kRmStats, p, a, 1, (hipStream_t)stream);
+}
+
+int vq_gumbel_reinmax_columns_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
+                                  const int64_t *ind, int64_t ind_rs, int64_t ind_hs, float *col, float *e, void *workspace,
+                                  int64_t workspace_bytes, void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    GumbelParams p;
+    if ((rc = fill_reinmax_params(p, a, g, g_rs, g_hs, tau, {lse2_tau, col, e}))) return rc;
+    if (!ind) return fail(VQ_E_BADARG, "vq_gumbel_reinmax_columns: ind is null");
+    if (a->M == 0) return 0;
+    ReinmaxWorkspace w;
+    if ((rc = fill_reinmax_codes(p, a, workspace, workspace_bytes, w))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    float *ws = (float *)workspace;
+    if ((rc = launch<vq_gumbel_pack_rows>(dim3((unsigned)((w.pl.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
+                                          (long long)a->x_rs, (long long)a->x_hs, g, (long long)g_rs, (long long)g_hs, (long long)a->M, w.pl.Mp,
+                                          a->D, padded_dim(a->D), a->metric, ws, ws + (long long)a->H * w.pl.img_floats, w.pl.img_floats)))
+        return rc;
+    if ((rc = launch<vq_gumbel_pack_ind>(dim3((unsigned)((p.st_hs + 255) / 256), (unsigned)a->H), dim3(256), 0, s, "vq_gumbel_pack_ind launch",
+                                         (const long long *)ind, (long long)ind_rs, (long long)ind_hs, (long long)a->M, p.st_hs,
+                                         (int *)(ws + w.ind_off))))
+        return rc;
+    p.lse = (float *)lse2_tau;
+    p.colp = ws + w.colp_off; p.ep = ws + w.ep_off;
+    p.cp_zs = (long long)a->H * p.ck_hs;
+    if ((rc = launch_reinmax(kRmCol, p, a, w.pl.splits, s))) return rc;
+    return launch<vq_gumbel_reduce_cols>(dim3((unsigned)((p.cp_zs + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_cols launch",
+                                         (const float *)p.colp, (const float *)p.ep, p.cp_zs, p.ck_hs, a->K, w.pl.splits, col, e);
+}
+
+int vq_gumbel_reinmax_backward_x_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
+                                     const float *lse2_one, const float *delta0, const int64_t *ind, int64_t ind_rs, int64_t ind_hs,
+                                     const float *col, const float *e, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    GumbelParams p;
+    if ((rc = fill_reinmax_params(p, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0, col, e}))) return rc;
+    if (!ind || !grad_x) return fail(VQ_E_BADARG, "vq_gumbel_reinmax_backward_x: null argument (ind / grad_x)");
+    if (a->M == 0) return 0;
+    if ((rc = fill_gumbel_rows(p, a))) return rc;
+    p.lse = (float *)lse2_tau; p.lse1 = (float *)lse2_one; p.delta = (float *)delta0;
+    p.ind = (const long long *)ind; p.ind_rs = ind_rs; p.ind_hs = ind_hs;
+    p.col = (float *)col; p.e = (float *)e;
+    p.out = grad_x; p.out_rs = gx_rs; p.out_hs = gx_hs;
+    return launch_reinmax(kRmX, p, a, 1, (hipStream_t)stream);
+}
+
+int vq_gumbel_reinmax_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
+                                         const float *lse2_one, const float *delta0, const float *col, const float *e,
+                                         float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    GumbelParams p;
+    if ((rc = fill_reinmax_params(p, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0, col, e}))) return rc;
+    if (!grad_codes) return fail(VQ_E_BADARG, "vq_gumbel_reinmax_backward_codes: grad_codes is null");
+    hipStream_t s = (hipStream_t)stream;
+    const long long n = (long long)a->H * a->K * a->D;
+    if (a->M == 0) {
+        const hipError_t err = hipMemsetAsync(grad_codes, 0, (size_t)n * 4, s);
+        return err == hipSuccess ? 0 : hip_fail(err, "vq_gumbel_reinmax_backward_codes memset");
+    }
+    ReinmaxWorkspace w;
+    if ((rc = fill_reinmax_codes(p, a, workspace, workspace_bytes, w))) return rc;
+    float *parts = (float *)workspace + w.parts_off;
+    p.lse = (float *)lse2_tau; p.lse1 = (float *)lse2_one; p.delta = (float *)delta0;
+    p.col = (float *)col; p.e = (float *)e;
+    p.out = w.pl.splits > 1 ? parts : grad_codes;
+    p.out_rs = a->D; p.out_hs = (long long)a->K * a->D; p.out_zs = n;
+    if ((rc = launch_reinmax(kRmC, p, a, w.pl.splits, s)) || w.pl.splits == 1) return rc;
+    return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
+                                          w.pl.splits, grad_codes);
 }
 
 int vq_max_fused_stages(int D, int want_sq_err) {

@@ -18,9 +18,12 @@ and it reaches ``x`` and the codes through the similarity's own backward (``loss
 requires grad also receives the ordinary gradient of the gather, ``scatter_add(ind, g)``.
 
 Straight-through on fp32 rows of up to 256 dims is three native sweeps (``vq_gumbel_*``: row statistics, d/dx, d/dcodes),
-none of which writes anything of ``[M, K]``.  Everything else -- reinmax (its column normalisation needs all rows of the
-head: three chunked passes), wider rows, backends without the kernels, the live-codes quirk of an EMA step between forward
-and backward -- runs on bounded row chunks of the similarity matrix, like the cross-entropy backward.
+none of which writes anything of ``[M, K]``.  Reinmax on the same rows is four (``vq_gumbel_reinmax_*``): row statistics
+(both log-sum-exps and delta0), column statistics (``col_k = sum_m p1_mk`` and ``e_k``: the normalisation over the rows of
+the head, summed per row split and added in split order), d/dx and d/dcodes; the selection ``ind`` is an input that the
+kernels only compare with code indices.  Everything else -- wider rows, backends without the kernels, the live-codes quirk
+of an EMA step between forward and backward -- runs on bounded row chunks of the similarity matrix, like the cross-entropy
+backward (reinmax there: three chunked passes).
 """
 from __future__ import annotations
 
@@ -100,9 +103,12 @@ class _RelaxedGatherFn(torch.autograd.Function):
         g = g.to(torch.float32)
         backend = search.get_backend()
         grads = None
-        fused = getattr(backend, "gumbel_backward", None)
-        if fused is not None and not ctx.reinmax and ctx.live is None:  # (None: outside the kernels' range, D > 256)
-            grads = fused(x, codes, g, metric=ctx.metric, tau=ctx.tau, need_x=need_x, need_codes=need_c)
+        fused = getattr(backend, "reinmax_backward" if ctx.reinmax else "gumbel_backward", None)
+        if fused is not None and ctx.live is None:  # (None: outside the kernels' range, D > 256)
+            if ctx.reinmax:
+                grads = fused(x, codes, g, ind, metric=ctx.metric, tau=ctx.tau, need_x=need_x, need_codes=need_c)
+            else:
+                grads = fused(x, codes, g, metric=ctx.metric, tau=ctx.tau, need_x=need_x, need_codes=need_c)
         if grads is None:
             grads = _chunked_backward(x, codes, ctx.live, ind, g, ctx.metric, ctx.tau, ctx.reinmax, need_x, need_c)
         gx, gc = grads

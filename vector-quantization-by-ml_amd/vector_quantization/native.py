@@ -155,6 +155,19 @@ def load():
         lib.vq_gumbel_backward_x_f32.restype = ctypes.c_int
         lib.vq_gumbel_backward_codes_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _vp]
         lib.vq_gumbel_backward_codes_f32.restype = ctypes.c_int
+        lib.vq_gumbel_reinmax_workspace_bytes.argtypes = [ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int]
+        lib.vq_gumbel_reinmax_workspace_bytes.restype = _i64
+        lib.vq_gumbel_reinmax_stats_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp]
+        lib.vq_gumbel_reinmax_stats_f32.restype = ctypes.c_int
+        lib.vq_gumbel_reinmax_columns_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
+                                                      _i64, _vp]
+        lib.vq_gumbel_reinmax_columns_f32.restype = ctypes.c_int
+        lib.vq_gumbel_reinmax_backward_x_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _i64,
+                                                         _vp, _vp, _vp, _i64, _i64, _vp]
+        lib.vq_gumbel_reinmax_backward_x_f32.restype = ctypes.c_int
+        lib.vq_gumbel_reinmax_backward_codes_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                             _vp, _i64, _vp]
+        lib.vq_gumbel_reinmax_backward_codes_f32.restype = ctypes.c_int
         lib.vq_gumbel_sample_f32.argtypes = [ap, ctypes.c_float, _vp, _vp]
         lib.vq_gumbel_sample_f32.restype = ctypes.c_int
         lib.vq_gumbel_noise_f32.argtypes = [_vp, ctypes.c_int, _i64, ctypes.c_int, _vp, _vp, _vp]
@@ -229,6 +242,8 @@ EXPORTED_SYMBOLS = (
     "vq_lq_workspace_bytes", "vq_lq_quantize_f32", "vq_lq_backward_f32",
     "vq_gumbel_row_stride", "vq_gumbel_workspace_bytes", "vq_gumbel_stats_f32", "vq_gumbel_backward_x_f32",
     "vq_gumbel_backward_codes_f32", "vq_gumbel_sample_f32", "vq_gumbel_noise_f32",
+    "vq_gumbel_reinmax_workspace_bytes", "vq_gumbel_reinmax_stats_f32", "vq_gumbel_reinmax_columns_f32",
+    "vq_gumbel_reinmax_backward_x_f32", "vq_gumbel_reinmax_backward_codes_f32",
     "vq_affine_stats_workspace_bytes", "vq_affine_stats_f32", "vq_affine_apply_f32",
 )
 
@@ -776,6 +791,121 @@ def gumbel_backward_codes(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, ls
         _check(load().vq_gumbel_backward_codes_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(),
                                                    delta.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws.numel() * 8,
                                                    _stream_ptr(x.device)), "vq_gumbel_backward_codes_f32")
+    return gc
+
+
+def _codes_args(x, cb, g, metric):
+    """vq_args of the codes-resident Gumbel sweeps (a->x rows, a->cb the natural codebook) and the strides of g."""
+    _require_gpu(x, cb, g)
+    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and g.dtype == torch.float32
+    assert x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous() and tuple(g.shape) == tuple(x.shape)
+    H, M, D = x.shape
+    K = cb.shape[1]
+    assert cb.shape[0] == H and cb.shape[2] == D and gumbel_codes_supported(H, M, K, D)
+    x_rs, x_hs = _row_strides(x)
+    g_rs, g_hs = _row_strides(g)
+    a = VqArgs()
+    a.H, a.Q, a.M, a.K, a.D, a.metric, a.flags = H, 1, M, K, D, metric, 0
+    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
+    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), K * D, 0
+    return a, g_rs, g_hs
+
+
+def _check_stat_arrays(x, n, *arrays):
+    stride = int(load().vq_gumbel_row_stride(n))
+    for t in arrays:
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (x.shape[0], stride) and t.device == x.device
+
+
+def _check_ind(x, ind):
+    _require_gpu(ind)
+    assert ind.dtype == torch.int64 and tuple(ind.shape) == tuple(x.shape[:2]) and ind.device == x.device
+    return (int(ind.stride(1)) if ind.shape[1] > 1 else 1), int(ind.stride(0))
+
+
+def gumbel_reinmax_stats(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, *, metric: int = EUCLID, tau: float = 1.0,
+                         packed: torch.Tensor | None = None):
+    """Row statistics of the reinmax Gumbel backward in one sweep: x, g [H, M, D] (strided rows ok), cb [H, K, D] ->
+    (lse2_tau, lse2_one, delta0), each [H, vq_gumbel_row_stride(M)] (columns past M unused): the log2-domain log-sum-exp of
+    the similarities at tau and at 1, and delta0 = sum_k softmax_k(sim) * (g . c_k)."""
+    a, packed, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
+    stride = int(load().vq_gumbel_row_stride(a.M))
+    out = [torch.empty((a.H, stride), dtype=torch.float32, device=x.device) for _ in range(3)]
+    with torch.cuda.device(x.device):
+        _check(load().vq_gumbel_reinmax_stats_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), out[0].data_ptr(),
+                                                  out[1].data_ptr(), out[2].data_ptr(), _stream_ptr(x.device)),
+               "vq_gumbel_reinmax_stats_f32")
+    return tuple(out)
+
+
+def gumbel_reinmax_workspace(x: torch.Tensor, K: int) -> torch.Tensor:
+    """The workspace gumbel_reinmax_columns fills and gumbel_reinmax_backward_codes reuses (vq_gumbel_reinmax_workspace_bytes)."""
+    H, M, D = x.shape
+    with torch.cuda.device(x.device):
+        nbytes = int(load().vq_gumbel_reinmax_workspace_bytes(H, M, K, D))
+    assert nbytes > 0, "vq_gumbel_reinmax: unsupported shape"
+    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=x.device)
+
+
+def gumbel_reinmax_columns(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, lse2_tau: torch.Tensor, ind: torch.Tensor, *,
+                           metric: int = EUCLID, tau: float = 1.0, workspace: torch.Tensor | None = None):
+    """Column statistics of the reinmax Gumbel backward: ind [H, M] int64 (any selection, only compared with code indices) ->
+    (col, e, workspace), col / e [H, vq_gumbel_row_stride(K)]: col_k = sum_m p1_mk, e_k = sum_m p1_mk (g_m . c_k) / col_k.
+    The workspace then holds the packed rows and the int32 selection gumbel_reinmax_backward_codes reuses.  Atomics-free."""
+    a, g_rs, g_hs = _codes_args(x, cb, g, metric)
+    _check_stat_arrays(x, a.M, lse2_tau)
+    i_rs, i_hs = _check_ind(x, ind)
+    if workspace is None:
+        workspace = gumbel_reinmax_workspace(x, a.K)
+    stride = int(load().vq_gumbel_row_stride(a.K))
+    col = torch.empty((a.H, stride), dtype=torch.float32, device=x.device)
+    e = torch.empty((a.H, stride), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(load().vq_gumbel_reinmax_columns_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2_tau.data_ptr(),
+                                                    ind.data_ptr(), i_rs, i_hs, col.data_ptr(), e.data_ptr(),
+                                                    workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                                    _stream_ptr(x.device)), "vq_gumbel_reinmax_columns_f32")
+    return col, e, workspace
+
+
+def gumbel_reinmax_backward_x(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, stats, ind: torch.Tensor, col: torch.Tensor,
+                              e: torch.Tensor, *, metric: int = EUCLID, tau: float = 1.0, packed: torch.Tensor | None = None,
+                              out: torch.Tensor | None = None) -> torch.Tensor:
+    """d/dx of the reinmax Gumbel softmax through the similarities, one fused sweep -> gx [H, M, D] (``out``: a destination
+    with strided rows).  ``stats``: the triple of gumbel_reinmax_stats; col / e: of gumbel_reinmax_columns."""
+    a, packed, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
+    H, M, D = x.shape
+    _check_stat_arrays(x, M, *stats)
+    _check_stat_arrays(x, a.K, col, e)
+    i_rs, i_hs = _check_ind(x, ind)
+    if out is None:
+        out = torch.empty((H, M, D), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (H, M, D) and out.device == x.device
+    o_rs, o_hs = _row_strides(out)
+    with torch.cuda.device(x.device):
+        _check(load().vq_gumbel_reinmax_backward_x_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), stats[0].data_ptr(),
+                                                       stats[1].data_ptr(), stats[2].data_ptr(), ind.data_ptr(), i_rs, i_hs,
+                                                       col.data_ptr(), e.data_ptr(), out.data_ptr(), o_rs, o_hs,
+                                                       _stream_ptr(x.device)), "vq_gumbel_reinmax_backward_x_f32")
+    return out
+
+
+def gumbel_reinmax_backward_codes(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, stats, col: torch.Tensor, e: torch.Tensor,
+                                  workspace: torch.Tensor, *, metric: int = EUCLID, tau: float = 1.0) -> torch.Tensor:
+    """d/dcodes of the reinmax Gumbel softmax through the similarities -> [H, K, D] (the gather's own scatter term is
+    ema_accumulate of g).  ``workspace``: the one gumbel_reinmax_columns returned for the same x, g and ind (its packed rows
+    and selection are reused).  Atomics-free: bit-identical from run to run on one device."""
+    a, g_rs, g_hs = _codes_args(x, cb, g, metric)
+    _check_stat_arrays(x, a.M, *stats)
+    _check_stat_arrays(x, a.K, col, e)
+    _require_gpu(workspace)
+    gc = torch.empty((a.H, a.K, a.D), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(load().vq_gumbel_reinmax_backward_codes_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau),
+                                                           stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(),
+                                                           col.data_ptr(), e.data_ptr(), gc.data_ptr(), workspace.data_ptr(),
+                                                           workspace.numel() * workspace.element_size(), _stream_ptr(x.device)),
+               "vq_gumbel_reinmax_backward_codes_f32")
     return gc
 
 

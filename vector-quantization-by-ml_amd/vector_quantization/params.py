@@ -38,7 +38,9 @@ class GumbelParams:
     """Options of the code selection: deterministic argmax (native, bit-exact) or stochastic Gumbel-max sampling (one native
     sweep with counter-based noise, seeded from torch's generator on the device).  ``straight_through`` (optionally with ``reinmax``) keeps the argmax selection and its value
     and adds the reference's gradient through ``softmax(similarities / temperature)`` to the encoder and to a learnable
-    codebook; it is active at ``temperature > 0`` with ``training`` while the module is in train mode (gumbel.py).
+    codebook; it is active at ``temperature > 0`` with ``training`` while the module is in train mode (gumbel.py).  On fp32
+    rows of up to 256 dims both gradients are fused native sweeps (three for straight-through, four for ``reinmax``); wider
+    rows run on bounded row chunks.
     ``reinmax`` needs ``straight_through``; ``stochastic`` together with ``straight_through`` raises NotImplementedError."""
 
     temperature: float = 1.0

@@ -181,6 +181,27 @@ class _NativeBackend:
         gc = native.gumbel_backward_codes(x, cb, g, lse2, delta, metric=metric, tau=tau) if need_codes else None
         return gx, gc
 
+    @staticmethod
+    def reinmax_backward(x, cb, g, ind, *, metric, tau, need_x=True, need_codes=True):
+        """Fused backward of the reinmax Gumbel softmax through the similarities: (gx | None, gc_sim | None) from
+        vq_gumbel_reinmax_stats_f32, vq_gumbel_reinmax_columns_f32 (the normalisation over the rows of a head) and
+        vq_gumbel_reinmax_backward_x_f32 / vq_gumbel_reinmax_backward_codes_f32; ``ind`` [H, M] int64 is the selection the
+        forward made (any selection: it is only compared with code indices).  None when the shape is outside the kernels'
+        range (the caller then works on row chunks)."""
+        H, M, D = x.shape
+        K = cb.shape[1]
+        if D > native.GUMBEL_MAX_DIM or M == 0 or not native.gumbel_codes_supported(H, M, K, D):
+            return None
+        cb = cb.contiguous()
+        if g.stride(-1) != 1 and g.shape[-1] != 1:
+            g = g.contiguous()
+        packed = native.pack_codebooks(cb, metric)
+        stats = native.gumbel_reinmax_stats(x, cb, g, metric=metric, tau=tau, packed=packed)
+        col, e, ws = native.gumbel_reinmax_columns(x, cb, g, stats[0], ind, metric=metric, tau=tau)
+        gx = native.gumbel_reinmax_backward_x(x, cb, g, stats, ind, col, e, metric=metric, tau=tau, packed=packed) if need_x else None
+        gc = native.gumbel_reinmax_backward_codes(x, cb, g, stats, col, e, ws, metric=metric, tau=tau) if need_codes else None
+        return gx, gc
+
 
 _backend = _NativeBackend
 
