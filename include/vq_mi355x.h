@@ -450,6 +450,35 @@ int vq_fsq_decode_f32(const void *idx, int idx_64, int64_t N, int Q, int d, cons
                       int drop_null, float *codes_sum, float *all_codes, void *stream);
 
 /*
+ * vq_decode_f32 -- indices -> code vectors for VectorQuantize / ResidualVQ / GroupedResidualVQ in one pass: the gather of
+ *   every stage's code and their sum, with nothing of [Q][N][D] in between (replaces vector_quantize_pytorch.py:156-180,
+ *   residual_vq.py:94-132,293-305: Q gathers, a masked_fill over [Q][N][D] and a reduce over it again).
+ *   Code (g, q, k) is cb[g * cb_gs + q * cb_qs + k * D + d] (cb_qs = 0: all stages share one codebook; cb_gs = 0: all
+ *   groups do).  Index (g, n, q), q < Q_given <= Q, is idx[g * idx_gs + n * idx_rs + q * idx_qs] (int32, or int64 when
+ *   idx_64; strides in elements, so a [.., :Q_given] view of a wider tensor is read in place); the stages q >= Q_given are
+ *   dropped.  With t_q = the code of stage q, or +0.0 when the stage is dropped:
+ *     all_codes[q * all_qs + g * all_gs + n * all_rs + d] = t_q                       (a bit copy of the codebook row)
+ *     codes_sum[g * sum_gs + n * sum_rs + d * sum_ds]     = ((0 + t_0) + t_1) + ...   (one fp32 add per stage, stage order:
+ *                                                            the order of vq_quantize_f32's `out`)
+ *   Either output may be NULL, not both.  The strides let one call write a multi-head result already concatenated on the
+ *   feature axis (sum_gs = D, sum_rs = G * D) or a channel-first result (sum_ds = the positions of a sample, sum_rs = 1,
+ *   the samples on the group axis with cb_gs = 0).
+ *   Index rule: drop_null = 1 (ResidualVQ, residual_vq.py:108-121): any i < 0 is a dropped stage.  drop_null = 0 (ATen's
+ *   indexing, vector_quantize_pytorch.py:161): i in [-K, -1] means i + K.  In both, an index outside the valid range never
+ *   becomes an address; it contributes +0.0 (ATen raises a device-side assert there: validating would cost the host a
+ *   synchronisation).  A dropped stage's code is not read into the result: a NaN in code 0 does not leak.
+ *   No host read, no allocation: the call can be captured in a hipGraph.  N == 0 returns 0 without a launch.
+ * Errors (VQ_E_BADARG, vq_last_error; the device is not touched): cb or idx NULL, both outputs NULL, G, Q, K or D not
+ *   positive, N negative, Q_given outside [1, Q], G * N * D beyond int64.
+ */
+int vq_decode_f32(const float *cb, int64_t cb_gs, int64_t cb_qs, int G, int Q, int K, int D,
+                  const void *idx, int idx_64, int64_t idx_gs, int64_t idx_rs, int64_t idx_qs, int64_t N, int Q_given,
+                  int drop_null,
+                  float *codes_sum, int64_t sum_gs, int64_t sum_rs, int64_t sum_ds,   /* may be NULL; sum_ds != 1: channel-first */
+                  float *all_codes, int64_t all_qs, int64_t all_gs, int64_t all_rs,   /* may be NULL */
+                  void *stream);
+
+/*
  * vq_lq_quantize_f32 -- latent quantization (LatentQuantize): the per-dimension level search of every (batch, position,
  *   codebook) sub-row in one pass, one thread per sub-row of d <= 16 values.  Element i of sub-row (b, p, c) is
  *   z[b * z_bs + p * z_ps + (c * d + i) * z_cs] (strides in elements: a channel-first [B][C * d][P] tensor is z_ps = 1,

@@ -42,10 +42,12 @@
 //                        fused squared-error loss and its backward
 //   vq_affine.inc        affine re-parameterisation: one-read column mean / squared deviations (Welford lanes, Chan merges),
 //                        the moment-matching transform of the codes and of the accumulated EMA sums
-//   this file            host-side dispatch and the C ABI (include/vq_mi355x.h)
+//   vq_decode.inc        indices -> code vectors: every stage's gather and their stage-ordered sum in one pass (vq_decode_f32)
+//   this file           host-side dispatch and the C ABI (include/vq_mi355x.h)
 //
 // Reference lines replaced (relative to the reference root): vector_quantization/codebooks.py:386-397,
-// utils/general.py:126-136,159-163, vector_quantize_pytorch.py:261-279,361-364, residual_vq.py:212-243.
+// utils/general.py:126-136,159-163, vector_quantize_pytorch.py:261-279,361-364, residual_vq.py:212-243; the decode side
+// (vq_decode.inc): vector_quantize_pytorch.py:156-180, residual_vq.py:94-132,293-305.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,7 +64,7 @@
 // the same file once per part (-DVQ_PART=n, in parallel) and links the objects: every part sees the same templates, but only
 // its own launchers are defined -- and with them instantiated -- there; the other parts call them through the
 // vqi::part_* entry points declared below.
-//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ, affine) 4 search Dp = 512 + wave-pair kernel
+//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ, affine, decode) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward
 //   7 Gumbel straight-through backward sweeps               8 Gumbel-max sampling sweeps + Gumbel reinmax backward sweeps
@@ -95,6 +97,7 @@ namespace {
 #include "vq_fsq.inc"
 #include "vq_lq.inc"
 #include "vq_affine.inc"
+#include "vq_decode.inc"
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -2193,6 +2196,27 @@ int vq_fsq_decode_f32(const void *idx, int idx_64, int64_t N, int Q, int d, cons
     hipStream_t s = (hipStream_t)stream;
     return fsq_launch_decode(d, dim3((unsigned)fsq_blocks(N)), s, "vq_fsq_decode launch", idx, idx_64 != 0, N, Q, lv, scales, drop_null != 0, codes_sum,
                              all_codes);
+}
+
+int vq_decode_f32(const float *cb, int64_t cb_gs, int64_t cb_qs, int G, int Q, int K, int D, const void *idx, int idx_64,
+                  int64_t idx_gs, int64_t idx_rs, int64_t idx_qs, int64_t N, int Q_given, int drop_null, float *codes_sum,
+                  int64_t sum_gs, int64_t sum_rs, int64_t sum_ds, float *all_codes, int64_t all_qs, int64_t all_gs,
+                  int64_t all_rs, void *stream) {
+    if (!cb || !idx) return fail(VQ_E_BADARG, "vq_decode: cb or idx is null");
+    if (!codes_sum && !all_codes) return fail(VQ_E_BADARG, "vq_decode: both outputs are null");
+    if (G <= 0 || Q <= 0 || K <= 0 || D <= 0 || N < 0) return fail(VQ_E_BADARG, "vq_decode: non-positive size");
+    if (Q_given < 1 || Q_given > Q) return fail(VQ_E_BADARG, "vq_decode: Q_given must be in [1, Q]");
+    if (N > INT64_MAX / D || N * D > INT64_MAX / G) return fail(VQ_E_BADARG, "vq_decode: too many elements");
+    if (N == 0) return 0;
+    DecodeParams p;
+    memset(&p, 0, sizeof(p));
+    p.cb = cb; p.cb_gs = cb_gs; p.cb_qs = cb_qs;
+    p.G = G; p.Q = Q; p.K = K; p.D = D;
+    p.idx = idx; p.idx64 = idx_64 != 0; p.idx_gs = idx_gs; p.idx_rs = idx_rs; p.idx_qs = idx_qs;
+    p.N = N; p.Qg = Q_given; p.drop_null = drop_null != 0;
+    p.sum = codes_sum; p.sum_gs = sum_gs; p.sum_rs = sum_rs; p.sum_ds = sum_ds;
+    p.all = all_codes; p.all_qs = all_qs; p.all_gs = all_gs; p.all_rs = all_rs;
+    return decode_launch(p, device_cus(), (hipStream_t)stream);
 }
 
 int64_t vq_lq_workspace_bytes(int64_t B, int64_t P, int C) {

@@ -214,6 +214,10 @@ def load():
         lib.vq_fsq_decode_f32.argtypes = [_vp, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp,
                                           _vp]
         lib.vq_fsq_decode_f32.restype = ctypes.c_int
+        lib.vq_decode_f32.argtypes = [_vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
+                                      _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _i64,
+                                      _i64, _vp]
+        lib.vq_decode_f32.restype = ctypes.c_int
         lib.vq_lq_workspace_bytes.argtypes = [_i64, _i64, ctypes.c_int]
         lib.vq_lq_workspace_bytes.restype = _i64
         lib.vq_lq_quantize_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64,
@@ -245,6 +249,7 @@ EXPORTED_SYMBOLS = (
     "vq_gumbel_reinmax_workspace_bytes", "vq_gumbel_reinmax_stats_f32", "vq_gumbel_reinmax_columns_f32",
     "vq_gumbel_reinmax_backward_x_f32", "vq_gumbel_reinmax_backward_codes_f32",
     "vq_affine_stats_workspace_bytes", "vq_affine_stats_f32", "vq_affine_apply_f32",
+    "vq_decode_f32",
 )
 
 
@@ -1366,6 +1371,55 @@ def fsq_decode(indices: torch.Tensor, levels, scales: torch.Tensor, *, drop_null
                                      codes_sum.data_ptr() if codes_sum is not None else None,
                                      all_codes.data_ptr() if all_codes is not None else None, _stream_ptr(dev)),
                "vq_fsq_decode_f32")
+    return codes_sum, all_codes
+
+
+# ------------------------------------------------------------------------------------------------
+# indices -> code vectors (vq_decode_f32 in include/vq_mi355x.h)
+# ------------------------------------------------------------------------------------------------
+def decode_codes(cb: torch.Tensor, indices: torch.Tensor, *, num_stages: int | None = None, drop_null: bool = True,
+                 want_sum: bool = True, want_all: bool = False, sum_out: torch.Tensor | None = None,
+                 all_out: torch.Tensor | None = None):
+    """cb [G | 1, Q | 1, K, D] fp32 (each [K, D] table contiguous, any group / stage strides; a size-1 group or stage axis
+    is shared by all groups / by ``num_stages`` stages), indices [G, N, Qg] int32 / int64 of any strides (Qg <= Q: the
+    later stages are dropped) -> (codes_sum [G, N, D] or None, all_codes [Q, G, N, D] or None).
+
+    ``drop_null``: any index < 0 is a dropped stage (+0.0); otherwise ATen's rule, [-K, -1] wraps.  An index outside the
+    valid range contributes +0.0 in both (it is never dereferenced).  codes_sum is ((0 + t_0) + t_1) + ... in fp32.
+    ``sum_out`` ([G, N, D] view, ANY strides: a channel-first or head-concatenated destination) and ``all_out``
+    ([Q, G, N, D] view, last dim contiguous) are written in place when given."""
+    _require_gpu(cb, indices, sum_out, all_out)
+    lib = load()
+    assert cb.dim() == 4 and cb.dtype == torch.float32, "cb must be [G, Q, K, D] fp32"
+    assert indices.dim() == 3 and indices.dtype in (torch.int32, torch.int64), "indices must be [G, N, Qg] int32 / int64"
+    G, N, Qg = indices.shape
+    Gc, Qc, K, D = cb.shape
+    Q = int(num_stages) if num_stages is not None else Qc
+    assert Gc in (1, G) and Qc in (1, Q) and 1 <= Qg <= Q, "cb / indices / num_stages do not fit together"
+    if (cb.stride(3) != 1 and D != 1) or (cb.stride(2) != D and K != 1):
+        cb = cb.contiguous()
+    cb_gs = int(cb.stride(0)) if Gc == G and G > 1 else 0
+    cb_qs = int(cb.stride(1)) if Qc == Q and Q > 1 else 0
+    dev = cb.device
+    codes_sum = all_codes = None
+    if want_sum:
+        codes_sum = sum_out if sum_out is not None else torch.empty((G, N, D), dtype=torch.float32, device=dev)
+        assert codes_sum.dtype == torch.float32 and tuple(codes_sum.shape) == (G, N, D)
+    if want_all:
+        all_codes = all_out if all_out is not None else torch.empty((Q, G, N, D), dtype=torch.float32, device=dev)
+        assert all_codes.dtype == torch.float32 and tuple(all_codes.shape) == (Q, G, N, D)
+        assert all_codes.stride(3) == 1 or D == 1, "all_out: last dim must be contiguous"
+    assert want_sum or want_all, "nothing requested"
+    if N == 0:
+        return codes_sum, all_codes
+    s = (0, 0, 1) if codes_sum is None else tuple(int(v) for v in codes_sum.stride())
+    a = (0, 0, 0) if all_codes is None else tuple(int(v) for v in all_codes.stride()[:3])
+    with torch.cuda.device(dev):
+        _check(lib.vq_decode_f32(cb.data_ptr(), cb_gs, cb_qs, G, Q, K, D, indices.data_ptr(), int(indices.dtype == torch.int64),
+                                 int(indices.stride(0)), int(indices.stride(1)), int(indices.stride(2)), N, Qg, int(drop_null),
+                                 codes_sum.data_ptr() if codes_sum is not None else None, *s,
+                                 all_codes.data_ptr() if all_codes is not None else None, *a, _stream_ptr(dev)),
+               "vq_decode_f32")
     return codes_sum, all_codes
 
 

@@ -13,6 +13,8 @@ instead of breaking the graph at an opaque Python call:
         (residual LFQ, native.rlfq_* and native.lfq_entropy_staged_*)
     torch.ops.vq_mi355x.fsq_quantize / fsq_backward / fsq_decode   (finite scalar quantization, native.fsq_*)
     torch.ops.vq_mi355x.lq_quantize / lq_backward   (latent quantization, native.lq_*)
+    torch.ops.vq_mi355x.decode_codes(cb, indices, num_stages, drop_null, want_sum, want_all) -> (codes_sum, all_codes)
+        (indices -> code vectors, native.decode_codes; differentiable with respect to cb)
 
 Eager forwards keep calling ``native.quantize`` directly (a custom-op dispatch costs tens of microseconds of host time,
 which is most of a small launch); the modules switch to these ops only while being compiled
@@ -228,6 +230,46 @@ def _(indices, levels, scales, drop_null, want_sum, want_all):
     N, Q = indices.shape
     d = len(levels)
     return scales.new_empty((N, d) if want_sum else (0,)), scales.new_empty((Q, N, d) if want_all else (0,))
+
+
+# indices -> code vectors (native.decode_codes).  An output that was not requested comes back as an empty tensor.
+@torch.library.custom_op(f"{_LIB_NS}::decode_codes", mutates_args=())
+def decode_codes(cb: torch.Tensor, indices: torch.Tensor, num_stages: int, drop_null: bool, want_sum: bool,
+                 want_all: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """cb [G | 1, Q | 1, K, D], indices [G, N, Qg] -> (codes summed over the stages [G, N, D] (or empty), all codes
+    [Q, G, N, D] (or empty))."""
+    codes_sum, all_codes = native.decode_codes(cb, indices, num_stages=num_stages, drop_null=drop_null, want_sum=want_sum,
+                                               want_all=want_all)
+    if codes_sum is None:
+        codes_sum = cb.new_empty((0,))
+    if all_codes is None:
+        all_codes = cb.new_empty((0,))
+    return codes_sum, all_codes
+
+
+@decode_codes.register_fake
+def _(cb, indices, num_stages, drop_null, want_sum, want_all):
+    G, N, _ = indices.shape
+    D = cb.shape[-1]
+    return cb.new_empty((G, N, D) if want_sum else (0,)), cb.new_empty((num_stages, G, N, D) if want_all else (0,))
+
+
+def _decode_setup(ctx, inputs, output):
+    cb, indices, _num_stages, drop_null, want_sum, want_all = inputs
+    ctx.save_for_backward(indices)
+    ctx.cb_shape, ctx.drop_null, ctx.want = tuple(cb.shape), drop_null, (want_sum, want_all)
+
+
+def _decode_backward(ctx, g_sum, g_all):
+    from .search import decode_grad_codes  # (search imports this module lazily as well)
+
+    (indices,) = ctx.saved_tensors
+    want_sum, want_all = ctx.want
+    return (decode_grad_codes(ctx.cb_shape, indices, ctx.drop_null, g_sum if want_sum else None, g_all if want_all else None),
+            None, None, None, None, None)
+
+
+decode_codes.register_autograd(_decode_backward, setup_context=_decode_setup)
 
 
 # latent quantization (native.lq_*).  z [B, P, C * d] of any strides; the codes come back laid out as z; indices or a loss

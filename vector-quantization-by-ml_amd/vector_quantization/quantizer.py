@@ -202,7 +202,35 @@ class VectorQuantize(nn.Module):
         with torch.no_grad():
             self._codebook.embeddings.copy_(codes)
 
+    def _decode_native(self, indices):
+        """A codebook per head: the heads' codes [b, ..., h * D] through ONE vq_decode_f32 call (ATen's index rule: [-K, -1]
+        wraps), the heads on the call's group axis and written side by side, instead of h gathers and a ``cat``.  None when
+        the call is not the fused decode's (search.decode_backend).  One shared codebook keeps ``codes[indices]``: it is one
+        gather either way (1.05 - 1.11 x at 262 144 rows, 0.57 x at 4096 rows where the wrapper's host time decides), and a
+        channel-first result stays a view of the channel-last one."""
+        from . import search
+
+        codes = self.codebook
+        if codes.ndim != 3 or self.shard_world != 1 or indices.dim() < 1 or indices.shape[-1] != codes.shape[0]:
+            return None
+        decode = search.decode_backend(codes, indices)
+        if decode is None or indices.numel() == 0:
+            return None
+        h, _, D = codes.shape
+        lead = indices.shape[:-1]
+        flat = indices.reshape(-1, h).t()[..., None]  # [h, N, 1]: read in place
+        tables = codes[:, None]
+        if search.decode_needs_grad(codes):  # a learnable codebook: fresh tensors through autograd, laid out afterwards
+            out, _ = search.decode_rows(decode, tables, flat, drop_null=False)
+            return out.transpose(0, 1).reshape(*lead, h * D)
+        buf = torch.empty((flat.shape[1], h, D), dtype=torch.float32, device=flat.device)
+        search.decode_rows(decode, tables, flat, drop_null=False, sum_out=buf.transpose(0, 1))
+        return buf.reshape(*lead, h * D)
+
     def get_codes_from_indices(self, indices):
+        out = self._decode_native(indices)
+        if out is not None:
+            return out if self.channel_last else out.movedim(-1, 1)
         codes = self.codebook
         if codes.ndim == 2:
             out = codes[indices]

@@ -87,14 +87,44 @@ class ResidualVQ(nn.Module):
         """[Q, K, D] stack of the per-layer codebooks."""
         return torch.stack([layer._codebook.embeddings[0] for layer in self.layers], dim=0)
 
-    def get_codes_from_indices(self, indices):
-        """indices [b, ..., q] (q may be < Q, -1 = dropped) -> [Q, b, ..., D]."""
-        q_given = indices.shape[-1]
-        if q_given < self.num_quantizers:
+    def _check_coarse(self, indices):
+        if indices.shape[-1] < self.num_quantizers:
             assert self.quantize_dropout > 0.0, (
                 "quantize dropout must be greater than 0 if you wish to reconstruct from a signal with less fine "
                 "quantizations"
             )
+
+    def _decode_tables(self):
+        """The codebooks as the fused decode reads them, [1, Q | 1, K, D]: the learnable ones through the autograd graph,
+        the others from the stack the fused forward keeps (_stage_codes)."""
+        cbs = [self.layers[0]._codebook] if self.shared_codebook else [layer._codebook for layer in self.layers]
+        if torch.is_grad_enabled() and any(cb.embeddings.requires_grad for cb in cbs):
+            return torch.stack([cb.embeddings[0] for cb in cbs], dim=0)[None]
+        return self._stage_codes()[0]
+
+    def _decode_native(self, indices, want_sum):
+        """(codes_sum [b, ..., D] | all_codes [Q, b, ..., D]) from one vq_decode_f32 call, or None when the call is not the
+        fused decode's (search.decode_backend)."""
+        first = self.layers[0]._codebook.embeddings
+        decode = search.decode_backend(first, indices)
+        if decode is None or indices.shape[-1] == 0:
+            return None
+        lead, Q = indices.shape[:-1], self.num_quantizers
+        flat = indices.reshape(1, -1, indices.shape[-1])  # coarse indices: the missing stages are the call's Q_given
+        codes_sum, all_codes = search.decode_rows(decode, self._decode_tables(), flat, num_stages=Q, drop_null=True,
+                                                  want_sum=want_sum, want_all=not want_sum)
+        if want_sum:
+            return codes_sum.reshape(*lead, codes_sum.shape[-1])
+        return all_codes.reshape(Q, *lead, all_codes.shape[-1])
+
+    def get_codes_from_indices(self, indices):
+        """indices [b, ..., q] (q may be < Q, -1 = dropped) -> [Q, b, ..., D]."""
+        self._check_coarse(indices)
+        codes = self._decode_native(indices, want_sum=False)
+        if codes is not None:
+            return codes
+        q_given = indices.shape[-1]
+        if q_given < self.num_quantizers:
             pad = indices.new_full((*indices.shape[:-1], self.num_quantizers - q_given), -1)
             indices = torch.cat([indices, pad], dim=-1)
         dropped = indices < 0
@@ -105,6 +135,10 @@ class ResidualVQ(nn.Module):
         return codes.masked_fill(dropped.movedim(-1, 0)[..., None], 0.0)
 
     def get_output_from_indices(self, indices):
+        self._check_coarse(indices)
+        codes_sum = self._decode_native(indices, want_sum=True)  # nothing of [Q, N, D]: the stages are summed in registers
+        if codes_sum is not None:
+            return self.project_out(codes_sum)
         return self.project_out(self.get_codes_from_indices(indices).sum(dim=0))
 
     # ------------------------------------------------------------------ forward
@@ -266,10 +300,58 @@ class GroupedResidualVQ(nn.Module):
     def codebooks(self):
         return torch.stack(tuple(rvq.codebooks for rvq in self.rvqs))
 
+    def _decode_uniform(self, indices):
+        """(decode, tables [G, Q, K, d]) when ONE vq_decode_f32 call with the groups on its group axis decodes ``indices``
+        [G, b, ..., q]: uniform groups (same Q, K, d, no projections, the condition _fusable checks for the shapes), else None."""
+        r0 = self.rvqs[0]
+        first = r0.layers[0]._codebook.embeddings
+        if not isinstance(indices, torch.Tensor) or indices.dim() < 2 or indices.shape[0] != self.groups or indices.shape[-1] == 0:
+            return None
+        decode = search.decode_backend(first, indices)
+        if decode is None:
+            return None
+        for rvq in self.rvqs:
+            if rvq.has_projections or rvq.shared_codebook or rvq.num_quantizers != r0.num_quantizers:
+                return None
+            for layer in rvq.layers:
+                e = layer._codebook.embeddings
+                if e.shape != first.shape or e.dtype != first.dtype or e.device != first.device:
+                    return None
+        for rvq in self.rvqs:
+            rvq._check_coarse(indices[0])
+        cbs = [layer._codebook for rvq in self.rvqs for layer in rvq.layers]
+        if torch.is_grad_enabled() and any(cb.embeddings.requires_grad for cb in cbs):
+            return decode, self.codebooks
+        return decode, self._stage_codes()[0]
+
     def get_codes_from_indices(self, indices):
+        uniform = self._decode_uniform(indices)
+        if uniform is not None:  # [G, Q, b, ..., d] written by one call
+            decode, tables = uniform
+            G, Q, d = self.groups, tables.shape[1], tables.shape[-1]
+            lead = indices.shape[1:-1]
+            flat = indices.reshape(G, -1, indices.shape[-1])
+            if search.decode_needs_grad(tables):
+                _, codes = search.decode_rows(decode, tables, flat, drop_null=True, want_sum=False, want_all=True)
+                return codes.transpose(0, 1).reshape(G, Q, *lead, d)
+            buf = torch.empty((G, Q, flat.shape[1], d), dtype=torch.float32, device=flat.device)
+            search.decode_rows(decode, tables, flat, drop_null=True, want_sum=False, want_all=True, all_out=buf.transpose(0, 1))
+            return buf.reshape(G, Q, *lead, d)
         return torch.stack(tuple(rvq.get_codes_from_indices(i) for rvq, i in zip(self.rvqs, indices)))
 
     def get_output_from_indices(self, indices):
+        uniform = self._decode_uniform(indices) if self.channel_last else None
+        if uniform is not None:  # the groups' sums written side by side on the feature axis by one call
+            decode, tables = uniform
+            G, d = self.groups, tables.shape[-1]
+            lead = indices.shape[1:-1]
+            flat = indices.reshape(G, -1, indices.shape[-1])
+            if search.decode_needs_grad(tables):
+                out, _ = search.decode_rows(decode, tables, flat, drop_null=True)
+                return out.transpose(0, 1).reshape(*lead, G * d)
+            buf = torch.empty((flat.shape[1], G, d), dtype=torch.float32, device=flat.device)
+            search.decode_rows(decode, tables, flat, drop_null=True, sum_out=buf.transpose(0, 1))
+            return buf.reshape(*lead, G * d)
         outs = tuple(rvq.get_output_from_indices(i) for rvq, i in zip(self.rvqs, indices))
         return torch.cat(outs, dim=self.split_dim)
 

@@ -8,6 +8,7 @@ layout logic on a machine without a GPU.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -162,6 +163,19 @@ class _NativeBackend:
 
             return ops.gumbel_sample(x, cb.contiguous(), packed, seed, metric, float(tau))
         return native.sample_codes(x, cb.contiguous(), metric=metric, tau=tau, seed=seed, packed=packed)
+
+    @staticmethod
+    def decode(cb, indices, *, num_stages=None, drop_null=True, want_sum=True, want_all=False, sum_out=None, all_out=None):
+        """Indices -> code vectors in one pass (vq_decode_f32): cb [G | 1, Q | 1, K, D], indices [G, N, Qg] ->
+        (codes_sum [G, N, D] | None, all_codes [Q, G, N, D] | None); see native.decode_codes."""
+        if torch.compiler.is_compiling() and sum_out is None and all_out is None:
+            from . import ops
+
+            q = int(num_stages) if num_stages is not None else cb.shape[1]
+            s, a = ops.decode_codes(cb, indices, q, drop_null, want_sum, want_all)
+            return (s if want_sum else None), (a if want_all else None)
+        return native.decode_codes(cb, indices, num_stages=num_stages, drop_null=drop_null, want_sum=want_sum,
+                                   want_all=want_all, sum_out=sum_out, all_out=all_out)
 
     @staticmethod
     def gumbel_backward(x, cb, g, *, metric, tau, need_x=True, need_codes=True):
@@ -335,6 +349,79 @@ def quantize_rows(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, st
                                                 out=out, idx=idx, **pk,
                                                 **({"sq_err_per_head": True} if sq_err_per_head else {}))
     return out, idx, sq_err
+
+
+# ------------------------------------------------------------------------------------------------
+# indices -> code vectors
+# ------------------------------------------------------------------------------------------------
+def decode_backend(cb: torch.Tensor, indices) -> Optional[object]:
+    """The backend's ``decode`` when the fused decode takes this call, else None (the caller keeps its tensor-op
+    expression): a backend that has one, device tensors, fp32 codes, int32 / int64 indices, and no VQ_NO_FUSED_DECODE=1 in
+    the environment (read per call: A/B timing, and tests that compare the two paths in one process)."""
+    fn = getattr(_backend, "decode", None)
+    if fn is None or os.environ.get("VQ_NO_FUSED_DECODE") == "1":
+        return None
+    if not (isinstance(indices, torch.Tensor) and cb.is_cuda and indices.is_cuda and cb.dtype == torch.float32
+            and indices.dtype in (torch.int32, torch.int64)):
+        return None
+    return fn
+
+
+def decode_grad_codes(cb_shape, indices, drop_null, g_sum, g_all):
+    """d/d cb of the decode: every stage scatter-adds its incoming gradient by index (g_sum reaches every stage, g_all[q]
+    stage q), dropped and out-of-range entries masked out, the wrap rule applied first.  One ``ema_accumulate`` per stage."""
+    Gc, Qc, K, D = cb_shape
+    G, N, Qg = indices.shape
+    ref = g_sum if g_sum is not None else g_all
+    gcb = torch.zeros(cb_shape, dtype=torch.float32, device=ref.device)
+    for q in range(Qg):
+        g = g_sum if g_all is None else (g_all[q] if g_sum is None else g_sum + g_all[q])
+        i = indices[..., q].to(torch.int64)
+        if not drop_null:
+            i = torch.where(i < 0, i + K, i)
+        valid = (i >= 0) & (i < K)
+        i = torch.where(valid, i, torch.zeros_like(i))
+        g = g.to(torch.float32).contiguous()
+        if Gc == 1 and G > 1:  # one table for all groups: their rows are one list
+            g, i, valid = g.reshape(1, G * N, D), i.reshape(1, G * N), valid.reshape(1, G * N)
+        _hits, sums = _backend.ema_accumulate(g, i.contiguous(), K, valid)
+        gcb[:, q if Qc > 1 else 0] += sums
+    return gcb
+
+
+class _DecodeFn(torch.autograd.Function):
+    """The fused decode with the gradient of the tensor-op expression it replaces: out = codebook[idx] is differentiable
+    with respect to a learnable codebook (a scatter-add of the incoming gradient by index); indices receive none."""
+
+    @staticmethod
+    def forward(ctx, cb, indices, num_stages, drop_null, want_sum, want_all):
+        s, a = _backend.decode(cb.detach(), indices, num_stages=num_stages, drop_null=drop_null, want_sum=want_sum,
+                               want_all=want_all)
+        ctx.save_for_backward(indices)
+        ctx.cb_shape, ctx.drop_null = tuple(cb.shape), drop_null
+        return s, a
+
+    @staticmethod
+    def backward(ctx, g_sum, g_all):
+        (indices,) = ctx.saved_tensors
+        return decode_grad_codes(ctx.cb_shape, indices, ctx.drop_null, g_sum, g_all), None, None, None, None, None
+
+
+def decode_rows(decode, cb: torch.Tensor, indices: torch.Tensor, *, num_stages: Optional[int] = None, drop_null: bool = True,
+                want_sum: bool = True, want_all: bool = False, sum_out: Optional[torch.Tensor] = None,
+                all_out: Optional[torch.Tensor] = None):
+    """``decode`` (from ``decode_backend``) on cb [G | 1, Q | 1, K, D] and indices [G, N, Qg] ->
+    (codes_sum [G, N, D] | None, all_codes [Q, G, N, D] | None).  A codebook that requires grad keeps its autograd edge
+    (the results are then fresh tensors: ``sum_out`` / ``all_out`` must not be given -- see ``decode_needs_grad``)."""
+    if decode_needs_grad(cb):
+        assert sum_out is None and all_out is None
+        return _DecodeFn.apply(cb, indices, num_stages, drop_null, want_sum, want_all)
+    return decode(cb.detach(), indices, num_stages=num_stages, drop_null=drop_null, want_sum=want_sum, want_all=want_all,
+                  sum_out=sum_out, all_out=all_out)
+
+
+def decode_needs_grad(cb: torch.Tensor) -> bool:
+    return torch.is_grad_enabled() and cb.requires_grad
 
 
 def nearest_with_distance(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID):
