@@ -270,6 +270,29 @@ def test_code_counts_on_the_tiling_boundaries(k, d, metric):
     _run_suite_case((1, 133, k, d), metric, 1.0)
 
 
+@pytest.mark.parametrize("entry", ["vq_gumbel_backward_codes_f32", "vq_gumbel_reinmax_backward_codes_f32"])
+def test_an_empty_call_clears_grad_codes(entry):
+    """M = 0 (H = 2, K = 7, D = 5) through the C ABI (the Python wrappers refuse M = 0): no sweep, grad_codes all zeros.  The
+    statistics arrays and the workspace of an empty call are NULL."""
+    import ctypes
+
+    from vector_quantization import native
+
+    h, k, d = 2, 7, 5
+    a = native.VqArgs()
+    a.H, a.Q, a.M, a.K, a.D, a.metric, a.flags = h, 1, 0, k, d, 0, 0
+    cb = torch.randn((h, k, d), device="cuda")
+    g = torch.empty((h, 0, d), device="cuda")
+    a.cb, a.cb_hs = cb.data_ptr(), k * d
+    gc = torch.full((h, k, d), float("nan"), device="cuda")
+    stats = [None] * (2 if entry == "vq_gumbel_backward_codes_f32" else 5)
+    with torch.cuda.device(gc.device):
+        rc = getattr(native.load(), entry)(ctypes.byref(a), g.data_ptr() or 16, d, 0, 1.0, *stats, gc.data_ptr(), None, 0,
+                                           native._stream_ptr(gc.device))
+    assert rc == 0, native.load().vq_last_error()
+    assert torch.equal(gc, torch.zeros_like(gc))
+
+
 # ------------------------------------------------------------------------------------------------ 4. online softmax under stress
 @pytest.mark.parametrize("metric", ["euclid", "dot"])
 @pytest.mark.parametrize("shape,tau", [((2, 133, 70, 48), 20.0), ((2, 133, 70, 48), 1e-3), ((1, 300, 520, 64), 8.0)],

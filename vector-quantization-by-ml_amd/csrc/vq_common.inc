@@ -21,6 +21,11 @@ int fail(int code, const char *msg) {
     return code;
 }
 
+int fail(int code, const char *who, const char *msg) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", who, msg);
+    return code;
+}
+
 int hip_fail(hipError_t e, const char *what) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
     return (int)e;

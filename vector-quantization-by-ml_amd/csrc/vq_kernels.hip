@@ -466,15 +466,15 @@ template <int DP> int part_aux(const AuxParams &p, int H, int metric, int mode, 
 template <int DP> int part_ce_bwd(const CeBwdParams &p, int H, int metric, hipStream_t s);
 template <int DP> int part_sample(const AuxParams &p, int H, int metric, hipStream_t s);
 template <int DP> int part_gumbel(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
-template <> int part_gumbel<32>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
-template <> int part_gumbel<64>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
-template <> int part_gumbel<128>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
-template <> int part_gumbel<256>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <int DP> int part_reinmax(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
-template <> int part_reinmax<32>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
-template <> int part_reinmax<64>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
-template <> int part_reinmax<128>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
-template <> int part_reinmax<256>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+#define VQ_DECLARE_GUMBEL_PARTS(DP)                                                                              \
+    template <> int part_gumbel<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s); \
+    template <> int part_reinmax<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+VQ_DECLARE_GUMBEL_PARTS(32)
+VQ_DECLARE_GUMBEL_PARTS(64)
+VQ_DECLARE_GUMBEL_PARTS(128)
+VQ_DECLARE_GUMBEL_PARTS(256)
+#undef VQ_DECLARE_GUMBEL_PARTS
 int part_pair(const SearchParams &p, int H, int splits, int metric, hipStream_t s);
 int part_persist(const SearchChoice &c, const SearchParams &p, int H, int cus, int metric, hipStream_t s);
 #define VQ_DECLARE_PARTS(DP)                                                                                         \
@@ -1780,33 +1780,74 @@ int vq_gumbel_noise_f32(const int64_t *seed, int H, int64_t M, int K, float *noi
                                           (const long long *)seed, H, (long long)M, K, noise, (unsigned *)bits);
 }
 
-// ---- Gumbel straight-through backward (vq_gumbel.inc) -----------------------------------------------------------------
+// ---- Gumbel backward through the similarities: straight-through (kGum*) and reinmax (kRm*) roles of vq_gumbel.inc -------
 int64_t vq_gumbel_row_stride(int64_t M) { return M <= 0 ? 0 : (M + 255) / 256 * 256; }
 
-int64_t vq_gumbel_workspace_bytes(int H, int64_t M, int K, int D) {
-    if (H <= 0 || M <= 0 || K <= 0 || D <= 0 || D > 256 || M > 0x7FFFFFFFll) return 0;
-    const GumbelCodesPlan pl = plan_gumbel_codes(H, M, K, D);
-    return 4 * (2 * (int64_t)H * pl.img_floats + (pl.splits > 1 ? (int64_t)pl.splits * H * K * D : 0));
+// Workspace of the codes-resident roles, offsets in 4-byte units (documented in vq_mi355x.h):
+//   [x image H x img_floats][g image H x img_floats]
+//   reinmax only: [ind int32 H x row_stride(M)][col partials splits x H x row_stride(K)][e partials splits x H x row_stride(K)]
+//   [grad_codes partials splits x H x K x D, splits > 1]
+struct GumbelWorkspace {
+    GumbelCodesPlan pl;
+    long long gimg_off, ind_off, colp_off, ep_off, parts_off, floats;
+};
+static GumbelWorkspace gumbel_workspace(int H, long long M, int K, int D, bool reinmax) {
+    GumbelWorkspace w;
+    w.pl = plan_gumbel_codes(H, M, K, D);
+    const long long ck = reinmax ? w.pl.splits * (long long)H * vq_gumbel_row_stride(K) : 0;
+    w.gimg_off = (long long)H * w.pl.img_floats;
+    w.ind_off = 2 * w.gimg_off;
+    w.colp_off = w.ind_off + (reinmax ? (long long)H * vq_gumbel_row_stride(M) : 0);
+    w.ep_off = w.colp_off + ck;
+    w.parts_off = w.ep_off + ck;
+    w.floats = w.parts_off + (w.pl.splits > 1 ? (long long)w.pl.splits * H * K * D : 0);
+    return w;
 }
+static int64_t gumbel_workspace_bytes(int H, int64_t M, int K, int D, bool reinmax) {
+    if (H <= 0 || M <= 0 || K <= 0 || D <= 0 || D > 256 || M > 0x7FFFFFFFll) return 0;
+    return 4 * gumbel_workspace(H, M, K, D, reinmax).floats;
+}
+int64_t vq_gumbel_workspace_bytes(int H, int64_t M, int K, int D) { return gumbel_workspace_bytes(H, M, K, D, false); }
+int64_t vq_gumbel_reinmax_workspace_bytes(int H, int64_t M, int K, int D) { return gumbel_workspace_bytes(H, M, K, D, true); }
 
-static int fill_gumbel_params(GumbelParams &p, const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau,
-                              const float *lse2, const float *delta) {
+// A family: its workspace regions, and the argument rules on which the two differ (callers may rely on either;
+// tests/test_gumbel_abi_host.py pins both):
+//   tau_finite: tau = +inf is rejected
+//   null_first: a null statistics array is reported with a null g, before tau and D; otherwise with the alignment, after them
+struct GumbelFamily {
+    bool reinmax, tau_finite, null_first;
+    const char *null_msg, *tau_msg, *ws_msg;
+};
+constexpr GumbelFamily kStraightThrough = {false, false, true, "null argument (g / lse2 / delta)", "tau must be positive",
+                                           "workspace too small or misaligned (see vq_gumbel_workspace_bytes)"};
+constexpr GumbelFamily kReinmax = {true, true, false, "g is null", "tau must be positive and finite",
+                                   "workspace too small or misaligned (see vq_gumbel_reinmax_workspace_bytes)"};
+
+// what every entry checks and fills; `arrays`: the per-row and per-code arrays the entry uses (non-null, 16-byte aligned)
+static int fill_gumbel_params(GumbelParams &p, const char *who, const GumbelFamily &f, const vq_args *a, const float *g, int64_t g_rs,
+                              int64_t g_hs, float tau, std::initializer_list<const void *> arrays) {
     memset(&p, 0, sizeof(p));
-    if (!g || !lse2 || !delta) return fail(VQ_E_BADARG, "vq_gumbel: null argument (g / lse2 / delta)");
-    if (!(tau > 0.0f)) return fail(VQ_E_BADARG, "vq_gumbel: tau must be positive");
-    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, "vq_gumbel: D > 256 (use row chunks of vq_similarities_f32)");
-    if (!aligned16(lse2) || !aligned16(delta)) return fail(VQ_E_BADARG, "vq_gumbel: lse2 / delta must be 16-byte aligned");
+    bool null_array = false, misaligned = false;
+    if (a->M > 0) {  // (M == 0: no launch, the per-row arrays are empty)
+        for (const void *q : arrays) {
+            null_array |= !q;
+            misaligned |= !aligned16(q);
+        }
+    }
+    if (!g || (f.null_first && null_array)) return fail(VQ_E_BADARG, who, f.null_msg);
+    if (!(tau > 0.0f) || (f.tau_finite && !(tau < __builtin_inff()))) return fail(VQ_E_BADARG, who, f.tau_msg);
+    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, who, "D > 256 (use row chunks of vq_similarities_f32)");
+    if (null_array || misaligned) return fail(VQ_E_BADARG, who, "a statistics array is null or not 16-byte aligned");
     p.D = a->D;
     p.tau = tau;
-    p.lse = (float *)lse2;
-    p.delta = (float *)delta;
     p.st_hs = vq_gumbel_row_stride(a->M);
+    p.ck_hs = vq_gumbel_row_stride(a->K);  // (read by the kRm* roles only)
     p.g = g; p.g_rs = g_rs; p.g_hs = g_hs;
     p.vec_g = vec4_ok(g, {a->D, g_rs, g_hs}) ? 1 : 0;
     return 0;
 }
 
-// kGumStats / kGumX: the rows are resident, the packed codebook is streamed
+// kGumStats / kGumX / kRmStats / kRmX: the rows are resident, the packed codebook is streamed
 static int fill_gumbel_rows(GumbelParams &p, const vq_args *a) {
     AuxParams ap;
     if (int rc = fill_aux_params(ap, a)) return rc;
@@ -1818,22 +1859,74 @@ static int fill_gumbel_rows(GumbelParams &p, const vq_args *a) {
     return 0;
 }
 
+// kGumC / kRmCol / kRmC: the codes are resident, the packed rows are streamed -- the plan, the workspace and the images in it
+static int fill_gumbel_codes(GumbelParams &p, const char *who, const GumbelFamily &f, const vq_args *a, void *workspace,
+                             int64_t workspace_bytes, GumbelWorkspace &w) {
+    if (!a->cb) return fail(VQ_E_BADARG, who, "cb is null");
+    if (a->M > 0x7FFFFFFFll) return fail(VQ_E_UNSUPPORTED, who, "too many rows (use row chunks)");
+    w = gumbel_workspace(a->H, a->M, a->K, a->D, f.reinmax);
+    if (w.pl.img_floats * 4 >= (1ll << 31)) return fail(VQ_E_UNSUPPORTED, who, "packed row image >= 2 GiB (use row chunks)");
+    if (!workspace || !aligned16(workspace) || workspace_bytes < 4 * w.floats) return fail(VQ_E_BADARG, who, f.ws_msg);
+    float *ws = (float *)workspace;
+    p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
+    p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
+    p.img = ws; p.gimg = ws + w.gimg_off;
+    p.img_hs = w.pl.img_floats; p.img_bytes = (unsigned)(w.pl.img_floats * 4);
+    if (f.reinmax) p.ind32 = (const int *)(ws + w.ind_off);
+    p.NR = a->K; p.NS = a->M;
+    p.ntiles = w.pl.ntiles;
+    p.tiles_per_split = w.pl.tiles_per_split;
+    return 0;
+}
+
+// the x rows and the g rows into the two images at the head of the workspace
+static int pack_gumbel_rows(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, const GumbelWorkspace &w, float *ws, hipStream_t s) {
+    return launch<vq_gumbel_pack_rows>(dim3((unsigned)((w.pl.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
+                                       (long long)a->x_rs, (long long)a->x_hs, g, (long long)g_rs, (long long)g_hs, (long long)a->M, w.pl.Mp,
+                                       a->D, padded_dim(a->D), a->metric, ws, ws + w.gimg_off, w.pl.img_floats);
+}
+
+// the only padded-dim dispatch of the seven roles: the kGum* kernels live in build part 7, the kRm* kernels in part 8
+static int launch_gumbel(int role, const GumbelParams &p, const vq_args *a, int gz, hipStream_t s) {
+    const int DP = padded_dim(a->D);
+    return with_padded_dim(DP == 512 ? 0 : DP,
+                           [&](auto dp) {
+                               constexpr int DPC = decltype(dp)::value;
+                               if constexpr (DPC > 256) return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
+                               else if (role < kRmStats) return vqi::part_gumbel<DPC>(role, p, a->H, gz, a->metric, s);
+                               else return vqi::part_reinmax<DPC>(role, p, a->H, gz, a->metric, s);
+                           },
+                           [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim"); });
+}
+
+// grad_codes [H][K][D] of the two *_backward_codes entries: all zeros for an empty call ...
+static int clear_grad_codes(const vq_args *a, float *grad_codes, hipStream_t s, const char *what) {
+    const hipError_t e = hipMemsetAsync(grad_codes, 0, (size_t)a->H * a->K * a->D * 4, s);
+    return e == hipSuccess ? 0 : hip_fail(e, what);
+}
+
+// ... else the sweep (kGumC / kRmC), straight into grad_codes or into one partial per row split that vq_gumbel_reduce_parts sums
+static int sweep_grad_codes(int role, GumbelParams &p, const vq_args *a, const GumbelWorkspace &w, float *ws, float *grad_codes, hipStream_t s) {
+    const long long n = (long long)a->H * a->K * a->D;
+    float *parts = ws + w.parts_off;
+    p.out = w.pl.splits > 1 ? parts : grad_codes;
+    p.out_rs = a->D; p.out_hs = (long long)a->K * a->D; p.out_zs = n;
+    if (int rc = launch_gumbel(role, p, a, w.pl.splits, s)) return rc;
+    if (w.pl.splits == 1) return 0;
+    return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
+                                          w.pl.splits, grad_codes);
+}
+
 int vq_gumbel_stats_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, float *lse2, float *delta,
                         void *stream) {
     int rc = check_common(a);
     if (rc) return rc;
     if (a->M == 0) return 0;
     GumbelParams p;
-    if ((rc = fill_gumbel_params(p, a, g, g_rs, g_hs, tau, lse2, delta))) return rc;
+    if ((rc = fill_gumbel_params(p, "vq_gumbel_stats", kStraightThrough, a, g, g_rs, g_hs, tau, {lse2, delta}))) return rc;
     if ((rc = fill_gumbel_rows(p, a))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    return with_padded_dim(padded_dim(a->D) == 512 ? 0 : padded_dim(a->D),
-                           [&](auto dp) {
-                               constexpr int DP = decltype(dp)::value;
-                               if constexpr (DP <= 256) return vqi::part_gumbel<DP>(kGumStats, p, a->H, 1, a->metric, s);
-                               else return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
-                           },
-                           [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim"); });
+    p.lse = lse2; p.delta = delta;
+    return launch_gumbel(kGumStats, p, a, 1, (hipStream_t)stream);
 }
 
 int vq_gumbel_backward_x_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2,
@@ -1843,135 +1936,28 @@ int vq_gumbel_backward_x_f32(const vq_args *a, const float *g, int64_t g_rs, int
     if (a->M == 0) return 0;
     if (!grad_x) return fail(VQ_E_BADARG, "vq_gumbel_backward_x: grad_x is null");
     GumbelParams p;
-    if ((rc = fill_gumbel_params(p, a, g, g_rs, g_hs, tau, lse2, delta))) return rc;
+    if ((rc = fill_gumbel_params(p, "vq_gumbel_backward_x", kStraightThrough, a, g, g_rs, g_hs, tau, {lse2, delta}))) return rc;
     if ((rc = fill_gumbel_rows(p, a))) return rc;
+    p.lse = (float *)lse2; p.delta = (float *)delta;
     p.out = grad_x; p.out_rs = gx_rs; p.out_hs = gx_hs;
-    hipStream_t s = (hipStream_t)stream;
-    return with_padded_dim(padded_dim(a->D) == 512 ? 0 : padded_dim(a->D),
-                           [&](auto dp) {
-                               constexpr int DP = decltype(dp)::value;
-                               if constexpr (DP <= 256) return vqi::part_gumbel<DP>(kGumX, p, a->H, 1, a->metric, s);
-                               else return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
-                           },
-                           [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim"); });
+    return launch_gumbel(kGumX, p, a, 1, (hipStream_t)stream);
 }
 
 int vq_gumbel_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2,
                                  const float *delta, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream) {
+    static const char who[] = "vq_gumbel_backward_codes";
     int rc = check_common(a);
     if (rc) return rc;
-    if (!grad_codes || !a->cb) return fail(VQ_E_BADARG, "vq_gumbel_backward_codes: null argument (grad_codes / cb)");
+    if (!grad_codes || !a->cb) return fail(VQ_E_BADARG, who, "null argument (grad_codes / cb)");
     hipStream_t s = (hipStream_t)stream;
-    const long long n = (long long)a->H * a->K * a->D;
-    if (a->M == 0) {
-        const hipError_t e = hipMemsetAsync(grad_codes, 0, (size_t)n * 4, s);
-        return e == hipSuccess ? 0 : hip_fail(e, "vq_gumbel_backward_codes memset");
-    }
+    if (a->M == 0) return clear_grad_codes(a, grad_codes, s, "vq_gumbel_backward_codes memset");
     GumbelParams p;
-    if ((rc = fill_gumbel_params(p, a, g, g_rs, g_hs, tau, lse2, delta))) return rc;
-    if (a->M > 0x7FFFFFFFll) return fail(VQ_E_UNSUPPORTED, "vq_gumbel_backward_codes: too many rows (use row chunks)");
-    const GumbelCodesPlan pl = plan_gumbel_codes(a->H, a->M, a->K, a->D);
-    if (pl.img_floats * 4 >= (1ll << 31))
-        return fail(VQ_E_UNSUPPORTED, "vq_gumbel_backward_codes: packed row image >= 2 GiB (use row chunks)");
-    if (!workspace || !aligned16(workspace) || workspace_bytes < vq_gumbel_workspace_bytes(a->H, a->M, a->K, a->D))
-        return fail(VQ_E_BADARG, "vq_gumbel_backward_codes: workspace too small or misaligned (see vq_gumbel_workspace_bytes)");
-    const int DP = padded_dim(a->D);
-    float *ximg = (float *)workspace, *gimg = ximg + (long long)a->H * pl.img_floats, *parts = gimg + (long long)a->H * pl.img_floats;
-    if ((rc = launch<vq_gumbel_pack_rows>(dim3((unsigned)((pl.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
-                                          (long long)a->x_rs, (long long)a->x_hs, g, (long long)g_rs, (long long)g_hs, (long long)a->M, pl.Mp,
-                                          a->D, DP, a->metric, ximg, gimg, pl.img_floats)))
-        return rc;
-    p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
-    p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
-    p.img = ximg; p.gimg = gimg; p.img_hs = pl.img_floats; p.img_bytes = (unsigned)(pl.img_floats * 4);
-    p.NR = a->K; p.NS = a->M;
-    p.ntiles = pl.ntiles;
-    p.tiles_per_split = pl.tiles_per_split;
-    p.out = pl.splits > 1 ? parts : grad_codes;
-    p.out_rs = a->D; p.out_hs = (long long)a->K * a->D; p.out_zs = n;
-    rc = with_padded_dim(DP == 512 ? 0 : DP,
-                         [&](auto dp) {
-                             constexpr int DPC = decltype(dp)::value;
-                             if constexpr (DPC <= 256) return vqi::part_gumbel<DPC>(kGumC, p, a->H, pl.splits, a->metric, s);
-                             else return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
-                         },
-                         [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim"); });
-    if (rc || pl.splits == 1) return rc;
-    return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
-                                          pl.splits, grad_codes);
-}
-
-// ---- Gumbel reinmax backward (the kRm* roles of vq_gumbel.inc) --------------------------------------------------------
-// workspace: [x image H x img_floats][g image H x img_floats][ind int32 H x row_stride(M)]
-//            [col partials splits x H x row_stride(K)][e partials splits x H x row_stride(K)][gc partials splits x H x K x D, splits > 1]
-struct ReinmaxWorkspace {
-    GumbelCodesPlan pl;
-    long long ind_off, colp_off, ep_off, parts_off, floats;  // offsets in 4-byte units
-};
-static ReinmaxWorkspace reinmax_workspace(int H, long long M, int K, int D) {
-    ReinmaxWorkspace w;
-    w.pl = plan_gumbel_codes(H, M, K, D);
-    const long long ck = (long long)H * vq_gumbel_row_stride(K);
-    w.ind_off = 2 * (long long)H * w.pl.img_floats;
-    w.colp_off = w.ind_off + (long long)H * vq_gumbel_row_stride(M);
-    w.ep_off = w.colp_off + w.pl.splits * ck;
-    w.parts_off = w.ep_off + w.pl.splits * ck;
-    w.floats = w.parts_off + (w.pl.splits > 1 ? (long long)w.pl.splits * H * K * D : 0);
-    return w;
-}
-
-int64_t vq_gumbel_reinmax_workspace_bytes(int H, int64_t M, int K, int D) {
-    if (H <= 0 || M <= 0 || K <= 0 || D <= 0 || D > 256 || M > 0x7FFFFFFFll) return 0;
-    return 4 * reinmax_workspace(H, M, K, D).floats;
-}
-
-// what every reinmax entry checks and fills; `arrays`: the per-row and per-code arrays the entry uses (non-null, 16-byte aligned)
-static int fill_reinmax_params(GumbelParams &p, const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau,
-                               std::initializer_list<const void *> arrays) {
-    memset(&p, 0, sizeof(p));
-    if (!g) return fail(VQ_E_BADARG, "vq_gumbel_reinmax: g is null");
-    if (!(tau > 0.0f) || !(tau < __builtin_inff())) return fail(VQ_E_BADARG, "vq_gumbel_reinmax: tau must be positive and finite");
-    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, "vq_gumbel_reinmax: D > 256 (use row chunks of vq_similarities_f32)");
-    for (const void *q : arrays)  // (M == 0: no launch, the per-row arrays are empty)
-        if (a->M > 0 && (!q || !aligned16(q))) return fail(VQ_E_BADARG, "vq_gumbel_reinmax: a statistics array is null or not 16-byte aligned");
-    p.D = a->D;
-    p.tau = tau;
-    p.st_hs = vq_gumbel_row_stride(a->M);
-    p.ck_hs = vq_gumbel_row_stride(a->K);
-    p.g = g; p.g_rs = g_rs; p.g_hs = g_hs;
-    p.vec_g = vec4_ok(g, {a->D, g_rs, g_hs}) ? 1 : 0;
-    return 0;
-}
-
-static int launch_reinmax(int role, const GumbelParams &p, const vq_args *a, int gz, hipStream_t s) {
-    const int DP = padded_dim(a->D);
-    return with_padded_dim(DP == 512 ? 0 : DP,
-                           [&](auto dp) {
-                               constexpr int DPC = decltype(dp)::value;
-                               if constexpr (DPC <= 256) return vqi::part_reinmax<DPC>(role, p, a->H, gz, a->metric, s);
-                               else return fail(VQ_E_UNSUPPORTED, "vq_gumbel_reinmax: unsupported padded dim");
-                           },
-                           [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel_reinmax: unsupported padded dim"); });
-}
-
-// the codes-resident roles: the plan, the workspace and the images in it
-static int fill_reinmax_codes(GumbelParams &p, const vq_args *a, void *workspace, int64_t workspace_bytes, ReinmaxWorkspace &w) {
-    if (!a->cb) return fail(VQ_E_BADARG, "vq_gumbel_reinmax: cb is null");
-    if (a->M > 0x7FFFFFFFll) return fail(VQ_E_UNSUPPORTED, "vq_gumbel_reinmax: too many rows (use row chunks)");
-    w = reinmax_workspace(a->H, a->M, a->K, a->D);
-    if (w.pl.img_floats * 4 >= (1ll << 31)) return fail(VQ_E_UNSUPPORTED, "vq_gumbel_reinmax: packed row image >= 2 GiB (use row chunks)");
-    if (!workspace || !aligned16(workspace) || workspace_bytes < 4 * w.floats)
-        return fail(VQ_E_BADARG, "vq_gumbel_reinmax: workspace too small or misaligned (see vq_gumbel_reinmax_workspace_bytes)");
-    float *ws = (float *)workspace;
-    p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
-    p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
-    p.img = ws; p.gimg = ws + (long long)a->H * w.pl.img_floats;
-    p.img_hs = w.pl.img_floats; p.img_bytes = (unsigned)(w.pl.img_floats * 4);
-    p.ind32 = (const int *)(ws + w.ind_off);
-    p.NR = a->K; p.NS = a->M;
-    p.ntiles = w.pl.ntiles;
-    p.tiles_per_split = w.pl.tiles_per_split;
-    return 0;
+    GumbelWorkspace w;
+    if ((rc = fill_gumbel_params(p, who, kStraightThrough, a, g, g_rs, g_hs, tau, {lse2, delta}))) return rc;
+    if ((rc = fill_gumbel_codes(p, who, kStraightThrough, a, workspace, workspace_bytes, w))) return rc;
+    if ((rc = pack_gumbel_rows(a, g, g_rs, g_hs, w, (float *)workspace, s))) return rc;
+    p.lse = (float *)lse2; p.delta = (float *)delta;
+    return sweep_grad_codes(kGumC, p, a, w, (float *)workspace, grad_codes, s);
 }
 
 int vq_gumbel_reinmax_stats_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, float *lse2_tau,
@@ -1979,30 +1965,28 @@ int vq_gumbel_reinmax_stats_f32(const vq_args *a, const float *g, int64_t g_rs, 
     int rc = check_common(a);
     if (rc) return rc;
     GumbelParams p;
-    if ((rc = fill_reinmax_params(p, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0}))) return rc;
+    if ((rc = fill_gumbel_params(p, "vq_gumbel_reinmax_stats", kReinmax, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0}))) return rc;
     if (a->M == 0) return 0;
     if ((rc = fill_gumbel_rows(p, a))) return rc;
     p.lse = lse2_tau; p.lse1 = lse2_one; p.delta = delta0;
-    return launch_reinmax(kRmStats, p, a, 1, (hipStream_t)stream);
+    return launch_gumbel(kRmStats, p, a, 1, (hipStream_t)stream);
 }
 
 int vq_gumbel_reinmax_columns_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
                                   const int64_t *ind, int64_t ind_rs, int64_t ind_hs, float *col, float *e, void *workspace,
                                   int64_t workspace_bytes, void *stream) {
+    static const char who[] = "vq_gumbel_reinmax_columns";
     int rc = check_common(a);
     if (rc) return rc;
     GumbelParams p;
-    if ((rc = fill_reinmax_params(p, a, g, g_rs, g_hs, tau, {lse2_tau, col, e}))) return rc;
-    if (!ind) return fail(VQ_E_BADARG, "vq_gumbel_reinmax_columns: ind is null");
+    GumbelWorkspace w;
+    if ((rc = fill_gumbel_params(p, who, kReinmax, a, g, g_rs, g_hs, tau, {lse2_tau, col, e}))) return rc;
+    if (!ind) return fail(VQ_E_BADARG, who, "ind is null");
     if (a->M == 0) return 0;
-    ReinmaxWorkspace w;
-    if ((rc = fill_reinmax_codes(p, a, workspace, workspace_bytes, w))) return rc;
+    if ((rc = fill_gumbel_codes(p, who, kReinmax, a, workspace, workspace_bytes, w))) return rc;
     hipStream_t s = (hipStream_t)stream;
     float *ws = (float *)workspace;
-    if ((rc = launch<vq_gumbel_pack_rows>(dim3((unsigned)((w.pl.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
-                                          (long long)a->x_rs, (long long)a->x_hs, g, (long long)g_rs, (long long)g_hs, (long long)a->M, w.pl.Mp,
-                                          a->D, padded_dim(a->D), a->metric, ws, ws + (long long)a->H * w.pl.img_floats, w.pl.img_floats)))
-        return rc;
+    if ((rc = pack_gumbel_rows(a, g, g_rs, g_hs, w, ws, s))) return rc;
     if ((rc = launch<vq_gumbel_pack_ind>(dim3((unsigned)((p.st_hs + 255) / 256), (unsigned)a->H), dim3(256), 0, s, "vq_gumbel_pack_ind launch",
                                          (const long long *)ind, (long long)ind_rs, (long long)ind_hs, (long long)a->M, p.st_hs,
                                          (int *)(ws + w.ind_off))))
@@ -2010,7 +1994,7 @@ int vq_gumbel_reinmax_columns_f32(const vq_args *a, const float *g, int64_t g_rs
     p.lse = (float *)lse2_tau;
     p.colp = ws + w.colp_off; p.ep = ws + w.ep_off;
     p.cp_zs = (long long)a->H * p.ck_hs;
-    if ((rc = launch_reinmax(kRmCol, p, a, w.pl.splits, s))) return rc;
+    if ((rc = launch_gumbel(kRmCol, p, a, w.pl.splits, s))) return rc;
     return launch<vq_gumbel_reduce_cols>(dim3((unsigned)((p.cp_zs + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_cols launch",
                                          (const float *)p.colp, (const float *)p.ep, p.cp_zs, p.ck_hs, a->K, w.pl.splits, col, e);
 }
@@ -2018,44 +2002,37 @@ int vq_gumbel_reinmax_columns_f32(const vq_args *a, const float *g, int64_t g_rs
 int vq_gumbel_reinmax_backward_x_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
                                      const float *lse2_one, const float *delta0, const int64_t *ind, int64_t ind_rs, int64_t ind_hs,
                                      const float *col, const float *e, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream) {
+    static const char who[] = "vq_gumbel_reinmax_backward_x";
     int rc = check_common(a);
     if (rc) return rc;
     GumbelParams p;
-    if ((rc = fill_reinmax_params(p, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0, col, e}))) return rc;
-    if (!ind || !grad_x) return fail(VQ_E_BADARG, "vq_gumbel_reinmax_backward_x: null argument (ind / grad_x)");
+    if ((rc = fill_gumbel_params(p, who, kReinmax, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0, col, e}))) return rc;
+    if (!ind || !grad_x) return fail(VQ_E_BADARG, who, "null argument (ind / grad_x)");
     if (a->M == 0) return 0;
     if ((rc = fill_gumbel_rows(p, a))) return rc;
     p.lse = (float *)lse2_tau; p.lse1 = (float *)lse2_one; p.delta = (float *)delta0;
     p.ind = (const long long *)ind; p.ind_rs = ind_rs; p.ind_hs = ind_hs;
     p.col = (float *)col; p.e = (float *)e;
     p.out = grad_x; p.out_rs = gx_rs; p.out_hs = gx_hs;
-    return launch_reinmax(kRmX, p, a, 1, (hipStream_t)stream);
+    return launch_gumbel(kRmX, p, a, 1, (hipStream_t)stream);
 }
 
 int vq_gumbel_reinmax_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
                                          const float *lse2_one, const float *delta0, const float *col, const float *e,
                                          float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream) {
+    static const char who[] = "vq_gumbel_reinmax_backward_codes";
     int rc = check_common(a);
     if (rc) return rc;
     GumbelParams p;
-    if ((rc = fill_reinmax_params(p, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0, col, e}))) return rc;
-    if (!grad_codes) return fail(VQ_E_BADARG, "vq_gumbel_reinmax_backward_codes: grad_codes is null");
+    GumbelWorkspace w;
+    if ((rc = fill_gumbel_params(p, who, kReinmax, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0, col, e}))) return rc;
+    if (!grad_codes) return fail(VQ_E_BADARG, who, "grad_codes is null");
     hipStream_t s = (hipStream_t)stream;
-    const long long n = (long long)a->H * a->K * a->D;
-    if (a->M == 0) {
-        const hipError_t err = hipMemsetAsync(grad_codes, 0, (size_t)n * 4, s);
-        return err == hipSuccess ? 0 : hip_fail(err, "vq_gumbel_reinmax_backward_codes memset");
-    }
-    ReinmaxWorkspace w;
-    if ((rc = fill_reinmax_codes(p, a, workspace, workspace_bytes, w))) return rc;
-    float *parts = (float *)workspace + w.parts_off;
+    if (a->M == 0) return clear_grad_codes(a, grad_codes, s, "vq_gumbel_reinmax_backward_codes memset");
+    if ((rc = fill_gumbel_codes(p, who, kReinmax, a, workspace, workspace_bytes, w))) return rc;
     p.lse = (float *)lse2_tau; p.lse1 = (float *)lse2_one; p.delta = (float *)delta0;
     p.col = (float *)col; p.e = (float *)e;
-    p.out = w.pl.splits > 1 ? parts : grad_codes;
-    p.out_rs = a->D; p.out_hs = (long long)a->K * a->D; p.out_zs = n;
-    if ((rc = launch_reinmax(kRmC, p, a, w.pl.splits, s)) || w.pl.splits == 1) return rc;
-    return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
-                                          w.pl.splits, grad_codes);
+    return sweep_grad_codes(kRmC, p, a, w, (float *)workspace, grad_codes, s);
 }
 
 int vq_max_fused_stages(int D, int want_sq_err) {

@@ -446,11 +446,6 @@ LfqCoef lfq_coef_args(const float *code_scale, const float *code_scale_dev, int 
     return k;
 }
 
-int lfq_fail(int code, const char *who, const char *msg) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", who, msg);
-    return code;
-}
-
 // The entropy forward of T stages (T = 1: vq_lfq_entropy_fwd_f32).  Stage t uses code_scale_dev[t % period] (a device
 // array) or, when code_scale_dev is NULL, the host value code_scale[0].
 int lfq_entropy_fwd_run(const float *v, int64_t v_rs, int64_t v_ss, const int64_t *rows, int64_t rows_ss, int64_t R, int T, int C,
@@ -458,12 +453,12 @@ int lfq_entropy_fwd_run(const float *v, int64_t v_rs, int64_t v_ss, const int64_
                         double *per_sample_sum, void *workspace, int64_t workspace_bytes, void *stream, const char *who) {
     int rc = lfq_check_shape(R, C, d);
     if (rc) return rc;
-    if (R < 1) return lfq_fail(VQ_E_BADARG, who, "no rows selected");
-    if (T < 1 || T > 65535 || period < 1 || (!code_scale_dev && period != 1)) return lfq_fail(VQ_E_BADARG, who, "bad stage count");
-    if (!v || !avg_prob || !per_sample_sum || !workspace || (!code_scale && !code_scale_dev)) return lfq_fail(VQ_E_BADARG, who, "null pointer");
-    if (v_rs < (int64_t)C * d) return lfq_fail(VQ_E_BADARG, who, "row stride < C * d");
+    if (R < 1) return fail(VQ_E_BADARG, who, "no rows selected");
+    if (T < 1 || T > 65535 || period < 1 || (!code_scale_dev && period != 1)) return fail(VQ_E_BADARG, who, "bad stage count");
+    if (!v || !avg_prob || !per_sample_sum || !workspace || (!code_scale && !code_scale_dev)) return fail(VQ_E_BADARG, who, "null pointer");
+    if (v_rs < (int64_t)C * d) return fail(VQ_E_BADARG, who, "row stride < C * d");
     const LfqWs ws = lfq_ws_layout(R, R, C, d, T);
-    if (workspace_bytes < ws.total) return lfq_fail(VQ_E_BADARG, who, "workspace too small");
+    if (workspace_bytes < ws.total) return fail(VQ_E_BADARG, who, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     char *base = (char *)workspace;
     float *ent = (float *)(base + ws.ent), *tabA = (float *)(base + ws.tabA), *tabB = (float *)(base + ws.tabB);
@@ -494,9 +489,9 @@ int lfq_entropy_bwd_run(const float *v, int64_t v_rs, int64_t v_ss, const int64_
     int rc = lfq_check_shape(R, C, d);
     if (rc) return rc;
     if (R == 0) return 0;
-    if (T < 1 || T > 65535 || period < 1 || (!code_scale_dev && period != 1)) return lfq_fail(VQ_E_BADARG, who, "bad stage count");
-    if (!v || !w_ps || !w_cb || !grad_v || (!code_scale && !code_scale_dev)) return lfq_fail(VQ_E_BADARG, who, "null pointer");
-    if (v_rs < (int64_t)C * d || gv_rs < (int64_t)C * d) return lfq_fail(VQ_E_BADARG, who, "row stride < C * d");
+    if (T < 1 || T > 65535 || period < 1 || (!code_scale_dev && period != 1)) return fail(VQ_E_BADARG, who, "bad stage count");
+    if (!v || !w_ps || !w_cb || !grad_v || (!code_scale && !code_scale_dev)) return fail(VQ_E_BADARG, who, "null pointer");
+    if (v_rs < (int64_t)C * d || gv_rs < (int64_t)C * d) return fail(VQ_E_BADARG, who, "row stride < C * d");
     hipStream_t s = (hipStream_t)stream;
     const LfqCoef coefs = lfq_coef_args(code_scale, code_scale_dev, period, inv_temperature);
     const int waves = lfq_task_waves(d);

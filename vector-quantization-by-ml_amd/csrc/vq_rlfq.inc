@@ -171,11 +171,11 @@ __global__ void __launch_bounds__(kRlfqThreads) rlfq_backward_kernel(
 }
 
 int rlfq_check(int64_t G, int64_t N, int d, int S, const float *stage_consts, const char *who) {
-    if (G < 1 || G > 65535 || N < 0) return lfq_fail(VQ_E_BADARG, who, "G must be in [1, 65535] and N >= 0");
-    if (d < 1 || d > kLfqMaxDim) return lfq_fail(VQ_E_UNSUPPORTED, who, "codebook_dim must be in [1, 20]");
-    if (S < 1 || S > VQ_RLFQ_MAX_STAGES) return lfq_fail(VQ_E_UNSUPPORTED, who, "stage count must be in [1, 32]");
-    if (!stage_consts) return lfq_fail(VQ_E_BADARG, who, "null stage constants");
-    if (G * N > ((int64_t)1 << 40) || rlfq_blocks(N) > 0x7fffffff) return lfq_fail(VQ_E_BADARG, who, "too many rows");
+    if (G < 1 || G > 65535 || N < 0) return fail(VQ_E_BADARG, who, "G must be in [1, 65535] and N >= 0");
+    if (d < 1 || d > kLfqMaxDim) return fail(VQ_E_UNSUPPORTED, who, "codebook_dim must be in [1, 20]");
+    if (S < 1 || S > VQ_RLFQ_MAX_STAGES) return fail(VQ_E_UNSUPPORTED, who, "stage count must be in [1, 32]");
+    if (!stage_consts) return fail(VQ_E_BADARG, who, "null stage constants");
+    if (G * N > ((int64_t)1 << 40) || rlfq_blocks(N) > 0x7fffffff) return fail(VQ_E_BADARG, who, "too many rows");
     return 0;
 }
 

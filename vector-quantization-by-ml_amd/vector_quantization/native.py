@@ -729,6 +729,23 @@ def _gumbel_args(x, cb, g, metric, packed):
     return a, packed, g_rs, g_hs
 
 
+def _grad_x_out(x, out):
+    """The destination of a *_backward_x sweep ([H, M, D], strided rows ok; allocated when None) and its strides."""
+    if out is None:
+        out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == tuple(x.shape) and out.device == x.device
+    return (out, *_row_strides(out))
+
+
+def _gumbel_workspace(x, K, sizer):
+    """A 16-byte aligned workspace of ``sizer`` (vq_gumbel_workspace_bytes / vq_gumbel_reinmax_workspace_bytes) bytes."""
+    H, M, D = x.shape
+    with torch.cuda.device(x.device):  # (the plan splits the rows over the CUs of the current device)
+        nbytes = int(getattr(load(), sizer)(H, M, K, D))
+    assert nbytes > 0, f"{sizer}: unsupported shape"
+    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=x.device)
+
+
 def gumbel_stats(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, *, metric: int = EUCLID, tau: float = 1.0,
                  packed: torch.Tensor | None = None):
     """Row statistics of the straight-through Gumbel backward: x, g [H, M, D] (strided rows ok), cb [H, K, D] ->
@@ -750,14 +767,8 @@ def gumbel_backward_x(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, lse2: 
     """d/dx of the straight-through Gumbel softmax through the similarities, one fused sweep -> gx [H, M, D]
     (``out``: a destination with strided rows)."""
     a, packed, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
-    H, M, D = x.shape
-    stride = int(load().vq_gumbel_row_stride(M))
-    for t in (lse2, delta):
-        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (H, stride) and t.device == x.device
-    if out is None:
-        out = torch.empty((H, M, D), dtype=torch.float32, device=x.device)
-    assert out.dtype == torch.float32 and tuple(out.shape) == (H, M, D) and out.device == x.device
-    o_rs, o_hs = _row_strides(out)
+    _check_stat_arrays(x, a.M, lse2, delta)
+    out, o_rs, o_hs = _grad_x_out(x, out)
     with torch.cuda.device(x.device):
         _check(load().vq_gumbel_backward_x_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(),
                                                delta.data_ptr(), out.data_ptr(), o_rs, o_hs, _stream_ptr(x.device)),
@@ -774,25 +785,11 @@ def gumbel_backward_codes(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, ls
                           metric: int = EUCLID, tau: float = 1.0) -> torch.Tensor:
     """d/dcodes of the straight-through Gumbel softmax through the similarities -> [H, K, D] (the gather's own scatter
     term is ema_accumulate of g).  Atomics-free: bit-identical from run to run on one device."""
-    _require_gpu(x, cb, g)
-    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and g.dtype == torch.float32
-    assert x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous() and tuple(g.shape) == tuple(x.shape)
-    H, M, D = x.shape
-    K = cb.shape[1]
-    assert cb.shape[0] == H and cb.shape[2] == D and gumbel_codes_supported(H, M, K, D)
-    stride = int(load().vq_gumbel_row_stride(M))
-    for t in (lse2, delta):
-        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (H, stride) and t.device == x.device
-    x_rs, x_hs = _row_strides(x)
-    g_rs, g_hs = _row_strides(g)
-    a = VqArgs()
-    a.H, a.Q, a.M, a.K, a.D, a.metric, a.flags = H, 1, M, K, D, metric, 0
-    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
-    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), K * D, 0
-    gc = torch.empty((H, K, D), dtype=torch.float32, device=x.device)
+    a, g_rs, g_hs = _codes_args(x, cb, g, metric)
+    _check_stat_arrays(x, a.M, lse2, delta)
+    ws = _gumbel_workspace(x, a.K, "vq_gumbel_workspace_bytes")
+    gc = torch.empty((a.H, a.K, a.D), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        nbytes = int(load().vq_gumbel_workspace_bytes(H, M, K, D))
-        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=x.device)
         _check(load().vq_gumbel_backward_codes_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(),
                                                    delta.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws.numel() * 8,
                                                    _stream_ptr(x.device)), "vq_gumbel_backward_codes_f32")
@@ -845,11 +842,7 @@ def gumbel_reinmax_stats(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, *, 
 
 def gumbel_reinmax_workspace(x: torch.Tensor, K: int) -> torch.Tensor:
     """The workspace gumbel_reinmax_columns fills and gumbel_reinmax_backward_codes reuses (vq_gumbel_reinmax_workspace_bytes)."""
-    H, M, D = x.shape
-    with torch.cuda.device(x.device):
-        nbytes = int(load().vq_gumbel_reinmax_workspace_bytes(H, M, K, D))
-    assert nbytes > 0, "vq_gumbel_reinmax: unsupported shape"
-    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=x.device)
+    return _gumbel_workspace(x, K, "vq_gumbel_reinmax_workspace_bytes")
 
 
 def gumbel_reinmax_columns(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, lse2_tau: torch.Tensor, ind: torch.Tensor, *,
@@ -879,14 +872,10 @@ def gumbel_reinmax_backward_x(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor
     """d/dx of the reinmax Gumbel softmax through the similarities, one fused sweep -> gx [H, M, D] (``out``: a destination
     with strided rows).  ``stats``: the triple of gumbel_reinmax_stats; col / e: of gumbel_reinmax_columns."""
     a, packed, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
-    H, M, D = x.shape
-    _check_stat_arrays(x, M, *stats)
+    _check_stat_arrays(x, a.M, *stats)
     _check_stat_arrays(x, a.K, col, e)
     i_rs, i_hs = _check_ind(x, ind)
-    if out is None:
-        out = torch.empty((H, M, D), dtype=torch.float32, device=x.device)
-    assert out.dtype == torch.float32 and tuple(out.shape) == (H, M, D) and out.device == x.device
-    o_rs, o_hs = _row_strides(out)
+    out, o_rs, o_hs = _grad_x_out(x, out)
     with torch.cuda.device(x.device):
         _check(load().vq_gumbel_reinmax_backward_x_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), stats[0].data_ptr(),
                                                        stats[1].data_ptr(), stats[2].data_ptr(), ind.data_ptr(), i_rs, i_hs,

@@ -182,14 +182,10 @@ class _NativeBackend:
         """Fused backward of the straight-through Gumbel softmax through the similarities: (gx | None, gc_sim | None) from
         vq_gumbel_stats_f32 + vq_gumbel_backward_x_f32 / vq_gumbel_backward_codes_f32; None when the shape is outside the
         kernels' range (the caller then works on row chunks)."""
-        H, M, D = x.shape
-        K = cb.shape[1]
-        if D > native.GUMBEL_MAX_DIM or M == 0 or (need_codes and not native.gumbel_codes_supported(H, M, K, D)):
+        ready = _gumbel_inputs(x, cb, g, metric, need_codes)
+        if ready is None:
             return None
-        cb = cb.contiguous()
-        if g.stride(-1) != 1 and g.shape[-1] != 1:
-            g = g.contiguous()
-        packed = native.pack_codebooks(cb, metric)
+        cb, g, packed = ready
         lse2, delta = native.gumbel_stats(x, cb, g, metric=metric, tau=tau, packed=packed)
         gx = native.gumbel_backward_x(x, cb, g, lse2, delta, metric=metric, tau=tau, packed=packed) if need_x else None
         gc = native.gumbel_backward_codes(x, cb, g, lse2, delta, metric=metric, tau=tau) if need_codes else None
@@ -202,19 +198,28 @@ class _NativeBackend:
         vq_gumbel_reinmax_backward_x_f32 / vq_gumbel_reinmax_backward_codes_f32; ``ind`` [H, M] int64 is the selection the
         forward made (any selection: it is only compared with code indices).  None when the shape is outside the kernels'
         range (the caller then works on row chunks)."""
-        H, M, D = x.shape
-        K = cb.shape[1]
-        if D > native.GUMBEL_MAX_DIM or M == 0 or not native.gumbel_codes_supported(H, M, K, D):
+        ready = _gumbel_inputs(x, cb, g, metric, True)  # (the column sweep is codes-resident whatever is asked for)
+        if ready is None:
             return None
-        cb = cb.contiguous()
-        if g.stride(-1) != 1 and g.shape[-1] != 1:
-            g = g.contiguous()
-        packed = native.pack_codebooks(cb, metric)
+        cb, g, packed = ready
         stats = native.gumbel_reinmax_stats(x, cb, g, metric=metric, tau=tau, packed=packed)
         col, e, ws = native.gumbel_reinmax_columns(x, cb, g, stats[0], ind, metric=metric, tau=tau)
         gx = native.gumbel_reinmax_backward_x(x, cb, g, stats, ind, col, e, metric=metric, tau=tau, packed=packed) if need_x else None
         gc = native.gumbel_reinmax_backward_codes(x, cb, g, stats, col, e, ws, metric=metric, tau=tau) if need_codes else None
         return gx, gc
+
+
+def _gumbel_inputs(x, cb, g, metric, codes_resident):
+    """What both fused Gumbel backwards start from: None when the shape is outside the kernels' range (``codes_resident``: a
+    codes-resident sweep will run), else (cb contiguous, g with contiguous dims, the packed codebook)."""
+    H, M, D = x.shape
+    K = cb.shape[1]
+    if D > native.GUMBEL_MAX_DIM or M == 0 or (codes_resident and not native.gumbel_codes_supported(H, M, K, D)):
+        return None
+    cb = cb.contiguous()
+    if g.stride(-1) != 1 and g.shape[-1] != 1:
+        g = g.contiguous()
+    return cb, g, native.pack_codebooks(cb, metric)
 
 
 _backend = _NativeBackend
