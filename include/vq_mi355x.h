@@ -479,6 +479,33 @@ int vq_decode_f32(const float *cb, int64_t cb_gs, int64_t cb_qs, int G, int Q, i
                   void *stream);
 
 /*
+ * vq_lfq_decode_f32 -- indices -> code vectors for LFQ / ResidualLFQ / GroupedResidualLFQ in one pass.  The lookup-free
+ *   family has no table: a code is a function of the index bits alone (replaces lookup_free_quantization.py:193-220,
+ *   residual_lfq.py:80-118,240-252: per stage a cast, an and, a compare, a convert and a scale, then a stack, a masked_fill
+ *   over [Q][N][d] and a reduce over it again).  The conventions are vq_decode_f32's.
+ *   Index (g, n, q), q < Q_given <= Q, is idx[g * idx_gs + n * idx_rs + q * idx_qs] (int32, or int64 when idx_64; strides in
+ *   elements, so any view is read in place); the stages q >= Q_given are dropped.  mag: Q host floats, the magnitude of
+ *   every entry of a stage's codes (read on the host during the call; nothing is allocated).  With
+ *     t_q[j] = +0.0 when stage q is dropped, else +mag[q] when bit d-1-j of the index is set, else -mag[q]
+ *   (MSB first, the modules' mask = 2 ** arange(d-1, -1, -1); only the low 32 bits of an int64 index count, their .int()):
+ *     all_codes[q * all_qs + g * all_gs + n * all_rs + j] = t_q[j]
+ *     codes_sum[g * sum_gs + n * sum_rs + j * sum_ds]     = ((0 + t_0[j]) + t_1[j]) + ...   (one fp32 add per stage, stage order)
+ *   Either output may be NULL, not both.  sum_gs = d, sum_rs = G * d writes a result already concatenated over the groups
+ *   (LFQ's num_codebooks, GroupedResidualLFQ's groups) on the feature axis.
+ *   drop_null = 1 (ResidualLFQ, residual_lfq.py:98): an index EQUAL to -1, the whole int64 value, is a dropped stage and
+ *   nothing else is.  drop_null = 0 (LFQ): -1 is all bits set, the all-positive code.  No index value is invalid and none
+ *   becomes an address.  No host read of device memory, no allocation: the call can be captured in a hipGraph.
+ *   N == 0 returns 0 without a launch.
+ * Errors (VQ_E_BADARG, vq_last_error; the device is not touched): idx or mag NULL, both outputs NULL, d outside [1, 20],
+ *   Q outside [1, VQ_RLFQ_MAX_STAGES], Q_given outside [1, Q], G outside [1, 65535], N negative or N * d beyond 2^39.
+ */
+int vq_lfq_decode_f32(const void *idx, int idx_64, int64_t idx_gs, int64_t idx_rs, int64_t idx_qs, int G, int64_t N,
+                      int Q_given, int Q, int d, const float *mag, int drop_null,
+                      float *codes_sum, int64_t sum_gs, int64_t sum_rs, int64_t sum_ds,   /* may be NULL */
+                      float *all_codes, int64_t all_qs, int64_t all_gs, int64_t all_rs,   /* may be NULL */
+                      void *stream);
+
+/*
  * vq_lq_quantize_f32 -- latent quantization (LatentQuantize): the per-dimension level search of every (batch, position,
  *   codebook) sub-row in one pass, one thread per sub-row of d <= 16 values.  Element i of sub-row (b, p, c) is
  *   z[b * z_bs + p * z_ps + (c * d + i) * z_cs] (strides in elements: a channel-first [B][C * d][P] tensor is z_ps = 1,

@@ -1,9 +1,11 @@
 """Timings of the decode side: ``get_output_from_indices`` / ``get_codes_from_indices`` of ResidualVQ, GroupedResidualVQ and
-VectorQuantize through the fused decode (vq_decode_f32) and through the tensor-op expressions it replaces
-(VQ_NO_FUSED_DECODE=1: the parent's code on the same inputs), alternating round by round in one process (DESIGN.md §18
-quotes these; the raw lines are kept in profiles/decode_bench.md).
+VectorQuantize through the fused decode (vq_decode_f32), those of ResidualLFQ and GroupedResidualLFQ and LFQ's
+``indices_to_codes`` through the lookup-free one (vq_lfq_decode_f32), and all of them through the tensor-op expressions the
+kernels replace (VQ_NO_FUSED_DECODE=1: the parent's code on the same inputs), alternating round by round in one process
+(DESIGN.md §18 quotes these; the raw lines are kept in profiles/decode_bench.md).
 
-    python tools/decode_bench.py            # on the GPU box
+    python tools/decode_bench.py            # on the GPU box: every family
+    python tools/decode_bench.py lfq        # the lookup-free family only
 """
 import os
 import statistics
@@ -56,10 +58,10 @@ def switchable(fn, off):
     return run
 
 
-def report(title, mod, idx, bytes_out, bytes_codes):
+def report(title, mod, idx, bytes_out, bytes_codes, methods=("get_output_from_indices", "get_codes_from_indices")):
     """bytes_*: the algorithmic bytes of the two methods (indices read + output written + the codebooks once)"""
-    print(title)
-    for method, nbytes in (("get_output_from_indices", bytes_out), ("get_codes_from_indices", bytes_codes)):
+    print(title, flush=True)
+    for method, nbytes in zip(methods, (bytes_out, bytes_codes)):
         fn = getattr(mod, method)
         res = interleaved({"fused": switchable(lambda: fn(idx), False), "tensor ops": switchable(lambda: fn(idx), True)})
         os.environ.pop("VQ_NO_FUSED_DECODE", None)
@@ -93,7 +95,36 @@ def single(N, K, D, heads=1, channel_last=True):
     report(f"VectorQuantize N={N} K={K} D={D} heads={heads} channel_last={channel_last}", mod, idx, nbytes, nbytes)
 
 
+def residual_lfq(N, Q, d):
+    mod = vq.ResidualLFQ(dim=d, num_quantizers=Q, codebook_size=2**d).to(DEV).eval()
+    idx = torch.randint(0, 2**d, (16, N // 16, Q), device=DEV)
+    report(f"ResidualLFQ N={N} Q={Q} d={d}", mod, idx, N * Q * 8 + N * d * 4, N * Q * 8 + Q * N * d * 4)
+
+
+def grouped_lfq(N, G, Q, d):
+    mod = vq.GroupedResidualLFQ(dim=G * d, groups=G, num_quantizers=Q, codebook_size=2**d).to(DEV).eval()
+    idx = torch.randint(0, 2**d, (G, 16, N // 16, Q), device=DEV)
+    report(f"GroupedResidualLFQ N={N} G={G} Q={Q} d={d}", mod, idx, G * (N * Q * 8 + N * d * 4), G * (N * Q * 8 + Q * N * d * 4))
+
+
+def single_lfq(N, c, d):
+    mod = vq.LFQ(codebook_size=2**d, num_codebooks=c).to(DEV).eval()
+    idx = torch.randint(0, 2**d, (16, N // 16, c) if c > 1 else (16, N // 16), device=DEV)
+    report(f"LFQ N={N} num_codebooks={c} d={d}", mod, idx, c * (N * 8 + N * d * 4), 0, methods=("indices_to_codes",))
+
+
+def lookup_free():
+    for N in (65536, 4096):
+        residual_lfq(N, 8, 10)
+        grouped_lfq(N, 4, 8, 16)
+        single_lfq(N, 1, 18)
+        single_lfq(N, 4, 8)
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["lfq"]:
+        lookup_free()
+        sys.exit(0)
     residual(65536, 8, 1024, 256)
     residual(65536, 8, 8192, 64)
     grouped(65536, 4, 8, 1024, 64)
@@ -102,3 +133,4 @@ if __name__ == "__main__":
     single(262144, 1024, 256)  # one shared codebook: codes[indices] on both sides (not dispatched to the fused decode), a control
     residual(65536, 8, 1024, 30)  # D % 4 != 0: the one-thread-per-element kernel
     residual(4096, 8, 1024, 256)  # few rows: launches and the wrappers' host time
+    lookup_free()

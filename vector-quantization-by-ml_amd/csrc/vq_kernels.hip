@@ -43,11 +43,13 @@
 //   vq_affine.inc        affine re-parameterisation: one-read column mean / squared deviations (Welford lanes, Chan merges),
 //                        the moment-matching transform of the codes and of the accumulated EMA sums
 //   vq_decode.inc        indices -> code vectors: every stage's gather and their stage-ordered sum in one pass (vq_decode_f32)
+//   vq_lfq_decode.inc    the same for the lookup-free family: codes from the index bits, no table (vq_lfq_decode_f32)
 //   this file           host-side dispatch and the C ABI (include/vq_mi355x.h)
 //
 // Reference lines replaced (relative to the reference root): vector_quantization/codebooks.py:386-397,
 // utils/general.py:126-136,159-163, vector_quantize_pytorch.py:261-279,361-364, residual_vq.py:212-243; the decode side
-// (vq_decode.inc): vector_quantize_pytorch.py:156-180, residual_vq.py:94-132,293-305.
+// (vq_decode.inc): vector_quantize_pytorch.py:156-180, residual_vq.py:94-132,293-305; (vq_lfq_decode.inc):
+// lookup_free_quantization.py:193-220, residual_lfq.py:80-118,240-252.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -64,7 +66,7 @@
 // the same file once per part (-DVQ_PART=n, in parallel) and links the objects: every part sees the same templates, but only
 // its own launchers are defined -- and with them instantiated -- there; the other parts call them through the
 // vqi::part_* entry points declared below.
-//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ, affine, decode) 4 search Dp = 512 + wave-pair kernel
+//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ, affine, decodes) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward
 //   7 Gumbel straight-through backward sweeps               8 Gumbel-max sampling sweeps + Gumbel reinmax backward sweeps
@@ -98,6 +100,7 @@ namespace {
 #include "vq_lq.inc"
 #include "vq_affine.inc"
 #include "vq_decode.inc"
+#include "vq_lfq_decode.inc"
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -2194,6 +2197,28 @@ int vq_decode_f32(const float *cb, int64_t cb_gs, int64_t cb_qs, int G, int Q, i
     p.sum = codes_sum; p.sum_gs = sum_gs; p.sum_rs = sum_rs; p.sum_ds = sum_ds;
     p.all = all_codes; p.all_qs = all_qs; p.all_gs = all_gs; p.all_rs = all_rs;
     return decode_launch(p, device_cus(), (hipStream_t)stream);
+}
+
+int vq_lfq_decode_f32(const void *idx, int idx_64, int64_t idx_gs, int64_t idx_rs, int64_t idx_qs, int G, int64_t N, int Q_given,
+                      int Q, int d, const float *mag, int drop_null, float *codes_sum, int64_t sum_gs, int64_t sum_rs,
+                      int64_t sum_ds, float *all_codes, int64_t all_qs, int64_t all_gs, int64_t all_rs, void *stream) {
+    const char *who = "vq_lfq_decode";
+    if (!idx || !mag) return fail(VQ_E_BADARG, who, "idx or mag is null");
+    if (!codes_sum && !all_codes) return fail(VQ_E_BADARG, who, "both outputs are null");
+    if (d < 1 || d > kLfqMaxDim) return fail(VQ_E_BADARG, who, "d must be in [1, 20]");
+    if (Q < 1 || Q > VQ_RLFQ_MAX_STAGES) return fail(VQ_E_BADARG, who, "Q must be in [1, 32]");
+    if (Q_given < 1 || Q_given > Q) return fail(VQ_E_BADARG, who, "Q_given must be in [1, Q]");
+    if (G < 1 || G > 65535 || N < 0) return fail(VQ_E_BADARG, who, "G must be in [1, 65535] and N non-negative");
+    if (N > (int64_t)0x7fffffff * kLfqDecodeThreads / d - kLfqDecodeThreads) return fail(VQ_E_BADARG, who, "too many rows");
+    if (N == 0) return 0;
+    LfqDecodeParams p;
+    memset(&p, 0, sizeof(p));
+    p.idx = idx; p.idx64 = idx_64 != 0; p.idx_gs = idx_gs; p.idx_rs = idx_rs; p.idx_qs = idx_qs;
+    p.N = N; p.Q = Q; p.Qg = Q_given; p.d = d; p.drop_null = drop_null != 0;
+    p.sum = codes_sum; p.sum_gs = sum_gs; p.sum_rs = sum_rs; p.sum_ds = sum_ds;
+    p.all = all_codes; p.all_qs = all_qs; p.all_gs = all_gs; p.all_rs = all_rs;
+    for (int q = 0; q < Q; ++q) p.mag[q] = mag[q];
+    return lfq_decode_launch(p, G, (hipStream_t)stream);
 }
 
 int64_t vq_lq_workspace_bytes(int64_t B, int64_t P, int C) {

@@ -1,8 +1,10 @@
 """Lookup-free quantization (LFQ, https://arxiv.org/abs/2310.05737), the reference's ``LFQ``
-(``vector_quantization/lookup_free_quantization.py:31-397``) with its two sweeps in HIP:
+(``vector_quantization/lookup_free_quantization.py:31-397``) with its sweeps in HIP:
 
 - the quantize step (signs -> +-a, int64 indices MSB first, straight-through value, commitment squared-error sum) is
   ``vq_lfq_quantize_f32``, one pass over the rows;
+- the decode side, ``indices_to_codes``, is ``vq_lfq_decode_f32``: the codes of every codebook from the index bits in one
+  pass, written side by side (device int32 / int64 indices; ``VQ_NO_FUSED_DECODE=1`` and CPU indices keep the tensor ops);
 - the entropy aux loss is ``vq_lfq_entropy_fwd_f32`` / ``vq_lfq_entropy_bwd_f32``.  The reference builds the
   ``[rows, 2^d]`` softmax several times over; here the softmax over ``{+-a}^d`` is factorised per dim
   (``p_k = A_u * B_w``, two tables of at most 1024 entries per row), so no buffer grows with ``rows * 2^d``.
@@ -16,14 +18,14 @@ from __future__ import annotations
 
 from collections import namedtuple
 from functools import partial
-from math import ceil, log2
+from math import ceil, log2, prod
 
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 from torch import nn
 
-from . import native
+from . import native, search
 
 Return = namedtuple("Return", ["quantized", "indices", "entropy_aux_loss"])
 
@@ -246,9 +248,23 @@ class LFQ(nn.Module):
         should_transpose = self.channel_first
         if not self.keep_num_codebooks_dim:
             indices = indices[..., None]
-        bits = ((indices[..., None].int() & self.mask) != 0).to(self.dtype)
-        codes = self.maybe_l2norm(self.bits_to_codes(bits))
-        codes = codes.reshape(*codes.shape[:-2], -1)
+        decode = search.lfq_decode_backend(indices) if self.dtype == torch.float32 else None
+        if decode is not None:
+            # one pass (vq_lfq_decode_f32): the codebooks are the kernel's group axis, their codes land side by side
+            C, d = self.num_codebooks, self.codebook_dim
+            lead = indices.shape[:-1]
+            flat = indices.reshape(prod(lead), C)
+            if torch.compiler.is_compiling():  # (the registered op returns fresh tensors)
+                codes = decode(flat.t()[..., None], (self._code_mag,), d, drop_null=False)[0].transpose(0, 1)
+            else:
+                codes = torch.empty((flat.shape[0], C * d), dtype=torch.float32, device=indices.device)
+                decode(flat.t()[..., None], (self._code_mag,), d, drop_null=False,
+                       sum_out=codes.view(flat.shape[0], C, d).transpose(0, 1))
+            codes = codes.reshape(*lead, C * d)
+        else:
+            bits = ((indices[..., None].int() & self.mask) != 0).to(self.dtype)
+            codes = self.maybe_l2norm(self.bits_to_codes(bits))
+            codes = codes.reshape(*codes.shape[:-2], -1)
         if project_out:
             codes = self.project_out(codes)
         if should_transpose:

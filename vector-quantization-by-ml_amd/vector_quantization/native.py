@@ -218,6 +218,9 @@ def load():
                                       _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _i64,
                                       _i64, _vp]
         lib.vq_decode_f32.restype = ctypes.c_int
+        lib.vq_lfq_decode_f32.argtypes = [_vp, ctypes.c_int, _i64, _i64, _i64, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, _vp, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp]
+        lib.vq_lfq_decode_f32.restype = ctypes.c_int
         lib.vq_lq_workspace_bytes.argtypes = [_i64, _i64, ctypes.c_int]
         lib.vq_lq_workspace_bytes.restype = _i64
         lib.vq_lq_quantize_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64,
@@ -249,7 +252,7 @@ EXPORTED_SYMBOLS = (
     "vq_gumbel_reinmax_workspace_bytes", "vq_gumbel_reinmax_stats_f32", "vq_gumbel_reinmax_columns_f32",
     "vq_gumbel_reinmax_backward_x_f32", "vq_gumbel_reinmax_backward_codes_f32",
     "vq_affine_stats_workspace_bytes", "vq_affine_stats_f32", "vq_affine_apply_f32",
-    "vq_decode_f32",
+    "vq_decode_f32", "vq_lfq_decode_f32",
 )
 
 
@@ -1409,6 +1412,58 @@ def decode_codes(cb: torch.Tensor, indices: torch.Tensor, *, num_stages: int | N
                                  codes_sum.data_ptr() if codes_sum is not None else None, *s,
                                  all_codes.data_ptr() if all_codes is not None else None, *a, _stream_ptr(dev)),
                "vq_decode_f32")
+    return codes_sum, all_codes
+
+
+# ------------------------------------------------------------------------------------------------
+# indices -> code vectors of the lookup-free family (vq_lfq_decode_f32 in include/vq_mi355x.h)
+# ------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=256)
+def _lfq_mag_arg(mag: tuple):
+    """Host fp32 copy of the stage magnitudes (the C ABI reads them on the host during the call)."""
+    return (ctypes.c_float * len(mag))(*mag)
+
+
+def lfq_decode(indices: torch.Tensor, mag, d: int, *, drop_null: bool = True, want_sum: bool = True, want_all: bool = False,
+               sum_out: torch.Tensor | None = None, all_out: torch.Tensor | None = None):
+    """indices [G, N, Qg] int32 / int64 of any strides, mag = one code magnitude per stage (Q = len(mag) >= Qg floats: the
+    later stages are dropped), d bits per index -> (codes_sum [G, N, d] or None, all_codes [Q, G, N, d] or None).
+
+    Dim j of stage q is +mag[q] where bit d-1-j of the index is set, else -mag[q]; only the low 32 bits of an int64 index
+    count.  ``drop_null``: an index equal to -1 is a dropped stage (+0.0).  codes_sum is ((0 + t_0) + t_1) + ... in fp32.
+    ``sum_out`` ([G, N, d] view, ANY strides: a group-concatenated destination) and ``all_out`` ([Q, G, N, d] view, last
+    dim contiguous) are written in place when given."""
+    if not indices.is_cuda:
+        _require_gpu(indices)
+    lib = load()
+    G, N, Qg = indices.shape
+    Q = len(mag)
+    dev = indices.device
+    assert indices.dtype in (torch.int32, torch.int64), "indices must be [G, N, Qg] int32 / int64"
+    assert 1 <= Qg <= Q <= RLFQ_MAX_STAGES and 1 <= d <= LFQ_MAX_DIM and (want_sum or want_all)
+    codes_sum = all_codes = None
+    sp = ap = None
+    s0 = s1 = a0 = a1 = a2 = 0
+    s2 = 1
+    if want_sum:
+        codes_sum = sum_out if sum_out is not None else torch.empty((G, N, d), dtype=torch.float32, device=dev)
+        assert codes_sum.dtype == torch.float32 and codes_sum.shape == (G, N, d) and codes_sum.device == dev
+        sp = codes_sum.data_ptr()
+        s0, s1, s2 = codes_sum.stride()
+    if want_all:
+        all_codes = all_out if all_out is not None else torch.empty((Q, G, N, d), dtype=torch.float32, device=dev)
+        assert all_codes.dtype == torch.float32 and all_codes.shape == (Q, G, N, d) and all_codes.device == dev
+        ap = all_codes.data_ptr()
+        a0, a1, a2, a3 = all_codes.stride()
+        assert a3 == 1 or d == 1, "all_out: last dim must be contiguous"
+    if N == 0:
+        return codes_sum, all_codes
+    i0, i1, i2 = indices.stride()
+    with torch.cuda.device(dev):
+        rc = lib.vq_lfq_decode_f32(indices.data_ptr(), indices.dtype == torch.int64, i0, i1, i2, G, N, Qg, Q, d,
+                                   _lfq_mag_arg(tuple(mag)), drop_null, sp, s0, s1, s2, ap, a0, a1, a2, _stream_ptr(dev))
+    if rc:
+        _check(rc, "vq_lfq_decode_f32")
     return codes_sum, all_codes
 
 

@@ -12,6 +12,8 @@ instead of breaking the graph at an opaque Python call:
     torch.ops.vq_mi355x.rlfq_quantize / rlfq_backward / lfq_entropy_staged_fwd / lfq_entropy_staged_bwd
         (residual LFQ, native.rlfq_* and native.lfq_entropy_staged_*)
     torch.ops.vq_mi355x.fsq_quantize / fsq_backward / fsq_decode   (finite scalar quantization, native.fsq_*)
+    torch.ops.vq_mi355x.lfq_decode(indices, mag, d, drop_null, want_sum, want_all) -> (codes_sum, all_codes)
+        (indices -> code vectors of the lookup-free family, native.lfq_decode)
     torch.ops.vq_mi355x.lq_quantize / lq_backward   (latent quantization, native.lq_*)
     torch.ops.vq_mi355x.decode_codes(cb, indices, num_stages, drop_null, want_sum, want_all) -> (codes_sum, all_codes)
         (indices -> code vectors, native.decode_codes; differentiable with respect to cb)
@@ -230,6 +232,28 @@ def _(indices, levels, scales, drop_null, want_sum, want_all):
     N, Q = indices.shape
     d = len(levels)
     return scales.new_empty((N, d) if want_sum else (0,)), scales.new_empty((Q, N, d) if want_all else (0,))
+
+
+# indices -> code vectors of the lookup-free family (native.lfq_decode): the codes are a function of the index bits, so the
+# op has no differentiable input.  An output that was not requested comes back as an empty tensor.
+@torch.library.custom_op(f"{_LIB_NS}::lfq_decode", mutates_args=())
+def lfq_decode(indices: torch.Tensor, mag: list[float], d: int, drop_null: bool, want_sum: bool,
+               want_all: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    """indices [G, N, Qg], one magnitude per stage -> (codes summed over the stages [G, N, d] (or empty), all codes
+    [Q, G, N, d] (or empty))."""
+    codes_sum, all_codes = native.lfq_decode(indices, mag, d, drop_null=drop_null, want_sum=want_sum, want_all=want_all)
+    if codes_sum is None:
+        codes_sum = indices.new_empty((0,), dtype=torch.float32)
+    if all_codes is None:
+        all_codes = indices.new_empty((0,), dtype=torch.float32)
+    return codes_sum, all_codes
+
+
+@lfq_decode.register_fake
+def _(indices, mag, d, drop_null, want_sum, want_all):
+    G, N, _ = indices.shape
+    return (indices.new_empty((G, N, d) if want_sum else (0,), dtype=torch.float32),
+            indices.new_empty((len(mag), G, N, d) if want_all else (0,), dtype=torch.float32))
 
 
 # indices -> code vectors (native.decode_codes).  An output that was not requested comes back as an empty tensor.

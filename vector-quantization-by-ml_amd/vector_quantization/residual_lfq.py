@@ -13,20 +13,25 @@ Fallback path.  A stage-by-stage loop over the module's own ``LFQ`` layers, line
 serves configurations the fused kernels do not cover: a straight-through activation other than ``nn.Identity``, more than
 ``MAX_FUSED_STAGES`` active stages, ``channel_first`` / several codebooks per layer, ``accept_image_fmap`` groups.
 
-Both paths run only on the GPU: CPU tensors raise ``native.NativeUnavailable`` (``get_codes_from_indices``,
-``get_output_from_indices`` and ``codebooks`` are pure torch and work anywhere).  DESIGN.md section 11 states the accuracy
-contract between the two paths and against the reference.
+Both paths run only on the GPU: CPU tensors raise ``native.NativeUnavailable`` (``codebooks`` is pure torch and works
+anywhere).  DESIGN.md section 11 states the accuracy contract between the two paths and against the reference.
+
+Decode side.  ``get_codes_from_indices`` and ``get_output_from_indices`` of device indices are one HIP pass
+(``vq_lfq_decode_f32``: every stage's code from its index bits, the stage-ordered sum, dropped stages as +0.0), for
+``GroupedResidualLFQ`` one pass over all groups with the sum written into the concatenated result.  CPU indices,
+``VQ_NO_FUSED_DECODE=1`` and stacks deeper than ``MAX_FUSED_STAGES`` keep the tensor-op expressions, which work anywhere
+(DESIGN.md section 18).
 """
 from __future__ import annotations
 
 import random
-from math import ceil, log2
+from math import ceil, log2, prod
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import native
+from . import native, search
 from .lookup_free_quantization import _EPS, LFQ, _entropy, _maybe_distributed_mean
 
 MAX_FUSED_STAGES = native.RLFQ_MAX_STAGES
@@ -226,6 +231,8 @@ class ResidualLFQ(nn.Module):
                 soft_clamp_input_value *= 0.5
 
         assert all([not lfq.has_projections for lfq in self.layers])
+        # one code magnitude per stage, as bits_to_codes gives it (unnormalised: +-codebook_scale), for the fused decode
+        self._stage_mags = tuple(float(lfq.codebook_scale) for lfq in self.layers)
 
         self.quantize_dropout = quantize_dropout and num_quantizers > 1
         assert quantize_dropout_cutoff_index >= 0
@@ -236,16 +243,35 @@ class ResidualLFQ(nn.Module):
     def codebooks(self):
         return torch.stack([layer.codebook for layer in self.layers], dim=0)
 
-    def get_codes_from_indices(self, indices):
-        """indices [b, ..., q] (q <= num_quantizers; -1 = dropped) -> codes [num_quantizers, b, ..., codebook_dim], the
-        unnormalised codes (bits_to_codes) of each stage, zero where dropped.  Computed from the index bits."""
-        quantize_dim = indices.shape[-1]
+    def _decode(self, decode, indices, want_sum, want_all):
+        """The fused decode (vq_lfq_decode_f32) of indices [b, ..., q]: (sum [b, ..., d] | None, all [Q, b, ..., d] | None)."""
         lead = indices.shape[:-1]
-        indices = indices.reshape(lead[0] if len(lead) else 1, -1, quantize_dim)
+        flat = indices.reshape(1, prod(lead), indices.shape[-1])
+        s, a = decode(flat, self._stage_mags, self.codebook_dim, drop_null=True, want_sum=want_sum, want_all=want_all)
+        if s is not None:
+            s = s.reshape(*lead, self.codebook_dim)
+        if a is not None:
+            a = a.reshape(self.num_quantizers, *lead, self.codebook_dim)
+        return s, a
+
+    def _check_stage_count(self, quantize_dim):
         if quantize_dim < self.num_quantizers:
             assert self.quantize_dropout > 0.0, (
                 "quantize dropout must be greater than 0 if you wish to reconstruct from a signal with less fine quantizations"
             )
+
+    def get_codes_from_indices(self, indices):
+        """indices [b, ..., q] (q <= num_quantizers; -1 = dropped) -> codes [num_quantizers, b, ..., codebook_dim], the
+        unnormalised codes (bits_to_codes) of each stage, zero where dropped.  Computed from the index bits."""
+        quantize_dim = indices.shape[-1]
+        decode = search.lfq_decode_backend(indices, self.num_quantizers)
+        if decode is not None:
+            self._check_stage_count(quantize_dim)
+            return self._decode(decode, indices, False, True)[1]
+        lead = indices.shape[:-1]
+        indices = indices.reshape(lead[0] if len(lead) else 1, -1, quantize_dim)
+        self._check_stage_count(quantize_dim)
+        if quantize_dim < self.num_quantizers:
             indices = F.pad(indices, (0, self.num_quantizers - quantize_dim), value=-1)
         dropped = indices == -1
         indices = indices.masked_fill(dropped, 0)
@@ -258,6 +284,10 @@ class ResidualLFQ(nn.Module):
         return all_codes.reshape(self.num_quantizers, *lead, all_codes.shape[-1])
 
     def get_output_from_indices(self, indices):
+        decode = search.lfq_decode_backend(indices, self.num_quantizers)
+        if decode is not None:
+            self._check_stage_count(indices.shape[-1])
+            return self.project_out(self._decode(decode, indices, True, False)[0])
         codes = self.get_codes_from_indices(indices)
         return self.project_out(codes.sum(dim=0))
 
@@ -328,6 +358,11 @@ class GroupedResidualLFQ(nn.Module):
         self.rvqs = nn.ModuleList([])
         for _ in range(groups):
             self.rvqs.append(ResidualLFQ(dim=dim_per_group, **kwargs))
+        # ONE decode launch serves every group when the stacks agree in depth, bits per index and stage scales (they do by
+        # construction: every group gets the same arguments)
+        rvq0 = self.rvqs[0]
+        self._uniform_stacks = all(rvq.codebook_dim == rvq0.codebook_dim and rvq._stage_mags == rvq0._stage_mags
+                                   for rvq in self.rvqs)
 
     @property
     def codebooks(self):
@@ -337,11 +372,48 @@ class GroupedResidualLFQ(nn.Module):
     def split_dim(self):
         return 1 if self.accept_image_fmap else -1
 
+    def _decode_backend(self, indices):
+        """The fused decode when one launch serves every group: a stacked index tensor and uniform stacks."""
+        if not (self._uniform_stacks and isinstance(indices, torch.Tensor) and indices.dim() >= 2
+                and indices.shape[0] == self.groups):
+            return None
+        return search.lfq_decode_backend(indices, self.rvqs[0].num_quantizers)
+
     def get_codes_from_indices(self, indices):
+        decode = self._decode_backend(indices)
+        if decode is not None:
+            rvq0 = self.rvqs[0]
+            G, Q, d = self.groups, rvq0.num_quantizers, rvq0.codebook_dim
+            lead = indices.shape[1:-1]
+            rvq0._check_stage_count(indices.shape[-1])
+            flat = indices.reshape(G, prod(lead), indices.shape[-1])
+            if _compiling():  # (the registered op returns fresh tensors)
+                codes = decode(flat, rvq0._stage_mags, d, drop_null=True, want_sum=False, want_all=True)[1].transpose(0, 1)
+            else:
+                codes = torch.empty((G, Q, flat.shape[1], d), dtype=torch.float32, device=indices.device)
+                decode(flat, rvq0._stage_mags, d, drop_null=True, want_sum=False, want_all=True, all_out=codes.transpose(0, 1))
+            return codes.reshape(G, Q, *lead, d)
         codes = tuple(rvq.get_codes_from_indices(chunk_indices) for rvq, chunk_indices in zip(self.rvqs, indices))
         return torch.stack(codes)
 
     def get_output_from_indices(self, indices):
+        decode = self._decode_backend(indices)
+        if decode is not None:
+            rvq0 = self.rvqs[0]
+            G, d = self.groups, rvq0.codebook_dim
+            lead = indices.shape[1:-1]
+            rvq0._check_stage_count(indices.shape[-1])
+            flat = indices.reshape(G, prod(lead), indices.shape[-1])
+            N = flat.shape[1]
+            mags = rvq0._stage_mags
+            if self.split_dim == -1 and not rvq0.has_projections and not _compiling():
+                # every group's sum lands in its columns of the concatenated result
+                out = torch.empty((N, G * d), dtype=torch.float32, device=indices.device)
+                decode(flat, mags, d, drop_null=True, sum_out=out.view(N, G, d).transpose(0, 1))
+                return out.view(*lead, G * d)
+            sums, _ = decode(flat, mags, d, drop_null=True)
+            outputs = tuple(rvq.project_out(sums[g].reshape(*lead, d)) for g, rvq in enumerate(self.rvqs))
+            return torch.cat(outputs, dim=self.split_dim)
         outputs = tuple(rvq.get_output_from_indices(chunk_indices) for rvq, chunk_indices in zip(self.rvqs, indices))
         return torch.cat(outputs, dim=self.split_dim)
 

@@ -178,6 +178,18 @@ class _NativeBackend:
                                    want_all=want_all, sum_out=sum_out, all_out=all_out)
 
     @staticmethod
+    def lfq_decode(indices, mag, d, *, drop_null=True, want_sum=True, want_all=False, sum_out=None, all_out=None):
+        """Indices -> code vectors of the lookup-free family in one pass (vq_lfq_decode_f32): indices [G, N, Qg], one code
+        magnitude per stage -> (codes_sum [G, N, d] | None, all_codes [len(mag), G, N, d] | None); see native.lfq_decode."""
+        if torch.compiler.is_compiling() and sum_out is None and all_out is None:
+            from . import ops
+
+            s, a = ops.lfq_decode(indices, list(mag), d, drop_null, want_sum, want_all)
+            return (s if want_sum else None), (a if want_all else None)
+        return native.lfq_decode(indices, mag, d, drop_null=drop_null, want_sum=want_sum, want_all=want_all,
+                                 sum_out=sum_out, all_out=all_out)
+
+    @staticmethod
     def gumbel_backward(x, cb, g, *, metric, tau, need_x=True, need_codes=True):
         """Fused backward of the straight-through Gumbel softmax through the similarities: (gx | None, gc_sim | None) from
         vq_gumbel_stats_f32 + vq_gumbel_backward_x_f32 / vq_gumbel_backward_codes_f32; None when the shape is outside the
@@ -368,6 +380,19 @@ def decode_backend(cb: torch.Tensor, indices) -> Optional[object]:
         return None
     if not (isinstance(indices, torch.Tensor) and cb.is_cuda and indices.is_cuda and cb.dtype == torch.float32
             and indices.dtype in (torch.int32, torch.int64)):
+        return None
+    return fn
+
+
+def lfq_decode_backend(indices, num_stages: int = 1) -> Optional[object]:
+    """The backend's ``lfq_decode`` when the fused decode of the lookup-free family takes this call, else None (the caller
+    keeps its tensor-op expression): the rule of ``decode_backend`` -- a backend that has one, device int32 / int64 indices,
+    no VQ_NO_FUSED_DECODE=1 in the environment (read per call) -- and a stack the kernel's argument block holds."""
+    fn = getattr(_backend, "lfq_decode", None)
+    if fn is None or os.environ.get("VQ_NO_FUSED_DECODE") == "1":
+        return None
+    if not (isinstance(indices, torch.Tensor) and indices.is_cuda and indices.dtype in (torch.int32, torch.int64)
+            and num_stages <= native.RLFQ_MAX_STAGES):
         return None
     return fn
 
