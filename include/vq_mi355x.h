@@ -265,6 +265,26 @@ int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_l
                        int64_t tgt_hs, const float *coef, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream);
 
 /*
+ * The same backward when the codebook has been rewritten between forward and backward.  In the reference the EMA step
+ * overwrites the codes through .data right after the similarities were computed (codebooks.py:418-425), which autograd does
+ * not see: the backward of the cross entropy (vector_quantize_pytorch.py:284-299,338-346) then multiplies the ratio matrix,
+ * computed from the OLD similarities, with the UPDATED codebook.  Per head, with x [M, D], c [K, D] the codes the forward
+ * searched (a->packed), l [K, D] the live codes at backward time (live_cb natural, live_packed its packed image: same K, D
+ * and metric as c), s = similarities(x, c) and
+ *   gs_mk = coef * [t_m >= 0] * (softmax_k(s_m)_k - [k == t_m]):
+ *   dot     grad_x_m = sum_k gs_mk l_k
+ *   Euclid  r_mk = gs_mk / s_mk (0 where s_mk == 0, ATen's mask);  grad_x_m = x_m sum_k r_mk - sum_k r_mk l_k
+ * Everything that decides the weights comes from c (the similarity sweep, lse, target_logit, the zero-distance mask, the
+ * sum of the ratios, the factor of the one-hot term); everything they are multiplied with from l.  a->cb is not read.
+ * live_cb == a->cb with live_packed == a->packed is legal; with l bit-equal to c the result is vq_ce_backward_f32's
+ * (its one-wave kernel, VQ_CE_NO_ROLES=1) bit for bit.  D <= 256: VQ_E_UNSUPPORTED beyond (two tile rings of wider rows do
+ * not fit in LDS; use row chunks of vq_similarities_f32).  The other arguments are vq_ce_backward_f32's.
+ */
+int vq_ce_backward_live_f32(const vq_args *a, const float *live_cb, int64_t live_cb_hs, const float *live_packed, int64_t live_pk_hs,
+                            const float *lse, const float *target_logit, const int64_t *target, int64_t tgt_rs, int64_t tgt_hs,
+                            const float *coef, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream);
+
+/*
  * Backward of the straight-through Gumbel softmax over the similarities (utils/general.py:147-149 with
  * codebooks.py:386-395), nothing of [M, K] in memory.  With s = similarities, g = dL/dquantize, a = g c^T, tau = 1 / temperature:
  *   p = softmax_k(tau s), delta_m = sum_k p_mk a_mk, w = tau p (a - delta) = dL/ds, and through the similarities

@@ -221,10 +221,83 @@ def half_inference():
           f"{th:.3f} ms ({262144 / th / 1e3:.1f} M rows/s)")
 
 
+def _rounds(variants, rounds=7, n=3, warm=2):
+    """variants {name: fn}: the variants alternate in this process, `rounds` rounds of `n` calls each between HIP events after
+    `warm` untimed calls -> {name: (median ms, min, max)}."""
+    times = {name: [] for name in variants}
+    for name, fn in variants.items():
+        for _ in range(warm):
+            fn()
+    for _ in range(rounds):
+        for name, fn in variants.items():
+            times[name].append(timed(fn, n=n, warm=0))
+    return {name: (sorted(t)[len(t) // 2], min(t), max(t)) for name, t in times.items()}
+
+
+def _with_env(name, fn):
+    def run():
+        os.environ[name] = "1"
+        try:
+            fn()
+        finally:
+            os.environ.pop(name, None)
+    return run
+
+
+def ce_live():
+    """The cross-entropy commitment step with the EMA update RUNNING (not frozen): backward through vq_ce_backward_live_f32
+    against the chunked path (VQ_CE_NO_LIVE=1), module forward + backward; then the live kernel alone against
+    vq_ce_backward_f32 on the same inputs.  `python tools/loss_bench.py ce_live`"""
+    dev = "cuda:0"
+    for shape, K in (((256, 1024, 256), 1024), ((64, 1024, 64), 8192), ((64, 1024, 128), 1024), ((64, 1024, 32), 1024)):
+        D = shape[-1]
+        mod = vq.VectorQuantize(dim=D, codebook_params=CodebookParams(dim=D, codebook_size=K, threshold_ema_dead_code=0),
+                                commitment_use_cross_entropy_loss=True).to(dev).train()
+        xs = torch.randn(*shape, device=dev, requires_grad=True)
+
+        def step():
+            xs.grad = None
+            q, i, loss = mod(xs)
+            loss.sum().backward()
+
+        def step_frozen():
+            xs.grad = None
+            q, i, loss = mod(xs, freeze_codebook=True)
+            loss.sum().backward()
+
+        res = _rounds({"fused live": step, "chunked (VQ_CE_NO_LIVE=1)": _with_env("VQ_CE_NO_LIVE", step), "frozen codebook": step_frozen})
+        for name, (med, lo, hi) in res.items():
+            print(f"CE commitment step, EMA update, x {list(shape)} K={K}: {name:27s} {med:8.3f} ms ({lo:.3f} - {hi:.3f})")
+        del mod, xs
+    g = torch.Generator(device=dev).manual_seed(0)
+    for M, K, D in ((262144, 1024, 256), (65536, 8192, 64), (65536, 1024, 128), (65536, 1024, 32)):
+        x = torch.randn((1, M, D), device=dev, generator=g)
+        cb = torch.randn((1, K, D), device=dev, generator=g)
+        live = 0.8 * cb + 0.2 * torch.randn((1, K, D), device=dev, generator=g)
+        tgt = torch.randint(0, K, (1, M), device=dev, generator=g)
+        pk, lpk = native.pack_codebooks(cb, 0), native.pack_codebooks(live, 0)
+        lse, tl = native.softmax_stats(x, cb, target=tgt, packed=pk)
+        coef = torch.tensor([1.0 / M], device=dev)
+        variants = {
+            "live": lambda: native.ce_backward(x, cb, lse, tl, tgt, coef, packed=pk, live=live, live_packed=lpk),
+            "not live": lambda: native.ce_backward(x, cb, lse, tl, tgt, coef, packed=pk),
+        }
+        if D > 128:
+            variants["not live, VQ_CE_NO_ROLES=1"] = _with_env("VQ_CE_NO_ROLES", variants["not live"])
+        f = 4.0 * M * K * D
+        for name, (med, lo, hi) in _rounds(variants, n=5).items():
+            print(f"CE backward kernel M={M} K={K} D={D}: {name:27s} {med:8.3f} ms ({lo:.3f} - {hi:.3f})  {f / med / 1e9:6.1f} TFLOP/s "
+                  f"({f / med / 1e9 / 157.3:.3f} of peak)")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["ce_live"]:
+        ce_live()
+        sys.exit(0)
     half_inference()
     main()
     train_steps()
     train_backward()
     rvq_train()
     cfg1_latency()
+    ce_live()

@@ -68,7 +68,7 @@
 // vqi::part_* entry points declared below.
 //   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ, affine, decodes) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
-//   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward
+//   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward (+ live codes)
 //   7 Gumbel straight-through backward sweeps               8 Gumbel-max sampling sweeps + Gumbel reinmax backward sweeps
 #ifndef VQ_PART
 #define VQ_PART -1
@@ -384,6 +384,18 @@ int launch_ce_bwd_m(const CeBwdParams &p, int H, int metric, hipStream_t s) {
     });
 }
 
+// live codes (Dp <= 256): the one-wave body with a second tile ring, whatever VQ_CE_NO_ROLES says
+template <int DP>
+int launch_ce_bwd_live_m(const CeBwdLiveParams &p, int H, int metric, hipStream_t s) {
+    return with_metric(metric, [&](auto m) {
+        constexpr int ME = decltype(m)::value;
+        constexpr int rows = 32 * CeLiveGeo<DP>::WAVES;
+        return launch<vq_ce_backward<DP, ME, true, CeLiveGeo<DP>::WAVES>, kBigLds>(dim3((unsigned)((p.M + rows - 1) / rows), (unsigned)H, 1),
+                                                                                   dim3(CeLiveGeo<DP>::WAVES * 64), CeLiveGeo<DP>::LDS_B, s,
+                                                                                   "vq_ce_backward (live) launch", p);
+    });
+}
+
 // Gumbel-max sampling: the kAuxSample epilogue, a build part of its own
 template <int DP>
 int launch_sample_m(const AuxParams &p, int H, int metric, hipStream_t s) {
@@ -473,6 +485,11 @@ template <int DP> int part_reinmax(int role, const GumbelParams &p, int H, int g
 #define VQ_DECLARE_GUMBEL_PARTS(DP)                                                                              \
     template <> int part_gumbel<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s); \
     template <> int part_reinmax<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <int DP> int part_ce_bwd_live(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
+template <> int part_ce_bwd_live<32>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
+template <> int part_ce_bwd_live<64>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
+template <> int part_ce_bwd_live<128>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
+template <> int part_ce_bwd_live<256>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
 VQ_DECLARE_GUMBEL_PARTS(32)
 VQ_DECLARE_GUMBEL_PARTS(64)
 VQ_DECLARE_GUMBEL_PARTS(128)
@@ -570,6 +587,13 @@ VQ_DEFINE_CE_PART(128)
 VQ_DEFINE_CE_PART(256)
 VQ_DEFINE_CE_PART(512)
 #undef VQ_DEFINE_CE_PART
+#define VQ_DEFINE_CE_LIVE_PART(DP) \
+    template <> int part_ce_bwd_live<DP>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s) { return launch_ce_bwd_live_m<DP>(p, H, metric, s); }
+VQ_DEFINE_CE_LIVE_PART(32)
+VQ_DEFINE_CE_LIVE_PART(64)
+VQ_DEFINE_CE_LIVE_PART(128)
+VQ_DEFINE_CE_LIVE_PART(256)
+#undef VQ_DEFINE_CE_LIVE_PART
 #endif
 #if VQ_OWN(7)
 #define VQ_DEFINE_GUMBEL_PART(DP) \
@@ -1723,6 +1747,26 @@ int vq_softmax_stats_f32(const vq_args *a, float scale, const int64_t *target, i
     return launch_aux(DP, p, a->H, a->metric, kAuxStats, (hipStream_t)stream);
 }
 
+// the arguments both cross-entropy backward entries share; `cb`: the natural codes the finalize takes the target's row from
+static int fill_ce_bwd_params(CeBwdParams &p, const vq_args *a, const float *cb, int64_t cb_hs, const float *lse, const float *target_logit,
+                              const int64_t *target, int64_t tgt_rs, int64_t tgt_hs, const float *coef, float *grad_x, int64_t gx_rs,
+                              int64_t gx_hs) {
+    AuxParams ap;
+    const int rc = fill_aux_params(ap, a);
+    if (rc) return rc;
+    memset(&p, 0, sizeof(p));
+    p.x = ap.x; p.x_rs = ap.x_rs; p.x_hs = ap.x_hs;
+    p.packed = ap.packed; p.pk_hs = ap.pk_hs; p.pk_bytes = ap.pk_bytes;
+    p.M = ap.M; p.K = ap.K; p.D = ap.D; p.ntiles = ap.ntiles; p.vec_x = ap.vec_x;
+    p.lse = lse;
+    p.target = (const long long *)target; p.tgt_rs = tgt_rs; p.tgt_hs = tgt_hs;
+    p.coef = coef;
+    p.cb = cb; p.cb_hs = cb_hs;
+    p.tgt_logit = target_logit;
+    p.gx = grad_x; p.gx_rs = gx_rs; p.gx_hs = gx_hs;
+    return 0;
+}
+
 int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_logit, const int64_t *target, int64_t tgt_rs,
                        int64_t tgt_hs, const float *coef, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream) {
     int rc = check_common(a);
@@ -1732,23 +1776,39 @@ int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_l
         return fail(VQ_E_BADARG, "vq_ce_backward: null argument (lse / target_logit / target / coef / grad_x / cb)");
     const int DP = padded_dim(a->D);
     if (DP == 0) return fail(VQ_E_UNSUPPORTED, "vq_ce_backward: D > 512 (use vq_similarities_f32 row chunks)");
-    AuxParams ap;
-    rc = fill_aux_params(ap, a);
-    if (rc) return rc;
     CeBwdParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = ap.x; p.x_rs = ap.x_rs; p.x_hs = ap.x_hs;
-    p.packed = ap.packed; p.pk_hs = ap.pk_hs; p.pk_bytes = ap.pk_bytes;
-    p.M = ap.M; p.K = ap.K; p.D = ap.D; p.ntiles = ap.ntiles; p.vec_x = ap.vec_x;
-    p.lse = lse;
-    p.target = (const long long *)target; p.tgt_rs = tgt_rs; p.tgt_hs = tgt_hs;
-    p.coef = coef;
-    p.cb = a->cb; p.cb_hs = a->cb_hs;
-    p.tgt_logit = target_logit;
-    p.gx = grad_x; p.gx_rs = gx_rs; p.gx_hs = gx_hs;
+    rc = fill_ce_bwd_params(p, a, a->cb, a->cb_hs, lse, target_logit, target, tgt_rs, tgt_hs, coef, grad_x, gx_rs, gx_hs);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     return with_padded_dim(DP, [&](auto dp) { return vqi::part_ce_bwd<decltype(dp)::value>(p, a->H, a->metric, s); },
                            [] { return fail(VQ_E_UNSUPPORTED, "vq_ce_backward: unsupported padded dim"); });
+}
+
+int vq_ce_backward_live_f32(const vq_args *a, const float *live_cb, int64_t live_cb_hs, const float *live_packed, int64_t live_pk_hs,
+                            const float *lse, const float *target_logit, const int64_t *target, int64_t tgt_rs, int64_t tgt_hs,
+                            const float *coef, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    if (!live_cb || !live_packed) return fail(VQ_E_BADARG, "vq_ce_backward_live: null argument (live_cb / live_packed)");
+    if (!lse || !target_logit || !target || !coef || !grad_x)
+        return fail(VQ_E_BADARG, "vq_ce_backward_live: null argument (lse / target_logit / target / coef / grad_x)");
+    if (!a->packed) return fail(VQ_E_BADARG, "vq_ce_backward_live: packed codebook is null (the codes the forward searched)");
+    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, "vq_ce_backward_live: D > 256 (four tile buffers of wider rows do not fit in LDS; use vq_similarities_f32 row chunks)");
+    if (a->M == 0) return 0;
+    const int DP = padded_dim(a->D);
+    CeBwdLiveParams p;
+    // (the finalize adds the target's term from p.cb: the live codes; a->cb is not read)
+    rc = fill_ce_bwd_params(p, a, live_cb, live_cb_hs, lse, target_logit, target, tgt_rs, tgt_hs, coef, grad_x, gx_rs, gx_hs);
+    if (rc) return rc;
+    p.live_packed = live_packed; p.live_pk_hs = live_pk_hs;
+    hipStream_t s = (hipStream_t)stream;
+    return with_padded_dim(DP,
+                           [&](auto dp) {
+                               constexpr int DPC = decltype(dp)::value;
+                               if constexpr (DPC > 256) return fail(VQ_E_UNSUPPORTED, "vq_ce_backward_live: unsupported padded dim");
+                               else return vqi::part_ce_bwd_live<DPC>(p, a->H, a->metric, s);
+                           },
+                           [] { return fail(VQ_E_UNSUPPORTED, "vq_ce_backward_live: unsupported padded dim"); });
 }
 
 // ---- Gumbel-max code sampling (vq_sample.inc, kAuxSample in vq_similarity.inc) -----------------------------------------

@@ -271,9 +271,19 @@ struct CeBwdParams {
     float *gx;
     long long gx_rs, gx_hs;
 };
+// live variant: `packed` = the codes the forward searched, `live_packed` the image of the codes at backward time (same K, D,
+// metric and byte size); `cb` is then the natural LIVE codebook
+struct CeBwdLiveParams : CeBwdParams {
+    const float *live_packed;
+    long long live_pk_hs;
+};
 }  // namespace vqi
 namespace {
 using vqi::CeBwdParams;
+using vqi::CeBwdLiveParams;
+#ifndef VQ_CE_LIVE_WAVES
+#define VQ_CE_LIVE_WAVES 8  // waves per workgroup of the live kernel at Dp <= 128 (4: A/B builds)
+#endif
 
 template <int DP>
 struct CeGeo {
@@ -362,9 +372,30 @@ __device__ __forceinline__ void ce_finish_rows(const CeBwdParams &p, int head, l
     }
 }
 
-template <int DP, int METRIC>
-__global__ void __launch_bounds__(256, (DP <= 128 ? 2 : 1)) vq_ce_backward(const CeBwdParams p) {
-    constexpr int WAVES = 4;
+// Live codes (vq_ce_backward_live_f32), Dp <= 256.  Four tile buffers: 133 120 B at Dp = 256 (the finalize staging, 134 656 B,
+// still aliases them), 135 168 / 139 264 / 147 456 B at Dp = 128 / 64 / 32 -- one workgroup per CU.  Dp = 256 is the one-wave
+// kernel as it stands (one wave per SIMD either way; the roles kernel's three buffers cannot be doubled).  Dp <= 128 has two
+// 4-wave workgroups per CU without live codes; with them ONE 8-wave workgroup walks 256 rows and shares each pair of tiles,
+// so the two waves per SIMD and their 256 registers stay.
+template <int DP>
+struct CeLiveGeo {
+    static constexpr int WAVES = DP <= 128 ? VQ_CE_LIVE_WAVES : 4;
+    static constexpr size_t TILES_B = (size_t)4 * Geo<DP, WAVES>::BUF_F4 * 16;
+    static constexpr size_t PRO_B = (size_t)WAVES * 32 * Geo<DP, WAVES>::XS * 4;      // prologue staging (load_x_fragments)
+    static constexpr size_t STG_B = (size_t)WAVES * (32 * CeGeo<DP>::GS + 96) * 4;    // finalize staging
+    static constexpr size_t LDS_B = TILES_B > STG_B ? (TILES_B > PRO_B ? TILES_B : PRO_B) : (STG_B > PRO_B ? STG_B : PRO_B);
+    static_assert(DP <= 256 && LDS_B <= 160 * 1024, "four tile buffers of Dp = 512 do not fit");
+};
+
+// The one-wave kernel.  LIVE: the weights come from the codes the forward searched (p.packed: S sweep, zero-distance fix-up,
+// sum of the ratios; lse / tgt_logit belong to them too), what they are multiplied with from the codes as they are now
+// (p.live_packed: the A operands of the G sweep; p.cb, the finalize's c_target, is the natural live codebook) -- the gradient
+// autograd gives after an EMA step has rewritten the codebook through .data.  A second tile ring (buffers 2, 3: same geometry,
+// tile index and parity) takes the live image, both tiles of a step are issued together; the MFMA chains and their order
+// are the non-live kernel's, so with live == searched codes the result is its result bit for bit.
+template <int DP, int METRIC, bool LIVE = false, int WAVES = 4>
+__global__ void __launch_bounds__(WAVES * 64, (DP <= 128 && WAVES == 4 ? 2 : 1))
+vq_ce_backward(const std::conditional_t<LIVE, CeBwdLiveParams, CeBwdParams> p) {
     using G = Geo<DP, WAVES>;
     using CG = CeGeo<DP>;
     constexpr int RS = G::RS, RS4 = G::RS4, SUB = G::SUB, NG = DP / 8, V = CG::V, NJ = CG::NJ, NACC = CG::NACC;
@@ -422,6 +453,11 @@ __global__ void __launch_bounds__(256, (DP <= 128 ? 2 : 1)) vq_ce_backward(const
             if (ck < G::TILE_CHUNKS)
                 lds_dma16(pk, p.pk_bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16,
                           tile4_lds + buf * G::BUF_F4 + ck * 64);
+            if constexpr (LIVE) {
+                if (ck < G::TILE_CHUNKS)
+                    lds_dma16(p.live_packed + (long long)head * p.live_pk_hs, p.pk_bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16,
+                              tile4_lds + (2 + buf) * G::BUF_F4 + ck * 64);
+            }
         }
     };
 
@@ -435,6 +471,7 @@ __global__ void __launch_bounds__(256, (DP <= 128 ? 2 : 1)) vq_ce_backward(const
             const int u = t * SUB + st;
             if (u * kTileCodes >= p.K) break;  // workgroup-uniform
             const f32x4 *tb = tile4 + cur * G::BUF_F4 + st * (kTileCodes * RS4);
+            const f32x4 *tg = LIVE ? tb + 2 * G::BUF_F4 : tb;  // the tile the G sweep multiplies with
             // ---- S sweep
             f32x16 acc = {0};
             {
@@ -487,7 +524,7 @@ __global__ void __launch_bounds__(256, (DP <= 128 ? 2 : 1)) vq_ce_backward(const
                 if (EUCLID) sum2 += v;
             };
             // ---- G sweep: gacc[J*V + e][pos-in-chunk i, row] += Cimg[code(r, half)][128J + 4i + e] * acc[r]
-            const float *trow = (const float *)tb + (4 * h) * RS + V * c + pos0;
+            const float *trow = (const float *)tg + (4 * h) * RS + V * c + pos0;
             // (wave-uniform; through readfirstlane so that it stays a run-time scalar: the dot variant otherwise gets one copy of
             // the sub-tile body per kind of tile and spills)
             const int plain_i = __builtin_amdgcn_readfirstlane((int)!(degenerate || tail));

@@ -11,9 +11,13 @@ Here the forward of the cross entropy is ONE native sweep with an online-softmax
 (``vq_softmax_stats_f32``: per row log-sum-exp + target logit).  Everything that needs actual matrix entries
 (backward passes, the diversity loss) works on bounded row chunks: ``vq_similarities_f32`` emits a chunk, the
 chunk's contribution is evaluated with ordinary tensor ops, and gradients flow through ``_SimilarityFn`` whose
-backward is ATen's ``_euclidean_dist_backward`` formula (two library GEMMs per chunk).
+backward is ATen's ``_euclidean_dist_backward`` formula (two library GEMMs per chunk).  The cross entropy's backward with
+respect to x is one fused native sweep instead (``vq_ce_backward_f32``; with an EMA codebook, whose update rewrites the codes
+between forward and backward, ``vq_ce_backward_live_f32``) wherever the kernels reach: D <= 512, with live codes D <= 256.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn.functional as F
@@ -140,11 +144,13 @@ class _ChunkedFn(torch.autograd.Function):
 class _CrossEntropyFn(torch.autograd.Function):
     """mean over non-ignored (h, m) of  logsumexp_k sims[h, m, k] - sims[h, m, target[h, m]]
     == F.cross_entropy(rearrange(distances, ...), codes, ignore_index=-1)   vector_quantize_pytorch.py:292-294.
-    Forward: one native sweep (online softmax).  Backward: bounded chunks of the similarity matrix."""
+    Forward: one native sweep (online softmax).  Backward: one fused sweep (vq_ce_backward_f32, with ``live_codes``
+    vq_ce_backward_live_f32); bounded chunks of the similarity matrix outside their range, for a learnable codebook and
+    under VQ_CE_NO_LIVE=1 (live codes only)."""
 
     @staticmethod
-    def forward(ctx, x, codes, target, metric, live_codes=None, lse=None, tl=None):
-        ctx.live_codes = live_codes
+    def forward(ctx, x, codes, target, metric, live_codes=None, lse=None, tl=None, live_packed=None):
+        ctx.live_codes, ctx.live_packed = live_codes, live_packed
         if lse is None:  # otherwise the search already produced them (vq_quantize_lse_f32): no second sweep
             lse, tl = search.get_backend().softmax_stats(x.detach(), codes.detach(), metric=metric, scale=1.0,
                                                          target=target)
@@ -159,12 +165,21 @@ class _CrossEntropyFn(torch.autograd.Function):
         x, codes, target, count, lse, tl = ctx.saved_tensors
         metric, live = ctx.metric, ctx.live_codes
         fused = getattr(search.get_backend(), "cross_entropy_backward", None)
-        if fused is not None and live is None and not ctx.needs_input_grad[1]:
+        if live is not None and os.environ.get("VQ_CE_NO_LIVE"):  # (read per call: tests and A/B runs compare both paths)
+            fused = None
+        if fused is not None and not ctx.needs_input_grad[1]:
             # one fused sweep (S = x c^T, softmax weights, second contraction with the codebook) -- nothing of [M, K]
             coef = (g / count).reshape(1).to(torch.float32)
-            gx = fused(x.detach(), codes.detach(), lse, tl, target, coef, metric=metric)
+            if live is None:
+                gx = fused(x.detach(), codes.detach(), lse, tl, target, coef, metric=metric)
+            else:
+                # the weights from `codes` (what the forward searched), the contraction with the codes as they are NOW: `live`
+                # and its image are read here, at backward time
+                packed = ctx.live_packed() if callable(ctx.live_packed) else ctx.live_packed
+                gx = fused(x.detach(), codes.detach(), lse, tl, target, coef, metric=metric, live=live.detach(),
+                           live_packed=packed)
             if gx is not None:
-                return gx, None, None, None, None, None, None
+                return gx, None, None, None, None, None, None, None
 
         def chunk_value(xc, cc, rows):
             sims = similarity_matrix(xc, cc, metric, live)
@@ -173,18 +188,20 @@ class _CrossEntropyFn(torch.autograd.Function):
 
         chunks = _row_slices(x.shape[1], _rows_per_chunk(x.shape[0], codes.shape[1]))
         gx, gc = _chunk_grads(chunk_value, x, codes, chunks, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        return gx, gc, None, None, None, None, None
+        return gx, gc, None, None, None, None, None, None
 
 
 def cross_entropy_to_codes(x: torch.Tensor, codes: torch.Tensor, target: torch.Tensor, metric: int,
-                           live_codes=None, stats=None) -> torch.Tensor:
+                           live_codes=None, stats=None, live_packed=None) -> torch.Tensor:
     """x [H, M, D] (strided rows fine), codes [H, K, D], target [H, M] int64 with -1 = ignore -> scalar.
     ``live_codes``: see similarity_matrix().  ``stats`` = (lse [H, M], target_logit [H, M]) when the search sweep already
-    produced them for exactly this target (cross-entropy commitment loss: target = the chosen code)."""
+    produced them for exactly this target (cross-entropy commitment loss: target = the chosen code).
+    ``live_packed``: the packed image of ``live_codes`` for the fused backward, or a callable that returns it -- called when
+    backward runs (``Codebook.packed_codes``: the image the next forward's search needs anyway); None: packed per call."""
     lse, tl = stats if stats is not None else (None, None)
     if lse is not None:
         lse, tl = lse.contiguous(), tl.contiguous()
-    return _CrossEntropyFn.apply(x.float(), codes, target, metric, live_codes, lse, tl)
+    return _CrossEntropyFn.apply(x.float(), codes, target, metric, live_codes, lse, tl, live_packed)
 
 
 # ------------------------------------------------------------------------------------------------ diversity

@@ -145,6 +145,8 @@ def load():
         lib.vq_softmax_stats_f32.restype = ctypes.c_int
         lib.vq_ce_backward_f32.argtypes = [ap, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]
         lib.vq_ce_backward_f32.restype = ctypes.c_int
+        lib.vq_ce_backward_live_f32.argtypes = [ap, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]
+        lib.vq_ce_backward_live_f32.restype = ctypes.c_int
         lib.vq_gumbel_row_stride.argtypes = [_i64]
         lib.vq_gumbel_row_stride.restype = _i64
         lib.vq_gumbel_workspace_bytes.argtypes = [ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int]
@@ -239,7 +241,7 @@ EXPORTED_SYMBOLS = (
     "vq_packed_floats", "vq_pack_codebooks_f32", "vq_workspace_bytes", "vq_workspace_bytes_wide", "vq_quantize_f32", "vq_nearest_f32",
     "vq_residual_f32", "vq_keys_init", "vq_search_keys_f32", "vq_finalize_keys_f32", "vq_last_error",
     "vq_device_info", "vq_ema_accumulate_f32", "vq_ema_update_f32", "vq_similarities_f32", "vq_softmax_stats_f32",
-    "vq_ce_backward_f32", "vq_quantize_lse_f32",
+    "vq_ce_backward_f32", "vq_ce_backward_live_f32", "vq_quantize_lse_f32",
     "vq_quantize_backward_f32", "vq_ema_accumulate_residual_f32", "vq_max_fused_stages", "vq_ema_accumulate_det_f32",
     "vq_ema_det_workspace_bytes", "vq_key_planes", "vq_search_key_planes_f32", "vq_finalize_key_planes_f32",
     "vq_lfq_workspace_bytes", "vq_lfq_quantize_f32", "vq_lfq_entropy_fwd_f32", "vq_lfq_entropy_bwd_f32",
@@ -674,6 +676,7 @@ def softmax_stats(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, sc
 
 
 CE_BACKWARD_MAX_DIM = 512
+CE_BACKWARD_LIVE_MAX_DIM = 256  # with live codes: two tile rings in LDS
 SOFTMAX_STATS_MAX_DIM = 512  # the online-softmax sweep (and the search's LSE variant) keep a row's dims in one launch
 
 
@@ -701,19 +704,37 @@ def _softmax_stats_wide(x, cb, metric, scale, target, packed):
 
 
 def ce_backward(x: torch.Tensor, cb: torch.Tensor, lse: torch.Tensor, target_logit: torch.Tensor, target: torch.Tensor,
-                coef: torch.Tensor, *, metric: int = EUCLID, packed: torch.Tensor | None = None) -> torch.Tensor:
+                coef: torch.Tensor, *, metric: int = EUCLID, packed: torch.Tensor | None = None,
+                live: torch.Tensor | None = None, live_packed: torch.Tensor | None = None) -> torch.Tensor:
     """Fused backward of the cross entropy over the codebook: grad_x [H, M, D] = coef * d/dx (lse - logit[target]) for
     rows with target >= 0 (0 otherwise).  lse, target_logit [H, M] from softmax_stats (scale 1), coef: 1-element fp32
-    device tensor."""
+    device tensor.
+
+    ``live`` [H, K, D]: the codes as they are NOW, when they have been rewritten since ``cb`` was searched (the EMA step):
+    the weights come from ``cb``, what they are multiplied with from ``live`` (vq_ce_backward_live_f32, D <= 256).
+    ``live_packed``: its packed image when the caller has one cached; packed here otherwise."""
     a, packed = _aux_args(x, cb, metric, packed, 0)
     H, M, D = x.shape
-    _require_gpu(lse, target_logit, target, coef)
-    assert D <= CE_BACKWARD_MAX_DIM
+    _require_gpu(lse, target_logit, target, coef, live)
+    assert D <= (CE_BACKWARD_MAX_DIM if live is None else CE_BACKWARD_LIVE_MAX_DIM)
     assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (H, M)
     assert target_logit.dtype == torch.float32 and target_logit.is_contiguous() and tuple(target_logit.shape) == (H, M)
     assert target.dtype == torch.int64 and tuple(target.shape) == (H, M)
     assert coef.dtype == torch.float32 and coef.numel() == 1
     gx = torch.empty((H, M, D), dtype=torch.float32, device=x.device)
+    if live is not None:
+        K = cb.shape[1]
+        assert live.dtype == torch.float32 and tuple(live.shape) == (H, K, D) and live.device == x.device
+        live = live.contiguous()
+        if live_packed is None:
+            live_packed = pack_codebooks(live, metric)
+        _check_packed(live_packed, H, K, D, x.device)
+        with torch.cuda.device(x.device):
+            _check(load().vq_ce_backward_live_f32(ctypes.byref(a), live.data_ptr(), K * D, live_packed.data_ptr(),
+                                                  live_packed.shape[-1], lse.data_ptr(), target_logit.data_ptr(), target.data_ptr(),
+                                                  int(target.stride(1)), int(target.stride(0)), coef.data_ptr(), gx.data_ptr(), D,
+                                                  M * D, _stream_ptr(x.device)), "vq_ce_backward_live_f32")
+        return gx
     with torch.cuda.device(x.device):
         _check(load().vq_ce_backward_f32(ctypes.byref(a), lse.data_ptr(), target_logit.data_ptr(), target.data_ptr(), int(target.stride(1)),
                                          int(target.stride(0)), coef.data_ptr(), gx.data_ptr(), D, M * D,

@@ -459,20 +459,24 @@ class VectorQuantize(nn.Module):
         #      used, i.e. BEFORE the EMA step below rewrites it
         needs_sims = return_loss or (training and ((want_loss and use_ce) or self.has_codebook_diversity_loss))
         if needs_sims:
-            codes, live = cb.effective_codes(), None
+            codes, live, live_packed = cb.effective_codes(), None, None
             if will_update and not cb.use_affine:  # (affine: the codes of this forward are a tensor of their own already)
                 # the backward pass recomputes similarities from the pre-update codebook; the reference's autograd then
                 # multiplies with the codebook as it is at backward time (losses.similarity_matrix: live_codes)
+                # (fused: vq_ce_backward_live_f32 with the module's cached image of the codes at that time -- the image the
+                # next forward's search packs anyway)
                 codes, live = codes.detach().clone().requires_grad_(codes.requires_grad), cb.embeddings
+                live_packed = cb.packed_codes
             if return_loss:
                 # cross entropy of the similarities against GIVEN codes (vector_quantize_pytorch.py:298-299)
                 given = per_head_rows(indices.reshape(rows, heads).to(torch.int64))
-                ce_given = losses.cross_entropy_to_codes(flat, codes, given, cb.metric, live)
+                ce_given = losses.cross_entropy_to_codes(flat, codes, given, cb.metric, live, live_packed=live_packed)
             if training and want_loss and use_ce:
                 target = idx_view[..., 0]
                 if flat_mask is not None:
                     target = target.masked_fill(~flat_mask, -1)
-                commit_loss = losses.cross_entropy_to_codes(flat, codes, target, cb.metric, live, stats=ce_stats)
+                commit_loss = losses.cross_entropy_to_codes(flat, codes, target, cb.metric, live, stats=ce_stats,
+                                                            live_packed=live_packed)
             if training and self.has_codebook_diversity_loss and not return_loss:
                 row_id = torch.arange(flat.shape[1], device=flat.device)
                 position = (row_id % n) if (self.separate_codebook_per_head or heads == 1) else (row_id // heads) % n

@@ -144,11 +144,14 @@ class _NativeBackend:
                                         sq_err_per_head=sq_err_per_head)
 
     @staticmethod
-    def cross_entropy_backward(x, cb, lse, target_logit, target, coef, *, metric):
-        """Fused d/dx of the cross entropy (vq_ce_backward_f32); None when the shape is outside the kernel's range."""
-        if x.shape[-1] > native.CE_BACKWARD_MAX_DIM:
+    def cross_entropy_backward(x, cb, lse, target_logit, target, coef, *, metric, live=None, live_packed=None):
+        """Fused d/dx of the cross entropy (vq_ce_backward_f32); None when the shape is outside the kernel's range.
+        ``live`` [H, K, D]: the codes as they are now when they were rewritten after ``cb`` was searched, ``live_packed`` their
+        packed image if the caller holds one (vq_ce_backward_live_f32: D <= 256)."""
+        if x.shape[-1] > (native.CE_BACKWARD_MAX_DIM if live is None else native.CE_BACKWARD_LIVE_MAX_DIM):
             return None
-        return native.ce_backward(x, cb.contiguous(), lse, target_logit, target, coef, metric=metric)
+        return native.ce_backward(x, cb.contiguous(), lse, target_logit, target, coef, metric=metric, live=live,
+                                  live_packed=live_packed)
 
 
     @staticmethod
