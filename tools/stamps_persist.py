@@ -7,6 +7,9 @@ and the read-back would return the all-zero copy of part 0):
 then  VQ_MI355X_LIB=.../lib/stamps.so python tools/stamps_persist.py [M,K,D]
 Without an argument the data is bench.py's headline workload (cfg2: 262144 x 256 rows of seed 1234, 1024 codes of seed 4321);
 with one, randn of seed 0.  VQ_NO_SCREEN=1 in the environment stamps the fp32 sweep of the same kernel.
+The screened sweep also stamps, per wave, six sub-tiles (12 .. 17) of row block 2: barrier release, start and end of the
+epilogue, barrier arrival.  Reported for waves 0-3 and 4-7 (SIMD partners w, w + 4): epilogue and sub-tile lengths and how
+much the partners' epilogue intervals overlap.  VQ_NO_STAGGER=1 puts all eight waves' epilogues at the same place.
 """
 import sys, os, ctypes, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +32,7 @@ while time.perf_counter() - t_s < 0.1:  # the stamps of the LAST call are read: 
         native.quantize(x, cb, packed=packed, want_best=False)
     torch.cuda.synchronize()
 lib = native.load()
-NST, NB = 64, 14
+NST, NB = 64, 8
 buf = (ctypes.c_uint64 * (8192 * NST))()
 lib.vq_debug_read_stamps.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
 rc = lib.vq_debug_read_stamps(buf, 8192 * NST)
@@ -74,6 +77,24 @@ for it in range(int(nb.max())):
     ok = (wg[:, 0, 57] > it)
     wres[ok] += (wg[ok][:, :, 4 * it + 3] - wg[ok][:, :, 4 * it + 2]).max(axis=1)
 row("per workgroup: sum over blocks of its slowest wave's resolve", wres)
+# screened sweep, sub-tiles 12 .. 17 of block 2: barrier release, epilogue start / end, barrier arrival per wave (slots 32 ..)
+sub = wg[(wg[:, :, 57].min(axis=1) > 2) & (wg[:, :, 32:56].min(axis=(1, 2)) > 0)][:, :, 32:56].reshape(-1, 8, 6, 4)
+if len(sub):
+    print(f"sub-tiles 12..17 of block 2, {len(sub)} workgroups (VQ_NO_STAGGER {'set' if os.environ.get('VQ_NO_STAGGER') else 'unset'}):")
+    for name, ws in (("waves 0-3", slice(0, 4)), ("waves 4-7", slice(4, 8))):
+        s = sub[:, ws]
+        row(f"  {name}: epilogue length", s[..., 2] - s[..., 1])
+        row(f"  {name}: release -> epilogue start", s[..., 1] - s[..., 0])
+        row(f"  {name}: epilogue end -> arrival", s[..., 3] - s[..., 2])
+        row(f"  {name}: release -> arrival", s[..., 3] - s[..., 0])
+        row(f"  {name}: sub-tile (release to release)", s[:, :, 1:, 0] - s[:, :, :-1, 0])
+    # SIMD partners w and w + 4: how much of one's epilogue interval lies inside the other's
+    a, b = sub[:, 0:4], sub[:, 4:8]
+    ov = np.maximum(0, np.minimum(a[..., 2], b[..., 2]) - np.maximum(a[..., 1], b[..., 1]))
+    row("  partners' epilogues overlap (cycles)", ov)
+    row("  ... in % of the early half's epilogue", 100.0 * ov / np.maximum(a[..., 2] - a[..., 1], 1))
+    row("  ... in % of the late half's epilogue", 100.0 * ov / np.maximum(b[..., 2] - b[..., 1], 1))
+    row("  barrier wait (arrival -> next release)", sub[:, :, 1:, 0] - sub[:, :, :-1, 3])
 rt = (st[:, 61] - st[:, 60]).astype(np.float64)
 clk = np.median((st[:, 56] - st[:, 0]) / np.maximum(rt, 1.0)) * 100.0
 print(f"wave life: median {np.median(rt) / 100:.1f} us, max {rt.max() / 100:.1f} us; first start .. last end of the launch: "

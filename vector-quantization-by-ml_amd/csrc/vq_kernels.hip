@@ -648,6 +648,9 @@ void set_screen_image(SearchParams &p, const vq_args *a) {
     p.scr_bytes = (unsigned)img;
     p.scr_count = (unsigned *)((char *)a->workspace + (long long)a->H * img);
     p.scr_list = p.scr_count + 64;
+    // VQ_NO_STAGGER in the environment: all eight waves run the sweep's epilogue at the same place (A/B measurements and
+    // tests; read per call like VQ_NO_SCREEN)
+    p.scr_stagger = getenv("VQ_NO_STAGGER") == nullptr;
 }
 
 // Small codebook, plain inference call (one stage, no straight-through / loss / LSE, aligned fp32 rows of D % 16 == 0 dims,

@@ -57,6 +57,9 @@ struct SearchParams {
     // from the back; both counts are zeroed by vq_pack_scr_kernel, the entries are decided by vq_resolve_rows_kernel
     unsigned *scr_count;
     unsigned *scr_list;
+    // that sweep: waves 4..7 fold the previous sub-tile's values in half a sub-tile after their SIMD partners 0..3 (0: all
+    // eight waves right after the first MFMA group; the results are the same bit for bit)
+    int scr_stagger;
 };
 }  // namespace vqi
 namespace {

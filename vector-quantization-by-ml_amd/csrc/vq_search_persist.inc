@@ -68,6 +68,12 @@
 constexpr int kScrRowBytes = 1040;                             // one code: 16 groups of 16 dims x (hi, lo) x 16 B, + 16 B pad
 constexpr int kScrTileBytes = kTileCodes * kScrRowBytes + 128;  // 32 codes + their 32 fp32 |c|^2
 constexpr int kScrCnOffset = kTileCodes * kScrRowBytes;
+// the MFMA group (of 16 per sub-tile) after which waves 4..7 run the sweep's epilogue; waves 0..3 run it after group 0
+// (8 = half a sub-tile; profiles/cfg2_stagger.md has the figures of 5, 6, 8, 10, 12 and 14)
+#ifndef VQ_SCR_LATE_GROUP
+#define VQ_SCR_LATE_GROUP 8
+#endif
+constexpr int kScrLateGroup = VQ_SCR_LATE_GROUP;
 inline long long scr_image_bytes(int ntiles) { return ((long long)ntiles * kScrTileBytes + 4ll * ntiles + 255) / 256 * 256; }
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -474,6 +480,11 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
     const int nblk = (int)((p.M + 32 * WAVES - 1) / (32 * WAVES));
     const int dl = 4 * lane;            // this lane's float4 of a natural row
     const bool dok = dl < p.D;
+    // SCREEN: waves w and w + 4 share a SIMD and run the same program between the same barriers.  With the epilogue at one
+    // place both would leave the matrix pipe idle at once and then compete for it; waves 4..7 (a scalar branch) run theirs
+    // after group kScrLateGroup instead, beside their partners' MFMAs.  When a wave folds a sub-tile into its three lowest
+    // values changes none of them (order statistics), so p.scr_stagger = 0 gives the same bits.
+    const bool scr_late = SCREEN && p.scr_stagger != 0 && wave >= 4;
 
     // deferred copy of the previous block's rows (all wave-uniform except the data registers)
     int cp_rows = 0, cp_next = 0;       // rows of the previous block / next row to load
@@ -527,10 +538,12 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             stage_tile<G, WAVES>(pk, p.pk_bytes, tile, tile4_lds + buf * G::BUF_F4, wave, lane);
         }
     };
-    // Diagnostic build (-DVQ_EXP_STAMPS; tools/stamps_persist.py): per wave and row block `it` < 14 the shader-clock time of
+    // Diagnostic build (-DVQ_EXP_STAMPS; tools/stamps_persist.py): per wave and row block `it` < 8 the shader-clock time of
     // block start, prologue end, sweep end and resolve end in slots 4 it .. 4 it + 3, the end of the open finalize in slot 56,
-    // the wave's block count in slot 57, the real-time pair in slots 60 / 61.
-#define PSTAMP(j) do { if (it < 14) STAMP(4 * it + (j)); } while (0)
+    // the wave's block count in slot 57, the real-time pair in slots 60 / 61.  SCREEN, sub-tiles 12 .. 17 of block it == 2:
+    // barrier release, start and end of the epilogue (of the sub-tile before), barrier arrival in slots 32 + 4 (u - 12) .. + 3.
+#define PSTAMP(j) do { if (it < 8) STAMP(4 * it + (j)); } while (0)
+#define SSTAMP(j) do { if (it == 2 && u >= 12 && u < 18) STAMP(32 + 4 * (u - 12) + (j)); } while (0)
     int it = 0;
     long long row0 = 0;
     STAMP_RT(60);
@@ -670,6 +683,8 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         // fragments read PF groups ahead, two ds_read_b128 per 3 MFMAs (the fp32 body's reads, same addresses per lane)
         auto run_sub_scr = [&](f32x16 &acc, f32x16 &prev, int u, bool have_prev) {
             constexpr int NGS = DP / 16, PF = 3;
+            static_assert(kScrLateGroup > 3 && kScrLateGroup < NGS, "the late epilogue sits inside the last range of groups");
+            SSTAMP(0);
             const int cur = u & 1;
             const char *tb = (const char *)(tile4 + cur * G::BUF_F4);
             const char *ta = tb + c * kScrRowBytes + 16 * h;
@@ -703,12 +718,26 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
                 }
             };
             groups(IntC<0>{}, IntC<1>{});
-            if (have_prev) epilogue(prev, u - 1);
+            if (have_prev && !scr_late) {
+                SSTAMP(1);
+                epilogue(prev, u - 1);
+                SSTAMP(2);
+            }
             __builtin_amdgcn_sched_barrier(0);
             groups(IntC<1>{}, IntC<3>{});
             if (u + 1 < t1) stage(u + 1, cur ^ 1);
             __builtin_amdgcn_sched_barrier(0);
-            groups(IntC<3>{}, IntC<NGS>{});
+            groups(IntC<3>{}, IntC<kScrLateGroup>{});
+            // waves 4..7: the same call, while their SIMD partners 0..3 are in their MFMA tails (`prev` is not written before
+            // the next sub-tile; the fences keep the block where it is)
+            if (have_prev && scr_late) {
+                SSTAMP(1);
+                epilogue(prev, u - 1);
+                SSTAMP(2);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            groups(IntC<kScrLateGroup>{}, IntC<NGS>{});
+            SSTAMP(3);
             __syncthreads();
         };
         auto run_sub = [&](f32x16 &acc, f32x16 &prev, int u, bool have_prev) {
@@ -905,4 +934,5 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
     if (lane == 0) g_stamps[(((long long)blockIdx.x * WAVES + wave) & 8191) * VQ_NSTAMP + 57] = (unsigned long long)it;
 #endif
 #undef PSTAMP
+#undef SSTAMP
 }
