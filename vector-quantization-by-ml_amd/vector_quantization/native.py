@@ -30,6 +30,8 @@ _LIB_PATH = os.environ.get(
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int32
 _vp = ctypes.c_void_p
+_int = ctypes.c_int
+_f32 = ctypes.c_float
 
 
 class VqArgs(ctypes.Structure):
@@ -46,6 +48,88 @@ class VqArgs(ctypes.Structure):
         ("sq_err", _vp),
         ("workspace", _vp), ("workspace_bytes", _i64),
     ]
+
+
+_ap = ctypes.POINTER(VqArgs)  # const vq_args *
+
+# The C ABI, one entry per prototype of include/vq_mi355x.h in the header's order: name -> (restype, argtypes).  load() binds
+# exactly this and tests/test_native_signatures.py compares it with the header type by type.  Every pointer is a c_void_p
+# except vq_args * (_ap) and the two char * (c_char_p).
+_SIGNATURES = {
+    "vq_packed_floats": (_i64, (_int, _int)),
+    "vq_pack_codebooks_f32": (_int, (_vp, _int, _i64, _int, _int, _int, _vp, _vp)),
+    "vq_workspace_bytes": (_i64, (_int, _i64, _int)),
+    "vq_workspace_bytes_wide": (_i64, (_int, _i64, _int, _int)),
+    "vq_quantize_f32": (_int, (_ap, _vp)),
+    "vq_quantize_lse_f32": (_int, (_ap, _vp, _vp)),
+    "vq_nearest_f32": (_int, (_ap, _vp)),
+    "vq_residual_f32": (_int, (_ap, _vp)),
+    "vq_max_fused_stages": (_int, (_int, _int)),
+    "vq_keys_init": (_int, (_vp, _i64, _vp)),
+    "vq_search_keys_f32": (_int, (_ap, _i64, _vp, _vp)),
+    "vq_key_planes": (_int, (_ap,)),
+    "vq_search_key_planes_f32": (_int, (_ap, _i64, _vp, _vp)),
+    "vq_finalize_keys_f32": (_int, (_ap, _vp, _vp)),
+    "vq_finalize_key_planes_f32": (_int, (_ap, _vp, _int, _vp)),
+    "vq_quantize_backward_f32": (_int, (_ap, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp)),
+    "vq_ema_accumulate_f32": (_int, (_vp, _i64, _i64, _vp, _i64, _i64, _vp, _int, _i64, _int, _int, _vp, _vp, _vp)),
+    "vq_ema_det_workspace_bytes": (_i64, (_int, _i64, _int, _int)),
+    "vq_ema_accumulate_det_f32": (_int, (_vp, _i64, _i64, _vp, _i64, _i64, _vp, _int, _i64, _int, _int, _vp, _vp, _vp, _i64,
+                                         _vp)),
+    "vq_ema_accumulate_residual_f32": (_int, (_ap, _vp, _vp, _vp)),
+    "vq_ema_update_f32": (_int, (_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, ctypes.c_double, _f32, _int, _vp)),
+    "vq_affine_stats_workspace_bytes": (_i64, (_int, _i64, _int)),
+    "vq_affine_stats_f32": (_int, (_vp, _i64, _i64, _vp, _i64, _i64, _int, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp)),
+    "vq_affine_apply_f32": (_int, (_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp)),
+    "vq_similarities_f32": (_int, (_ap, _vp, _i64, _i64, _vp)),
+    "vq_softmax_stats_f32": (_int, (_ap, _f32, _vp, _i64, _i64, _vp, _vp, _vp)),
+    "vq_ce_backward_f32": (_int, (_ap, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp)),
+    "vq_ce_backward_live_f32": (_int, (_ap, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp)),
+    "vq_gumbel_row_stride": (_i64, (_i64,)),
+    "vq_gumbel_workspace_bytes": (_i64, (_int, _i64, _int, _int)),
+    "vq_gumbel_stats_f32": (_int, (_ap, _vp, _i64, _i64, _f32, _vp, _vp, _vp)),
+    "vq_gumbel_backward_x_f32": (_int, (_ap, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _i64, _i64, _vp)),
+    "vq_gumbel_backward_codes_f32": (_int, (_ap, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _i64, _vp)),
+    "vq_gumbel_reinmax_workspace_bytes": (_i64, (_int, _i64, _int, _int)),
+    "vq_gumbel_reinmax_stats_f32": (_int, (_ap, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp)),
+    "vq_gumbel_reinmax_columns_f32": (_int, (_ap, _vp, _i64, _i64, _f32, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp)),
+    "vq_gumbel_reinmax_backward_x_f32": (_int, (_ap, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
+                                                _i64, _i64, _vp)),
+    "vq_gumbel_reinmax_backward_codes_f32": (_int, (_ap, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                                    _vp)),
+    "vq_gumbel_sample_f32": (_int, (_ap, _f32, _vp, _vp)),
+    "vq_gumbel_noise_f32": (_int, (_vp, _int, _i64, _int, _vp, _vp, _vp)),
+    "vq_lfq_workspace_bytes": (_i64, (_i64, _i64, _int, _int)),
+    "vq_lfq_quantize_f32": (_int, (_vp, _i64, _vp, _i64, _i64, _int, _int, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp)),
+    "vq_lfq_entropy_fwd_f32": (_int, (_vp, _i64, _vp, _i64, _int, _int, _f32, _f32, _vp, _vp, _vp, _i64, _vp)),
+    "vq_lfq_entropy_bwd_f32": (_int, (_vp, _i64, _vp, _i64, _int, _int, _f32, _f32, _vp, _vp, _vp, _i64, _vp)),
+    "vq_lfq_staged_workspace_bytes": (_i64, (_i64, _int, _int)),
+    "vq_lfq_entropy_staged_fwd_f32": (_int, (_vp, _i64, _i64, _vp, _i64, _i64, _int, _int, _vp, _int, _f32, _vp, _vp, _vp,
+                                             _i64, _vp)),
+    "vq_lfq_entropy_staged_bwd_f32": (_int, (_vp, _i64, _i64, _vp, _i64, _i64, _int, _int, _vp, _int, _f32, _vp, _vp, _vp,
+                                             _i64, _i64, _vp)),
+    "vq_rlfq_workspace_bytes": (_i64, (_i64, _i64, _int)),
+    "vq_rlfq_quantize_f32": (_int, (_vp, _i64, _i64, _i64, _i64, _int, _int, _vp, _int, _int, _vp, _vp, _i64, _i64, _vp, _vp,
+                                    _vp, _vp, _i64, _vp)),
+    "vq_rlfq_backward_f32": (_int, (_vp, _i64, _i64, _i64, _i64, _int, _int, _vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
+                                    _i64, _i64, _vp)),
+    "vq_fsq_quantize_f32": (_int, (_vp, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _int, _vp, _i64, _i64, _vp, _vp)),
+    "vq_fsq_backward_f32": (_int, (_vp, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _int, _vp, _i64, _i64, _vp, _i64, _i64,
+                                   _vp)),
+    "vq_fsq_decode_f32": (_int, (_vp, _int, _i64, _int, _int, _vp, _vp, _int, _vp, _vp, _vp)),
+    "vq_decode_f32": (_int, (_vp, _i64, _i64, _int, _int, _int, _int, _vp, _int, _i64, _i64, _i64, _i64, _int, _int,
+                             _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp)),
+    "vq_lfq_decode_f32": (_int, (_vp, _int, _i64, _i64, _i64, _int, _i64, _int, _int, _int, _vp, _int,
+                                 _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp)),
+    "vq_lq_workspace_bytes": (_i64, (_i64, _i64, _int)),
+    "vq_lq_quantize_f32": (_int, (_vp, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp,
+                                  _f32, _f32, _vp, _i64, _vp)),
+    "vq_lq_backward_f32": (_int, (_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _f32, _i64, _i64,
+                                  _int, _vp, _i64, _i64, _i64, _vp)),
+    "vq_last_error": (ctypes.c_char_p, ()),
+    "vq_device_info": (_int, (ctypes.c_char_p, ctypes.c_size_t)),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 
 class NativeUnavailable(RuntimeError):
@@ -92,170 +176,11 @@ def load():
                 "(or __graft_entry__.build()).  There is no CPU/PyTorch fallback for the search path."
             )
         lib = ctypes.CDLL(_LIB_PATH)
-        ap = ctypes.POINTER(VqArgs)
-        lib.vq_last_error.restype = ctypes.c_char_p
-        lib.vq_packed_floats.argtypes = [ctypes.c_int, ctypes.c_int]
-        lib.vq_packed_floats.restype = _i64
-        lib.vq_workspace_bytes.argtypes = [ctypes.c_int, _i64, ctypes.c_int]
-        lib.vq_workspace_bytes.restype = _i64
-        lib.vq_workspace_bytes_wide.argtypes = [ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int]
-        lib.vq_workspace_bytes_wide.restype = _i64
-        lib.vq_pack_codebooks_f32.argtypes = [_vp, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp]
-        lib.vq_pack_codebooks_f32.restype = ctypes.c_int
-        lib.vq_quantize_lse_f32.argtypes = [ap, _vp, _vp]
-        lib.vq_quantize_lse_f32.restype = ctypes.c_int
-        for name in ("vq_quantize_f32", "vq_nearest_f32", "vq_residual_f32"):
+        for name, (restype, argtypes) in _SIGNATURES.items():
             fn = getattr(lib, name)
-            fn.argtypes = [ap, _vp]
-            fn.restype = ctypes.c_int
-        lib.vq_keys_init.argtypes = [_vp, _i64, _vp]
-        lib.vq_keys_init.restype = ctypes.c_int
-        lib.vq_search_keys_f32.argtypes = [ap, _i64, _vp, _vp]
-        lib.vq_search_keys_f32.restype = ctypes.c_int
-        lib.vq_finalize_keys_f32.argtypes = [ap, _vp, _vp]
-        lib.vq_finalize_keys_f32.restype = ctypes.c_int
-        lib.vq_key_planes.argtypes = [ap]
-        lib.vq_key_planes.restype = ctypes.c_int
-        lib.vq_search_key_planes_f32.argtypes = [ap, _i64, _vp, _vp]
-        lib.vq_search_key_planes_f32.restype = ctypes.c_int
-        lib.vq_finalize_key_planes_f32.argtypes = [ap, _vp, ctypes.c_int, _vp]
-        lib.vq_finalize_key_planes_f32.restype = ctypes.c_int
-        lib.vq_ema_accumulate_f32.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _vp, ctypes.c_int, _i64, ctypes.c_int,
-                                              ctypes.c_int, _vp, _vp, _vp]
-        lib.vq_ema_accumulate_f32.restype = ctypes.c_int
-        lib.vq_ema_accumulate_det_f32.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _vp, ctypes.c_int, _i64, ctypes.c_int,
-                                                  ctypes.c_int, _vp, _vp, _vp, _i64, _vp]
-        lib.vq_ema_accumulate_det_f32.restype = ctypes.c_int
-        lib.vq_ema_det_workspace_bytes.argtypes = [ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int]
-        lib.vq_ema_det_workspace_bytes.restype = _i64
-        lib.vq_ema_update_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_double, ctypes.c_float, ctypes.c_int, _vp]
-        lib.vq_ema_update_f32.restype = ctypes.c_int
-        lib.vq_affine_stats_workspace_bytes.argtypes = [ctypes.c_int, _i64, ctypes.c_int]
-        lib.vq_affine_stats_workspace_bytes.restype = _i64
-        lib.vq_affine_stats_f32.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, ctypes.c_int, _i64, ctypes.c_int, _vp, _vp, _vp,
-                                            _vp, _i64, _vp]
-        lib.vq_affine_stats_f32.restype = ctypes.c_int
-        lib.vq_affine_apply_f32.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_int, _vp]
-        lib.vq_affine_apply_f32.restype = ctypes.c_int
-        lib.vq_similarities_f32.argtypes = [ap, _vp, _i64, _i64, _vp]
-        lib.vq_similarities_f32.restype = ctypes.c_int
-        lib.vq_softmax_stats_f32.argtypes = [ap, ctypes.c_float, _vp, _i64, _i64, _vp, _vp, _vp]
-        lib.vq_softmax_stats_f32.restype = ctypes.c_int
-        lib.vq_ce_backward_f32.argtypes = [ap, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]
-        lib.vq_ce_backward_f32.restype = ctypes.c_int
-        lib.vq_ce_backward_live_f32.argtypes = [ap, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]
-        lib.vq_ce_backward_live_f32.restype = ctypes.c_int
-        lib.vq_gumbel_row_stride.argtypes = [_i64]
-        lib.vq_gumbel_row_stride.restype = _i64
-        lib.vq_gumbel_workspace_bytes.argtypes = [ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int]
-        lib.vq_gumbel_workspace_bytes.restype = _i64
-        lib.vq_gumbel_stats_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp]
-        lib.vq_gumbel_stats_f32.restype = ctypes.c_int
-        lib.vq_gumbel_backward_x_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _vp]
-        lib.vq_gumbel_backward_x_f32.restype = ctypes.c_int
-        lib.vq_gumbel_backward_codes_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _vp]
-        lib.vq_gumbel_backward_codes_f32.restype = ctypes.c_int
-        lib.vq_gumbel_reinmax_workspace_bytes.argtypes = [ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int]
-        lib.vq_gumbel_reinmax_workspace_bytes.restype = _i64
-        lib.vq_gumbel_reinmax_stats_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp]
-        lib.vq_gumbel_reinmax_stats_f32.restype = ctypes.c_int
-        lib.vq_gumbel_reinmax_columns_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
-                                                      _i64, _vp]
-        lib.vq_gumbel_reinmax_columns_f32.restype = ctypes.c_int
-        lib.vq_gumbel_reinmax_backward_x_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _i64,
-                                                         _vp, _vp, _vp, _i64, _i64, _vp]
-        lib.vq_gumbel_reinmax_backward_x_f32.restype = ctypes.c_int
-        lib.vq_gumbel_reinmax_backward_codes_f32.argtypes = [ap, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                             _vp, _i64, _vp]
-        lib.vq_gumbel_reinmax_backward_codes_f32.restype = ctypes.c_int
-        lib.vq_gumbel_sample_f32.argtypes = [ap, ctypes.c_float, _vp, _vp]
-        lib.vq_gumbel_sample_f32.restype = ctypes.c_int
-        lib.vq_gumbel_noise_f32.argtypes = [_vp, ctypes.c_int, _i64, ctypes.c_int, _vp, _vp, _vp]
-        lib.vq_gumbel_noise_f32.restype = ctypes.c_int
-        lib.vq_quantize_backward_f32.argtypes = [ap, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp]
-        lib.vq_quantize_backward_f32.restype = ctypes.c_int
-        lib.vq_ema_accumulate_residual_f32.argtypes = [ap, _vp, _vp, _vp]
-        lib.vq_ema_accumulate_residual_f32.restype = ctypes.c_int
-        lib.vq_max_fused_stages.argtypes = [ctypes.c_int, ctypes.c_int]
-        lib.vq_max_fused_stages.restype = ctypes.c_int
-        lib.vq_lfq_workspace_bytes.argtypes = [_i64, _i64, ctypes.c_int, ctypes.c_int]
-        lib.vq_lfq_workspace_bytes.restype = _i64
-        lib.vq_lfq_quantize_f32.argtypes = [_vp, _i64, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp,
-                                            _vp, _vp, _vp, _vp, _i64, _vp]
-        lib.vq_lfq_quantize_f32.restype = ctypes.c_int
-        lib.vq_lfq_entropy_fwd_f32.argtypes = [_vp, _i64, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
-                                               _vp, _vp, _vp, _i64, _vp]
-        lib.vq_lfq_entropy_fwd_f32.restype = ctypes.c_int
-        lib.vq_lfq_entropy_bwd_f32.argtypes = [_vp, _i64, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
-                                               _vp, _vp, _vp, _i64, _vp]
-        lib.vq_lfq_entropy_bwd_f32.restype = ctypes.c_int
-        lib.vq_lfq_staged_workspace_bytes.argtypes = [_i64, ctypes.c_int, ctypes.c_int]
-        lib.vq_lfq_staged_workspace_bytes.restype = _i64
-        lib.vq_lfq_entropy_staged_fwd_f32.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp,
-                                                      ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _i64, _vp]
-        lib.vq_lfq_entropy_staged_fwd_f32.restype = ctypes.c_int
-        lib.vq_lfq_entropy_staged_bwd_f32.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp,
-                                                      ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _vp]
-        lib.vq_lfq_entropy_staged_bwd_f32.restype = ctypes.c_int
-        lib.vq_rlfq_workspace_bytes.argtypes = [_i64, _i64, ctypes.c_int]
-        lib.vq_rlfq_workspace_bytes.restype = _i64
-        lib.vq_rlfq_quantize_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
-                                             ctypes.c_int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]
-        lib.vq_rlfq_quantize_f32.restype = ctypes.c_int
-        lib.vq_rlfq_backward_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp,
-                                             _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp]
-        lib.vq_rlfq_backward_f32.restype = ctypes.c_int
-        lib.vq_fsq_quantize_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int,
-                                            _vp, _i64, _i64, _vp, _vp]
-        lib.vq_fsq_quantize_f32.restype = ctypes.c_int
-        lib.vq_fsq_backward_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int,
-                                            _vp, _i64, _i64, _vp, _i64, _i64, _vp]
-        lib.vq_fsq_backward_f32.restype = ctypes.c_int
-        lib.vq_fsq_decode_f32.argtypes = [_vp, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp,
-                                          _vp]
-        lib.vq_fsq_decode_f32.restype = ctypes.c_int
-        lib.vq_decode_f32.argtypes = [_vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int,
-                                      _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _i64,
-                                      _i64, _vp]
-        lib.vq_decode_f32.restype = ctypes.c_int
-        lib.vq_lfq_decode_f32.argtypes = [_vp, ctypes.c_int, _i64, _i64, _i64, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int, _vp, ctypes.c_int, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp]
-        lib.vq_lfq_decode_f32.restype = ctypes.c_int
-        lib.vq_lq_workspace_bytes.argtypes = [_i64, _i64, ctypes.c_int]
-        lib.vq_lq_workspace_bytes.restype = _i64
-        lib.vq_lq_quantize_f32.argtypes = [_vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64,
-                                           _i64, _i64, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _i64, _vp]
-        lib.vq_lq_quantize_f32.restype = ctypes.c_int
-        lib.vq_lq_backward_f32.argtypes = [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
-                                           ctypes.c_float, _i64, _i64, ctypes.c_int, _vp, _i64, _i64, _i64, _vp]
-        lib.vq_lq_backward_f32.restype = ctypes.c_int
-        lib.vq_device_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
-        lib.vq_device_info.restype = ctypes.c_int
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = lib
     return _lib
-
-
-EXPORTED_SYMBOLS = (
-    "vq_packed_floats", "vq_pack_codebooks_f32", "vq_workspace_bytes", "vq_workspace_bytes_wide", "vq_quantize_f32", "vq_nearest_f32",
-    "vq_residual_f32", "vq_keys_init", "vq_search_keys_f32", "vq_finalize_keys_f32", "vq_last_error",
-    "vq_device_info", "vq_ema_accumulate_f32", "vq_ema_update_f32", "vq_similarities_f32", "vq_softmax_stats_f32",
-    "vq_ce_backward_f32", "vq_ce_backward_live_f32", "vq_quantize_lse_f32",
-    "vq_quantize_backward_f32", "vq_ema_accumulate_residual_f32", "vq_max_fused_stages", "vq_ema_accumulate_det_f32",
-    "vq_ema_det_workspace_bytes", "vq_key_planes", "vq_search_key_planes_f32", "vq_finalize_key_planes_f32",
-    "vq_lfq_workspace_bytes", "vq_lfq_quantize_f32", "vq_lfq_entropy_fwd_f32", "vq_lfq_entropy_bwd_f32",
-    "vq_lfq_staged_workspace_bytes", "vq_lfq_entropy_staged_fwd_f32", "vq_lfq_entropy_staged_bwd_f32",
-    "vq_rlfq_workspace_bytes", "vq_rlfq_quantize_f32", "vq_rlfq_backward_f32",
-    "vq_fsq_quantize_f32", "vq_fsq_backward_f32", "vq_fsq_decode_f32",
-    "vq_lq_workspace_bytes", "vq_lq_quantize_f32", "vq_lq_backward_f32",
-    "vq_gumbel_row_stride", "vq_gumbel_workspace_bytes", "vq_gumbel_stats_f32", "vq_gumbel_backward_x_f32",
-    "vq_gumbel_backward_codes_f32", "vq_gumbel_sample_f32", "vq_gumbel_noise_f32",
-    "vq_gumbel_reinmax_workspace_bytes", "vq_gumbel_reinmax_stats_f32", "vq_gumbel_reinmax_columns_f32",
-    "vq_gumbel_reinmax_backward_x_f32", "vq_gumbel_reinmax_backward_codes_f32",
-    "vq_affine_stats_workspace_bytes", "vq_affine_stats_f32", "vq_affine_apply_f32",
-    "vq_decode_f32", "vq_lfq_decode_f32",
-)
 
 
 def _check(rc: int, what: str):
@@ -277,6 +202,36 @@ def _require_gpu(*tensors):
 
 def _stream_ptr(device) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _call(name: str, device, *args, accept=(0,)) -> int:
+    """Enqueue the entry point ``name`` (its last C parameter is ``void *stream``) on ``device``'s current stream with
+    ``device`` current.  -> its return code; one outside ``accept`` raises with the library's error text."""
+    with torch.cuda.device(device):
+        rc = getattr(load(), name)(*args, _stream_ptr(device))
+    if rc not in accept:
+        _check(rc, name)
+    return rc
+
+
+def _ptr(t):
+    """The device address of an optional tensor (None = a NULL pointer)."""
+    return None if t is None else t.data_ptr()
+
+
+def _alloc_workspace(nbytes: int, device):
+    """-> (buffer of at least ``nbytes`` bytes, 16-byte aligned and a multiple of 16 bytes long; its length in bytes, which
+    is the workspace_bytes handed to C)."""
+    ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=device)
+    return ws, ws.numel() * 8
+
+
+def _sized_workspace(sizer: str, device, *dims):
+    """_alloc_workspace of ``sizer(*dims)`` bytes, for the sizers that answer <= 0 (and set vq_last_error) on a shape they reject."""
+    nbytes = int(getattr(load(), sizer)(*dims))
+    if nbytes <= 0:
+        raise RuntimeError(f"{sizer}({', '.join(str(v) for v in dims)}) failed: {load().vq_last_error().decode()}")
+    return _alloc_workspace(nbytes, device)
 
 
 def device_info() -> str:
@@ -303,9 +258,7 @@ def pack_codebooks(cb: torch.Tensor, metric: int) -> torch.Tensor:
     n = cb.numel() // (K * D)
     pf = packed_floats(K, D)
     packed = torch.empty((n, pf), dtype=torch.float32, device=cb.device)
-    with torch.cuda.device(cb.device):
-        _check(load().vq_pack_codebooks_f32(cb.data_ptr(), n, K * D, K, D, metric, packed.data_ptr(),
-                                            _stream_ptr(cb.device)), "vq_pack_codebooks_f32")
+    _call("vq_pack_codebooks_f32", cb.device, cb.data_ptr(), n, K * D, K, D, metric, packed.data_ptr())
     return packed
 
 
@@ -318,17 +271,61 @@ def _check_packed(packed: torch.Tensor, n: int, K: int, D: int, device) -> None:
                          f"{n} codebook(s) of K={K}, D={D} on {device} (expected [{n}, {packed_floats(K, D)}] contiguous fp32)")
 
 
-def _workspace(H: int, M: int, Q: int, device, K: int = 0, D: int = 0) -> torch.Tensor:
+def _packed_image(cb: torch.Tensor, metric: int, packed, n: int, K: int, D: int, device) -> torch.Tensor:
+    """The caller's cached image of the ``n`` codebooks in ``cb`` after _check_packed, or a fresh one when it has none."""
+    if packed is None:
+        packed = pack_codebooks(cb, metric)
+    _check_packed(packed, n, K, D, device)
+    return packed
+
+
+def _search_workspace(H: int, M: int, Q: int, device, K: int = 0, D: int = 0):
     nbytes = int(load().vq_workspace_bytes(H, M, Q))
     if D > 512:  # rows wider than 512 dims: room for the distance chains carried between the slices of the sweep
         nbytes = max(nbytes, int(load().vq_workspace_bytes_wide(H, M, K, D)))
-    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=device)
+    return _alloc_workspace(nbytes, device)
 
 
 def _row_strides(t: torch.Tensor):
     """t is [H, M, D] (any strides, last dim contiguous) -> (row_stride, head_stride) in elements."""
     assert t.dim() == 3 and (t.shape[-1] == 1 or t.stride(-1) == 1), "last dim must be contiguous"
     return int(t.stride(1)), int(t.stride(0))
+
+
+def _vq_args(x: torch.Tensor, cb: torch.Tensor, *, Q: int = 1, shared: bool = True, metric: int = EUCLID, flags: int = 0,
+             packed=None, out=None, idx=None, idx_strides=None, best=None, sq_err=None, workspace=None) -> VqArgs:
+    """The one place a ``struct vq_args`` is filled.  x [H, M, D] (strided rows ok); cb [H, K, D], or [H, Qc, K, D] for a
+    residual stack of Q stages; ``shared``: every stage reads the head's first codebook.  The rest is optional: packed (the
+    image of cb), out [H, M, D], idx with ``idx_strides`` = (row, head, stage) when they are not those of an [H, M, Q]
+    tensor, best (laid out as idx), sq_err, workspace = the pair of _alloc_workspace."""
+    H, M, D = x.shape
+    K = cb.shape[-2]
+    Qc = cb.shape[1] if cb.dim() == 4 else 1
+    a = VqArgs()
+    a.H, a.Q, a.M, a.K, a.D, a.metric, a.flags = H, Q, M, K, D, metric, flags
+    a.x = x.data_ptr()
+    a.x_rs, a.x_hs = _row_strides(x)
+    # a stage stride of 0 is how the header spells "all stages share one codebook", for the codes and for their image
+    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), Qc * K * D, (0 if shared else K * D)
+    if packed is not None:
+        pf = packed.shape[-1]
+        a.packed, a.pk_hs, a.pk_qs = packed.data_ptr(), Qc * pf, (0 if shared else pf)
+    if out is not None:
+        a.out = out.data_ptr()
+        a.out_rs, a.out_hs = _row_strides(out)
+    if idx is not None:
+        a.idx = idx.data_ptr()
+        a.idx_rs, a.idx_hs, a.idx_qs = idx_strides or (int(idx.stride(1)), int(idx.stride(0)), int(idx.stride(2)))
+    if best is not None:
+        a.best = best.data_ptr()
+    if sq_err is not None:
+        a.sq_err = sq_err.data_ptr()
+    if workspace is not None:
+        a.workspace, a.workspace_bytes = workspace[0].data_ptr(), workspace[1]
+    # the struct holds bare addresses: the tensors behind them (a packed image or a workspace made on the way here has no
+    # other owner) live as long as it does, that is until the launch that reads them is enqueued
+    a.tensors = (x, cb, packed, out, idx, best, sq_err, workspace)
+    return a
 
 
 def quantize(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, ste: bool = False, want_out: bool = True,
@@ -365,11 +362,7 @@ def quantize(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, ste: bo
     else:
         Q = Qc
     dev = x.device
-    if packed is None:
-        packed = pack_codebooks(cb, metric)
-    _check_packed(packed, Hc * Qc, K, D, dev)
-    pf = packed.shape[-1]
-    x_rs, x_hs = _row_strides(x)
+    packed = _packed_image(cb, metric, packed, Hc * Qc, K, D, dev)
     if idx is None:
         idx = torch.empty((H, M, Q), dtype=torch.int64, device=dev)
     assert idx.dtype == torch.int64 and tuple(idx.shape) == (H, M, Q)
@@ -381,69 +374,55 @@ def quantize(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, ste: bo
         if out is None:
             out = torch.empty((H, M, D), dtype=torch.float32, device=dev)
         assert out.dtype == torch.float32 and tuple(out.shape) == (H, M, D)
-        o_rs, o_hs = _row_strides(out)
     else:
-        out, o_rs, o_hs = None, 0, 0
+        out = None
     sq_err = torch.empty((H, Q) if sq_err_per_head else (Q,), dtype=torch.float64, device=dev) if want_sq_err else None
-    ws = _workspace(H, M, Q, dev, K, D)
-    a = VqArgs()
-    a.H, a.Q, a.M, a.K, a.D, a.metric = H, Q, M, K, D, metric
-    a.flags = flags | (F_STE if ste else 0) | (F_SQERR_PER_HEAD if (sq_err_per_head and want_sq_err) else 0)
-    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
-    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), Qc * K * D, (0 if stages_share_codebook else K * D)
-    a.packed, a.pk_hs, a.pk_qs = packed.data_ptr(), Qc * pf, (0 if stages_share_codebook else pf)
-    a.out, a.out_rs, a.out_hs = (out.data_ptr() if out is not None else None), o_rs, o_hs
-    a.idx, a.idx_hs, a.idx_rs, a.idx_qs = idx.data_ptr(), int(idx.stride(0)), int(idx.stride(1)), int(idx.stride(2))
-    a.best = best.data_ptr() if best is not None else None
-    a.sq_err = sq_err.data_ptr() if sq_err is not None else None
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
-    with torch.cuda.device(dev):
-        if _event_sink is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(dev))
-        if want_lse:
-            assert Q == 1
-            lse = torch.empty((H, M), dtype=torch.float32, device=dev)
-            _check(load().vq_quantize_lse_f32(ctypes.byref(a), lse.data_ptr(), _stream_ptr(dev)), "vq_quantize_lse_f32")
-        else:
-            lse = None
-            _check(load().vq_quantize_f32(ctypes.byref(a), _stream_ptr(dev)), "vq_quantize_f32")
-        if _event_sink is not None:
-            e1.record(torch.cuda.current_stream(dev))
-            _event_sink.append((e0, e1))
+    flags |= (F_STE if ste else 0) | (F_SQERR_PER_HEAD if (sq_err_per_head and want_sq_err) else 0)
+    a = _vq_args(x, cb, Q=Q, shared=stages_share_codebook, metric=metric, flags=flags, packed=packed, out=out, idx=idx,
+                 best=best, sq_err=sq_err, workspace=_search_workspace(H, M, Q, dev, K, D))
+    lse = None
+    if want_lse:
+        assert Q == 1
+        lse = torch.empty((H, M), dtype=torch.float32, device=dev)
+    if _event_sink is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(torch.cuda.current_stream(dev))
+    if want_lse:
+        _call("vq_quantize_lse_f32", dev, a, lse.data_ptr())
+    else:
+        _call("vq_quantize_f32", dev, a)
+    if _event_sink is not None:
+        e1.record(torch.cuda.current_stream(dev))
+        _event_sink.append((e0, e1))
     return dict(out=out, idx=idx, best=best, sq_err=sq_err, lse=lse)
 
 
 def keys_init(keys: torch.Tensor):
     _require_gpu(keys)
     assert keys.dtype == torch.int64 and keys.is_contiguous()
-    with torch.cuda.device(keys.device):
-        _check(load().vq_keys_init(keys.data_ptr(), keys.numel(), _stream_ptr(keys.device)), "vq_keys_init")
+    _call("vq_keys_init", keys.device, keys.data_ptr(), keys.numel())
+
+
+def _search_args(x: torch.Tensor, cb: torch.Tensor, metric: int, packed, flags: int, *, wide_workspace: bool = True,
+                 **outputs) -> VqArgs:
+    """vq_args of a one-stage sweep, as search_keys and search_key_planes make it: x [H, M, D], cb [H, K, D] contiguous, its
+    image packed here unless given; ``outputs`` go to _vq_args.  Such a sweep needs no scratch memory except for rows wider
+    than 512 dims, whose distance chains wait in a workspace between two slices: ``wide_workspace`` attaches it."""
+    assert x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous()
+    H, M, D = x.shape
+    _, K, _ = cb.shape
+    packed = _packed_image(cb, metric, packed, H, K, D, x.device)
+    ws = _search_workspace(H, M, 1, x.device, K, D) if wide_workspace and D > 512 else None
+    return _vq_args(x, cb, metric=metric, flags=flags, packed=packed, workspace=ws, **outputs)
 
 
 def search_keys(x: torch.Tensor, cb: torch.Tensor, keys: torch.Tensor, *, metric: int = EUCLID, idx_offset: int = 0,
                 packed: torch.Tensor | None = None, flags: int = 0):
     """Shard-local search: atomically MIN-combine packed (value, idx + idx_offset) keys into keys [H, M]."""
     _require_gpu(x, cb, keys)
-    assert x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous() and keys.dtype == torch.int64
-    H, M, D = x.shape
-    _, K, _ = cb.shape
-    assert keys.shape == (H, M) and keys.is_contiguous()
-    if packed is None:
-        packed = pack_codebooks(cb, metric)
-    _check_packed(packed, H, K, D, x.device)
-    x_rs, x_hs = _row_strides(x)
-    a = VqArgs()
-    a.H, a.Q, a.M, a.K, a.D, a.metric, a.flags = H, 1, M, K, D, metric, flags
-    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
-    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), K * D, 0
-    a.packed, a.pk_hs, a.pk_qs = packed.data_ptr(), packed.shape[-1], 0
-    if D > 512:
-        ws = _workspace(H, M, 1, x.device, K, D)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
-    with torch.cuda.device(x.device):
-        _check(load().vq_search_keys_f32(ctypes.byref(a), idx_offset, keys.data_ptr(), _stream_ptr(x.device)),
-               "vq_search_keys_f32")
+    assert keys.dtype == torch.int64 and keys.shape == tuple(x.shape[:2]) and keys.is_contiguous()
+    a = _search_args(x, cb, metric, packed, flags)
+    _call("vq_search_keys_f32", x.device, a, idx_offset, keys.data_ptr())
 
 
 def search_key_planes(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, idx_offset: int = 0,
@@ -451,26 +430,11 @@ def search_key_planes(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID
     """Shard-local search without init launch or atomics: -> keys [P, H, M] int64, P = the K splits the library chose for
     this shape (vq_key_planes); the winner of a row is the MIN over the planes (and over the other shards' planes)."""
     _require_gpu(x, cb)
-    assert x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous()
-    H, M, D = x.shape
-    _, K, _ = cb.shape
-    if packed is None:
-        packed = pack_codebooks(cb, metric)
-    _check_packed(packed, H, K, D, x.device)
-    x_rs, x_hs = _row_strides(x)
-    a = VqArgs()
-    a.H, a.Q, a.M, a.K, a.D, a.metric, a.flags = H, 1, M, K, D, metric, flags
-    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
-    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), K * D, 0
-    a.packed, a.pk_hs, a.pk_qs = packed.data_ptr(), packed.shape[-1], 0
-    if D > 512:
-        ws = _workspace(H, M, 1, x.device, K, D)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
-    with torch.cuda.device(x.device):
-        planes = int(load().vq_key_planes(ctypes.byref(a)))
-        keys = torch.empty((planes, H, M), dtype=torch.int64, device=x.device)
-        _check(load().vq_search_key_planes_f32(ctypes.byref(a), idx_offset, keys.data_ptr(), _stream_ptr(x.device)),
-               "vq_search_key_planes_f32")
+    a = _search_args(x, cb, metric, packed, flags)
+    with torch.cuda.device(x.device):  # (the split count follows the CUs of the current device)
+        planes = int(load().vq_key_planes(a))
+    keys = torch.empty((planes, a.H, a.M), dtype=torch.int64, device=x.device)
+    _call("vq_search_key_planes_f32", x.device, a, idx_offset, keys.data_ptr())
     return keys
 
 
@@ -486,7 +450,6 @@ def finalize_keys(x: torch.Tensor, cb_full: torch.Tensor, keys: torch.Tensor, *,
         planes = keys.shape[0]
         assert tuple(keys.shape[1:]) == (H, M)
     assert keys.dtype == torch.int64 and keys.is_contiguous()
-    K = cb_full.shape[1]
     dev = x.device
     if idx is None:  # (idx / best may be [H, M] views of larger buffers: same strides, last dim contiguous)
         idx = torch.empty((H, M), dtype=torch.int64, device=dev)
@@ -497,23 +460,11 @@ def finalize_keys(x: torch.Tensor, cb_full: torch.Tensor, keys: torch.Tensor, *,
     if want_out and out is None:
         out = torch.empty((H, M, D), dtype=torch.float32, device=dev)
     sq_err = torch.empty((1,), dtype=torch.float64, device=dev) if want_sq_err else None
-    ws = _workspace(H, M, 1, dev)
-    x_rs, x_hs = _row_strides(x)
-    a = VqArgs()
-    a.H, a.Q, a.M, a.K, a.D, a.metric = H, 1, M, K, D, metric
-    a.flags = F_STE if ste else 0
-    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
-    a.cb, a.cb_hs, a.cb_qs = cb_full.data_ptr(), K * D, 0
-    if out is not None:
-        o_rs, o_hs = _row_strides(out)
-        a.out, a.out_rs, a.out_hs = out.data_ptr(), o_rs, o_hs
-    a.idx, a.idx_rs, a.idx_hs, a.idx_qs = idx.data_ptr(), int(idx.stride(1)) if M > 1 else 1, int(idx.stride(0)), 0
-    a.best = best.data_ptr()
-    a.sq_err = sq_err.data_ptr() if sq_err is not None else None
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
-    with torch.cuda.device(dev):
-        _check(load().vq_finalize_key_planes_f32(ctypes.byref(a), keys.data_ptr(), planes, _stream_ptr(dev)),
-               "vq_finalize_key_planes_f32")
+    # idx is [H, M]: no stage axis (stride 0), and the dense row stride where torch's own is arbitrary (at most one row)
+    idx_strides = (int(idx.stride(1)) if M > 1 else 1, int(idx.stride(0)), 0)
+    a = _vq_args(x, cb_full, metric=metric, flags=F_STE if ste else 0, out=out, idx=idx, idx_strides=idx_strides, best=best,
+                 sq_err=sq_err, workspace=_search_workspace(H, M, 1, dev))
+    _call("vq_finalize_key_planes_f32", dev, a, keys.data_ptr(), planes)
     return dict(out=out, idx=idx, best=best, sq_err=sq_err)
 
 
@@ -531,20 +482,17 @@ def ema_accumulate(x: torch.Tensor, idx: torch.Tensor, K: int, mask: torch.Tenso
     if mask is not None:
         m8 = mask.to(torch.uint8).contiguous()
         assert tuple(m8.shape) == (H, M)
-    with torch.cuda.device(dev):
-        if deterministic and M > 0:
+    args = (x.data_ptr(), x_rs, x_hs, idx.data_ptr(), int(idx.stride(1)), int(idx.stride(0)), _ptr(m8), H, M, K, D,
+            counts.data_ptr(), sums.data_ptr())
+    if deterministic and M > 0:
+        with torch.cuda.device(dev):  # (the plan spreads the row blocks over the CUs of the current device)
             nbytes = int(load().vq_ema_det_workspace_bytes(H, M, K, D))
-            if nbytes == 0:
-                raise RuntimeError(f"deterministic EMA accumulation supports D <= 2048 (got D = {D})")
-            ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
-            _check(load().vq_ema_accumulate_det_f32(x.data_ptr(), x_rs, x_hs, idx.data_ptr(), int(idx.stride(1)),
-                                                    int(idx.stride(0)), m8.data_ptr() if m8 is not None else None, H, M, K, D,
-                                                    counts.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel() * 8,
-                                                    _stream_ptr(dev)), "vq_ema_accumulate_det_f32")
-            return counts, sums
-        _check(load().vq_ema_accumulate_f32(x.data_ptr(), x_rs, x_hs, idx.data_ptr(), int(idx.stride(1)), int(idx.stride(0)),
-                                            m8.data_ptr() if m8 is not None else None, H, M, K, D, counts.data_ptr(),
-                                            sums.data_ptr(), _stream_ptr(dev)), "vq_ema_accumulate_f32")
+        if nbytes == 0:
+            raise RuntimeError(f"deterministic EMA accumulation supports D <= 2048 (got D = {D})")
+        ws, ws_bytes = _alloc_workspace(nbytes, dev)
+        _call("vq_ema_accumulate_det_f32", dev, *args, ws.data_ptr(), ws_bytes)
+    else:
+        _call("vq_ema_accumulate_f32", dev, *args)
     return counts, sums
 
 
@@ -557,10 +505,8 @@ def ema_update(cluster_size: torch.Tensor, embed_avg: torch.Tensor, embeddings: 
     H, K, D = embed_avg.shape
     dev = embed_avg.device
     total = torch.empty((H,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _check(load().vq_ema_update_f32(cluster_size.data_ptr(), embed_avg.data_ptr(), embeddings.data_ptr(),
-                                        counts.data_ptr(), sums.data_ptr(), total.data_ptr(), H, K, D, float(decay),
-                                        float(eps), 1 if l2norm else 0, _stream_ptr(dev)), "vq_ema_update_f32")
+    _call("vq_ema_update_f32", dev, cluster_size.data_ptr(), embed_avg.data_ptr(), embeddings.data_ptr(), counts.data_ptr(),
+          sums.data_ptr(), total.data_ptr(), H, K, D, float(decay), float(eps), 1 if l2norm else 0)
 
 
 def column_stats(x: torch.Tensor, mask: torch.Tensor | None = None):
@@ -581,12 +527,9 @@ def column_stats(x: torch.Tensor, mask: torch.Tensor | None = None):
     count = torch.empty((H,), dtype=torch.int64, device=dev)
     mean = torch.empty((H, D), dtype=torch.float32, device=dev)
     m2 = torch.empty((H, D), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        nbytes = int(load().vq_affine_stats_workspace_bytes(H, M, D))
-        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
-        _check(load().vq_affine_stats_f32(x.data_ptr(), x_rs, x_hs, m8.data_ptr() if m8 is not None else None, m_rs, m_hs,
-                                          H, M, D, count.data_ptr(), mean.data_ptr(), m2.data_ptr(), ws.data_ptr(),
-                                          ws.numel() * 8, _stream_ptr(dev)), "vq_affine_stats_f32")
+    ws, ws_bytes = _alloc_workspace(int(load().vq_affine_stats_workspace_bytes(H, M, D)), dev)
+    _call("vq_affine_stats_f32", dev, x.data_ptr(), x_rs, x_hs, _ptr(m8), m_rs, m_hs, H, M, D, count.data_ptr(),
+          mean.data_ptr(), m2.data_ptr(), ws.data_ptr(), ws_bytes)
     return count, mean, m2
 
 
@@ -606,48 +549,32 @@ def affine_apply(src: torch.Tensor, codebook_mean: torch.Tensor, codebook_varian
     if out is None:
         out = torch.empty_like(src)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == src.shape
-    dev = src.device
-    with torch.cuda.device(dev):
-        _check(load().vq_affine_apply_f32(src.data_ptr(), out.data_ptr(), hits.data_ptr() if hits is not None else None,
-                                          *(t.data_ptr() for t in stats), H, K, D, int(mode), _stream_ptr(dev)),
-               "vq_affine_apply_f32")
+    _call("vq_affine_apply_f32", src.device, src.data_ptr(), out.data_ptr(), _ptr(hits), *(t.data_ptr() for t in stats),
+          H, K, D, int(mode))
     return out
 
 
-def _aux_args(x: torch.Tensor, cb: torch.Tensor, metric: int, packed, flags: int):
+def _aux_args(x: torch.Tensor, cb: torch.Tensor, metric: int, packed, flags: int, *, wide_workspace: bool = False,
+              **outputs) -> VqArgs:
+    """_search_args for the sweeps that consume the similarities: fp32 only, cb's heads and dims must be x's, and the wide
+    rows' workspace only on request (most of these sweeps stop at 512 dims or fewer)."""
     _require_gpu(x, cb)
     assert x.dtype == torch.float32 and cb.dtype == torch.float32
-    assert x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous()
-    H, M, D = x.shape
-    Hc, K, Dc = cb.shape
-    assert Hc == H and Dc == D
-    if packed is None:
-        packed = pack_codebooks(cb, metric)
-    _check_packed(packed, H, K, D, x.device)
-    x_rs, x_hs = _row_strides(x)
-    a = VqArgs()
-    a.H, a.Q, a.M, a.K, a.D, a.metric, a.flags = H, 1, M, K, D, metric, flags
-    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
-    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), K * D, 0
-    a.packed, a.pk_hs, a.pk_qs = packed.data_ptr(), packed.shape[-1], 0
-    return a, packed
+    assert x.dim() == 3 and cb.dim() == 3 and cb.shape[0] == x.shape[0] and cb.shape[2] == x.shape[2]
+    return _search_args(x, cb, metric, packed, flags, wide_workspace=wide_workspace, **outputs)
 
 
 def similarities(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, packed: torch.Tensor | None = None,
                  flags: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
     """x [H, M, D] (strided rows ok), cb [H, K, D] -> sims [H, M, K]: -cdist (Euclid) or dot products, the values the
     search compares (codebooks.py:386).  The caller bounds M (row chunks): this DOES materialise [H, M, K]."""
-    a, packed = _aux_args(x, cb, metric, packed, flags)
+    # rows wider than 512 dims: the sliced sweep needs its workspace (the one-thread-per-entry kernel does not)
+    a = _aux_args(x, cb, metric, packed, flags, wide_workspace=not (flags & F_FORCE_SIMPLE))
     H, M, K = a.H, a.M, a.K
     if out is None:
         out = torch.empty((H, M, K), dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and tuple(out.shape) == (H, M, K) and (K == 1 or out.stride(2) == 1)
-    if a.D > 512 and not (flags & F_FORCE_SIMPLE):  # rows wider than 512 dims: the sliced sweep needs its workspace
-        ws = _workspace(H, M, 1, x.device, K, a.D)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
-    with torch.cuda.device(x.device):
-        _check(load().vq_similarities_f32(ctypes.byref(a), out.data_ptr(), int(out.stride(1)), int(out.stride(0)),
-                                          _stream_ptr(x.device)), "vq_similarities_f32")
+    _call("vq_similarities_f32", x.device, a, out.data_ptr(), int(out.stride(1)), int(out.stride(0)))
     return out
 
 
@@ -657,21 +584,18 @@ def softmax_stats(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, sc
     (negative = ignored -> 0).  -> (lse [H, M], target_logit [H, M] | None).  [M, K] is never materialised."""
     if x.shape[-1] > SOFTMAX_STATS_MAX_DIM:
         return _softmax_stats_wide(x, cb, metric, scale, target, packed)
-    a, packed = _aux_args(x, cb, metric, packed, 0)
+    a = _aux_args(x, cb, metric, packed, 0)
     H, M = a.H, a.M
     dev = x.device
     lse = torch.empty((H, M), dtype=torch.float32, device=dev)
     tl = None
-    t_ptr, t_rs, t_hs = None, 0, 0
+    t_rs, t_hs = 0, 0
     if target is not None:
         _require_gpu(target)
         assert target.dtype == torch.int64 and tuple(target.shape) == (H, M)
         tl = torch.empty((H, M), dtype=torch.float32, device=dev)
-        t_ptr, t_rs, t_hs = target.data_ptr(), int(target.stride(1)), int(target.stride(0))
-    with torch.cuda.device(dev):
-        _check(load().vq_softmax_stats_f32(ctypes.byref(a), float(scale), t_ptr, t_rs, t_hs, lse.data_ptr(),
-                                           tl.data_ptr() if tl is not None else None, _stream_ptr(dev)),
-               "vq_softmax_stats_f32")
+        t_rs, t_hs = int(target.stride(1)), int(target.stride(0))
+    _call("vq_softmax_stats_f32", dev, a, float(scale), _ptr(target), t_rs, t_hs, lse.data_ptr(), _ptr(tl))
     return lse, tl
 
 
@@ -690,7 +614,7 @@ def _softmax_stats_wide(x, cb, metric, scale, target, packed):
     if packed is None:
         packed = pack_codebooks(cb, metric)  # once for all row chunks
     lse = torch.empty((H, M), dtype=torch.float32, device=x.device)
-    tl = torch.zeros((H, M), dtype=torch.float32, device=x.device) if target is not None else None
+    tl = None if target is None else torch.zeros((H, M), dtype=torch.float32, device=x.device)
     step = max(1, (64 << 20) // max(1, H * K))  # <= 256 MiB of matrix alive
     for r0 in range(0, M, step):
         logits = similarities(x[:, r0:r0 + step], cb, metric=metric, packed=packed) * scale
@@ -713,7 +637,7 @@ def ce_backward(x: torch.Tensor, cb: torch.Tensor, lse: torch.Tensor, target_log
     ``live`` [H, K, D]: the codes as they are NOW, when they have been rewritten since ``cb`` was searched (the EMA step):
     the weights come from ``cb``, what they are multiplied with from ``live`` (vq_ce_backward_live_f32, D <= 256).
     ``live_packed``: its packed image when the caller has one cached; packed here otherwise."""
-    a, packed = _aux_args(x, cb, metric, packed, 0)
+    a = _aux_args(x, cb, metric, packed, 0)
     H, M, D = x.shape
     _require_gpu(lse, target_logit, target, coef, live)
     assert D <= (CE_BACKWARD_MAX_DIM if live is None else CE_BACKWARD_LIVE_MAX_DIM)
@@ -722,23 +646,17 @@ def ce_backward(x: torch.Tensor, cb: torch.Tensor, lse: torch.Tensor, target_log
     assert target.dtype == torch.int64 and tuple(target.shape) == (H, M)
     assert coef.dtype == torch.float32 and coef.numel() == 1
     gx = torch.empty((H, M, D), dtype=torch.float32, device=x.device)
+    args = (lse.data_ptr(), target_logit.data_ptr(), target.data_ptr(), int(target.stride(1)), int(target.stride(0)),
+            coef.data_ptr(), gx.data_ptr(), D, M * D)
     if live is not None:
         K = cb.shape[1]
         assert live.dtype == torch.float32 and tuple(live.shape) == (H, K, D) and live.device == x.device
         live = live.contiguous()
-        if live_packed is None:
-            live_packed = pack_codebooks(live, metric)
-        _check_packed(live_packed, H, K, D, x.device)
-        with torch.cuda.device(x.device):
-            _check(load().vq_ce_backward_live_f32(ctypes.byref(a), live.data_ptr(), K * D, live_packed.data_ptr(),
-                                                  live_packed.shape[-1], lse.data_ptr(), target_logit.data_ptr(), target.data_ptr(),
-                                                  int(target.stride(1)), int(target.stride(0)), coef.data_ptr(), gx.data_ptr(), D,
-                                                  M * D, _stream_ptr(x.device)), "vq_ce_backward_live_f32")
-        return gx
-    with torch.cuda.device(x.device):
-        _check(load().vq_ce_backward_f32(ctypes.byref(a), lse.data_ptr(), target_logit.data_ptr(), target.data_ptr(), int(target.stride(1)),
-                                         int(target.stride(0)), coef.data_ptr(), gx.data_ptr(), D, M * D,
-                                         _stream_ptr(x.device)), "vq_ce_backward_f32")
+        live_packed = _packed_image(live, metric, live_packed, H, K, D, x.device)
+        _call("vq_ce_backward_live_f32", x.device, a, live.data_ptr(), K * D, live_packed.data_ptr(), live_packed.shape[-1],
+              *args)
+    else:
+        _call("vq_ce_backward_f32", x.device, a, *args)
     return gx
 
 
@@ -746,11 +664,10 @@ GUMBEL_MAX_DIM = 256  # vq_gumbel_*_f32: rows of one launch
 
 
 def _gumbel_args(x, cb, g, metric, packed):
-    a, packed = _aux_args(x, cb, metric, packed, 0)
+    a = _aux_args(x, cb, metric, packed, 0)
     _require_gpu(g)
     assert a.D <= GUMBEL_MAX_DIM and g.dtype == torch.float32 and tuple(g.shape) == tuple(x.shape)
-    g_rs, g_hs = _row_strides(g)
-    return a, packed, g_rs, g_hs
+    return (a, *_row_strides(g))
 
 
 def _grad_x_out(x, out):
@@ -767,7 +684,7 @@ def _gumbel_workspace(x, K, sizer):
     with torch.cuda.device(x.device):  # (the plan splits the rows over the CUs of the current device)
         nbytes = int(getattr(load(), sizer)(H, M, K, D))
     assert nbytes > 0, f"{sizer}: unsupported shape"
-    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=x.device)
+    return _alloc_workspace(nbytes, x.device)[0]
 
 
 def gumbel_stats(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, *, metric: int = EUCLID, tau: float = 1.0,
@@ -775,13 +692,11 @@ def gumbel_stats(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, *, metric: 
     """Row statistics of the straight-through Gumbel backward: x, g [H, M, D] (strided rows ok), cb [H, K, D] ->
     (lse2, delta), both [H, vq_gumbel_row_stride(M)] (columns past M unused): lse2 = log2 sum_k exp2(tau * sim * log2 e),
     delta = sum_k softmax_k(tau * sim) * (g . c_k).  The pair is what gumbel_backward_x / gumbel_backward_codes take."""
-    a, packed, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
+    a, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
     stride = int(load().vq_gumbel_row_stride(a.M))
     lse2 = torch.empty((a.H, stride), dtype=torch.float32, device=x.device)
     delta = torch.empty((a.H, stride), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(load().vq_gumbel_stats_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(),
-                                          delta.data_ptr(), _stream_ptr(x.device)), "vq_gumbel_stats_f32")
+    _call("vq_gumbel_stats_f32", x.device, a, g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(), delta.data_ptr())
     return lse2, delta
 
 
@@ -790,13 +705,11 @@ def gumbel_backward_x(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, lse2: 
                       out: torch.Tensor | None = None) -> torch.Tensor:
     """d/dx of the straight-through Gumbel softmax through the similarities, one fused sweep -> gx [H, M, D]
     (``out``: a destination with strided rows)."""
-    a, packed, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
+    a, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
     _check_stat_arrays(x, a.M, lse2, delta)
     out, o_rs, o_hs = _grad_x_out(x, out)
-    with torch.cuda.device(x.device):
-        _check(load().vq_gumbel_backward_x_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(),
-                                               delta.data_ptr(), out.data_ptr(), o_rs, o_hs, _stream_ptr(x.device)),
-               "vq_gumbel_backward_x_f32")
+    _call("vq_gumbel_backward_x_f32", x.device, a, g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(), delta.data_ptr(),
+          out.data_ptr(), o_rs, o_hs)
     return out
 
 
@@ -813,10 +726,8 @@ def gumbel_backward_codes(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, ls
     _check_stat_arrays(x, a.M, lse2, delta)
     ws = _gumbel_workspace(x, a.K, "vq_gumbel_workspace_bytes")
     gc = torch.empty((a.H, a.K, a.D), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(load().vq_gumbel_backward_codes_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(),
-                                                   delta.data_ptr(), gc.data_ptr(), ws.data_ptr(), ws.numel() * 8,
-                                                   _stream_ptr(x.device)), "vq_gumbel_backward_codes_f32")
+    _call("vq_gumbel_backward_codes_f32", x.device, a, g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(), delta.data_ptr(),
+          gc.data_ptr(), ws.data_ptr(), ws.numel() * 8)
     return gc
 
 
@@ -828,13 +739,7 @@ def _codes_args(x, cb, g, metric):
     H, M, D = x.shape
     K = cb.shape[1]
     assert cb.shape[0] == H and cb.shape[2] == D and gumbel_codes_supported(H, M, K, D)
-    x_rs, x_hs = _row_strides(x)
-    g_rs, g_hs = _row_strides(g)
-    a = VqArgs()
-    a.H, a.Q, a.M, a.K, a.D, a.metric, a.flags = H, 1, M, K, D, metric, 0
-    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
-    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), K * D, 0
-    return a, g_rs, g_hs
+    return (_vq_args(x, cb, metric=metric), *_row_strides(g))
 
 
 def _check_stat_arrays(x, n, *arrays):
@@ -854,13 +759,10 @@ def gumbel_reinmax_stats(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, *, 
     """Row statistics of the reinmax Gumbel backward in one sweep: x, g [H, M, D] (strided rows ok), cb [H, K, D] ->
     (lse2_tau, lse2_one, delta0), each [H, vq_gumbel_row_stride(M)] (columns past M unused): the log2-domain log-sum-exp of
     the similarities at tau and at 1, and delta0 = sum_k softmax_k(sim) * (g . c_k)."""
-    a, packed, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
+    a, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
     stride = int(load().vq_gumbel_row_stride(a.M))
     out = [torch.empty((a.H, stride), dtype=torch.float32, device=x.device) for _ in range(3)]
-    with torch.cuda.device(x.device):
-        _check(load().vq_gumbel_reinmax_stats_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), out[0].data_ptr(),
-                                                  out[1].data_ptr(), out[2].data_ptr(), _stream_ptr(x.device)),
-               "vq_gumbel_reinmax_stats_f32")
+    _call("vq_gumbel_reinmax_stats_f32", x.device, a, g.data_ptr(), g_rs, g_hs, float(tau), *(t.data_ptr() for t in out))
     return tuple(out)
 
 
@@ -882,11 +784,9 @@ def gumbel_reinmax_columns(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, l
     stride = int(load().vq_gumbel_row_stride(a.K))
     col = torch.empty((a.H, stride), dtype=torch.float32, device=x.device)
     e = torch.empty((a.H, stride), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(load().vq_gumbel_reinmax_columns_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), lse2_tau.data_ptr(),
-                                                    ind.data_ptr(), i_rs, i_hs, col.data_ptr(), e.data_ptr(),
-                                                    workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                                                    _stream_ptr(x.device)), "vq_gumbel_reinmax_columns_f32")
+    _call("vq_gumbel_reinmax_columns_f32", x.device, a, g.data_ptr(), g_rs, g_hs, float(tau), lse2_tau.data_ptr(),
+          ind.data_ptr(), i_rs, i_hs, col.data_ptr(), e.data_ptr(), workspace.data_ptr(),
+          workspace.numel() * workspace.element_size())
     return col, e, workspace
 
 
@@ -895,16 +795,14 @@ def gumbel_reinmax_backward_x(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor
                               out: torch.Tensor | None = None) -> torch.Tensor:
     """d/dx of the reinmax Gumbel softmax through the similarities, one fused sweep -> gx [H, M, D] (``out``: a destination
     with strided rows).  ``stats``: the triple of gumbel_reinmax_stats; col / e: of gumbel_reinmax_columns."""
-    a, packed, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
+    a, g_rs, g_hs = _gumbel_args(x, cb, g, metric, packed)
     _check_stat_arrays(x, a.M, *stats)
     _check_stat_arrays(x, a.K, col, e)
     i_rs, i_hs = _check_ind(x, ind)
     out, o_rs, o_hs = _grad_x_out(x, out)
-    with torch.cuda.device(x.device):
-        _check(load().vq_gumbel_reinmax_backward_x_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau), stats[0].data_ptr(),
-                                                       stats[1].data_ptr(), stats[2].data_ptr(), ind.data_ptr(), i_rs, i_hs,
-                                                       col.data_ptr(), e.data_ptr(), out.data_ptr(), o_rs, o_hs,
-                                                       _stream_ptr(x.device)), "vq_gumbel_reinmax_backward_x_f32")
+    _call("vq_gumbel_reinmax_backward_x_f32", x.device, a, g.data_ptr(), g_rs, g_hs, float(tau), stats[0].data_ptr(),
+          stats[1].data_ptr(), stats[2].data_ptr(), ind.data_ptr(), i_rs, i_hs, col.data_ptr(), e.data_ptr(), out.data_ptr(),
+          o_rs, o_hs)
     return out
 
 
@@ -918,12 +816,9 @@ def gumbel_reinmax_backward_codes(x: torch.Tensor, cb: torch.Tensor, g: torch.Te
     _check_stat_arrays(x, a.K, col, e)
     _require_gpu(workspace)
     gc = torch.empty((a.H, a.K, a.D), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(load().vq_gumbel_reinmax_backward_codes_f32(ctypes.byref(a), g.data_ptr(), g_rs, g_hs, float(tau),
-                                                           stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(),
-                                                           col.data_ptr(), e.data_ptr(), gc.data_ptr(), workspace.data_ptr(),
-                                                           workspace.numel() * workspace.element_size(), _stream_ptr(x.device)),
-               "vq_gumbel_reinmax_backward_codes_f32")
+    _call("vq_gumbel_reinmax_backward_codes_f32", x.device, a, g.data_ptr(), g_rs, g_hs, float(tau), stats[0].data_ptr(),
+          stats[1].data_ptr(), stats[2].data_ptr(), col.data_ptr(), e.data_ptr(), gc.data_ptr(), workspace.data_ptr(),
+          workspace.numel() * workspace.element_size())
     return gc
 
 
@@ -943,17 +838,12 @@ def sample_codes(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, tau
     1 / temperature, seed = two int64 words on the device -> idx [H, M] int64 = first argmax_k of sim * tau + noise, the noise
     a function of (seed, head, row, code) only (gumbel_noise returns it).  Nothing of [M, K] is written.  None where the
     library answers VQ_E_UNSUPPORTED (D > 512)."""
-    a, packed = _aux_args(x, cb, metric, packed, 0)
-    _check_seed(seed, x.device)
-    H, M = a.H, a.M
+    H, M = x.shape[:2]
     out = torch.empty((H, M), dtype=torch.int64, device=x.device)
-    a.idx, a.idx_rs, a.idx_hs, a.idx_qs = out.data_ptr(), 1, M, 0
-    with torch.cuda.device(x.device):
-        rc = load().vq_gumbel_sample_f32(ctypes.byref(a), float(tau), seed.data_ptr(), _stream_ptr(x.device))
-    if rc == E_UNSUPPORTED:
-        return None
-    _check(rc, "vq_gumbel_sample_f32")
-    return out
+    a = _aux_args(x, cb, metric, packed, 0, idx=out, idx_strides=(1, M, 0))  # out is a dense [H, M]: no stage axis
+    _check_seed(seed, x.device)
+    rc = _call("vq_gumbel_sample_f32", x.device, a, float(tau), seed.data_ptr(), accept=(0, E_UNSUPPORTED))
+    return out if rc == 0 else None
 
 
 def gumbel_noise(seed: torch.Tensor, H: int, M: int, K: int, want_bits: bool = False):
@@ -962,9 +852,7 @@ def gumbel_noise(seed: torch.Tensor, H: int, M: int, K: int, want_bits: bool = F
     _check_seed(seed, seed.device)
     noise = torch.empty((H, M, K), dtype=torch.float32, device=seed.device)
     bits = torch.empty((H, M, K), dtype=torch.int32, device=seed.device) if want_bits else None
-    with torch.cuda.device(seed.device):
-        _check(load().vq_gumbel_noise_f32(seed.data_ptr(), H, M, K, noise.data_ptr(), bits.data_ptr() if want_bits else None,
-                                          _stream_ptr(seed.device)), "vq_gumbel_noise_f32")
+    _call("vq_gumbel_noise_f32", seed.device, seed.data_ptr(), H, M, K, noise.data_ptr(), _ptr(bits))
     return (noise, bits) if want_bits else noise
 
 
@@ -980,28 +868,18 @@ def quantize_backward(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor, grad
     Q = idx.shape[-1]
     assert Hc == H and Dc == D and tuple(idx.shape[:2]) == (H, M) and (Qc == Q or (stages_share_codebook and Qc == 1))
     gx = torch.empty((H, M, D), dtype=torch.float32, device=x.device)
-    x_rs, x_hs = _row_strides(x)
-    a = VqArgs()
-    a.H, a.Q, a.M, a.K, a.D, a.metric = H, Q, M, K, D, EUCLID
-    a.flags = (F_STE if ste else 0) | (F_SQERR_PER_HEAD if sq_err_per_head else 0)
-    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
-    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), Qc * K * D, (0 if stages_share_codebook else K * D)
-    a.idx, a.idx_hs, a.idx_rs, a.idx_qs = idx.data_ptr(), int(idx.stride(0)), int(idx.stride(1)), int(idx.stride(2))
-    go_ptr, go_rs, go_hs = None, 0, 0
+    a = _vq_args(x, cb, Q=Q, shared=stages_share_codebook, idx=idx,
+                 flags=(F_STE if ste else 0) | (F_SQERR_PER_HEAD if sq_err_per_head else 0))
+    go_rs, go_hs = 0, 0
     if grad_out is not None:
         assert grad_out.dtype == torch.float32 and tuple(grad_out.shape) == (H, M, D)
         if grad_out.stride(-1) != 1:
             grad_out = grad_out.contiguous()
-        go_ptr = grad_out.data_ptr()
         go_rs, go_hs = _row_strides(grad_out)
-    ge_ptr = None
     if grad_sq_err is not None:
         grad_sq_err = grad_sq_err.to(torch.float64).contiguous()
         assert grad_sq_err.numel() == (H * Q if sq_err_per_head else Q)
-        ge_ptr = grad_sq_err.data_ptr()
-    with torch.cuda.device(x.device):
-        _check(load().vq_quantize_backward_f32(ctypes.byref(a), go_ptr, go_rs, go_hs, ge_ptr, gx.data_ptr(), D, M * D,
-                                               _stream_ptr(x.device)), "vq_quantize_backward_f32")
+    _call("vq_quantize_backward_f32", x.device, a, _ptr(grad_out), go_rs, go_hs, _ptr(grad_sq_err), gx.data_ptr(), D, M * D)
     return gx
 
 
@@ -1032,16 +910,8 @@ def ema_accumulate_residual(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor
         return torch.stack(counts, 1), torch.stack(sums, 1)
     counts = torch.zeros((H, Q, K), dtype=torch.float32, device=x.device)
     sums = torch.zeros((H, Q, K, D), dtype=torch.float32, device=x.device)
-    x_rs, x_hs = _row_strides(x)
-    a = VqArgs()
-    a.H, a.Q, a.M, a.K, a.D, a.metric = H, Q, M, K, D, EUCLID
-    a.flags = F_STE if ste else 0
-    a.x, a.x_rs, a.x_hs = x.data_ptr(), x_rs, x_hs
-    a.cb, a.cb_hs, a.cb_qs = cb.data_ptr(), Qc * K * D, (0 if stages_share_codebook else K * D)
-    a.idx, a.idx_hs, a.idx_rs, a.idx_qs = idx.data_ptr(), int(idx.stride(0)), int(idx.stride(1)), int(idx.stride(2))
-    with torch.cuda.device(x.device):
-        _check(load().vq_ema_accumulate_residual_f32(ctypes.byref(a), counts.data_ptr(), sums.data_ptr(),
-                                                     _stream_ptr(x.device)), "vq_ema_accumulate_residual_f32")
+    a = _vq_args(x, cb, Q=Q, shared=stages_share_codebook, flags=F_STE if ste else 0, idx=idx)
+    _call("vq_ema_accumulate_residual_f32", x.device, a, counts.data_ptr(), sums.data_ptr())
     return counts, sums
 
 
@@ -1059,11 +929,9 @@ def _lfq_rows(v: torch.Tensor):
     return int(v.stride(0)) if N > 1 else C * d
 
 
-def _lfq_workspace(N: int, R: int, C: int, d: int, device) -> torch.Tensor:
-    nbytes = int(load().vq_lfq_workspace_bytes(N, R, C, d))
-    if nbytes <= 0:
-        raise RuntimeError(f"vq_lfq_workspace_bytes({N}, {R}, {C}, {d}) failed: {load().vq_last_error().decode()}")
-    return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=device)
+def _row_mask(mask, N: int):
+    """An optional [N] bool mask as the kernels read it: contiguous uint8, or None."""
+    return None if mask is None else mask.reshape(N).to(torch.uint8).contiguous()
 
 
 def lfq_quantize(v: torch.Tensor, qmag: float, *, xa: torch.Tensor | None = None, mask: torch.Tensor | None = None,
@@ -1072,7 +940,6 @@ def lfq_quantize(v: torch.Tensor, qmag: float, *, xa: torch.Tensor | None = None
     commit_sum float64 scalar or None).
     mask: [N] bool (rows counted in the squared-error sum)."""
     _require_gpu(v, xa, mask)
-    lib = load()
     N, C, d = v.shape
     v_rs = _lfq_rows(v)
     dev = v.device
@@ -1083,20 +950,13 @@ def lfq_quantize(v: torch.Tensor, qmag: float, *, xa: torch.Tensor | None = None
         assert xa.shape == v.shape
         xa_rs = _lfq_rows(xa)
         out = torch.empty_like(q)
-    m8 = None
-    if mask is not None:
-        m8 = mask.reshape(N).to(torch.uint8).contiguous()
-    commit = ws = None
+    m8 = _row_mask(mask, N)
+    commit, ws, ws_bytes = None, None, 0
     if want_commit:
         commit = torch.empty((), dtype=torch.float64, device=dev)
-        ws = _lfq_workspace(N, 0, C, d, dev)
-    with torch.cuda.device(dev):
-        _check(lib.vq_lfq_quantize_f32(v.data_ptr(), v_rs, xa.data_ptr() if xa is not None else None, xa_rs or 0, N, C, d,
-                                       float(qmag), m8.data_ptr() if m8 is not None else None, q.data_ptr(),
-                                       out.data_ptr() if out is not None else None, idx.data_ptr(),
-                                       commit.data_ptr() if commit is not None else None,
-                                       ws.data_ptr() if ws is not None else None, ws.numel() * 8 if ws is not None else 0,
-                                       _stream_ptr(dev)), "vq_lfq_quantize_f32")
+        ws, ws_bytes = _sized_workspace("vq_lfq_workspace_bytes", dev, N, 0, C, d)
+    _call("vq_lfq_quantize_f32", dev, v.data_ptr(), v_rs, _ptr(xa), xa_rs or 0, N, C, d, float(qmag), _ptr(m8), q.data_ptr(),
+          _ptr(out), idx.data_ptr(), _ptr(commit), _ptr(ws), ws_bytes)
     return q, (out if out is not None else q), idx, commit
 
 
@@ -1104,7 +964,6 @@ def lfq_entropy_forward(v: torch.Tensor, rows: torch.Tensor | None, code_scale: 
     """Entropy statistics of the selected rows of v [N, C, d] (rows: int64 row numbers on v's device, None = all rows)
     -> (per_sample_sum float64 scalar = sum over (row, c) of the clamped entropy, avg_prob [C, 2^d] fp32)."""
     _require_gpu(v, rows)
-    lib = load()
     N, C, d = v.shape
     R = N if rows is None else int(rows.numel())
     dev = v.device
@@ -1112,11 +971,9 @@ def lfq_entropy_forward(v: torch.Tensor, rows: torch.Tensor | None, code_scale: 
         rows = rows.to(torch.int64).contiguous()
     avg = torch.empty((C, 1 << d), dtype=torch.float32, device=dev)
     ps = torch.empty((), dtype=torch.float64, device=dev)
-    ws = _lfq_workspace(R, R, C, d, dev)
-    with torch.cuda.device(dev):
-        _check(lib.vq_lfq_entropy_fwd_f32(v.data_ptr(), _lfq_rows(v), rows.data_ptr() if rows is not None else None, R, C, d,
-                                          float(code_scale), float(inv_temperature), avg.data_ptr(), ps.data_ptr(),
-                                          ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)), "vq_lfq_entropy_fwd_f32")
+    ws, ws_bytes = _sized_workspace("vq_lfq_workspace_bytes", dev, R, R, C, d)
+    _call("vq_lfq_entropy_fwd_f32", dev, v.data_ptr(), _lfq_rows(v), _ptr(rows), R, C, d, float(code_scale),
+          float(inv_temperature), avg.data_ptr(), ps.data_ptr(), ws.data_ptr(), ws_bytes)
     return ps, avg
 
 
@@ -1124,7 +981,6 @@ def lfq_entropy_backward(v: torch.Tensor, rows: torch.Tensor | None, code_scale:
                          w_ps: torch.Tensor, w_cb: torch.Tensor) -> torch.Tensor:
     """dL/dv [N, C, d] (zero on rows not selected) for L = w_ps * sum of per-sample entropies + sum w_cb * p (see the header)."""
     _require_gpu(v, rows, w_ps, w_cb)
-    lib = load()
     N, C, d = v.shape
     R = N if rows is None else int(rows.numel())
     dev = v.device
@@ -1134,10 +990,8 @@ def lfq_entropy_backward(v: torch.Tensor, rows: torch.Tensor | None, code_scale:
     w_cb = w_cb.to(torch.float32).contiguous()
     assert w_cb.numel() == C << d
     gv = torch.zeros((N, C, d), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.vq_lfq_entropy_bwd_f32(v.data_ptr(), _lfq_rows(v), rows.data_ptr() if rows is not None else None, R, C, d,
-                                          float(code_scale), float(inv_temperature), w_ps.data_ptr(), w_cb.data_ptr(),
-                                          gv.data_ptr(), C * d, _stream_ptr(dev)), "vq_lfq_entropy_bwd_f32")
+    _call("vq_lfq_entropy_bwd_f32", dev, v.data_ptr(), _lfq_rows(v), _ptr(rows), R, C, d, float(code_scale),
+          float(inv_temperature), w_ps.data_ptr(), w_cb.data_ptr(), gv.data_ptr(), C * d)
     return gv
 
 
@@ -1155,7 +1009,7 @@ def rlfq_stages(qmag, clamp, scale, device) -> torch.Tensor:
     return torch.tensor(rows, dtype=torch.float32).to(device, non_blocking=False)
 
 
-def _rlfq_rows(x: torch.Tensor):
+def _group_rows(x: torch.Tensor):
     """x [G, N, d] fp32 whose rows are contiguous -> (group stride, row stride) in elements."""
     assert x.dim() == 3 and x.dtype == torch.float32, "x must be [G, N, d] fp32"
     assert x.shape[2] <= 1 or x.stride(2) == 1, "each row's d values must be contiguous"
@@ -1169,32 +1023,23 @@ def rlfq_quantize(x: torch.Tensor, qmag, clamp, scale, *, spherical: bool = Fals
     -> (out [G, N, d] (the caller's view when given), idx [G, N, S] int64, v_all [G, S, N, d] or None,
     commit_sum [G, S] float64 or None).  mask: [N] bool (rows counted in the commitment sums)."""
     _require_gpu(x, mask)
-    lib = load()
     G, N, d = x.shape
     dev = x.device
     st = rlfq_stages(qmag, clamp, scale, dev)
     S = st.shape[1]
-    x_gs, x_rs = _rlfq_rows(x)
+    x_gs, x_rs = _group_rows(x)
     if out is None:
         out = torch.empty((G, N, d), dtype=torch.float32, device=dev)
-    o_gs, o_rs = _rlfq_rows(out)
+    o_gs, o_rs = _group_rows(out)
     idx = torch.empty((G, N, S), dtype=torch.int64, device=dev)
     v_all = torch.empty((G, S, N, d), dtype=torch.float32, device=dev) if want_v else None
-    m8 = mask.reshape(N).to(torch.uint8).contiguous() if mask is not None else None
-    commit = ws = None
+    m8 = _row_mask(mask, N)
+    commit, ws, ws_bytes = None, None, 0
     if want_commit:
         commit = torch.empty((G, S), dtype=torch.float64, device=dev)
-        nbytes = int(lib.vq_rlfq_workspace_bytes(G, N, S))
-        if nbytes <= 0:
-            raise RuntimeError(f"vq_rlfq_workspace_bytes({G}, {N}, {S}) failed: {lib.vq_last_error().decode()}")
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.vq_rlfq_quantize_f32(x.data_ptr(), x_gs, x_rs, G, N, d, S, st.data_ptr(), int(spherical), int(ste),
-                                        m8.data_ptr() if m8 is not None else None, out.data_ptr(), o_gs, o_rs, idx.data_ptr(),
-                                        v_all.data_ptr() if v_all is not None else None,
-                                        commit.data_ptr() if commit is not None else None,
-                                        ws.data_ptr() if ws is not None else None, ws.numel() * 8 if ws is not None else 0,
-                                        _stream_ptr(dev)), "vq_rlfq_quantize_f32")
+        ws, ws_bytes = _sized_workspace("vq_rlfq_workspace_bytes", dev, G, N, S)
+    _call("vq_rlfq_quantize_f32", dev, x.data_ptr(), x_gs, x_rs, G, N, d, S, st.data_ptr(), int(spherical), int(ste),
+          _ptr(m8), out.data_ptr(), o_gs, o_rs, idx.data_ptr(), _ptr(v_all), _ptr(commit), _ptr(ws), ws_bytes)
     return out, idx, v_all, commit
 
 
@@ -1204,16 +1049,15 @@ def rlfq_backward(x: torch.Tensor, qmag, clamp, scale, *, spherical: bool = Fals
     """dL/dx [G, N, d] of the training chain of rlfq_quantize (see the header): g_out [G, N, d] upstream gradient of out,
     w_commit [G, S] = 2 * upstream gradient of the commitment sums, g_ent [G, S, N, d] gradient at the stage inputs."""
     _require_gpu(x, mask, g_out, w_commit, g_ent)
-    lib = load()
     G, N, d = x.shape
     dev = x.device
     st = rlfq_stages(qmag, clamp, scale, dev)
     S = st.shape[1]
-    x_gs, x_rs = _rlfq_rows(x)
+    x_gs, x_rs = _group_rows(x)
     if g_out is not None:
         if g_out.shape[2] > 1 and g_out.stride(2) != 1:
             g_out = g_out.contiguous()
-        g_gs, g_rs = _rlfq_rows(g_out)
+        g_gs, g_rs = _group_rows(g_out)
     else:
         g_gs = g_rs = 0
     if w_commit is not None:
@@ -1223,15 +1067,10 @@ def rlfq_backward(x: torch.Tensor, qmag, clamp, scale, *, spherical: bool = Fals
         g_ent = g_ent.contiguous()
     if grad_x is None:
         grad_x = torch.empty((G, N, d), dtype=torch.float32, device=dev)
-    gx_gs, gx_rs = _rlfq_rows(grad_x)
-    m8 = mask.reshape(N).to(torch.uint8).contiguous() if mask is not None else None
-    with torch.cuda.device(dev):
-        _check(lib.vq_rlfq_backward_f32(x.data_ptr(), x_gs, x_rs, G, N, d, S, st.data_ptr(), int(spherical),
-                                        m8.data_ptr() if m8 is not None else None,
-                                        g_out.data_ptr() if g_out is not None else None, g_gs, g_rs,
-                                        w_commit.data_ptr() if w_commit is not None else None,
-                                        g_ent.data_ptr() if g_ent is not None else None, grad_x.data_ptr(), gx_gs, gx_rs,
-                                        _stream_ptr(dev)), "vq_rlfq_backward_f32")
+    gx_gs, gx_rs = _group_rows(grad_x)
+    m8 = _row_mask(mask, N)
+    _call("vq_rlfq_backward_f32", dev, x.data_ptr(), x_gs, x_rs, G, N, d, S, st.data_ptr(), int(spherical), _ptr(m8),
+          _ptr(g_out), g_gs, g_rs, _ptr(w_commit), _ptr(g_ent), grad_x.data_ptr(), gx_gs, gx_rs)
     return grad_x
 
 
@@ -1256,20 +1095,13 @@ def lfq_entropy_staged_forward(v: torch.Tensor, rows: torch.Tensor | None, code_
     """lfq_entropy_forward of T stages at once: v [T, N, d], rows None / [R] / [T, R], code_scale a list whose entry
     t % len applies to stage t -> (per_sample_sum float64 [T], avg_prob [T, 2^d])."""
     _require_gpu(v, rows)
-    lib = load()
     T, N, d, R, v_ss, v_rs, rows, rows_ss, scales = _staged_args(v, rows, code_scale)
     dev = v.device
     avg = torch.empty((T, 1 << d), dtype=torch.float32, device=dev)
     ps = torch.empty((T,), dtype=torch.float64, device=dev)
-    nbytes = int(lib.vq_lfq_staged_workspace_bytes(R, T, d))
-    if nbytes <= 0:
-        raise RuntimeError(f"vq_lfq_staged_workspace_bytes({R}, {T}, {d}) failed: {lib.vq_last_error().decode()}")
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.vq_lfq_entropy_staged_fwd_f32(v.data_ptr(), v_rs, v_ss, rows.data_ptr() if rows is not None else None,
-                                                 rows_ss, R, T, d, scales.data_ptr(), scales.numel(), float(inv_temperature), avg.data_ptr(),
-                                                 ps.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream_ptr(dev)),
-               "vq_lfq_entropy_staged_fwd_f32")
+    ws, ws_bytes = _sized_workspace("vq_lfq_staged_workspace_bytes", dev, R, T, d)
+    _call("vq_lfq_entropy_staged_fwd_f32", dev, v.data_ptr(), v_rs, v_ss, _ptr(rows), rows_ss, R, T, d, scales.data_ptr(),
+          scales.numel(), float(inv_temperature), avg.data_ptr(), ps.data_ptr(), ws.data_ptr(), ws_bytes)
     return ps, avg
 
 
@@ -1277,18 +1109,14 @@ def lfq_entropy_staged_backward(v: torch.Tensor, rows: torch.Tensor | None, code
                                 w_ps: torch.Tensor, w_cb: torch.Tensor) -> torch.Tensor:
     """lfq_entropy_backward of T stages at once: w_ps [T], w_cb [T, 2^d] -> dL/dv [T, N, d] (zero on rows not selected)."""
     _require_gpu(v, rows, w_ps, w_cb)
-    lib = load()
     T, N, d, R, v_ss, v_rs, rows, rows_ss, scales = _staged_args(v, rows, code_scale)
     dev = v.device
     w_ps = w_ps.to(torch.float32).reshape(T).contiguous()
     w_cb = w_cb.to(torch.float32).contiguous()
     assert w_cb.numel() == T << d
     gv = torch.zeros((T, N, d), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.vq_lfq_entropy_staged_bwd_f32(v.data_ptr(), v_rs, v_ss, rows.data_ptr() if rows is not None else None,
-                                                 rows_ss, R, T, d, scales.data_ptr(), scales.numel(), float(inv_temperature),
-                                                 w_ps.data_ptr(), w_cb.data_ptr(), gv.data_ptr(), d, N * d, _stream_ptr(dev)),
-               "vq_lfq_entropy_staged_bwd_f32")
+    _call("vq_lfq_entropy_staged_bwd_f32", dev, v.data_ptr(), v_rs, v_ss, _ptr(rows), rows_ss, R, T, d, scales.data_ptr(),
+          scales.numel(), float(inv_temperature), w_ps.data_ptr(), w_cb.data_ptr(), gv.data_ptr(), d, N * d)
     return gv
 
 
@@ -1304,34 +1132,24 @@ def _levels_arg(levels):
     return arr
 
 
-def _fsq_rows(x: torch.Tensor):
-    """x [G, N, d] fp32 whose rows are contiguous -> (group stride, row stride) in elements."""
-    assert x.dim() == 3 and x.dtype == torch.float32, "x must be [G, N, d] fp32"
-    assert x.shape[2] <= 1 or x.stride(2) == 1, "each row's d values must be contiguous"
-    return int(x.stride(0)), int(x.stride(1))
-
-
 def fsq_quantize(x: torch.Tensor, levels, consts: torch.Tensor, *, prebound: bool = False, want_idx: bool = True,
                  out: torch.Tensor | None = None):
     """Every stage of an FSQ stack over x [G, N, d] -> (out [G, N, d] (the caller's view when given), idx [G, N, S] int32
     or None).  consts: device fp32 [3 + S, d] (half_l, offset, shift, then the stage scales; see the header)."""
     _require_gpu(x, consts)
-    lib = load()
     G, N, d = x.shape
     dev = x.device
     S = consts.shape[0] - 3
     assert consts.dtype == torch.float32 and consts.shape == (3 + S, d) and consts.is_contiguous()
-    x_gs, x_rs = _fsq_rows(x)
+    x_gs, x_rs = _group_rows(x)
     if out is None:
         out = torch.empty((G, N, d), dtype=torch.float32, device=dev)
-    o_gs, o_rs = _fsq_rows(out)
+    o_gs, o_rs = _group_rows(out)
     idx = torch.empty((G, N, S), dtype=torch.int32, device=dev) if want_idx else None
     if N == 0:
         return out, idx
-    with torch.cuda.device(dev):
-        _check(lib.vq_fsq_quantize_f32(x.data_ptr(), x_gs, x_rs, G, N, d, _levels_arg(levels), S, consts.data_ptr(),
-                                       int(prebound), out.data_ptr(), o_gs, o_rs, idx.data_ptr() if idx is not None else None,
-                                       _stream_ptr(dev)), "vq_fsq_quantize_f32")
+    _call("vq_fsq_quantize_f32", dev, x.data_ptr(), x_gs, x_rs, G, N, d, _levels_arg(levels), S, consts.data_ptr(),
+          int(prebound), out.data_ptr(), o_gs, o_rs, _ptr(idx))
     return out, idx
 
 
@@ -1339,25 +1157,22 @@ def fsq_backward(x: torch.Tensor, levels, consts: torch.Tensor, g_out: torch.Ten
                  grad_x: torch.Tensor | None = None) -> torch.Tensor:
     """dL/dx [G, N, d] of fsq_quantize's out for the upstream gradient g_out [G, N, d] (straight-through rounding)."""
     _require_gpu(x, consts, g_out)
-    lib = load()
     G, N, d = x.shape
     dev = x.device
     S = consts.shape[0] - 3
     assert consts.dtype == torch.float32 and consts.shape == (3 + S, d) and consts.is_contiguous()
-    x_gs, x_rs = _fsq_rows(x)
+    x_gs, x_rs = _group_rows(x)
     g_out = g_out.to(torch.float32)
     if g_out.shape[2] > 1 and g_out.stride(2) != 1:
         g_out = g_out.contiguous()
-    g_gs, g_rs = _fsq_rows(g_out)
+    g_gs, g_rs = _group_rows(g_out)
     if grad_x is None:
         grad_x = torch.empty((G, N, d), dtype=torch.float32, device=dev)
-    gx_gs, gx_rs = _fsq_rows(grad_x)
+    gx_gs, gx_rs = _group_rows(grad_x)
     if N == 0:
         return grad_x
-    with torch.cuda.device(dev):
-        _check(lib.vq_fsq_backward_f32(x.data_ptr(), x_gs, x_rs, G, N, d, _levels_arg(levels), S, consts.data_ptr(),
-                                       int(prebound), g_out.data_ptr(), g_gs, g_rs, grad_x.data_ptr(), gx_gs, gx_rs,
-                                       _stream_ptr(dev)), "vq_fsq_backward_f32")
+    _call("vq_fsq_backward_f32", dev, x.data_ptr(), x_gs, x_rs, G, N, d, _levels_arg(levels), S, consts.data_ptr(),
+          int(prebound), g_out.data_ptr(), g_gs, g_rs, grad_x.data_ptr(), gx_gs, gx_rs)
     return grad_x
 
 
@@ -1367,7 +1182,6 @@ def fsq_decode(indices: torch.Tensor, levels, scales: torch.Tensor, *, drop_null
     index i at stage q being ((i // basis) % L - hw) / hw * scales[q] (scales: device fp32 [Q, d]); -1 gives a zero code
     when drop_null."""
     _require_gpu(indices, scales)
-    lib = load()
     N, Q = indices.shape
     d = len(levels)
     dev = indices.device
@@ -1378,12 +1192,8 @@ def fsq_decode(indices: torch.Tensor, levels, scales: torch.Tensor, *, drop_null
     all_codes = torch.empty((Q, N, d), dtype=torch.float32, device=dev) if want_all else None
     if N == 0:
         return codes_sum, all_codes
-    with torch.cuda.device(dev):
-        _check(lib.vq_fsq_decode_f32(indices.data_ptr(), int(indices.dtype == torch.int64), N, Q, d, _levels_arg(levels),
-                                     scales.data_ptr(), int(drop_null),
-                                     codes_sum.data_ptr() if codes_sum is not None else None,
-                                     all_codes.data_ptr() if all_codes is not None else None, _stream_ptr(dev)),
-               "vq_fsq_decode_f32")
+    _call("vq_fsq_decode_f32", dev, indices.data_ptr(), int(indices.dtype == torch.int64), N, Q, d, _levels_arg(levels),
+          scales.data_ptr(), int(drop_null), _ptr(codes_sum), _ptr(all_codes))
     return codes_sum, all_codes
 
 
@@ -1402,7 +1212,6 @@ def decode_codes(cb: torch.Tensor, indices: torch.Tensor, *, num_stages: int | N
     ``sum_out`` ([G, N, D] view, ANY strides: a channel-first or head-concatenated destination) and ``all_out``
     ([Q, G, N, D] view, last dim contiguous) are written in place when given."""
     _require_gpu(cb, indices, sum_out, all_out)
-    lib = load()
     assert cb.dim() == 4 and cb.dtype == torch.float32, "cb must be [G, Q, K, D] fp32"
     assert indices.dim() == 3 and indices.dtype in (torch.int32, torch.int64), "indices must be [G, N, Qg] int32 / int64"
     G, N, Qg = indices.shape
@@ -1427,12 +1236,9 @@ def decode_codes(cb: torch.Tensor, indices: torch.Tensor, *, num_stages: int | N
         return codes_sum, all_codes
     s = (0, 0, 1) if codes_sum is None else tuple(int(v) for v in codes_sum.stride())
     a = (0, 0, 0) if all_codes is None else tuple(int(v) for v in all_codes.stride()[:3])
-    with torch.cuda.device(dev):
-        _check(lib.vq_decode_f32(cb.data_ptr(), cb_gs, cb_qs, G, Q, K, D, indices.data_ptr(), int(indices.dtype == torch.int64),
-                                 int(indices.stride(0)), int(indices.stride(1)), int(indices.stride(2)), N, Qg, int(drop_null),
-                                 codes_sum.data_ptr() if codes_sum is not None else None, *s,
-                                 all_codes.data_ptr() if all_codes is not None else None, *a, _stream_ptr(dev)),
-               "vq_decode_f32")
+    _call("vq_decode_f32", dev, cb.data_ptr(), cb_gs, cb_qs, G, Q, K, D, indices.data_ptr(), int(indices.dtype == torch.int64),
+          int(indices.stride(0)), int(indices.stride(1)), int(indices.stride(2)), N, Qg, int(drop_null), _ptr(codes_sum), *s,
+          _ptr(all_codes), *a)
     return codes_sum, all_codes
 
 
@@ -1456,7 +1262,6 @@ def lfq_decode(indices: torch.Tensor, mag, d: int, *, drop_null: bool = True, wa
     dim contiguous) are written in place when given."""
     if not indices.is_cuda:
         _require_gpu(indices)
-    lib = load()
     G, N, Qg = indices.shape
     Q = len(mag)
     dev = indices.device
@@ -1480,11 +1285,8 @@ def lfq_decode(indices: torch.Tensor, mag, d: int, *, drop_null: bool = True, wa
     if N == 0:
         return codes_sum, all_codes
     i0, i1, i2 = indices.stride()
-    with torch.cuda.device(dev):
-        rc = lib.vq_lfq_decode_f32(indices.data_ptr(), indices.dtype == torch.int64, i0, i1, i2, G, N, Qg, Q, d,
-                                   _lfq_mag_arg(tuple(mag)), drop_null, sp, s0, s1, s2, ap, a0, a1, a2, _stream_ptr(dev))
-    if rc:
-        _check(rc, "vq_lfq_decode_f32")
+    _call("vq_lfq_decode_f32", dev, indices.data_ptr(), indices.dtype == torch.int64, i0, i1, i2, G, N, Qg, Q, d,
+          _lfq_mag_arg(tuple(mag)), drop_null, sp, s0, s1, s2, ap, a0, a1, a2)
     return codes_sum, all_codes
 
 
@@ -1508,7 +1310,6 @@ def lq_quantize(z: torch.Tensor, levels, tables: torch.Tensor, num_codebooks: in
     tables: device fp32 [sum(levels)], the d value tables back to back.  loss_weights (w_c, w_q): also the fused
     squared-error loss, a device fp32 [2] = (w_c * m + w_q * m, m) with m the mean of (codes - z)^2."""
     _require_gpu(z, tables)
-    lib = load()
     B, P, W = z.shape
     C = int(num_codebooks)
     d = len(levels)
@@ -1522,7 +1323,7 @@ def lq_quantize(z: torch.Tensor, levels, tables: torch.Tensor, num_codebooks: in
     assert out.shape == z.shape
     os_ = _lq_strides(out)
     idx = torch.empty((B, P, C), dtype=torch.int32, device=dev) if want_idx else None
-    loss = ws = None
+    loss, ws, ws_bytes = None, None, 0
     w_c = w_q = 0.0
     if loss_weights is not None:
         w_c, w_q = float(loss_weights[0]), float(loss_weights[1])
@@ -1532,13 +1333,9 @@ def lq_quantize(z: torch.Tensor, levels, tables: torch.Tensor, num_codebooks: in
             loss.fill_(float("nan"))  # the mean over no element
         return out, idx, loss
     if loss is not None:
-        ws = torch.empty((int(lib.vq_lq_workspace_bytes(B, P, C)),), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib.vq_lq_quantize_f32(z.data_ptr(), *zs, B, P, C, d, _levels_arg(levels), tables.data_ptr(), out.data_ptr(),
-                                      *os_, idx.data_ptr() if idx is not None else None,
-                                      loss.data_ptr() if loss is not None else None, w_c, w_q,
-                                      ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
-                                      _stream_ptr(dev)), "vq_lq_quantize_f32")
+        ws, ws_bytes = _alloc_workspace(int(load().vq_lq_workspace_bytes(B, P, C)), dev)
+    _call("vq_lq_quantize_f32", dev, z.data_ptr(), *zs, B, P, C, d, _levels_arg(levels), tables.data_ptr(), out.data_ptr(),
+          *os_, _ptr(idx), _ptr(loss), w_c, w_q, _ptr(ws), ws_bytes)
     return out, idx, loss
 
 
@@ -1547,7 +1344,6 @@ def lq_backward(x: torch.Tensor, out: torch.Tensor, g_out: torch.Tensor, g_loss:
     """grad_x = g_out + (g_loss * coef) * (out - x) over [B, P, W] fp32 tensors of any strides (g_loss a device scalar);
     grad_x is laid out as x unless given."""
     _require_gpu(x, out, g_out, g_loss)
-    lib = load()
     B, P, W = x.shape
     dev = x.device
     assert out.shape == x.shape and g_out.shape == x.shape
@@ -1557,9 +1353,7 @@ def lq_backward(x: torch.Tensor, out: torch.Tensor, g_out: torch.Tensor, g_loss:
         grad_x = torch.empty_like(x)  # x's strides when they are dense, else contiguous
     if x.numel() == 0:
         return grad_x
-    with torch.cuda.device(dev):
-        _check(lib.vq_lq_backward_f32(x.data_ptr(), *_lq_strides(x), out.data_ptr(), *_lq_strides(out), g_out.data_ptr(),
-                                      *_lq_strides(g_out), g_loss.data_ptr(), float(coef), B, P, W, grad_x.data_ptr(),
-                                      *_lq_strides(grad_x), _stream_ptr(dev)), "vq_lq_backward_f32")
+    _call("vq_lq_backward_f32", dev, x.data_ptr(), *_lq_strides(x), out.data_ptr(), *_lq_strides(out), g_out.data_ptr(),
+          *_lq_strides(g_out), g_loss.data_ptr(), float(coef), B, P, W, grad_x.data_ptr(), *_lq_strides(grad_x))
     return grad_x
 
