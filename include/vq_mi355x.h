@@ -246,6 +246,9 @@ int vq_affine_apply_f32(const float *in, float *out, const float *hits /* mode 1
  *   of code target[h*tgt_hs + m*tgt_rs] (0 for a negative = ignored target; -inf for one >= K).  This is
  *   F.cross_entropy(distances, codes, ignore_index=-1) -- vector_quantize_pytorch.py:287-297 -- as an online-softmax
  *   epilogue of the sweep: [M, K] never exists.  target may be NULL (lse only).  Accuracy: native sqrt/exp/log (1e-6 rel).
+ *   A target is compared with 0 and K as the 64-bit value it is, before any narrowing (2^32 + 3 is out of range, not code 3);
+ *   vq_ce_backward_f32 and vq_ce_backward_live_f32 ignore a row whose target is negative OR >= K (its grad_x is exactly 0).
+ *   A row with a NaN or a +inf logit has lse = NaN (ATen's log_softmax), a NaN target logit stays NaN.
  */
 int vq_similarities_f32(const vq_args *a, float *sims, int64_t sims_rs, int64_t sims_hs, void *stream);
 int vq_softmax_stats_f32(const vq_args *a, float scale, const int64_t *target, int64_t tgt_rs, int64_t tgt_hs, float *lse,

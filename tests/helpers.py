@@ -180,3 +180,38 @@ def checksum_close(t: torch.Tensor, ref, rtol=1e-6):
     t64 = t.detach().double().flatten()
     got = [float(t64.sum()), float(t64.abs().sum()), float(t64[0]), float(t64[-1])]
     return np.allclose(got, ref, rtol=rtol, atol=1e-6, equal_nan=True), got
+
+
+NAN, INF = float("nan"), float("inf")
+
+
+def poison_rows(x: torch.Tensor, seed: int = 0):
+    """x [M, D] (in place): a NaN element, a +inf, a -inf, an all-inf row, +inf and -inf together, a NaN in the last dim, spread
+    over the row blocks (first / middle / last rows).  Returns the poisoned row numbers."""
+    M, D = x.shape
+    g = np.random.default_rng(seed)
+    rows = sorted(set([0, 1, 2, 3, 4, min(5, M - 1), M // 2, M - 1] + [int(v) for v in g.integers(0, M, 12)]))
+    kinds = ["nan", "inf", "-inf", "allinf", "mixed", "nanlast", "nan", "-inf"]
+    for i, r in enumerate(rows):
+        kind = kinds[i % len(kinds)]
+        d = int(g.integers(0, D))
+        if kind == "nan":
+            x[r, d] = NAN
+        elif kind == "inf":
+            x[r, d] = INF
+        elif kind == "-inf":
+            x[r, d] = -INF
+        elif kind == "allinf":
+            x[r, :] = INF
+        elif kind == "mixed":
+            x[r, 0] = INF
+            x[r, D - 1] = -INF if D > 1 else INF
+        else:
+            x[r, D - 1] = NAN
+    return rows
+
+
+def same_values(got: np.ndarray, want: np.ndarray) -> bool:
+    """bit-equal where finite / inf, NaN where NaN (the payload of a NaN is not part of the contract)"""
+    gn, wn = np.isnan(got), np.isnan(want)
+    return bool(np.array_equal(gn, wn) and np.array_equal(got[~gn].view(np.uint32), want[~wn].view(np.uint32)))

@@ -6,7 +6,10 @@ inf - inf, a code holding a NaN wins EVERY row, a code holding an inf the rows o
 rule and is pinned to the reference by the nf_* fixtures (tests/test_oracle_golden.py, the module tests); here every
 kernel / launch plan must reproduce the oracle bit for bit on poisoned inputs: the one-block kernel at every padded
 dim, the persistent kernel, the wave-pair kernel, K split into packed keys, the main + tail plan, rows wider than 512
-dims (keys and fused), 2-byte rows, residual stacks, shard keys, the log-sum-exp variant and the similarity emission.
+dims (keys and fused), 2-byte rows, residual stacks, shard keys, the log-sum-exp variant (NaN rows, Euclid, one shape) and
+the similarity emission.  The cross-entropy producers -- vq_softmax_stats_f32, the search's log-sum-exp under both metrics,
+with inf rows and poisoned codes, and both cross-entropy backward entries -- are pinned on poisoned inputs at every padded
+dim in tests/test_gpu_ce_value_edges.py; the host side of the loss in tests/test_ce_loss_nonfinite_host.py.
 """
 from __future__ import annotations
 
@@ -15,6 +18,8 @@ import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
+
+from helpers import poison_rows, same_values  # noqa: E402
 
 DEV = "cuda:0"
 NAN, INF = float("nan"), float("inf")
@@ -25,38 +30,6 @@ def _native():
 
     native.load()
     return native
-
-
-def poison_rows(x: torch.Tensor, seed: int = 0):
-    """x [M, D] (in place): a NaN element, a +inf, a -inf, an all-inf row, +inf and -inf together, a NaN in the last dim, spread
-    over the row blocks (first / middle / last rows).  Returns the poisoned row numbers."""
-    M, D = x.shape
-    g = np.random.default_rng(seed)
-    rows = sorted(set([0, 1, 2, 3, 4, min(5, M - 1), M // 2, M - 1] + [int(v) for v in g.integers(0, M, 12)]))
-    kinds = ["nan", "inf", "-inf", "allinf", "mixed", "nanlast", "nan", "-inf"]
-    for i, r in enumerate(rows):
-        kind = kinds[i % len(kinds)]
-        d = int(g.integers(0, D))
-        if kind == "nan":
-            x[r, d] = NAN
-        elif kind == "inf":
-            x[r, d] = INF
-        elif kind == "-inf":
-            x[r, d] = -INF
-        elif kind == "allinf":
-            x[r, :] = INF
-        elif kind == "mixed":
-            x[r, 0] = INF
-            x[r, D - 1] = -INF if D > 1 else INF
-        else:
-            x[r, D - 1] = NAN
-    return rows
-
-
-def same_values(got: np.ndarray, want: np.ndarray) -> bool:
-    """bit-equal where finite / inf, NaN where NaN (the payload of a NaN is not part of the contract)"""
-    gn, wn = np.isnan(got), np.isnan(want)
-    return bool(np.array_equal(gn, wn) and np.array_equal(got[~gn].view(np.uint32), want[~wn].view(np.uint32)))
 
 
 def check_rows(oracle, r, x, cb, metric, rows=None):

@@ -69,8 +69,12 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_sweep_aux(
     const float *pk = p.packed + (long long)head * p.pk_hs;
     const float b_aug = h ? 1.0f : xn0;
 
-    // kAuxStats state: running max / sum of exp over the codes this lane has seen, and the target's logit
+    // kAuxStats state: running max / sum of exp over the codes this lane has seen, and the target's logit.  A NaN logit makes
+    // the row's log-sum-exp NaN (ATen's logsumexp; the search's LSE variant does the same).  Once a lane has a running max, the
+    // accumulation carries a NaN logit into run_s by itself (exp(NaN) is NaN, and it survives every rescaling); fmaxf drops a
+    // NaN, so a lane that has seen nothing but NaN / -inf logits never gets that far and remembers the NaN in a flag.
     float run_m = -INF, run_s = 0.0f, tgt_l = -INF;
+    bool saw_nan = false;
     int tgt = -1;
     if (MODE == kAuxStats && p.target && row_ok) {
         const long long tv = p.target[(long long)head * p.tgt_hs + row * p.tgt_rs];
@@ -146,7 +150,7 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_sweep_aux(
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float tv = acc[r];
-                l[r] = EUCLID ? -p.scale * __builtin_amdgcn_sqrtf(fmaxf(tv, 0.0f)) : p.scale * tv;
+                l[r] = EUCLID ? -p.scale * __builtin_amdgcn_sqrtf(tv < 0.0f ? 0.0f : tv) : p.scale * tv;  // keeps NaN, like kAuxSims
             }
             if (u * kTileCodes + kTileCodes > p.K) {
 #pragma unroll
@@ -167,6 +171,11 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_sweep_aux(
             if (run_m > -INF) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) run_s += __expf(l[r] - run_m);
+            } else {
+                // (taken after the tail masking: the padding codes of a row that holds an inf are NaN by 0 * inf and do not count)
+                asm volatile("" ::: "memory");  // keep this a branch: rows without a finite logit are rare
+#pragma unroll
+                for (int r = 0; r < 16; ++r) saw_nan = saw_nan || l[r] != l[r];
             }
         }
     };
@@ -224,13 +233,18 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_sweep_aux(
         if (h == 0 && row_ok) p.idx[(long long)head * p.idx_hs + row * p.idx_rs] = take ? oc : best_code;
     }
     if (MODE == kAuxStats) {
+        if (saw_nan) {  // travels to the other lane half in the sum: NaN * exp(0 - mm) stays NaN for every mm
+            run_m = 0.0f;
+            run_s = __builtin_nanf("");
+        }
         const float om = __shfl_xor(run_m, 32), os = __shfl_xor(run_s, 32), ot = __shfl_xor(tgt_l, 32);
         const float mm = fmaxf(run_m, om);  // lane half 0 always saw code 0, so mm is finite
         const float s = (run_m > -INF ? run_s * __expf(run_m - mm) : 0.0f) + (om > -INF ? os * __expf(om - mm) : 0.0f);
         if (h == 0 && row_ok) {
             const long long o = (long long)head * p.M + row;
             p.lse[o] = mm + __logf(s);
-            if (p.tgt_logit) p.tgt_logit[o] = (tgt == -1) ? 0.0f : fmaxf(tgt_l, ot);
+            // the lane half that holds the target recorded its logit (fmaxf of the two would drop a NaN one); -2: stays -inf
+            if (p.tgt_logit) p.tgt_logit[o] = (tgt == -1) ? 0.0f : ((tgt >= 0 && ((tgt >> 2) & 1)) ? ot : tgt_l);
         }
     }
 }

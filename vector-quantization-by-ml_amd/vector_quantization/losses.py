@@ -158,7 +158,8 @@ class _CrossEntropyFn(torch.autograd.Function):
         count = valid.sum()
         ctx.save_for_backward(x, codes, target, count, lse, tl)
         ctx.metric = metric
-        return ((lse - tl) * valid).sum() / count
+        # (select, not multiply: an ignored row may hold NaN / inf and NaN * 0 is NaN -- ATen's ignore_index never reads such a row)
+        return torch.where(valid, lse - tl, torch.zeros_like(lse)).sum() / count
 
     @staticmethod
     def backward(ctx, g):

@@ -618,7 +618,9 @@ def _softmax_stats_wide(x, cb, metric, scale, target, packed):
     step = max(1, (64 << 20) // max(1, H * K))  # <= 256 MiB of matrix alive
     for r0 in range(0, M, step):
         logits = similarities(x[:, r0:r0 + step], cb, metric=metric, packed=packed) * scale
-        lse[:, r0:r0 + step] = torch.logsumexp(logits, dim=-1)
+        # the sweep's rule (and ATen's log_softmax): a +inf logit makes the row NaN, where torch.logsumexp answers +inf
+        row_lse = torch.logsumexp(logits, dim=-1)
+        lse[:, r0:r0 + step] = torch.where(torch.isposinf(logits).any(dim=-1), torch.full_like(row_lse, float("nan")), row_lse)
         if target is not None:
             t = target[:, r0:r0 + step]
             picked = torch.gather(logits, 2, t.clamp(0, K - 1)[..., None])[..., 0]
