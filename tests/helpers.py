@@ -211,6 +211,34 @@ def poison_rows(x: torch.Tensor, seed: int = 0):
     return rows
 
 
+def finalize_reference(planes: np.ndarray, cb: np.ndarray, x: np.ndarray, metric: int, ste: bool):
+    """What the finalize-from-keys kernel computes, in plain numpy.  planes [P, H, M] int64 packed keys, cb [H, K, D] and
+    x [H, M, D] float32 -> (idx [H, M] int64, best [H, M] f32, out [H, M, D] f32, sq_err: the fp64 sum over all heads)."""
+    assert planes.dtype == np.int64 and cb.dtype == np.float32 and x.dtype == np.float32
+    key = planes.min(axis=0)  # int64, signed
+    idx = key & np.int64(0xFFFFFFFF)
+    best = vq_oracle.unpack_key(key, metric)[0]
+    q = cb[np.arange(cb.shape[0])[:, None], idx]  # exact gather
+    with np.errstate(all="ignore"):
+        out = x + (q - x) if ste else q  # float32, one rounding each, as vq_oracle.vq_forward writes it
+        sq = float(np.sum((q.astype(np.float64) - x.astype(np.float64)) ** 2))
+    return idx, best, out, sq
+
+
+def finalize_rows_per_wave(M: int) -> int:
+    """Rows one wave of the finalize kernel walks: the grid is capped at 2048 workgroups x 4 waves."""
+    return -(-M // (4 * min(-(-M // 4), 2048)))
+
+
+def finalize_sq_err_bound(D: int, M: int, vec: bool) -> float:
+    """Relative error bound of the finalize kernel's sq_err against the fp64 sum, for finite data: (L R + 9) 2^-24.
+    Every term is a square, so relative errors do not amplify: one rounding in c - x (2 ulp-halves once squared), one per fmaf
+    step of a lane's chain (L per row -- ceil(D / 64) on the scalar path, 4 ceil(D / 256) on the float4 path -- times R rows
+    per wave), six butterfly additions, one half-ulp of slack for the second-order terms; the double sum is negligible."""
+    chain = 4 * -(-D // 256) if vec else -(-D // 64)
+    return (chain * finalize_rows_per_wave(M) + 9) * 2.0 ** -24
+
+
 def same_values(got: np.ndarray, want: np.ndarray) -> bool:
     """bit-equal where finite / inf, NaN where NaN (the payload of a NaN is not part of the contract)"""
     gn, wn = np.isnan(got), np.isnan(want)

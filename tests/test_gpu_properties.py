@@ -155,17 +155,31 @@ def test_rows_wider_than_512_dims_take_the_sliced_sweep(oracle):
     np.testing.assert_array_equal(r["out"].cpu().numpy(), ref["out"])
 
 
-def test_sharded_search_single_rank_api(oracle):
+@pytest.mark.parametrize("metric", [0, 1])
+@pytest.mark.parametrize("ste", [False, True])
+def test_sharded_search_single_rank_api(oracle, ste, metric):
+    from helpers import finalize_sq_err_bound
     from vector_quantization.sharded import ShardedCodebookSearch
 
-    full = _rand((4096, 128), 9).to(DEV)
-    x = _rand((777, 128), 10).to(DEV)
-    s = ShardedCodebookSearch(full)
-    out, idx, best, sq = s(x, want_sq_err=True)
-    ri, rb = oracle.nearest(x.cpu().numpy(), full.cpu().numpy(), oracle.EUCLID)
+    M, D = 777, 128
+    full = _rand((4096, D), 9).to(DEV)
+    x = _rand((M, D), 10).to(DEV)
+    s = ShardedCodebookSearch(full, use_cosine_sim=metric == oracle.DOT)
+    out, idx, best, sq = s(x, ste=ste, want_sq_err=True)
+    xn, fn = x.cpu().numpy(), full.cpu().numpy()
+    ri, rb = oracle.nearest(xn, fn, metric)
     np.testing.assert_array_equal(idx.cpu().numpy(), ri)
     assert np.array_equal(best.cpu().numpy().view(np.uint32), rb.view(np.uint32))
-    assert torch.equal(out, full[idx])
+    q = fn[ri]
+    if ste:  # the straight-through value, one float32 rounding per operation
+        assert np.array_equal(out.cpu().numpy().view(np.uint32), (xn + (q - xn)).view(np.uint32))
+    else:
+        assert torch.equal(out, full[idx])
+    # the squared error against the fp64 sum: dense 16-byte aligned rows of D % 4 == 0 take the finalize's float4 path
+    want = float(np.sum((q.astype(np.float64) - xn.astype(np.float64)) ** 2))
+    ratio = abs(float(sq[0]) - want) / want / finalize_sq_err_bound(D, M, True)
+    print(f"sharded single rank ste={ste} metric={metric}: sq_err error / bound = {ratio:.3f} (vector path)")
+    assert ratio <= 1.0
 
 
 def test_stream_reentrancy():

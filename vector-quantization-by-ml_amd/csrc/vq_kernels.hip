@@ -1252,10 +1252,10 @@ int vq_finalize_key_planes_f32(const vq_args *a, const int64_t *keys, int n_plan
     if (rc) return rc;
     if (n_planes < 1) return fail(VQ_E_BADARG, "vq_finalize_keys: n_planes must be >= 1");
     if (a->Q != 1) return fail(VQ_E_BADARG, "vq_finalize_keys: Q must be 1");
-    if (!keys || !a->cb) return fail(VQ_E_BADARG, "vq_finalize_keys: keys / cb is null");
-    if (a->M == 0) {
+    if (a->M == 0) {  // (no rows: no keys either -- an empty tensor's address is null, as x's may be in check_common)
         return a->sq_err ? clear_sq_err(a->sq_err, 1, (hipStream_t)stream, "vq_finalize_keys: clearing sq_err") : 0;
     }
+    if (!keys || !a->cb) return fail(VQ_E_BADARG, "vq_finalize_keys: keys / cb is null");
     hipStream_t s = (hipStream_t)stream;
     float *loss_part = nullptr;
     if (a->sq_err) {
