@@ -352,6 +352,56 @@ int vq_gumbel_reinmax_backward_codes_f32(const vq_args *a, const float *g, int64
                                          float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * Codebook diversity loss (vector_quantize_pytorch.py:324-334 with utils/general.py:25-30) and its gradient with respect to
+ * the rows, nothing of [M, K] in memory.  With s the similarities [H][M][K] as above, T the diversity temperature, N the
+ * number of sequence positions and n(m) = (m / pos_div) % N the position of row m of every head (pos_div = 1, or the number
+ * of heads when the heads of one shared codebook are interleaved in the rows); C = H * M / N rows per position:
+ *   p_hmk = softmax_k(-T s_hmk)                     (the sign is the reference's: under Euclid the FAR codes get the mass)
+ *   A_nk  = (1 / C) sum over h and the rows m with n(m) = n of p_hmk          (over the heads too, in head order)
+ *   loss  = (1 / N) sum_nk A_nk log(max(A_nk, 1e-5))
+ *   U_nk  = g / (N C) * (log(max(A_nk, 1e-5)) + [A_nk >= 1e-5])               (g = dL/dloss; ATen's clamp backward)
+ *   delta_hm = sum_k p_hmk U[n(m)][k]               w_hmk = dL/ds_hmk = -T p_hmk (U[n(m)][k] - delta_hm)
+ *   dot:    grad_x = w l             Euclid:  r = w / s (0 where s == 0),  grad_x = x rowsum(r) - r l
+ * where l = the live codes when live_packed is given, else the codes of a->packed: everything that decides the weights (s,
+ * lse2, the zero mask, rowsum(r)) comes from a->packed, what they are multiplied with from live_packed (the convention of
+ * vq_ce_backward_live_f32).  loss and U are [N][K] element-wise work on A and are left to the caller.
+ * All four use a->x (strided rows), H, M, K, D (<= 256: VQ_E_UNSUPPORTED beyond) and metric; Q is ignored.  Checked before
+ * any launch (VQ_E_BADARG): T finite; N > 0, pos_div > 0 and M a multiple of N * pos_div; every array argument non-null
+ * and 16-byte aligned.  M == 0: nothing is launched and nothing is written.
+ * lse2, delta: [H][vq_gumbel_row_stride(M)] floats (columns past M unused).  A, U: [N][vq_gumbel_row_stride(K)] floats; the
+ * entries of A past K are written as 0, those of U must be finite (they are read and discarded).
+ * vq_diversity_stats_f32 (a->packed): lse2[h][m] = log2 sum_k exp2(-T s log2 e).
+ * vq_diversity_accumulate_f32 (a->cb, the natural codes): writes A.  The rows are packed into the workspace in position-major
+ *   order -- image row n*Cp + j holds row ((j / pos_div) N + n) pos_div + j % pos_div for j < M / N, with
+ *   Cp = ceil(M / N / 32) * 32: every position is padded to whole 32-row sub-tiles, the padding contributes exactly 0 -- and
+ *   lse2 beside them in the same order.  A wave owns 32 codes and sums p over the rows of one position at a time; the
+ *   positions (never the rows of one position) are split over workgroups, the heads' partial tables are added in head order.
+ *   No float atomics: bit-identical results from run to run on one device.  The sweep's work grows with Cp / (M / N): up
+ *   to 32x for one row per position.
+ *   Workspace (>= vq_diversity_workspace_bytes bytes, 16-byte aligned; 0 = unsupported shape), in 4-byte units, with
+ *   Mp = N*Cp rounded up to the staged tile (32 * max(1, 256 / Dp) rows, Dp = D rounded up to 32 / 64 / 128 / 256) and
+ *   rsK = vq_gumbel_row_stride(K):
+ *     [x image: H * (Mp*(Dp + 4) + 2048)][lse2 in image order: H*Mp][partials of A: H*N*rsK]
+ *   More than 2^31 - 1 rows or an image of 2 GiB or more: VQ_E_UNSUPPORTED (use row chunks).
+ * vq_diversity_delta_f32 (a->packed): delta from lse2 and U, as sum_k p U / sum_k p with the p it summed (1 within rounding).
+ *   w, and with it grad_x, does not change when a constant is added to a row of U (delta moves with it): a caller who
+ *   subtracts a per-position constant near the row's values first shrinks every rounding error of delta and of U - delta by
+ *   |U - constant| / |U|.
+ * vq_diversity_backward_x_f32 (a->packed): grad_x (h, m, d) at grad_x[h*gx_hs + m*gx_rs + d].  live_packed: NULL, or the
+ *   packed images of the live codes (vq_pack_codebooks_f32 of [H][K][D] with the same metric, head stride live_pk_hs floats);
+ *   an image bit-equal to a->packed gives bit for bit the result of NULL.
+ */
+int64_t vq_diversity_workspace_bytes(int H, int64_t M, int K, int D, int N);
+int vq_diversity_stats_f32(const vq_args *a, float T, float *lse2, void *stream);
+int vq_diversity_accumulate_f32(const vq_args *a, float T, int N, int pos_div, const float *lse2, float *A, void *workspace,
+                                int64_t workspace_bytes, void *stream);
+int vq_diversity_delta_f32(const vq_args *a, float T, int N, int pos_div, const float *lse2, const float *U, float *delta,
+                           void *stream);
+int vq_diversity_backward_x_f32(const vq_args *a, const float *live_packed, int64_t live_pk_hs, float T, int N, int pos_div,
+                                const float *lse2, const float *delta, const float *U, float *grad_x, int64_t gx_rs, int64_t gx_hs,
+                                void *stream);
+
+/*
  * Gumbel-max sampling of the code, utils/general.py:112-129 (ind = argmax(similarities / temperature + gumbel_noise)) with
  * the noise of utils/general.py:25-30, as an epilogue of the similarity sweep: nothing of [M, K] in memory, one launch.
  *   idx[h*idx_hs + m*idx_rs] = first index of the maximum over k < K of  key = fl(fl(s * tau) + g)

@@ -32,6 +32,19 @@
 //   kRmX       as kGumX: the statistics and ind of the lane's row, col / e of the streamed codes read four at a time
 //   kRmC       as kGumC: the statistics and ind of the streamed rows read four at a time, col / e of the lane's code
 // ind is only ever compared with a code index.  Streamed padding is masked AFTER the clamp (p1 = 1e-5 there, not 0).
+//
+// Codebook diversity loss (vector_quantize_pytorch.py:324-334) through the same sweep, four more roles with ONE product per
+// sub-tile (there is no g: what a = g c^T is above is a lookup in the table U [N, K] here).  tau = -T, so p = softmax_k(-T s):
+//   kDivStats  as kGumStats without the second product -> lse2
+//   kDivAcc    the orientation of kRmCol: the streamed image holds the x rows in position-major order, every position padded
+//              to whole 32-row sub-tiles (vq_gumbel_pack_rows with a RowMap), the log-sum-exps in the same order; the per-lane
+//              sums of p are flushed at the last sub-tile of a position -> one partial [N, K] per head.  blockIdx.z splits
+//              the POSITIONS, so no position is summed across workgroups; padding rows are masked (select, no clamp)
+//   kDivDelta  as kGumStats: delta_m = sum_k p_mk U[n(m)][k] / sum_k p_mk, U read four codes at a time in the row of the lane's
+//              position
+//   kDivX      as kGumX with a = U[n(m)][k]; when a second image is given (the live codes) the contraction reads ITS tile,
+//              staged beside the first the way the codes-resident roles stage the g rows
+// n(m) = (m / pos_div) % N.
 // ------------------------------------------------------------------------------------------------
 constexpr int kGumStats = 0;
 constexpr int kGumX = 1;
@@ -40,6 +53,10 @@ constexpr int kRmStats = 3;
 constexpr int kRmCol = 4;
 constexpr int kRmX = 5;
 constexpr int kRmC = 6;
+constexpr int kDivStats = 7;
+constexpr int kDivAcc = 8;
+constexpr int kDivDelta = 9;
+constexpr int kDivX = 10;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 }  // namespace
@@ -70,6 +87,11 @@ struct GumbelParams {
     long long ck_hs;
     float *colp, *ep;              // kRmCol: partials [splits][H][ck_hs]
     long long cp_zs;
+    // diversity roles (tau = -T; lse: per row, kDivAcc in image order; delta; out: gx, kDivAcc the per-head partials of A)
+    const float *U;                // kDivDelta / kDivX: [N][U_rs], finite past K
+    long long U_rs, gimg_hs;       // gimg (kDivX): the packed live codes or null, head stride gimg_hs
+    int div_N, div_posdiv;         // position of row m: (m / div_posdiv) % div_N
+    int div_spp, div_ch, div_pps;  // kDivAcc: sub-tiles per position, rows per position and head, positions per blockIdx.z
 };
 }  // namespace vqi
 namespace {
@@ -110,10 +132,13 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     using GG = GumGeo<DP>;
     constexpr int RS = G::RS, RS4 = G::RS4, SUB = G::SUB, NG = DP / 8, V = GG::V, NJ = GG::NJ, NACC = GG::NACC;
     constexpr bool EUCLID = (METRIC == VQ_METRIC_EUCLID);
-    constexpr bool CODES = (ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC);
-    constexpr bool RM = (ROLE >= kRmStats);
+    constexpr bool DIV = (ROLE >= kDivStats);  // one product per sub-tile, no g
+    constexpr bool CODES = (ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC || ROLE == kDivAcc);
+    constexpr bool RM = (ROLE >= kRmStats && ROLE <= kRmC);
     constexpr bool COLS = (ROLE == kRmCol);
-    constexpr bool STATS = (ROLE == kGumStats || ROLE == kRmStats || COLS);  // no contraction: no gradient accumulators
+    // no contraction: no gradient accumulators
+    constexpr bool STATS = (ROLE == kGumStats || ROLE == kRmStats || COLS || ROLE == kDivStats || ROLE == kDivAcc || ROLE == kDivDelta);
+    constexpr bool GIMG = CODES && !DIV;  // a second streamed image at compile time: the packed g rows
     constexpr int IMG_F4 = 2 * G::BUF_F4;  // the two tile buffers of one image
     constexpr float LOG2E = 1.4426950408889634f;
     const float INF = __builtin_inff();
@@ -134,8 +159,8 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     float rn0 = 0.0f;
     load_x_fragments<G::CH, G::XS, DP / G::CH, EUCLID>(rh, p.res_rs, p.NR, p.D, p.vec_res, row0, true, smem, wave, lane, rf, rn0);
     __syncthreads();  // (the staging regions are reused: by the second pass, then as tile buffers)
-    float gf[CODES ? 1 : DP / 2];
-    if constexpr (!CODES) {
+    float gf[(CODES || DIV) ? 1 : DP / 2];
+    if constexpr (!CODES && !DIV) {
         float unused = 0.0f;
         load_x_fragments<G::CH, G::XS, DP / G::CH, false>(p.g + (long long)head * p.g_hs, p.g_rs, p.NR, p.D, p.vec_g, row0, true, smem,
                                                           wave, lane, gf, unused);
@@ -145,16 +170,24 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     const long long row = row0 + c;
     const bool row_ok = row < p.NR;
     const float *img = p.img + (long long)head * p.img_hs;
-    const float *gimg = CODES ? p.gimg + (long long)head * p.img_hs : nullptr;
-    const float b_aug = h ? 1.0f : rn0;
+    const bool live = (ROLE == kDivX) && p.gimg != nullptr;  // (workgroup-uniform) contract with the tile of a second image
+    const float *gimg = GIMG ? p.gimg + (long long)head * p.img_hs : (live ? p.gimg + (long long)head * p.gimg_hs : nullptr);
+    // (kDivAcc: the streamed row's norm first, as in the rows-resident roles -- its similarities are theirs bit for bit)
+    const float b_aug = (ROLE == kDivAcc) ? (h ? rn0 : 1.0f) : (h ? 1.0f : rn0);
     const float tau2 = p.tau * LOG2E;
     const long long st0 = (long long)head * p.st_hs;
 
     // per resident row (kGumX): the statistics of this lane's row
     float lse_row = 0.0f, delta_row = 0.0f;
-    if ((ROLE == kGumX || ROLE == kRmX) && row_ok) {
+    if ((ROLE == kGumX || ROLE == kRmX || ROLE == kDivX) && row_ok) {
         lse_row = p.lse[st0 + row];
         delta_row = p.delta[st0 + row];
+    }
+    // diversity: the row of U of this lane's sequence position
+    const float *u_row = nullptr;
+    if constexpr (ROLE == kDivDelta || ROLE == kDivX) {
+        if (ROLE == kDivDelta && row_ok) lse_row = p.lse[st0 + row];
+        u_row = p.U + (row_ok ? (row / p.div_posdiv) % p.div_N : 0) * p.U_rs;
     }
     // reinmax: kRmX the rest of the row's statistics and its selected code; kRmC the lane's own code's 1 / col and e
     float lse1_row = 0.0f, rcol_own = 0.0f, e_own = 0.0f;
@@ -182,17 +215,32 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
             const int ck = i * WAVES + wave;
             if (ck < G::TILE_CHUNKS) {
                 lds_dma16(img, p.img_bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16, tile4_lds + buf * G::BUF_F4 + ck * 64);
-                if constexpr (CODES)
+                if constexpr (GIMG)
                     lds_dma16(gimg, p.img_bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16,
                               tile4_lds + IMG_F4 + buf * G::BUF_F4 + ck * 64);
+                if constexpr (ROLE == kDivX) {
+                    if (live)
+                        lds_dma16(gimg, p.img_bytes, lane * 16, (tile * G::TILE_F4 + ck * 64) * 16,
+                                  tile4_lds + IMG_F4 + buf * G::BUF_F4 + ck * 64);
+                }
             }
         }
     };
 
     int t_begin = 0, t_end = p.ntiles;
-    if constexpr (CODES) {
+    if constexpr (GIMG) {
         t_begin = (int)blockIdx.z * p.tiles_per_split;
         t_end = t_begin + p.tiles_per_split < p.ntiles ? t_begin + p.tiles_per_split : p.ntiles;
+    }
+    // kDivAcc: the sub-tiles [u_lo, u_hi) of this split's positions, and the staged tiles that hold them
+    int u_lo = 0, u_hi = 0;
+    if constexpr (ROLE == kDivAcc) {
+        const int n0 = (int)blockIdx.z * p.div_pps;
+        const int n1 = n0 + p.div_pps < p.div_N ? n0 + p.div_pps : p.div_N;
+        u_lo = n0 * p.div_spp;
+        u_hi = n1 * p.div_spp;
+        t_begin = u_lo / SUB;
+        t_end = (u_hi + SUB - 1) / SUB;
     }
     stage(t_begin, 0);
     __syncthreads();
@@ -203,6 +251,10 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
         for (int st = 0; st < SUB; ++st) {
             const int u = t * SUB + st;
             if ((long long)u * kTileCodes >= p.NS) break;  // workgroup-uniform: nothing but padding from here on
+            if constexpr (ROLE == kDivAcc) {
+                if (u < u_lo) continue;  // (a neighbour split's position in the same staged tile)
+                if (u >= u_hi) break;
+            }
             const f32x4 *tb = tile4 + cur * G::BUF_F4 + st * (kTileCodes * RS4);
             const long long sbase = (long long)u * kTileCodes + 4 * h;  // streamed row of this lane's register 0
             // kGumC: the statistics of the 16 streamed rows this lane's registers stand for (rows 8 g + 4 h + 0..3 of the sub-tile)
@@ -211,7 +263,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     l4[g] = *(const f32x4 *)(p.lse + st0 + sbase + 8 * g);
-                    d4[g] = *(const f32x4 *)(p.delta + st0 + sbase + 8 * g);
+                    if constexpr (!DIV) d4[g] = *(const f32x4 *)(p.delta + st0 + sbase + 8 * g);
                 }
             }
             // ---- the two products: acc = t (squared distance / dot product), acca = the image's multiple of a
@@ -221,14 +273,14 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                 f32x4 a[NG];
                 const float cnv = EUCLID ? ((const float *)tb)[c * RS + DP] : 0.0f;
                 mfma_prefetch<DP>(a, ta);
-                if constexpr (CODES) mfma_range<DP, 0, NG>(acc, a, ta, rf);
+                if constexpr (CODES || DIV) mfma_range<DP, 0, NG>(acc, a, ta, rf);
                 else mfma_range2<DP>(acc, acca, a, ta, rf, gf);
                 if (EUCLID) {
-                    const float a_aug = h ? cnv : 1.0f;
+                    const float a_aug = (ROLE == kDivAcc) ? (h ? 1.0f : cnv) : (h ? cnv : 1.0f);
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a_aug, b_aug, acc, 0, 0, 0);
                 }
             }
-            if constexpr (CODES) {
+            if constexpr (GIMG) {
                 const f32x4 *ta = tb + IMG_F4 + c * RS4 + h;
                 f32x4 a[NG];
                 mfma_prefetch<DP>(a, ta);
@@ -236,7 +288,56 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
             }
             // (the codebook image of the Euclid metric holds -2 c; the image of the g rows holds g)
             const float a_scale = (EUCLID && !CODES) ? -0.5f : 1.0f;
-            if constexpr (ROLE == kRmStats) {
+            if constexpr (ROLE == kDivAcc) {
+                // ---- p of the 16 streamed rows of this lane's registers; row j of the position is real while j < div_ch
+                const int jb = (u % p.div_spp) * kTileCodes + 4 * h;
+                float sum_p = 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float tv = acc[r];
+                    const float lse2 = l4[r >> 2][r & 3];
+                    // (the logit exactly as kDivStats rounded it, then minus the row's lse2: the p of a row sum to 1 within rounding)
+                    const float lg = EUCLID ? -tau2 * __builtin_amdgcn_sqrtf(tv < 0.0f ? 0.0f : tv) : tau2 * tv;
+                    const float pr = __builtin_amdgcn_exp2f(lg - lse2);
+                    sum_p += (jb + (r & 3) + 8 * (r >> 2) < p.div_ch) ? pr : 0.0f;
+                }
+                run_s += sum_p;
+                if ((u + 1) % p.div_spp == 0) {  // the position's last sub-tile: its sum over the rows of this head is complete
+                    const float tot = run_s + __shfl_xor(run_s, 32);
+                    if (h == 0 && row_ok) p.out[(long long)head * p.out_hs + (long long)(u / p.div_spp) * p.out_rs + row] = tot;
+                    run_s = 0.0f;
+                }
+            } else if constexpr (ROLE == kDivDelta || ROLE == kDivX) {
+                // ---- kDivDelta: run_d += p U;  kDivX: acc[r] <- w (dot) / r = w / s (Euclid) in place, w = tau p (U - delta)
+                float sum_u = 0.0f;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 u4 = *(const f32x4 *)(u_row + sbase + 8 * g);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int r = 4 * g + q;
+                        const bool pad = sbase + 8 * g + q >= p.NS;  // padding codes of the streamed image
+                        const float tv = acc[r];
+                        const float tc = tv < 0.0f ? 0.0f : tv;  // (keeps a NaN, unlike fmaxf)
+                        const float lg = EUCLID ? -tau2 * __builtin_amdgcn_sqrtf(tc) : tau2 * tv;  // as kDivStats rounded it
+                        const float pr = __builtin_amdgcn_exp2f(lg - lse_row);
+                        if constexpr (ROLE == kDivDelta) {
+                            run_s += pad ? 0.0f : pr;
+                            run_d += pad ? 0.0f : pr * u4[q];
+                        } else {
+                            float v = (p.tau * pr) * (u4[q] - delta_row);
+                            if (EUCLID) {
+                                v = -v * __builtin_amdgcn_rsqf(tc);  // w / s with s = -dist
+                                if (tc == 0.0f) v = 0.0f;            // s == 0: ATen's subgradient 0 (a NaN stays a NaN)
+                            }
+                            if (pad) v = 0.0f;
+                            acc[r] = v;
+                            sum_u += v;
+                        }
+                    }
+                }
+                sum_ratio += sum_u;
+            } else if constexpr (ROLE == kRmStats) {
                 float b[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -319,11 +420,14 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                 sum_ratio += sum_u;
             } else if constexpr (STATS) {
                 float l[16];
+                bool nan_seen = false;  // kDivStats: a NaN similarity makes the row's lse2 NaN (fmaxf below would drop it)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float tv = acc[r];
-                    l[r] = EUCLID ? -tau2 * __builtin_amdgcn_sqrtf(fmaxf(tv, 0.0f)) : tau2 * tv;
+                    if constexpr (DIV) l[r] = EUCLID ? -tau2 * __builtin_amdgcn_sqrtf(tv < 0.0f ? 0.0f : tv) : tau2 * tv;
+                    else l[r] = EUCLID ? -tau2 * __builtin_amdgcn_sqrtf(fmaxf(tv, 0.0f)) : tau2 * tv;
                     if (sbase + (r & 3) + 8 * (r >> 2) >= p.NS) l[r] = -INF;
+                    if constexpr (DIV) nan_seen |= l[r] != l[r];
                 }
                 float tm = l[0];
 #pragma unroll
@@ -339,8 +443,11 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                     for (int r = 0; r < 16; ++r) {
                         const float e = __builtin_amdgcn_exp2f(l[r] - run_m);
                         run_s += e;
-                        run_d = fmaf(e, a_scale * acca[r], run_d);
+                        if constexpr (!DIV) run_d = fmaf(e, a_scale * acca[r], run_d);
                     }
+                }
+                if constexpr (DIV) {
+                    if (nan_seen) run_s = __builtin_nanf("");
                 }
             } else {
                 // ---- acc[r] <- w (dot) / r = w / s (Euclid) of (streamed row sbase + (r&3) + 8(r>>2), this lane's resident row)
@@ -370,7 +477,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
             }
             if constexpr (!STATS) {
                 // ---- contraction: gacc[J*V + e][position i, resident row] += img[streamed row (r, half)][128 J + V i + e] * acc[r]
-                const float *trow = (const float *)tb + (4 * h) * RS + V * c;
+                const float *trow = (const float *)(live ? tb + IMG_F4 : tb) + (4 * h) * RS + V * c;
                 if constexpr (V == 4) {
                     constexpr int NSEQ = NJ * 16, PF = 4;
                     auto frag = [&](int n) -> f32x4 {
@@ -409,7 +516,14 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
         __syncthreads();  // next tile landed, everybody is done reading this one
     }
 
-    if constexpr (COLS) {
+    if constexpr (ROLE == kDivAcc) {
+        // (every position was flushed inside the sweep)
+    } else if constexpr (ROLE == kDivDelta) {
+        // (divided by the p that were summed, 1 within rounding: sum_k w_k = 0 then holds for the p kDivX recomputes)
+        run_s += __shfl_xor(run_s, 32);
+        run_d += __shfl_xor(run_d, 32);
+        if (h == 0 && row_ok) p.delta[st0 + row] = run_d / run_s;
+    } else if constexpr (COLS) {
         // the two lane halves hold the two halves of every sub-tile's rows; one partial per (split, code)
         run_s += __shfl_xor(run_s, 32);
         run_d += __shfl_xor(run_d, 32);
@@ -442,7 +556,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
         const float d = run_d * w0 + od * w1;
         if (h == 0 && row_ok) {
             p.lse[st0 + row] = mm + __builtin_amdgcn_logf(s);
-            p.delta[st0 + row] = d / s;
+            if constexpr (!DIV) p.delta[st0 + row] = d / s;
         }
     } else {
         // ---------------- finalize: fragment layout -> natural rows through LDS ----------------
@@ -483,16 +597,39 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
 
 // packed images of the x rows (metric-scaled, |x|^2 behind every row: vq_pack.inc layout) and of the g rows (plain) for
 // kGumC; rows may be strided.  One thread per packed row; rows past M are zero (|x|^2 = +inf under Euclid, as for padding codes).
+// With a RowMap (Cp > 0; the diversity loss, g == nullptr: no g image) the image is position-major: image row n Cp + j holds
+// row j of sequence position n for j < C -- source row ((j / pos_div) N + n) pos_div + j % pos_div, the j-th row m in
+// ascending order with (m / pos_div) % N == n -- and padding for C <= j < Cp and past N Cp; `stat` (a per-row array,
+// [head][stat_hs]) is copied along in image order, 0 in the padding.
+}  // namespace
+namespace vqi {
+struct RowMap {
+    long long C, Cp;  // rows per position and head; the same padded to whole sub-tiles (0: image row m = source row m)
+    int N, pos_div;
+    const float *stat;
+    float *stat_img;
+    long long stat_hs, stat_img_hs;
+};
+}  // namespace vqi
+namespace {
+using vqi::RowMap;
 __global__ void __launch_bounds__(64) vq_gumbel_pack_rows(const float *__restrict__ x, long long x_rs, long long x_hs,
                                                           const float *__restrict__ g, long long g_rs, long long g_hs, long long M,
                                                           long long Mp, int D, int DP, int metric, float *__restrict__ ximg,
-                                                          float *__restrict__ gimg, long long img_hs) {
+                                                          float *__restrict__ gimg, long long img_hs, const RowMap map) {
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= Mp) return;
     const int RS = DP + 4;
-    const bool real = m < M;
-    const float *xs = x + (long long)blockIdx.y * x_hs + (real ? m : 0) * x_rs;
-    const float *gs = g + (long long)blockIdx.y * g_hs + (real ? m : 0) * g_rs;
+    bool real = m < M;
+    long long src = m;
+    if (map.Cp > 0) {
+        const long long n = m / map.Cp, j = m % map.Cp;
+        real = n < map.N && j < map.C;
+        src = ((j / map.pos_div) * map.N + n) * map.pos_div + j % map.pos_div;
+        map.stat_img[(long long)blockIdx.y * map.stat_img_hs + m] = real ? map.stat[(long long)blockIdx.y * map.stat_hs + src] : 0.0f;
+    }
+    const float *xs = x + (long long)blockIdx.y * x_hs + (real ? src : 0) * x_rs;
+    const float *gs = g ? g + (long long)blockIdx.y * g_hs + (real ? src : 0) * g_rs : xs;
     float *xd = ximg + (long long)blockIdx.y * img_hs + m * RS;
     float *gd = gimg + (long long)blockIdx.y * img_hs + m * RS;
     const float scale = (metric == VQ_METRIC_EUCLID) ? -2.0f : 1.0f;
@@ -509,13 +646,15 @@ __global__ void __launch_bounds__(64) vq_gumbel_pack_rows(const float *__restric
         }
         *(f32x4 *)(xd + 8 * g8) = (f32x4){scale * v[0], scale * v[2], scale * v[4], scale * v[6]};
         *(f32x4 *)(xd + 8 * g8 + 4) = (f32x4){scale * v[1], scale * v[3], scale * v[5], scale * v[7]};
-        *(f32x4 *)(gd + 8 * g8) = (f32x4){w[0], w[2], w[4], w[6]};
-        *(f32x4 *)(gd + 8 * g8 + 4) = (f32x4){w[1], w[3], w[5], w[7]};
+        if (g) {
+            *(f32x4 *)(gd + 8 * g8) = (f32x4){w[0], w[2], w[4], w[6]};
+            *(f32x4 *)(gd + 8 * g8 + 4) = (f32x4){w[1], w[3], w[5], w[7]};
+        }
     }
     const float chain = real ? cn : 0.0f;
     if (!real) cn = __builtin_inff();
     *(f32x4 *)(xd + DP) = (f32x4){(metric == VQ_METRIC_EUCLID) ? cn : 0.0f, 1.0f, chain, 0.0f};
-    *(f32x4 *)(gd + DP) = (f32x4){0.0f, 1.0f, 0.0f, 0.0f};
+    if (g) *(f32x4 *)(gd + DP) = (f32x4){0.0f, 1.0f, 0.0f, 0.0f};
 }
 
 // gc[i] = parts[0][i] + parts[1][i] + ... in this order, i over [H, K, D]

@@ -44,6 +44,7 @@
 //                        the moment-matching transform of the codes and of the accumulated EMA sums
 //   vq_decode.inc        indices -> code vectors: every stage's gather and their stage-ordered sum in one pass (vq_decode_f32)
 //   vq_lfq_decode.inc    the same for the lookup-free family: codes from the index bits, no table (vq_lfq_decode_f32)
+//   vq_diversity.inc     codebook diversity loss: the head-ordered sum of the position table (its sweeps are roles of vq_gumbel.inc)
 //   this file           host-side dispatch and the C ABI (include/vq_mi355x.h)
 //
 // Reference lines replaced (relative to the reference root): vector_quantization/codebooks.py:386-397,
@@ -70,6 +71,7 @@
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward (+ live codes)
 //   7 Gumbel straight-through backward sweeps               8 Gumbel-max sampling sweeps + Gumbel reinmax backward sweeps
+//   9 codebook diversity loss sweeps
 #ifndef VQ_PART
 #define VQ_PART -1
 #endif
@@ -101,6 +103,7 @@ namespace {
 #include "vq_affine.inc"
 #include "vq_decode.inc"
 #include "vq_lfq_decode.inc"
+#include "vq_diversity.inc"
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -407,8 +410,9 @@ template <int DP, int METRIC, int ROLE>
 int launch_gumbel_t(const GumbelParams &p, int H, int gz, hipStream_t s) {
     using G = Geo<DP, 4>;
     using GG = GumGeo<DP>;
-    constexpr bool two_images = ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC;  // packed x rows and packed g rows
-    constexpr bool no_gradient = ROLE == kGumStats || ROLE == kRmStats || ROLE == kRmCol;
+    // packed x rows and packed g rows; kDivX: the searched codes and the live codes
+    const bool two_images = ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC || (ROLE == kDivX && p.gimg);
+    constexpr bool no_gradient = ROLE == kGumStats || ROLE == kRmStats || ROLE == kRmCol || ROLE == kDivStats || ROLE == kDivAcc || ROLE == kDivDelta;
     const size_t tile_floats = (size_t)(two_images ? 2 : 1) * 2 * G::BUF_F4 * 4, rows_floats = (size_t)4 * 32 * G::XS;
     const size_t stage_floats = no_gradient ? 0 : (size_t)4 * (32 * GG::GS + 32);
     size_t floats = tile_floats > rows_floats ? tile_floats : rows_floats;
@@ -436,6 +440,18 @@ int launch_reinmax_m(int role, const GumbelParams &p, int H, int gz, int metric,
         if (role == kRmCol) return launch_gumbel_t<DP, ME, kRmCol>(p, H, gz, s);
         if (role == kRmX) return launch_gumbel_t<DP, ME, kRmX>(p, H, 1, s);
         return launch_gumbel_t<DP, ME, kRmC>(p, H, gz, s);
+    });
+}
+
+// the diversity roles of the same sweep: a build part of their own
+template <int DP>
+int launch_diversity_m(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s) {
+    return with_metric(metric, [&](auto m) {
+        constexpr int ME = decltype(m)::value;
+        if (role == kDivStats) return launch_gumbel_t<DP, ME, kDivStats>(p, H, 1, s);
+        if (role == kDivAcc) return launch_gumbel_t<DP, ME, kDivAcc>(p, H, gz, s);
+        if (role == kDivDelta) return launch_gumbel_t<DP, ME, kDivDelta>(p, H, 1, s);
+        return launch_gumbel_t<DP, ME, kDivX>(p, H, 1, s);
     });
 }
 
@@ -482,9 +498,11 @@ template <int DP> int part_ce_bwd(const CeBwdParams &p, int H, int metric, hipSt
 template <int DP> int part_sample(const AuxParams &p, int H, int metric, hipStream_t s);
 template <int DP> int part_gumbel(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <int DP> int part_reinmax(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <int DP> int part_diversity(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 #define VQ_DECLARE_GUMBEL_PARTS(DP)                                                                              \
     template <> int part_gumbel<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s); \
-    template <> int part_reinmax<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+    template <> int part_reinmax<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);  \
+    template <> int part_diversity<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <int DP> int part_ce_bwd_live(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
 template <> int part_ce_bwd_live<32>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
 template <> int part_ce_bwd_live<64>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
@@ -620,6 +638,15 @@ VQ_DEFINE_REINMAX_PART(64)
 VQ_DEFINE_REINMAX_PART(128)
 VQ_DEFINE_REINMAX_PART(256)
 #undef VQ_DEFINE_REINMAX_PART
+#endif
+#if VQ_OWN(9)
+#define VQ_DEFINE_DIVERSITY_PART(DP) \
+    template <> int part_diversity<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s) { return launch_diversity_m<DP>(role, p, H, gz, metric, s); }
+VQ_DEFINE_DIVERSITY_PART(32)
+VQ_DEFINE_DIVERSITY_PART(64)
+VQ_DEFINE_DIVERSITY_PART(128)
+VQ_DEFINE_DIVERSITY_PART(256)
+#undef VQ_DEFINE_DIVERSITY_PART
 #endif
 }  // namespace vqi
 
@@ -1949,16 +1976,17 @@ static int fill_gumbel_codes(GumbelParams &p, const char *who, const GumbelFamil
 static int pack_gumbel_rows(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, const GumbelWorkspace &w, float *ws, hipStream_t s) {
     return launch<vq_gumbel_pack_rows>(dim3((unsigned)((w.pl.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
                                        (long long)a->x_rs, (long long)a->x_hs, g, (long long)g_rs, (long long)g_hs, (long long)a->M, w.pl.Mp,
-                                       a->D, padded_dim(a->D), a->metric, ws, ws + w.gimg_off, w.pl.img_floats);
+                                       a->D, padded_dim(a->D), a->metric, ws, ws + w.gimg_off, w.pl.img_floats, vqi::RowMap{});
 }
 
-// the only padded-dim dispatch of the seven roles: the kGum* kernels live in build part 7, the kRm* kernels in part 8
+// the only padded-dim dispatch of the eleven roles: the kGum* kernels live in build part 7, the kRm* kernels in part 8, the kDiv* kernels in part 9
 static int launch_gumbel(int role, const GumbelParams &p, const vq_args *a, int gz, hipStream_t s) {
     const int DP = padded_dim(a->D);
     return with_padded_dim(DP == 512 ? 0 : DP,
                            [&](auto dp) {
                                constexpr int DPC = decltype(dp)::value;
                                if constexpr (DPC > 256) return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
+                               else if (role >= kDivStats) return vqi::part_diversity<DPC>(role, p, a->H, gz, a->metric, s);
                                else if (role < kRmStats) return vqi::part_gumbel<DPC>(role, p, a->H, gz, a->metric, s);
                                else return vqi::part_reinmax<DPC>(role, p, a->H, gz, a->metric, s);
                            },
@@ -2099,6 +2127,149 @@ int vq_gumbel_reinmax_backward_codes_f32(const vq_args *a, const float *g, int64
     p.lse = (float *)lse2_tau; p.lse1 = (float *)lse2_one; p.delta = (float *)delta0;
     p.col = (float *)col; p.e = (float *)e;
     return sweep_grad_codes(kRmC, p, a, w, (float *)workspace, grad_codes, s);
+}
+
+// ---- codebook diversity loss: the kDiv* roles of vq_gumbel.inc, vq_diversity.inc ------------------------------------------
+// The position-major row image of the accumulate sweep: every position's Ch = M / N rows of a head padded to spp whole
+// 32-row sub-tiles, the positions split over blockIdx.z so that every CU has a workgroup (a workgroup owns 128 codes of one
+// head).  Workspace, offsets in 4-byte units (documented in vq_mi355x.h):
+//   [x image H x img_floats][lse2 in image order H x Mp][partials of A: H x N x row_stride(K)]
+struct DiversityPlan {
+    long long Ch, Cp, Mp, img_floats, rsK, lse_off, part_off, floats;
+    int spp, ntiles, pps, splits;
+};
+static DiversityPlan plan_diversity(int H, long long M, int K, int D, int N) {
+    DiversityPlan pl;
+    const int DP = padded_dim(D);
+    const int tile = kTileCodes * sub_tiles(DP);
+    pl.Ch = M / N;
+    pl.spp = (int)((pl.Ch + kTileCodes - 1) / kTileCodes);
+    pl.Cp = (long long)pl.spp * kTileCodes;
+    pl.Mp = ((long long)N * pl.Cp + tile - 1) / tile * tile;
+    pl.img_floats = pl.Mp * (DP + 4) + kPackSlack;
+    pl.ntiles = (int)(pl.Mp / tile);
+    pl.rsK = vq_gumbel_row_stride(K);
+    const long long blocks = (long long)((K + 127) / 128) * H;
+    long long want = (device_cus() + blocks - 1) / blocks;
+    if (want > 64) want = 64;
+    if (want > N) want = N;
+    if (want < 1) want = 1;
+    pl.pps = (int)((N + want - 1) / want);
+    pl.splits = (N + pl.pps - 1) / pl.pps;
+    pl.lse_off = (long long)H * pl.img_floats;
+    pl.part_off = pl.lse_off + (long long)H * pl.Mp;
+    pl.floats = pl.part_off + (long long)H * N * pl.rsK;
+    return pl;
+}
+// the sizes every diversity entry checks the same way; `rows`: M must be whole groups of N * pos_div rows
+static bool diversity_shape_ok(int H, int64_t M, int K, int D, int N, int pos_div) {
+    return H > 0 && M >= 0 && K > 0 && D > 0 && N > 0 && pos_div > 0 && M % ((int64_t)N * pos_div) == 0;
+}
+// padded rows of the image < 2^31 and the image < 2 GiB (one buffer descriptor)
+static bool diversity_image_ok(int64_t M, int D, int N) {
+    if (M > 0x7FFFFFFFll) return false;
+    const long long rows = ((M / N + 31) / 32 * 32) * N + 256;
+    return rows <= 0x7FFFFFFFll && (rows * (padded_dim(D) + 4) + kPackSlack) * 4 < (1ll << 31);
+}
+
+int64_t vq_diversity_workspace_bytes(int H, int64_t M, int K, int D, int N) {
+    if (!diversity_shape_ok(H, M, K, D, N, 1) || M == 0 || D > 256 || !diversity_image_ok(M, D, N)) return 0;
+    return 4 * plan_diversity(H, M, K, D, N).floats;
+}
+
+// what the four entries check before any launch and fill: tau = -T
+static int fill_diversity_params(GumbelParams &p, const char *who, const vq_args *a, float T, int N, int pos_div,
+                                 std::initializer_list<const void *> arrays) {
+    memset(&p, 0, sizeof(p));
+    if (!(__builtin_fabsf(T) < __builtin_inff())) return fail(VQ_E_BADARG, who, "T is not finite");
+    if (!diversity_shape_ok(a->H, a->M, a->K, a->D, N, pos_div))
+        return fail(VQ_E_BADARG, who, "N and pos_div must be positive and M a multiple of N * pos_div");
+    for (const void *q : arrays)
+        if (!q || !aligned16(q)) return fail(VQ_E_BADARG, who, "an array argument is null or not 16-byte aligned");
+    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, who, "D > 256 (use row chunks of vq_similarities_f32)");
+    p.D = a->D;
+    p.tau = -T;
+    p.st_hs = vq_gumbel_row_stride(a->M);
+    p.U_rs = vq_gumbel_row_stride(a->K);
+    p.div_N = N;
+    p.div_posdiv = pos_div;
+    return 0;
+}
+
+int vq_diversity_stats_f32(const vq_args *a, float T, float *lse2, void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    GumbelParams p;
+    if ((rc = fill_diversity_params(p, "vq_diversity_stats", a, T, 1, 1, {lse2}))) return rc;
+    if (a->M == 0) return 0;
+    if ((rc = fill_gumbel_rows(p, a))) return rc;
+    p.lse = lse2;
+    return launch_gumbel(kDivStats, p, a, 1, (hipStream_t)stream);
+}
+
+int vq_diversity_accumulate_f32(const vq_args *a, float T, int N, int pos_div, const float *lse2, float *A, void *workspace,
+                                int64_t workspace_bytes, void *stream) {
+    static const char who[] = "vq_diversity_accumulate";
+    int rc = check_common(a);
+    if (rc) return rc;
+    GumbelParams p;
+    if ((rc = fill_diversity_params(p, who, a, T, N, pos_div, {lse2, A}))) return rc;
+    if (!a->cb) return fail(VQ_E_BADARG, who, "cb is null");
+    if (a->M == 0) return 0;
+    if (!diversity_image_ok(a->M, a->D, N)) return fail(VQ_E_UNSUPPORTED, who, "packed row image >= 2 GiB or too many rows (use row chunks)");
+    const DiversityPlan pl = plan_diversity(a->H, a->M, a->K, a->D, N);
+    if (!workspace || !aligned16(workspace) || workspace_bytes < 4 * pl.floats)
+        return fail(VQ_E_BADARG, who, "workspace too small or misaligned (see vq_diversity_workspace_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    float *ws = (float *)workspace;
+    vqi::RowMap map;
+    map.C = pl.Ch; map.Cp = pl.Cp; map.N = N; map.pos_div = pos_div;
+    map.stat = lse2; map.stat_hs = p.st_hs;
+    map.stat_img = ws + pl.lse_off; map.stat_img_hs = pl.Mp;
+    if ((rc = launch<vq_gumbel_pack_rows>(dim3((unsigned)((pl.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
+                                          (long long)a->x_rs, (long long)a->x_hs, (const float *)nullptr, 0ll, 0ll, (long long)a->M, pl.Mp, a->D,
+                                          padded_dim(a->D), a->metric, ws, (float *)nullptr, pl.img_floats, map)))
+        return rc;
+    p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
+    p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
+    p.img = ws; p.img_hs = pl.img_floats; p.img_bytes = (unsigned)(pl.img_floats * 4);
+    p.NR = a->K; p.NS = (long long)N * pl.Cp;
+    p.ntiles = pl.ntiles;
+    p.lse = ws + pl.lse_off; p.st_hs = pl.Mp;
+    p.div_spp = pl.spp; p.div_ch = (int)pl.Ch; p.div_pps = pl.pps;
+    p.out = ws + pl.part_off; p.out_rs = pl.rsK; p.out_hs = (long long)N * pl.rsK;
+    if ((rc = launch_gumbel(kDivAcc, p, a, pl.splits, s))) return rc;
+    const long long n = (long long)N * pl.rsK;
+    return launch<vq_diversity_reduce_heads>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_diversity_reduce_heads launch",
+                                             (const float *)p.out, n, pl.rsK, a->K, a->H, (float)((double)a->H * (double)pl.Ch), A);
+}
+
+int vq_diversity_delta_f32(const vq_args *a, float T, int N, int pos_div, const float *lse2, const float *U, float *delta,
+                           void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    GumbelParams p;
+    if ((rc = fill_diversity_params(p, "vq_diversity_delta", a, T, N, pos_div, {lse2, U, delta}))) return rc;
+    if (a->M == 0) return 0;
+    if ((rc = fill_gumbel_rows(p, a))) return rc;
+    p.lse = (float *)lse2; p.delta = delta; p.U = U;
+    return launch_gumbel(kDivDelta, p, a, 1, (hipStream_t)stream);
+}
+
+int vq_diversity_backward_x_f32(const vq_args *a, const float *live_packed, int64_t live_pk_hs, float T, int N, int pos_div,
+                                const float *lse2, const float *delta, const float *U, float *grad_x, int64_t gx_rs, int64_t gx_hs,
+                                void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    GumbelParams p;
+    if ((rc = fill_diversity_params(p, "vq_diversity_backward_x", a, T, N, pos_div, {lse2, delta, U}))) return rc;
+    if (!grad_x) return fail(VQ_E_BADARG, "vq_diversity_backward_x: grad_x is null");
+    if (a->M == 0) return 0;
+    if ((rc = fill_gumbel_rows(p, a))) return rc;
+    p.lse = (float *)lse2; p.delta = (float *)delta; p.U = U;
+    p.gimg = live_packed; p.gimg_hs = live_pk_hs;
+    p.out = grad_x; p.out_rs = gx_rs; p.out_hs = gx_hs;
+    return launch_gumbel(kDivX, p, a, 1, (hipStream_t)stream);
 }
 
 int vq_max_fused_stages(int D, int want_sq_err) {

@@ -9,11 +9,15 @@ The reference hands the full ``similarities [h, M, K]`` tensor (its ``distances`
 
 Here the forward of the cross entropy is ONE native sweep with an online-softmax epilogue
 (``vq_softmax_stats_f32``: per row log-sum-exp + target logit).  Everything that needs actual matrix entries
-(backward passes, the diversity loss) works on bounded row chunks: ``vq_similarities_f32`` emits a chunk, the
+(backward passes outside the fused kernels' range, the diversity loss of a learnable codebook) works on bounded row chunks: ``vq_similarities_f32`` emits a chunk, the
 chunk's contribution is evaluated with ordinary tensor ops, and gradients flow through ``_SimilarityFn`` whose
 backward is ATen's ``_euclidean_dist_backward`` formula (two library GEMMs per chunk).  The cross entropy's backward with
 respect to x is one fused native sweep instead (``vq_ce_backward_f32``; with an EMA codebook, whose update rewrites the codes
 between forward and backward, ``vq_ce_backward_live_f32``) wherever the kernels reach: D <= 512, with live codes D <= 256.
+The diversity loss is four fused sweeps (``vq_diversity_*_f32``: row log-sum-exps, the position table [N, K], delta per row,
+grad_x -- against the live codes of an EMA codebook) for D <= 256 and a codebook that needs no gradient, from
+``DIVERSITY_FUSED_MIN_ROWS`` rows per sequence position on (``diversity_runs_fused``); the gradient with respect to a
+learnable codebook is not fused: such a call runs on the chunks, forward and backward.
 """
 from __future__ import annotations
 
@@ -206,14 +210,130 @@ def cross_entropy_to_codes(x: torch.Tensor, codes: torch.Tensor, target: torch.T
 
 
 # ------------------------------------------------------------------------------------------------ diversity
+# Rows per sequence position (and head) from which the fused sweeps run.  The accumulate sweep pads every position's rows to
+# whole 32-row sub-tiles, so below 32 rows its work grows by 32 / rows while the position table [N, K] approaches [M, K].
+# Measured on an MI355X (profiles/diversity_bench.md): forward + backward of VectorQuantize(codebook_diversity_loss_weight=0.5)
+# in train mode with the EMA codebook, ms, chunked (the parent commit) / fused, two alternating runs each:
+#   rows  x [B, N, D], K        chunked        fused
+#     1   [1, 1024, 64], 8192   2.77 / 2.64    2.96 / 2.94    fused slower
+#     1   [1, 16384, 256], 1024 2.55 / 2.52    4.45 / 4.38    fused slower
+#     1   [1, 16384, 64], 8192  13.1 / 12.8    12.3 / 12.2
+#     2   [2, 1024, 64], 8192   2.96 / 2.89    2.98 / 2.93    no faster
+#     2   [2, 16384, 64], 8192  20.6 / 20.2    12.5 / 12.3
+#     4   [4, 1024, 64], 1024   1.66 / 1.79    1.06 / 1.20
+#     4   [4, 1024, 64], 8192   3.49 / 3.54    2.85 / 2.95
+#     4   [4, 16384, 64], 8192  35.1 / 35.0    14.2 / 14.1
+#    16   [16, 1024, 64], 1024  1.82 / 1.88    1.07 / 1.19
+#    16   [16, 1024, 64], 8192  8.49 / 8.46    3.02 / 3.09
+# From 4 rows on the fused path was faster at every measured shape; at 1 and 2 rows it was not, at 3 it was not measured.
+DIVERSITY_FUSED_MIN_ROWS = 4
+
+
+def diversity_runs_fused(rows_per_position: int, heads: int = 1) -> bool:
+    """The dispatch rule of the diversity loss, a pure function of the shape: ``rows_per_position`` = C = H * M / N rows of
+    all ``heads`` (separate codebooks) at one sequence position.  C >= 32 always runs fused; below that the rows of one head,
+    C / heads -- what the accumulate sweep pads to 32 -- decide against DIVERSITY_FUSED_MIN_ROWS."""
+    if rows_per_position >= 32:
+        return True
+    return rows_per_position // max(1, heads) >= DIVERSITY_FUSED_MIN_ROWS
+
+
+def _position_chunks(table: torch.Tensor):
+    """Row slices of a position table [N, stride] whose element-wise temporaries stay below CHUNK_BYTES."""
+    return _row_slices(table.shape[0], max(1, CHUNK_BYTES // (4 * table.shape[1])))
+
+
+def diversity_upstream(table: torch.Tensor, g, n_positions: int, count: int, k: int):
+    """U = dL/dp per (position, code) from the position table A [N, stride] (K real columns) and the upstream gradient g of
+    the loss: d loss / d A = (log(max(A, 1e-5)) + [A >= 1e-5]) / N (ATen's clamp backward) and d A / d p = 1 / C.
+    -> (U - centre, centre [N]): dL/ds = -T p (U - delta) does not change when a row of U is shifted (delta = sum_k p U
+    shifts with it), so every row is handed to the sweeps minus its mean over the K codes: at a low temperature the entries
+    of a row differ by a small fraction of their size, and U - delta would otherwise cancel most of its digits.  The padding
+    of the table past K holds A = 0, which gives a finite value there (the sweeps read and discard it)."""
+    scale = torch.as_tensor(g, dtype=torch.float32, device=table.device) / (n_positions * count)
+    u = torch.empty_like(table)
+    centre = torch.empty(table.shape[0], dtype=table.dtype, device=table.device)
+    for rows in _position_chunks(table):  # (the temporaries stay below CHUNK_BYTES)
+        t = table[rows]
+        v = (t.clamp(min=1e-5).log() + (t >= 1e-5).to(t.dtype)) * scale
+        centre[rows] = v[:, :k].mean(dim=-1)
+        u[rows] = v - centre[rows, None]
+    return u, centre
+
+
+class _DiversityFn(torch.autograd.Function):
+    """The diversity loss through the fused sweeps (vq_diversity_*_f32): nothing of [M, K].  Forward: row log-sum-exps, the
+    position table A [N, K], then the entropy with the reference's own tensor ops on A.  Backward: U [N, K] from A and the
+    upstream gradient, delta per row, one sweep for grad_x -- against ``live_codes`` when the codes were rewritten since
+    (weights from ``codes``, contraction with ``live_codes``: the convention of _CrossEntropyFn).  No gradient for the codes:
+    the caller takes the chunked path for a learnable codebook."""
+
+    @staticmethod
+    def forward(ctx, x, codes, metric, temperature, n_positions, pos_div, live_codes, live_packed, backend):
+        lse2, table, packed = backend.diversity_table(x.detach(), codes.detach(), metric=metric, temperature=temperature,
+                                                      n_positions=n_positions, pos_div=pos_div)
+        total = None
+        for rows in _position_chunks(table):  # (one chunk unless [N, K] itself outgrows CHUNK_BYTES)
+            avg = table[rows, :codes.shape[1]]
+            ent = (-avg * avg.clamp(min=1e-5).log()).sum(-1)  # utils/general.py:25-30
+            total = ent.sum() if total is None else total + ent.sum()
+        ctx.save_for_backward(x, codes, lse2, table, packed)
+        ctx.args = (metric, temperature, n_positions, pos_div)
+        ctx.live_codes, ctx.live_packed, ctx.backend = live_codes, live_packed, backend
+        return -total / n_positions
+
+    @staticmethod
+    def backward(ctx, g):
+        x, codes, lse2, table, packed = ctx.saved_tensors
+        metric, temperature, n_positions, pos_div = ctx.args
+        count = x.shape[0] * x.shape[1] // n_positions  # C: rows per position over all heads
+        u, _ = diversity_upstream(table, g, n_positions, count, codes.shape[1])
+        live, live_packed = ctx.live_codes, ctx.live_packed
+        if live is not None:  # read here, at backward time: the codes as they are NOW and their image
+            live = live.detach()
+            live_packed = live_packed() if callable(live_packed) else live_packed
+        gx = ctx.backend.diversity_backward(x.detach(), codes.detach(), lse2, u.contiguous(), metric=metric, temperature=temperature,
+                                            n_positions=n_positions, pos_div=pos_div, packed=packed, live=live,
+                                            live_packed=live_packed)
+        return gx, None, None, None, None, None, None, None, None
+
+
+def _diversity_fused_backend(x, codes, n_positions, pos_div):
+    """The backend whose fused sweeps take this call, or None: the chunked path."""
+    if os.environ.get("VQ_DIVERSITY_NO_FUSED"):  # (read per call: tests and A/B runs compare both paths)
+        return None
+    backend = search.get_backend()
+    if not (hasattr(backend, "diversity_table") and hasattr(backend, "diversity_backward")):
+        return None
+    if not x.is_cuda or (torch.is_grad_enabled() and codes.requires_grad):
+        return None
+    h, m, d = x.shape
+    if pos_div is None or n_positions <= 0 or m == 0 or m % (n_positions * pos_div):
+        return None
+    if not diversity_runs_fused(h * m // n_positions, h):
+        return None
+    return backend if backend.diversity_supported(h, m, codes.shape[1], d, n_positions, pos_div) else None
+
+
 def codebook_diversity_loss(x: torch.Tensor, codes: torch.Tensor, metric: int, temperature: float,
-                            position: torch.Tensor, n_positions: int, live_codes=None) -> torch.Tensor:
+                            position: torch.Tensor, n_positions: int, live_codes=None, pos_div=None,
+                            live_packed=None) -> torch.Tensor:
     """-mean_n entropy(avg_prob[n]),  avg_prob[n] = mean over all (head, batch) rows at sequence position n of
     softmax(-similarities * temperature)   -- vector_quantize_pytorch.py:324-334 (sign and all).
 
-    x [H, M, D]; position [M] int64 = sequence position of each row.  Chunked over positions: every chunk holds all
-    rows of a set of positions, so its entropies are complete and the loss is a plain sum over chunks.
+    x [H, M, D]; position [M] int64 = sequence position of each row, or a callable that returns it (only the chunked path
+    asks).  ``pos_div``: position[m] == (m // pos_div) % n_positions -- with it the fused sweeps run (_DiversityFn) wherever
+    they reach: D <= 256, a codebook that needs no gradient, diversity_runs_fused(); VQ_DIVERSITY_NO_FUSED=1 keeps the
+    chunked path.  ``live_packed``: as in cross_entropy_to_codes.
+    Chunked over positions otherwise: every chunk holds all rows of a set of positions, so its entropies are complete and
+    the loss is a plain sum over chunks.
     """
+    backend = _diversity_fused_backend(x, codes, n_positions, pos_div)
+    if backend is not None:
+        return _DiversityFn.apply(x.float(), codes, metric, float(temperature), int(n_positions), int(pos_div), live_codes,
+                                  live_packed, backend)
+    if callable(position):
+        position = position()
     h, m, _ = x.shape
     k = codes.shape[1]
     counts = torch.bincount(position, minlength=n_positions)

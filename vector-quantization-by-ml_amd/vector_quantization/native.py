@@ -97,6 +97,11 @@ _SIGNATURES = {
                                                 _i64, _i64, _vp)),
     "vq_gumbel_reinmax_backward_codes_f32": (_int, (_ap, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                                     _vp)),
+    "vq_diversity_workspace_bytes": (_i64, (_int, _i64, _int, _int, _int)),
+    "vq_diversity_stats_f32": (_int, (_ap, _f32, _vp, _vp)),
+    "vq_diversity_accumulate_f32": (_int, (_ap, _f32, _int, _int, _vp, _vp, _vp, _i64, _vp)),
+    "vq_diversity_delta_f32": (_int, (_ap, _f32, _int, _int, _vp, _vp, _vp, _vp)),
+    "vq_diversity_backward_x_f32": (_int, (_ap, _vp, _i64, _f32, _int, _int, _vp, _vp, _vp, _vp, _i64, _i64, _vp)),
     "vq_gumbel_sample_f32": (_int, (_ap, _f32, _vp, _vp)),
     "vq_gumbel_noise_f32": (_int, (_vp, _int, _i64, _int, _vp, _vp, _vp)),
     "vq_lfq_workspace_bytes": (_i64, (_i64, _i64, _int, _int)),
@@ -822,6 +827,96 @@ def gumbel_reinmax_backward_codes(x: torch.Tensor, cb: torch.Tensor, g: torch.Te
           stats[1].data_ptr(), stats[2].data_ptr(), col.data_ptr(), e.data_ptr(), gc.data_ptr(), workspace.data_ptr(),
           workspace.numel() * workspace.element_size())
     return gc
+
+
+DIVERSITY_MAX_DIM = 256  # vq_diversity_*_f32: rows of one launch
+
+
+def diversity_supported(H: int, M: int, K: int, D: int, N: int, pos_div: int = 1) -> bool:
+    """The four vq_diversity_*_f32 sweeps take this shape (rows of at most 256 dims, whole groups of N * pos_div rows, a
+    position-major row image below 2 GiB)."""
+    if D > DIVERSITY_MAX_DIM or M <= 0 or N <= 0 or pos_div <= 0 or M % (N * pos_div):
+        return False
+    return int(load().vq_diversity_workspace_bytes(H, M, K, D, N)) > 0
+
+
+def _diversity_args(x, cb, metric, packed, n_positions, pos_div):
+    a = _aux_args(x, cb, metric, packed, 0)
+    assert a.D <= DIVERSITY_MAX_DIM and n_positions > 0 and pos_div > 0 and a.M % (n_positions * pos_div) == 0
+    return a
+
+
+def _check_position_table(t, n_positions: int, K: int, device):
+    stride = int(load().vq_gumbel_row_stride(K))
+    assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (n_positions, stride) and t.device == device
+
+
+def diversity_stats(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, temperature: float = 1.0,
+                    packed: torch.Tensor | None = None) -> torch.Tensor:
+    """Row statistics of the codebook diversity loss: x [H, M, D] (strided rows ok), cb [H, K, D] -> lse2
+    [H, vq_gumbel_row_stride(M)] (columns past M unused) = log2 sum_k exp2(-temperature * sim * log2 e)."""
+    a = _diversity_args(x, cb, metric, packed, 1, 1)
+    lse2 = torch.empty((a.H, int(load().vq_gumbel_row_stride(a.M))), dtype=torch.float32, device=x.device)
+    _call("vq_diversity_stats_f32", x.device, a, float(temperature), lse2.data_ptr())
+    return lse2
+
+
+def diversity_accumulate(x: torch.Tensor, cb: torch.Tensor, lse2: torch.Tensor, *, metric: int = EUCLID,
+                         temperature: float = 1.0, n_positions: int, pos_div: int = 1) -> torch.Tensor:
+    """The position table of the diversity loss -> A [n_positions, vq_gumbel_row_stride(K)] (0 past K): A[n, k] = mean over
+    the heads and the rows m with (m // pos_div) % n_positions == n of softmax_k(-temperature * sim).  Atomics-free:
+    bit-identical from run to run on one device."""
+    _require_gpu(x, cb, lse2)
+    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous()
+    H, M, D = x.shape
+    K = cb.shape[1]
+    assert cb.shape[0] == H and cb.shape[2] == D and diversity_supported(H, M, K, D, n_positions, pos_div)
+    _check_stat_arrays(x, M, lse2)
+    a = _vq_args(x, cb, metric=metric)
+    ws, ws_bytes = _sized_workspace("vq_diversity_workspace_bytes", x.device, H, M, K, D, n_positions)
+    A = torch.empty((n_positions, int(load().vq_gumbel_row_stride(K))), dtype=torch.float32, device=x.device)
+    _call("vq_diversity_accumulate_f32", x.device, a, float(temperature), n_positions, pos_div, lse2.data_ptr(), A.data_ptr(),
+          ws.data_ptr(), ws_bytes)
+    return A
+
+
+def diversity_delta(x: torch.Tensor, cb: torch.Tensor, lse2: torch.Tensor, U: torch.Tensor, *, metric: int = EUCLID,
+                    temperature: float = 1.0, n_positions: int, pos_div: int = 1,
+                    packed: torch.Tensor | None = None) -> torch.Tensor:
+    """delta [H, vq_gumbel_row_stride(M)]: delta[h, m] = sum_k softmax_k(-temperature * sim)[h, m, k] * U[position of m, k];
+    U [n_positions, vq_gumbel_row_stride(K)], finite past K."""
+    a = _diversity_args(x, cb, metric, packed, n_positions, pos_div)
+    _check_stat_arrays(x, a.M, lse2)
+    _check_position_table(U, n_positions, a.K, x.device)
+    delta = torch.empty_like(lse2)
+    _call("vq_diversity_delta_f32", x.device, a, float(temperature), n_positions, pos_div, lse2.data_ptr(), U.data_ptr(),
+          delta.data_ptr())
+    return delta
+
+
+def diversity_backward_x(x: torch.Tensor, cb: torch.Tensor, lse2: torch.Tensor, delta: torch.Tensor, U: torch.Tensor, *,
+                         metric: int = EUCLID, temperature: float = 1.0, n_positions: int, pos_div: int = 1,
+                         packed: torch.Tensor | None = None, live: torch.Tensor | None = None,
+                         live_packed: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """d/dx of the diversity loss, one fused sweep -> gx [H, M, D] (``out``: a destination with strided rows).  U carries the
+    upstream gradient.  ``live`` [H, K, D]: the codes as they are NOW when they were rewritten since ``cb`` was searched:
+    the weights come from ``cb``, what they are multiplied with from ``live`` (``live_packed``: its image, packed here when
+    None)."""
+    a = _diversity_args(x, cb, metric, packed, n_positions, pos_div)
+    _check_stat_arrays(x, a.M, lse2, delta)
+    _check_position_table(U, n_positions, a.K, x.device)
+    out, o_rs, o_hs = _grad_x_out(x, out)
+    lp, lp_hs = None, 0
+    if live is not None or live_packed is not None:
+        if live is not None:
+            _require_gpu(live)
+            assert live.dtype == torch.float32 and tuple(live.shape) == (a.H, a.K, a.D) and live.device == x.device
+            live = live.contiguous()
+        live_packed = _packed_image(live, metric, live_packed, a.H, a.K, a.D, x.device)
+        lp, lp_hs = live_packed.data_ptr(), live_packed.shape[-1]
+    _call("vq_diversity_backward_x_f32", x.device, a, lp, lp_hs, float(temperature), n_positions, pos_div, lse2.data_ptr(),
+          delta.data_ptr(), U.data_ptr(), out.data_ptr(), o_rs, o_hs)
+    return out
 
 
 E_UNSUPPORTED = -2  # VQ_E_UNSUPPORTED

@@ -478,10 +478,14 @@ class VectorQuantize(nn.Module):
                 commit_loss = losses.cross_entropy_to_codes(flat, codes, target, cb.metric, live, stats=ce_stats,
                                                             live_packed=live_packed)
             if training and self.has_codebook_diversity_loss and not return_loss:
-                row_id = torch.arange(flat.shape[1], device=flat.device)
-                position = (row_id % n) if (self.separate_codebook_per_head or heads == 1) else (row_id // heads) % n
+                # the sequence position of row m is (m // pos_div) % n; the fused sweeps take the rule, the chunked path the tensor
+                pos_div = 1 if (self.separate_codebook_per_head or heads == 1) else heads
+
+                def position():
+                    return (torch.arange(flat.shape[1], device=flat.device) // pos_div) % n
+
                 diversity_loss = losses.codebook_diversity_loss(flat, codes, cb.metric, self.codebook_diversity_temperature,
-                                                                position, n, live)
+                                                                position, n, live, pos_div=pos_div, live_packed=live_packed)
                 loss = loss + diversity_loss * self.codebook_diversity_loss_weight
         if want_loss:
             loss = loss + commit_loss * self.commitment_weight

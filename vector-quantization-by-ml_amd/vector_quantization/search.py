@@ -155,6 +155,32 @@ class _NativeBackend:
 
 
     @staticmethod
+    def diversity_supported(H, M, K, D, n_positions, pos_div):
+        """The fused sweeps of the codebook diversity loss take this shape (native.diversity_supported)."""
+        return native.diversity_supported(H, M, K, D, n_positions, pos_div)
+
+    @staticmethod
+    def diversity_table(x, cb, *, metric, temperature, n_positions, pos_div):
+        """Forward of the fused diversity loss: -> (lse2 [H, stride(M)], A [n_positions, stride(K)], the packed codes) from
+        vq_diversity_stats_f32 and vq_diversity_accumulate_f32; A[n] = mean softmax(-temperature * sim) over the rows (of all
+        heads) at sequence position n = (row // pos_div) % n_positions."""
+        cb = cb.contiguous()
+        packed = native.pack_codebooks(cb, metric)
+        lse2 = native.diversity_stats(x, cb, metric=metric, temperature=temperature, packed=packed)
+        table = native.diversity_accumulate(x, cb, lse2, metric=metric, temperature=temperature, n_positions=n_positions,
+                                            pos_div=pos_div)
+        return lse2, table, packed
+
+    @staticmethod
+    def diversity_backward(x, cb, lse2, u, *, metric, temperature, n_positions, pos_div, packed=None, live=None, live_packed=None):
+        """Backward of the fused diversity loss with respect to the rows: vq_diversity_delta_f32 + vq_diversity_backward_x_f32;
+        ``u`` [n_positions, stride(K)] carries the upstream gradient, ``live`` / ``live_packed`` as in cross_entropy_backward."""
+        cb = cb.contiguous()
+        kw = dict(metric=metric, temperature=temperature, n_positions=n_positions, pos_div=pos_div, packed=packed)
+        delta = native.diversity_delta(x, cb, lse2, u, **kw)
+        return native.diversity_backward_x(x, cb, lse2, delta, u, live=live, live_packed=live_packed, **kw)
+
+    @staticmethod
     def sample_codes(x, cb, *, metric, tau, seed, packed=None):
         """Gumbel-max sampling of the code in one sweep (vq_gumbel_sample_f32): -> idx [H, M] int64 = argmax_k of
         similarity * tau + Gumbel noise, the noise counter-based from ``seed`` (two int64 words on the device,
