@@ -91,7 +91,28 @@ typedef struct vq_args {
     /* scratch */
     void *workspace;       /* >= vq_workspace_bytes() bytes, 16-byte aligned                        */
     int64_t workspace_bytes;
+    /* optional, vq_quantize_f32 only: the caller-cached screen image of `packed` (vq_pack_screen_image_f32) and its
+       vq_screen_image_bytes(); NULL and 0: the call builds its own in the workspace.  Ignored by calls that take
+       another kernel; a byte count that does not match is VQ_E_BADARG.                               */
+    void *screen;
+    int64_t screen_bytes;
 } vq_args;
+
+/*
+ * The screen image: what the bf16x3 screened sweep reads instead of the fp32 packed image (plain Euclid inference calls of
+ * 128 < D <= 256 with 1 024 <= Kp <= 3 072 codes and enough rows to fill the chip), followed by a small control block that
+ * the call's kernels share.  It is a pure function of the packed image, so a caller whose codebook stays put between calls
+ * builds it once and hands it over in vq_args.screen: the call then launches no pack kernel.
+ *   vq_screen_image_bytes: bytes of the H images plus the control block; 0 where no screened sweep exists for the shape
+ *     (host arithmetic only).
+ *   vq_pack_screen_image_f32: builds the images of `packed` (head stride pk_hs floats) into `screen` (16-byte aligned,
+ *     screen_bytes == vq_screen_image_bytes(...)) and zeroes the control block.
+ * One image serves one call at a time: calls that share it must be ordered on one stream (the control block holds the
+ * call's counts; every call leaves it zeroed for the next).
+ */
+int64_t vq_screen_image_bytes(int H, int K, int D, int metric);
+int vq_pack_screen_image_f32(const float *packed, int H, int64_t pk_hs, int K, int D, int metric, void *screen,
+                             int64_t screen_bytes, void *stream);
 
 /* Bytes of scratch vq_quantize_f32 / vq_search_keys_f32 may need for (H, M, Q): packed keys (+ 8 MiB of key planes for K
  * splits), squared-error partials and -- residual stacks (Q > 1) of more than 32 768 rows -- 64 MiB for the residual rows of a

@@ -161,6 +161,7 @@ struct SearchChoice {
     int waves;      // waves per workgroup of the chosen kernel
     bool train;     // kPersist: the deferred copy does the straight-through / squared-error arithmetic
     bool screened;  // kPersist: the bf16x3 screened sweep + the second pass over its listed rows
+    bool cached;    // screened: the images and the control block are the caller's (vq_args.screen), no pack kernel runs
 };
 }  // namespace vqi
 namespace {
@@ -188,15 +189,23 @@ bool use_pair512() {
     return !off;
 }
 
-// the screened sweep's share of the workspace: [bf16x3 images][two counts, 256 B][rows for the second pass: one uint32 per row of the
-// call, the full-search list from the front and the rescore list from the back]
-inline long long screen_bytes(int H, long long M, int ntiles) { return (long long)H * scr_image_bytes(ntiles) + 256 + 4ll * H * M; }
+// the screened sweep's share of the workspace: [bf16x3 images][control block, kScrCtrlBytes][rows for the second pass: one uint32 per
+// row of the call, the full-search list from the front and the rescore list from the back].  A caller-cached screen image
+// (vq_args.screen, vq_screen_image_bytes) is the first two; the row list, which needs no initialisation, stays in the workspace.
+inline long long screen_list_bytes(int H, long long M) { return 4ll * H * M; }
+inline long long screen_image_bytes(int H, int ntiles) { return (long long)H * scr_image_bytes(ntiles) + kScrCtrlBytes; }
+inline long long screen_bytes(int H, long long M, int ntiles) { return screen_image_bytes(H, ntiles) + screen_list_bytes(H, M); }
+// sub-tiles per sweep for which the screened (and the persistent) kernel exists: one row per sub-tile needs 32; beyond ~100 the
+// finalize is < 1 % of a block
+constexpr int kPersistMinSub = 32, kPersistMaxSub = 96;
 
 // In order of precedence.  `waves` is the one-block kernel's workgroup size (the caller's plan); `scr_room` the bytes of
-// workspace the screened sweep may use (0: none).  Only a whole fused call (no K split, kModeFused) can be taken by the
+// workspace the screened sweep may use (0: none), `scr_cached` whether the caller brought the images (then only the row list
+// has to fit the room).  Only a whole fused call (no K split, kModeFused) can be taken by the
 // resident or the persistent kernel: keys-mode searches and the slices of wide rows get wave pairs or one block.
-SearchChoice choose_search(int DP, int waves, const SearchParams &p, int H, int splits, int metric, int cus, long long scr_room = 0) {
-    SearchChoice c = {kOneBlock, waves, false, false};
+SearchChoice choose_search(int DP, int waves, const SearchParams &p, int H, int splits, int metric, int cus, long long scr_room = 0,
+                           bool scr_cached = false) {
+    SearchChoice c = {kOneBlock, waves, false, false, false};
     const bool whole_call = splits == 1 && p.mode == kModeFused;
     // Small codebook whose image fits the LDS beside the row slabs (resident_image_for set p.res_img_floats)
     if (whole_call && p.res_img_floats > 0 && (DP == 32 || DP == 64 || DP == 128)) {
@@ -214,7 +223,7 @@ SearchChoice choose_search(int DP, int waves, const SearchParams &p, int H, int 
     if (whole_call && !no_persist && DP == 256 && waves == 8 && p.Q == 1 && !p.lse && !p.xt && p.vec_x && p.vec_fin && p.D % 4 == 0 &&
         (p.out || p.loss_part) &&                                // (else nothing to copy)
         !(train && getenv("VQ_NO_PERSIST_TRAIN") != nullptr) &&
-        nsub >= 32 && nsub <= 96 &&                              // one row per sub-tile needs 32; beyond ~100 the finalize is < 1 % of a block
+        nsub >= kPersistMinSub && nsub <= kPersistMaxSub &&
         one_block_grid_x(p.M, waves) * H >= 2ll * cus) {         // at least two blocks per resident workgroup
         c.kind = kPersist;
         c.train = train;
@@ -222,7 +231,9 @@ SearchChoice choose_search(int DP, int waves, const SearchParams &p, int H, int 
         // images and row list fit the room.  VQ_NO_SCREEN in the environment keeps the fp32 sweep (read per call: tests
         // compare both in one process).
         c.screened = !train && metric == VQ_METRIC_EUCLID && !p.best && getenv("VQ_NO_SCREEN") == nullptr &&
-                     screen_bytes(H, p.M, p.ntiles) <= scr_room && scr_image_bytes(p.ntiles) < (1ll << 31) && (long long)H * p.M < (1ll << 31);
+                     (scr_cached ? screen_list_bytes(H, p.M) : screen_bytes(H, p.M, p.ntiles)) <= scr_room &&
+                     scr_image_bytes(p.ntiles) < (1ll << 31) && (long long)H * p.M < (1ll << 31);
+        c.cached = c.screened && scr_cached;
         return c;
     }
     // The wave-pair kernel runs wave B one tile behind wave A: one extra step per sweep.  Worth it from 8 tiles per sweep on.
@@ -293,24 +304,34 @@ int launch_pair_any(const SearchParams &p, int H, int splits, int metric, hipStr
 }
 #endif
 
+// the bf16x3 images of H codebooks from their fp32 packed images, and a zeroed control block behind them (a template, so
+// that only the build part that launches it instantiates the kernel)
+template <int DP>
+int launch_pack_scr(const float *packed, long long pk_hs, int K, int ntiles, int H, char *img, long long img_hs, unsigned *ctrl, hipStream_t s) {
+    return launch<vq_pack_scr_kernel<DP>>(dim3((unsigned)ntiles, (unsigned)H), dim3(256), 0, s, "vq_pack_scr launch", packed, pk_hs, K, ntiles, img,
+                                           img_hs, ctrl);
+}
+
 template <int METRIC, bool TRAIN = false, bool SCREEN = false>
-int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s) {
+int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s, bool scr_cached = false) {
     using G = Geo<256, 8>;
     const size_t lds = (size_t)G::MAIN_FLOATS_S * 4 + 2 * 8 * 32 * 4;
-    if constexpr (SCREEN) {  // the bf16x3 images of this call's codebooks, from their fp32 packed images
-        if (int rc = launch<vq_pack_scr_kernel<256>>(dim3((unsigned)p.ntiles, (unsigned)H), dim3(256), 0, s, "vq_pack_scr launch", p.packed, p.pk_hs,
-                                                     p.K, p.ntiles, (char *)p.scr, p.scr_hs, p.scr_count))
-            return rc;
+    if constexpr (SCREEN) {  // this call's images, unless the caller brought them (then the control block is clean: see the second pass)
+        if (!scr_cached)
+            if (int rc = launch_pack_scr<256>(p.packed, p.pk_hs, p.K, p.ntiles, H, (char *)p.scr, p.scr_hs, p.scr_count, s)) return rc;
     }
     if (int rc = launch<vq_search_persist<256, 8, METRIC, TRAIN, SCREEN>, kBigLds>(dim3((unsigned)persist_grid_x(p.M, H, cus), (unsigned)H, 1), dim3(512),
                                                                                    lds, s, "vq_search_persist launch", p))
         return rc;
     if constexpr (SCREEN) {
         // second pass: the rows of both lists, in stream order behind the sweep.  One workgroup per CU: the few full searches
-        // of a usual call (tens) take one round, the other workgroups share the rescore batches, and a workgroup that finds
-        // nothing for itself ends after one load of the counts.
+        // of a usual call (tens) are split over several workgroups each, the other workgroups share the rescore batches, and
+        // every workgroup stays for the exit ticket that leaves the control block clean (vq_resolve_rows_kernel).
+        // VQ_RESOLVE_NO_SPLIT in the environment: no split of the full searches (A/B measurements and tests; read per call like
+        // VQ_NO_STAGGER)
+        const int flags = getenv("VQ_RESOLVE_NO_SPLIT") ? kResolveNoSplit : 0;
         return launch<vq_resolve_rows_kernel<256>, kBigLds>(dim3((unsigned)(cus > 0 ? cus : 1)), dim3(kResolveWaves * 64), resolve_lds_bytes<256>(), s,
-                                                            "vq_resolve_rows launch", p, H);
+                                                            "vq_resolve_rows launch", p, H, flags);
     }
     return 0;
 }
@@ -515,6 +536,7 @@ VQ_DECLARE_GUMBEL_PARTS(256)
 #undef VQ_DECLARE_GUMBEL_PARTS
 int part_pair(const SearchParams &p, int H, int splits, int metric, hipStream_t s);
 int part_persist(const SearchChoice &c, const SearchParams &p, int H, int cus, int metric, hipStream_t s);
+int part_pack_scr(const float *packed, long long pk_hs, int K, int ntiles, int H, char *img, long long img_hs, unsigned *ctrl, hipStream_t s);
 #define VQ_DECLARE_PARTS(DP)                                                                                         \
     template <> int part_search<DP>(int waves, const SearchParams &p, int H, int splits, int metric, hipStream_t s); \
     template <> int part_wide<DP>(int wide, const SearchParams &p, int H, int splits, int metric, hipStream_t s);    \
@@ -554,11 +576,14 @@ VQ_DEFINE_RESIDENT_PART(128)
 #if VQ_OWN(3)
 VQ_DEFINE_SEARCH_PART(256, 4)
 int part_persist(const SearchChoice &c, const SearchParams &p, int H, int cus, int metric, hipStream_t s) {
-    if (c.screened) return launch_persist_t<VQ_METRIC_EUCLID, false, true>(p, H, cus, s);  // (choose_search: Euclid inference calls)
+    if (c.screened) return launch_persist_t<VQ_METRIC_EUCLID, false, true>(p, H, cus, s, c.cached);  // (choose_search: Euclid inference calls)
     return with_metric(metric, [&](auto m) {
         constexpr int ME = decltype(m)::value;
         return c.train ? launch_persist_t<ME, true>(p, H, cus, s) : launch_persist_t<ME>(p, H, cus, s);
     });
+}
+int part_pack_scr(const float *packed, long long pk_hs, int K, int ntiles, int H, char *img, long long img_hs, unsigned *ctrl, hipStream_t s) {
+    return launch_pack_scr<256>(packed, pk_hs, K, ntiles, H, img, img_hs, ctrl, s);
 }
 #endif
 #if VQ_OWN(4)
@@ -667,14 +692,16 @@ bool vec4_ok(const void *p, std::initializer_list<long long> strides, unsigned a
 }
 
 // The screened sweep's bf16x3 images are built per call into the key area of the workspace, which a fused call does not use,
-// and behind them the two lists of rows for the second pass (vq_resolve_rows_kernel): the layout of screen_bytes.
-void set_screen_image(SearchParams &p, const vq_args *a) {
+// and behind them the control block and the two lists of rows for the second pass (vq_resolve_rows_kernel): the layout of
+// screen_bytes.  With the caller's image (`cached`: vq_args.screen, checked by check_screen) only the lists are in the workspace.
+void set_screen_image(SearchParams &p, const vq_args *a, bool cached) {
     const long long img = scr_image_bytes(p.ntiles);
-    p.scr = (const float *)a->workspace;
+    char *base = (char *)(cached ? a->screen : a->workspace);
+    p.scr = (const float *)base;
     p.scr_hs = img;
     p.scr_bytes = (unsigned)img;
-    p.scr_count = (unsigned *)((char *)a->workspace + (long long)a->H * img);
-    p.scr_list = p.scr_count + 64;
+    p.scr_count = (unsigned *)(base + (long long)a->H * img);
+    p.scr_list = cached ? (unsigned *)a->workspace : p.scr_count + kScrCtrlBytes / 4;
     // VQ_NO_STAGGER in the environment: all eight waves run the sweep's epilogue at the same place (A/B measurements and
     // tests; read per call like VQ_NO_SCREEN)
     p.scr_stagger = getenv("VQ_NO_STAGGER") == nullptr;
@@ -725,6 +752,15 @@ int launch_aux(int DP, const AuxParams &p, int H, int metric, int mode, hipStrea
 int launch_wide(int wide, int DP, const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
     return with_padded_dim(DP, [&](auto dp) { return vqi::part_wide<decltype(dp)::value>(wide, p, H, splits, metric, s); },
                            [] { return fail(VQ_E_UNSUPPORTED, "vq_search: unsupported padded dim"); });
+}
+
+// a caller-cached screen image must be THE image of this call's codebooks' shape: anything else is an argument error
+int check_screen(const vq_args *a) {
+    if (!a->screen && a->screen_bytes == 0) return 0;
+    if (!a->screen || a->screen_bytes <= 0 || a->screen_bytes != vq_screen_image_bytes(a->H, a->K, a->D, a->metric))
+        return fail(VQ_E_BADARG, "vq_quantize: screen / screen_bytes do not match vq_screen_image_bytes(H, K, D, metric)");
+    if (!aligned16(a->screen)) return fail(VQ_E_BADARG, "vq_quantize: screen is not 16-byte aligned");
+    return 0;
 }
 
 int check_common(const vq_args *a) {
@@ -1202,6 +1238,25 @@ int64_t vq_workspace_bytes(int H, int64_t M, int Q) {
     return ws_core_bytes(H, M, Q) + residual_tail_room(H, M, Q);
 }
 
+int64_t vq_screen_image_bytes(int H, int K, int D, int metric) {
+    if (H <= 0 || K <= 0 || D <= 0 || metric != VQ_METRIC_EUCLID || padded_dim(D) != 256) return 0;
+    const int ntiles = (K + kTileCodes * sub_tiles(256) - 1) / (kTileCodes * sub_tiles(256)), nsub = ntiles * sub_tiles(256);
+    if (nsub < kPersistMinSub || nsub > kPersistMaxSub) return 0;
+    return screen_image_bytes(H, ntiles);
+}
+
+int vq_pack_screen_image_f32(const float *packed, int H, int64_t pk_hs, int K, int D, int metric, void *screen, int64_t screen_bytes,
+                             void *stream) {
+    const int64_t need = vq_screen_image_bytes(H, K, D, metric);
+    if (need == 0) return fail(VQ_E_UNSUPPORTED, "vq_pack_screen_image: no screened sweep for this shape (see vq_screen_image_bytes)");
+    if (!packed || !screen || screen_bytes != need || !aligned16(packed) || !aligned16(screen) || pk_hs < vq_packed_floats(K, D))
+        return fail(VQ_E_BADARG, "vq_pack_screen_image: bad argument");
+    const int ntiles = (K + kTileCodes - 1) / kTileCodes;  // (sub_tiles(256) == 1)
+    const long long img = scr_image_bytes(ntiles);
+    return vqi::part_pack_scr(packed, pk_hs, K, ntiles, H, (char *)screen, img, (unsigned *)((char *)screen + (long long)H * img),
+                              (hipStream_t)stream);
+}
+
 int vq_pack_codebooks_f32(const float *cb, int n_codebooks, int64_t cb_stride, int K, int D, int metric, float *packed,
                           void *stream) {
     if (!cb || !packed || n_codebooks <= 0 || K <= 0 || D <= 0) return fail(VQ_E_BADARG, "vq_pack: bad argument");
@@ -1392,6 +1447,8 @@ static int residual_tail_staged(const vq_args *a, long long m1, void *stream) {
 static int quantize_impl(const vq_args *a, void *stream, float *lse) {
     int rc = check_common(a);
     if (rc) return rc;
+    rc = check_screen(a);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (lse && (a->Q != 1 || padded_dim(a->D) == 0 || (a->flags & (VQ_F_FORCE_SIMPLE | VQ_F_FORCE_SPLIT))))
         return fail(VQ_E_UNSUPPORTED, "vq_quantize_lse: needs Q == 1, D <= 512 and the fused MFMA path");
@@ -1502,8 +1559,9 @@ static int quantize_impl(const vq_args *a, void *stream, float *lse) {
             p.res_nbuf = (DP < 128 && full <= 160 * 1024) ? DP / 16 : 1;
         }
         // the one decision which kernel runs this call: the screen images, the launch and the partials' count all follow it
-        const SearchChoice c = choose_search(DP, waves, p, a->H, 1, a->metric, cus, /*scr_room=*/ws_keys_bytes(a->H, a->M));
-        if (c.screened) set_screen_image(p, a);
+        const SearchChoice c = choose_search(DP, waves, p, a->H, 1, a->metric, cus, /*scr_room=*/ws_keys_bytes(a->H, a->M),
+                                             /*scr_cached=*/a->screen != nullptr);
+        if (c.screened) set_screen_image(p, a, c.cached);
         rc = launch_search(c, DP, p, a->H, 1, a->metric, cus, s);
         if (rc || !a->sq_err) return rc;
         const long long per_head = loss_partials_per_head(c, a->M, a->H, cus);

@@ -75,6 +75,18 @@ constexpr int kScrCnOffset = kTileCodes * kScrRowBytes;
 #endif
 constexpr int kScrLateGroup = VQ_SCR_LATE_GROUP;
 inline long long scr_image_bytes(int ntiles) { return ((long long)ntiles * kScrTileBytes + 4ll * ntiles + 255) / 256 * 256; }
+#include "vq_resolve_plan.h"
+// The control block behind the images (SearchParams::scr_count points at it), 32-bit words: [0] rows on the full-search list,
+// [1] rows on the rescore list, [2] exit ticket of the second pass, [4] and [5] the two counts of the previous call (no kernel
+// reads them: tests and diagnostics do); from word kScrRowTicketWord on one ticket per split full-search row, and from
+// kScrSlotWord on kResolveMaxSplit 8-byte result slots for each (vq_resolve_plan.h).  vq_pack_scr_kernel zeroes the block; the
+// second pass leaves words 0..2 and every ticket zero again (vq_resolve_rows_kernel), so an image that outlives the call needs
+// no per-call zeroing.
+constexpr int kScrCtrlBytes = 16384;
+constexpr int kScrTicketWord = 2, kScrLastCountsWord = 4, kScrRowTicketWord = 8;
+constexpr int kScrSlotWord = kScrRowTicketWord + (int)kResolveMaxSplitRows;
+static_assert(kScrSlotWord % 2 == 0 && (kScrSlotWord + 2 * (int)(kResolveMaxSplitRows * kResolveMaxSplit)) * 4 <= kScrCtrlBytes,
+              "8-byte slots, inside the block");
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
@@ -90,13 +102,18 @@ __device__ __forceinline__ void split_bf16x2(const f32x8 &v, bf16x8 &hi, bf16x8 
 // the padding rows).  Per 32-code tile: row c at c * 1040 bytes, for each group s of 16 dims hi[16s .. 16s+7], hi[16s+8 ..
 // 16s+15], lo[16s ..], lo[16s+8 ..] (16 B each: one ds_read_b128 is one MFMA's A fragment), then the 32 |c|^2 of the tile;
 // behind the tiles the maximum |c|^2 of each tile's real codes.  Grid (tiles, heads), 256 threads: 8 per code.
-// One thread also zeroes the counts of the call's two lists of rows for the second pass (vq_resolve_rows_kernel).
+// One workgroup also zeroes the control block `ctrl` (kScrCtrlBytes): the counts of the two lists of rows for the second pass
+// (vq_resolve_rows_kernel) and its exit ticket.
 template <int DP>
 __global__ void __launch_bounds__(256) vq_pack_scr_kernel(const float *__restrict__ packed, long long pk_hs, int K, int ntiles,
-                                                          char *__restrict__ img, long long img_hs, unsigned *__restrict__ list_count) {
+                                                          char *__restrict__ img, long long img_hs, unsigned *__restrict__ ctrl) {
     static_assert(DP == 256, "the screened sweep is built for Dp = 256");
-    // first on the stream in every screened call: both lists of rows for the second pass start empty
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) list_count[0] = list_count[1] = 0u;
+    static_assert(kScrCtrlBytes % (256 * 16) == 0, "whole rounds of 16 B per thread");
+    // ahead of the sweep on the stream: both lists of rows for the second pass start empty
+    if (blockIdx.x == 0 && blockIdx.y == 0) {
+#pragma unroll
+        for (int i = 0; i < kScrCtrlBytes / (256 * 16); ++i) ((uint4 *)ctrl)[i * 256 + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    }
     constexpr int RS = DP + 4;
     const int t = blockIdx.x, c = threadIdx.x >> 3, part = threadIdx.x & 7;
     const int k = t * kTileCodes + c;
@@ -138,7 +155,8 @@ __global__ void __launch_bounds__(256) vq_pack_scr_kernel(const float *__restric
 // 64 codes at a time, one per lane: the k-ordered fmaf chain over the dims, + |x|^2, + |c|^2, clamp_min(0), correctly rounded
 // sqrt; first NaN, else first minimum, then the 6-step butterfly (NaN first, value, index): every lane returns the wave's
 // (bn = a NaN was met, bv, bi).  better_euclid is the order of that rule.  `rowbuf` = the row in LDS (Dp floats, zeros behind
-// D), `xn` = its d-ordered |x|^2 chain.
+// D); its |x|^2 chain in the prologue's order (d-ordered fmaf from 0) runs beside the distance chain of every pass, as in
+// rescore_batch: a second, independent chain in the same loop costs no time, a loop of its own ahead of the first load did.
 // A lane walking its own code row of the packed image reads 16 B of a different cache line than every other lane: 64 tag
 // look-ups per load instruction, 66 k per row at K = 1024, which is what such a search costs (30 us on one CU, measured).
 // So the codes come through `stage` (wave-private LDS, 64 rows of kExStageRow floats), 32 dims at a time: 8 lanes load the
@@ -175,7 +193,7 @@ __device__ __forceinline__ bool better_euclid(bool on, float ov, int oi, bool bn
 }
 template <int DP>
 __device__ __forceinline__ void exact_row_euclid(const float *rowbuf, float *stage, const float *pk, int kbeg, int kend, int lane,
-                                                 float xn, bool &bn, float &bv, int &bi) {
+                                                 bool &bn, float &bv, int &bi) {
     constexpr int RS = DP + 4, CD = kExChunk, SR = kExStageRow, NCH = DP / CD, NL = kExCodes / 8;
     static_assert(DP % CD == 0, "whole chunks");
     bv = __builtin_inff();
@@ -197,7 +215,7 @@ __device__ __forceinline__ void exact_row_euclid(const float *rowbuf, float *sta
 #pragma unroll
         for (int i = 0; i < NL; ++i) g[i] = *(const f32x4 *)(src[i]);
         const float cn = pk[(long long)(ok ? k : kend - 1) * RS + DP];
-        float acc = 0.0f;
+        float acc = 0.0f, xn = 0.0f;
 #pragma clang loop unroll(disable)
         for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
@@ -210,6 +228,14 @@ __device__ __forceinline__ void exact_row_euclid(const float *rowbuf, float *sta
             for (int q = 0; q < CD / 8; ++q) {
                 const f32x4 ce = *(const f32x4 *)(cr + 8 * q), co = *(const f32x4 *)(cr + 8 * q + 4);
                 const f32x4 xa = *(const f32x4 *)(rowbuf + ch * CD + 8 * q), xb = *(const f32x4 *)(rowbuf + ch * CD + 8 * q + 4);
+                xn = fmaf(xa.x, xa.x, xn);
+                xn = fmaf(xa.y, xa.y, xn);
+                xn = fmaf(xa.z, xa.z, xn);
+                xn = fmaf(xa.w, xa.w, xn);
+                xn = fmaf(xb.x, xb.x, xn);
+                xn = fmaf(xb.y, xb.y, xn);
+                xn = fmaf(xb.z, xb.z, xn);
+                xn = fmaf(xb.w, xb.w, xn);
                 acc = exact_chain8(acc, xa, xb, ce, co);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the chunk has been read: the next one may overwrite it
@@ -346,27 +372,58 @@ __device__ __forceinline__ void rescore_batch(const SearchParams &p, unsigned ca
 //    entries per wave.  A full search keeps a workgroup busy for ~20 us, a batch a wave for a few, so the batches are dealt
 //    to the workgroups that have no full-search entry: from the last workgroup downwards, one batch for every such workgroup
 //    before a second wave of any of them gets one.  When every workgroup has a full search to do, all of them share.
+// Few full searches (at most half the grid): the K codes of each row are split over S workgroups, workgroup e * S + s takes
+// slice s of row e (resolve_plan in vq_resolve_plan.h: the one rule for S, the slices' codes and the dealing of the batches).
+// A slice's workgroup publishes its (NaN met, value, index) as ONE 8-byte word in its slot of the control block (agent-scope
+// atomic store), waits for that store (s_waitcnt vmcnt(0)) and adds to the row's ticket (agent-scope); the workgroup whose
+// add returned S - 1 reads the S slots (agent-scope atomic loads), reduces them in slice order by the rule, stores idx and
+// the quantized row and sets the ticket back to 0.  8-byte agent atomics on both sides need no fence.  More rows than that:
+// S = 1, the rows are dealt grid-stride, a workgroup finishes its rows alone, no tickets.
+// The kernel is the last reader of the two counts and leaves them zero for the next call on the image (which may be a cached
+// one that no pack kernel touches again): every workgroup, also one with nothing to do, reads the counts, joins one barrier
+// and then adds to the exit ticket (agent scope).  The workgroup whose add returned gridDim.x - 1 knows that all others have
+// read the counts: when it has finished its own work it copies them to words kScrLastCountsWord, + 1 and zeroes the counts
+// and the ticket.
+// No workgroup ever waits for another (no spin loop, no polling: "the last arriver does the work" is the only step across
+// workgroups), so a defect in these protocols could give a wrong result but never a hang.
+// `flags` (A/B measurements and tests, from the environment per call): kResolveNoSplit = S is 1 whatever the counts
+// (VQ_RESOLVE_NO_SPLIT).
 // Dynamic LDS only (the launcher raises the kernel's dynamic limit to the CU's 160 KiB, which leaves no room for static
 // arrays): [row, Dp floats][8 waves x 64 x kExStageRow floats of code staging][8 waves x kRsEntries x kExStageRow floats of
 // row staging][the waves' winners: 3 x 8 words].
 constexpr int kResolveWaves = 8;
+constexpr int kResolveNoSplit = 1;
+static_assert(kResolveWaves == (int)kResolvePlanWaves && kExCodes == (int)kResolvePassCodes && kRsEntries == (int)kResolveBatchRows,
+              "vq_resolve_plan.h describes this kernel");
 template <int DP>
 constexpr size_t resolve_lds_bytes() {
     return ((size_t)DP + kResolveWaves * (kExCodes + kRsEntries) * kExStageRow + 3 * kResolveWaves) * 4;
 }
+// a slice's result as one word: value bits high, NaN flag and index (< 2^31) low
+__device__ __forceinline__ unsigned long long resolve_slot_pack(bool bn, float bv, int bi) {
+    return ((unsigned long long)__float_as_uint(bv) << 32) | (bn ? 0x80000000u : 0u) | ((unsigned)bi & 0x7FFFFFFFu);
+}
 template <int DP>
-__global__ void __launch_bounds__(kResolveWaves * 64) vq_resolve_rows_kernel(const SearchParams p, int H) {
+__global__ void __launch_bounds__(kResolveWaves * 64) vq_resolve_rows_kernel(const SearchParams p, int H, int flags) {
     constexpr int WAVES = kResolveWaves;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
     const unsigned cap = (unsigned)((long long)H * p.M);  // (choose_search: H M < 2^31, the array holds them all)
-    unsigned count = p.scr_count[0], n1 = p.scr_count[1];
+    unsigned *ctrl = p.scr_count;
+    // (atomic loads: the values stay in registers, nothing reads the words again after the exit ticket below)
+    const unsigned listed0 = __hip_atomic_load(ctrl + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned listed1 = __hip_atomic_load(ctrl + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // The exit ticket is drawn HERE, once every wave of the workgroup holds the counts (the wait, then the barrier), and its
+    // answer is looked at when the workgroup has finished: all that the cleaning workgroup has to know is that nobody will
+    // read the counts any more, and this way the atomic's round trip runs beside the work instead of behind the last wave.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    unsigned exit_ticket = 0u;
+    if (threadIdx.x == 0) exit_ticket = __hip_atomic_fetch_add(ctrl + kScrTicketWord, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned count = listed0, n1 = listed1;
     if (count > cap) count = cap;
     if (n1 > cap - count) n1 = cap - count;
-    // workgroups without a full-search entry, counted from the last one: they share the rescore batches
-    const unsigned nfree = gridDim.x > count ? gridDim.x - count : 0u;
-    const unsigned sharers = nfree ? nfree : gridDim.x, from_last = gridDim.x - 1u - blockIdx.x;
-    const unsigned nbatch = (n1 + kRsEntries - 1) / kRsEntries;
-    if (blockIdx.x >= count && (from_last >= sharers || from_last >= nbatch)) return;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const unsigned grid = gridDim.x, wg = blockIdx.x;
+    const ResolvePlan pl = resolve_plan(count, n1, grid, (unsigned)p.K, !(flags & kResolveNoSplit));  // (workgroup-uniform, the same in all)
     float *rowbuf = smem;
     float *red_v = smem + DP + WAVES * (kExCodes + kRsEntries) * kExStageRow;
     int *red_i = (int *)(red_v + WAVES), *red_n = red_i + WAVES;
@@ -374,29 +431,24 @@ __global__ void __launch_bounds__(kResolveWaves * 64) vq_resolve_rows_kernel(con
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float *stage = smem + DP + wave * (kExCodes * kExStageRow);
     float *xstage = smem + DP + WAVES * (kExCodes * kExStageRow) + wave * (kRsEntries * kExStageRow);
-    const int per = ((p.K + WAVES - 1) / WAVES + kExCodes - 1) / kExCodes * kExCodes;  // codes per wave: whole passes
-    const int kbeg = wave * per < p.K ? wave * per : p.K, kend = kbeg + per < p.K ? kbeg + per : p.K;
-    for (unsigned e = blockIdx.x; e < count; e += gridDim.x) {
+    // rows of this workgroup: slice `s` of row wg / S, or (S == 1) rows wg, wg + grid, ...
+    unsigned e_first, e_step, s;
+    resolve_wg_rows(pl, count, grid, wg, e_first, e_step, s);
+    unsigned kb, ke;
+    resolve_wave_codes((unsigned)p.K, pl.S, s, (unsigned)wave, kb, ke);
+    const int kbeg = (int)kb, kend = (int)ke;
+    for (unsigned e = e_first; e < count; e += e_step) {
         const unsigned ent = p.scr_list[e];
-        if (ent >= cap) continue;  // (workgroup-uniform; never true for a list the sweep wrote)
+        if (ent >= cap) continue;  // (workgroup-uniform, and the same in every slice of the row; never true for a list the sweep wrote)
         const int head = (int)(ent / (unsigned long long)p.M);
         const long long row = (long long)ent - (long long)head * p.M;
         const float *xr = p.x + (long long)head * p.x_hs + row * p.x_rs;
         if (tid < DP) rowbuf[tid] = (tid < p.D) ? xr[tid] : 0.0f;
         __syncthreads();
-        float xn = 0.0f;
-#pragma unroll 16
-        for (int d = 0; d < DP; d += 4) {
-            const f32x4 v = *(const f32x4 *)(rowbuf + d);
-            xn = fmaf(v.x, v.x, xn);
-            xn = fmaf(v.y, v.y, xn);
-            xn = fmaf(v.z, v.z, xn);
-            xn = fmaf(v.w, v.w, xn);
-        }
         bool bn;
         float bv;
         int bi;
-        exact_row_euclid<DP>(rowbuf, stage, p.packed + (long long)head * p.pk_hs, kbeg, kend, lane, xn, bn, bv, bi);
+        exact_row_euclid<DP>(rowbuf, stage, p.packed + (long long)head * p.pk_hs, kbeg, kend, lane, bn, bv, bi);
         if (lane == 0) {
             red_n[wave] = (int)bn;
             red_v[wave] = bv;
@@ -418,19 +470,62 @@ __global__ void __launch_bounds__(kResolveWaves * 64) vq_resolve_rows_kernel(con
                     bi = oi;
                 }
             }
-            if (lane == 0) p.idx[(long long)head * p.idx_hs + row * p.idx_rs] = bi;
-            const int dl = 4 * lane;
-            if (p.out && dl < p.D)  // (the persistent kernel's deferred copy: float4 of natural rows)
-                *(f32x4 *)(p.out + (long long)head * p.out_hs + row * p.out_rs + dl) =
-                    *(const f32x4 *)(p.cb + (long long)head * p.cb_hs + (long long)bi * p.D + dl);
+            bool finish = true;
+            if (pl.S > 1) {  // (e < kResolveMaxSplitRows, s < S <= kResolveMaxSplit: resolve_plan)
+                unsigned long long *slots = (unsigned long long *)(ctrl + kScrSlotWord) + (size_t)e * kResolveMaxSplit;
+                unsigned *ticket = ctrl + kScrRowTicketWord + e;
+                int last = 0;
+                if (lane == 0) {
+                    __hip_atomic_store(slots + s, resolve_slot_pack(bn, bv, bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the slot has left before the ticket is drawn
+                    last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == pl.S - 1u ? 1 : 0;
+                }
+                finish = __shfl(last, 0) != 0;
+                if (finish) {  // every slice of the row has published: lane i reads slot i, the reduction runs in slice order
+                    const unsigned long long mine =
+                        (unsigned)lane < pl.S ? __hip_atomic_load(slots + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+                    const unsigned lo = (unsigned)mine, hi = (unsigned)(mine >> 32);
+                    bn = (__shfl(lo, 0) & 0x80000000u) != 0u;
+                    bv = __uint_as_float(__shfl(hi, 0));
+                    bi = (int)(__shfl(lo, 0) & 0x7FFFFFFFu);
+                    for (unsigned i = 1; i < pl.S; ++i) {
+                        const unsigned olo = __shfl(lo, (int)i), ohi = __shfl(hi, (int)i);
+                        const bool on = (olo & 0x80000000u) != 0u;
+                        const float ov = __uint_as_float(ohi);
+                        const int oi = (int)(olo & 0x7FFFFFFFu);
+                        if (better_euclid(on, ov, oi, bn, bv, bi)) {
+                            bn = on;
+                            bv = ov;
+                            bi = oi;
+                        }
+                    }
+                    if (lane == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (all S adds are in)
+                }
+            }
+            if (finish) {
+                if (lane == 0) p.idx[(long long)head * p.idx_hs + row * p.idx_rs] = bi;
+                const int dl = 4 * lane;
+                if (p.out && dl < p.D)  // (the persistent kernel's deferred copy: float4 of natural rows)
+                    *(f32x4 *)(p.out + (long long)head * p.out_hs + row * p.out_rs + dl) =
+                        *(const f32x4 *)(p.cb + (long long)head * p.cb_hs + (long long)bi * p.D + dl);
+            }
         }
     }
-    // the rescore batches of this wave (no barrier from here on: the staging regions are the wave's own)
-    if (from_last < sharers)
-        for (unsigned b = from_last + (unsigned)wave * sharers; b < nbatch; b += sharers * WAVES)
-            rescore_batch<DP>(p, cap, b * kRsEntries, n1, stage, xstage, lane);
+    // the rescore batches of this wave (no barrier from here to the end of the work: the staging regions are the wave's own)
+    unsigned bfirst, bstride;
+    resolve_wave_batches(pl, grid, wg, (unsigned)wave, bfirst, bstride);
+    for (unsigned b = bfirst; b < pl.nbatch; b += bstride) rescore_batch<DP>(p, cap, b * kRsEntries, n1, stage, xstage, lane);
+    // leave the control block clean: the workgroup that drew the last exit ticket does it (see above)
+    if (tid == 0) {
+        if (exit_ticket == grid - 1u) {
+            __hip_atomic_store(ctrl + kScrLastCountsWord, listed0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(ctrl + kScrLastCountsWord + 1, listed1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(ctrl + 0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(ctrl + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(ctrl + kScrTicketWord, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
-
 
 #ifdef VQ_EXP_SCREEN_COUNT
 __device__ unsigned long long g_scr_rows[3];  // [0] rows listed for the second pass, [1] rows screened, [2] rows rescored

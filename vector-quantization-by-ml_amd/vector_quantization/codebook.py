@@ -210,6 +210,9 @@ class Codebook(nn.Module):
         self._packed = None
         self._packed_key = None
         self._packed_epoch = 0
+        # screen image of `_packed` for the screened sweep, one per stream that runs this module (see screen_codes)
+        self._screen = {}
+        self._screen_key = None
 
     # ------------------------------------------------------------------ helpers
     def _stochastic_requested(self) -> bool:
@@ -246,6 +249,8 @@ class Codebook(nn.Module):
         """Call after changing ``embeddings`` through ``.data`` or a raw pointer (every writer in this package does)."""
         self._packed_epoch += 1
         self._effective = None
+        self._screen = {}
+        self._screen_key = None
 
     def packed_codes(self):
         """Packed image [h, packed_floats] of the codes for the native search (None for backends without one), cached:
@@ -270,6 +275,33 @@ class Codebook(nn.Module):
                 self._packed = backend.pack(self.embeddings.detach().contiguous(), self.metric)
             self._packed_key = key
         return self._packed
+
+    _SCREEN_STREAMS = 4  # images kept: one per stream that ran this module last
+
+    def screen_codes(self):
+        """The screen image of ``packed_codes()`` for inference searches (``backend.pack_screen``), cached like the packed
+        image: an inference forward of an unchanged codebook launches no pack kernel at all.  The image ends in the counts
+        that the kernels of one call share, so two streams that run this module at the same time must not share one: the
+        current stream is part of the key, and the few most recent streams keep theirs.  None: backends without one, affine
+        codebooks (their codes change with every forward), traced or graph-captured forwards (the pack stays a node of the
+        graph, which reads the weights of its own time) and shapes the screened sweep does not take."""
+        backend = search.get_backend()
+        if (not getattr(backend, "uses_packed", False) or not hasattr(backend, "pack_screen") or self.use_affine
+                or torch.compiler.is_compiling() or not self.embeddings.is_cuda or self.metric != search.EUCLID
+                or torch.cuda.is_current_stream_capturing()):
+            return None
+        packed = self.packed_codes()
+        key = self._packed_key
+        if self._screen_key != key:
+            self._screen, self._screen_key = {}, key
+        stream = torch.cuda.current_stream(self.embeddings.device).cuda_stream
+        if stream not in self._screen:
+            h, k, d = self.embeddings.shape
+            while len(self._screen) >= self._SCREEN_STREAMS:
+                self._screen.pop(next(iter(self._screen)))
+            with torch.no_grad():
+                self._screen[stream] = backend.pack_screen(packed, h, k, d, self.metric)
+        return self._screen[stream]
 
     # ------------------------------------------------------------------ affine re-parameterisation
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
@@ -418,9 +450,15 @@ class Codebook(nn.Module):
             codes = codes.clone()
         # (the search sweep emits the log-sum-exp only for rows one launch holds; wider rows leave it to the loss)
         lse_here = want_lse and flat.shape[-1] <= search.LSE_MAX_DIM
-        res = search.quantize_rows(flat, codes[:, None], metric=self.metric, ste=ste, want_sq_err=want_sq_err,
-                                   codebook_grad_from_err=codebook_grad_from_err, out=out, idx=idx, want_lse=lse_here,
-                                   packed=packed)
+        # (the screened sweep takes plain inference searches only: the others would build the image for nothing)
+        screen = self.screen_codes() if not (ste or want_sq_err or want_lse) else None
+        try:
+            res = search.quantize_rows(flat, codes[:, None], metric=self.metric, ste=ste, want_sq_err=want_sq_err,
+                                       codebook_grad_from_err=codebook_grad_from_err, out=out, idx=idx, want_lse=lse_here,
+                                       packed=packed, screen=screen)
+        except Exception:
+            self._screen = {}  # a call that failed may have left its counts behind in the image
+            raise
         out, idx, sq_err = res[:3]
         if want_lse and not lse_here:
             return out, idx[..., 0], sq_err, None
@@ -436,8 +474,12 @@ class Codebook(nn.Module):
 
         g = self.gumbel_params
         with torch.no_grad():
-            _, ind, _ = search.quantize_rows(flat.detach(), codes.detach()[:, None], metric=self.metric, idx=idx,
-                                             packed=packed)
+            try:
+                _, ind, _ = search.quantize_rows(flat.detach(), codes.detach()[:, None], metric=self.metric, idx=idx,
+                                                 packed=packed, screen=self.screen_codes())
+            except Exception:
+                self._screen = {}  # a call that failed may have left its counts behind in the image
+                raise
         ind = ind[..., 0]
         live = None
         if self.ema_update and not frozen:

@@ -47,6 +47,7 @@ class VqArgs(ctypes.Structure):
         ("best", _vp),
         ("sq_err", _vp),
         ("workspace", _vp), ("workspace_bytes", _i64),
+        ("screen", _vp), ("screen_bytes", _i64),
     ]
 
 
@@ -58,6 +59,8 @@ _ap = ctypes.POINTER(VqArgs)  # const vq_args *
 _SIGNATURES = {
     "vq_packed_floats": (_i64, (_int, _int)),
     "vq_pack_codebooks_f32": (_int, (_vp, _int, _i64, _int, _int, _int, _vp, _vp)),
+    "vq_screen_image_bytes": (_i64, (_int, _int, _int, _int)),
+    "vq_pack_screen_image_f32": (_int, (_vp, _int, _i64, _int, _int, _int, _vp, _i64, _vp)),
     "vq_workspace_bytes": (_i64, (_int, _i64, _int)),
     "vq_workspace_bytes_wide": (_i64, (_int, _i64, _int, _int)),
     "vq_quantize_f32": (_int, (_ap, _vp)),
@@ -267,6 +270,26 @@ def pack_codebooks(cb: torch.Tensor, metric: int) -> torch.Tensor:
     return packed
 
 
+def screen_image_bytes(H: int, K: int, D: int, metric: int) -> int:
+    """Bytes of the screen image of H codebooks (vq_screen_image_bytes); 0 where no screened sweep exists for the shape."""
+    return int(load().vq_screen_image_bytes(int(H), int(K), int(D), int(metric)))
+
+
+def pack_screen(packed: torch.Tensor, H: int, K: int, D: int, metric: int):
+    """packed [H, packed_floats(K, D)] (pack_codebooks) -> the screen image of those codebooks, a uint8 tensor of
+    screen_image_bytes(H, K, D, metric) bytes for ``quantize(..., screen=)``, or None where that answers 0.  The image ends
+    in a control block that the kernels of a call share: calls that use one image must be ordered on one stream."""
+    _require_gpu(packed)
+    nbytes = screen_image_bytes(H, K, D, metric)
+    if nbytes == 0:
+        return None
+    _check_packed(packed, H, K, D, packed.device)
+    screen = torch.empty((nbytes,), dtype=torch.uint8, device=packed.device)
+    _call("vq_pack_screen_image_f32", packed.device, packed.data_ptr(), H, packed.shape[-1], K, D, metric, screen.data_ptr(),
+          nbytes)
+    return screen
+
+
 def _check_packed(packed: torch.Tensor, n: int, K: int, D: int, device) -> None:
     """A caller-cached image must be THE image of these codebooks' shape: the kernels take its row stride from K and D and
     read it through a buffer descriptor sized by vq_packed_floats -- a stale or foreign image would be read out of bounds."""
@@ -298,11 +321,11 @@ def _row_strides(t: torch.Tensor):
 
 
 def _vq_args(x: torch.Tensor, cb: torch.Tensor, *, Q: int = 1, shared: bool = True, metric: int = EUCLID, flags: int = 0,
-             packed=None, out=None, idx=None, idx_strides=None, best=None, sq_err=None, workspace=None) -> VqArgs:
+             packed=None, out=None, idx=None, idx_strides=None, best=None, sq_err=None, workspace=None, screen=None) -> VqArgs:
     """The one place a ``struct vq_args`` is filled.  x [H, M, D] (strided rows ok); cb [H, K, D], or [H, Qc, K, D] for a
     residual stack of Q stages; ``shared``: every stage reads the head's first codebook.  The rest is optional: packed (the
     image of cb), out [H, M, D], idx with ``idx_strides`` = (row, head, stage) when they are not those of an [H, M, Q]
-    tensor, best (laid out as idx), sq_err, workspace = the pair of _alloc_workspace."""
+    tensor, best (laid out as idx), sq_err, workspace = the pair of _alloc_workspace, screen (the image of pack_screen)."""
     H, M, D = x.shape
     K = cb.shape[-2]
     Qc = cb.shape[1] if cb.dim() == 4 else 1
@@ -327,16 +350,19 @@ def _vq_args(x: torch.Tensor, cb: torch.Tensor, *, Q: int = 1, shared: bool = Tr
         a.sq_err = sq_err.data_ptr()
     if workspace is not None:
         a.workspace, a.workspace_bytes = workspace[0].data_ptr(), workspace[1]
+    if screen is not None:
+        a.screen, a.screen_bytes = screen.data_ptr(), screen.numel() * screen.element_size()
     # the struct holds bare addresses: the tensors behind them (a packed image or a workspace made on the way here has no
     # other owner) live as long as it does, that is until the launch that reads them is enqueued
-    a.tensors = (x, cb, packed, out, idx, best, sq_err, workspace)
+    a.tensors = (x, cb, packed, out, idx, best, sq_err, workspace, screen)
     return a
 
 
 def quantize(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, ste: bool = False, want_out: bool = True,
              want_sq_err: bool = False, want_best: bool = True, packed: torch.Tensor | None = None,
              stages_share_codebook: bool = False, flags: int = 0, out: torch.Tensor | None = None,
-             idx: torch.Tensor | None = None, want_lse: bool = False, sq_err_per_head: bool = False):
+             idx: torch.Tensor | None = None, want_lse: bool = False, sq_err_per_head: bool = False,
+             screen: torch.Tensor | None = None):
     """The hot path through the C ABI.
 
     x   [H, M, D] fp32 (rows may be strided, last dim contiguous)
@@ -344,6 +370,8 @@ def quantize(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, ste: bo
         are then given by ``idx.shape[-1]`` or default to 1)
     out [H, M, D] optional destination VIEW (any row / head strides), idx [H, M, Q] optional int64 VIEW
     want_lse (Q == 1): also the per-row log-sum-exp of the similarities over the codebook, from the same sweep
+    screen: the cached image of ``pack_screen(packed, ...)``; a call the screened sweep takes then launches no pack kernel,
+        every other call ignores it
     returns dict(out [H, M, D] | None, idx [H, M, Q] int64, best [H, M, Q] | None, sq_err [Q] float64 | None,
                  lse [H, M] | None)
     """
@@ -384,7 +412,7 @@ def quantize(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, ste: bo
     sq_err = torch.empty((H, Q) if sq_err_per_head else (Q,), dtype=torch.float64, device=dev) if want_sq_err else None
     flags |= (F_STE if ste else 0) | (F_SQERR_PER_HEAD if (sq_err_per_head and want_sq_err) else 0)
     a = _vq_args(x, cb, Q=Q, shared=stages_share_codebook, metric=metric, flags=flags, packed=packed, out=out, idx=idx,
-                 best=best, sq_err=sq_err, workspace=_search_workspace(H, M, Q, dev, K, D))
+                 best=best, sq_err=sq_err, workspace=_search_workspace(H, M, Q, dev, K, D), screen=screen)
     lse = None
     if want_lse:
         assert Q == 1

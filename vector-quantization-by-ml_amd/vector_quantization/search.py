@@ -60,10 +60,17 @@ class _NativeBackend:
         return native.pack_codebooks(cb, metric)
 
     @staticmethod
+    def pack_screen(packed, H, K, D, metric):
+        """packed images of ``pack`` -> the screen image the screened sweep reads (vq_pack_screen_image_f32), or None where
+        no screened sweep exists for the shape.  One image serves one stream."""
+        return native.pack_screen(packed, H, K, D, metric)
+
+    @staticmethod
     def quantize(x, cb, *, metric, ste, want_sq_err, share, want_best=False, out=None, idx=None, want_lse=False,
-                 sq_err_per_head=False, packed=None):
+                 sq_err_per_head=False, packed=None, screen=None):
         """-> (out, idx, best, sq_err) and, with ``want_lse`` (single stage), a fifth element: the per-row log-sum-exp
-        of the similarities from the same sweep (vq_quantize_lse_f32)."""
+        of the similarities from the same sweep (vq_quantize_lse_f32).  ``screen``: the cached image of ``pack_screen``
+        (eager calls only: a traced call packs its own)."""
         if torch.compiler.is_compiling() and not (want_best or want_lse):
             # being traced by torch.compile / export: go through the registered op (ops.py) so the graph does not break here
             from . import ops
@@ -78,7 +85,7 @@ class _NativeBackend:
             return out, idx, None, (sq_err if want_sq_err else None)
         r = native.quantize(x, cb, metric=metric, ste=ste, want_sq_err=want_sq_err, want_best=want_best or want_lse,
                             stages_share_codebook=share, out=out, idx=idx, want_lse=want_lse,
-                            sq_err_per_head=sq_err_per_head, packed=packed)
+                            sq_err_per_head=sq_err_per_head, packed=packed, screen=screen)
         if want_lse:
             return r["out"], r["idx"], r["best"], r["sq_err"], r["lse"]
         return r["out"], r["idx"], r["best"], r["sq_err"]
@@ -355,7 +362,8 @@ class _QuantizeFn(torch.autograd.Function):
 def quantize_rows(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, ste: bool = False,
                   want_sq_err: bool = False, share: bool = False, codebook_grad_from_err: bool = False,
                   out: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None, want_lse: bool = False,
-                  sq_err_per_head: bool = False, packed: Optional[torch.Tensor] = None):
+                  sq_err_per_head: bool = False, packed: Optional[torch.Tensor] = None,
+                  screen: Optional[torch.Tensor] = None):
     """x [H, M, D] (strided rows allowed), cb [H, Q, K, D] contiguous ([H, 1, K, D] when ``share``; the number
     of stages is then ``idx.shape[-1]``).  ``out`` / ``idx`` may be pre-allocated (strided) destination views.
 
@@ -365,9 +373,13 @@ def quantize_rows(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, st
     ``sq_err_per_head``: sq_err is [H, Q] (one sum per head: GroupedResidualVQ reports a loss per group).
     ``packed``: a cached packed image of ``cb`` from ``get_backend().pack`` (backends with ``uses_packed``); without it
     the native backend packs on every call.
+    ``screen``: the cached screen image that goes with ``packed`` (``get_backend().pack_screen``); only a call that needs no
+    gradient uses it.
     """
     if packed is not None and not getattr(_backend, "uses_packed", False):
         packed = None
+    if packed is None or not hasattr(_backend, "pack_screen"):
+        screen = None
     if not cb.is_contiguous():
         cb = cb.contiguous()
     # x receives a gradient only through the straight-through output or the squared error: an eval-mode gather
@@ -387,6 +399,8 @@ def quantize_rows(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, st
             return out, idx, (sq_err if want_sq_err else None), dict(best=res[3], lse=res[4])
         return out, idx, (sq_err if want_sq_err else None)
     pk = {"packed": packed} if packed is not None else {}
+    if screen is not None:
+        pk["screen"] = screen
     if want_lse:
         out, idx, best, sq_err, lse = _backend.quantize(x, cb, metric=metric, ste=ste, want_sq_err=want_sq_err,
                                                         share=share, out=out, idx=idx, want_lse=True, **pk)
