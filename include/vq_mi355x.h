@@ -99,14 +99,19 @@ typedef struct vq_args {
 } vq_args;
 
 /*
- * The screen image: what the bf16x3 screened sweep reads instead of the fp32 packed image (plain Euclid inference calls of
+ * The screen image: what the fp16 screened sweep reads instead of the fp32 packed image (plain Euclid inference calls of
  * 128 < D <= 256 with 1 024 <= Kp <= 3 072 codes and enough rows to fill the chip), followed by a small control block that
  * the call's kernels share.  It is a pure function of the packed image, so a caller whose codebook stays put between calls
  * builds it once and hands it over in vq_args.screen: the call then launches no pack kernel.
  *   vq_screen_image_bytes: bytes of the H images plus the control block; 0 where no screened sweep exists for the shape
- *     (host arithmetic only).
+ *     (host arithmetic only).  The room per image is that of the earlier bf16-pair image, so buffers sized by it stay
+ *     valid and the control block stays where it was; the fp16 image fills about half of it and the rest is unused.
  *   vq_pack_screen_image_f32: builds the images of `packed` (head stride pk_hs floats) into `screen` (16-byte aligned,
- *     screen_bytes == vq_screen_image_bytes(...)) and zeroes the control block.
+ *     screen_bytes == vq_screen_image_bytes(...)) and zeroes the control block.  Per head: every code as one fp16 value
+ *     fp16(s_c * -2c), 32-code tiles of 528-byte rows with the tile's |c|^2 s_c s_x behind them; behind the tiles, per
+ *     tile, max |c|^2, the codes' largest rounding error |s_c c' - fp16|_2 and largest sum |fp16|, a flag and max |-2c_i|,
+ *     then the exponents of the two power-of-two scales s_c, s_x (csrc/vq_search_persist.inc has the layout and the
+ *     error bound that reads it).  Two kernels on `stream`.
  * One image serves one call at a time: calls that share it must be ordered on one stream (the control block holds the
  * call's counts; every call leaves it zeroed for the next).
  */

@@ -160,7 +160,7 @@ struct SearchChoice {
     SearchKind kind;
     int waves;      // waves per workgroup of the chosen kernel
     bool train;     // kPersist: the deferred copy does the straight-through / squared-error arithmetic
-    bool screened;  // kPersist: the bf16x3 screened sweep + the second pass over its listed rows
+    bool screened;  // kPersist: the fp16 screened sweep + the second pass over its listed rows
     bool cached;    // screened: the images and the control block are the caller's (vq_args.screen), no pack kernel runs
 };
 }  // namespace vqi
@@ -189,7 +189,7 @@ bool use_pair512() {
     return !off;
 }
 
-// the screened sweep's share of the workspace: [bf16x3 images][control block, kScrCtrlBytes][rows for the second pass: one uint32 per
+// the screened sweep's share of the workspace: [fp16 screen images][control block, kScrCtrlBytes][rows for the second pass: one uint32 per
 // row of the call, the full-search list from the front and the rescore list from the back].  A caller-cached screen image
 // (vq_args.screen, vq_screen_image_bytes) is the first two; the row list, which needs no initialisation, stays in the workspace.
 inline long long screen_list_bytes(int H, long long M) { return 4ll * H * M; }
@@ -304,10 +304,14 @@ int launch_pair_any(const SearchParams &p, int H, int splits, int metric, hipStr
 }
 #endif
 
-// the bf16x3 images of H codebooks from their fp32 packed images, and a zeroed control block behind them (a template, so
-// that only the build part that launches it instantiates the kernel)
+// the fp16 screen images of H codebooks from their fp32 packed images (the tiles' max |c'_i| first: the pack kernel derives the
+// head's scales from them), and a zeroed control block behind them (a template, so that only the build part that launches it
+// instantiates the kernels)
 template <int DP>
 int launch_pack_scr(const float *packed, long long pk_hs, int K, int ntiles, int H, char *img, long long img_hs, unsigned *ctrl, hipStream_t s) {
+    if (int rc = launch<vq_scr_absmax_kernel<DP>>(dim3((unsigned)ntiles, (unsigned)H), dim3(256), 0, s, "vq_scr_absmax launch", packed, pk_hs, ntiles,
+                                                  img, img_hs))
+        return rc;
     return launch<vq_pack_scr_kernel<DP>>(dim3((unsigned)ntiles, (unsigned)H), dim3(256), 0, s, "vq_pack_scr launch", packed, pk_hs, K, ntiles, img,
                                            img_hs, ctrl);
 }
@@ -691,7 +695,7 @@ bool vec4_ok(const void *p, std::initializer_list<long long> strides, unsigned a
     return ((uintptr_t)p & (align - 1)) == 0;
 }
 
-// The screened sweep's bf16x3 images are built per call into the key area of the workspace, which a fused call does not use,
+// The screened sweep's fp16 images are built per call into the key area of the workspace, which a fused call does not use,
 // and behind them the control block and the two lists of rows for the second pass (vq_resolve_rows_kernel): the layout of
 // screen_bytes.  With the caller's image (`cached`: vq_args.screen, checked by check_screen) only the lists are in the workspace.
 void set_screen_image(SearchParams &p, const vq_args *a, bool cached) {

@@ -47,7 +47,7 @@ struct SearchParams {
     const float *xn_ws;  // [head][xn_hs]: |x|^2 chain over the dims of the earlier slices
     float *xn_out;       // the chain including this slice (another buffer: the workgroups of a K split share the rows)
     long long xn_hs;
-    // Dp = 256 screened sweep (vq_search_persist.inc, SCREEN): the bf16x3 image of every head, `scr_hs` bytes apart, each
+    // Dp = 256 screened sweep (vq_search_persist.inc, SCREEN): the fp16 screen image of every head, `scr_hs` bytes apart, each
     // `scr_bytes` long (NULL: the fp32 sweep)
     const float *scr;
     long long scr_hs;
@@ -149,7 +149,7 @@ __device__ __forceinline__ void stage_tile(const float *img, unsigned bytes, int
 // be read as float4.  No barrier at the end: the caller knows whether the region is about to be reused by other waves.
 // Shared by the similarity / softmax-statistics / sampling sweeps, the cross-entropy backward kernels and the Gumbel sweeps.
 // The three inference search kernels (vq_search_mfma below, vq_search_pair512, vq_search_persist) keep this body written out
-// in place, with their own variations (fp16 / bf16 rows, non-temporal loads, the screened sweep's bf16 pairing): routed
+// in place, with their own variations (fp16 / bf16 rows, non-temporal loads, the screened sweep's fp16 pairing): routed
 // through this function their VGPR / AGPR counts move (profiles/prologue_refactor_codegen.md), and those kernels are tuned
 // to their register budgets.  A change to the chain or the swaps has to be made in all four places.
 template <int CH, int XS, int NCHUNK, bool EUCLID>

@@ -15,12 +15,16 @@
 // same way: the deferred step of a row loads the code row AND the x row (read again: the fragment registers of that block are
 // gone), does the finalize's arithmetic on the float4 and stores; the wave's squared-error partial is written once at the end.
 // ------------------------------------------------------------------------------------------------
-// SCREEN (Dp = 256, Euclid, plain inference call): a bf16x3 screen with a proven error bound, exact rule for the rest
+// SCREEN (Dp = 256, Euclid, plain inference call): an fp16 screen with a proven error bound, exact rule for the rest
 // ------------------------------------------------------------------------------------------------
-// The fp32 sweep runs v_mfma_f32_32x32x2_f32 (4 096 FLOP in 64 cycles); v_mfma_f32_32x32x16_bf16 does 32 768 FLOP in 32.
-// The screened sweep splits both operands into bf16 pairs, v = hi + lo + r with hi = bf16(v), lo = bf16(v - hi), and
-// accumulates hi_c * hi_x + lo_c * hi_x + hi_c * lo_x (3 bf16 MFMAs per 16 dims: 48 per 32 x 32 sub-tile instead of 129 fp32
-// ones), starting from |c|^2 (the fp32 chain of the packed image) in the accumulator.  Each lane keeps the three lowest
+// The fp32 sweep runs v_mfma_f32_32x32x2_f32 (4 096 FLOP in 64 cycles); v_mfma_f32_32x32x16_f16 does 32 768 FLOP in 32.
+// The screened sweep holds every code as ONE fp16 value ct = fp16(s_c c') (c' = -2c as packed, s_c a power of two per head that
+// puts max |c'| s_c in [2^13, 2^14)) and every row as an fp16 pair of X = s_x x (s_x a second power of two per head, max |c_i|
+// s_x in [2^7, 2^8)): xh = fp16(X), xl = fp16(X - xh).  It accumulates ct * xh + ct * xl (2 fp16 MFMAs per 16 dims: 32 per
+// 32 x 32 sub-tile instead of 129 fp32 ones), starting from |c|^2 s_c s_x (the fp32 chain of the packed image times an exact
+// power of two) in the accumulator, and divides the values it keeps by sg = s_c s_x once, after the sweep.  The rounding of
+// the codes is the one first-order error left; it is a property of the codebook, which the pack kernel measures (E_c below)
+// instead of bounding it.  Each lane keeps the three lowest
 // screened values of its codes over distinct codes, and the codes of the two lowest.  A row whose two lowest screened values
 // are further apart than the bound below can only have the screened winner as its exact winner.  The other rows are decided
 // by a second kernel on the same stream (vq_resolve_rows_kernel), none of them inside the sweep kernel, where one wave's
@@ -38,43 +42,70 @@
 //
 // The bound.  u = 2^-24; for a row x (fp32 chain xn = d-ordered sum of squares) and code c (fp32 chain cn), c' = -2c as
 // packed (exact), Q = sum_k x_k c'_k in real arithmetic, nx = sqrt(xn), nc = sqrt(max cn) over the codebook, L = 2 nx nc.
-// Cauchy-Schwarz: sum_k |x_k c'_k| <= 2 |x| |c| <= L (1 + gamma_256) (the chains xn, cn are sums of non-negative terms,
-// relative error <= gamma_256 = 256u / (1 - 256u) < 1.6e-5).
-//  S = screened value, E = exact fp32 value minus xn (the kernels' D = fl(fl(P + xn) + cn), P the k-ordered fmaf chain).
-//  (1) split: x = xh + xl + rx with |xh - x| <= 2^-9 |x| (round to nearest, 8-bit significand), x - xh exact in fp32,
-//      |rx| <= 2^-8 |x - xh| <= 2^-16 |x|, the same for c'.  x c' - (xh ch + xh cl + xl ch) = rx c' + x rc - rx rc + xl cl,
-//      and |xl cl| <= 2^-16 (1 + 2^-8)^2 |x c'|: in all <= 3.0001 * 2^-16 |x_k c'_k| per term, <= 4.58e-5 * 1.0001 L.
-//  (2) bf16 x bf16 products are exact in fp32 (16 significant bits); the MFMA adds the 3 D = 768 products and the
-//      initial cn in an undocumented order: any order of n - 1 = 768 additions is within gamma_768 < 4.59e-5 of the sum of
-//      the absolute values, here <= (1 + 4 * 2^-8) L * 1.0001 + cn: <= 4.59e-5 (1.016 L + nc^2).
-//  (3) denormals: bf16 operands and fp32 partial sums below 2^-126 may be flushed (the ISA does not promise either way).
-//      A flushed operand changes a product by < 2^-126 * 2 max(|x_k|, |c'_k|), a flushed product or sum by < 2^-126: over
-//      768 products and sums < 2^-115 (1 + nx + 2 nc) in absolute terms.
-//  (4) the exact side: |P - Q| <= gamma_256 sum |x_k c'_k| <= 1.53e-5 L * 1.0001 (k-ordered fmaf chain), the two
+// The chains xn, cn are sums of non-negative terms, relative error <= gamma_256 = 256u / (1 - 256u) < 1.6e-5, so
+// |x| <= nx (1 + 8e-6) and Cauchy-Schwarz gives sum_k |x_k c'_k| <= 2 |x| |c| <= L * 1.0001.  Scaling by s_c, s_x, sg = s_c s_x
+// is exact (powers of two; the pack kernel flags a head whose exponents leave +-62, where a scaled value could leave the
+// normal range).  Per head, from the pack kernel: E_c = max_k |s_c c'_k - ct_k|_2 and l1 = max_k sum_i |ct_ki|, both over
+// the value ct the MFMA sees (an fp16 below 2^-14 counted as 0), both rounded up.
+//  S = screened value (accumulator / sg), E = exact fp32 value minus xn (the kernels' D = fl(fl(P + xn) + cn), P the
+//  k-ordered fmaf chain).
+//  (1) codes: |sum_k (s_c c'_k - ct_k) X_k| <= E_c |X|_2 (Cauchy-Schwarz); over sg: <= (E_c / s_c) |x| <= (E_c / s_c) nx
+//      (1 + 8e-6).  ct_k = fp16(s_c c'_k) by round to nearest, |ct_k| < 2^14 + 8: finite.
+//  (2) row split: X = xh + xl + r.  |X| >= 2^-14: |X - xh| <= 2^-11 |X| (round to nearest, 11-bit significand), X - xh exact
+//      in fp32, and, where that is >= 2^-14 too, |r| <= 2^-11 |X - xh| <= 2^-22 |X|.  Eligible rows have |X_k| <= 2^15
+//      (below), so xh is finite.  sum_k |ct_k| 2^-22 |X_k| <= 2^-22 |ct|_2 |X|_2 with |ct|_2 <= s_c |c'| + E_c: over sg
+//      <= 2^-22 (1.0001 L + (E_c / s_c) nx (1 + 8e-6)).
+//  (3) fp16 subnormals: the ISA does not promise that the MFMA keeps fp16 operands below 2^-14, nor that the conversion
+//      does; assume either may give 0.  A part of X (xh, or xl) below 2^-14 then costs < 2^-14, whatever was done to it (kept:
+//      <= 2^-25 of rounding): per element <= 2 * 2^-14 in all, sum_k |ct_k| 2^-13 <= 2^-13 l1; over sg: 2^-13 l1 / sg.
+//      On the code side the pack kernel stores the flushed ct and measures E_c against it: inside (1).
+//  (4) fp16 x fp16 products are exact in fp32 (22 significant bits, >= 2^-28); the MFMAs add the 2 D = 512 products and the
+//      initial cn sg in an undocumented order: any order of 512 additions is within gamma_512 < 3.052e-5 of the sum of the
+//      absolute values, here <= cn sg + |ct|_2 |X|_2 (1 + 2^-10): over sg <= 3.052e-5 (1.002 L + 1.002 (E_c / s_c) nx + nc^2).
+//      fp32 partial sums below 2^-126 may be flushed: < 513 * 2^-126 < 2^-116, over sg; the division by sg rounds only a
+//      result below 2^-126: <= 2^-149.
+//  (5) the exact side: |P - Q| <= gamma_256 sum |x_k c'_k| <= 1.53e-5 L * 1.0001 (k-ordered fmaf chain), the two
 //      additions of xn and cn add <= u (|P + xn| + |D|) <= 1.2e-7 (L + xn + nc^2) * 1.0001; fp32 denormals in the chain
 //      < 258 * 2^-149.
-//  => |S - E| <= 1.080e-4 L + 4.61e-5 nc^2 + 1.2e-7 xn + 2^-114 (1 + nx + nc) =: delta_0.  The kernel uses
-//     delta = 2.5e-4 L + 1e-4 nc^2 + 3e-7 xn + 2^-110 (1 + nx + nc) >= 2.16 delta_0 (the rounding of delta's own evaluation
-//     and of the fp32 sqrt are far inside that factor).
+//  => |S - E| <= 1.0001 (E_c / s_c) nx + 4.63e-5 L + 3.07e-5 nc^2 + 1.21e-7 xn + (2^-13 l1 + 2^-116) / sg + 2^-140 =: delta_0
+//     ((1): 1 + 8e-6, (2): 2.4e-7, (4): 3.06e-5 on the first term; (2): 2.4e-7, (4): 3.058e-5, (5): 1.542e-5 on L).
+//     The kernel uses delta = 1.1 delta_0: the factor covers the rounding of delta's own evaluation (a dozen fp32
+//     operations on non-negative terms, < 2e-6) and of the two fp32 sqrt.
 // A row is CERTAIN when (b1, b2 = lowest and second lowest screened values over distinct codes of the row)
 //  * b2 - b1 > 2 delta + w, w = 2^-20 (|b1| + xn + delta): every other code j has E_j >= b2 - delta > b1 + delta + w >=
 //    E_win + w, so D_j - D_win > w >= 2^-21 D_win * 2: the two squared distances cannot share a correctly rounded sqrt (two
 //    values more than 2^-21 apart relative never do -- the fp32 sweep's tie rule), the screened argmin is the unique winner;
 //  * b1 + xn > 2 delta: the winner's D is positive, so no code clamps to 0 (several clamped codes would tie at 0 and the
 //    lowest index, not the screened argmin, would win);
-//  * eligibility: xn <= 2^100 and max cn <= 2^100 (no partial sum can overflow; NaN / inf rows fail this test and take the
-//    exact path, which follows the non-finite rule), and the codebook is not flagged non-finite.
+//  * eligibility: xn s_x^2 <= 2^30 (no element of X reaches fp16's largest value; NaN / inf rows fail this test and take the
+//    exact path, which follows the non-finite rule) and max cn <= 2^100, the codebook is not flagged non-finite, and the
+//    pack kernel has not flagged the head (an exponent outside +-62, or a real code whose cn sg is not 0 or a normal fp32).
 // The winning distance is then known only through the screen, so calls that request it (`best`) keep the fp32 sweep.
-constexpr int kScrRowBytes = 1040;                             // one code: 16 groups of 16 dims x (hi, lo) x 16 B, + 16 B pad
-constexpr int kScrTileBytes = kTileCodes * kScrRowBytes + 128;  // 32 codes + their 32 fp32 |c|^2
+constexpr int kScrRowBytes = 528;                              // one code: 16 groups of 16 dims x 2 x 16 B of fp16, + 16 B pad
+constexpr int kScrTileBytes = kTileCodes * kScrRowBytes + 128;  // 32 codes + their 32 fp32 |c|^2 s_c s_x
 constexpr int kScrCnOffset = kTileCodes * kScrRowBytes;
+constexpr int kScrChunks = (kScrTileBytes + 1023) / 1024;      // 1-KiB wave copies per tile (over-copy into the next tile)
+// Behind the ntiles tiles of a head, 32-bit words, ntiles of each: max |c|^2 of the tile's real codes (unscaled), E_c and l1
+// of the tile (scaled units, rounded up), the tile's flag, max |c'_i| of the tile (written by vq_scr_absmax_kernel, from which
+// every workgroup of the pack kernel derives the head's exponents); then the two exponents e_c, e_x (s_c = 2^e_c, s_x = 2^e_x).
+constexpr int kScrTailMcn = 0, kScrTailEc = 1, kScrTailL1 = 2, kScrTailFlag = 3, kScrTailAbs = 4, kScrTailExp = 5;
+constexpr int kScrMaxExp = 62;
+// The room of an image is still that of the bf16-pair image this one replaced (32 * 1040 + 128 bytes per tile and 4 behind):
+// vq_screen_image_bytes is part of the ABI and callers have sized buffers by it.  The image uses the front of the room; the
+// rest is unused and never read.
+constexpr int kScrTileRoom = kTileCodes * 1040 + 128;
+static_assert(kScrChunks * 1024 + 4 * kScrTailExp + 8 <= kScrTileRoom + 4, "tiles, over-copy and tail fit the room of one tile");
 // the MFMA group (of 16 per sub-tile) after which waves 4..7 run the sweep's epilogue; waves 0..3 run it after group 0
 // (8 = half a sub-tile; profiles/cfg2_stagger.md has the figures of 5, 6, 8, 10, 12 and 14)
 #ifndef VQ_SCR_LATE_GROUP
 #define VQ_SCR_LATE_GROUP 8
 #endif
 constexpr int kScrLateGroup = VQ_SCR_LATE_GROUP;
-inline long long scr_image_bytes(int ntiles) { return ((long long)ntiles * kScrTileBytes + 4ll * ntiles + 255) / 256 * 256; }
+// groups of 16 dims whose A fragments are read ahead of their MFMAs (3 or 4: profiles/cfg2_fp16_screen.md)
+#ifndef VQ_SCR_PF
+#define VQ_SCR_PF 3
+#endif
+inline long long scr_image_bytes(int ntiles) { return ((long long)ntiles * kScrTileRoom + 4ll * ntiles + 255) / 256 * 256; }
 #include "vq_resolve_plan.h"
 // The control block behind the images (SearchParams::scr_count points at it), 32-bit words: [0] rows on the full-search list,
 // [1] rows on the rescore list, [2] exit ticket of the second pass, [4] and [5] the two counts of the previous call (no kernel
@@ -88,20 +119,51 @@ constexpr int kScrSlotWord = kScrRowTicketWord + (int)kResolveMaxSplitRows;
 static_assert(kScrSlotWord % 2 == 0 && (kScrSlotWord + 2 * (int)(kResolveMaxSplitRows * kResolveMaxSplit)) * 4 <= kScrCtrlBytes,
               "8-byte slots, inside the block");
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 
-// hi = bf16(v), lo = bf16(v - hi) of 8 floats (plain round-to-nearest casts: v_cvt_pk_bf16_f32)
-__device__ __forceinline__ void split_bf16x2(const f32x8 &v, bf16x8 &hi, bf16x8 &lo) {
-    hi = __builtin_convertvector(v, bf16x8);
+// hi = fp16(v), lo = fp16(v - hi) of 8 floats (plain casts: v_cvt_f16_f32 under the default round-to-nearest mode, never
+// v_cvt_pkrtz_f16_f32)
+__device__ __forceinline__ void split_f16x2(const f32x8 &v, f16x8 &hi, f16x8 &lo) {
+    hi = __builtin_convertvector(v, f16x8);
     const f32x8 r = v - __builtin_convertvector(hi, f32x8);
-    lo = __builtin_convertvector(r, bf16x8);
+    lo = __builtin_convertvector(r, f16x8);
+}
+// 2^e as a float, -126 <= e <= 127
+__device__ __forceinline__ float scr_pow2(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
+
+// max |c'_i| of every 32-code tile of the fp32 packed image (padding rows hold zeros), NaN ignored: word kScrTailAbs of the
+// image's tail.  Grid (tiles, heads), 256 threads, ahead of vq_pack_scr_kernel on the stream.
+template <int DP>
+__global__ void __launch_bounds__(256) vq_scr_absmax_kernel(const float *__restrict__ packed, long long pk_hs, int ntiles,
+                                                            char *__restrict__ img, long long img_hs) {
+    constexpr int RS = DP + 4;
+    static_assert(DP == 256, "8 threads per code, 32 floats each");
+    const int t = blockIdx.x, c = threadIdx.x >> 3, part = threadIdx.x & 7;
+    const float *prow = packed + (long long)blockIdx.y * pk_hs + (long long)(t * kTileCodes + c) * RS + 32 * part;
+    float m = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const f32x4 v = *(const f32x4 *)(prow + 4 * i);
+        m = fmaxf(m, fmaxf(fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), fmaxf(__builtin_fabsf(v.z), __builtin_fabsf(v.w))));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    __shared__ float red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        ((float *)(img + (long long)blockIdx.y * img_hs + (long long)ntiles * kScrTileBytes))[kScrTailAbs * ntiles + t] =
+            fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-// The bf16x3 image of a Dp = 256 Euclid codebook, built from its fp32 packed image (values -2c, |c|^2 at float Dp, +inf for
-// the padding rows).  Per 32-code tile: row c at c * 1040 bytes, for each group s of 16 dims hi[16s .. 16s+7], hi[16s+8 ..
-// 16s+15], lo[16s ..], lo[16s+8 ..] (16 B each: one ds_read_b128 is one MFMA's A fragment), then the 32 |c|^2 of the tile;
-// behind the tiles the maximum |c|^2 of each tile's real codes.  Grid (tiles, heads), 256 threads: 8 per code.
+// The fp16 image of a Dp = 256 Euclid codebook, built from its fp32 packed image (values c' = -2c, |c|^2 at float Dp, +inf for
+// the padding rows).  Per 32-code tile: row c at c * 528 bytes, for each group s of 16 dims ct[16s .. 16s+7], ct[16s+8 ..
+// 16s+15] (16 B each: one ds_read_b128 is one MFMA's A fragment), ct = fp16(s_c c') with values below 2^-14 stored as 0; then
+// the 32 |c|^2 s_c s_x of the tile; behind the tiles the words described at kScrTailMcn.  Every workgroup derives the head's
+// exponents from the tiles' max |c'_i| (vq_scr_absmax_kernel): e_c = 13 - floor(log2 max |c'|), e_x = e_c - 5 (max |c_i| =
+// max |c'| / 2 in [2^7, 2^8)); both 0 for an all-zero codebook, both 0 and the head flagged when one leaves +-kScrMaxExp
+// (non-finite or subnormal maxima included).  Grid (tiles, heads), 256 threads: 8 per code.
 // One workgroup also zeroes the control block `ctrl` (kScrCtrlBytes): the counts of the two lists of rows for the second pass
 // (vq_resolve_rows_kernel) and its exit ticket.
 template <int DP>
@@ -118,8 +180,26 @@ __global__ void __launch_bounds__(256) vq_pack_scr_kernel(const float *__restric
     const int t = blockIdx.x, c = threadIdx.x >> 3, part = threadIdx.x & 7;
     const int k = t * kTileCodes + c;
     const float *prow = packed + (long long)blockIdx.y * pk_hs + (long long)k * RS;
-    char *tile = img + (long long)blockIdx.y * img_hs + (long long)t * kScrTileBytes;
+    char *himg = img + (long long)blockIdx.y * img_hs;
+    char *tile = himg + (long long)t * kScrTileBytes;
+    float *tail = (float *)(himg + (long long)ntiles * kScrTileBytes);
     char *dst = tile + c * kScrRowBytes;
+    // the head's exponents (the same in every workgroup of the head)
+    float hmax = 0.0f;
+    for (int i = 0; i < ntiles; ++i) hmax = fmaxf(hmax, tail[kScrTailAbs * ntiles + i]);
+    int e_c = 0, e_x = 0;
+    unsigned flag = 0u;
+    if (hmax != 0.0f) {
+        const int lg = (int)((__float_as_uint(hmax) >> 23) & 0xFFu) - 127;  // floor(log2 hmax) of a normal value
+        e_c = 13 - lg;
+        e_x = e_c - 5;
+        if (e_c > kScrMaxExp || e_c < -kScrMaxExp || e_x > kScrMaxExp || e_x < -kScrMaxExp) {
+            e_c = e_x = 0;
+            flag = 1u;
+        }
+    }
+    const float s_c = scr_pow2(e_c), sg = scr_pow2(e_c + e_x);
+    float d2 = 0.0f, l1 = 0.0f;  // this thread's part of |s_c c' - ct|^2 and of sum |ct|
 #pragma unroll
     for (int ss = 0; ss < 2; ++ss) {
         const int s = 2 * part + ss;
@@ -127,27 +207,59 @@ __global__ void __launch_bounds__(256) vq_pack_scr_kernel(const float *__restric
         for (int h = 0; h < 2; ++h) {
             const int g = 2 * s + h;  // 8-dim group of the fp32 image: evens first, then odds
             const f32x4 ev = *(const f32x4 *)(prow + 8 * g), od = *(const f32x4 *)(prow + 8 * g + 4);
-            const f32x8 v = {ev.x, od.x, ev.y, od.y, ev.z, od.z, ev.w, od.w};
-            bf16x8 hi, lo;
-            split_bf16x2(v, hi, lo);
-            *(bf16x8 *)(dst + 64 * s + 16 * h) = hi;
-            *(bf16x8 *)(dst + 64 * s + 32 + 16 * h) = lo;
+            const f32x8 v = (f32x8){ev.x, od.x, ev.y, od.y, ev.z, od.z, ev.w, od.w} * s_c;
+            f16x8 ct = __builtin_convertvector(v, f16x8);
+            f32x8 cf = __builtin_convertvector(ct, f32x8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                if (__builtin_fabsf(cf[e]) < 0x1p-14f) {  // what the MFMA may see as 0 is stored as 0
+                    ct[e] = (_Float16)0.0f;
+                    cf[e] = 0.0f;
+                }
+                const float d = v[e] - cf[e];  // exact in fp32
+                d2 = fmaf(d, d, d2);
+                l1 += __builtin_fabsf(cf[e]);
+            }
+            *(f16x8 *)(dst + 32 * s + 16 * h) = ct;
         }
     }
-    if (part == 0) *(f32x4 *)(dst + 1024) = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-    float cmax = 0.0f;
-    if (part == 0) {
-        *(float *)(tile + kScrCnOffset + 4 * c) = prow[DP];  // the packed |c|^2 (+inf for padding rows)
-        cmax = (k < K) ? prow[DP + 2] : 0.0f;
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) {
+        d2 += __shfl_xor(d2, o);
+        l1 += __shfl_xor(l1, o);
     }
-    // (threads 8c of the first 4 waves hold the values: a max over the workgroup through LDS)
-    __shared__ float red[kTileCodes];
-    if (part == 0) red[c] = cmax;
+    // (threads 8c of the first 4 waves hold the values: maxima over the workgroup through LDS)
+    __shared__ float red_cn[kTileCodes], red_ec[kTileCodes], red_l1[kTileCodes];
+    __shared__ unsigned red_fl[kTileCodes];
+    if (part == 0) {
+        *(f32x4 *)(dst + 512) = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        const float cn = prow[DP];  // the packed |c|^2 (+inf for padding rows)
+        const float cs = cn * sg;
+        *(float *)(tile + kScrCnOffset + 4 * c) = cs;
+        const bool real = k < K;
+        // rounded up: the chains and the sqrt are within 2e-5 of the real values
+        red_cn[c] = real ? prow[DP + 2] : 0.0f;
+        red_ec[c] = real ? sqrtf(d2) * (1.0f + 0x1p-10f) : 0.0f;
+        red_l1[c] = real ? l1 * (1.0f + 0x1p-10f) : 0.0f;
+        red_fl[c] = (real && cn < __builtin_inff() && !(cs == 0.0f ? cn == 0.0f : (cs >= 0x1p-126f && cs < __builtin_inff()))) ? 1u : 0u;
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        float m = 0.0f;
-        for (int i = 0; i < kTileCodes; ++i) m = (red[i] > m || red[i] != red[i]) ? red[i] : m;
-        *(float *)(img + (long long)blockIdx.y * img_hs + (long long)ntiles * kScrTileBytes + 4 * t) = m;
+        float m = 0.0f, ec = 0.0f, ml1 = 0.0f;
+        for (int i = 0; i < kTileCodes; ++i) {
+            m = (red_cn[i] > m || red_cn[i] != red_cn[i]) ? red_cn[i] : m;
+            ec = (red_ec[i] > ec || red_ec[i] != red_ec[i]) ? red_ec[i] : ec;
+            ml1 = (red_l1[i] > ml1 || red_l1[i] != red_l1[i]) ? red_l1[i] : ml1;
+            flag |= red_fl[i];
+        }
+        tail[kScrTailMcn * ntiles + t] = m;
+        tail[kScrTailEc * ntiles + t] = ec;
+        tail[kScrTailL1 * ntiles + t] = ml1;
+        ((unsigned *)tail)[kScrTailFlag * ntiles + t] = flag;
+        if (t == 0) {
+            ((int *)tail)[kScrTailExp * ntiles] = e_c;
+            ((int *)tail)[kScrTailExp * ntiles + 1] = e_x;
+        }
     }
 }
 
@@ -531,7 +643,7 @@ __global__ void __launch_bounds__(kResolveWaves * 64) vq_resolve_rows_kernel(con
 __device__ unsigned long long g_scr_rows[3];  // [0] rows listed for the second pass, [1] rows screened, [2] rows rescored
 #endif
 
-// SCREEN: the screened sweep described above (Dp = 256, Euclid, no TRAIN); p.scr holds the bf16x3 images.
+// SCREEN: the screened sweep described above (Dp = 256, Euclid, no TRAIN); p.scr holds the fp16 images.
 template <int DP, int WAVES, int METRIC, bool TRAIN = false, bool SCREEN = false>
 __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchParams p) {
     static_assert(!SCREEN || (DP == 256 && METRIC == VQ_METRIC_EUCLID && !TRAIN), "screened sweep: Dp = 256, Euclid, inference");
@@ -555,20 +667,42 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
     const float *pk = p.packed + (long long)head * p.pk_hs;
     const float *cbh = p.cb + (long long)head * p.cb_hs;
     const float *scrh = SCREEN ? (const float *)((const char *)p.scr + head * p.scr_hs) : nullptr;
-    // SCREEN: max |c|^2 of the codebook (the bound's nc^2) from the per-tile maxima behind the tiles
-    float scr_mcn = 0.0f;
+    // SCREEN, per head from the words behind the tiles (all wave-uniform: scalar registers): max |c|^2 of the codebook (the
+    // bound's nc^2), E_c / s_c, the bound's absolute term, the pack kernel's flag and the scales
+    float scr_mcn = 0.0f, scr_ecs = 0.0f, scr_abs = 0.0f, scr_sx = 1.0f, scr_isg = 1.0f;
+    unsigned scr_flag = 0u;
     if constexpr (SCREEN) {
-        const float *tmax = (const float *)((const char *)scrh + (long long)p.ntiles * kScrTileBytes);
+        const float *tail = (const float *)((const char *)scrh + (long long)p.ntiles * kScrTileBytes);
+        float ec = 0.0f, l1 = 0.0f;
+        auto nanmax = [](float a, float v) { return (v > a || v != v) ? v : a; };
         for (int i = lane; i < p.ntiles; i += 64) {
-            const float v = tmax[i];
-            scr_mcn = (v > scr_mcn || v != v) ? v : scr_mcn;
+            scr_mcn = nanmax(scr_mcn, tail[kScrTailMcn * p.ntiles + i]);
+            ec = nanmax(ec, tail[kScrTailEc * p.ntiles + i]);
+            l1 = nanmax(l1, tail[kScrTailL1 * p.ntiles + i]);
+            scr_flag |= ((const unsigned *)tail)[kScrTailFlag * p.ntiles + i];
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
-            const float v = __shfl_xor(scr_mcn, o);
-            scr_mcn = (v > scr_mcn || v != v) ? v : scr_mcn;
+            scr_mcn = nanmax(scr_mcn, __shfl_xor(scr_mcn, o));
+            ec = nanmax(ec, __shfl_xor(ec, o));
+            l1 = nanmax(l1, __shfl_xor(l1, o));
+            scr_flag |= (unsigned)__shfl_xor((int)scr_flag, o);
         }
-        scr_mcn = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scr_mcn)));  // (wave-uniform: a scalar register)
+        int e_c = ((const int *)tail)[kScrTailExp * p.ntiles], e_x = ((const int *)tail)[kScrTailExp * p.ntiles + 1];
+        if (e_c > kScrMaxExp || e_c < -kScrMaxExp || e_x > kScrMaxExp || e_x < -kScrMaxExp) {  // (never, for an image the pack kernel wrote)
+            e_c = e_x = 0;
+            scr_flag = 1u;
+        }
+        scr_sx = scr_pow2(e_x);
+        scr_isg = scr_pow2(-(e_c + e_x));
+        scr_ecs = ec * scr_pow2(-e_c);
+        scr_abs = (0x1p-13f * l1 + 0x1p-116f) * scr_isg + 0x1p-140f;
+        scr_mcn = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scr_mcn)));
+        scr_ecs = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scr_ecs)));
+        scr_abs = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scr_abs)));
+        scr_sx = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scr_sx)));
+        scr_isg = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(scr_isg)));
+        scr_flag = __builtin_amdgcn_readfirstlane(scr_flag);
     }
     float *outh = p.out ? p.out + (long long)head * p.out_hs : nullptr;
     const float INF = __builtin_inff();
@@ -621,12 +755,12 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
     };
 
     auto stage = [&](int tile, int buf) {
-        if constexpr (SCREEN) {  // a bf16x3 tile: its own length, whole KiB
-            static_assert(kScrTileBytes <= G::BUF_F4 * 16, "a bf16x3 tile fits the fp32 tile's buffer");
+        if constexpr (SCREEN) {  // an fp16 tile: its own length, whole KiB
+            static_assert(kScrChunks * 1024 <= G::BUF_F4 * 16, "an fp16 tile fits the fp32 tile's buffer");
 #pragma unroll
-            for (int i2 = 0; i2 < (G::TILE_CHUNKS + WAVES - 1) / WAVES; ++i2) {
+            for (int i2 = 0; i2 < (kScrChunks + WAVES - 1) / WAVES; ++i2) {
                 const int ck = i2 * WAVES + wave;
-                if (ck < (kScrTileBytes + 1023) / 1024)
+                if (ck < kScrChunks)
                     lds_dma16(scrh, p.scr_bytes, lane * 16, tile * kScrTileBytes + ck * 1024, tile4_lds + buf * G::BUF_F4 + ck * 64);
             }
         } else {
@@ -650,10 +784,10 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         stage(0, 0);
         // ---------------- prologue: this wave's 32 rows -> MFMA fragments in registers ----------------
         // (load_x_fragments of vq_search.inc written out in place: vector loads only, and SCREEN pairs the groups of 8 dims
-        //  into bf16 fragments instead of swapping them -- see there)
+        //  into fp16 fragments instead of swapping them -- see there)
         __builtin_amdgcn_s_setprio(2);
         float xf[NS];  // (unused by SCREEN)
-        bf16x8 xhf[SCREEN ? DP / 16 : 1], xlf[SCREEN ? DP / 16 : 1];  // SCREEN: B fragments of group s = 16 dims (hi, lo)
+        f16x8 xhf[SCREEN ? DP / 16 : 1], xlf[SCREEN ? DP / 16 : 1];  // SCREEN: B fragments of group s = 16 dims (hi, lo) of s_x x
         float xn0 = 0.0f;
         {
             float *xs = smem + G::NBUF * G::BUF_F4 * 4 + wave * (32 * XS);
@@ -702,12 +836,12 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
                         asm volatile("" : "+v"(xn0));
                     }
                     if constexpr (SCREEN) {
-                        // B operand of v_mfma_f32_32x32x16_bf16: lane (c, h) holds dims 16 s + 8 h .. + 7 of row c
+                        // B operand of v_mfma_f32_32x32x16_f16: lane (c, h) holds dims 16 s + 8 h .. + 7 of row c
                         if (j & 1) {
                             const f32x8 v8 = h ? (f32x8){lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}
                                                : (f32x8){plo.x, plo.y, plo.z, plo.w, phi.x, phi.y, phi.z, phi.w};
                             const int sg = ch * (CH / 16) + (j >> 1);
-                            split_bf16x2(v8, xhf[sg], xlf[sg]);
+                            split_f16x2(v8 * scr_sx, xhf[sg], xlf[sg]);
                         } else {
                             plo = lo;
                             phi = hi;
@@ -774,16 +908,16 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         };
 
         const int t1 = p.ntiles;
-        // SCREEN sub-tile: 16 groups of 16 dims, 3 bf16 MFMAs each (hi.hi, lo.hi, hi.lo), |c|^2 as the accumulator's start;
-        // fragments read PF groups ahead, two ds_read_b128 per 3 MFMAs (the fp32 body's reads, same addresses per lane)
+        // SCREEN sub-tile: 16 groups of 16 dims, 2 fp16 MFMAs each (ct.xh, ct.xl), |c|^2 s_c s_x as the accumulator's start;
+        // fragments read PF groups ahead, one ds_read_b128 per 2 MFMAs
         auto run_sub_scr = [&](f32x16 &acc, f32x16 &prev, int u, bool have_prev) {
-            constexpr int NGS = DP / 16, PF = 3;
+            constexpr int NGS = DP / 16, PF = VQ_SCR_PF;
             static_assert(kScrLateGroup > 3 && kScrLateGroup < NGS, "the late epilogue sits inside the last range of groups");
             SSTAMP(0);
             const int cur = u & 1;
             const char *tb = (const char *)(tile4 + cur * G::BUF_F4);
             const char *ta = tb + c * kScrRowBytes + 16 * h;
-            bf16x8 ah[NGS], al[NGS];
+            f16x8 ah[NGS];
             {
                 const f32x4 *cn4 = (const f32x4 *)(tb + kScrCnOffset);  // acc[r] <-> code 4 h + (r & 3) + 8 (r >> 2)
 #pragma unroll
@@ -793,22 +927,15 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
                 }
             }
 #pragma unroll
-            for (int g = 0; g < PF; ++g) {
-                ah[g] = *(const bf16x8 *)(ta + 64 * g);
-                al[g] = *(const bf16x8 *)(ta + 64 * g + 32);
-            }
+            for (int g = 0; g < PF; ++g) ah[g] = *(const f16x8 *)(ta + 32 * g);
             copy_step();
             auto groups = [&](auto g0c, auto g1c) {
                 constexpr int G0 = decltype(g0c)::value, G1 = decltype(g1c)::value;
 #pragma unroll
                 for (int g = G0; g < G1; ++g) {
-                    if (g + PF < NGS) {
-                        ah[g + PF] = *(const bf16x8 *)(ta + 64 * (g + PF));
-                        al[g + PF] = *(const bf16x8 *)(ta + 64 * (g + PF) + 32);
-                    }
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[g], xhf[g], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[g], xhf[g], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[g], xlf[g], acc, 0, 0, 0);
+                    if (g + PF < NGS) ah[g + PF] = *(const f16x8 *)(ta + 32 * (g + PF));
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[g], xhf[g], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[g], xlf[g], acc, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
@@ -894,7 +1021,9 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         bool has_cand = false;
         if constexpr (SCREEN) {
             // the screened argmin of this lane (lowest code holding the lowest value), then both lane halves of the row
-            const float l1 = lb.best_t, l2 = scr_b2;  // this lane's two lowest (codes lb.pend_u, scr_i2)
+            // (the accumulators are in units of s_c s_x: one exact division by that power of two for the values kept)
+            const float l1 = lb.best_t * scr_isg, l2 = scr_b2 * scr_isg;  // this lane's two lowest (codes lb.pend_u, scr_i2)
+            scr_b3 *= scr_isg;
             const int li1 = lb.pend_u, li2 = scr_i2;
             best_i = li1 < p.K ? li1 : p.K - 1;
             float b1 = l1;
@@ -907,9 +1036,10 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             }
             // certainty test (the bound: top of this file)
             const float nx = sqrtf(xn0), nc = sqrtf(scr_mcn);
-            const float delta = 2.5e-4f * (2.0f * nx * nc) + 1e-4f * scr_mcn + 3e-7f * xn0 + 0x1p-110f * (1.0f + nx + nc);
+            const float delta = 1.1f * (1.0001f * scr_ecs * nx + 4.63e-5f * (2.0f * nx * nc) + 3.07e-5f * scr_mcn + 1.21e-7f * xn0 + scr_abs);
             const float w = 0x1p-20f * (__builtin_fabsf(b1) + xn0 + delta);
-            const bool eligible = cb_flag == 0u && xn0 <= 0x1p100f && scr_mcn <= 0x1p100f && (b1 + xn0 > 2.0f * delta);
+            const bool eligible = cb_flag == 0u && scr_flag == 0u && xn0 * scr_sx * scr_sx <= 0x1p30f && scr_mcn <= 0x1p100f &&
+                                  (b1 + xn0 > 2.0f * delta);
             const bool certain = eligible && (b2 - b1 > 2.0f * delta + w);
             best_s = 0.0f;  // (the screened calls do not return distances)
             // Uncertain rows.  Only a code with S <= thr = b1 + 2 delta + w can beat or tie the exact winner (its D would
