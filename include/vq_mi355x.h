@@ -378,8 +378,8 @@ int vq_gumbel_reinmax_backward_codes_f32(const vq_args *a, const float *g, int64
                                          float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
- * Codebook diversity loss (vector_quantize_pytorch.py:324-334 with utils/general.py:25-30) and its gradient with respect to
- * the rows, nothing of [M, K] in memory.  With s the similarities [H][M][K] as above, T the diversity temperature, N the
+ * Codebook diversity loss (vector_quantize_pytorch.py:324-334 with utils/general.py:25-30) and its gradients with respect to
+ * the rows and to a learnable codebook, nothing of [M, K] in memory.  With s the similarities [H][M][K] as above, T the diversity temperature, N the
  * number of sequence positions and n(m) = (m / pos_div) % N the position of row m of every head (pos_div = 1, or the number
  * of heads when the heads of one shared codebook are interleaved in the rows); C = H * M / N rows per position:
  *   p_hmk = softmax_k(-T s_hmk)                     (the sign is the reference's: under Euclid the FAR codes get the mass)
@@ -388,12 +388,13 @@ int vq_gumbel_reinmax_backward_codes_f32(const vq_args *a, const float *g, int64
  *   U_nk  = g / (N C) * (log(max(A_nk, 1e-5)) + [A_nk >= 1e-5])               (g = dL/dloss; ATen's clamp backward)
  *   delta_hm = sum_k p_hmk U[n(m)][k]               w_hmk = dL/ds_hmk = -T p_hmk (U[n(m)][k] - delta_hm)
  *   dot:    grad_x = w l             Euclid:  r = w / s (0 where s == 0),  grad_x = x rowsum(r) - r l
+ *   dot:    grad_codes_k = sum_m w_mk x_m            Euclid:  grad_codes_k = c_k sum_m r_mk - sum_m r_mk x_m      (all rows of the head)
  * where l = the live codes when live_packed is given, else the codes of a->packed: everything that decides the weights (s,
  * lse2, the zero mask, rowsum(r)) comes from a->packed, what they are multiplied with from live_packed (the convention of
  * vq_ce_backward_live_f32).  loss and U are [N][K] element-wise work on A and are left to the caller.
- * All four use a->x (strided rows), H, M, K, D (<= 256: VQ_E_UNSUPPORTED beyond) and metric; Q is ignored.  Checked before
+ * All five use a->x (strided rows), H, M, K, D (<= 256: VQ_E_UNSUPPORTED beyond) and metric; Q is ignored.  Checked before
  * any launch (VQ_E_BADARG): T finite; N > 0, pos_div > 0 and M a multiple of N * pos_div; every array argument non-null
- * and 16-byte aligned.  M == 0: nothing is launched and nothing is written.
+ * and 16-byte aligned.  M == 0: nothing is launched and nothing is written (backward_codes zeroes grad_codes).
  * lse2, delta: [H][vq_gumbel_row_stride(M)] floats (columns past M unused).  A, U: [N][vq_gumbel_row_stride(K)] floats; the
  * entries of A past K are written as 0, those of U must be finite (they are read and discarded).
  * vq_diversity_stats_f32 (a->packed): lse2[h][m] = log2 sum_k exp2(-T s log2 e).
@@ -416,6 +417,18 @@ int vq_gumbel_reinmax_backward_codes_f32(const vq_args *a, const float *g, int64
  * vq_diversity_backward_x_f32 (a->packed): grad_x (h, m, d) at grad_x[h*gx_hs + m*gx_rs + d].  live_packed: NULL, or the
  *   packed images of the live codes (vq_pack_codebooks_f32 of [H][K][D] with the same metric, head stride live_pk_hs floats);
  *   an image bit-equal to a->packed gives bit for bit the result of NULL.
+ * vq_diversity_backward_codes_f32 (a->cb, the natural codes; lse2, delta and U as for backward_x, in the caller's row order):
+ *   grad_codes [H][K][D] contiguous.  It packs the position-major image of vq_diversity_accumulate_f32 again (the forward's
+ *   workspace need not outlive the forward), lse2 and delta beside it in image order.  A wave owns 32 codes and recomputes p
+ *   with the expression the other sweeps rounded it with; w / r of a position's padding rows is selected to 0.  The staged
+ *   tiles are split over workgroups by the plan of vq_gumbel_backward_codes_f32 (splits = min(64, tiles, ceil(CUs / (H *
+ *   ceil(K / 128)))) regrouped into equal runs of tiles), every split stores its partial and the partials are added in
+ *   split order: no float atomics, bit-identical results from run to run on one device.  Also VQ_E_BADARG: a->cb or
+ *   grad_codes null, a workspace that is too small or misaligned.
+ *   Workspace (>= vq_diversity_codes_workspace_bytes bytes, 16-byte aligned; 0 for exactly the shapes
+ *   vq_diversity_workspace_bytes gives 0 for), in 4-byte units, Mp and Dp as above:
+ *     [x image: H * (Mp*(Dp + 4) + 2048)][lse2 in image order: H*Mp][delta in image order: H*Mp]
+ *     [grad_codes partials: splits*H*K*D, only when splits > 1]
  */
 int64_t vq_diversity_workspace_bytes(int H, int64_t M, int K, int D, int N);
 int vq_diversity_stats_f32(const vq_args *a, float T, float *lse2, void *stream);
@@ -426,6 +439,9 @@ int vq_diversity_delta_f32(const vq_args *a, float T, int N, int pos_div, const 
 int vq_diversity_backward_x_f32(const vq_args *a, const float *live_packed, int64_t live_pk_hs, float T, int N, int pos_div,
                                 const float *lse2, const float *delta, const float *U, float *grad_x, int64_t gx_rs, int64_t gx_hs,
                                 void *stream);
+int64_t vq_diversity_codes_workspace_bytes(int H, int64_t M, int K, int D, int N);
+int vq_diversity_backward_codes_f32(const vq_args *a, float T, int N, int pos_div, const float *lse2, const float *delta,
+                                    const float *U, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * Gumbel-max sampling of the code, utils/general.py:112-129 (ind = argmax(similarities / temperature + gumbel_noise)) with

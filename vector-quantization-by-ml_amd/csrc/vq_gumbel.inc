@@ -33,7 +33,7 @@
 //   kRmC       as kGumC: the statistics and ind of the streamed rows read four at a time, col / e of the lane's code
 // ind is only ever compared with a code index.  Streamed padding is masked AFTER the clamp (p1 = 1e-5 there, not 0).
 //
-// Codebook diversity loss (vector_quantize_pytorch.py:324-334) through the same sweep, four more roles with ONE product per
+// Codebook diversity loss (vector_quantize_pytorch.py:324-334) through the same sweep, five more roles with ONE product per
 // sub-tile (there is no g: what a = g c^T is above is a lookup in the table U [N, K] here).  tau = -T, so p = softmax_k(-T s):
 //   kDivStats  as kGumStats without the second product -> lse2
 //   kDivAcc    the orientation of kRmCol: the streamed image holds the x rows in position-major order, every position padded
@@ -44,6 +44,13 @@
 //              position
 //   kDivX      as kGumX with a = U[n(m)][k]; when a second image is given (the live codes) the contraction reads ITS tile,
 //              staged beside the first the way the codes-resident roles stage the g rows
+//   kDivC      the orientation of kGumC with the image of kDivAcc (lse2 AND delta copied along in image order): a wave owns 32
+//              codes, a = U[n][own code] is one scalar per position, w (or r) of the 16 streamed rows in place in the
+//              accumulator of s, the contraction onto the same staged x tile, the column sum of r for the rank-one term.  The
+//              staged tiles are split over blockIdx.z as for kGumC (gc sums over ALL rows: a position may straddle workgroups),
+//              one partial [K, D] per split.  A position's padding rows hold |x|^2 = +inf under Euclid: with tau < 0 their
+//              logit is +inf, p = inf and r = inf * rsqrt(inf) = NaN, which the contraction would multiply with the zero x
+//              row -- w / r of a padding row is therefore SELECTED to 0 before the contraction and the column sum
 // n(m) = (m / pos_div) % N.
 // ------------------------------------------------------------------------------------------------
 constexpr int kGumStats = 0;
@@ -57,6 +64,7 @@ constexpr int kDivStats = 7;
 constexpr int kDivAcc = 8;
 constexpr int kDivDelta = 9;
 constexpr int kDivX = 10;
+constexpr int kDivC = 11;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 }  // namespace
@@ -77,7 +85,7 @@ struct GumbelParams {
     long long st_hs;
     float *out;  // gx (kGumX) / the partials of gc (kGumC)
     long long out_rs, out_hs, out_zs;
-    int tiles_per_split;  // kGumC: streamed tiles per blockIdx.z
+    int tiles_per_split;  // kGumC / kDivC: streamed tiles per blockIdx.z
     // reinmax roles (lse / delta above: the log-sum-exp at tau and delta0)
     float *lse1;                   // [H][st_hs]: log2-domain log-sum-exp at temperature 1
     const long long *ind;          // kRmX: the caller's selection, (h, m) at ind[h*ind_hs + m*ind_rs]
@@ -87,11 +95,12 @@ struct GumbelParams {
     long long ck_hs;
     float *colp, *ep;              // kRmCol: partials [splits][H][ck_hs]
     long long cp_zs;
-    // diversity roles (tau = -T; lse: per row, kDivAcc in image order; delta; out: gx, kDivAcc the per-head partials of A)
-    const float *U;                // kDivDelta / kDivX: [N][U_rs], finite past K
+    // diversity roles (tau = -T; lse: per row, kDivAcc / kDivC in image order; delta (kDivC: in image order); out: gx, kDivAcc
+    // the per-head partials of A, kDivC the partials of gc)
+    const float *U;                // kDivDelta / kDivX / kDivC: [N][U_rs], finite past K
     long long U_rs, gimg_hs;       // gimg (kDivX): the packed live codes or null, head stride gimg_hs
     int div_N, div_posdiv;         // position of row m: (m / div_posdiv) % div_N
-    int div_spp, div_ch, div_pps;  // kDivAcc: sub-tiles per position, rows per position and head, positions per blockIdx.z
+    int div_spp, div_ch, div_pps;  // kDivAcc / kDivC: sub-tiles per position, rows per position and head; kDivAcc: positions per blockIdx.z
 };
 }  // namespace vqi
 namespace {
@@ -133,12 +142,13 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     constexpr int RS = G::RS, RS4 = G::RS4, SUB = G::SUB, NG = DP / 8, V = GG::V, NJ = GG::NJ, NACC = GG::NACC;
     constexpr bool EUCLID = (METRIC == VQ_METRIC_EUCLID);
     constexpr bool DIV = (ROLE >= kDivStats);  // one product per sub-tile, no g
-    constexpr bool CODES = (ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC || ROLE == kDivAcc);
+    constexpr bool CODES = (ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC || ROLE == kDivAcc || ROLE == kDivC);
     constexpr bool RM = (ROLE >= kRmStats && ROLE <= kRmC);
     constexpr bool COLS = (ROLE == kRmCol);
     // no contraction: no gradient accumulators
     constexpr bool STATS = (ROLE == kGumStats || ROLE == kRmStats || COLS || ROLE == kDivStats || ROLE == kDivAcc || ROLE == kDivDelta);
     constexpr bool GIMG = CODES && !DIV;  // a second streamed image at compile time: the packed g rows
+    constexpr bool DIVIMG = (ROLE == kDivAcc || ROLE == kDivC);  // the streamed image is the position-major x image
     constexpr int IMG_F4 = 2 * G::BUF_F4;  // the two tile buffers of one image
     constexpr float LOG2E = 1.4426950408889634f;
     const float INF = __builtin_inff();
@@ -172,8 +182,8 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     const float *img = p.img + (long long)head * p.img_hs;
     const bool live = (ROLE == kDivX) && p.gimg != nullptr;  // (workgroup-uniform) contract with the tile of a second image
     const float *gimg = GIMG ? p.gimg + (long long)head * p.img_hs : (live ? p.gimg + (long long)head * p.gimg_hs : nullptr);
-    // (kDivAcc: the streamed row's norm first, as in the rows-resident roles -- its similarities are theirs bit for bit)
-    const float b_aug = (ROLE == kDivAcc) ? (h ? rn0 : 1.0f) : (h ? 1.0f : rn0);
+    // (kDivAcc / kDivC: the streamed row's norm first, as in the rows-resident roles -- its similarities are theirs bit for bit)
+    const float b_aug = DIVIMG ? (h ? rn0 : 1.0f) : (h ? 1.0f : rn0);
     const float tau2 = p.tau * LOG2E;
     const long long st0 = (long long)head * p.st_hs;
 
@@ -228,7 +238,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     };
 
     int t_begin = 0, t_end = p.ntiles;
-    if constexpr (GIMG) {
+    if constexpr (GIMG || ROLE == kDivC) {
         t_begin = (int)blockIdx.z * p.tiles_per_split;
         t_end = t_begin + p.tiles_per_split < p.ntiles ? t_begin + p.tiles_per_split : p.ntiles;
     }
@@ -242,6 +252,9 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
         t_begin = u_lo / SUB;
         t_end = (u_hi + SUB - 1) / SUB;
     }
+    // kDivC: U[n][own code] of the position the sweep is in
+    int u_pos = -1;
+    float u_own = 0.0f;
     stage(t_begin, 0);
     __syncthreads();
     for (int t = t_begin; t < t_end; ++t) {
@@ -263,7 +276,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     l4[g] = *(const f32x4 *)(p.lse + st0 + sbase + 8 * g);
-                    if constexpr (!DIV) d4[g] = *(const f32x4 *)(p.delta + st0 + sbase + 8 * g);
+                    if constexpr (!DIV || ROLE == kDivC) d4[g] = *(const f32x4 *)(p.delta + st0 + sbase + 8 * g);
                 }
             }
             // ---- the two products: acc = t (squared distance / dot product), acca = the image's multiple of a
@@ -276,7 +289,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                 if constexpr (CODES || DIV) mfma_range<DP, 0, NG>(acc, a, ta, rf);
                 else mfma_range2<DP>(acc, acca, a, ta, rf, gf);
                 if (EUCLID) {
-                    const float a_aug = (ROLE == kDivAcc) ? (h ? 1.0f : cnv) : (h ? cnv : 1.0f);
+                    const float a_aug = DIVIMG ? (h ? 1.0f : cnv) : (h ? cnv : 1.0f);
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a_aug, b_aug, acc, 0, 0, 0);
                 }
             }
@@ -307,6 +320,32 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                     if (h == 0 && row_ok) p.out[(long long)head * p.out_hs + (long long)(u / p.div_spp) * p.out_rs + row] = tot;
                     run_s = 0.0f;
                 }
+            } else if constexpr (ROLE == kDivC) {
+                // ---- acc[r] <- w (dot) / r = w / s (Euclid) of (streamed row r of the position, this lane's code), w = tau p (U - delta)
+                const int n = u / p.div_spp;
+                if (n != u_pos) {  // (workgroup-uniform)
+                    u_pos = n;
+                    u_own = row_ok ? p.U[(long long)n * p.U_rs + row] : 0.0f;
+                }
+                const int jb = (u % p.div_spp) * kTileCodes + 4 * h;
+                float sum_u = 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float tv = acc[r];
+                    const float tc = tv < 0.0f ? 0.0f : tv;  // (keeps a NaN, unlike fmaxf)
+                    const float lg = EUCLID ? -tau2 * __builtin_amdgcn_sqrtf(tc) : tau2 * tv;  // as kDivStats rounded it
+                    const float pr = __builtin_amdgcn_exp2f(lg - l4[r >> 2][r & 3]);
+                    float v = (p.tau * pr) * (u_own - d4[r >> 2][r & 3]);
+                    if (EUCLID) {
+                        v = -v * __builtin_amdgcn_rsqf(tc);  // w / s with s = -dist
+                        if (tc == 0.0f) v = 0.0f;            // s == 0: ATen's subgradient 0 (a NaN stays a NaN)
+                    }
+                    // row j of the position is real while j < div_ch; a padding row gives inf / NaN under Euclid: select, never multiply
+                    v = (jb + (r & 3) + 8 * (r >> 2) < p.div_ch) ? v : 0.0f;
+                    acc[r] = v;
+                    sum_u += v;
+                }
+                sum_ratio += sum_u;
             } else if constexpr (ROLE == kDivDelta || ROLE == kDivX) {
                 // ---- kDivDelta: run_d += p U;  kDivX: acc[r] <- w (dot) / r = w / s (Euclid) in place, w = tau p (U - delta)
                 float sum_u = 0.0f;
@@ -600,7 +639,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
 // With a RowMap (Cp > 0; the diversity loss, g == nullptr: no g image) the image is position-major: image row n Cp + j holds
 // row j of sequence position n for j < C -- source row ((j / pos_div) N + n) pos_div + j % pos_div, the j-th row m in
 // ascending order with (m / pos_div) % N == n -- and padding for C <= j < Cp and past N Cp; `stat` (a per-row array,
-// [head][stat_hs]) is copied along in image order, 0 in the padding.
+// [head][stat_hs]) is copied along in image order, 0 in the padding, and so is `stat2` when it is given (same strides).
 }  // namespace
 namespace vqi {
 struct RowMap {
@@ -609,6 +648,8 @@ struct RowMap {
     const float *stat;
     float *stat_img;
     long long stat_hs, stat_img_hs;
+    const float *stat2;  // optional second per-row array (kDivC: delta beside lse2)
+    float *stat2_img;
 };
 }  // namespace vqi
 namespace {
@@ -627,6 +668,8 @@ __global__ void __launch_bounds__(64) vq_gumbel_pack_rows(const float *__restric
         real = n < map.N && j < map.C;
         src = ((j / map.pos_div) * map.N + n) * map.pos_div + j % map.pos_div;
         map.stat_img[(long long)blockIdx.y * map.stat_img_hs + m] = real ? map.stat[(long long)blockIdx.y * map.stat_hs + src] : 0.0f;
+        if (map.stat2)
+            map.stat2_img[(long long)blockIdx.y * map.stat_img_hs + m] = real ? map.stat2[(long long)blockIdx.y * map.stat_hs + src] : 0.0f;
     }
     const float *xs = x + (long long)blockIdx.y * x_hs + (real ? src : 0) * x_rs;
     const float *gs = g ? g + (long long)blockIdx.y * g_hs + (real ? src : 0) * g_rs : xs;

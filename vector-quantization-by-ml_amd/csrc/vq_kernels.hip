@@ -437,6 +437,7 @@ int launch_gumbel_t(const GumbelParams &p, int H, int gz, hipStream_t s) {
     using GG = GumGeo<DP>;
     // packed x rows and packed g rows; kDivX: the searched codes and the live codes
     const bool two_images = ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC || (ROLE == kDivX && p.gimg);
+    // (kDivC: one streamed image and the finalize staging)
     constexpr bool no_gradient = ROLE == kGumStats || ROLE == kRmStats || ROLE == kRmCol || ROLE == kDivStats || ROLE == kDivAcc || ROLE == kDivDelta;
     const size_t tile_floats = (size_t)(two_images ? 2 : 1) * 2 * G::BUF_F4 * 4, rows_floats = (size_t)4 * 32 * G::XS;
     const size_t stage_floats = no_gradient ? 0 : (size_t)4 * (32 * GG::GS + 32);
@@ -476,6 +477,7 @@ int launch_diversity_m(int role, const GumbelParams &p, int H, int gz, int metri
         if (role == kDivStats) return launch_gumbel_t<DP, ME, kDivStats>(p, H, 1, s);
         if (role == kDivAcc) return launch_gumbel_t<DP, ME, kDivAcc>(p, H, gz, s);
         if (role == kDivDelta) return launch_gumbel_t<DP, ME, kDivDelta>(p, H, 1, s);
+        if (role == kDivC) return launch_gumbel_t<DP, ME, kDivC>(p, H, gz, s);
         return launch_gumbel_t<DP, ME, kDivX>(p, H, 1, s);
     });
 }
@@ -2041,7 +2043,7 @@ static int pack_gumbel_rows(const vq_args *a, const float *g, int64_t g_rs, int6
                                        a->D, padded_dim(a->D), a->metric, ws, ws + w.gimg_off, w.pl.img_floats, vqi::RowMap{});
 }
 
-// the only padded-dim dispatch of the eleven roles: the kGum* kernels live in build part 7, the kRm* kernels in part 8, the kDiv* kernels in part 9
+// the only padded-dim dispatch of the twelve roles: the kGum* kernels live in build part 7, the kRm* kernels in part 8, the kDiv* kernels in part 9
 static int launch_gumbel(int role, const GumbelParams &p, const vq_args *a, int gz, hipStream_t s) {
     const int DP = padded_dim(a->D);
     return with_padded_dim(DP == 512 ? 0 : DP,
@@ -2055,7 +2057,7 @@ static int launch_gumbel(int role, const GumbelParams &p, const vq_args *a, int 
                            [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim"); });
 }
 
-// grad_codes [H][K][D] of the two *_backward_codes entries: all zeros for an empty call ...
+// grad_codes [H][K][D] of the *_backward_codes entries: all zeros for an empty call ...
 static int clear_grad_codes(const vq_args *a, float *grad_codes, hipStream_t s, const char *what) {
     const hipError_t e = hipMemsetAsync(grad_codes, 0, (size_t)a->H * a->K * a->D * 4, s);
     return e == hipSuccess ? 0 : hip_fail(e, what);
@@ -2284,7 +2286,7 @@ int vq_diversity_accumulate_f32(const vq_args *a, float T, int N, int pos_div, c
         return fail(VQ_E_BADARG, who, "workspace too small or misaligned (see vq_diversity_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
     float *ws = (float *)workspace;
-    vqi::RowMap map;
+    vqi::RowMap map{};  // (no second per-row array)
     map.C = pl.Ch; map.Cp = pl.Cp; map.N = N; map.pos_div = pos_div;
     map.stat = lse2; map.stat_hs = p.st_hs;
     map.stat_img = ws + pl.lse_off; map.stat_img_hs = pl.Mp;
@@ -2332,6 +2334,79 @@ int vq_diversity_backward_x_f32(const vq_args *a, const float *live_packed, int6
     p.gimg = live_packed; p.gimg_hs = live_pk_hs;
     p.out = grad_x; p.out_rs = gx_rs; p.out_hs = gx_hs;
     return launch_gumbel(kDivX, p, a, 1, (hipStream_t)stream);
+}
+
+// The codes sweep (kDivC) over the same position-major image, the staged tiles split over blockIdx.z by kGumC's rule (every CU a
+// workgroup, at most 64 splits, at least one staged tile each).  Workspace, offsets in 4-byte units (documented in vq_mi355x.h):
+//   [x image H x img_floats][lse2 in image order H x Mp][delta in image order H x Mp][partials of gc: splits x H x K x D, splits > 1]
+struct DiversityCodesPlan {
+    DiversityPlan im;
+    long long delta_off, parts_off, floats;
+    int tiles_per_split, splits;
+};
+static DiversityCodesPlan plan_diversity_codes(int H, long long M, int K, int D, int N) {
+    DiversityCodesPlan pl;
+    pl.im = plan_diversity(H, M, K, D, N);
+    const long long blocks = (long long)((K + 127) / 128) * H;
+    long long want = (device_cus() + blocks - 1) / blocks;
+    if (want > 64) want = 64;
+    if (want > pl.im.ntiles) want = pl.im.ntiles;
+    if (want < 1) want = 1;
+    pl.tiles_per_split = (int)((pl.im.ntiles + want - 1) / want);
+    pl.splits = (pl.im.ntiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
+    pl.delta_off = pl.im.lse_off + (long long)H * pl.im.Mp;
+    pl.parts_off = pl.delta_off + (long long)H * pl.im.Mp;
+    pl.floats = pl.parts_off + (pl.splits > 1 ? (long long)pl.splits * H * K * D : 0);
+    return pl;
+}
+
+int64_t vq_diversity_codes_workspace_bytes(int H, int64_t M, int K, int D, int N) {
+    if (!diversity_shape_ok(H, M, K, D, N, 1) || M == 0 || D > 256 || !diversity_image_ok(M, D, N)) return 0;
+    return 4 * plan_diversity_codes(H, M, K, D, N).floats;
+}
+
+int vq_diversity_backward_codes_f32(const vq_args *a, float T, int N, int pos_div, const float *lse2, const float *delta,
+                                    const float *U, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream) {
+    static const char who[] = "vq_diversity_backward_codes";
+    int rc = check_common(a);
+    if (rc) return rc;
+    GumbelParams p;
+    if ((rc = fill_diversity_params(p, who, a, T, N, pos_div, {lse2, delta, U}))) return rc;
+    if (!grad_codes || !a->cb) return fail(VQ_E_BADARG, who, "null argument (grad_codes / cb)");
+    hipStream_t s = (hipStream_t)stream;
+    if (a->M == 0) return clear_grad_codes(a, grad_codes, s, "vq_diversity_backward_codes memset");
+    if (!diversity_image_ok(a->M, a->D, N)) return fail(VQ_E_UNSUPPORTED, who, "packed row image >= 2 GiB or too many rows (use row chunks)");
+    const DiversityCodesPlan pl = plan_diversity_codes(a->H, a->M, a->K, a->D, N);
+    if (!workspace || !aligned16(workspace) || workspace_bytes < 4 * pl.floats)
+        return fail(VQ_E_BADARG, who, "workspace too small or misaligned (see vq_diversity_codes_workspace_bytes)");
+    float *ws = (float *)workspace;
+    // the image is packed again here: keeping the forward's alive until backward would double the activation memory of the rows
+    vqi::RowMap map{};
+    map.C = pl.im.Ch; map.Cp = pl.im.Cp; map.N = N; map.pos_div = pos_div;
+    map.stat = lse2; map.stat_hs = p.st_hs;
+    map.stat_img = ws + pl.im.lse_off; map.stat_img_hs = pl.im.Mp;
+    map.stat2 = delta; map.stat2_img = ws + pl.delta_off;
+    if ((rc = launch<vq_gumbel_pack_rows>(dim3((unsigned)((pl.im.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
+                                          (long long)a->x_rs, (long long)a->x_hs, (const float *)nullptr, 0ll, 0ll, (long long)a->M, pl.im.Mp,
+                                          a->D, padded_dim(a->D), a->metric, ws, (float *)nullptr, pl.im.img_floats, map)))
+        return rc;
+    p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
+    p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
+    p.img = ws; p.img_hs = pl.im.img_floats; p.img_bytes = (unsigned)(pl.im.img_floats * 4);
+    p.NR = a->K; p.NS = (long long)N * pl.im.Cp;
+    p.ntiles = pl.im.ntiles;
+    p.tiles_per_split = pl.tiles_per_split;
+    p.lse = ws + pl.im.lse_off; p.delta = ws + pl.delta_off; p.st_hs = pl.im.Mp;
+    p.U = U;
+    p.div_spp = pl.im.spp; p.div_ch = (int)pl.im.Ch;
+    const long long n = (long long)a->H * a->K * a->D;
+    float *parts = ws + pl.parts_off;
+    p.out = pl.splits > 1 ? parts : grad_codes;
+    p.out_rs = a->D; p.out_hs = (long long)a->K * a->D; p.out_zs = n;
+    if ((rc = launch_gumbel(kDivC, p, a, pl.splits, s))) return rc;
+    if (pl.splits == 1) return 0;
+    return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
+                                          pl.splits, grad_codes);
 }
 
 int vq_max_fused_stages(int D, int want_sq_err) {

@@ -9,15 +9,16 @@ The reference hands the full ``similarities [h, M, K]`` tensor (its ``distances`
 
 Here the forward of the cross entropy is ONE native sweep with an online-softmax epilogue
 (``vq_softmax_stats_f32``: per row log-sum-exp + target logit).  Everything that needs actual matrix entries
-(backward passes outside the fused kernels' range, the diversity loss of a learnable codebook) works on bounded row chunks: ``vq_similarities_f32`` emits a chunk, the
+(backward passes outside the fused kernels' range, the cross entropy of a learnable codebook) works on bounded row chunks: ``vq_similarities_f32`` emits a chunk, the
 chunk's contribution is evaluated with ordinary tensor ops, and gradients flow through ``_SimilarityFn`` whose
 backward is ATen's ``_euclidean_dist_backward`` formula (two library GEMMs per chunk).  The cross entropy's backward with
 respect to x is one fused native sweep instead (``vq_ce_backward_f32``; with an EMA codebook, whose update rewrites the codes
 between forward and backward, ``vq_ce_backward_live_f32``) wherever the kernels reach: D <= 512, with live codes D <= 256.
 The diversity loss is four fused sweeps (``vq_diversity_*_f32``: row log-sum-exps, the position table [N, K], delta per row,
-grad_x -- against the live codes of an EMA codebook) for D <= 256 and a codebook that needs no gradient, from
-``DIVERSITY_FUSED_MIN_ROWS`` rows per sequence position on (``diversity_runs_fused``); the gradient with respect to a
-learnable codebook is not fused: such a call runs on the chunks, forward and backward.
+grad_x -- against the live codes of an EMA codebook) for D <= 256, from ``DIVERSITY_FUSED_MIN_ROWS`` rows per sequence
+position on (``diversity_runs_fused``); a learnable codebook gets its gradient from a fifth sweep
+(``vq_diversity_backward_codes_f32``) from ``DIVERSITY_CODES_FUSED_MIN_ROWS`` rows on (``diversity_codes_runs_fused``), unless
+its codes are rewritten before backward (live codes): such a call runs on the chunks, forward and backward.
 """
 from __future__ import annotations
 
@@ -238,6 +239,37 @@ def diversity_runs_fused(rows_per_position: int, heads: int = 1) -> bool:
     return rows_per_position // max(1, heads) >= DIVERSITY_FUSED_MIN_ROWS
 
 
+# The cut for a learnable codebook (codes that require grad).  Its gradient is one more sweep over the padded position-major
+# image (vq_diversity_backward_codes_f32), so below 32 rows per position the fused step costs what 32 rows cost while the
+# chunked step shrinks with the rows -- sooner the wider the rows.  Measured on an MI355X (profiles/diversity_codes_bench.md):
+# forward + backward of VectorQuantize(CodebookParams(learnable_codebook=True, ema_update=False),
+# codebook_diversity_loss_weight=0.5) in train mode, x [rows, 1024, D], ms, the parent commit (chunked) / fused, two
+# alternating runs each; "no" = the slower fused run was not faster than the faster parent run:
+#   D     K      4 rows                          8 rows                          16 rows
+#   32    8192   3.04 3.17 / 2.61 2.64           4.33 4.41 / 2.62 2.70           -
+#   64    1024   1.74 1.64 / 1.07 1.12           1.74 1.64 / 1.08 1.14           1.77 1.72 / 1.08 1.11
+#   64    8192   3.49 3.45 / 3.50 3.57   no      4.68 4.69 / 3.51 3.58           9.08 8.72 / 3.59 3.65
+#   128   1024   1.37 1.62 / 1.13 1.27           1.44 1.57 / 1.14 1.28           1.62 1.75 / 1.16 1.28
+#   128   8192   3.95 4.04 / 5.28 5.34   no      5.29 5.37 / 5.32 5.39   no      9.95 10.07 / 5.48 5.49
+#   256   1024   1.37 1.61 / 1.63 1.65   no      1.46 1.60 / 1.64 1.67   no      1.88 1.93 / 1.73 1.75
+#   256   8192   5.25 5.42 / 9.04 8.95   no      6.80 6.93 / 9.12 9.09   no      12.89 13.04 / 9.33 9.33
+# Per padded row width (32 / 64 / 128 / 256 dims) the cut is the fewest measured rows from which the fused step was faster at
+# every measured K; row counts between two measured ones take the higher cut.  The cut of a codebook without a gradient
+# (DIVERSITY_FUSED_MIN_ROWS) is not touched by this.
+DIVERSITY_CODES_FUSED_MIN_ROWS = {32: 4, 64: 8, 128: 16, 256: 16}
+
+
+def diversity_codes_runs_fused(rows_per_position: int, heads: int, dim: int) -> bool:
+    """The additional dispatch rule when the codes require grad, a pure function of the shape: the rows of one head at one
+    sequence position -- what the image pads to 32 -- against DIVERSITY_CODES_FUSED_MIN_ROWS of the padded row width.  32 rows
+    of a head and more always run fused."""
+    rows = rows_per_position // max(1, heads)
+    if rows >= 32:
+        return True
+    cut = next((c for dp, c in sorted(DIVERSITY_CODES_FUSED_MIN_ROWS.items()) if dim <= dp), None)
+    return cut is not None and rows >= cut
+
+
 def _position_chunks(table: torch.Tensor):
     """Row slices of a position table [N, stride] whose element-wise temporaries stay below CHUNK_BYTES."""
     return _row_slices(table.shape[0], max(1, CHUNK_BYTES // (4 * table.shape[1])))
@@ -265,8 +297,10 @@ class _DiversityFn(torch.autograd.Function):
     """The diversity loss through the fused sweeps (vq_diversity_*_f32): nothing of [M, K].  Forward: row log-sum-exps, the
     position table A [N, K], then the entropy with the reference's own tensor ops on A.  Backward: U [N, K] from A and the
     upstream gradient, delta per row, one sweep for grad_x -- against ``live_codes`` when the codes were rewritten since
-    (weights from ``codes``, contraction with ``live_codes``: the convention of _CrossEntropyFn).  No gradient for the codes:
-    the caller takes the chunked path for a learnable codebook."""
+    (weights from ``codes``, contraction with ``live_codes``: the convention of _CrossEntropyFn).  A learnable codebook
+    (``codes`` requires grad, no live codes: _diversity_fused_backend admits nothing else) gets its gradient from one more
+    sweep (vq_diversity_backward_codes_f32) that shares delta with the rows' sweep; the rows' sweep is skipped when only the
+    codes need a gradient."""
 
     @staticmethod
     def forward(ctx, x, codes, metric, temperature, n_positions, pos_div, live_codes, live_packed, backend):
@@ -289,6 +323,11 @@ class _DiversityFn(torch.autograd.Function):
         count = x.shape[0] * x.shape[1] // n_positions  # C: rows per position over all heads
         u, _ = diversity_upstream(table, g, n_positions, count, codes.shape[1])
         live, live_packed = ctx.live_codes, ctx.live_packed
+        if ctx.needs_input_grad[1]:
+            gx, gc = ctx.backend.diversity_backward_codes(x.detach(), codes.detach(), lse2, u.contiguous(), metric=metric,
+                                                          temperature=temperature, n_positions=n_positions, pos_div=pos_div,
+                                                          packed=packed, need_x=ctx.needs_input_grad[0])
+            return gx, gc, None, None, None, None, None, None, None
         if live is not None:  # read here, at backward time: the codes as they are NOW and their image
             live = live.detach()
             live_packed = live_packed() if callable(live_packed) else live_packed
@@ -298,21 +337,32 @@ class _DiversityFn(torch.autograd.Function):
         return gx, None, None, None, None, None, None, None, None
 
 
-def _diversity_fused_backend(x, codes, n_positions, pos_div):
+def _diversity_fused_backend(x, codes, n_positions, pos_div, live_codes=None):
     """The backend whose fused sweeps take this call, or None: the chunked path."""
     if os.environ.get("VQ_DIVERSITY_NO_FUSED"):  # (read per call: tests and A/B runs compare both paths)
         return None
     backend = search.get_backend()
     if not (hasattr(backend, "diversity_table") and hasattr(backend, "diversity_backward")):
         return None
-    if not x.is_cuda or (torch.is_grad_enabled() and codes.requires_grad):
+    if not x.is_cuda:
+        return None
+    # a learnable codebook: the backend needs the codes sweep, and codes that are rewritten before backward (live codes: an
+    # EMA codebook whose codes require grad for the orthogonal loss) keep the chunked path
+    learnable = torch.is_grad_enabled() and codes.requires_grad
+    if learnable and (live_codes is not None or getattr(backend, "diversity_backward_codes", None) is None):
         return None
     h, m, d = x.shape
     if pos_div is None or n_positions <= 0 or m == 0 or m % (n_positions * pos_div):
         return None
     if not diversity_runs_fused(h * m // n_positions, h):
         return None
-    return backend if backend.diversity_supported(h, m, codes.shape[1], d, n_positions, pos_div) else None
+    if learnable and not diversity_codes_runs_fused(h * m // n_positions, h, d):
+        return None
+    if not backend.diversity_supported(h, m, codes.shape[1], d, n_positions, pos_div):
+        return None
+    if learnable and not backend.diversity_codes_supported(h, m, codes.shape[1], d, n_positions, pos_div):
+        return None
+    return backend
 
 
 def codebook_diversity_loss(x: torch.Tensor, codes: torch.Tensor, metric: int, temperature: float,
@@ -323,12 +373,12 @@ def codebook_diversity_loss(x: torch.Tensor, codes: torch.Tensor, metric: int, t
 
     x [H, M, D]; position [M] int64 = sequence position of each row, or a callable that returns it (only the chunked path
     asks).  ``pos_div``: position[m] == (m // pos_div) % n_positions -- with it the fused sweeps run (_DiversityFn) wherever
-    they reach: D <= 256, a codebook that needs no gradient, diversity_runs_fused(); VQ_DIVERSITY_NO_FUSED=1 keeps the
-    chunked path.  ``live_packed``: as in cross_entropy_to_codes.
+    they reach: D <= 256, diversity_runs_fused(), and -- when ``codes`` requires grad (a learnable codebook) -- no
+    ``live_codes`` and diversity_codes_runs_fused(); VQ_DIVERSITY_NO_FUSED=1 keeps the chunked path.  ``live_packed``: as in cross_entropy_to_codes.
     Chunked over positions otherwise: every chunk holds all rows of a set of positions, so its entropies are complete and
     the loss is a plain sum over chunks.
     """
-    backend = _diversity_fused_backend(x, codes, n_positions, pos_div)
+    backend = _diversity_fused_backend(x, codes, n_positions, pos_div, live_codes)
     if backend is not None:
         return _DiversityFn.apply(x.float(), codes, metric, float(temperature), int(n_positions), int(pos_div), live_codes,
                                   live_packed, backend)

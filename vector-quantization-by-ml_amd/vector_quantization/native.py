@@ -105,6 +105,8 @@ _SIGNATURES = {
     "vq_diversity_accumulate_f32": (_int, (_ap, _f32, _int, _int, _vp, _vp, _vp, _i64, _vp)),
     "vq_diversity_delta_f32": (_int, (_ap, _f32, _int, _int, _vp, _vp, _vp, _vp)),
     "vq_diversity_backward_x_f32": (_int, (_ap, _vp, _i64, _f32, _int, _int, _vp, _vp, _vp, _vp, _i64, _i64, _vp)),
+    "vq_diversity_codes_workspace_bytes": (_i64, (_int, _i64, _int, _int, _int)),
+    "vq_diversity_backward_codes_f32": (_int, (_ap, _f32, _int, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp)),
     "vq_gumbel_sample_f32": (_int, (_ap, _f32, _vp, _vp)),
     "vq_gumbel_noise_f32": (_int, (_vp, _int, _i64, _int, _vp, _vp, _vp)),
     "vq_lfq_workspace_bytes": (_i64, (_i64, _i64, _int, _int)),
@@ -944,6 +946,41 @@ def diversity_backward_x(x: torch.Tensor, cb: torch.Tensor, lse2: torch.Tensor, 
         lp, lp_hs = live_packed.data_ptr(), live_packed.shape[-1]
     _call("vq_diversity_backward_x_f32", x.device, a, lp, lp_hs, float(temperature), n_positions, pos_div, lse2.data_ptr(),
           delta.data_ptr(), U.data_ptr(), out.data_ptr(), o_rs, o_hs)
+    return out
+
+
+def diversity_codes_supported(H: int, M: int, K: int, D: int, N: int, pos_div: int = 1) -> bool:
+    """vq_diversity_backward_codes_f32 takes this shape: exactly the shapes of diversity_supported (it packs the same image)."""
+    if D > DIVERSITY_MAX_DIM or M <= 0 or N <= 0 or pos_div <= 0 or M % (N * pos_div):
+        return False
+    return int(load().vq_diversity_codes_workspace_bytes(H, M, K, D, N)) > 0
+
+
+def diversity_backward_codes(x: torch.Tensor, cb: torch.Tensor, lse2: torch.Tensor, delta: torch.Tensor, U: torch.Tensor, *,
+                             metric: int = EUCLID, temperature: float = 1.0, n_positions: int, pos_div: int = 1,
+                             out: torch.Tensor | None = None) -> torch.Tensor:
+    """d/dcodes of the diversity loss for a learnable codebook, one fused sweep -> gc [H, K, D] (``out``: a contiguous
+    destination); lse2, delta and U as for diversity_backward_x (the rows are packed again here, in position-major order).
+    No rows: gc is all zeros.  Atomics-free: bit-identical from run to run on one device."""
+    _require_gpu(x, cb, lse2, delta, U, out)
+    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous()
+    H, M, D = x.shape
+    K = cb.shape[1]
+    assert cb.shape[0] == H and cb.shape[2] == D and n_positions > 0 and pos_div > 0 and M % (n_positions * pos_div) == 0
+    if out is None:
+        out = torch.empty((H, K, D), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (H, K, D) and out.is_contiguous() and out.device == x.device
+    _check_stat_arrays(x, M, lse2, delta)
+    _check_position_table(U, n_positions, K, x.device)
+    a = _vq_args(x, cb, metric=metric)
+    head = (float(temperature), n_positions, pos_div)
+    if M == 0:  # (the per-row arrays are empty and have no address: any aligned one stands for them; nothing reads it)
+        _call("vq_diversity_backward_codes_f32", x.device, a, *head, U.data_ptr(), U.data_ptr(), U.data_ptr(), out.data_ptr(), None, 0)
+        return out
+    assert diversity_codes_supported(H, M, K, D, n_positions, pos_div)
+    ws, ws_bytes = _sized_workspace("vq_diversity_codes_workspace_bytes", x.device, H, M, K, D, n_positions)
+    _call("vq_diversity_backward_codes_f32", x.device, a, *head, lse2.data_ptr(), delta.data_ptr(), U.data_ptr(), out.data_ptr(),
+          ws.data_ptr(), ws_bytes)
     return out
 
 

@@ -188,6 +188,22 @@ class _NativeBackend:
         return native.diversity_backward_x(x, cb, lse2, delta, u, live=live, live_packed=live_packed, **kw)
 
     @staticmethod
+    def diversity_codes_supported(H, M, K, D, n_positions, pos_div):
+        """The fused codes sweep of the diversity loss takes this shape (native.diversity_codes_supported)."""
+        return native.diversity_codes_supported(H, M, K, D, n_positions, pos_div)
+
+    @staticmethod
+    def diversity_backward_codes(x, cb, lse2, u, *, metric, temperature, n_positions, pos_div, packed=None, need_x=True):
+        """Backward of the fused diversity loss for a learnable codebook (no live codes: the searched codes are the ones that
+        learn) -> (gx | None, gc [H, K, D]): vq_diversity_delta_f32 once for both sweeps, vq_diversity_backward_x_f32 only when
+        the rows need a gradient, vq_diversity_backward_codes_f32."""
+        cb = cb.contiguous()
+        kw = dict(metric=metric, temperature=temperature, n_positions=n_positions, pos_div=pos_div)
+        delta = native.diversity_delta(x, cb, lse2, u, packed=packed, **kw)
+        gx = native.diversity_backward_x(x, cb, lse2, delta, u, packed=packed, **kw) if need_x else None
+        return gx, native.diversity_backward_codes(x, cb, lse2, delta, u, **kw)
+
+    @staticmethod
     def sample_codes(x, cb, *, metric, tau, seed, packed=None):
         """Gumbel-max sampling of the code in one sweep (vq_gumbel_sample_f32): -> idx [H, M] int64 = argmax_k of
         similarity * tau + Gumbel noise, the noise counter-based from ``seed`` (two int64 words on the device,
