@@ -202,8 +202,11 @@ int vq_quantize_backward_f32(const vq_args *a, const float *grad_out, int64_t go
 /*
  * Training-state step that FOLLOWS the hot path -- exponential-moving-average codebook update.
  * vq_ema_accumulate_f32: counts[h*K + k] += 1 and sums[(h*K + k)*D + d] += x[h, m, d] for every row m assigned to
- *   code k = idx[h*idx_hs + m*idx_rs] (rows with mask[h*M + m] == 0 are skipped; mask may be NULL).  The caller
- *   zeroes counts / sums (and all-reduces them across replicas when codebooks are synchronised).
+ *   code k = idx[h*idx_hs + m*idx_rs] (rows with mask[h*M + m] == 0 are skipped; mask may be NULL).  Rows whose index is
+ *   outside [0, K) -- negative, K or larger, compared as 64-bit values -- are skipped as well: not counted, their x rows not read.
+ *   Both this entry and vq_ema_accumulate_det_f32 ADD INTO the existing contents of counts / sums (a second call on the
+ *   same buffers doubles the contribution); the caller zeroes them for a fresh result (and all-reduces them across
+ *   replicas when codebooks are synchronised).  x, idx and mask are only read.  M == 0 returns 0 without a launch.
  *   Replaces embed_onehot.sum(1) and einsum("h n d, h n c -> h c d") -- codebooks.py:405-415 -- without the one-hot.
  * vq_ema_update_f32: cluster_size.lerp_(counts, 1-decay); embed_avg.lerp_(sums, 1-decay); embeddings =
  *   [l2norm](embed_avg / laplace_smoothing(cluster_size) * total) -- codebooks.py:411,417-425.  total_scratch: H floats.

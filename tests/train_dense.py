@@ -4,6 +4,8 @@ tests feed them (test helper; CPU only, imports neither oracle/ nor the referenc
   quantize_backward_model   vq_quantize_backward_kernel    gx = (ste ? Q go : 0) + sum_q 2 ge[q] (r_q - c_q)
   ema_update_model          vq_ema_sizes_kernel + vq_ema_codes_kernel   lerp / Laplace smoothing / optional l2norm
   residual_stats_model      vq_ema_accumulate_residual_kernel           per-stage counts and sums of the residual chain
+  accumulate_model          vq_ema_accumulate_kernel, vq_ema_accumulate_owner_kernel + vq_ema_reduce_parts_kernel
+                                                                        counts and sums of the rows of each code
 
 The residual chain r_0 = x, quant = ste ? r + (c - r) : c, r <- r - quant is elementwise IEEE add / sub: there is nothing a
 compiler can contract, so the fp32 chain computed here is the chain on the device bit for bit.  Everything after the chain
@@ -37,6 +39,18 @@ doubles the count.  None of them is fitted to a measurement.
   residual sums.  A code's sum is n_k fp32 additions (atomics in any order, or the owner kernel's partial sums plus their
     fixed-order reduction: never more than n_k additions touch a value, the one into 0 being exact); each is off by at
     most u times a partial sum of at most sum |terms| (1 + O(n u)):  n_k 2^-23 sum |terms|, in any order.
+  accumulated sums (accumulate_model: vq_ema_accumulate_kernel, vq_ema_accumulate_owner_kernel and
+    vq_ema_reduce_parts_kernel).  The same bound, counted per kernel.  Let code k have n_k rows, n_b of them in row block b,
+    B row blocks non-empty.  Inside a block its partial sum is n_b additions, the first one into 0 (exact): n_b - 1
+    roundings, whether a wave adds its queued rows into its LDS table or (one block, B = 1, n_b = n_k) the rows arrive as
+    float atomics in any order.  Merging the B partials -- atomics into the zeroed output, or the fixed-order reduction,
+    whose first addition is again into 0 -- rounds B - 1 times.  sum_b (n_b - 1) + B - 1 = n_k - 1 roundings in all, each
+    at most u times a partial sum of at most sum |terms| (1 + O(n u)); doubled and rounded up to n_k this is
+    residual_sums_bound, in any order, for all three kernels.  (Output that was not zero before the call adds one more
+    addition; the tests of the += contract use exact data.)
+  exact data (exact_inputs).  Rows are integers in [-15, 15] times 2^-3, so every partial sum of at most M <= 2^20 of them
+    is an integer below 2^24 times 2^-3: representable, every fp32 addition exact, in any order and any blocking.  On such
+    data all three kernels must return the integer model bit for bit, and an empty code +0.0.
 """
 from __future__ import annotations
 
@@ -297,6 +311,143 @@ def residual_inputs(H, M, D, Q, K, seed, *, share, drop=True):
         gone = dropped[..., None] & (torch.arange(Q)[None, None, :] >= first[..., None])
         idx = torch.where(gone, torch.full_like(idx, -1), idx)
     return x, cb, idx
+
+
+# ------------------------------------------------------------------------------------------------
+# EMA accumulation (the scatter-add)
+# ------------------------------------------------------------------------------------------------
+def _scatter_rows(vals, k, K):
+    """vals fp64 [n, D], k [n] in [0, K) -> [K, D]: the rows of each code added up in fp64, in row order."""
+    out = np.zeros((K, vals.shape[1]), dtype=np.float64)
+    if k.size:
+        order = np.argsort(k, kind="stable")
+        ks = k[order]
+        starts = np.flatnonzero(np.r_[True, ks[1:] != ks[:-1]])
+        with np.errstate(invalid="ignore"):  # (inf - inf of the non-finite inputs)
+            out[ks[starts]] = np.add.reduceat(vals[order], starts, axis=0)
+    return out
+
+
+def accumulate_model(x, idx, mask, K):
+    """x [H, M, D] fp32, idx [H, M], mask [H, M] or None -> (counts int64 [H, K], sums fp64 [H, K, D], abs_sums fp64
+    [H, K, D]).  A row contributes when its mask byte is non-zero (or there is no mask) and 0 <= idx < K."""
+    x, idx = _np32(x), _idx(idx)
+    H, M, D = x.shape
+    assert idx.shape == (H, M)
+    keep = (idx >= 0) & (idx < K)
+    if mask is not None:
+        m = np.asarray(mask.detach().cpu().numpy() if isinstance(mask, torch.Tensor) else mask)
+        assert m.shape == (H, M)
+        keep &= m != 0
+    counts = np.zeros((H, K), dtype=np.int64)
+    sums = np.zeros((H, K, D), dtype=np.float64)
+    abs_sums = np.zeros((H, K, D), dtype=np.float64)
+    for h in range(H):
+        rows = np.flatnonzero(keep[h])
+        k = idx[h, rows]
+        counts[h] = np.bincount(k, minlength=K)
+        v = x[h, rows].astype(np.float64)
+        sums[h] = _scatter_rows(v, k, K)
+        abs_sums[h] = _scatter_rows(np.abs(v), k, K)
+    return counts, sums, abs_sums
+
+
+# (H, M, K, D): what each shape is for is told where the GPU tests use them (tests/test_gpu_ema_accumulate.py)
+ACC_SHAPES = (
+    (1, 1024, 8, 32), (1, 1023, 8, 32), (1, 5000, 3, 4), (2, 4500, 70, 20), (1, 3000, 40, 5), (1, 2048, 1, 64),
+    (1, 2100, 2, 256), (1, 2100, 2, 257), (1, 2100, 2, 260), (1, 2100, 2, 512), (1, 3100, 7, 600), (1, 2100, 2, 2048),
+    (1, 2100, 2, 2052), (1, 37, 5, 3), (2, 1000, 256, 64), (1, 300, 8192, 16), (1, 1, 4, 8), (1, 0, 4, 8),
+)
+ACC_PATTERNS = ("uniform", "one_code", "last_code", "half_empty", "runs")
+ACC_MASK_SHAPES = ((2, 4500, 70, 20), (1, 3000, 40, 5))
+# owner path, atomic path, and cw = 64 with K = 70 inside the last owner's range [64, 128)
+ACC_RANGE_SHAPES = ((1, 3000, 40, 5), (2, 1000, 256, 64), (2, 4500, 70, 20))
+ACC_NONFINITE_SHAPES = ((1, 3000, 40, 5), (2, 1000, 256, 64))  # owner path, atomic path
+ACC_ROWS_PER_BLOCK = 2048  # the owner kernel's row block at these sizes (ema_owner_plan: at least 2048 rows per block)
+
+
+def acc_seed(H, M, K, D):
+    return 9000 + H * 1000003 + M * 4099 + K * 131 + D
+
+
+def _acc_indices(rng, H, M, K, pattern):
+    if pattern == "uniform":
+        return rng.integers(0, K, (H, M))
+    if pattern == "one_code":
+        return np.zeros((H, M), dtype=np.int64)
+    if pattern == "last_code":
+        return np.full((H, M), K - 1, dtype=np.int64)
+    if pattern == "half_empty":
+        return 2 * rng.integers(0, (K + 1) // 2, (H, M))
+    if pattern == "runs":
+        return np.repeat(rng.integers(0, K, (H, (M + 63) // 64)), 64, axis=1)[:, :M]
+    raise ValueError(pattern)
+
+
+def exact_inputs(H, M, K, D, seed, pattern):
+    """-> (x [H, M, D] fp32, idx [H, M] int64) CPU tensors: rows of integers in [-15, 15] times 2^-3, whose sums are exact in
+    fp32 in any order (module docstring), and one of ACC_PATTERNS: uniform / one_code (every row to code 0) / last_code
+    (every row to K - 1) / half_empty (odd codes never hit) / runs (64 consecutive rows share a code: a whole scan group
+    of the owner kernel belongs to one owner, the next group to none of its codes)."""
+    rng = np.random.default_rng(seed)
+    x = (rng.integers(-15, 16, (H, M, D)).astype(F32) * F32(0.125)).astype(F32)
+    idx = _acc_indices(rng, H, M, K, pattern).astype(np.int64).reshape(H, M)
+    return torch.from_numpy(x), torch.from_numpy(idx)
+
+
+def float_inputs(H, M, K, D, seed):
+    """-> (x, idx): randn rows with a power-of-two scale per column, 2^-20 .. 2^20 (column d: 2^(-20 + 17 d mod 41), the
+    last column 2^20), uniform indices; for the codes with k % 4 == 1 the rows come in pairs v, -v (1 - 2^-10 t), t uniform
+    in [-1, 1] (an odd row out is scaled by 2^-10), so that those sums are about 2^-10 of sum |terms|."""
+    rng = np.random.default_rng(seed)
+    e = -20 + (17 * np.arange(D)) % 41
+    if D > 1:
+        e[-1] = 20
+    x = (rng.standard_normal((H, M, D)) * np.exp2(e)).astype(F32)
+    idx = rng.integers(0, K, (H, M)).astype(np.int64).reshape(H, M)
+    for h in range(H):
+        for k in range(1, K, 4):
+            rows = np.flatnonzero(idx[h] == k)
+            a, b = rows[0:len(rows) // 2 * 2:2], rows[1::2]
+            t = rng.uniform(-1.0, 1.0, (len(a), D))
+            x[h, b] = (-x[h, a].astype(np.float64) * (1.0 - 2.0 ** -10 * t)).astype(F32)
+            x[h, rows[len(a) + len(b):]] *= F32(2.0 ** -10)  # (the odd row out)
+    return torch.from_numpy(x), torch.from_numpy(idx)
+
+
+def acc_mask(H, M, seed, keep=0.7):
+    """A random bool mask that keeps about `keep` of the rows."""
+    return torch.from_numpy(np.random.default_rng(seed + 1).random((H, M)) < keep)
+
+
+def out_of_range_indices(idx, K, seed):
+    """About a tenth of the rows get an index outside [0, K): -1, K, K + 63, 2^40, -2^63 in turn.
+    -> (idx', the rows changed [H, M] bool)."""
+    rng = np.random.default_rng(seed + 2)
+    idx = _idx(idx).copy()
+    hit = rng.random(idx.shape) < 0.1
+    bad = np.array([-1, K, K + 63, 2 ** 40, -2 ** 63], dtype=np.int64)
+    idx[hit] = bad[np.arange(int(hit.sum())) % len(bad)]
+    return torch.from_numpy(idx), torch.from_numpy(hit)
+
+
+def nonfinite_inputs(H, M, K, D, seed):
+    """float_inputs with three rows of the last head changed (D >= 3, K >= 2): row a = M // 7 has NaN in column 0; rows
+    b = M // 3 and c = M - 2 share a code other than a's, b has +inf in columns 1 and 2, c has -inf in columns 1 and 0.
+    The model's sums are then NaN at (code of a, 0) and (code of b, 1), +inf at (code of b, 2), -inf at (code of b, 0).
+    -> (x, idx, (a, b, c))."""
+    assert D >= 3 and K >= 2 and M >= 8
+    x, idx = float_inputs(H, M, K, D, seed)
+    a, b, c = M // 7, M // 3, M - 2
+    ka = int(idx[-1, a])
+    kb = (ka + 1 + int(idx[-1, b])) % K
+    if kb == ka:
+        kb = (ka + 1) % K
+    idx[-1, b] = idx[-1, c] = kb
+    x[-1, a, 0] = float("nan")
+    x[-1, b, 1] = x[-1, b, 2] = float("inf")
+    x[-1, c, 1] = x[-1, c, 0] = float("-inf")
+    return x, idx, (a, b, c)
 
 
 def error_ratio(got, want, tol):

@@ -318,7 +318,8 @@ def _search_workspace(H: int, M: int, Q: int, device, K: int = 0, D: int = 0):
 
 def _row_strides(t: torch.Tensor):
     """t is [H, M, D] (any strides, last dim contiguous) -> (row_stride, head_stride) in elements."""
-    assert t.dim() == 3 and (t.shape[-1] == 1 or t.stride(-1) == 1), "last dim must be contiguous"
+    # (a tensor without elements may carry any strides -- torch.from_numpy of an empty array gives zeros -- none is used)
+    assert t.dim() == 3 and (t.shape[-1] == 1 or t.stride(-1) == 1 or t.numel() == 0), "last dim must be contiguous"
     return int(t.stride(1)), int(t.stride(0))
 
 
