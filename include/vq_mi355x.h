@@ -447,6 +447,27 @@ int vq_diversity_backward_codes_f32(const vq_args *a, float T, int N, int pos_di
                                     const float *U, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * Orthogonal regularisation loss (utils/losses.py:23-28) without the [n, n] cosine matrix: one sweep with the same rows on
+ * both sides.  With x the n rows of a head AS GIVEN -- the entry does not normalise; the caller hands in F.normalize(codes)
+ * and differentiates through the normalisation itself; it is defined for any finite rows --
+ *   cos_ij  = x_i . x_j
+ *   rowsq_i = sum_j cos_ij^2                          (row sums of squares)
+ *   G_i     = sum_j cos_ij x_j                        (the gram matrix times the rows, [n][D])
+ *   loss    = sum_{h,i} rowsq_i / (H n^2) - 1 / n     d loss / d x_i = 4 G_i / (H n^2)   (cos is symmetric)
+ * Reads a->H, a->K (= n, the number of rows), a->D (<= 256: VQ_E_UNSUPPORTED beyond), a->metric (must be VQ_METRIC_DOT),
+ * a->x with x_rs / x_hs (the resident rows [H][n][D]; D and strides need not be multiples of 4) and a->packed with pk_hs
+ * (vq_pack_codebooks_f32 of the SAME rows with VQ_METRIC_DOT, K = n).  M, Q, cb and everything else are ignored.
+ * rowsq: [H][vq_gumbel_row_stride(n)] floats, 16-byte aligned; entries past n are not written.  gram: NULL (only rowsq is
+ * produced, the contraction is skipped) or G with (h, i, d) at gram[h*g_hs + i*g_rs + d], 16-byte aligned base, any strides.
+ * Checked before any launch (VQ_E_BADARG, vq_last_error names the argument): non-positive H, K or D, a metric other than dot,
+ * null x or packed, a null or misaligned rowsq, a misaligned gram.
+ * fp32 MFMA throughout.  The image's padding codes and a workgroup's rows past n contribute exactly nothing (selected to 0
+ * by index); a NaN / inf in a real row reaches rowsq and G of every row.  Every rowsq entry and G row is accumulated by one
+ * lane set in tile order: no float atomics, bit-identical results from run to run on one device.
+ */
+int vq_orthogonal_gram_f32(const vq_args *a, float *rowsq, float *gram, int64_t g_rs, int64_t g_hs, void *stream);
+
+/*
  * Gumbel-max sampling of the code, utils/general.py:112-129 (ind = argmax(similarities / temperature + gumbel_noise)) with
  * the noise of utils/general.py:25-30, as an epilogue of the similarity sweep: nothing of [M, K] in memory, one launch.
  *   idx[h*idx_hs + m*idx_rs] = first index of the maximum over k < K of  key = fl(fl(s * tau) + g)

@@ -15,12 +15,12 @@ if [ "${VQ_BUILD_SINGLE:-0}" = "1" ]; then
 fi
 tag=$(echo "$OUT $FLAGS" | md5sum | cut -c1-8)
 pids=()
-for part in 0 1 2 3 4 5 6 7 8 9; do
+for part in 0 1 2 3 4 5 6 7 8 9 10; do
     $HIPCC $FLAGS -DVQ_PART=$part -c csrc/vq_kernels.hip -o build/vq_part${part}_$tag.o &
     pids+=($!)
 done
 rc=0
 for pid in "${pids[@]}"; do wait "$pid" || rc=1; done
 [ $rc -eq 0 ] || { echo "build.sh: a part failed to compile" >&2; exit 1; }
-$HIPCC --offload-arch=gfx950 -shared -fPIC build/vq_part[0-9]_$tag.o -o "$OUT"
-rm -f build/vq_part[0-9]_$tag.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC build/vq_part*_$tag.o -o "$OUT"
+rm -f build/vq_part*_$tag.o

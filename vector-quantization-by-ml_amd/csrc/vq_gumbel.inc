@@ -52,6 +52,14 @@
 //              logit is +inf, p = inf and r = inf * rsqrt(inf) = NaN, which the contraction would multiply with the zero x
 //              row -- w / r of a padding row is therefore SELECTED to 0 before the contraction and the column sum
 // n(m) = (m / pos_div) % N.
+//
+// Orthogonal regularisation loss (utils/losses.py:23-28) through the same sweep, one more role (dot metric only): the codes on
+// BOTH sides, cos = x x^T of the rows x [n, D] as given (the caller normalises), nothing of [n, n] in memory:
+//   kOrth      as kDivX with w = s and no table: resident rows x, streamed the dot image of the same rows.  Each 32x32 block of
+//              cos is squared into the lane's running sum -> rowsq_i = sum_j cos_ij^2 (p.lse), then contracted with the
+//              same staged tile -> G_i = sum_j cos_ij x_j (p.out; null: the contraction and the finalize are skipped).
+//              cos of a streamed row past n and of a resident row past n is SELECTED to 0 by index before either use; a
+//              NaN / inf of a real row goes through untouched.  One lane set per row, tile order, no atomics.
 // ------------------------------------------------------------------------------------------------
 constexpr int kGumStats = 0;
 constexpr int kGumX = 1;
@@ -65,6 +73,7 @@ constexpr int kDivAcc = 8;
 constexpr int kDivDelta = 9;
 constexpr int kDivX = 10;
 constexpr int kDivC = 11;
+constexpr int kOrth = 12;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 }  // namespace
@@ -95,6 +104,7 @@ struct GumbelParams {
     long long ck_hs;
     float *colp, *ep;              // kRmCol: partials [splits][H][ck_hs]
     long long cp_zs;
+    // orthogonal role (kOrth): lse = rowsq [H][st_hs], out = G or null
     // diversity roles (tau = -T; lse: per row, kDivAcc / kDivC in image order; delta (kDivC: in image order); out: gx, kDivAcc
     // the per-head partials of A, kDivC the partials of gc)
     const float *U;                // kDivDelta / kDivX / kDivC: [N][U_rs], finite past K
@@ -181,6 +191,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     const bool row_ok = row < p.NR;
     const float *img = p.img + (long long)head * p.img_hs;
     const bool live = (ROLE == kDivX) && p.gimg != nullptr;  // (workgroup-uniform) contract with the tile of a second image
+    const bool contract = ROLE != kOrth || p.out != nullptr;  // (workgroup-uniform) kOrth without G: rowsq only
     const float *gimg = GIMG ? p.gimg + (long long)head * p.img_hs : (live ? p.gimg + (long long)head * p.gimg_hs : nullptr);
     // (kDivAcc / kDivC: the streamed row's norm first, as in the rows-resident roles -- its similarities are theirs bit for bit)
     const float b_aug = DIVIMG ? (h ? rn0 : 1.0f) : (h ? 1.0f : rn0);
@@ -346,6 +357,17 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                     sum_u += v;
                 }
                 sum_ratio += sum_u;
+            } else if constexpr (ROLE == kOrth) {
+                // ---- acc[r] <- cos of (streamed row sbase + (r&3) + 8(r>>2), this lane's resident row), 0 by index in the padding
+                float sq = 0.0f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const bool pad = !row_ok || sbase + (r & 3) + 8 * (r >> 2) >= p.NS;
+                    const float v = pad ? 0.0f : acc[r];
+                    acc[r] = v;
+                    sq = fmaf(v, v, sq);
+                }
+                run_s += sq;
             } else if constexpr (ROLE == kDivDelta || ROLE == kDivX) {
                 // ---- kDivDelta: run_d += p U;  kDivX: acc[r] <- w (dot) / r = w / s (Euclid) in place, w = tau p (U - delta)
                 float sum_u = 0.0f;
@@ -514,7 +536,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                 }
                 sum_ratio += sum_u;
             }
-            if constexpr (!STATS) {
+            if constexpr (!STATS) if (contract) {
                 // ---- contraction: gacc[J*V + e][position i, resident row] += img[streamed row (r, half)][128 J + V i + e] * acc[r]
                 const float *trow = (const float *)(live ? tb + IMG_F4 : tb) + (4 * h) * RS + V * c;
                 if constexpr (V == 4) {
@@ -598,6 +620,12 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
             if constexpr (!DIV) p.delta[st0 + row] = d / s;
         }
     } else {
+        if constexpr (ROLE == kOrth) {
+            // the two lane halves hold the two halves of every sub-tile's codes
+            run_s += __shfl_xor(run_s, 32);
+            if (h == 0 && row_ok) p.lse[st0 + row] = run_s;
+            if (p.out == nullptr) return;  // (workgroup-uniform, behind the last barrier)
+        }
         // ---------------- finalize: fragment layout -> natural rows through LDS ----------------
         // (the loop's last barrier guarantees nobody reads the tile buffers any more; the region is wave-private)
         constexpr int GS = GG::GS;

@@ -45,6 +45,7 @@
 //   vq_decode.inc        indices -> code vectors: every stage's gather and their stage-ordered sum in one pass (vq_decode_f32)
 //   vq_lfq_decode.inc    the same for the lookup-free family: codes from the index bits, no table (vq_lfq_decode_f32)
 //   vq_diversity.inc     codebook diversity loss: the head-ordered sum of the position table (its sweeps are roles of vq_gumbel.inc)
+//   (orthogonal regularisation loss: the kOrth role of vq_gumbel.inc, no file of its own)
 //   this file           host-side dispatch and the C ABI (include/vq_mi355x.h)
 //
 // Reference lines replaced (relative to the reference root): vector_quantization/codebooks.py:386-397,
@@ -71,7 +72,7 @@
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward (+ live codes)
 //   7 Gumbel straight-through backward sweeps               8 Gumbel-max sampling sweeps + Gumbel reinmax backward sweeps
-//   9 codebook diversity loss sweeps
+//   9 codebook diversity loss sweeps                       10 orthogonal regularisation loss sweep
 #ifndef VQ_PART
 #define VQ_PART -1
 #endif
@@ -482,6 +483,12 @@ int launch_diversity_m(int role, const GumbelParams &p, int H, int gz, int metri
     });
 }
 
+// the orthogonal role of the same sweep (dot metric only): a build part of its own
+template <int DP>
+int launch_orthogonal_m(const GumbelParams &p, int H, hipStream_t s) {
+    return launch_gumbel_t<DP, VQ_METRIC_DOT, kOrth>(p, H, 1, s);
+}
+
 #ifndef VQ_EXP_RESIDENT_MIN_ROWS_PER_CU
 #define VQ_EXP_RESIDENT_MIN_ROWS_PER_CU 512  // rows per CU from which the resident-codebook kernel takes a small codebook
 #endif
@@ -526,10 +533,12 @@ template <int DP> int part_sample(const AuxParams &p, int H, int metric, hipStre
 template <int DP> int part_gumbel(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <int DP> int part_reinmax(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <int DP> int part_diversity(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+template <int DP> int part_orthogonal(const GumbelParams &p, int H, hipStream_t s);
 #define VQ_DECLARE_GUMBEL_PARTS(DP)                                                                              \
     template <> int part_gumbel<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s); \
     template <> int part_reinmax<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);  \
-    template <> int part_diversity<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
+    template <> int part_diversity<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s); \
+    template <> int part_orthogonal<DP>(const GumbelParams &p, int H, hipStream_t s);
 template <int DP> int part_ce_bwd_live(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
 template <> int part_ce_bwd_live<32>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
 template <> int part_ce_bwd_live<64>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
@@ -678,6 +687,15 @@ VQ_DEFINE_DIVERSITY_PART(64)
 VQ_DEFINE_DIVERSITY_PART(128)
 VQ_DEFINE_DIVERSITY_PART(256)
 #undef VQ_DEFINE_DIVERSITY_PART
+#endif
+#if VQ_OWN(10)
+#define VQ_DEFINE_ORTHOGONAL_PART(DP) \
+    template <> int part_orthogonal<DP>(const GumbelParams &p, int H, hipStream_t s) { return launch_orthogonal_m<DP>(p, H, s); }
+VQ_DEFINE_ORTHOGONAL_PART(32)
+VQ_DEFINE_ORTHOGONAL_PART(64)
+VQ_DEFINE_ORTHOGONAL_PART(128)
+VQ_DEFINE_ORTHOGONAL_PART(256)
+#undef VQ_DEFINE_ORTHOGONAL_PART
 #endif
 }  // namespace vqi
 
@@ -2043,13 +2061,15 @@ static int pack_gumbel_rows(const vq_args *a, const float *g, int64_t g_rs, int6
                                        a->D, padded_dim(a->D), a->metric, ws, ws + w.gimg_off, w.pl.img_floats, vqi::RowMap{});
 }
 
-// the only padded-dim dispatch of the twelve roles: the kGum* kernels live in build part 7, the kRm* kernels in part 8, the kDiv* kernels in part 9
+// the only padded-dim dispatch of the thirteen roles: the kGum* kernels live in build part 7, the kRm* kernels in part 8, the kDiv* kernels in
+// part 9, kOrth in part 10
 static int launch_gumbel(int role, const GumbelParams &p, const vq_args *a, int gz, hipStream_t s) {
     const int DP = padded_dim(a->D);
     return with_padded_dim(DP == 512 ? 0 : DP,
                            [&](auto dp) {
                                constexpr int DPC = decltype(dp)::value;
                                if constexpr (DPC > 256) return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
+                               else if (role == kOrth) return vqi::part_orthogonal<DPC>(p, a->H, s);
                                else if (role >= kDivStats) return vqi::part_diversity<DPC>(role, p, a->H, gz, a->metric, s);
                                else if (role < kRmStats) return vqi::part_gumbel<DPC>(role, p, a->H, gz, a->metric, s);
                                else return vqi::part_reinmax<DPC>(role, p, a->H, gz, a->metric, s);
@@ -2407,6 +2427,33 @@ int vq_diversity_backward_codes_f32(const vq_args *a, float T, int N, int pos_di
     if (pl.splits == 1) return 0;
     return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
                                           pl.splits, grad_codes);
+}
+
+// ---- orthogonal regularisation loss: the kOrth role of vq_gumbel.inc ---------------------------------------------------
+// n = a->K rows on both sides: resident from a->x, streamed from a->packed (the dot image of the same rows)
+int vq_orthogonal_gram_f32(const vq_args *a, float *rowsq, float *gram, int64_t g_rs, int64_t g_hs, void *stream) {
+    static const char who[] = "vq_orthogonal_gram";
+    if (!a) return fail(VQ_E_BADARG, who, "args is null");
+    if (a->H <= 0 || a->K <= 0 || a->D <= 0) return fail(VQ_E_BADARG, who, "H, K (the number of rows n) and D must be positive");
+    if (a->metric != VQ_METRIC_DOT) return fail(VQ_E_BADARG, who, "metric must be VQ_METRIC_DOT");
+    if (!a->x) return fail(VQ_E_BADARG, who, "x is null");
+    if (!a->packed) return fail(VQ_E_BADARG, who, "packed is null (the dot image of the rows)");
+    if (!rowsq || !aligned16(rowsq)) return fail(VQ_E_BADARG, who, "rowsq is null or not 16-byte aligned");
+    if (gram && !aligned16(gram)) return fail(VQ_E_BADARG, who, "gram is not 16-byte aligned");
+    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, who, "D > 256");
+    if (vq_packed_floats(a->K, a->D) * 4 >= (1ll << 31)) return fail(VQ_E_UNSUPPORTED, who, "packed image >= 2 GiB");
+    GumbelParams p;
+    memset(&p, 0, sizeof(p));
+    p.D = a->D;
+    p.res = a->x; p.res_rs = a->x_rs; p.res_hs = a->x_hs;
+    p.vec_res = vec4_ok(a->x, {a->D, a->x_rs, a->x_hs}) ? 1 : 0;
+    p.img = a->packed; p.img_hs = a->pk_hs; p.img_bytes = (unsigned)(vq_packed_floats(a->K, a->D) * 4);
+    p.NR = a->K; p.NS = a->K;
+    const int tc = kTileCodes * sub_tiles(padded_dim(a->D));
+    p.ntiles = (a->K + tc - 1) / tc;
+    p.lse = rowsq; p.st_hs = vq_gumbel_row_stride(a->K);
+    p.out = gram; p.out_rs = g_rs; p.out_hs = g_hs;
+    return launch_gumbel(kOrth, p, a, 1, (hipStream_t)stream);
 }
 
 int vq_max_fused_stages(int D, int want_sq_err) {

@@ -19,6 +19,11 @@ grad_x -- against the live codes of an EMA codebook) for D <= 256, from ``DIVERS
 position on (``diversity_runs_fused``); a learnable codebook gets its gradient from a fifth sweep
 (``vq_diversity_backward_codes_f32``) from ``DIVERSITY_CODES_FUSED_MIN_ROWS`` rows on (``diversity_codes_runs_fused``), unless
 its codes are rewritten before backward (live codes): such a call runs on the chunks, forward and backward.
+The orthogonal regulariser is one fused sweep over the normalised codes (``vq_orthogonal_gram_f32``: row sums of squared
+cosines and the gram matrix times the rows, nothing of ``[n, n]``; the backward is a scale of the saved product) for CUDA fp32
+codes of d <= 256 dims from ``ORTHOGONAL_FUSED_MIN_CODES`` codes per head on (``orthogonal_runs_fused``, measured per padded
+row width and head count); everything else -- CPU
+tensors, wider rows, smaller codebooks, VQ_ORTHOGONAL_NO_FUSED=1 -- is the reference's GEMM.
 """
 from __future__ import annotations
 
@@ -26,6 +31,7 @@ import os
 
 import torch
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import search
 
@@ -411,10 +417,77 @@ def codebook_diversity_loss(x: torch.Tensor, codes: torch.Tensor, metric: int, t
 
 
 # ------------------------------------------------------------------------------------------------ orthogonal
+# Codes per head from which the fused sweep runs: per padded row width (32 / 64 / 128 / 256 dims) a map {heads: cut}; the cuts
+# of the listed head counts <= h apply to h heads (the smallest wins: more heads only add workgroups), a width without an entry
+# for the head count keeps the GEMM.  A wave owns 32 rows for the whole sweep and nothing splits the streamed side, so one head
+# of n codes is n / 32 waves on a chip of 1 024 SIMDs: a single codebook of 4 096 or 8 192 wide codes runs on a quarter of the
+# CUs and loses to the library GEMMs, eight of them fill the chip.  Measured on an MI355X (profiles/orthogonal_bench.md):
+# losses.orthogonal_loss forward + backward, ms, the parent commit (GEMM) / fused, two alternating runs each; "no" = the slower
+# fused run was not faster than the faster parent run:
+#   h  n       d = 32                     d = 64                     d = 128                       d = 256
+#   1  256     0.40 0.39 / 0.30 0.29      0.40 0.40 / 0.22 0.30      0.40 0.40 / 0.22 0.29         0.39 0.30 / 0.22 0.30  no
+#   1  512     0.41 0.42 / 0.30 0.30      0.41 0.41 / 0.22 0.30      0.41 0.41 / 0.21 0.30         0.40 0.29 / 0.22 0.30  no
+#   1  1024    0.41 0.41 / 0.30 0.30      0.41 0.41 / 0.22 0.29      0.41 0.41 / 0.22 0.30         0.41 0.29 / 0.33 0.33  no
+#   1  2048    0.41 0.41 / 0.30 0.30      0.41 0.41 / 0.23 0.30      0.41 0.41 / 0.34 0.34         0.40 0.29 / 0.59 0.59  no
+#   1  4096    0.41 0.41 / 0.31 0.31      0.40 0.41 / 0.38 0.38      0.41 0.36 / 0.61 0.61  no     0.42 0.42 / 1.09 1.09  no
+#   1  8192    0.74 0.74 / 0.45 0.45      0.80 0.80 / 0.70 0.69      0.97 0.97 / 1.14 1.14  no     1.32 1.32 / 2.08 2.08  no
+#   1  16384   2.53 2.54 / 0.83 0.83      2.78 2.80 / 1.31 1.32      3.54 3.60 / 2.20 2.19         4.92 5.09 / 4.06 4.05
+#   8  8192    4.91 4.93 / 0.78 0.78      5.62 5.59 / 1.25 1.28      7.02 7.01 / 2.18 2.17         10.09 10.08 / 4.35 4.34
+# Per padded width and measured head count the cut is the fewest measured codes from which the fused step was faster at every
+# larger measured size; sizes (and head counts) between two measured ones take the higher cut.  The memory does not depend on
+# the cut (h = 8, n = 8192: 8.4 GiB -> 49 to 385 MiB): lower the entries, or set {dp: {1: 1}}, to trade time for it.
+ORTHOGONAL_FUSED_MIN_CODES = {32: {1: 256}, 64: {1: 256}, 128: {1: 16384, 8: 8192}, 256: {1: 16384, 8: 8192}}
+ORTHOGONAL_MAX_DIM = 256  # vq_orthogonal_gram_f32: rows of one launch
+
+
+def orthogonal_runs_fused(n_codes: int, dim: int, heads: int = 1) -> bool:
+    """The dispatch rule of the orthogonal loss, a pure function of the shape: ``n_codes`` per head against the cuts that
+    ORTHOGONAL_FUSED_MIN_CODES lists for the padded row width at head counts up to ``heads``."""
+    by_heads = next((c for dp, c in sorted(ORTHOGONAL_FUSED_MIN_CODES.items()) if dim <= dp), None)
+    cuts = [c for hh, c in (by_heads or {}).items() if heads >= hh]
+    return bool(cuts) and n_codes >= min(cuts)
+
+
+class _OrthogonalFn(torch.autograd.Function):
+    """sum_{h,i,j} cos_ij^2 of rows that are already normalised, through one fused sweep (vq_orthogonal_gram_f32): nothing of
+    [n, n].  Forward: rowsq_i = sum_j cos_ij^2 and -- only when a gradient is needed -- G_i = sum_j cos_ij normed_j, saved.
+    Backward: d/d normed_i = 4 G_i (cos is symmetric: row i appears on both sides), a scale of the saved G; no second sweep."""
+
+    @staticmethod
+    def forward(ctx, normed, backend):
+        rowsq, gram = backend.orthogonal_gram(normed.detach(), want_g=ctx.needs_input_grad[0])
+        ctx.save_for_backward(gram)
+        return rowsq.sum(dtype=torch.float64).to(torch.float32)  # (no host synchronisation)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (gram,) = ctx.saved_tensors
+        return g * 4 * gram, None
+
+
+def _orthogonal_fused_backend(codes):
+    """The backend whose fused sweep takes this call, or None: the GEMM."""
+    if os.environ.get("VQ_ORTHOGONAL_NO_FUSED"):  # (read per call: tests and A/B runs compare both paths)
+        return None
+    if not (codes.is_cuda and codes.dtype == torch.float32 and codes.dim() == 3):
+        return None
+    h, n, d = codes.shape
+    if h == 0 or n == 0 or d == 0 or d > ORTHOGONAL_MAX_DIM or not orthogonal_runs_fused(n, d, h):
+        return None
+    backend = search.get_backend()
+    return backend if getattr(backend, "orthogonal_gram", None) is not None else None
+
+
 def orthogonal_loss(codes: torch.Tensor) -> torch.Tensor:
     """Eq. (2) of arXiv:2112.00384 on codes [h, n, d]  (utils/losses.py:23-28): mean squared cosine similarity
-    between codes, minus 1/n.  Touches only the codebook, so it is a plain library GEMM."""
+    between codes, minus 1/n.  Touches only the codebook.  CUDA fp32 codes of d <= 256 dims run as one fused sweep over the
+    normalised codes (_OrthogonalFn: no [n, n] matrix, forward or backward) from ORTHOGONAL_FUSED_MIN_CODES codes on;
+    VQ_ORTHOGONAL_NO_FUSED=1, CPU tensors, other dtypes, wider rows and smaller codebooks keep the library GEMM."""
     h, n = codes.shape[:2]
     normed = F.normalize(codes, p=2, dim=-1)
+    backend = _orthogonal_fused_backend(codes)
+    if backend is not None:
+        return _OrthogonalFn.apply(normed, backend) / (h * n ** 2) - (1 / n)
     cos = normed @ normed.transpose(-1, -2)
     return (cos ** 2).sum() / (h * n ** 2) - (1 / n)

@@ -107,6 +107,7 @@ _SIGNATURES = {
     "vq_diversity_backward_x_f32": (_int, (_ap, _vp, _i64, _f32, _int, _int, _vp, _vp, _vp, _vp, _i64, _i64, _vp)),
     "vq_diversity_codes_workspace_bytes": (_i64, (_int, _i64, _int, _int, _int)),
     "vq_diversity_backward_codes_f32": (_int, (_ap, _f32, _int, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp)),
+    "vq_orthogonal_gram_f32": (_int, (_ap, _vp, _vp, _i64, _i64, _vp)),
     "vq_gumbel_sample_f32": (_int, (_ap, _f32, _vp, _vp)),
     "vq_gumbel_noise_f32": (_int, (_vp, _int, _i64, _int, _vp, _vp, _vp)),
     "vq_lfq_workspace_bytes": (_i64, (_i64, _i64, _int, _int)),
@@ -983,6 +984,32 @@ def diversity_backward_codes(x: torch.Tensor, cb: torch.Tensor, lse2: torch.Tens
     _call("vq_diversity_backward_codes_f32", x.device, a, *head, lse2.data_ptr(), delta.data_ptr(), U.data_ptr(), out.data_ptr(),
           ws.data_ptr(), ws_bytes)
     return out
+
+
+ORTHOGONAL_MAX_DIM = 256  # vq_orthogonal_gram_f32: rows of one launch
+
+
+def orthogonal_gram(x: torch.Tensor, *, packed: torch.Tensor | None = None, want_g: bool = True,
+                    rowsq_out: torch.Tensor | None = None):
+    """The orthogonal regularisation loss's sweep over rows x [H, n, D] AS GIVEN (strided rows ok; the caller normalises),
+    nothing of [n, n]: -> (rowsq [H, n], G [H, n, D] or None) with cos = x x^T, rowsq_i = sum_j cos_ij^2 and
+    G_i = sum_j cos_ij x_j.  ``packed``: the DOT image of the same rows (pack_codebooks), packed here when None.
+    ``want_g=False`` skips the contraction; rowsq is bit-equal either way.  ``rowsq_out``: the padded destination
+    [H, vq_gumbel_row_stride(n)] (entries past n are left as they are).  Atomics-free: bit-identical from run to run."""
+    _require_gpu(x, packed)
+    assert x.dtype == torch.float32 and x.dim() == 3 and x.shape[1] > 0 and 0 < x.shape[2] <= ORTHOGONAL_MAX_DIM
+    H, n, D = x.shape
+    packed = _packed_image(x if x.is_contiguous() else x.contiguous(), DOT, packed, H, n, D, x.device)
+    a = _vq_args(x, x, metric=DOT, packed=packed)
+    stride = int(load().vq_gumbel_row_stride(n))
+    rowsq = torch.empty((H, stride), dtype=torch.float32, device=x.device) if rowsq_out is None else rowsq_out
+    assert rowsq.dtype == torch.float32 and tuple(rowsq.shape) == (H, stride) and rowsq.is_contiguous() and rowsq.device == x.device
+    G, g_rs, g_hs = None, 0, 0
+    if want_g:
+        G = torch.empty((H, n, D), dtype=torch.float32, device=x.device)
+        g_rs, g_hs = _row_strides(G)
+    _call("vq_orthogonal_gram_f32", x.device, a, rowsq.data_ptr(), _ptr(G), g_rs, g_hs)
+    return rowsq[:, :n], G
 
 
 E_UNSUPPORTED = -2  # VQ_E_UNSUPPORTED

@@ -204,6 +204,12 @@ class _NativeBackend:
         return gx, native.diversity_backward_codes(x, cb, lse2, delta, u, **kw)
 
     @staticmethod
+    def orthogonal_gram(x, *, want_g=True):
+        """The fused sweep of the orthogonal regularisation loss (vq_orthogonal_gram_f32) over the rows x [H, n, D] as given:
+        -> (rowsq [H, n], G [H, n, D] | None), nothing of [n, n]."""
+        return native.orthogonal_gram(x, want_g=want_g)
+
+    @staticmethod
     def sample_codes(x, cb, *, metric, tau, seed, packed=None):
         """Gumbel-max sampling of the code in one sweep (vq_gumbel_sample_f32): -> idx [H, M] int64 = argmax_k of
         similarity * tau + Gumbel noise, the noise counter-based from ``seed`` (two int64 words on the device,
