@@ -24,8 +24,9 @@
 // 32 x 32 sub-tile instead of 129 fp32 ones), starting from |c|^2 s_c s_x (the fp32 chain of the packed image times an exact
 // power of two) in the accumulator, and divides the values it keeps by sg = s_c s_x once, after the sweep.  The rounding of
 // the codes is the one first-order error left; it is a property of the codebook, which the pack kernel measures (E_c below)
-// instead of bounding it.  Each lane keeps the three lowest
-// screened values of its codes over distinct codes, and the codes of the two lowest.  A row whose two lowest screened values
+// instead of bounding it.  Each lane keeps the three lowest screened values of its codes -- as KEYS: the value with the
+// accumulator register's number in its 4 low mantissa bits, item (6) below -- and the sub-tiles of the two lowest, from which
+// their codes are decoded after the sweep (vq_scr_keys.h).  A row whose two lowest screened values
 // are further apart than the bound below can only have the screened winner as its exact winner.  The other rows are decided
 // by a second kernel on the same stream (vq_resolve_rows_kernel), none of them inside the sweep kernel, where one wave's
 // exact chains would hold the other seven at the next tile barrier.  The sweep puts them on one of two lists, which share one
@@ -67,11 +68,20 @@
 //  (5) the exact side: |P - Q| <= gamma_256 sum |x_k c'_k| <= 1.53e-5 L * 1.0001 (k-ordered fmaf chain), the two
 //      additions of xn and cn add <= u (|P + xn| + |D|) <= 1.2e-7 (L + xn + nc^2) * 1.0001; fp32 denormals in the chain
 //      < 258 * 2^-149.
-//  => |S - E| <= 1.0001 (E_c / s_c) nx + 4.63e-5 L + 3.07e-5 nc^2 + 1.21e-7 xn + (2^-13 l1 + 2^-116) / sg + 2^-140 =: delta_0
-//     ((1): 1 + 8e-6, (2): 2.4e-7, (4): 3.06e-5 on the first term; (2): 2.4e-7, (4): 3.058e-5, (5): 1.542e-5 on L).
+//  (6) the key: what the kernel keeps, compares and thresholds is not the accumulator A but its KEY, A with the 4 low mantissa
+//      bits replaced by the accumulator register's number (vq_scr_keys.h), so S = key / sg.  |key - A| <= 15 ulp(A): for a
+//      normal A <= 15 * 2^-23 |A| < 1.789e-6 |A|, and |A| is within gamma_512 of the sum of the absolute values of (4):
+//      |A| / sg <= (1 + 3.1e-5) (nc^2 + 1.002 L + 1.002 (E_c / s_c) nx), so the key costs <= 1.789e-6 nc^2 + 1.793e-6 L +
+//      1.793e-6 (E_c / s_c) nx.  A subnormal A (|A| < 2^-126, the exact 0 of a zero code that wins included) moves by
+//      <= 15 * 2^-149 < 2^-145, over sg: inside the 2^-116 / sg of (4), which was claimed for 513 * 2^-126 = 2^-116.997
+//      (the rest, 511 * 2^-126, is 2^19 times the key's share).  The padding codes' start value (finite instead of +inf,
+//      last sub-tile) is no code's screened value and stays above every threshold (vq_scr_keys.h).
+//  => |S - E| <= 1.0001 (E_c / s_c) nx + 4.81e-5 L + 3.25e-5 nc^2 + 1.21e-7 xn + (2^-13 l1 + 2^-116) / sg + 2^-140 =: delta_0
+//     ((1): 1 + 8e-6, (2): 2.4e-7, (4): 3.06e-5, (6): 1.8e-6 on the first term, 1.0000406 in all; (2): 2.4e-7, (4): 3.058e-5,
+//     (5): 1.542e-5, (6): 1.793e-6 on L, 4.804e-5 in all; (4): 3.052e-5, (5): 1.2e-7, (6): 1.789e-6 on nc^2, 3.243e-5 in all).
 //     The kernel uses delta = 1.1 delta_0: the factor covers the rounding of delta's own evaluation (a dozen fp32
 //     operations on non-negative terms, < 2e-6) and of the two fp32 sqrt.
-// A row is CERTAIN when (b1, b2 = lowest and second lowest screened values over distinct codes of the row)
+// A row is CERTAIN when (b1, b2 = lowest and second lowest keys / sg over distinct codes of the row)
 //  * b2 - b1 > 2 delta + w, w = 2^-20 (|b1| + xn + delta): every other code j has E_j >= b2 - delta > b1 + delta + w >=
 //    E_win + w, so D_j - D_win > w >= 2^-21 D_win * 2: the two squared distances cannot share a correctly rounded sqrt (two
 //    values more than 2^-21 apart relative never do -- the fp32 sweep's tie rule), the screened argmin is the unique winner;
@@ -96,7 +106,8 @@ constexpr int kScrMaxExp = 62;
 constexpr int kScrTileRoom = kTileCodes * 1040 + 128;
 static_assert(kScrChunks * 1024 + 4 * kScrTailExp + 8 <= kScrTileRoom + 4, "tiles, over-copy and tail fit the room of one tile");
 // the MFMA group (of 16 per sub-tile) after which waves 4..7 run the sweep's epilogue; waves 0..3 run it after group 0
-// (8 = half a sub-tile; profiles/cfg2_stagger.md has the figures of 5, 6, 8, 10, 12 and 14)
+// (8 = half a sub-tile; profiles/cfg2_stagger.md has the figures of 5, 6, 8, 10, 12 and 14, profiles/cfg2_tagged_keys.md
+// those of 4, 5, 6, 8 and 10 with the shorter epilogue of the tagged keys)
 #ifndef VQ_SCR_LATE_GROUP
 #define VQ_SCR_LATE_GROUP 8
 #endif
@@ -107,6 +118,7 @@ constexpr int kScrLateGroup = VQ_SCR_LATE_GROUP;
 #endif
 inline long long scr_image_bytes(int ntiles) { return ((long long)ntiles * kScrTileRoom + 4ll * ntiles + 255) / 256 * 256; }
 #include "vq_resolve_plan.h"
+#include "vq_scr_keys.h"
 // The control block behind the images (SearchParams::scr_count points at it), 32-bit words: [0] rows on the full-search list,
 // [1] rows on the rescore list, [2] exit ticket of the second pass, [4] and [5] the two counts of the previous call (no kernel
 // reads them: tests and diagnostics do); from word kScrRowTicketWord on one ticket per split full-search row, and from
@@ -868,40 +880,14 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         const unsigned cb_flag = codebook_flag(pk, p.pk_bytes);
         // (SCREEN starts from +inf: a flagged codebook makes every row uncertain instead, below)
         LaneBest lb = lane_best_start<METRIC>(SCREEN ? INF : sweep_start_value<METRIC>(cb_flag));
-        // SCREEN, per lane over its codes: lowest value b1 (lb.best_t, its code lb.pend_u), second lowest b2 (code scr_i2) and
-        // third lowest b3 over distinct codes.  Per value v: b3 = med3(b2, b3, v), b2 = med3(b1, b2, v), b1 = min(b1, v) (each
-        // med3 is the new k-th lowest because b1 <= b2 <= b3); the codes are looked up only when the two lowest change.
-        float scr_b2 = INF, scr_b3 = INF;
-        int scr_i2 = 0;
-        auto epilogue = [&](const f32x16 &v, int u) {
+        // SCREEN, per lane over its codes: the three lowest KEYS (the screened value with the accumulator register's number in
+        // its 4 low mantissa bits) and the sub-tiles in which the two lowest arrived (vq_scr_keys.h: tag, three-lowest block and
+        // sub-tile update, no branch and no search of the registers; the codes are decoded once, after the sweep).  The keys
+        // overwrite the accumulators, which are dead after their epilogue.
+        ScrTrack scr_t = scr_track_start();
+        auto epilogue = [&](f32x16 &v, int u) {
             if constexpr (SCREEN) {
-                const float o1 = lb.best_t, o2 = scr_b2;
-                float b1 = o1, b2 = o2;
-#define VQ_SCR_STEP(r) "v_med3_f32 %2, %1, %2, %" #r "\n\tv_med3_f32 %1, %0, %1, %" #r "\n\tv_min_f32 %0, %0, %" #r "\n\t"
-                asm(VQ_SCR_STEP(3) VQ_SCR_STEP(4) VQ_SCR_STEP(5) VQ_SCR_STEP(6) VQ_SCR_STEP(7) VQ_SCR_STEP(8) VQ_SCR_STEP(9)
-                    VQ_SCR_STEP(10) VQ_SCR_STEP(11) VQ_SCR_STEP(12) VQ_SCR_STEP(13) VQ_SCR_STEP(14) VQ_SCR_STEP(15) VQ_SCR_STEP(16)
-                    VQ_SCR_STEP(17) VQ_SCR_STEP(18)
-                    : "+v"(b1), "+v"(b2), "+v"(scr_b3)
-                    : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]), "v"(v[9]),
-                      "v"(v[10]), "v"(v[11]), "v"(v[12]), "v"(v[13]), "v"(v[14]), "v"(v[15]));
-#undef VQ_SCR_STEP
-                const bool nb1 = b1 < o1;
-                if (nb1 || b2 < o2) {  // the two lowest changed: their codes (lowest r holding the value, distinct codes)
-                    int off1 = 0, off2 = 0;
-#pragma unroll
-                    for (int r = 15; r >= 0; --r) off1 = (v[r] == b1) ? (r & 3) + 8 * (r >> 2) : off1;
-#pragma unroll
-                    for (int r = 15; r >= 0; --r) {
-                        const int o = (r & 3) + 8 * (r >> 2);
-                        off2 = (v[r] == b2 && !(nb1 && o == off1)) ? o : off2;
-                    }
-                    const int base = u * kTileCodes + 4 * h;
-                    const int i1 = lb.pend_u;
-                    scr_i2 = (nb1 && b2 == o1) ? i1 : base + off2;  // the old lowest demoted, or a code of this sub-tile
-                    if (nb1) lb.pend_u = base + off1;
-                    lb.best_t = b1;
-                    scr_b2 = b2;
-                }
+                scr_track_update(scr_t, v, u);
             } else {
                 tile_epilogue<METRIC, DP, false>(v, u, h, p.K, lb);
             }
@@ -924,6 +910,12 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
                 for (int q = 0; q < 4; ++q) {
                     const f32x4 cv = cn4[2 * q + h];
                     acc[4 * q + 0] = cv.x; acc[4 * q + 1] = cv.y; acc[4 * q + 2] = cv.z; acc[4 * q + 3] = cv.w;
+                }
+                // the last sub-tile may hold padding codes, whose +inf would become a NaN key: they start from a large finite
+                // value instead, which no real code's |c|^2 s_c s_x (< 2^29) reaches (vq_scr_keys.h; a wave-uniform branch)
+                if (u + 1 == t1) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = scr_start_clamp(acc[r]);
                 }
             }
 #pragma unroll
@@ -1022,10 +1014,12 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
         if constexpr (SCREEN) {
             // the screened argmin of this lane (lowest code holding the lowest value), then both lane halves of the row
             // (the accumulators are in units of s_c s_x: one exact division by that power of two for the values kept)
-            const float l1 = lb.best_t * scr_isg, l2 = scr_b2 * scr_isg;  // this lane's two lowest (codes lb.pend_u, scr_i2)
-            scr_b3 *= scr_isg;
-            const int li1 = lb.pend_u, li2 = scr_i2;
-            best_i = li1 < p.K ? li1 : p.K - 1;
+            // this lane's two lowest keys and their codes, decoded from the keys' low bits BEFORE the scaling (which keeps the
+            // order and, for normal results, the bits; the codes are right where it matters: (I1), (I2) of vq_scr_keys.h)
+            const int li1 = scr_key_code(scr_t.b1, scr_t.u1, h), li2 = scr_key_code(scr_t.b2, scr_t.u2, h);
+            const float l1 = scr_t.b1 * scr_isg, l2 = scr_t.b2 * scr_isg;
+            const float scr_b3 = scr_t.b3 * scr_isg;
+            best_i = li1 < p.K ? li1 : p.K - 1;  // (a NaN / inf row's keys decode to anything in [0, 32 ntiles))
             float b1 = l1;
             const float ob1 = __shfl_xor(l1, 32), ob2 = __shfl_xor(l2, 32), ob3 = __shfl_xor(scr_b3, 32);
             const int oi = __shfl_xor(best_i, 32);
@@ -1036,7 +1030,7 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
             }
             // certainty test (the bound: top of this file)
             const float nx = sqrtf(xn0), nc = sqrtf(scr_mcn);
-            const float delta = 1.1f * (1.0001f * scr_ecs * nx + 4.63e-5f * (2.0f * nx * nc) + 3.07e-5f * scr_mcn + 1.21e-7f * xn0 + scr_abs);
+            const float delta = 1.1f * (1.0001f * scr_ecs * nx + 4.81e-5f * (2.0f * nx * nc) + 3.25e-5f * scr_mcn + 1.21e-7f * xn0 + scr_abs);
             const float w = 0x1p-20f * (__builtin_fabsf(b1) + xn0 + delta);
             const bool eligible = cb_flag == 0u && scr_flag == 0u && xn0 * scr_sx * scr_sx <= 0x1p30f && scr_mcn <= 0x1p100f &&
                                   (b1 + xn0 > 2.0f * delta);
