@@ -15,6 +15,11 @@
  *   - return value: 0 on success, a negative VQ_E* code for argument errors, or a positive
  *     hipError_t.  vq_last_error() returns a human-readable string for the calling thread.
  *   - re-entrant across streams; no global mutable state besides the per-thread error string.
+ *   - buffers: the contents of a workspace are unspecified on entry and on exit -- every call writes what it later reads,
+ *     so a caller may hand over uninitialised memory and reuse one buffer across calls (the one exception is stated where
+ *     it applies: vq_gumbel_reinmax_backward_codes_f32 reuses what vq_gumbel_reinmax_columns_f32 left).  No call writes
+ *     outside the workspace_bytes it was given or outside the documented extent of an output; an output is written in
+ *     full unless its description names the elements that are left as they were.
  */
 #ifndef VQ_MI355X_H
 #define VQ_MI355X_H
@@ -105,7 +110,8 @@ typedef struct vq_args {
  * builds it once and hands it over in vq_args.screen: the call then launches no pack kernel.
  *   vq_screen_image_bytes: bytes of the H images plus the control block; 0 where no screened sweep exists for the shape
  *     (host arithmetic only).  The room per image is that of the earlier bf16-pair image, so buffers sized by it stay
- *     valid and the control block stays where it was; the fp16 image fills about half of it and the rest is unused.
+ *     valid and the control block stays where it was; the fp16 image fills about half of it and the rest is unused
+ *     (never written, never read).
  *   vq_pack_screen_image_f32: builds the images of `packed` (head stride pk_hs floats) into `screen` (16-byte aligned,
  *     screen_bytes == vq_screen_image_bytes(...)) and zeroes the control block.  Per head: every code as one fp16 value
  *     fp16(s_c * -2c), 32-code tiles of 528-byte rows with the tile's |c|^2 s_c s_x behind them; behind the tiles, per
@@ -113,7 +119,7 @@ typedef struct vq_args {
  *     then the exponents of the two power-of-two scales s_c, s_x (csrc/vq_search_persist.inc has the layout and the
  *     error bound that reads it).  Two kernels on `stream`.
  * One image serves one call at a time: calls that share it must be ordered on one stream (the control block holds the
- * call's counts; every call leaves it zeroed for the next).
+ * call's counts and tickets; every call leaves those zeroed for the next).
  */
 int64_t vq_screen_image_bytes(int H, int K, int D, int metric);
 int vq_pack_screen_image_f32(const float *packed, int H, int64_t pk_hs, int K, int D, int metric, void *screen,
@@ -322,7 +328,7 @@ int vq_ce_backward_live_f32(const vq_args *a, const float *live_cb, int64_t live
  *   p = softmax_k(tau s), delta_m = sum_k p_mk a_mk, w = tau p (a - delta) = dL/ds, and through the similarities
  *   dot: gx = w c, gc = w^T x;   Euclid: r = w / s (0 at s == 0), gx = x rowsum(r) - r c, gc = c colsum(r) - r^T x.
  * All three use a->x, H, M, K, D (<= 256: VQ_E_UNSUPPORTED beyond), metric and the rows g (h, m, d) at g[h*g_hs + m*g_rs + d].
- * lse2 / delta: [H][vq_gumbel_row_stride(M)] floats, 16-byte aligned.
+ * lse2 / delta: [H][vq_gumbel_row_stride(M)] floats, 16-byte aligned; columns past M are not written and reach no result.
  * vq_gumbel_stats_f32 (a->packed): writes lse2[h][m] = log2 sum_k exp2(tau s log2 e) and delta[h][m].
  * vq_gumbel_backward_x_f32 (a->packed): grad_x (h, m, d) at grad_x[h*gx_hs + m*gx_rs + d].
  * vq_gumbel_backward_codes_f32 (a->cb, the natural codebook): grad_codes [H][K][D] contiguous -- the part through the
@@ -348,8 +354,8 @@ int vq_gumbel_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs,
  *   w_mk = 2 (p1_mk / col_k)(a_mk - e_k) - 0.5 p0_mk (a_mk - delta0_m) = dL/ds, and through the similarities as above.
  * All four use a->x, H, M, K, D (<= 256: VQ_E_UNSUPPORTED beyond), metric and the rows g; tau must be positive and finite
  * (VQ_E_BADARG).  M == 0: nothing is launched (backward_codes zeroes grad_codes).
- * Per-row arrays lse2_tau / lse2_one / delta0: [H][vq_gumbel_row_stride(M)] floats; per-code arrays col / e:
- * [H][vq_gumbel_row_stride(K)] floats (entries past K are written as col = 1, e = 0); all 16-byte aligned.
+ * Per-row arrays lse2_tau / lse2_one / delta0: [H][vq_gumbel_row_stride(M)] floats (columns past M are not written and
+ * reach no result); per-code arrays col / e: [H][vq_gumbel_row_stride(K)] floats (entries past K are written as col = 1, e = 0); all 16-byte aligned.
  * ind: int64, element (h, m) at ind[h*ind_hs + m*ind_rs].  It is only ever COMPARED with a code index: a value outside
  * [0, K) selects nothing.  It need not be the argmax of the similarities.
  * vq_gumbel_reinmax_stats_f32 (a->packed): lse2_tau[h][m] = log2 sum_k exp2(tau s log2 e), lse2_one the same at tau = 1, delta0.
@@ -398,8 +404,9 @@ int vq_gumbel_reinmax_backward_codes_f32(const vq_args *a, const float *g, int64
  * All five use a->x (strided rows), H, M, K, D (<= 256: VQ_E_UNSUPPORTED beyond) and metric; Q is ignored.  Checked before
  * any launch (VQ_E_BADARG): T finite; N > 0, pos_div > 0 and M a multiple of N * pos_div; every array argument non-null
  * and 16-byte aligned.  M == 0: nothing is launched and nothing is written (backward_codes zeroes grad_codes).
- * lse2, delta: [H][vq_gumbel_row_stride(M)] floats (columns past M unused).  A, U: [N][vq_gumbel_row_stride(K)] floats; the
- * entries of A past K are written as 0, those of U must be finite (they are read and discarded).
+ * lse2, delta: [H][vq_gumbel_row_stride(M)] floats (columns past M are not written and reach no result).
+ * A, U: [N][vq_gumbel_row_stride(K)] floats; the entries of A past K are written as 0, those of U must be finite (they are
+ * read and discarded).
  * vq_diversity_stats_f32 (a->packed): lse2[h][m] = log2 sum_k exp2(-T s log2 e).
  * vq_diversity_accumulate_f32 (a->cb, the natural codes): writes A.  The rows are packed into the workspace in position-major
  *   order -- image row n*Cp + j holds row ((j / pos_div) N + n) pos_div + j % pos_div for j < M / N, with
