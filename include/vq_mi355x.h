@@ -240,6 +240,51 @@ int vq_ema_update_f32(float *cluster_size, float *embed_avg, float *embeddings, 
                       float *total_scratch, int H, int K, int D, double decay, float eps, int l2norm, void *stream);
 
 /*
+ * Dead-code expiry decided and carried out on the device (codebooks.py:216-262, expire_codes_ / replace): no host
+ * synchronisation, capturable in a hipGraph.  Two launches on `stream`, issued whatever the cluster sizes hold.
+ * Per head h of cluster_size [H][K], embed_avg [H][K][D], embeddings [H][K][D] (contiguous):
+ *   code k is dead iff cluster_size[h][k] < threshold, an fp32 comparison (a NaN is not dead); its rank r is the number of
+ *   dead codes below k, n_dead the number of dead codes of the head.  The three entries of a live code are not written.
+ *   A dead code gets embeddings[h][k][:] = row, cluster_size[h][k] = reset_cluster_size, embed_avg[h][k][:] =
+ *   fl(row * reset_cluster_size), where row is pool row sel(h, r) -- element (h, n, d) of the pool at
+ *   pool[h*pool_hs + n*pool_rs + d], N rows per head, pool_hs may be 0 (one pool for all heads) -- copied bit for bit when
+ *   l2norm == 0, and divided by max(||row||, 1e-12) when l2norm == 1 (F.normalize of the picked row: fp32 sum of squares, one
+ *   square root, one division per element; an all-zero row stays zero).
+ * Row selection: sel(h, r) is a function of (seed, h, r, n_dead <= N, N) only, never of the launch geometry.  P(c0, c1) names
+ * the four words of Philox4x32-10 (the generator of vq_gumbel_sample_f32) with
+ *   key      k0 = seed[0] bits 31..0, k1 = seed[0] bits 63..32
+ *   counter  (c0, c1) as given, (c3 : c2) = (h << 32) + seed[1]  (mod 2^64, c2 the low word).
+ *   n_dead > N (with replacement, the reference's randint): w = P(r, 0xFFFFFFFF); sel = ((w[1] << 32) | w[0]) mod N.
+ *   n_dead <= N (without replacement, the reference's randperm(N)[:n_dead]): b = the bit length of N - 1 (0 for N == 1), so
+ *     that 2^b < 2N.  One application of the bijection F of [0, 2^b) is six Feistel rounds on uneven halves: with widths
+ *     wl = b / 2 (rounded down) and wr = b - wl, round i = 0 .. 5 splits y into hi = y >> wr and lo = y mod 2^wr and sets
+ *     y = (lo << wl) | ((hi xor P(lo, i)[0]) mod 2^wl), then swaps wl and wr.  Cycle walk: y = r; repeat y = F(y) until
+ *     y < N, at most 64 applications; sel = y.  F is a bijection, so sel(h, .) is injective on [0, N).  A walk from a point
+ *     below N leaves [0, N) for at most 2^b - N applications in a row, so the bound cannot be reached at all while
+ *     2^b - N < 64; beyond that every application lands below N with probability above 1/2 (N / 2^b), and a walk reaches the bound
+ *     with probability below 2^-64 per dead code (F taken as a random permutation).  At the bound sel = y - N: inside [0, N),
+ *     as y < 2^b < 2N, but the head's selection may then hold that row twice.
+ * picked (may be NULL): picked[h][k] = sel for a dead code, -1 for a live one (written in full).  n_expired (may be NULL):
+ *   n_expired[h] = n_dead.  seed: TWO 64-bit words on the DEVICE.
+ * Residual chain: with chain != NULL the pool is not read (pool may be NULL; N = chain->M).  Row n of the pool is the
+ *   stage-`stage` residual of row n of chain->x, rebuilt for the picked rows only with the fp32 operations of the
+ *   straight-through chain in its order: r = x; for j < stage: c = cb_j[idx[n][j]]; quant = r + (c - r); r = r - quant (an
+ *   index outside [0, K) ends the row's chain, as in vq_ema_accumulate_residual_f32).  Reads chain->x (x_rs), chain->cb
+ *   (stages cb_qs apart; 0 = shared), chain->idx (idx_rs, idx_qs), M, K, D, Q; H and chain->H must be 1, K and D the
+ *   codebook's, 0 <= stage < Q.  chain->cb must not overlap `embeddings` (the stage codes of the forward are a copy).
+ * workspace: >= vq_expire_workspace_bytes(H, K) bytes, 16-byte aligned ([n_dead: H int32][dead codes in ascending order:
+ *   H * K int32]).  N == 0, H == 0 or K == 0: returns 0 without a launch (nothing is written).  VQ_E_BADARG: D < 1, a
+ *   negative size, H > 65535, a null required pointer, a chain that does not fit.
+ * Rows of any D and alignment: 16-byte accesses when D % 4 == 0 and the picked row, the code's two rows and the chain's
+ *   codebooks lie on the 16-byte grid (decided per picked row), else one float at a time.
+ */
+int64_t vq_expire_workspace_bytes(int H, int K);
+int vq_expire_codes_f32(float *cluster_size, float *embed_avg, float *embeddings, const float *pool, int64_t pool_rs, int64_t pool_hs,
+                        int64_t N, const vq_args *chain, int stage, int H, int K, int D, float threshold, float reset_cluster_size,
+                        int l2norm, const int64_t *seed /* 2 words, device */, int64_t *picked /* [H][K] or NULL */,
+                        int32_t *n_expired /* [H] or NULL */, void *workspace, void *stream);
+
+/*
  * Affine re-parameterisation of a codebook (codebooks.py:275-348, 379-384, 400-403).
  *
  * vq_affine_stats_f32: per-column statistics of the rows (h, m, :) at x[h*x_hs + m*x_rs + d] in ONE read of x:

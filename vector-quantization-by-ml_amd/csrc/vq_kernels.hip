@@ -68,7 +68,7 @@
 // the same file once per part (-DVQ_PART=n, in parallel) and links the objects: every part sees the same templates, but only
 // its own launchers are defined -- and with them instantiated -- there; the other parts call them through the
 // vqi::part_* entry points declared below.
-//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, LFQ, FSQ, LQ, affine, decodes) 4 search Dp = 512 + wave-pair kernel
+//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, expiry, LFQ, FSQ, LQ, affine, decodes) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward (+ live codes)
 //   7 Gumbel straight-through backward sweeps               8 Gumbel-max sampling sweeps + Gumbel reinmax backward sweeps
@@ -97,6 +97,7 @@ namespace {
 #include "vq_gumbel.inc"
 #if VQ_OWN(0)
 #include "vq_finalize_ema.inc"
+#include "vq_expire.inc"
 #include "vq_lfq.inc"
 #include "vq_rlfq.inc"
 #include "vq_fsq.inc"
@@ -1746,6 +1747,49 @@ int vq_ema_update_f32(float *cluster_size, float *embed_avg, float *embeddings, 
     const long long rows = (long long)H * K;
     return launch<vq_ema_codes_kernel>(dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, "vq_ema_update launch", cluster_size, total_scratch, embed_avg,
                                        sums, embeddings, H, K, D, weight, eps, l2norm);
+}
+
+static int64_t expire_round16(int64_t n) { return (n + 15) / 16 * 16; }
+
+int64_t vq_expire_workspace_bytes(int H, int K) {
+    if (H < 0 || K < 0) return 0;
+    return expire_round16((int64_t)H * 4) + expire_round16((int64_t)H * K * 4) + 16;  // [n_dead: H][list: H * K], int32
+}
+
+int vq_expire_codes_f32(float *cluster_size, float *embed_avg, float *embeddings, const float *pool, int64_t pool_rs, int64_t pool_hs,
+                        int64_t N, const vq_args *chain, int stage, int H, int K, int D, float threshold, float reset_cluster_size,
+                        int l2norm, const int64_t *seed, int64_t *picked, int32_t *n_expired, void *workspace, void *stream) {
+    if (H < 0 || K < 0 || D < 1 || H > 65535) return fail(VQ_E_BADARG, "vq_expire_codes: bad size (H in [0, 65535], K >= 0, D >= 1)");
+    ExpireChain ch = {};
+    if (chain) {
+        if (H > 1 || chain->H != 1 || chain->K != K || chain->D != D || stage < 0 || stage >= chain->Q || chain->M < 0)
+            return fail(VQ_E_BADARG, "vq_expire_codes: the chain needs H == 1, the codebook's K and D, and 0 <= stage < Q");
+        N = chain->M;
+    }
+    if (N < 0) return fail(VQ_E_BADARG, "vq_expire_codes: negative N");
+    if (N == 0 || H == 0 || K == 0) return 0;
+    if (!cluster_size || !embed_avg || !embeddings || !seed || !workspace)
+        return fail(VQ_E_BADARG, "vq_expire_codes: cluster_size / embed_avg / embeddings / seed / workspace is null");
+    if ((uintptr_t)workspace & 15) return fail(VQ_E_BADARG, "vq_expire_codes: workspace is not 16-byte aligned");
+    if (chain) {
+        if (!chain->x || (stage > 0 && (!chain->cb || !chain->idx))) return fail(VQ_E_BADARG, "vq_expire_codes: chain x / cb / idx is null");
+        ch.x = chain->x, ch.x_rs = chain->x_rs, ch.cb = chain->cb, ch.cb_qs = chain->cb_qs;
+        ch.idx = (const long long *)chain->idx, ch.idx_rs = chain->idx_rs, ch.idx_qs = chain->idx_qs, ch.stage = stage;
+    } else if (!pool) {
+        return fail(VQ_E_BADARG, "vq_expire_codes: pool is null and no chain is given");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    int *n_dead_ws = (int *)workspace;
+    int *list_ws = (int *)((char *)workspace + expire_round16((int64_t)H * 4));
+    if (int rc = launch<vq_expire_scan_kernel>(dim3((unsigned)H), dim3(256), 0, s, "vq_expire_scan launch", (const float *)cluster_size, K, threshold,
+                                               n_dead_ws, list_ws, (long long *)picked, (int *)n_expired))
+        return rc;
+    int blocks = (K + 3) / 4;
+    if (blocks > 2048) blocks = 2048;
+    return launch<vq_expire_copy_kernel>(dim3((unsigned)blocks, (unsigned)H), dim3(256), 0, s, "vq_expire_copy launch", cluster_size, embed_avg,
+                                         embeddings, pool, (long long)pool_rs, (long long)pool_hs, (long long)N, ch, chain ? 1 : 0, K, D,
+                                         reset_cluster_size, l2norm ? 1 : 0, (const long long *)seed, (long long *)picked,
+                                         (const int *)n_dead_ws, (const int *)list_ws);
 }
 
 int64_t vq_affine_stats_workspace_bytes(int H, int64_t M, int D) {

@@ -16,9 +16,9 @@ table of values) runs the per-dimension level search, the straight-through value
 in one HIP pass over the caller's channel-first tensor.
 """
 from . import ops  # noqa: F401  (registers torch.ops.vq_mi355x.*)
-from .codebook import Codebook
+from .codebook import Codebook, set_expire_on_device
 from .finite_scalar_quantization import FSQ
-from .graphs import GraphedForward
+from .graphs import GraphedForward, GraphedTrainForward
 from .latent_quantization import LatentQuantize
 from .lookup_free_quantization import LFQ
 from .params import AffineParameters, CodebookParams, GumbelParams, KmeansParameters
@@ -35,6 +35,7 @@ __all__ = [
     "CodebookParams",
     "FSQ",
     "GraphedForward",
+    "GraphedTrainForward",
     "GroupedResidualFSQ",
     "GroupedResidualLFQ",
     "GroupedResidualVQ",
@@ -49,4 +50,5 @@ __all__ = [
     "ResidualVQ",
     "ShardedCodebookSearch",
     "VectorQuantize",
+    "set_expire_on_device",
 ]

@@ -96,6 +96,16 @@ def _affine_std(variance: torch.Tensor) -> torch.Tensor:
     return variance.clamp(min=1e-5).sqrt()
 
 
+def set_expire_on_device(module: nn.Module, enabled: bool = True) -> nn.Module:
+    """Switch every ``Codebook`` below ``module`` to (or back from) dead-code expiry on the device: the training forward then
+    never waits for the GPU and can be captured in a graph (graphs.GraphedTrainForward).  The replacement rows are then chosen
+    by the rule of vq_expire_codes_f32 from ONE seed drawn from torch's generator per expiry step, not by randperm / randint."""
+    for m in module.modules():
+        if isinstance(m, Codebook):
+            m.expire_on_device = bool(enabled)
+    return module
+
+
 class _AffineCodes(torch.autograd.Function):
     """codes [h, K, D] -> (codes - codebook_mean) * (batch_std / codebook_std) + batch_mean, natively (vq_affine_apply_f32,
     mode 0) when ``fused`` is the backend's hook, else with the reference's own op sequence.  Backward: g * scale; the scale
@@ -201,6 +211,9 @@ class Codebook(nn.Module):
             self.register_buffer("codebook_mean", torch.zeros(num_codebooks, 1, dim))
             self.register_buffer("codebook_variance_needs_init", torch.Tensor([True]))
             self.register_buffer("codebook_variance", torch.zeros(num_codebooks, 1, dim))
+        # opt-in (set_expire_on_device): dead codes are found and re-seeded by launches that never make the host wait, with
+        # rows chosen by a counter-based rule instead of torch.randperm / randint.  Not part of the state_dict.
+        self.expire_on_device = False
         # host-side mirror of the two *_needs_init flags (no device read in steady state; refreshed by load_state_dict)
         self._codebook_stats_need_init = True
         # the statistics the current forward uses (update_affine) and the effective codes made from them
@@ -636,11 +649,42 @@ class Codebook(nn.Module):
         self.embeddings.data.copy_(fresh)
         self.invalidate_packed()
 
+    def _expire_on_device(self, flat, sharded: bool = False):
+        """reseed_dead_codes with ``expire_on_device``: one seed from torch's generator (on the device), then the backend's
+        launches, issued whether or not a code expired -- no ``.any()``, no ``.item()``, nothing the host waits for."""
+        from . import gumbel
+
+        if sharded or (self.use_ddp and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            raise NotImplementedError("expire_on_device draws the replacement rows on each device for itself: replicas (use_ddp) "
+                                      "and the shards of a sharded codebook would not stay identical; turn it off for them")
+        expire = getattr(search.get_backend(), "expire_codes", None)
+        if expire is None:
+            raise RuntimeError("expire_on_device needs a backend with the native expiry kernel (expire_codes)")
+        pool, chain, stage = None, None, 0
+        if isinstance(flat, tuple):  # (x [M, D], stage codes [Q | 1, K, D], idx [M, Q], q): the residual r_q is never made
+            x, codes, idx, stage = flat
+            chain = (x if x.dtype == torch.float32 else x.float(), codes.contiguous(), idx)
+        else:
+            pool = flat() if callable(flat) else flat
+            if pool.dtype != torch.float32:
+                pool = pool.float()
+            if pool.stride(-1) != 1 and pool.shape[-1] != 1:
+                pool = pool.contiguous()
+        seed = gumbel.draw_seed(self.embeddings.device)
+        expire(self.cluster_size.data, self.embed_avg.data, self.embeddings.data, pool, chain=chain, stage=stage,
+               threshold=self.threshold_ema_dead_code, reset_cluster_size=self.reset_cluster_size,
+               l2norm=self.weights_regularization is _unit_rows, seed=seed)
+        self.invalidate_packed()
+
     @torch.no_grad()
-    def reseed_dead_codes(self, flat):
-        """``flat`` [h, M, D], or a callable producing it (evaluated only if some code actually expired)."""
+    def reseed_dead_codes(self, flat, sharded: bool = False):
+        """``flat`` [h, M, D], or a callable producing it (evaluated only if some code actually expired).  With
+        ``expire_on_device`` also a residual chain (x [M, D], codes [Q | 1, K, D], idx [M, Q], stage), and the whole step is
+        left to the device (see _expire_on_device); ``sharded``: the codebook is one shard of a larger one."""
         if self.threshold_ema_dead_code == 0:
             return
+        if self.expire_on_device:
+            return self._expire_on_device(flat, sharded)
         dead = self.cluster_size < self.threshold_ema_dead_code
         if not bool(dead.any()):
             return

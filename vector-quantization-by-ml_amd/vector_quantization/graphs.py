@@ -10,6 +10,9 @@ hipGraph and replayed with one launch.
 
 The outputs are the graph's own static tensors: copy them if they must outlive the next call.  The codebook is read at
 replay time (its buffer address is captured, not its values), so loading new weights in place needs no re-capture.
+
+``GraphedTrainForward`` does the same for a train-mode forward without gradients -- search, EMA update and dead-code expiry in
+one graph -- for modules whose codebooks expire their dead codes on the device (``set_expire_on_device``).
 """
 from __future__ import annotations
 
@@ -20,10 +23,15 @@ from torch import nn
 class GraphedForward:
     def __init__(self, module: nn.Module, example: torch.Tensor, warmup: int = 2, **forward_kwargs):
         if module.training:
-            raise ValueError("GraphedForward captures inference: call module.eval() first "
-                             "(training forwards update the codebook and may synchronise for dead-code expiry)")
+            raise ValueError("GraphedForward captures inference: call module.eval() first (a training forward updates the "
+                             "codebook, and its default dead-code expiry synchronises; GraphedTrainForward captures one "
+                             "whose codebooks expire on the device)")
         if not example.is_cuda:
             raise ValueError("GraphedForward needs a ROCm device tensor")
+        self._capture(module, example, warmup, forward_kwargs)
+
+    def _capture(self, module, example, warmup, forward_kwargs):
+        """Warm up on a side stream, then record one no-grad forward of ``module`` (in the mode it is in) on ``example``."""
         self.module = module
         self.static_in = example.clone()
         self._kwargs = forward_kwargs
@@ -59,3 +67,33 @@ class GraphedForward:
         self.static_in.copy_(x, non_blocking=True)
         self.graph.replay()
         return self.static_out
+
+
+class GraphedTrainForward(GraphedForward):
+    """hipGraph replay of a TRAIN-mode forward without gradients: search, EMA update and dead-code expiry are nodes of the
+    graph, so one replay is one whole training step of the codebooks (a tokenizer trained by EMA alone, or the codebook side of
+    a step whose gradients are taken elsewhere).  Every ``Codebook`` below ``module`` must expire its dead codes on the device
+    (``set_expire_on_device``): the default expiry step asks the host whether a code died, which a capture cannot record.
+
+    The ``warmup`` forwards on ``example`` are real training steps: they move the codebooks.  Each replay draws a fresh
+    expiry seed from torch's generator (the graph registers its Philox offset), so ``torch.manual_seed`` governs replays too.
+
+        vq.set_expire_on_device(module.train())
+        step = GraphedTrainForward(module, example_input)
+        quantized, indices, loss = step(x)          # outputs are the graph's static tensors
+    """
+
+    def __init__(self, module: nn.Module, example: torch.Tensor, warmup: int = 2, **forward_kwargs):
+        from .codebook import Codebook
+
+        if not module.training:
+            raise ValueError("GraphedTrainForward captures a training forward: call module.train() first "
+                             "(GraphedForward captures inference)")
+        books = [m for m in module.modules() if isinstance(m, Codebook)]
+        if not books or not all(m.expire_on_device for m in books):
+            raise ValueError("GraphedTrainForward needs expire_on_device on every Codebook below the module "
+                             "(vector_quantization.set_expire_on_device): the default dead-code expiry synchronises")
+        if not example.is_cuda:
+            raise ValueError("GraphedTrainForward needs a ROCm device tensor")
+        # (a replay reads the codes the previous replay left: the packs are nodes of the graph here too)
+        self._capture(module, example, warmup, forward_kwargs)

@@ -81,6 +81,9 @@ _SIGNATURES = {
                                          _vp)),
     "vq_ema_accumulate_residual_f32": (_int, (_ap, _vp, _vp, _vp)),
     "vq_ema_update_f32": (_int, (_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, ctypes.c_double, _f32, _int, _vp)),
+    "vq_expire_workspace_bytes": (_i64, (_int, _int)),
+    "vq_expire_codes_f32": (_int, (_vp, _vp, _vp, _vp, _i64, _i64, _i64, _ap, _int, _int, _int, _int, _f32, _f32, _int, _vp, _vp,
+                                   _vp, _vp, _vp)),
     "vq_affine_stats_workspace_bytes": (_i64, (_int, _i64, _int)),
     "vq_affine_stats_f32": (_int, (_vp, _i64, _i64, _vp, _i64, _i64, _int, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp)),
     "vq_affine_apply_f32": (_int, (_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _int, _vp)),
@@ -544,6 +547,52 @@ def ema_update(cluster_size: torch.Tensor, embed_avg: torch.Tensor, embeddings: 
     total = torch.empty((H,), dtype=torch.float32, device=dev)
     _call("vq_ema_update_f32", dev, cluster_size.data_ptr(), embed_avg.data_ptr(), embeddings.data_ptr(), counts.data_ptr(),
           sums.data_ptr(), total.data_ptr(), H, K, D, float(decay), float(eps), 1 if l2norm else 0)
+
+
+def expire_codes(cluster_size: torch.Tensor, embed_avg: torch.Tensor, embeddings: torch.Tensor, pool: torch.Tensor | None = None, *,
+                 chain=None, stage: int = 0, threshold: float, reset_cluster_size: float, l2norm: bool, seed: torch.Tensor,
+                 want_picked: bool = False):
+    """Dead-code expiry on the device (vq_expire_codes_f32), in place on the module buffers ([H, K], [H, K, D], [H, K, D];
+    contiguous fp32): every code with cluster_size < threshold takes a row of ``pool`` [H | 1, N, D] (strided rows ok; one
+    pool may serve all heads), chosen from ``seed`` (two int64 words on the device) by the rule in the header, normalised with
+    ``l2norm``.  ``chain`` = (x [M, D], codes [Q | 1, K, D] contiguous, idx [M, Q]) instead of a pool (H == 1): the pool is
+    the stage-``stage`` residual of x, rebuilt for the picked rows only.  Nothing is read back: no host synchronisation.
+    -> (n_expired [H] int32, picked [H, K] int64 (-1 for a live code) or None)."""
+    _require_gpu(cluster_size, embed_avg, embeddings, pool, seed)
+    for t in (cluster_size, embed_avg, embeddings):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    H, K, D = embeddings.shape
+    assert tuple(embed_avg.shape) == (H, K, D) and tuple(cluster_size.shape) == (H, K)
+    dev = embeddings.device
+    _check_seed(seed, dev)
+    n_expired = torch.zeros((H,), dtype=torch.int32, device=dev)  # (stays 0 where the library launches nothing: N == 0)
+    picked = torch.empty((H, K), dtype=torch.int64, device=dev) if want_picked else None
+    ws, _ = _sized_workspace("vq_expire_workspace_bytes", dev, H, K)
+    a, pool_rs, pool_hs, N = None, 0, 0, 0
+    if chain is not None:
+        assert pool is None and H == 1, "a residual chain stands in for the pool of ONE codebook"
+        x, codes, idx = chain
+        _require_gpu(x, codes, idx)
+        assert x.dtype == torch.float32 and codes.dtype == torch.float32 and codes.is_contiguous() and idx.dtype == torch.int64
+        x = x.reshape(1, -1, D) if x.dim() == 2 else x
+        Q = idx.shape[-1]
+        assert codes.dim() == 3 and tuple(codes.shape[1:]) == (K, D) and codes.shape[0] in (1, Q) and 0 <= stage < Q
+        assert tuple(idx.shape[-2:]) == (x.shape[1], Q)
+        idx3 = idx if idx.dim() == 3 else idx[None]
+        a = _vq_args(x, codes[None], Q=Q, shared=codes.shape[0] == 1 and Q > 1, idx=idx3)
+        N = x.shape[1]
+    else:
+        assert pool is not None and pool.dtype == torch.float32 and pool.dim() == 3 and pool.shape[0] in (1, H) and pool.shape[2] == D
+        N = pool.shape[1]
+        pool_rs, pool_hs = _row_strides(pool)
+        if pool.shape[0] == 1:
+            pool_hs = 0
+    _call("vq_expire_codes_f32", dev, cluster_size.data_ptr(), embed_avg.data_ptr(), embeddings.data_ptr(), _ptr(pool), pool_rs,
+          pool_hs, N, a, int(stage), H, K, D, float(threshold), float(reset_cluster_size), 1 if l2norm else 0, seed.data_ptr(),
+          _ptr(picked), n_expired.data_ptr(), ws.data_ptr())
+    if picked is not None and N == 0:  # (no rows to pick from: the library launched nothing)
+        picked.fill_(-1)
+    return n_expired, picked
 
 
 def column_stats(x: torch.Tensor, mask: torch.Tensor | None = None):

@@ -8,6 +8,9 @@ instead of breaking the graph at an opaque Python call:
     torch.ops.vq_mi355x.quantize_into(x, cb, packed, out, idx, metric, ste, want_sq_err, share, per_head) -> sq_err
         (writes the quantized rows and the indices into the caller's -- possibly strided -- ``out`` / ``idx`` views)
     torch.ops.vq_mi355x.gumbel_sample(x, cb, packed, seed, metric, tau) -> idx [H, M]   (Gumbel-max sampling, native.sample_codes)
+    torch.ops.vq_mi355x.expire_codes(cluster_size, embed_avg, embeddings, pool, chain_x, chain_codes, chain_idx, stage,
+        threshold, reset_cluster_size, l2norm, seed) -> picked [H, K]   (dead-code expiry on the device, native.expire_codes;
+        mutates the three buffers)
     torch.ops.vq_mi355x.lfq_quantize / lfq_entropy_fwd / lfq_entropy_bwd   (lookup-free quantization, native.lfq_*)
     torch.ops.vq_mi355x.rlfq_quantize / rlfq_backward / lfq_entropy_staged_fwd / lfq_entropy_staged_bwd
         (residual LFQ, native.rlfq_* and native.lfq_entropy_staged_*)
@@ -77,6 +80,22 @@ def gumbel_sample(x: torch.Tensor, cb: torch.Tensor, packed: Optional[torch.Tens
 @gumbel_sample.register_fake
 def _(x, cb, packed, seed, metric, tau):
     return x.new_empty((x.shape[0], x.shape[1]), dtype=torch.int64)
+
+
+@torch.library.custom_op(f"{_LIB_NS}::expire_codes", mutates_args=("cluster_size", "embed_avg", "embeddings"))
+def expire_codes(cluster_size: torch.Tensor, embed_avg: torch.Tensor, embeddings: torch.Tensor, pool: Optional[torch.Tensor],
+                 chain_x: Optional[torch.Tensor], chain_codes: Optional[torch.Tensor], chain_idx: Optional[torch.Tensor],
+                 stage: int, threshold: float, reset_cluster_size: float, l2norm: bool, seed: torch.Tensor) -> torch.Tensor:
+    """Dead-code expiry on the device, in place on the three buffers (native.expire_codes); the pool is ``pool`` [H | 1, N, D]
+    or the stage-``stage`` residual of the chain (x [M, D], codes [Q | 1, K, D], idx [M, Q]) -> picked [H, K] int64."""
+    chain = None if chain_x is None else (chain_x, chain_codes, chain_idx)
+    return native.expire_codes(cluster_size, embed_avg, embeddings, pool, chain=chain, stage=stage, threshold=threshold,
+                               reset_cluster_size=reset_cluster_size, l2norm=l2norm, seed=seed, want_picked=True)[1]
+
+
+@expire_codes.register_fake
+def _(cluster_size, embed_avg, embeddings, pool, chain_x, chain_codes, chain_idx, stage, threshold, reset_cluster_size, l2norm, seed):
+    return cluster_size.new_empty(cluster_size.shape, dtype=torch.int64)
 
 
 # lookup-free quantization (native.lfq_*): the same calls with a dispatcher identity and fake implementations

@@ -310,7 +310,7 @@ class VectorQuantize(nn.Module):
         mine = (local >= 0) & (local < k_local)
         hits, sums = search.get_backend().ema_accumulate(flat.float(), local.clamp(0, k_local - 1).contiguous(), k_local, mine)
         cb.ema_apply_shard(hits, sums, self.shard_group, self.codebook_size)
-        cb.reseed_dead_codes(flat)
+        cb.reseed_dead_codes(flat, sharded=True)  # (expire_on_device refuses: the shards would draw for themselves)
 
     # ------------------------------------------------------------------ forward
     def forward(self, x, indices=None, mask=None, freeze_codebook=False, return_loss_breakdown=False):

@@ -244,7 +244,10 @@ class ResidualVQ(nn.Module):
                                                                           ste=True, share=self.shared_codebook)
                 for q, layer in enumerate(self.layers):
                     layer._codebook.ema_apply(hits[:, q], sums[:, q])
-                    layer._codebook.reseed_dead_codes(lambda q=q: residual_rows(q))
+                    if layer._codebook.expire_on_device:  # the kernel rebuilds r_q for the rows it picks: no chain here
+                        layer._codebook.reseed_dead_codes((flat[0].detach(), codes[0].detach(), idx[0], q))
+                    else:
+                        layer._codebook.reseed_dead_codes(lambda q=q: residual_rows(q))
         if training and wide_input:
             out = out.double()
         return out.reshape(*lead, d), idx.reshape(*lead, Q), losses
@@ -448,7 +451,10 @@ class GroupedResidualVQ(nn.Module):
                         cbq = layer._codebook
                         if cbq.ema_update:
                             cbq.ema_apply(hits[g:g + 1, q], sums[g:g + 1, q])
-                            cbq.reseed_dead_codes(lambda g=g, q=q: residual_rows(g, q))
+                            if cbq.expire_on_device:  # (flat[g]: a row-strided view of the input, read in place)
+                                cbq.reseed_dead_codes((flat[g].detach(), codes[g].detach(), idx[g], q))
+                            else:
+                                cbq.reseed_dead_codes(lambda g=g, q=q: residual_rows(g, q))
         quantized = out.permute(1, 0, 2).reshape(*lead, self.dim)  # q_buf's memory; keeps the autograd edge of `out`
         if training and x.dtype == torch.float64:
             quantized = quantized.double()

@@ -134,6 +134,21 @@ class _NativeBackend:
         native.ema_update(cluster_size, embed_avg, embeddings, hits, sums, decay, eps, l2norm)
 
     @staticmethod
+    def expire_codes(cluster_size, embed_avg, embeddings, pool=None, *, chain=None, stage=0, threshold, reset_cluster_size,
+                     l2norm, seed):
+        """Dead-code expiry decided on the device, in place on the three buffers (vq_expire_codes_f32): no host
+        synchronisation.  ``pool`` [H | 1, N, D], or ``chain`` = (x [M, D], codes [Q | 1, K, D], idx [M, Q]) with ``stage``."""
+        if torch.compiler.is_compiling():
+            from . import ops
+
+            cx, cc, ci = chain if chain is not None else (None, None, None)
+            ops.expire_codes(cluster_size, embed_avg, embeddings, pool, cx, cc, ci, int(stage), float(threshold),
+                             float(reset_cluster_size), bool(l2norm), seed)
+            return
+        native.expire_codes(cluster_size, embed_avg, embeddings, pool, chain=chain, stage=stage, threshold=threshold,
+                            reset_cluster_size=reset_cluster_size, l2norm=l2norm, seed=seed)
+
+    @staticmethod
     def column_stats(x, mask=None):
         """-> (count [H] int64, mean [H, D], m2 [H, D]) of the kept rows of x [H, M, D] in one read (vq_affine_stats_f32)."""
         return native.column_stats(x, mask)
