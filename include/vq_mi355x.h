@@ -670,6 +670,51 @@ int vq_decode_f32(const float *cb, int64_t cb_gs, int64_t cb_qs, int G, int Q, i
                   void *stream);
 
 /*
+ * vq_residual_mask_f32 -- the mask pass of a residual stack: what ResidualVQ / GroupedResidualVQ compute with `mask=`
+ *   (residual_vq.py:212-243 over vector_quantize_pytorch.py:347-364,413-418), from the indices vq_quantize_f32 wrote for ALL rows.
+ *   Row (g, m) is x[g * x_gs + m * x_rs + d], code (g, q, k) is cb[g * cb_gs + q * cb_qs + k * D + d] (cb_qs = 0: the stages
+ *   share one codebook), its index of stage q is idx[g * idx_gs + m * idx_rs + q * idx_qs], its mask byte is
+ *   mask[g * mask_gs + m] (mask_gs = 0: every group uses the same mask; non-zero = kept).  Strides in elements.
+ *   Per row, with r_0 = x, acc = +0.0, for q = 0 .. Q-1, every operation one IEEE fp32 operation in this order:
+ *     kept row:        c = cb[g][q][idx_q];  e_q += sum_d (c - r_q)^2;  quant = train ? r_q + (c - r_q) : c
+ *     masked-out row:  quant = r_q      (where(mask, quantize, orig_input), vector_quantize_pytorch.py:415-418)
+ *     both:            acc = acc + quant;  r_{q+1} = r_q - quant  (residual_vq.py:232);  out = acc after the last stage
+ *   A finite masked-out row so has r_q = 0 for q >= 1 and out = x.  The reference searches that zero row: the call WRITES
+ *     idx_q = zero_idx[g * Q + q]  for q >= 1 on masked-out rows that are finite in every element (zero_idx: the answer
+ *             of stage q's codebook to the all-zero row, from vq_quantize_f32 itself),
+ *     idx_q = 0                    for q >= 1 on masked-out rows that hold a non-finite element (r_1 has a NaN there, and a
+ *             row holding a NaN answers code 0; the NaN reaches out in those elements).
+ *   idx of kept rows and stage 0 of every row are only read.  An index outside [0, K) never becomes an address: code 0 of
+ *   the stage is read in its place.
+ *   sq_err (may be NULL): device doubles, [Q] (the sum over all groups) or [G][Q] with sq_err_per_group, e_q summed over
+ *   the KEPT rows only (the commitment loss is the mean over mask, vector_quantize_pytorch.py:347-360; no kept row: 0).  One
+ *   fp32 partial per stage and <= 32 rows in `workspace`, then a fixed-order fp64 sum: no atomics, run-to-run identical.
+ *   workspace (used only with sq_err): 4-byte aligned, 4 * G * Q * ceil(M / 2) bytes always suffice.
+ *   No host read, no allocation: capturable in a hipGraph.  M == 0 returns 0 without a launch (sq_err is zeroed).
+ * vq_residual_mask_backward_f32 -- its backward with respect to x, the masked counterpart of vq_quantize_backward_f32:
+ *     grad_x[m] = (train ? Q * grad_out[m] : 0) + (mask[m] ? sum_q 2 * grad_sq_err[q] * (r_q - c_q[idx_q]) : 0)
+ *   with the chain r_q rebuilt in the forward's fp32 order (every layer returns its input on a masked-out row, and every
+ *   residual is x minus detached terms: d out / d x = Q * I there too).  grad_out (laid out like out) and grad_sq_err ([Q],
+ *   or [G][Q] with sq_err_per_group, device doubles, read on the device) may each be NULL.  idx is only read.
+ * Errors (VQ_E_BADARG, vq_last_error; the device is not touched): G outside [1, 65535], Q or K not positive, M negative,
+ *   D outside [1, 512] (what one fused residual launch takes), G * M * D beyond int64, and with M > 0 a NULL x, cb, idx,
+ *   mask, out / grad_x or zero_idx, or a workspace that is NULL, misaligned or too small while sq_err is given.
+ */
+int vq_residual_mask_f32(const float *x, int64_t x_gs, int64_t x_rs, const float *cb, int64_t cb_gs, int64_t cb_qs,
+                         int64_t *idx, int64_t idx_gs, int64_t idx_rs, int64_t idx_qs,
+                         const uint8_t *mask, int64_t mask_gs, const int64_t *zero_idx,
+                         int G, int64_t M, int Q, int K, int D, int train,
+                         float *out, int64_t out_gs, int64_t out_rs,
+                         double *sq_err, int sq_err_per_group, void *workspace, int64_t workspace_bytes, void *stream);
+int vq_residual_mask_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, const float *cb, int64_t cb_gs, int64_t cb_qs,
+                                  const int64_t *idx, int64_t idx_gs, int64_t idx_rs, int64_t idx_qs,
+                                  const uint8_t *mask, int64_t mask_gs,
+                                  int G, int64_t M, int Q, int K, int D, int train,
+                                  const float *grad_out, int64_t go_gs, int64_t go_rs,
+                                  const double *grad_sq_err, int sq_err_per_group,
+                                  float *grad_x, int64_t gx_gs, int64_t gx_rs, void *stream);
+
+/*
  * vq_lfq_decode_f32 -- indices -> code vectors for LFQ / ResidualLFQ / GroupedResidualLFQ in one pass.  The lookup-free
  *   family has no table: a code is a function of the index bits alone (replaces lookup_free_quantization.py:193-220,
  *   residual_lfq.py:80-118,240-252: per stage a cast, an and, a compare, a convert and a scale, then a stack, a masked_fill

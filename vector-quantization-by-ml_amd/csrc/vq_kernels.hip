@@ -104,6 +104,7 @@ namespace {
 #include "vq_lq.inc"
 #include "vq_affine.inc"
 #include "vq_decode.inc"
+#include "vq_residual_mask.inc"
 #include "vq_lfq_decode.inc"
 #include "vq_diversity.inc"
 #endif
@@ -2659,6 +2660,81 @@ int vq_decode_f32(const float *cb, int64_t cb_gs, int64_t cb_qs, int G, int Q, i
     p.sum = codes_sum; p.sum_gs = sum_gs; p.sum_rs = sum_rs; p.sum_ds = sum_ds;
     p.all = all_codes; p.all_qs = all_qs; p.all_gs = all_gs; p.all_rs = all_rs;
     return decode_launch(p, device_cus(), (hipStream_t)stream);
+}
+
+static int rm_check(const char *who, const float *x, const float *cb, const void *idx, const uint8_t *mask, int G, int64_t M, int Q,
+                    int K, int D) {
+    if (G <= 0 || G > 65535 || Q <= 0 || K <= 0 || M < 0) return fail(VQ_E_BADARG, who, "G must be in [1, 65535], Q and K positive, M non-negative");
+    if (D < 1 || D > 512) return fail(VQ_E_BADARG, who, "D must be in [1, 512]");
+    if (M > INT64_MAX / D || M * D > INT64_MAX / G || M > INT64_MAX / Q / G) return fail(VQ_E_BADARG, who, "too many elements");
+    if (M == 0) return 0;
+    if (!x || !cb || !idx || !mask) return fail(VQ_E_BADARG, who, "x, cb, idx or mask is null");
+    return 0;
+}
+
+int vq_residual_mask_f32(const float *x, int64_t x_gs, int64_t x_rs, const float *cb, int64_t cb_gs, int64_t cb_qs, int64_t *idx,
+                         int64_t idx_gs, int64_t idx_rs, int64_t idx_qs, const uint8_t *mask, int64_t mask_gs,
+                         const int64_t *zero_idx, int G, int64_t M, int Q, int K, int D, int train, float *out, int64_t out_gs,
+                         int64_t out_rs, double *sq_err, int sq_err_per_group, void *workspace, int64_t workspace_bytes,
+                         void *stream) {
+    const char *who = "vq_residual_mask";
+    int rc = rm_check(who, x, cb, idx, mask, G, M, Q, K, D);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (M == 0) {  // no launch: the sums of no rows
+        if (sq_err) return clear_sq_err(sq_err, (size_t)Q * (sq_err_per_group ? G : 1), s, "vq_residual_mask memset");
+        return 0;
+    }
+    if (!out || !zero_idx) return fail(VQ_E_BADARG, who, "out or zero_idx is null");
+    ResMaskParams p;
+    memset(&p, 0, sizeof(p));
+    p.x = x; p.x_gs = x_gs; p.x_rs = x_rs;
+    p.cb = cb; p.cb_gs = cb_gs; p.cb_qs = cb_qs;
+    p.idx = (long long *)idx; p.idx_gs = idx_gs; p.idx_rs = idx_rs; p.idx_qs = idx_qs;
+    p.mask = mask; p.mask_gs = mask_gs;
+    p.zero_idx = (const long long *)zero_idx;
+    p.M = M; p.Q = Q; p.K = K; p.D = D; p.train = train != 0;
+    p.out = out; p.out_gs = out_gs; p.out_rs = out_rs;
+    rm_plan(p);
+    if (sq_err) {
+        if (!workspace || ((uintptr_t)workspace & 3) || workspace_bytes < (int64_t)sizeof(float) * G * p.units * Q)
+            return fail(VQ_E_BADARG, who, "workspace is null, misaligned or smaller than 4 * G * Q * ceil(M / 2) bytes");
+        p.part = (float *)workspace;
+    }
+    const bool vec = D % 4 == 0 && rm_aligned(x, {x_gs, x_rs}) && rm_aligned(cb, {cb_gs, cb_qs}) && rm_aligned(out, {out_gs, out_rs});
+    rc = rm_dispatch<RmForward>(p, vec, G, device_cus(), s, "vq_residual_mask launch");
+    if (rc || !sq_err) return rc;
+    // part is [G][units][Q]: one sum per group, or the groups' partials as one list
+    if (sq_err_per_group)
+        return launch<vq_loss_reduce_kernel>(dim3((unsigned)Q, (unsigned)G), dim3(256), 0, s, "vq_residual_mask reduce launch", (const float *)p.part,
+                                             p.units, Q, sq_err, 0, -1);
+    return launch<vq_loss_reduce_kernel>(dim3((unsigned)Q), dim3(256), 0, s, "vq_residual_mask reduce launch", (const float *)p.part,
+                                         p.units * G, Q, sq_err, 0, -1);
+}
+
+int vq_residual_mask_backward_f32(const float *x, int64_t x_gs, int64_t x_rs, const float *cb, int64_t cb_gs, int64_t cb_qs,
+                                  const int64_t *idx, int64_t idx_gs, int64_t idx_rs, int64_t idx_qs, const uint8_t *mask,
+                                  int64_t mask_gs, int G, int64_t M, int Q, int K, int D, int train, const float *grad_out,
+                                  int64_t go_gs, int64_t go_rs, const double *grad_sq_err, int sq_err_per_group, float *grad_x,
+                                  int64_t gx_gs, int64_t gx_rs, void *stream) {
+    const char *who = "vq_residual_mask_backward";
+    int rc = rm_check(who, x, cb, idx, mask, G, M, Q, K, D);
+    if (rc || M == 0) return rc;
+    if (!grad_x) return fail(VQ_E_BADARG, who, "grad_x is null");
+    ResMaskParams p;
+    memset(&p, 0, sizeof(p));
+    p.x = x; p.x_gs = x_gs; p.x_rs = x_rs;
+    p.cb = cb; p.cb_gs = cb_gs; p.cb_qs = cb_qs;
+    p.idx = (long long *)idx; p.idx_gs = idx_gs; p.idx_rs = idx_rs; p.idx_qs = idx_qs;
+    p.mask = mask; p.mask_gs = mask_gs;
+    p.M = M; p.Q = Q; p.K = K; p.D = D; p.train = train != 0;
+    p.out = grad_x; p.out_gs = gx_gs; p.out_rs = gx_rs;
+    p.go = grad_out; p.go_gs = go_gs; p.go_rs = go_rs;
+    p.g_err = grad_sq_err; p.g_err_gs = sq_err_per_group ? Q : 0;
+    rm_plan(p);
+    const bool vec = D % 4 == 0 && rm_aligned(x, {x_gs, x_rs}) && rm_aligned(cb, {cb_gs, cb_qs}) && rm_aligned(grad_x, {gx_gs, gx_rs}) &&
+                     (!grad_out || rm_aligned(grad_out, {go_gs, go_rs}));
+    return rm_dispatch<RmBackward>(p, vec, G, device_cus(), (hipStream_t)stream, "vq_residual_mask_backward launch");
 }
 
 int vq_lfq_decode_f32(const void *idx, int idx_64, int64_t idx_gs, int64_t idx_rs, int64_t idx_qs, int G, int64_t N, int Q_given,

@@ -133,6 +133,10 @@ _SIGNATURES = {
     "vq_fsq_decode_f32": (_int, (_vp, _int, _i64, _int, _int, _vp, _vp, _int, _vp, _vp, _vp)),
     "vq_decode_f32": (_int, (_vp, _i64, _i64, _int, _int, _int, _int, _vp, _int, _i64, _i64, _i64, _i64, _int, _int,
                              _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp)),
+    "vq_residual_mask_f32": (_int, (_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _int, _i64, _int,
+                                    _int, _int, _int, _vp, _i64, _i64, _vp, _int, _vp, _i64, _vp)),
+    "vq_residual_mask_backward_f32": (_int, (_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _int, _i64,
+                                             _int, _int, _int, _int, _vp, _i64, _i64, _vp, _int, _vp, _i64, _i64, _vp)),
     "vq_lfq_decode_f32": (_int, (_vp, _int, _i64, _i64, _i64, _int, _i64, _int, _int, _int, _vp, _int,
                                  _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp)),
     "vq_lq_workspace_bytes": (_i64, (_i64, _i64, _int)),
@@ -1152,6 +1156,76 @@ def ema_accumulate_residual(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor
     a = _vq_args(x, cb, Q=Q, shared=stages_share_codebook, flags=F_STE if ste else 0, idx=idx)
     _call("vq_ema_accumulate_residual_f32", x.device, a, counts.data_ptr(), sums.data_ptr())
     return counts, sums
+
+
+# ------------------------------------------------------------------------------------------------
+# the mask pass of a residual stack (vq_residual_mask_* in include/vq_mi355x.h)
+# ------------------------------------------------------------------------------------------------
+RESIDUAL_MASK_MAX_DIM = 512
+
+
+def _residual_mask_args(x, cb, idx, mask):
+    """The operands both mask-pass entry points share -> (leading C arguments, G, M, Q, K, D, the mask bytes kept alive)."""
+    _require_gpu(x, cb, idx, mask)
+    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and cb.is_contiguous() and idx.dtype == torch.int64
+    assert x.dim() == 3 and cb.dim() == 4 and idx.dim() == 3
+    G, M, D = x.shape
+    Gc, Qc, K, Dc = cb.shape
+    Q = idx.shape[-1]
+    assert Gc == G and Dc == D and tuple(idx.shape[:2]) == (G, M) and Qc in (1, Q), "x / cb / idx do not fit together"
+    assert 1 <= D <= RESIDUAL_MASK_MAX_DIM, f"the mask pass takes rows of 1 .. {RESIDUAL_MASK_MAX_DIM} dims"
+    m8 = mask.contiguous()
+    m8 = m8.view(torch.uint8) if m8.dtype == torch.bool else m8.to(torch.uint8)
+    assert tuple(m8.shape) in ((M,), (G, M)), "mask must be [M] (shared by the groups) or [G, M]"
+    x_rs, x_gs = _row_strides(x)
+    args = (x.data_ptr(), x_gs, x_rs, cb.data_ptr(), Qc * K * D, (K * D if Qc == Q and Q > 1 else 0), idx.data_ptr(),
+            int(idx.stride(0)), int(idx.stride(1)), int(idx.stride(2)), m8.data_ptr(), (M if m8.dim() == 2 else 0))
+    return args, G, M, Q, K, D, m8
+
+
+def residual_mask(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor, mask: torch.Tensor, zero_idx: torch.Tensor, *,
+                  train: bool, want_sq_err: bool = False, sq_err_per_group: bool = False, out: torch.Tensor | None = None):
+    """The mask pass of a residual stack (vq_residual_mask_f32): x [G, M, D] (strided rows ok), cb [G, Q | 1, K, D]
+    contiguous, idx [G, M, Q] int64 as the search wrote it for all rows (any strides; REWRITTEN in place for the stages
+    q >= 1 of masked-out rows), mask [M] or [G, M] bool / uint8 (non-zero = kept), zero_idx [G, Q] int64 (every stage's
+    answer to the all-zero row) -> (out [G, M, D], sq_err [Q] or [G, Q] float64 over the kept rows, or None)."""
+    args, G, M, Q, K, D, m8 = _residual_mask_args(x, cb, idx, mask)
+    _require_gpu(zero_idx, out)
+    assert zero_idx.dtype == torch.int64 and zero_idx.is_contiguous() and tuple(zero_idx.shape) == (G, Q)
+    dev = x.device
+    if out is None:
+        out = torch.empty((G, M, D), dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (G, M, D)
+    out_rs, out_gs = _row_strides(out)
+    sq_err, ws, ws_bytes = None, None, 0
+    if want_sq_err:
+        sq_err = torch.empty((G, Q) if sq_err_per_group else (Q,), dtype=torch.float64, device=dev)
+        ws, ws_bytes = _alloc_workspace(4 * G * Q * ((M + 1) // 2), dev)
+    _call("vq_residual_mask_f32", dev, *args, zero_idx.data_ptr(), G, M, Q, K, D, 1 if train else 0, out.data_ptr(), out_gs,
+          out_rs, _ptr(sq_err), 1 if sq_err_per_group else 0, _ptr(ws), ws_bytes)
+    return out, sq_err
+
+
+def residual_mask_backward(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor, mask: torch.Tensor,
+                           grad_out: torch.Tensor | None, grad_sq_err: torch.Tensor | None, *, train: bool,
+                           sq_err_per_group: bool = False) -> torch.Tensor:
+    """d/dx of residual_mask in one pass (vq_residual_mask_backward_f32): the operands of the forward (idx as the forward
+    left it), grad_out [G, M, D] | None, grad_sq_err [Q] or [G, Q] float64 | None (read on the device) -> grad_x [G, M, D]."""
+    args, G, M, Q, K, D, m8 = _residual_mask_args(x, cb, idx, mask)
+    _require_gpu(grad_out, grad_sq_err)
+    gx = torch.empty((G, M, D), dtype=torch.float32, device=x.device)
+    go_rs, go_gs = 0, 0
+    if grad_out is not None:
+        assert grad_out.dtype == torch.float32 and tuple(grad_out.shape) == (G, M, D)
+        if grad_out.stride(-1) != 1 and D != 1:
+            grad_out = grad_out.contiguous()
+        go_rs, go_gs = _row_strides(grad_out)
+    if grad_sq_err is not None:
+        grad_sq_err = grad_sq_err.to(torch.float64).contiguous()
+        assert grad_sq_err.numel() == (G * Q if sq_err_per_group else Q)
+    _call("vq_residual_mask_backward_f32", x.device, *args, G, M, Q, K, D, 1 if train else 0, _ptr(grad_out), go_gs, go_rs,
+          _ptr(grad_sq_err), 1 if sq_err_per_group else 0, gx.data_ptr(), M * D, D)
+    return gx
 
 
 # ------------------------------------------------------------------------------------------------

@@ -11,6 +11,8 @@ instead of breaking the graph at an opaque Python call:
     torch.ops.vq_mi355x.expire_codes(cluster_size, embed_avg, embeddings, pool, chain_x, chain_codes, chain_idx, stage,
         threshold, reset_cluster_size, l2norm, seed) -> picked [H, K]   (dead-code expiry on the device, native.expire_codes;
         mutates the three buffers)
+    torch.ops.vq_mi355x.residual_mask(x, cb, idx, mask, zero_idx, out, train, want_sq_err, per_group) -> sq_err
+        (the mask pass of a residual stack, native.residual_mask; rewrites ``idx`` on masked-out rows and writes ``out``)
     torch.ops.vq_mi355x.lfq_quantize / lfq_entropy_fwd / lfq_entropy_bwd   (lookup-free quantization, native.lfq_*)
     torch.ops.vq_mi355x.rlfq_quantize / rlfq_backward / lfq_entropy_staged_fwd / lfq_entropy_staged_bwd
         (residual LFQ, native.rlfq_* and native.lfq_entropy_staged_*)
@@ -96,6 +98,26 @@ def expire_codes(cluster_size: torch.Tensor, embed_avg: torch.Tensor, embeddings
 @expire_codes.register_fake
 def _(cluster_size, embed_avg, embeddings, pool, chain_x, chain_codes, chain_idx, stage, threshold, reset_cluster_size, l2norm, seed):
     return cluster_size.new_empty(cluster_size.shape, dtype=torch.int64)
+
+
+@torch.library.custom_op(f"{_LIB_NS}::residual_mask", mutates_args=("idx", "out"))
+def residual_mask(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor, mask: torch.Tensor, zero_idx: torch.Tensor,
+                  out: torch.Tensor, train: bool, want_sq_err: bool, per_group: bool) -> torch.Tensor:
+    """The mask pass of a residual stack (native.residual_mask): x [G, M, D], cb [G, Q | 1, K, D], idx [G, M, Q] as the search
+    wrote it (rewritten on masked-out rows), mask [M] | [G, M], zero_idx [G, Q]; writes ``out`` [G, M, D] -> sq_err over the
+    kept rows ([Q] or [G, Q] float64; zeros when not requested)."""
+    _, sq_err = native.residual_mask(x, cb, idx, mask, zero_idx, train=train, want_sq_err=want_sq_err,
+                                     sq_err_per_group=per_group, out=out)
+    if sq_err is not None:
+        return sq_err
+    q = idx.shape[-1]
+    return torch.zeros((x.shape[0], q) if per_group else (q,), dtype=torch.float64, device=x.device)
+
+
+@residual_mask.register_fake
+def _(x, cb, idx, mask, zero_idx, out, train, want_sq_err, per_group):
+    q = idx.shape[-1]
+    return x.new_empty((x.shape[0], q) if per_group else (q,), dtype=torch.float64)
 
 
 # lookup-free quantization (native.lfq_*): the same calls with a dispatcher identity and fake implementations

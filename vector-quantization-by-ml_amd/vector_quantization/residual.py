@@ -7,8 +7,13 @@ in registers across the Q codebook sweeps, the kernel writes ``indices[..., q]``
 ``quantized_out`` and the per-stage squared errors.  ``GroupedResidualVQ`` maps its groups onto the
 kernel's head axis, so G groups x Q stages are still one launch.
 
-Heterogeneous stacks (masks, per-layer input normalisation, quantize-dropout, k-means seeding on the
-first batch, channel-first layers) fall back to a per-layer loop in which each layer call is itself a
+A ``mask=`` keeps the one launch: the search runs on every row and one more native pass (the mask pass,
+``search.quantize_rows_masked``) applies the reference's rule for masked-out rows to the output, the indices and
+the per-stage squared errors.  Quantize dropout keeps it too: a stack cut after stage ``cut`` is the same launch
+on ``cut + 1`` stages.  ``VQ_RVQ_NO_FUSED_MASK=1`` in the environment (read per call) sends both back to the loop.
+
+Heterogeneous stacks (per-layer input normalisation, k-means seeding on the first batch, channel-first layers,
+a mask together with device-side expiry) fall back to a per-layer loop in which each layer call is itself a
 native launch.
 """
 from __future__ import annotations
@@ -39,6 +44,53 @@ def _residual_chain(x: torch.Tensor, codes: torch.Tensor, idx: torch.Tensor, ste
         quant = r + (c - r) if ste else c
         r = r - quant
     return residuals
+
+
+def _residual_chain_masked(x: torch.Tensor, codes: torch.Tensor, idx: torch.Tensor, mask: torch.Tensor) -> List[torch.Tensor]:
+    """_residual_chain (train arithmetic) of a masked stack: a masked-out row's layer returns its input, so its residual is
+    r_q - r_q from stage 1 on -- the rows the reference's layers hand to their dead-code re-seeding.  mask [M] bool."""
+    residuals = []
+    r = x
+    kept = mask[:, None]
+    for q in range(idx.shape[-1]):
+        residuals.append(r)
+        c = codes[q][idx[:, q]]
+        r = r - torch.where(kept, r + (c - r), r)
+    return residuals
+
+
+def _zero_row_indices(owner, codes: torch.Tensor, packed, metric: int, Q: int) -> torch.Tensor:
+    """[G, Q] int64: every stage codebook's answer to the all-zero row (search.zero_row_indices: one tiny launch of the real
+    search), kept on ``owner`` beside its _stage_cache and rebuilt when that is."""
+    key = None if torch.compiler.is_compiling() or owner._stage_cache is None else owner._stage_cache[0]
+    cached = owner._zero_idx_cache
+    if key is not None and cached is not None and cached[0] == key:
+        return cached[1]
+    with torch.no_grad():
+        zero_idx = search.zero_row_indices(codes, metric=metric, packed=packed)
+        if zero_idx.shape[1] != Q:  # one shared codebook: the same answer at every stage
+            zero_idx = zero_idx.expand(-1, Q)
+        zero_idx = zero_idx.contiguous()
+    if key is not None:
+        owner._zero_idx_cache = (key, zero_idx)
+    return zero_idx
+
+
+def _mask_fusable(layers, x, mask, groups: int = 1) -> bool:
+    """A masked (or quantize-dropout) call may take the fused path: a backend with the mask pass, not switched off, and for
+    a mask one flag per row and no device-side expiry (its kernel rebuilds r_q from the chain and does not know the mask)."""
+    if search.masked_backend() is None:
+        return False
+    if mask is None:
+        # quantize dropout on image / video input: the reference's own index shapes do not stack there
+        # (residual_vq.py:198-208); the layer loop keeps that behaviour
+        return x.ndim < 4
+    d = x.shape[-1]
+    # a [b, n] mask for [b, n, d] rows (anything else is the layer loop's to accept or refuse, as the reference does)
+    if (x.ndim != 3 or mask.dtype != torch.bool or tuple(mask.shape) != tuple(x.shape[:2]) or d == 0 or d // groups > 512
+            or mask.device != x.device):
+        return False
+    return not any(layer._codebook.expire_on_device for layer in layers)
 
 
 class ResidualVQ(nn.Module):
@@ -79,6 +131,7 @@ class ResidualVQ(nn.Module):
             for layer in self.layers[1:]:
                 layer._codebook = first
         self._stage_cache = None   # (key, stacked natural codebooks [1, Q|1, K, D], packed images) of the fused launch
+        self._zero_idx_cache = None  # (the same key, [1, Q] indices of the all-zero row) of the fused masked launch
         self._zero_losses = None
 
     # ------------------------------------------------------------------ codes
@@ -143,7 +196,7 @@ class ResidualVQ(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def _fusable(self, x, mask, drop_active: bool) -> bool:
-        if mask is not None or drop_active:
+        if (mask is not None or drop_active) and not _mask_fusable(self.layers, x, mask):
             return False
         first = self.layers[0]
         cb0 = first._codebook
@@ -178,7 +231,9 @@ class ResidualVQ(nn.Module):
         shared_and_moving = (self.shared_codebook and self.training and not freeze_codebook
                              and self.layers[0]._codebook.ema_update)
         if not shared_and_moving and self._fusable(x, mask, drop_active):
-            quantized, all_indices, all_losses = self._forward_fused(x, freeze_codebook)
+            # quantize dropout: a stack cut after stage `cut` is the fused launch on cut + 1 stages
+            cut = self._draw_cut(x, rand_quantize_dropout_fixed_seed) if drop_active else None
+            quantized, all_indices, all_losses = self._forward_fused(x, freeze_codebook, mask=mask, cut=cut)
         else:
             quantized, all_indices, all_losses = self._forward_layers(x, mask, freeze_codebook, drop_active,
                                                                       rand_quantize_dropout_fixed_seed)
@@ -207,7 +262,9 @@ class ResidualVQ(nn.Module):
             self._stage_cache = (key, codes, packed)
         return self._stage_cache[1], self._stage_cache[2]
 
-    def _forward_fused(self, x, freeze_codebook):
+    def _forward_fused(self, x, freeze_codebook, mask=None, cut=None):
+        """One launch for the stages 0 .. cut (all of them without quantize dropout); with ``mask`` [b, n] the search runs on
+        every row and the mask pass (search.quantize_rows_masked) follows -- nothing waits for the device in either."""
         first = self.layers[0]
         cb0 = first._codebook
         training = self.training
@@ -217,32 +274,59 @@ class ResidualVQ(nn.Module):
         if flat.dtype != torch.float32:
             flat = flat.float()
         Q = self.num_quantizers
+        run = Q if cut is None else cut + 1  # the stages that run; the dropped ones report index -1 and a zero loss
         codes, packed = self._stage_codes()  # [1, Q, K, D] ([1, 1, K, D] when shared); fusable stacks are not learnable
         want_loss = training and first.has_commitment_loss
-        idx_buf = torch.empty((1, flat.shape[1], Q), dtype=torch.int64, device=flat.device)
-        out, idx, sq_err = search.quantize_rows(flat, codes, metric=cb0.metric, ste=training, want_sq_err=want_loss,
-                                                share=self.shared_codebook, idx=idx_buf, packed=packed)
+        rows = flat.shape[1]
+        row_mask = zero_idx = None
+        if mask is not None:
+            row_mask = mask.reshape(rows)
+            zero_idx = _zero_row_indices(self, codes, packed, cb0.metric, Q)[:, :run]
+        if run < Q:
+            idx_buf = torch.full((1, rows, Q), -1, dtype=torch.int64, device=flat.device)
+            if not self.shared_codebook:  # views: the first `run` codebooks and their images
+                codes, packed = codes[:, :run], (packed[:run] if packed is not None else None)
+        else:
+            idx_buf = torch.empty((1, rows, Q), dtype=torch.int64, device=flat.device)
+        if mask is None:
+            out, idx, sq_err = search.quantize_rows(flat, codes, metric=cb0.metric, ste=training, want_sq_err=want_loss,
+                                                    share=self.shared_codebook, idx=idx_buf[..., :run], packed=packed)
+            denom = flat.numel()
+        else:
+            out, idx, sq_err = search.quantize_rows_masked(flat, codes, row_mask, zero_idx, metric=cb0.metric, ste=training,
+                                                           want_sq_err=want_loss, share=self.shared_codebook,
+                                                           idx=idx_buf[..., :run], packed=packed)
+            denom = row_mask.sum() * d  # on the device: no kept row gives NaN, the reference's mean over nothing
         if want_loss:
-            losses = (sq_err / flat.numel()).to(torch.float32)[None, :] * first.commitment_weight
+            losses = (sq_err / denom).to(torch.float32)[None, :] * first.commitment_weight
         elif training:
-            losses = torch.zeros((1, Q), dtype=torch.float32, device=flat.device)
+            losses = torch.zeros((1, run), dtype=torch.float32, device=flat.device)
         else:
             losses = _cached_zeros(self, "_zero_losses", (1, Q), flat.device)  # no fill kernel per inference forward
+        if run < Q:  # (train mode only)
+            losses = torch.cat([losses, torch.zeros((1, Q - run), dtype=losses.dtype, device=flat.device)], dim=1)
 
         if training and not freeze_codebook and cb0.ema_update:
             with torch.no_grad():
-                stage_codes = codes[0].expand(Q, -1, -1) if self.shared_codebook else codes[0]
+                stage_codes = codes[0].expand(run, -1, -1) if self.shared_codebook else codes[0]
                 chain = []
 
                 def residual_rows(q):
                     if not chain:  # only needed when a code expired
-                        chain.extend(_residual_chain(flat[0].detach(), stage_codes.detach(), idx[0], ste=True))
+                        if row_mask is None:
+                            chain.extend(_residual_chain(flat[0].detach(), stage_codes.detach(), idx[0], ste=True))
+                        else:
+                            chain.extend(_residual_chain_masked(flat[0].detach(), stage_codes.detach(), idx[0], row_mask))
                     return chain[q][None]
 
+                idx_ema = idx
+                if row_mask is not None:  # an index outside [0, K) ends a row's chain: masked-out rows contribute nothing
+                    idx_ema = idx.clone()
+                    idx_ema[0, :, 0].masked_fill_(~row_mask, -1)
                 # one pass rebuilds the residual chain from the indices and scatter-adds every stage's statistics
-                hits, sums = search.get_backend().ema_accumulate_residual(flat.detach(), codes.detach().contiguous(), idx,
+                hits, sums = search.get_backend().ema_accumulate_residual(flat.detach(), codes.detach().contiguous(), idx_ema,
                                                                           ste=True, share=self.shared_codebook)
-                for q, layer in enumerate(self.layers):
+                for q, layer in enumerate(self.layers[:run]):
                     layer._codebook.ema_apply(hits[:, q], sums[:, q])
                     if layer._codebook.expire_on_device:  # the kernel rebuilds r_q for the rows it picks: no chain here
                         layer._codebook.reseed_dead_codes((flat[0].detach(), codes[0].detach(), idx[0], q))
@@ -250,23 +334,28 @@ class ResidualVQ(nn.Module):
                         layer._codebook.reseed_dead_codes(lambda q=q: residual_rows(q))
         if training and wide_input:
             out = out.double()
-        return out.reshape(*lead, d), idx.reshape(*lead, Q), losses
+        return out.reshape(*lead, d), idx_buf.reshape(*lead, Q), losses
+
+    def _draw_cut(self, x, fixed_seed) -> int:
+        """The last stage that runs under quantize dropout (residual_vq.py:194-207): one draw per forward, from the given
+        seed, from a seed agreed between the replicas, or from the process-wide generator."""
+        Q = self.num_quantizers
+        if fixed_seed is not None:
+            rng = random.Random(fixed_seed)
+        elif dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            seed = torch.tensor(random.randrange(10_000), device=x.device)
+            dist.all_reduce(seed)
+            rng = random.Random(int(seed.item()))
+        else:
+            rng = random
+        cut = rng.randrange(self.quantize_dropout_cutoff_index, Q)
+        if self.quantize_dropout_multiple_of != 1:
+            cut = _round_up(cut + 1, self.quantize_dropout_multiple_of) - 1
+        return cut
 
     def _forward_layers(self, x, mask, freeze_codebook, drop_active, fixed_seed):
         Q = self.num_quantizers
-        cut = Q
-        if drop_active:
-            if fixed_seed is not None:
-                rng = random.Random(fixed_seed)
-            elif dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                seed = torch.tensor(random.randrange(10_000), device=x.device)
-                dist.all_reduce(seed)
-                rng = random.Random(int(seed.item()))
-            else:
-                rng = random
-            cut = rng.randrange(self.quantize_dropout_cutoff_index, Q)
-            if self.quantize_dropout_multiple_of != 1:
-                cut = _round_up(cut + 1, self.quantize_dropout_multiple_of) - 1
+        cut = self._draw_cut(x, fixed_seed) if drop_active else Q
         residual = x
         quantized_out = 0.0
         all_indices, all_losses = [], []
@@ -293,6 +382,7 @@ class GroupedResidualVQ(nn.Module):
         self.channel_last = channel_last
         self.rvqs = nn.ModuleList([ResidualVQ(dim=dim // groups, **kwargs) for _ in range(groups)])
         self._stage_cache = None
+        self._zero_idx_cache = None
         self._zero_losses = None
 
     @property
@@ -359,13 +449,17 @@ class GroupedResidualVQ(nn.Module):
         return torch.cat(outs, dim=self.split_dim)
 
     def _fusable(self, x, mask) -> bool:
-        if not self.channel_last or mask is not None:
+        if not self.channel_last:
+            return False
+        # one mask for all groups: one grouped launch and one mask pass (active quantize dropout keeps the loop over the
+        # groups below, every group drawing its own cut and fusing on its own)
+        if mask is not None and not _mask_fusable([layer for rvq in self.rvqs for layer in rvq.layers], x, mask, self.groups):
             return False
         r0 = self.rvqs[0]
         for rvq in self.rvqs:
             if rvq.has_projections or rvq.shared_codebook or rvq.num_quantizers != r0.num_quantizers:
                 return False
-            if not rvq._fusable(x, None, rvq.training and rvq.quantize_dropout):
+            if (rvq.training and rvq.quantize_dropout) or not rvq._fusable(x, None, False):
                 return False
             if rvq.layers[0]._codebook.embeddings.shape != r0.layers[0]._codebook.embeddings.shape:
                 return False
@@ -377,7 +471,7 @@ class GroupedResidualVQ(nn.Module):
         assert x.shape[self.split_dim] == self.dim
         assert indices is None or len(indices) == 0, "cross-entropy to given indices is not supported"
         if self._fusable(x, mask):
-            return self._forward_fused(x, return_all_codes, freeze_codebook)
+            return self._forward_fused(x, return_all_codes, freeze_codebook, mask)
         chunks = x.chunk(self.groups, dim=self.split_dim)
         seed = random.randint(0, int(1e7))
         outs = tuple(
@@ -410,8 +504,9 @@ class GroupedResidualVQ(nn.Module):
             self._stage_cache = (key, codes, packed)
         return self._stage_cache[1], self._stage_cache[2]
 
-    def _forward_fused(self, x, return_all_codes, freeze_codebook):
-        """Groups on the kernel's head axis: x [..., G*d] is searched in place as a [G, rows, d] view."""
+    def _forward_fused(self, x, return_all_codes, freeze_codebook, mask=None):
+        """Groups on the kernel's head axis: x [..., G*d] is searched in place as a [G, rows, d] view; ``mask`` [b, n] is shared by
+        the groups (the search on every row, then one mask pass for all groups)."""
         G = self.groups
         r0 = self.rvqs[0]
         Q = r0.num_quantizers
@@ -427,10 +522,20 @@ class GroupedResidualVQ(nn.Module):
         want_loss = training and first.has_commitment_loss
         q_buf = torch.empty((rows, G, d), dtype=torch.float32, device=xc.device)
         # one launch for all groups and stages; squared errors come back per group (head) and stage
-        out, idx, sq_err = search.quantize_rows(flat, codes, metric=cb0.metric, ste=training, want_sq_err=want_loss,
-                                                out=q_buf.permute(1, 0, 2), sq_err_per_head=True, packed=packed)
+        row_mask = None
+        if mask is None:
+            out, idx, sq_err = search.quantize_rows(flat, codes, metric=cb0.metric, ste=training, want_sq_err=want_loss,
+                                                    out=q_buf.permute(1, 0, 2), sq_err_per_head=True, packed=packed)
+            denom = rows * d
+        else:
+            row_mask = mask.reshape(rows)
+            zero_idx = _zero_row_indices(self, codes, packed, cb0.metric, Q)
+            out, idx, sq_err = search.quantize_rows_masked(flat, codes, row_mask, zero_idx, metric=cb0.metric, ste=training,
+                                                           want_sq_err=want_loss, out=q_buf.permute(1, 0, 2),
+                                                           sq_err_per_head=True, packed=packed)
+            denom = row_mask.sum() * d  # on the device
         if want_loss:
-            losses = (sq_err / (rows * d)).to(torch.float32)[:, None, :] * first.commitment_weight
+            losses = (sq_err / denom).to(torch.float32)[:, None, :] * first.commitment_weight
         elif training:
             losses = torch.zeros((G, 1, Q), dtype=torch.float32, device=xc.device)
         else:
@@ -441,10 +546,17 @@ class GroupedResidualVQ(nn.Module):
 
                 def residual_rows(g, q):
                     if g not in chains:  # only when a code expired
-                        chains[g] = _residual_chain(flat[g].detach(), codes[g].detach(), idx[g], ste=True)
+                        if row_mask is None:
+                            chains[g] = _residual_chain(flat[g].detach(), codes[g].detach(), idx[g], ste=True)
+                        else:
+                            chains[g] = _residual_chain_masked(flat[g].detach(), codes[g].detach(), idx[g], row_mask)
                     return chains[g][q][None]
 
-                hits, sums = search.get_backend().ema_accumulate_residual(flat.detach(), codes.detach().contiguous(), idx,
+                idx_ema = idx
+                if row_mask is not None:  # an index outside [0, K) ends a row's chain: masked-out rows contribute nothing
+                    idx_ema = idx.clone()
+                    idx_ema[:, :, 0].masked_fill_(~row_mask[None, :], -1)
+                hits, sums = search.get_backend().ema_accumulate_residual(flat.detach(), codes.detach().contiguous(), idx_ema,
                                                                           ste=True, share=False)
                 for g, rvq in enumerate(self.rvqs):
                     for q, layer in enumerate(rvq.layers):

@@ -166,6 +166,25 @@ class _NativeBackend:
                                         sq_err_per_head=sq_err_per_head)
 
     @staticmethod
+    def residual_mask(x, cb, idx, mask, zero_idx, *, train, want_sq_err, per_group=False, out=None):
+        """The mask pass of a residual stack after the fused search (vq_residual_mask_f32): rewrites ``idx`` on the
+        masked-out rows -> (out [G, M, D], sq_err over the kept rows | None)."""
+        if torch.compiler.is_compiling():
+            from . import ops
+
+            if out is None:
+                out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            sq_err = ops.residual_mask(x, cb, idx, mask, zero_idx, out, train, want_sq_err, per_group)
+            return out, (sq_err if want_sq_err else None)
+        return native.residual_mask(x, cb, idx, mask, zero_idx, train=train, want_sq_err=want_sq_err,
+                                    sq_err_per_group=per_group, out=out)
+
+    @staticmethod
+    def residual_mask_backward(x, cb, idx, mask, grad_out, grad_sq_err, *, train, per_group=False):
+        """d/dx of the mask pass in one native pass (vq_residual_mask_backward_f32)."""
+        return native.residual_mask_backward(x, cb, idx, mask, grad_out, grad_sq_err, train=train, sq_err_per_group=per_group)
+
+    @staticmethod
     def cross_entropy_backward(x, cb, lse, target_logit, target, coef, *, metric, live=None, live_packed=None):
         """Fused d/dx of the cross entropy (vq_ce_backward_f32); None when the shape is outside the kernel's range.
         ``live`` [H, K, D]: the codes as they are now when they were rewritten after ``cb`` was searched, ``live_packed`` their
@@ -445,6 +464,83 @@ def quantize_rows(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, st
     out, idx, _best, sq_err = _backend.quantize(x, cb, metric=metric, ste=ste, want_sq_err=want_sq_err, share=share,
                                                 out=out, idx=idx, **pk,
                                                 **({"sq_err_per_head": True} if sq_err_per_head else {}))
+    return out, idx, sq_err
+
+
+# ------------------------------------------------------------------------------------------------
+# residual stacks with a mask: the fused search on all rows, then the mask pass
+# ------------------------------------------------------------------------------------------------
+def masked_backend():
+    """The backend when the fused masked residual forward exists and is not switched off (VQ_RVQ_NO_FUSED_MASK=1 in the
+    environment, read per call like VQ_NO_FUSED_DECODE), else None: the caller walks its layers."""
+    if os.environ.get("VQ_RVQ_NO_FUSED_MASK") == "1" or not hasattr(_backend, "residual_mask"):
+        return None
+    return _backend
+
+
+def zero_row_indices(cb: torch.Tensor, *, metric: int, packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cb [G, Qc, K, D] -> [G, Qc] int64: every stage codebook's answer to the all-zero row, from the search kernel itself (the
+    stage codebooks on the head axis against one zero row each): its metric, its first-index rule, its NaN-code rule."""
+    G, Qc, K, D = cb.shape
+    heads = cb.reshape(G * Qc, 1, K, D)
+    zeros = torch.zeros((G * Qc, 1, D), dtype=torch.float32, device=cb.device)
+    pk = {"packed": packed} if (packed is not None and getattr(_backend, "uses_packed", False)) else {}
+    _out, idx, _best, _err = _backend.quantize(zeros, heads, metric=metric, ste=False, want_sq_err=False, share=False, **pk)
+    return idx.reshape(G, Qc)
+
+
+class _MaskedQuantizeFn(torch.autograd.Function):
+    """_QuantizeFn for a residual stack with a row mask: the fused search on every row, then the mask pass.  Gradients (the
+    reference's, for a stack whose codebooks do not learn): every layer returns its INPUT on a masked-out row
+    (vector_quantize_pytorch.py:415-418) and r_q + (c_q - r_q).detach() on a kept one, each residual being x minus detached
+    terms, so in train mode d out / d x = Q * I on every row; sq_err_q sums over the kept rows only."""
+
+    @staticmethod
+    def forward(ctx, x, cb, mask, zero_idx, metric, ste, want_sq_err, share, out_buf, idx_buf, per_head, packed):
+        extra = {"packed": packed} if packed is not None else {}
+        xd, cbd = x.detach(), cb.detach()
+        # (the search writes its own ``out`` first; the mask pass then rewrites all of it)
+        out, idx = _backend.quantize(xd, cbd, metric=metric, ste=ste, want_sq_err=False, share=share, out=out_buf, idx=idx_buf,
+                                     **extra)[:2]
+        out, sq_err = _backend.residual_mask(xd, cbd, idx, mask, zero_idx, train=ste, want_sq_err=want_sq_err,
+                                             per_group=per_head, out=out)
+        ctx.save_for_backward(x, cb, idx, mask)
+        ctx.ste, ctx.want_sq_err, ctx.per_head = ste, want_sq_err, per_head
+        if sq_err is None:
+            sq_err = torch.zeros((x.shape[0], idx.shape[-1]) if per_head else idx.shape[-1], dtype=torch.float64, device=x.device)
+        ctx.mark_non_differentiable(idx)
+        return out, idx, sq_err
+
+    @staticmethod
+    def backward(ctx, g_out, _g_idx, g_err):
+        x, cb, idx, mask = ctx.saved_tensors
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = _backend.residual_mask_backward(x.detach(), cb.detach(), idx, mask, g_out if ctx.ste else None,
+                                                 g_err if ctx.want_sq_err else None, train=ctx.ste, per_group=ctx.per_head)
+        return gx, None, None, None, None, None, None, None, None, None, None, None
+
+
+def quantize_rows_masked(x: torch.Tensor, cb: torch.Tensor, mask: torch.Tensor, zero_idx: torch.Tensor, *, metric: int = EUCLID,
+                         ste: bool = False, want_sq_err: bool = False, share: bool = False, out: Optional[torch.Tensor] = None,
+                         idx: Optional[torch.Tensor] = None, sq_err_per_head: bool = False,
+                         packed: Optional[torch.Tensor] = None):
+    """``quantize_rows`` for a residual stack with a row mask: x [H, M, D] fp32, cb [H, Q | 1, K, D] (not learnable), mask [M]
+    or [H, M] (True = kept), zero_idx [H, Q] (``zero_row_indices``) -> (out, idx, sq_err over the kept rows | None)."""
+    if packed is not None and not getattr(_backend, "uses_packed", False):
+        packed = None
+    if not cb.is_contiguous():
+        cb = cb.contiguous()
+    if x.dtype != torch.float32:
+        x = x.float()
+    if torch.is_grad_enabled() and x.requires_grad and (ste or want_sq_err):
+        out, idx, sq_err = _MaskedQuantizeFn.apply(x, cb, mask, zero_idx, metric, ste, want_sq_err, share, out, idx,
+                                                   sq_err_per_head, packed)
+        return out, idx, (sq_err if want_sq_err else None)
+    extra = {"packed": packed} if packed is not None else {}
+    out, idx = _backend.quantize(x, cb, metric=metric, ste=ste, want_sq_err=False, share=share, out=out, idx=idx, **extra)[:2]
+    out, sq_err = _backend.residual_mask(x, cb, idx, mask, zero_idx, train=ste, want_sq_err=want_sq_err,
+                                         per_group=sq_err_per_head, out=out)
     return out, idx, sq_err
 
 
