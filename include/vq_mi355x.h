@@ -342,7 +342,7 @@ int vq_softmax_stats_f32(const vq_args *a, float scale, const int64_t *target, i
  * the gradient runs through the MFMA sweep, the one-hot part is a rank-one term per row added from a->cb, the natural
  * codebook, with 1 / dist_target taken from target_logit); coef: ONE float on the device
  * (upstream gradient / number of non-ignored rows).  D <= 512 (VQ_E_UNSUPPORTED beyond: use row chunks of
- * vq_similarities_f32).  Gradient with respect to the codebook is not produced.
+ * vq_similarities_f32).  The gradient with respect to a learnable codebook is vq_ce_backward_codes_f32 below.
  */
 int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_logit, const int64_t *target, int64_t tgt_rs,
                        int64_t tgt_hs, const float *coef, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream);
@@ -366,6 +366,30 @@ int vq_ce_backward_f32(const vq_args *a, const float *lse, const float *target_l
 int vq_ce_backward_live_f32(const vq_args *a, const float *live_cb, int64_t live_cb_hs, const float *live_packed, int64_t live_pk_hs,
                             const float *lse, const float *target_logit, const int64_t *target, int64_t tgt_rs, int64_t tgt_hs,
                             const float *coef, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream);
+
+/*
+ * Backward of the same cross entropy with respect to a learnable codebook (the codes the forward searched, unchanged since),
+ * nothing of [M, K] in memory.  Per head, with s = similarities(x, c), t the targets and lse / coef as for vq_ce_backward_f32:
+ *   w_mk = coef * (exp(s_mk - lse_m) - [k == t_m])   for rows with 0 <= t_m < K, 0 for every other (= ignored) row
+ *   dot     grad_codes_k = sum_m w_mk x_m
+ *   Euclid  r_mk = w_mk / s_mk (0 where s_mk == 0, ATen's mask);   grad_codes_k = c_k sum_m r_mk - sum_m r_mk x_m
+ * Reads a->x (strided rows), a->cb (the natural codebook), H, M, K, D, metric; lse [H][M] contiguous (scale 1, natural log);
+ * target (h, m) at target[h*tgt_hs + m*tgt_rs], compared with 0 and K as the 64-bit value it is; coef: ONE float on the
+ * device.  grad_codes [H][K][D] contiguous.  The x, the lse and the logits of an ignored row are never multiplied with
+ * anything (they may be NaN / inf): its weight is selected to 0 and its row is packed as padding.  A wave owns 32 codes,
+ * the packed rows are streamed; the one-hot term is a comparison inside the sweep.  The rows are split over workgroups by the
+ * plan of vq_gumbel_backward_codes_f32 and the splits' partial sums are added in split order: no float atomics,
+ * bit-identical results from run to run on one device.  M == 0: grad_codes is cleared, nothing else is touched.
+ * VQ_E_UNSUPPORTED: D > 256, more than 2^31 - 1 rows, a packed row image of 2 GiB or more (use row chunks of
+ * vq_similarities_f32).  VQ_E_BADARG: a->cb, grad_codes, lse, target or coef null; a workspace that is too small or misaligned.
+ * Workspace (>= vq_ce_codes_workspace_bytes bytes, 16-byte aligned; 0 = unsupported shape), in 4-byte units, with
+ * img = vq_packed_floats(M, D), rsM = vq_gumbel_row_stride(M) and splits as in the reinmax entry below:
+ *   [x image: H*img][target int32: H*rsM (-1 = ignored or past M)][lse: H*rsM]
+ *   [grad_codes partials: splits*H*K*D, only when splits > 1]
+ */
+int64_t vq_ce_codes_workspace_bytes(int H, int64_t M, int K, int D);
+int vq_ce_backward_codes_f32(const vq_args *a, const float *lse, const int64_t *target, int64_t tgt_rs, int64_t tgt_hs,
+                             const float *coef, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * Backward of the straight-through Gumbel softmax over the similarities (utils/general.py:147-149 with

@@ -24,7 +24,7 @@ def main():
             "-c", "-Rpass-analysis=kernel-resource-usage", SRC]
     # the build parts of vq_kernels.hip compile in parallel (every kernel belongs to exactly one part)
     procs = [subprocess.Popen(base + [f"-DVQ_PART={part}", "-o", f"/tmp/vq_resusage_{part}.o", *extra], stderr=subprocess.PIPE,
-                              text=True) for part in range(11)]
+                              text=True) for part in range(12)]
     err = "".join(p.communicate()[1] for p in procs)
     if any(p.returncode for p in procs):
         sys.stderr.write(err[-4000:])

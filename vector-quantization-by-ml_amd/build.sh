@@ -15,7 +15,7 @@ if [ "${VQ_BUILD_SINGLE:-0}" = "1" ]; then
 fi
 tag=$(echo "$OUT $FLAGS" | md5sum | cut -c1-8)
 pids=()
-for part in 0 1 2 3 4 5 6 7 8 9 10; do
+for part in 0 1 2 3 4 5 6 7 8 9 10 11; do
     $HIPCC $FLAGS -DVQ_PART=$part -c csrc/vq_kernels.hip -o build/vq_part${part}_$tag.o &
     pids+=($!)
 done

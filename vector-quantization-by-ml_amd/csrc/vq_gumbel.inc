@@ -60,6 +60,17 @@
 //              same staged tile -> G_i = sum_j cos_ij x_j (p.out; null: the contraction and the finalize are skipped).
 //              cos of a streamed row past n and of a resident row past n is SELECTED to 0 by index before either use; a
 //              NaN / inf of a real row goes through untouched.  One lane set per row, tile order, no atomics.
+//
+// Cross-entropy loss over the similarities (vector_quantize_pytorch.py:287-297), the gradient with respect to a learnable
+// codebook, one more role with one product per sub-tile.  lse = the natural-log log-sum-exp vq_softmax_stats_f32 wrote (scale 1),
+// t the target of the row, coef one float on the device:   w_mk = coef (exp(s_mk - lse_m) - [k == t_m])
+//   kCeC       the orientation of kGumC over the natural-order x image: lse and the int32 copy of the target of the 16 streamed
+//              rows read four at a time (as kRmC reads its statistics and ind32); the one-hot term is the comparison of the
+//              row's target with the lane's code, no side pass.  The int32 copy holds -1 for an ignored row (target < 0 or
+//              >= K, compared as the 64-bit value) and past M, and the image holds such a row as padding (zeros, |x|^2 = +inf):
+//              its w / r is SELECTED to 0 before the contraction and the column sum, whatever NaN / inf its x or lse holds.
+//              The norms enter the product in vq_sweep_aux's order, so s is the value lse was summed from bit for bit (one
+//              code: exp(s - lse) = 1 and the gradient is exactly 0).  Row splits and partials as kGumC.
 // ------------------------------------------------------------------------------------------------
 constexpr int kGumStats = 0;
 constexpr int kGumX = 1;
@@ -74,6 +85,7 @@ constexpr int kDivDelta = 9;
 constexpr int kDivX = 10;
 constexpr int kDivC = 11;
 constexpr int kOrth = 12;
+constexpr int kCeC = 13;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 }  // namespace
@@ -105,6 +117,8 @@ struct GumbelParams {
     float *colp, *ep;              // kRmCol: partials [splits][H][ck_hs]
     long long cp_zs;
     // orthogonal role (kOrth): lse = rowsq [H][st_hs], out = G or null
+    // cross-entropy role (kCeC): lse = the natural-log log-sum-exp [H][st_hs], ind32 = the targets (-1: ignored), out the partials of gc
+    const float *coef;             // kCeC: one float, upstream gradient / number of non-ignored rows
     // diversity roles (tau = -T; lse: per row, kDivAcc / kDivC in image order; delta (kDivC: in image order); out: gx, kDivAcc
     // the per-head partials of A, kDivC the partials of gc)
     const float *U;                // kDivDelta / kDivX / kDivC: [N][U_rs], finite past K
@@ -152,13 +166,14 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     constexpr int RS = G::RS, RS4 = G::RS4, SUB = G::SUB, NG = DP / 8, V = GG::V, NJ = GG::NJ, NACC = GG::NACC;
     constexpr bool EUCLID = (METRIC == VQ_METRIC_EUCLID);
     constexpr bool DIV = (ROLE >= kDivStats);  // one product per sub-tile, no g
-    constexpr bool CODES = (ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC || ROLE == kDivAcc || ROLE == kDivC);
+    constexpr bool CODES = (ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC || ROLE == kDivAcc || ROLE == kDivC || ROLE == kCeC);
     constexpr bool RM = (ROLE >= kRmStats && ROLE <= kRmC);
     constexpr bool COLS = (ROLE == kRmCol);
     // no contraction: no gradient accumulators
     constexpr bool STATS = (ROLE == kGumStats || ROLE == kRmStats || COLS || ROLE == kDivStats || ROLE == kDivAcc || ROLE == kDivDelta);
     constexpr bool GIMG = CODES && !DIV;  // a second streamed image at compile time: the packed g rows
     constexpr bool DIVIMG = (ROLE == kDivAcc || ROLE == kDivC);  // the streamed image is the position-major x image
+    constexpr bool XNORM_FIRST = DIVIMG || ROLE == kCeC;         // |x|^2 of the streamed row enters the product before |c|^2
     constexpr int IMG_F4 = 2 * G::BUF_F4;  // the two tile buffers of one image
     constexpr float LOG2E = 1.4426950408889634f;
     const float INF = __builtin_inff();
@@ -193,8 +208,9 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     const bool live = (ROLE == kDivX) && p.gimg != nullptr;  // (workgroup-uniform) contract with the tile of a second image
     const bool contract = ROLE != kOrth || p.out != nullptr;  // (workgroup-uniform) kOrth without G: rowsq only
     const float *gimg = GIMG ? p.gimg + (long long)head * p.img_hs : (live ? p.gimg + (long long)head * p.gimg_hs : nullptr);
-    // (kDivAcc / kDivC: the streamed row's norm first, as in the rows-resident roles -- its similarities are theirs bit for bit)
-    const float b_aug = DIVIMG ? (h ? rn0 : 1.0f) : (h ? 1.0f : rn0);
+    // (kDivAcc / kDivC: the streamed row's norm first, as in the rows-resident roles -- its similarities are theirs bit for bit;
+    // kCeC: as in vq_sweep_aux, whose log-sum-exp it reads)
+    const float b_aug = XNORM_FIRST ? (h ? rn0 : 1.0f) : (h ? 1.0f : rn0);
     const float tau2 = p.tau * LOG2E;
     const long long st0 = (long long)head * p.st_hs;
 
@@ -212,6 +228,8 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     }
     // reinmax: kRmX the rest of the row's statistics and its selected code; kRmC the lane's own code's 1 / col and e
     float lse1_row = 0.0f, rcol_own = 0.0f, e_own = 0.0f;
+    float coef = 0.0f;
+    if constexpr (ROLE == kCeC) coef = *p.coef;
     long long ind_row = -1;
     if (ROLE == kRmX && row_ok) {
         lse1_row = p.lse1[st0 + row];
@@ -249,7 +267,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     };
 
     int t_begin = 0, t_end = p.ntiles;
-    if constexpr (GIMG || ROLE == kDivC) {
+    if constexpr (GIMG || ROLE == kDivC || ROLE == kCeC) {
         t_begin = (int)blockIdx.z * p.tiles_per_split;
         t_end = t_begin + p.tiles_per_split < p.ntiles ? t_begin + p.tiles_per_split : p.ntiles;
     }
@@ -283,7 +301,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
             const long long sbase = (long long)u * kTileCodes + 4 * h;  // streamed row of this lane's register 0
             // kGumC: the statistics of the 16 streamed rows this lane's registers stand for (rows 8 g + 4 h + 0..3 of the sub-tile)
             f32x4 l4[4], d4[4];
-            if constexpr (CODES && !RM) {
+            if constexpr (CODES && !RM && ROLE != kCeC) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     l4[g] = *(const f32x4 *)(p.lse + st0 + sbase + 8 * g);
@@ -300,7 +318,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                 if constexpr (CODES || DIV) mfma_range<DP, 0, NG>(acc, a, ta, rf);
                 else mfma_range2<DP>(acc, acca, a, ta, rf, gf);
                 if (EUCLID) {
-                    const float a_aug = DIVIMG ? (h ? 1.0f : cnv) : (h ? cnv : 1.0f);
+                    const float a_aug = XNORM_FIRST ? (h ? 1.0f : cnv) : (h ? cnv : 1.0f);
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a_aug, b_aug, acc, 0, 0, 0);
                 }
             }
@@ -355,6 +373,32 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                     v = (jb + (r & 3) + 8 * (r >> 2) < p.div_ch) ? v : 0.0f;
                     acc[r] = v;
                     sum_u += v;
+                }
+                sum_ratio += sum_u;
+            } else if constexpr (ROLE == kCeC) {
+                // ---- acc[r] <- w (dot) / r = w / s (Euclid) of (streamed row sbase + 8 g + q, this lane's code), w = coef (p - onehot)
+                float sum_u = 0.0f;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 ls4 = *(const f32x4 *)(p.lse + st0 + sbase + 8 * g);
+                    const i32x4 t4 = *(const i32x4 *)(p.ind32 + st0 + sbase + 8 * g);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int r = 4 * g + q;
+                        const float tv = acc[r];
+                        const float tc = tv < 0.0f ? 0.0f : tv;  // (keeps a NaN, unlike fmaxf)
+                        const float sv = EUCLID ? -__builtin_amdgcn_sqrtf(tc) : tv;  // the logit vq_sweep_aux summed
+                        const float pr = __builtin_amdgcn_exp2f((sv - ls4[q]) * LOG2E);
+                        float v = coef * (pr - (((long long)t4[q] == row) ? 1.0f : 0.0f));
+                        if (EUCLID) {
+                            v = -v * __builtin_amdgcn_rsqf(tc);  // w / s with s = -dist
+                            if (tc == 0.0f) v = 0.0f;            // s == 0: ATen's subgradient 0 (a NaN stays a NaN)
+                        }
+                        // an ignored row and a row past M: its x, its lse and with them v may be NaN / inf -- select, never multiply
+                        v = t4[q] >= 0 ? v : 0.0f;
+                        acc[r] = v;
+                        sum_u += v;
+                    }
                 }
                 sum_ratio += sum_u;
             } else if constexpr (ROLE == kOrth) {
@@ -668,6 +712,8 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
 // row j of sequence position n for j < C -- source row ((j / pos_div) N + n) pos_div + j % pos_div, the j-th row m in
 // ascending order with (m / pos_div) % N == n -- and padding for C <= j < Cp and past N Cp; `stat` (a per-row array,
 // [head][stat_hs]) is copied along in image order, 0 in the padding, and so is `stat2` when it is given (same strides).
+// With `keep` (the cross-entropy loss: the int32 targets vq_gumbel_pack_ind wrote) a row whose entry is negative is packed as
+// padding and its x is not read: a NaN / inf there must not meet the zero weight of the row in the contraction.
 }  // namespace
 namespace vqi {
 struct RowMap {
@@ -678,6 +724,8 @@ struct RowMap {
     long long stat_hs, stat_img_hs;
     const float *stat2;  // optional second per-row array (kDivC: delta beside lse2)
     float *stat2_img;
+    const int *keep;  // optional (kCeC, Cp == 0): [head][keep_hs], image row m is real only where keep >= 0
+    long long keep_hs;
 };
 }  // namespace vqi
 namespace {
@@ -690,6 +738,7 @@ __global__ void __launch_bounds__(64) vq_gumbel_pack_rows(const float *__restric
     if (m >= Mp) return;
     const int RS = DP + 4;
     bool real = m < M;
+    if (map.keep && real) real = map.keep[(long long)blockIdx.y * map.keep_hs + m] >= 0;
     long long src = m;
     if (map.Cp > 0) {
         const long long n = m / map.Cp, j = m % map.Cp;
@@ -739,17 +788,21 @@ __global__ void __launch_bounds__(256) vq_gumbel_reduce_parts(const float *__res
 }
 
 // the int32 copy of ind the codes-resident reinmax roles read 16 bytes at a time: [H][stride], -1 past M and for values no
-// code index can equal (the copy is only ever compared)
+// code index can equal (the copy is only ever compared).  K > 0 (kCeC: ind is the target of the cross entropy): a value >= K
+// is -1 too -- the 64-bit value is compared, before the narrowing -- and `stat` [H][stat_hs] (the log-sum-exp, rows of M
+// floats) is copied along to stat_out [H][stride], 0 past M.
 __global__ void __launch_bounds__(256) vq_gumbel_pack_ind(const long long *__restrict__ ind, long long ind_rs, long long ind_hs, long long M,
-                                                          long long stride, int *__restrict__ out) {
+                                                          long long stride, int *__restrict__ out, int K, const float *__restrict__ stat,
+                                                          long long stat_hs, float *__restrict__ stat_out) {
     const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
     if (m >= stride) return;
     int v = -1;
     if (m < M) {
         const long long i = ind[(long long)blockIdx.y * ind_hs + m * ind_rs];
-        if (i >= 0 && i <= 0x7FFFFFFFll) v = (int)i;
+        if (i >= 0 && i <= 0x7FFFFFFFll && (K <= 0 || i < K)) v = (int)i;
     }
     out[(long long)blockIdx.y * stride + m] = v;
+    if (stat) stat_out[(long long)blockIdx.y * stride + m] = m < M ? stat[(long long)blockIdx.y * stat_hs + m] : 0.0f;
 }
 
 // col[h][k] = colp[0] + colp[1] + ... and e[h][k] = (ep[0] + ep[1] + ...) / col in this order; 1 / 0 in the padding past K

@@ -73,6 +73,7 @@
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward (+ live codes)
 //   7 Gumbel straight-through backward sweeps               8 Gumbel-max sampling sweeps + Gumbel reinmax backward sweeps
 //   9 codebook diversity loss sweeps                       10 orthogonal regularisation loss sweep
+//  11 cross-entropy loss: the codes-gradient sweep
 #ifndef VQ_PART
 #define VQ_PART -1
 #endif
@@ -485,6 +486,12 @@ int launch_diversity_m(int role, const GumbelParams &p, int H, int gz, int metri
     });
 }
 
+// the cross-entropy role of the same sweep (the gradient with respect to a learnable codebook): a build part of its own
+template <int DP>
+int launch_ce_codes_m(const GumbelParams &p, int H, int gz, int metric, hipStream_t s) {
+    return with_metric(metric, [&](auto m) { return launch_gumbel_t<DP, decltype(m)::value, kCeC>(p, H, gz, s); });
+}
+
 // the orthogonal role of the same sweep (dot metric only): a build part of its own
 template <int DP>
 int launch_orthogonal_m(const GumbelParams &p, int H, hipStream_t s) {
@@ -536,11 +543,13 @@ template <int DP> int part_gumbel(int role, const GumbelParams &p, int H, int gz
 template <int DP> int part_reinmax(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <int DP> int part_diversity(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <int DP> int part_orthogonal(const GumbelParams &p, int H, hipStream_t s);
+template <int DP> int part_ce_codes(const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 #define VQ_DECLARE_GUMBEL_PARTS(DP)                                                                              \
     template <> int part_gumbel<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s); \
     template <> int part_reinmax<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s);  \
     template <> int part_diversity<DP>(int role, const GumbelParams &p, int H, int gz, int metric, hipStream_t s); \
-    template <> int part_orthogonal<DP>(const GumbelParams &p, int H, hipStream_t s);
+    template <> int part_orthogonal<DP>(const GumbelParams &p, int H, hipStream_t s);                              \
+    template <> int part_ce_codes<DP>(const GumbelParams &p, int H, int gz, int metric, hipStream_t s);
 template <int DP> int part_ce_bwd_live(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
 template <> int part_ce_bwd_live<32>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
 template <> int part_ce_bwd_live<64>(const CeBwdLiveParams &p, int H, int metric, hipStream_t s);
@@ -698,6 +707,15 @@ VQ_DEFINE_ORTHOGONAL_PART(64)
 VQ_DEFINE_ORTHOGONAL_PART(128)
 VQ_DEFINE_ORTHOGONAL_PART(256)
 #undef VQ_DEFINE_ORTHOGONAL_PART
+#endif
+#if VQ_OWN(11)
+#define VQ_DEFINE_CE_CODES_PART(DP) \
+    template <> int part_ce_codes<DP>(const GumbelParams &p, int H, int gz, int metric, hipStream_t s) { return launch_ce_codes_m<DP>(p, H, gz, metric, s); }
+VQ_DEFINE_CE_CODES_PART(32)
+VQ_DEFINE_CE_CODES_PART(64)
+VQ_DEFINE_CE_CODES_PART(128)
+VQ_DEFINE_CE_CODES_PART(256)
+#undef VQ_DEFINE_CE_CODES_PART
 #endif
 }  // namespace vqi
 
@@ -2007,25 +2025,28 @@ int64_t vq_gumbel_row_stride(int64_t M) { return M <= 0 ? 0 : (M + 255) / 256 * 
 //   [x image H x img_floats][g image H x img_floats]
 //   reinmax only: [ind int32 H x row_stride(M)][col partials splits x H x row_stride(K)][e partials splits x H x row_stride(K)]
 //   [grad_codes partials splits x H x K x D, splits > 1]
+// The cross entropy (vq_ce_backward_codes_f32) has no g image:
+//   [x image H x img_floats][target int32 H x row_stride(M)][lse H x row_stride(M)][grad_codes partials splits x H x K x D, splits > 1]
 struct GumbelWorkspace {
     GumbelCodesPlan pl;
-    long long gimg_off, ind_off, colp_off, ep_off, parts_off, floats;
+    long long gimg_off, ind_off, lse_off, colp_off, ep_off, parts_off, floats;
 };
-static GumbelWorkspace gumbel_workspace(int H, long long M, int K, int D, bool reinmax) {
+static GumbelWorkspace gumbel_workspace(int H, long long M, int K, int D, bool reinmax, bool ce = false) {
     GumbelWorkspace w;
     w.pl = plan_gumbel_codes(H, M, K, D);
     const long long ck = reinmax ? w.pl.splits * (long long)H * vq_gumbel_row_stride(K) : 0;
     w.gimg_off = (long long)H * w.pl.img_floats;
-    w.ind_off = 2 * w.gimg_off;
-    w.colp_off = w.ind_off + (reinmax ? (long long)H * vq_gumbel_row_stride(M) : 0);
+    w.ind_off = ce ? w.gimg_off : 2 * w.gimg_off;
+    w.lse_off = w.ind_off + ((reinmax || ce) ? (long long)H * vq_gumbel_row_stride(M) : 0);
+    w.colp_off = w.lse_off + (ce ? (long long)H * vq_gumbel_row_stride(M) : 0);
     w.ep_off = w.colp_off + ck;
     w.parts_off = w.ep_off + ck;
     w.floats = w.parts_off + (w.pl.splits > 1 ? (long long)w.pl.splits * H * K * D : 0);
     return w;
 }
-static int64_t gumbel_workspace_bytes(int H, int64_t M, int K, int D, bool reinmax) {
+static int64_t gumbel_workspace_bytes(int H, int64_t M, int K, int D, bool reinmax, bool ce = false) {
     if (H <= 0 || M <= 0 || K <= 0 || D <= 0 || D > 256 || M > 0x7FFFFFFFll) return 0;
-    return 4 * gumbel_workspace(H, M, K, D, reinmax).floats;
+    return 4 * gumbel_workspace(H, M, K, D, reinmax, ce).floats;
 }
 int64_t vq_gumbel_workspace_bytes(int H, int64_t M, int K, int D) { return gumbel_workspace_bytes(H, M, K, D, false); }
 int64_t vq_gumbel_reinmax_workspace_bytes(int H, int64_t M, int K, int D) { return gumbel_workspace_bytes(H, M, K, D, true); }
@@ -2037,11 +2058,14 @@ int64_t vq_gumbel_reinmax_workspace_bytes(int H, int64_t M, int K, int D) { retu
 struct GumbelFamily {
     bool reinmax, tau_finite, null_first;
     const char *null_msg, *tau_msg, *ws_msg;
+    bool ce;  // the cross entropy's workspace: no g image, the int32 targets and the log-sum-exp behind the x image
 };
 constexpr GumbelFamily kStraightThrough = {false, false, true, "null argument (g / lse2 / delta)", "tau must be positive",
                                            "workspace too small or misaligned (see vq_gumbel_workspace_bytes)"};
 constexpr GumbelFamily kReinmax = {true, true, false, "g is null", "tau must be positive and finite",
                                    "workspace too small or misaligned (see vq_gumbel_reinmax_workspace_bytes)"};
+constexpr GumbelFamily kCrossEntropy = {false, false, false, nullptr, nullptr,
+                                        "workspace too small or misaligned (see vq_ce_codes_workspace_bytes)", true};
 
 // what every entry checks and fills; `arrays`: the per-row and per-code arrays the entry uses (non-null, 16-byte aligned)
 static int fill_gumbel_params(GumbelParams &p, const char *who, const GumbelFamily &f, const vq_args *a, const float *g, int64_t g_rs,
@@ -2084,30 +2108,31 @@ static int fill_gumbel_codes(GumbelParams &p, const char *who, const GumbelFamil
                              int64_t workspace_bytes, GumbelWorkspace &w) {
     if (!a->cb) return fail(VQ_E_BADARG, who, "cb is null");
     if (a->M > 0x7FFFFFFFll) return fail(VQ_E_UNSUPPORTED, who, "too many rows (use row chunks)");
-    w = gumbel_workspace(a->H, a->M, a->K, a->D, f.reinmax);
+    w = gumbel_workspace(a->H, a->M, a->K, a->D, f.reinmax, f.ce);
     if (w.pl.img_floats * 4 >= (1ll << 31)) return fail(VQ_E_UNSUPPORTED, who, "packed row image >= 2 GiB (use row chunks)");
     if (!workspace || !aligned16(workspace) || workspace_bytes < 4 * w.floats) return fail(VQ_E_BADARG, who, f.ws_msg);
     float *ws = (float *)workspace;
     p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
     p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
-    p.img = ws; p.gimg = ws + w.gimg_off;
+    p.img = ws; p.gimg = f.ce ? nullptr : ws + w.gimg_off;
     p.img_hs = w.pl.img_floats; p.img_bytes = (unsigned)(w.pl.img_floats * 4);
-    if (f.reinmax) p.ind32 = (const int *)(ws + w.ind_off);
+    if (f.reinmax || f.ce) p.ind32 = (const int *)(ws + w.ind_off);
     p.NR = a->K; p.NS = a->M;
     p.ntiles = w.pl.ntiles;
     p.tiles_per_split = w.pl.tiles_per_split;
     return 0;
 }
 
-// the x rows and the g rows into the two images at the head of the workspace
-static int pack_gumbel_rows(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, const GumbelWorkspace &w, float *ws, hipStream_t s) {
+// the x rows and the g rows into the two images at the head of the workspace (g null: the x image alone)
+static int pack_gumbel_rows(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, const GumbelWorkspace &w, float *ws, hipStream_t s,
+                            const vqi::RowMap &map = vqi::RowMap{}) {
     return launch<vq_gumbel_pack_rows>(dim3((unsigned)((w.pl.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
                                        (long long)a->x_rs, (long long)a->x_hs, g, (long long)g_rs, (long long)g_hs, (long long)a->M, w.pl.Mp,
-                                       a->D, padded_dim(a->D), a->metric, ws, ws + w.gimg_off, w.pl.img_floats, vqi::RowMap{});
+                                       a->D, padded_dim(a->D), a->metric, ws, ws + w.gimg_off, w.pl.img_floats, map);
 }
 
-// the only padded-dim dispatch of the thirteen roles: the kGum* kernels live in build part 7, the kRm* kernels in part 8, the kDiv* kernels in
-// part 9, kOrth in part 10
+// the only padded-dim dispatch of the fourteen roles: the kGum* kernels live in build part 7, the kRm* kernels in part 8, the kDiv* kernels in
+// part 9, kOrth in part 10, kCeC in part 11
 static int launch_gumbel(int role, const GumbelParams &p, const vq_args *a, int gz, hipStream_t s) {
     const int DP = padded_dim(a->D);
     return with_padded_dim(DP == 512 ? 0 : DP,
@@ -2115,6 +2140,7 @@ static int launch_gumbel(int role, const GumbelParams &p, const vq_args *a, int 
                                constexpr int DPC = decltype(dp)::value;
                                if constexpr (DPC > 256) return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
                                else if (role == kOrth) return vqi::part_orthogonal<DPC>(p, a->H, s);
+                               else if (role == kCeC) return vqi::part_ce_codes<DPC>(p, a->H, gz, a->metric, s);
                                else if (role >= kDivStats) return vqi::part_diversity<DPC>(role, p, a->H, gz, a->metric, s);
                                else if (role < kRmStats) return vqi::part_gumbel<DPC>(role, p, a->H, gz, a->metric, s);
                                else return vqi::part_reinmax<DPC>(role, p, a->H, gz, a->metric, s);
@@ -2128,7 +2154,7 @@ static int clear_grad_codes(const vq_args *a, float *grad_codes, hipStream_t s, 
     return e == hipSuccess ? 0 : hip_fail(e, what);
 }
 
-// ... else the sweep (kGumC / kRmC), straight into grad_codes or into one partial per row split that vq_gumbel_reduce_parts sums
+// ... else the sweep (kGumC / kRmC / kCeC), straight into grad_codes or into one partial per row split that vq_gumbel_reduce_parts sums
 static int sweep_grad_codes(int role, GumbelParams &p, const vq_args *a, const GumbelWorkspace &w, float *ws, float *grad_codes, hipStream_t s) {
     const long long n = (long long)a->H * a->K * a->D;
     float *parts = ws + w.parts_off;
@@ -2212,7 +2238,7 @@ int vq_gumbel_reinmax_columns_f32(const vq_args *a, const float *g, int64_t g_rs
     if ((rc = pack_gumbel_rows(a, g, g_rs, g_hs, w, ws, s))) return rc;
     if ((rc = launch<vq_gumbel_pack_ind>(dim3((unsigned)((p.st_hs + 255) / 256), (unsigned)a->H), dim3(256), 0, s, "vq_gumbel_pack_ind launch",
                                          (const long long *)ind, (long long)ind_rs, (long long)ind_hs, (long long)a->M, p.st_hs,
-                                         (int *)(ws + w.ind_off))))
+                                         (int *)(ws + w.ind_off), 0, (const float *)nullptr, 0ll, (float *)nullptr)))
         return rc;
     p.lse = (float *)lse2_tau;
     p.colp = ws + w.colp_off; p.ep = ws + w.ep_off;
@@ -2472,6 +2498,40 @@ int vq_diversity_backward_codes_f32(const vq_args *a, float T, int N, int pos_di
     if (pl.splits == 1) return 0;
     return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
                                           pl.splits, grad_codes);
+}
+
+// ---- cross-entropy loss, the gradient with respect to a learnable codebook: the kCeC role of vq_gumbel.inc --------------
+int64_t vq_ce_codes_workspace_bytes(int H, int64_t M, int K, int D) { return gumbel_workspace_bytes(H, M, K, D, false, true); }
+
+int vq_ce_backward_codes_f32(const vq_args *a, const float *lse, const int64_t *target, int64_t tgt_rs, int64_t tgt_hs,
+                             const float *coef, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream) {
+    static const char who[] = "vq_ce_backward_codes";
+    int rc = check_common(a);
+    if (rc) return rc;
+    if (!grad_codes || !a->cb || !coef) return fail(VQ_E_BADARG, who, "null argument (grad_codes / cb / coef)");
+    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, who, "D > 256 (use row chunks of vq_similarities_f32)");
+    hipStream_t s = (hipStream_t)stream;
+    if (a->M == 0) return clear_grad_codes(a, grad_codes, s, "vq_ce_backward_codes memset");
+    if (!lse || !target) return fail(VQ_E_BADARG, who, "null argument (lse / target)");
+    GumbelParams p;
+    GumbelWorkspace w;
+    memset(&p, 0, sizeof(p));
+    p.D = a->D;
+    p.st_hs = vq_gumbel_row_stride(a->M);
+    if ((rc = fill_gumbel_codes(p, who, kCrossEntropy, a, workspace, workspace_bytes, w))) return rc;
+    float *ws = (float *)workspace;
+    // the targets (-1: ignored, compared as 64-bit values) and the log-sum-exp at the sweep's 16-byte aligned head stride ...
+    if ((rc = launch<vq_gumbel_pack_ind>(dim3((unsigned)((p.st_hs + 255) / 256), (unsigned)a->H), dim3(256), 0, s, "vq_gumbel_pack_ind launch",
+                                         (const long long *)target, (long long)tgt_rs, (long long)tgt_hs, (long long)a->M, p.st_hs,
+                                         (int *)(ws + w.ind_off), a->K, lse, (long long)a->M, ws + w.lse_off)))
+        return rc;
+    // ... then the x image, an ignored row as padding
+    vqi::RowMap map{};
+    map.keep = p.ind32; map.keep_hs = p.st_hs;
+    if ((rc = pack_gumbel_rows(a, nullptr, 0, 0, w, ws, s, map))) return rc;
+    p.lse = ws + w.lse_off;
+    p.coef = coef;
+    return sweep_grad_codes(kCeC, p, a, w, ws, grad_codes, s);
 }
 
 // ---- orthogonal regularisation loss: the kOrth role of vq_gumbel.inc ---------------------------------------------------

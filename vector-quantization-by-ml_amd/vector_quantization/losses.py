@@ -9,11 +9,14 @@ The reference hands the full ``similarities [h, M, K]`` tensor (its ``distances`
 
 Here the forward of the cross entropy is ONE native sweep with an online-softmax epilogue
 (``vq_softmax_stats_f32``: per row log-sum-exp + target logit).  Everything that needs actual matrix entries
-(backward passes outside the fused kernels' range, the cross entropy of a learnable codebook) works on bounded row chunks: ``vq_similarities_f32`` emits a chunk, the
+(backward passes outside the fused kernels' range or below their measured cuts) works on bounded row chunks: ``vq_similarities_f32`` emits a chunk, the
 chunk's contribution is evaluated with ordinary tensor ops, and gradients flow through ``_SimilarityFn`` whose
 backward is ATen's ``_euclidean_dist_backward`` formula (two library GEMMs per chunk).  The cross entropy's backward with
 respect to x is one fused native sweep instead (``vq_ce_backward_f32``; with an EMA codebook, whose update rewrites the codes
 between forward and backward, ``vq_ce_backward_live_f32``) wherever the kernels reach: D <= 512, with live codes D <= 256.
+A learnable codebook gets the cross entropy's gradient from one more fused sweep (``vq_ce_backward_codes_f32``, D <= 256) from
+``CE_CODES_FUSED_MIN_ROWS`` rows per head on (``ce_codes_runs_fused``), unless its codes are rewritten before backward (live
+codes); VQ_CE_CODES_NO_FUSED=1 keeps the chunks.
 The diversity loss is four fused sweeps (``vq_diversity_*_f32``: row log-sum-exps, the position table [N, K], delta per row,
 grad_x -- against the live codes of an EMA codebook) for D <= 256, from ``DIVERSITY_FUSED_MIN_ROWS`` rows per sequence
 position on (``diversity_runs_fused``); a learnable codebook gets its gradient from a fifth sweep
@@ -156,8 +159,10 @@ class _CrossEntropyFn(torch.autograd.Function):
     """mean over non-ignored (h, m) of  logsumexp_k sims[h, m, k] - sims[h, m, target[h, m]]
     == F.cross_entropy(rearrange(distances, ...), codes, ignore_index=-1)   vector_quantize_pytorch.py:292-294.
     Forward: one native sweep (online softmax).  Backward: one fused sweep (vq_ce_backward_f32, with ``live_codes``
-    vq_ce_backward_live_f32); bounded chunks of the similarity matrix outside their range, for a learnable codebook and
-    under VQ_CE_NO_LIVE=1 (live codes only)."""
+    vq_ce_backward_live_f32); codes that require grad get their gradient from one more sweep (vq_ce_backward_codes_f32) from
+    CE_CODES_FUSED_MIN_ROWS rows on (``ce_codes_runs_fused``), unless they are rewritten before backward (live codes) or
+    VQ_CE_CODES_NO_FUSED=1 is set.  Bounded chunks of the similarity matrix outside the kernels' range, for such a
+    learnable codebook and under VQ_CE_NO_LIVE=1 (live codes only)."""
 
     @staticmethod
     def forward(ctx, x, codes, target, metric, live_codes=None, lse=None, tl=None, live_packed=None):
@@ -192,6 +197,15 @@ class _CrossEntropyFn(torch.autograd.Function):
                            live_packed=packed)
             if gx is not None:
                 return gx, None, None, None, None, None, None, None
+        if fused is not None and ctx.needs_input_grad[1] and _ce_codes_fused(x, codes, live):
+            # a learnable codebook: the same sweep for the rows (only when they need a gradient) and one more with the codes
+            # resident for theirs (vq_ce_backward_codes_f32) -- nothing of [M, K] either
+            backend = search.get_backend()
+            coef = (g / count).reshape(1).to(torch.float32)
+            gc = backend.cross_entropy_backward_codes(x.detach(), codes.detach(), lse, target, coef, metric=metric)
+            gx = fused(x.detach(), codes.detach(), lse, tl, target, coef, metric=metric) if ctx.needs_input_grad[0] else None
+            if gc is not None and (gx is not None or not ctx.needs_input_grad[0]):
+                return gx, gc, None, None, None, None, None, None
 
         def chunk_value(xc, cc, rows):
             sims = similarity_matrix(xc, cc, metric, live)
@@ -201,6 +215,48 @@ class _CrossEntropyFn(torch.autograd.Function):
         chunks = _row_slices(x.shape[1], _rows_per_chunk(x.shape[0], codes.shape[1]))
         gx, gc = _chunk_grads(chunk_value, x, codes, chunks, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return gx, gc, None, None, None, None, None, None
+
+
+# Rows per head from which the fused backward of a cross entropy whose codes require grad runs, per padded row width (32 / 64 /
+# 128 / 256 dims).  The step is two sweeps: vq_ce_backward_f32 for the rows -- one workgroup per 128 rows streams ALL codes, so
+# few rows of a large, wide codebook leave the chip idle -- and vq_ce_backward_codes_f32 for the codes; the chunked step is two
+# library GEMMs on a matrix that is small when the rows are few.  Measured on an MI355X (profiles/ce_codes_bench.md): forward +
+# backward of VectorQuantize(CodebookParams(learnable_codebook=True, ema_update=False), commitment_use_cross_entropy_loss=True)
+# in train mode, x [B, N, D], ms, the parent commit's path (VQ_CE_CODES_NO_FUSED=1) / fused, two alternating runs each; "no" =
+# the slower fused run was not faster than the faster chunked run:
+#   D     K      32 rows                  256 rows                 1024 rows                4096 rows                16384 rows
+#   32    1024   0.79 0.57 / 0.31 0.40    0.79 0.56 / 0.31 0.41    0.74 0.68 / 0.43 0.51    0.75 0.69 / 0.42 0.49    0.96 0.70 / 0.43 0.52
+#   32    8192   0.83 0.75 / 0.65 0.65    0.80 0.80 / 0.67 0.67    1.08 0.88 / 0.68 0.68    1.26 1.26 / 0.73 0.73    3.25 3.24 / 0.96 0.95
+#   64    1024   0.57 0.55 / 0.30 0.30    0.57 0.54 / 0.31 0.30    1.17 0.71 / 0.44 0.51    1.08 0.68 / 0.46 0.52    2.74 0.71 / 0.44 0.52
+#   64    8192   1.01 1.01 / 1.01 1.01 no 1.07 1.07 / 1.02 1.02    1.15 1.15 / 1.05 1.05    2.77 1.53 / 1.14 1.14    3.67 3.67 / 1.47 1.46
+#   128   1024   0.56 0.54 / 0.31 0.31    0.56 0.54 / 0.32 0.32    0.97 0.69 / 0.44 0.53    1.14 0.68 / 0.44 0.53    1.29 0.72 / 0.44 0.53
+#   128   8192   1.49 1.49 / 1.74 1.74 no 1.53 1.53 / 1.76 1.76 no 1.63 1.63 / 1.80 1.80 no 2.10 2.11 / 1.94 1.92    4.66 4.66 / 2.41 2.41
+#   256   1024   0.55 0.54 / 0.50 0.50    0.56 0.55 / 0.52 0.52    0.91 0.56 / 0.55 0.55    0.99 0.56 / 0.58 0.58 no 1.28 0.89 / 0.72 0.71
+#   256   8192   2.48 2.49 / 3.09 3.09 no 2.55 2.55 / 3.12 3.12 no 2.68 2.68 / 3.19 3.19 no 3.24 3.24 / 3.45 3.44 no 6.77 6.78 / 4.29 4.28
+# Per padded row width the cut is the fewest measured rows from which the fused step was faster at every measured K and at
+# every larger measured row count; row counts between two measured ones take the higher cut, fewer than 32 rows were not
+# measured.  The memory does not depend on the cut (16384 rows, K = 8192: 1.4 GiB -> 17 to 105 MiB): lower the entries to
+# trade time for it.
+CE_CODES_FUSED_MIN_ROWS = {32: 32, 64: 256, 128: 4096, 256: 16384}
+
+
+def ce_codes_runs_fused(rows: int, dim: int) -> bool:
+    """The dispatch rule of the cross entropy's gradient with respect to a learnable codebook, a pure function of the shape:
+    ``rows`` = M rows per head against CE_CODES_FUSED_MIN_ROWS of the padded row width; wider rows keep the chunks."""
+    cut = next((c for dp, c in sorted(CE_CODES_FUSED_MIN_ROWS.items()) if dim <= dp), None)
+    return cut is not None and rows >= cut
+
+
+def _ce_codes_fused(x, codes, live) -> bool:
+    """The fused sweeps take the backward of a cross entropy whose codes require grad: no live codes (an EMA codebook that
+    learns through the orthogonal loss is rewritten before backward), a backend with the codes sweep, the kernel's range, the
+    measured cut; VQ_CE_CODES_NO_FUSED=1 keeps the chunks."""
+    if live is not None or os.environ.get("VQ_CE_CODES_NO_FUSED"):  # (read per call: tests and A/B runs compare both paths)
+        return False
+    backend = search.get_backend()
+    if getattr(backend, "cross_entropy_backward_codes", None) is None or not x.is_cuda:
+        return False
+    return ce_codes_runs_fused(x.shape[1], x.shape[2])  # (no entry for rows wider than 256 dims: they keep the chunks)
 
 
 def cross_entropy_to_codes(x: torch.Tensor, codes: torch.Tensor, target: torch.Tensor, metric: int,

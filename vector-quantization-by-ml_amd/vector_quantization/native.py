@@ -91,6 +91,8 @@ _SIGNATURES = {
     "vq_softmax_stats_f32": (_int, (_ap, _f32, _vp, _i64, _i64, _vp, _vp, _vp)),
     "vq_ce_backward_f32": (_int, (_ap, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp)),
     "vq_ce_backward_live_f32": (_int, (_ap, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp)),
+    "vq_ce_codes_workspace_bytes": (_i64, (_int, _i64, _int, _int)),
+    "vq_ce_backward_codes_f32": (_int, (_ap, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp)),
     "vq_gumbel_row_stride": (_i64, (_i64,)),
     "vq_gumbel_workspace_bytes": (_i64, (_int, _i64, _int, _int)),
     "vq_gumbel_stats_f32": (_int, (_ap, _vp, _i64, _i64, _f32, _vp, _vp, _vp)),
@@ -753,6 +755,44 @@ def ce_backward(x: torch.Tensor, cb: torch.Tensor, lse: torch.Tensor, target_log
 
 
 GUMBEL_MAX_DIM = 256  # vq_gumbel_*_f32: rows of one launch
+CE_CODES_MAX_DIM = GUMBEL_MAX_DIM  # vq_ce_backward_codes_f32 is a role of the same sweep
+
+
+def ce_codes_supported(H: int, M: int, K: int, D: int) -> bool:
+    """vq_ce_backward_codes_f32 takes this shape (D <= 256, fewer than 2^31 rows, a packed row image below 2 GiB)."""
+    if D > CE_CODES_MAX_DIM or M <= 0 or M > 0x7FFFFFFF:
+        return False
+    if int(load().vq_ce_codes_workspace_bytes(H, M, K, D)) <= 0:
+        return False
+    return int(load().vq_packed_floats(M, D)) * 4 < (1 << 31)
+
+
+def ce_backward_codes(x: torch.Tensor, cb: torch.Tensor, lse: torch.Tensor, target: torch.Tensor, coef: torch.Tensor, *,
+                      metric: int = EUCLID, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Fused backward of the cross entropy over the codebook with respect to a learnable codebook: gc [H, K, D] =
+    coef * d/dcodes sum over the rows with 0 <= target < K of (lse - logit[target]) (``out``: a contiguous destination).
+    lse [H, M] from softmax_stats (scale 1), target [H, M] int64 (any strides), coef: 1-element fp32 device tensor.
+    No rows: gc is all zeros.  Atomics-free: bit-identical from run to run on one device."""
+    _require_gpu(x, cb, lse, target, coef, out)
+    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous()
+    H, M, D = x.shape
+    K = cb.shape[1]
+    assert cb.shape[0] == H and cb.shape[2] == D and D <= CE_CODES_MAX_DIM
+    assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (H, M)
+    assert target.dtype == torch.int64 and tuple(target.shape) == (H, M)
+    assert coef.dtype == torch.float32 and coef.numel() == 1
+    if out is None:
+        out = torch.empty((H, K, D), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (H, K, D) and out.is_contiguous() and out.device == x.device
+    a = _vq_args(x, cb, metric=metric)
+    tail = (int(target.stride(1)), int(target.stride(0)), coef.data_ptr(), out.data_ptr())
+    if M == 0:  # (the per-row arrays are empty and have no address; nothing reads them)
+        _call("vq_ce_backward_codes_f32", x.device, a, None, None, *tail, None, 0)
+        return out
+    assert ce_codes_supported(H, M, K, D)
+    ws, ws_bytes = _sized_workspace("vq_ce_codes_workspace_bytes", x.device, H, M, K, D)
+    _call("vq_ce_backward_codes_f32", x.device, a, lse.data_ptr(), target.data_ptr(), *tail, ws.data_ptr(), ws_bytes)
+    return out
 
 
 def _gumbel_args(x, cb, g, metric, packed):

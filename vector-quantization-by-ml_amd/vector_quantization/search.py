@@ -194,6 +194,15 @@ class _NativeBackend:
         return native.ce_backward(x, cb.contiguous(), lse, target_logit, target, coef, metric=metric, live=live,
                                   live_packed=live_packed)
 
+    @staticmethod
+    def cross_entropy_backward_codes(x, cb, lse, target, coef, *, metric):
+        """Fused d/dcodes of the cross entropy for a learnable codebook (vq_ce_backward_codes_f32) -> gc [H, K, D]; None when
+        the shape is outside the kernel's range (D > 256, 2^31 rows, a packed row image of 2 GiB: the caller works on row
+        chunks)."""
+        h, m, d = x.shape
+        if d > native.CE_CODES_MAX_DIM or (m > 0 and not native.ce_codes_supported(h, m, cb.shape[1], d)):
+            return None
+        return native.ce_backward_codes(x, cb.contiguous(), lse.contiguous(), target, coef, metric=metric)
 
     @staticmethod
     def diversity_supported(H, M, K, D, n_positions, pos_div):
