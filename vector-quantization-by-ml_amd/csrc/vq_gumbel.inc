@@ -1,4 +1,5 @@
-// vq_gumbel.inc -- backward of the straight-through and of the reinmax Gumbel softmax over the similarities
+// vq_gumbel.inc -- one resident/streamed sweep, fourteen roles (the role table `sweep_role` below; host side: vq_sweep_host.inc).
+// First the backward of the straight-through and of the reinmax Gumbel softmax over the similarities
 // (utils/general.py:131-149, codebooks.py:386-395), nothing of [M, K] in memory.  Included by vq_kernels.hip (after vq_similarity.inc: shares its row
 // prologue, the tile geometry and the fragment pipeline of the search).
 // ------------------------------------------------------------------------------------------------
@@ -6,7 +7,7 @@
 //   p = softmax_k(tau s)      delta_m = sum_k p_mk a_mk      w = tau p (a - delta) = dL/ds
 //   dot     gx = w c                    gc = w^T x
 //   Euclid  r = w / s (0 at s == 0)     gx = x rowsum(r) - r c      gc = c colsum(r) - r^T x
-// One kernel, three roles.  "Resident" rows become MFMA B fragments of a wave (32 rows per wave), "streamed" rows pass
+// One kernel, three roles to begin with.  "Resident" rows become MFMA B fragments of a wave (32 rows per wave), "streamed" rows pass
 // through LDS as packed images (vq_pack.inc layout) and are the A operands:
 //   kGumStats  resident x and g rows, streamed codes: two products per tile (s and a), online softmax in the log2 domain
 //              -> lse2[m] = log2 sum_k exp2(tau s log2 e) and delta[m]
@@ -86,6 +87,40 @@ constexpr int kDivX = 10;
 constexpr int kDivC = 11;
 constexpr int kOrth = 12;
 constexpr int kCeC = 13;
+
+// The role table: ONE row per role, read by the kernel (its compile-time switches), by launch_gumbel_t (the dynamic LDS those
+// switches use) and by the host's launch_gumbel (the build part that owns the role's kernels).  A new role is a new row.
+enum SweepPart { kPartGumbel = 7, kPartReinmax = 8, kPartDiversity = 9, kPartOrthogonal = 10, kPartCeCodes = 11 };  // = VQ_PART
+struct SweepRole {
+    int part;
+    bool codes_resident;  // a wave owns 32 codes and the packed rows are streamed (else: rows resident, packed codes streamed)
+    bool one_product;     // one product per sub-tile: no g rows, nothing of a = g c^T
+    bool reinmax;
+    bool no_contraction;  // statistics only: no gradient accumulators, no finalize
+    bool second_image;    // a second streamed image at compile time: the packed g rows
+    bool xnorm_first;     // |x|^2 of the streamed row enters the product before |c|^2
+    bool z_splits_tiles;  // blockIdx.z owns tiles_per_split staged tiles
+};
+constexpr SweepRole sweep_role(int role) {
+    switch (role) {
+        //                      part             codes  one    reinmx no_con img2   xnorm  z_tiles
+        case kGumStats: return {kPartGumbel,     false, false, false, true,  false, false, false};
+        case kGumX:     return {kPartGumbel,     false, false, false, false, false, false, false};
+        case kGumC:     return {kPartGumbel,     true,  false, false, false, true,  false, true};
+        case kRmStats:  return {kPartReinmax,    false, false, true,  true,  false, false, false};
+        case kRmCol:    return {kPartReinmax,    true,  false, true,  true,  true,  false, true};
+        case kRmX:      return {kPartReinmax,    false, false, true,  false, false, false, false};
+        case kRmC:      return {kPartReinmax,    true,  false, true,  false, true,  false, true};
+        case kDivStats: return {kPartDiversity,  false, true,  false, true,  false, false, false};
+        case kDivAcc:   return {kPartDiversity,  true,  true,  false, true,  false, true,  false};
+        case kDivDelta: return {kPartDiversity,  false, true,  false, true,  false, false, false};
+        case kDivX:     return {kPartDiversity,  false, true,  false, false, false, false, false};
+        case kDivC:     return {kPartDiversity,  true,  true,  false, false, false, true,  true};
+        case kOrth:     return {kPartOrthogonal, false, true,  false, false, false, false, false};
+        case kCeC:      return {kPartCeCodes,    true,  true,  false, false, false, true,  true};
+        default:        return {-1,              false, false, false, false, false, false, false};
+    }
+}
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 }  // namespace
@@ -158,6 +193,17 @@ __device__ __forceinline__ void mfma_range2(f32x16 &acc, f32x16 &acc2, f32x4 (&a
     }
 }
 
+// the weight through the similarity (kDivC, kCeC, kDivX): dot w as it stands; Euclid r = w / s with s = -dist = -sqrt(tc), and at
+// s == 0 ATen's subgradient 0 (a NaN stays a NaN)
+template <bool EUCLID>
+__device__ __forceinline__ float euclid_ratio(float v, float tc) {
+    if (EUCLID) {
+        v = -v * __builtin_amdgcn_rsqf(tc);
+        if (tc == 0.0f) v = 0.0f;
+    }
+    return v;
+}
+
 template <int DP, int METRIC, int ROLE>
 __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const GumbelParams p) {
     constexpr int WAVES = 4;
@@ -165,15 +211,14 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     using GG = GumGeo<DP>;
     constexpr int RS = G::RS, RS4 = G::RS4, SUB = G::SUB, NG = DP / 8, V = GG::V, NJ = GG::NJ, NACC = GG::NACC;
     constexpr bool EUCLID = (METRIC == VQ_METRIC_EUCLID);
-    constexpr bool DIV = (ROLE >= kDivStats);  // one product per sub-tile, no g
-    constexpr bool CODES = (ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC || ROLE == kDivAcc || ROLE == kDivC || ROLE == kCeC);
-    constexpr bool RM = (ROLE >= kRmStats && ROLE <= kRmC);
+    constexpr SweepRole R = sweep_role(ROLE);  // (the fields are described at the table)
+    constexpr bool DIV = R.one_product;  // (the diversity roles, kOrth and kCeC)
+    constexpr bool CODES = R.codes_resident;
+    constexpr bool RM = R.reinmax;
     constexpr bool COLS = (ROLE == kRmCol);
-    // no contraction: no gradient accumulators
-    constexpr bool STATS = (ROLE == kGumStats || ROLE == kRmStats || COLS || ROLE == kDivStats || ROLE == kDivAcc || ROLE == kDivDelta);
-    constexpr bool GIMG = CODES && !DIV;  // a second streamed image at compile time: the packed g rows
-    constexpr bool DIVIMG = (ROLE == kDivAcc || ROLE == kDivC);  // the streamed image is the position-major x image
-    constexpr bool XNORM_FIRST = DIVIMG || ROLE == kCeC;         // |x|^2 of the streamed row enters the product before |c|^2
+    constexpr bool STATS = R.no_contraction;
+    constexpr bool GIMG = R.second_image;
+    constexpr bool XNORM_FIRST = R.xnorm_first;
     constexpr int IMG_F4 = 2 * G::BUF_F4;  // the two tile buffers of one image
     constexpr float LOG2E = 1.4426950408889634f;
     const float INF = __builtin_inff();
@@ -267,7 +312,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
     };
 
     int t_begin = 0, t_end = p.ntiles;
-    if constexpr (GIMG || ROLE == kDivC || ROLE == kCeC) {
+    if constexpr (R.z_splits_tiles) {
         t_begin = (int)blockIdx.z * p.tiles_per_split;
         t_end = t_begin + p.tiles_per_split < p.ntiles ? t_begin + p.tiles_per_split : p.ntiles;
     }
@@ -365,10 +410,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                     const float lg = EUCLID ? -tau2 * __builtin_amdgcn_sqrtf(tc) : tau2 * tv;  // as kDivStats rounded it
                     const float pr = __builtin_amdgcn_exp2f(lg - l4[r >> 2][r & 3]);
                     float v = (p.tau * pr) * (u_own - d4[r >> 2][r & 3]);
-                    if (EUCLID) {
-                        v = -v * __builtin_amdgcn_rsqf(tc);  // w / s with s = -dist
-                        if (tc == 0.0f) v = 0.0f;            // s == 0: ATen's subgradient 0 (a NaN stays a NaN)
-                    }
+                    v = euclid_ratio<EUCLID>(v, tc);
                     // row j of the position is real while j < div_ch; a padding row gives inf / NaN under Euclid: select, never multiply
                     v = (jb + (r & 3) + 8 * (r >> 2) < p.div_ch) ? v : 0.0f;
                     acc[r] = v;
@@ -390,10 +432,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                         const float sv = EUCLID ? -__builtin_amdgcn_sqrtf(tc) : tv;  // the logit vq_sweep_aux summed
                         const float pr = __builtin_amdgcn_exp2f((sv - ls4[q]) * LOG2E);
                         float v = coef * (pr - (((long long)t4[q] == row) ? 1.0f : 0.0f));
-                        if (EUCLID) {
-                            v = -v * __builtin_amdgcn_rsqf(tc);  // w / s with s = -dist
-                            if (tc == 0.0f) v = 0.0f;            // s == 0: ATen's subgradient 0 (a NaN stays a NaN)
-                        }
+                        v = euclid_ratio<EUCLID>(v, tc);
                         // an ignored row and a row past M: its x, its lse and with them v may be NaN / inf -- select, never multiply
                         v = t4[q] >= 0 ? v : 0.0f;
                         acc[r] = v;
@@ -431,10 +470,7 @@ __global__ void __launch_bounds__(256, (DP <= 64 ? 2 : 1)) vq_gumbel_sweep(const
                             run_d += pad ? 0.0f : pr * u4[q];
                         } else {
                             float v = (p.tau * pr) * (u4[q] - delta_row);
-                            if (EUCLID) {
-                                v = -v * __builtin_amdgcn_rsqf(tc);  // w / s with s = -dist
-                                if (tc == 0.0f) v = 0.0f;            // s == 0: ATen's subgradient 0 (a NaN stays a NaN)
-                            }
+                            v = euclid_ratio<EUCLID>(v, tc);
                             if (pad) v = 0.0f;
                             acc[r] = v;
                             sum_u += v;

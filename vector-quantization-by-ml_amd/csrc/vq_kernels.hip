@@ -33,7 +33,10 @@
 //   vq_sample.inc        counter-based Gumbel noise (Philox4x32-10) for Gumbel-max code sampling, its test-hook kernel
 //   vq_similarity.inc    the same sweep with the similarity / online-softmax / Gumbel-max sampling epilogues, fused
 //                        cross-entropy backward
-//   vq_finalize_ema.inc  scalar fallback search, finalize-from-keys, loss reduction, EMA codebook update
+//   vq_gumbel.inc        the resident/streamed sweep with its role table, fourteen roles: Gumbel straight-through and reinmax
+//                        backward, codebook diversity loss, orthogonal regularisation loss, the cross-entropy loss's codes
+//                        gradient; the row / index packers and the split reductions
+//   vq_finalize_ema.inc scalar fallback search, finalize-from-keys, loss reduction, EMA codebook update
 //   vq_lfq.inc           lookup-free quantization: sign quantizer, factorised entropy loss forward / backward (stage axis)
 //   vq_rlfq.inc          residual LFQ: every stage's quantize step in one pass (residual in registers), its backward
 //   vq_fsq.inc           finite scalar quantization (FSQ / residual FSQ): every stage of every group in one pass, its
@@ -47,6 +50,9 @@
 //   vq_diversity.inc     codebook diversity loss: the head-ordered sum of the position table (its sweeps are roles of vq_gumbel.inc)
 //   (orthogonal regularisation loss: the kOrth role of vq_gumbel.inc, no file of its own)
 //   this file           host-side dispatch and the C ABI (include/vq_mi355x.h)
+//   vq_sweep_host.inc    the host side of vq_gumbel.inc's roles (included in the C ABI block below, build part 0): one plan and
+//                        workspace description, one codes-resident path, the Gumbel / reinmax / diversity / cross-entropy codes /
+//                        orthogonal entries
 //
 // Reference lines replaced (relative to the reference root): vector_quantization/codebooks.py:386-397,
 // utils/general.py:126-136,159-163, vector_quantize_pytorch.py:261-279,361-364, residual_vq.py:212-243; the decode side
@@ -439,12 +445,11 @@ template <int DP, int METRIC, int ROLE>
 int launch_gumbel_t(const GumbelParams &p, int H, int gz, hipStream_t s) {
     using G = Geo<DP, 4>;
     using GG = GumGeo<DP>;
-    // packed x rows and packed g rows; kDivX: the searched codes and the live codes
-    const bool two_images = ROLE == kGumC || ROLE == kRmCol || ROLE == kRmC || (ROLE == kDivX && p.gimg);
-    // (kDivC: one streamed image and the finalize staging)
-    constexpr bool no_gradient = ROLE == kGumStats || ROLE == kRmStats || ROLE == kRmCol || ROLE == kDivStats || ROLE == kDivAcc || ROLE == kDivDelta;
+    constexpr SweepRole R = sweep_role(ROLE);  // (the table the kernel reads: the LDS below is what ITS switches use)
+    // packed x rows and packed g rows; kDivX: the searched codes and, given at run time, the live codes
+    const bool two_images = R.second_image || (ROLE == kDivX && p.gimg);
     const size_t tile_floats = (size_t)(two_images ? 2 : 1) * 2 * G::BUF_F4 * 4, rows_floats = (size_t)4 * 32 * G::XS;
-    const size_t stage_floats = no_gradient ? 0 : (size_t)4 * (32 * GG::GS + 32);
+    const size_t stage_floats = R.no_contraction ? 0 : (size_t)4 * (32 * GG::GS + 32);  // the finalize staging
     size_t floats = tile_floats > rows_floats ? tile_floats : rows_floats;
     if (stage_floats > floats) floats = stage_floats;
     return launch<vq_gumbel_sweep<DP, METRIC, ROLE>, kBigLds>(dim3((unsigned)((p.NR + 127) / 128), (unsigned)H, (unsigned)gz),
@@ -1203,28 +1208,6 @@ int run_search_keys(const vq_args *a, long long idx_offset, long long *keys, hip
     p.tiles_per_split = kp.tiles_per_split;
     const int cus = device_cus();  // (a keys-mode search is never a whole fused call: wave pairs or one block)
     return launch_search(choose_search(kp.DP, kp.waves, p, a->H, kp.splits, a->metric, cus), kp.DP, p, a->H, kp.splits, a->metric, cus, s);
-}
-
-// vq_gumbel_backward_codes_f32: the rows are streamed as packed images (vq_packed_floats layout) and split over
-// workgroups so that every CU has one (a workgroup owns 128 codes of one head); every split is at least one staged tile
-struct GumbelCodesPlan {
-    long long Mp, img_floats;
-    int ntiles, tiles_per_split, splits;
-};
-GumbelCodesPlan plan_gumbel_codes(int H, long long M, int K, int D) {
-    GumbelCodesPlan pl;
-    const int tile = kTileCodes * sub_tiles(padded_dim(D));
-    pl.Mp = (M + tile - 1) / tile * tile;
-    pl.img_floats = pl.Mp * (padded_dim(D) + 4) + kPackSlack;
-    pl.ntiles = (int)(pl.Mp / tile);
-    const long long blocks = (long long)((K + 127) / 128) * H;
-    long long want = (device_cus() + blocks - 1) / blocks;
-    if (want > 64) want = 64;
-    if (want > pl.ntiles) want = pl.ntiles;
-    if (want < 1) want = 1;
-    pl.tiles_per_split = (int)((pl.ntiles + want - 1) / want);
-    pl.splits = (pl.ntiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
-    return pl;
 }
 
 }  // namespace
@@ -2018,548 +2001,8 @@ int vq_gumbel_noise_f32(const int64_t *seed, int H, int64_t M, int K, float *noi
                                           (const long long *)seed, H, (long long)M, K, noise, (unsigned *)bits);
 }
 
-// ---- Gumbel backward through the similarities: straight-through (kGum*) and reinmax (kRm*) roles of vq_gumbel.inc -------
-int64_t vq_gumbel_row_stride(int64_t M) { return M <= 0 ? 0 : (M + 255) / 256 * 256; }
-
-// Workspace of the codes-resident roles, offsets in 4-byte units (documented in vq_mi355x.h):
-//   [x image H x img_floats][g image H x img_floats]
-//   reinmax only: [ind int32 H x row_stride(M)][col partials splits x H x row_stride(K)][e partials splits x H x row_stride(K)]
-//   [grad_codes partials splits x H x K x D, splits > 1]
-// The cross entropy (vq_ce_backward_codes_f32) has no g image:
-//   [x image H x img_floats][target int32 H x row_stride(M)][lse H x row_stride(M)][grad_codes partials splits x H x K x D, splits > 1]
-struct GumbelWorkspace {
-    GumbelCodesPlan pl;
-    long long gimg_off, ind_off, lse_off, colp_off, ep_off, parts_off, floats;
-};
-static GumbelWorkspace gumbel_workspace(int H, long long M, int K, int D, bool reinmax, bool ce = false) {
-    GumbelWorkspace w;
-    w.pl = plan_gumbel_codes(H, M, K, D);
-    const long long ck = reinmax ? w.pl.splits * (long long)H * vq_gumbel_row_stride(K) : 0;
-    w.gimg_off = (long long)H * w.pl.img_floats;
-    w.ind_off = ce ? w.gimg_off : 2 * w.gimg_off;
-    w.lse_off = w.ind_off + ((reinmax || ce) ? (long long)H * vq_gumbel_row_stride(M) : 0);
-    w.colp_off = w.lse_off + (ce ? (long long)H * vq_gumbel_row_stride(M) : 0);
-    w.ep_off = w.colp_off + ck;
-    w.parts_off = w.ep_off + ck;
-    w.floats = w.parts_off + (w.pl.splits > 1 ? (long long)w.pl.splits * H * K * D : 0);
-    return w;
-}
-static int64_t gumbel_workspace_bytes(int H, int64_t M, int K, int D, bool reinmax, bool ce = false) {
-    if (H <= 0 || M <= 0 || K <= 0 || D <= 0 || D > 256 || M > 0x7FFFFFFFll) return 0;
-    return 4 * gumbel_workspace(H, M, K, D, reinmax, ce).floats;
-}
-int64_t vq_gumbel_workspace_bytes(int H, int64_t M, int K, int D) { return gumbel_workspace_bytes(H, M, K, D, false); }
-int64_t vq_gumbel_reinmax_workspace_bytes(int H, int64_t M, int K, int D) { return gumbel_workspace_bytes(H, M, K, D, true); }
-
-// A family: its workspace regions, and the argument rules on which the two differ (callers may rely on either;
-// tests/test_gumbel_abi_host.py pins both):
-//   tau_finite: tau = +inf is rejected
-//   null_first: a null statistics array is reported with a null g, before tau and D; otherwise with the alignment, after them
-struct GumbelFamily {
-    bool reinmax, tau_finite, null_first;
-    const char *null_msg, *tau_msg, *ws_msg;
-    bool ce;  // the cross entropy's workspace: no g image, the int32 targets and the log-sum-exp behind the x image
-};
-constexpr GumbelFamily kStraightThrough = {false, false, true, "null argument (g / lse2 / delta)", "tau must be positive",
-                                           "workspace too small or misaligned (see vq_gumbel_workspace_bytes)"};
-constexpr GumbelFamily kReinmax = {true, true, false, "g is null", "tau must be positive and finite",
-                                   "workspace too small or misaligned (see vq_gumbel_reinmax_workspace_bytes)"};
-constexpr GumbelFamily kCrossEntropy = {false, false, false, nullptr, nullptr,
-                                        "workspace too small or misaligned (see vq_ce_codes_workspace_bytes)", true};
-
-// what every entry checks and fills; `arrays`: the per-row and per-code arrays the entry uses (non-null, 16-byte aligned)
-static int fill_gumbel_params(GumbelParams &p, const char *who, const GumbelFamily &f, const vq_args *a, const float *g, int64_t g_rs,
-                              int64_t g_hs, float tau, std::initializer_list<const void *> arrays) {
-    memset(&p, 0, sizeof(p));
-    bool null_array = false, misaligned = false;
-    if (a->M > 0) {  // (M == 0: no launch, the per-row arrays are empty)
-        for (const void *q : arrays) {
-            null_array |= !q;
-            misaligned |= !aligned16(q);
-        }
-    }
-    if (!g || (f.null_first && null_array)) return fail(VQ_E_BADARG, who, f.null_msg);
-    if (!(tau > 0.0f) || (f.tau_finite && !(tau < __builtin_inff()))) return fail(VQ_E_BADARG, who, f.tau_msg);
-    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, who, "D > 256 (use row chunks of vq_similarities_f32)");
-    if (null_array || misaligned) return fail(VQ_E_BADARG, who, "a statistics array is null or not 16-byte aligned");
-    p.D = a->D;
-    p.tau = tau;
-    p.st_hs = vq_gumbel_row_stride(a->M);
-    p.ck_hs = vq_gumbel_row_stride(a->K);  // (read by the kRm* roles only)
-    p.g = g; p.g_rs = g_rs; p.g_hs = g_hs;
-    p.vec_g = vec4_ok(g, {a->D, g_rs, g_hs}) ? 1 : 0;
-    return 0;
-}
-
-// kGumStats / kGumX / kRmStats / kRmX: the rows are resident, the packed codebook is streamed
-static int fill_gumbel_rows(GumbelParams &p, const vq_args *a) {
-    AuxParams ap;
-    if (int rc = fill_aux_params(ap, a)) return rc;
-    p.res = a->x; p.res_rs = a->x_rs; p.res_hs = a->x_hs;
-    p.vec_res = ap.vec_x;
-    p.img = ap.packed; p.img_hs = ap.pk_hs; p.img_bytes = ap.pk_bytes;
-    p.NR = a->M; p.NS = a->K;
-    p.ntiles = ap.ntiles;
-    return 0;
-}
-
-// kGumC / kRmCol / kRmC: the codes are resident, the packed rows are streamed -- the plan, the workspace and the images in it
-static int fill_gumbel_codes(GumbelParams &p, const char *who, const GumbelFamily &f, const vq_args *a, void *workspace,
-                             int64_t workspace_bytes, GumbelWorkspace &w) {
-    if (!a->cb) return fail(VQ_E_BADARG, who, "cb is null");
-    if (a->M > 0x7FFFFFFFll) return fail(VQ_E_UNSUPPORTED, who, "too many rows (use row chunks)");
-    w = gumbel_workspace(a->H, a->M, a->K, a->D, f.reinmax, f.ce);
-    if (w.pl.img_floats * 4 >= (1ll << 31)) return fail(VQ_E_UNSUPPORTED, who, "packed row image >= 2 GiB (use row chunks)");
-    if (!workspace || !aligned16(workspace) || workspace_bytes < 4 * w.floats) return fail(VQ_E_BADARG, who, f.ws_msg);
-    float *ws = (float *)workspace;
-    p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
-    p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
-    p.img = ws; p.gimg = f.ce ? nullptr : ws + w.gimg_off;
-    p.img_hs = w.pl.img_floats; p.img_bytes = (unsigned)(w.pl.img_floats * 4);
-    if (f.reinmax || f.ce) p.ind32 = (const int *)(ws + w.ind_off);
-    p.NR = a->K; p.NS = a->M;
-    p.ntiles = w.pl.ntiles;
-    p.tiles_per_split = w.pl.tiles_per_split;
-    return 0;
-}
-
-// the x rows and the g rows into the two images at the head of the workspace (g null: the x image alone)
-static int pack_gumbel_rows(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, const GumbelWorkspace &w, float *ws, hipStream_t s,
-                            const vqi::RowMap &map = vqi::RowMap{}) {
-    return launch<vq_gumbel_pack_rows>(dim3((unsigned)((w.pl.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
-                                       (long long)a->x_rs, (long long)a->x_hs, g, (long long)g_rs, (long long)g_hs, (long long)a->M, w.pl.Mp,
-                                       a->D, padded_dim(a->D), a->metric, ws, ws + w.gimg_off, w.pl.img_floats, map);
-}
-
-// the only padded-dim dispatch of the fourteen roles: the kGum* kernels live in build part 7, the kRm* kernels in part 8, the kDiv* kernels in
-// part 9, kOrth in part 10, kCeC in part 11
-static int launch_gumbel(int role, const GumbelParams &p, const vq_args *a, int gz, hipStream_t s) {
-    const int DP = padded_dim(a->D);
-    return with_padded_dim(DP == 512 ? 0 : DP,
-                           [&](auto dp) {
-                               constexpr int DPC = decltype(dp)::value;
-                               if constexpr (DPC > 256) return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim");
-                               else if (role == kOrth) return vqi::part_orthogonal<DPC>(p, a->H, s);
-                               else if (role == kCeC) return vqi::part_ce_codes<DPC>(p, a->H, gz, a->metric, s);
-                               else if (role >= kDivStats) return vqi::part_diversity<DPC>(role, p, a->H, gz, a->metric, s);
-                               else if (role < kRmStats) return vqi::part_gumbel<DPC>(role, p, a->H, gz, a->metric, s);
-                               else return vqi::part_reinmax<DPC>(role, p, a->H, gz, a->metric, s);
-                           },
-                           [] { return fail(VQ_E_UNSUPPORTED, "vq_gumbel: unsupported padded dim"); });
-}
-
-// grad_codes [H][K][D] of the *_backward_codes entries: all zeros for an empty call ...
-static int clear_grad_codes(const vq_args *a, float *grad_codes, hipStream_t s, const char *what) {
-    const hipError_t e = hipMemsetAsync(grad_codes, 0, (size_t)a->H * a->K * a->D * 4, s);
-    return e == hipSuccess ? 0 : hip_fail(e, what);
-}
-
-// ... else the sweep (kGumC / kRmC / kCeC), straight into grad_codes or into one partial per row split that vq_gumbel_reduce_parts sums
-static int sweep_grad_codes(int role, GumbelParams &p, const vq_args *a, const GumbelWorkspace &w, float *ws, float *grad_codes, hipStream_t s) {
-    const long long n = (long long)a->H * a->K * a->D;
-    float *parts = ws + w.parts_off;
-    p.out = w.pl.splits > 1 ? parts : grad_codes;
-    p.out_rs = a->D; p.out_hs = (long long)a->K * a->D; p.out_zs = n;
-    if (int rc = launch_gumbel(role, p, a, w.pl.splits, s)) return rc;
-    if (w.pl.splits == 1) return 0;
-    return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
-                                          w.pl.splits, grad_codes);
-}
-
-int vq_gumbel_stats_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, float *lse2, float *delta,
-                        void *stream) {
-    int rc = check_common(a);
-    if (rc) return rc;
-    if (a->M == 0) return 0;
-    GumbelParams p;
-    if ((rc = fill_gumbel_params(p, "vq_gumbel_stats", kStraightThrough, a, g, g_rs, g_hs, tau, {lse2, delta}))) return rc;
-    if ((rc = fill_gumbel_rows(p, a))) return rc;
-    p.lse = lse2; p.delta = delta;
-    return launch_gumbel(kGumStats, p, a, 1, (hipStream_t)stream);
-}
-
-int vq_gumbel_backward_x_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2,
-                             const float *delta, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream) {
-    int rc = check_common(a);
-    if (rc) return rc;
-    if (a->M == 0) return 0;
-    if (!grad_x) return fail(VQ_E_BADARG, "vq_gumbel_backward_x: grad_x is null");
-    GumbelParams p;
-    if ((rc = fill_gumbel_params(p, "vq_gumbel_backward_x", kStraightThrough, a, g, g_rs, g_hs, tau, {lse2, delta}))) return rc;
-    if ((rc = fill_gumbel_rows(p, a))) return rc;
-    p.lse = (float *)lse2; p.delta = (float *)delta;
-    p.out = grad_x; p.out_rs = gx_rs; p.out_hs = gx_hs;
-    return launch_gumbel(kGumX, p, a, 1, (hipStream_t)stream);
-}
-
-int vq_gumbel_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2,
-                                 const float *delta, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream) {
-    static const char who[] = "vq_gumbel_backward_codes";
-    int rc = check_common(a);
-    if (rc) return rc;
-    if (!grad_codes || !a->cb) return fail(VQ_E_BADARG, who, "null argument (grad_codes / cb)");
-    hipStream_t s = (hipStream_t)stream;
-    if (a->M == 0) return clear_grad_codes(a, grad_codes, s, "vq_gumbel_backward_codes memset");
-    GumbelParams p;
-    GumbelWorkspace w;
-    if ((rc = fill_gumbel_params(p, who, kStraightThrough, a, g, g_rs, g_hs, tau, {lse2, delta}))) return rc;
-    if ((rc = fill_gumbel_codes(p, who, kStraightThrough, a, workspace, workspace_bytes, w))) return rc;
-    if ((rc = pack_gumbel_rows(a, g, g_rs, g_hs, w, (float *)workspace, s))) return rc;
-    p.lse = (float *)lse2; p.delta = (float *)delta;
-    return sweep_grad_codes(kGumC, p, a, w, (float *)workspace, grad_codes, s);
-}
-
-int vq_gumbel_reinmax_stats_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, float *lse2_tau,
-                                float *lse2_one, float *delta0, void *stream) {
-    int rc = check_common(a);
-    if (rc) return rc;
-    GumbelParams p;
-    if ((rc = fill_gumbel_params(p, "vq_gumbel_reinmax_stats", kReinmax, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0}))) return rc;
-    if (a->M == 0) return 0;
-    if ((rc = fill_gumbel_rows(p, a))) return rc;
-    p.lse = lse2_tau; p.lse1 = lse2_one; p.delta = delta0;
-    return launch_gumbel(kRmStats, p, a, 1, (hipStream_t)stream);
-}
-
-int vq_gumbel_reinmax_columns_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
-                                  const int64_t *ind, int64_t ind_rs, int64_t ind_hs, float *col, float *e, void *workspace,
-                                  int64_t workspace_bytes, void *stream) {
-    static const char who[] = "vq_gumbel_reinmax_columns";
-    int rc = check_common(a);
-    if (rc) return rc;
-    GumbelParams p;
-    GumbelWorkspace w;
-    if ((rc = fill_gumbel_params(p, who, kReinmax, a, g, g_rs, g_hs, tau, {lse2_tau, col, e}))) return rc;
-    if (!ind) return fail(VQ_E_BADARG, who, "ind is null");
-    if (a->M == 0) return 0;
-    if ((rc = fill_gumbel_codes(p, who, kReinmax, a, workspace, workspace_bytes, w))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    float *ws = (float *)workspace;
-    if ((rc = pack_gumbel_rows(a, g, g_rs, g_hs, w, ws, s))) return rc;
-    if ((rc = launch<vq_gumbel_pack_ind>(dim3((unsigned)((p.st_hs + 255) / 256), (unsigned)a->H), dim3(256), 0, s, "vq_gumbel_pack_ind launch",
-                                         (const long long *)ind, (long long)ind_rs, (long long)ind_hs, (long long)a->M, p.st_hs,
-                                         (int *)(ws + w.ind_off), 0, (const float *)nullptr, 0ll, (float *)nullptr)))
-        return rc;
-    p.lse = (float *)lse2_tau;
-    p.colp = ws + w.colp_off; p.ep = ws + w.ep_off;
-    p.cp_zs = (long long)a->H * p.ck_hs;
-    if ((rc = launch_gumbel(kRmCol, p, a, w.pl.splits, s))) return rc;
-    return launch<vq_gumbel_reduce_cols>(dim3((unsigned)((p.cp_zs + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_cols launch",
-                                         (const float *)p.colp, (const float *)p.ep, p.cp_zs, p.ck_hs, a->K, w.pl.splits, col, e);
-}
-
-int vq_gumbel_reinmax_backward_x_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
-                                     const float *lse2_one, const float *delta0, const int64_t *ind, int64_t ind_rs, int64_t ind_hs,
-                                     const float *col, const float *e, float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream) {
-    static const char who[] = "vq_gumbel_reinmax_backward_x";
-    int rc = check_common(a);
-    if (rc) return rc;
-    GumbelParams p;
-    if ((rc = fill_gumbel_params(p, who, kReinmax, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0, col, e}))) return rc;
-    if (!ind || !grad_x) return fail(VQ_E_BADARG, who, "null argument (ind / grad_x)");
-    if (a->M == 0) return 0;
-    if ((rc = fill_gumbel_rows(p, a))) return rc;
-    p.lse = (float *)lse2_tau; p.lse1 = (float *)lse2_one; p.delta = (float *)delta0;
-    p.ind = (const long long *)ind; p.ind_rs = ind_rs; p.ind_hs = ind_hs;
-    p.col = (float *)col; p.e = (float *)e;
-    p.out = grad_x; p.out_rs = gx_rs; p.out_hs = gx_hs;
-    return launch_gumbel(kRmX, p, a, 1, (hipStream_t)stream);
-}
-
-int vq_gumbel_reinmax_backward_codes_f32(const vq_args *a, const float *g, int64_t g_rs, int64_t g_hs, float tau, const float *lse2_tau,
-                                         const float *lse2_one, const float *delta0, const float *col, const float *e,
-                                         float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream) {
-    static const char who[] = "vq_gumbel_reinmax_backward_codes";
-    int rc = check_common(a);
-    if (rc) return rc;
-    GumbelParams p;
-    GumbelWorkspace w;
-    if ((rc = fill_gumbel_params(p, who, kReinmax, a, g, g_rs, g_hs, tau, {lse2_tau, lse2_one, delta0, col, e}))) return rc;
-    if (!grad_codes) return fail(VQ_E_BADARG, who, "grad_codes is null");
-    hipStream_t s = (hipStream_t)stream;
-    if (a->M == 0) return clear_grad_codes(a, grad_codes, s, "vq_gumbel_reinmax_backward_codes memset");
-    if ((rc = fill_gumbel_codes(p, who, kReinmax, a, workspace, workspace_bytes, w))) return rc;
-    p.lse = (float *)lse2_tau; p.lse1 = (float *)lse2_one; p.delta = (float *)delta0;
-    p.col = (float *)col; p.e = (float *)e;
-    return sweep_grad_codes(kRmC, p, a, w, (float *)workspace, grad_codes, s);
-}
-
-// ---- codebook diversity loss: the kDiv* roles of vq_gumbel.inc, vq_diversity.inc ------------------------------------------
-// The position-major row image of the accumulate sweep: every position's Ch = M / N rows of a head padded to spp whole
-// 32-row sub-tiles, the positions split over blockIdx.z so that every CU has a workgroup (a workgroup owns 128 codes of one
-// head).  Workspace, offsets in 4-byte units (documented in vq_mi355x.h):
-//   [x image H x img_floats][lse2 in image order H x Mp][partials of A: H x N x row_stride(K)]
-struct DiversityPlan {
-    long long Ch, Cp, Mp, img_floats, rsK, lse_off, part_off, floats;
-    int spp, ntiles, pps, splits;
-};
-static DiversityPlan plan_diversity(int H, long long M, int K, int D, int N) {
-    DiversityPlan pl;
-    const int DP = padded_dim(D);
-    const int tile = kTileCodes * sub_tiles(DP);
-    pl.Ch = M / N;
-    pl.spp = (int)((pl.Ch + kTileCodes - 1) / kTileCodes);
-    pl.Cp = (long long)pl.spp * kTileCodes;
-    pl.Mp = ((long long)N * pl.Cp + tile - 1) / tile * tile;
-    pl.img_floats = pl.Mp * (DP + 4) + kPackSlack;
-    pl.ntiles = (int)(pl.Mp / tile);
-    pl.rsK = vq_gumbel_row_stride(K);
-    const long long blocks = (long long)((K + 127) / 128) * H;
-    long long want = (device_cus() + blocks - 1) / blocks;
-    if (want > 64) want = 64;
-    if (want > N) want = N;
-    if (want < 1) want = 1;
-    pl.pps = (int)((N + want - 1) / want);
-    pl.splits = (N + pl.pps - 1) / pl.pps;
-    pl.lse_off = (long long)H * pl.img_floats;
-    pl.part_off = pl.lse_off + (long long)H * pl.Mp;
-    pl.floats = pl.part_off + (long long)H * N * pl.rsK;
-    return pl;
-}
-// the sizes every diversity entry checks the same way; `rows`: M must be whole groups of N * pos_div rows
-static bool diversity_shape_ok(int H, int64_t M, int K, int D, int N, int pos_div) {
-    return H > 0 && M >= 0 && K > 0 && D > 0 && N > 0 && pos_div > 0 && M % ((int64_t)N * pos_div) == 0;
-}
-// padded rows of the image < 2^31 and the image < 2 GiB (one buffer descriptor)
-static bool diversity_image_ok(int64_t M, int D, int N) {
-    if (M > 0x7FFFFFFFll) return false;
-    const long long rows = ((M / N + 31) / 32 * 32) * N + 256;
-    return rows <= 0x7FFFFFFFll && (rows * (padded_dim(D) + 4) + kPackSlack) * 4 < (1ll << 31);
-}
-
-int64_t vq_diversity_workspace_bytes(int H, int64_t M, int K, int D, int N) {
-    if (!diversity_shape_ok(H, M, K, D, N, 1) || M == 0 || D > 256 || !diversity_image_ok(M, D, N)) return 0;
-    return 4 * plan_diversity(H, M, K, D, N).floats;
-}
-
-// what the four entries check before any launch and fill: tau = -T
-static int fill_diversity_params(GumbelParams &p, const char *who, const vq_args *a, float T, int N, int pos_div,
-                                 std::initializer_list<const void *> arrays) {
-    memset(&p, 0, sizeof(p));
-    if (!(__builtin_fabsf(T) < __builtin_inff())) return fail(VQ_E_BADARG, who, "T is not finite");
-    if (!diversity_shape_ok(a->H, a->M, a->K, a->D, N, pos_div))
-        return fail(VQ_E_BADARG, who, "N and pos_div must be positive and M a multiple of N * pos_div");
-    for (const void *q : arrays)
-        if (!q || !aligned16(q)) return fail(VQ_E_BADARG, who, "an array argument is null or not 16-byte aligned");
-    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, who, "D > 256 (use row chunks of vq_similarities_f32)");
-    p.D = a->D;
-    p.tau = -T;
-    p.st_hs = vq_gumbel_row_stride(a->M);
-    p.U_rs = vq_gumbel_row_stride(a->K);
-    p.div_N = N;
-    p.div_posdiv = pos_div;
-    return 0;
-}
-
-int vq_diversity_stats_f32(const vq_args *a, float T, float *lse2, void *stream) {
-    int rc = check_common(a);
-    if (rc) return rc;
-    GumbelParams p;
-    if ((rc = fill_diversity_params(p, "vq_diversity_stats", a, T, 1, 1, {lse2}))) return rc;
-    if (a->M == 0) return 0;
-    if ((rc = fill_gumbel_rows(p, a))) return rc;
-    p.lse = lse2;
-    return launch_gumbel(kDivStats, p, a, 1, (hipStream_t)stream);
-}
-
-int vq_diversity_accumulate_f32(const vq_args *a, float T, int N, int pos_div, const float *lse2, float *A, void *workspace,
-                                int64_t workspace_bytes, void *stream) {
-    static const char who[] = "vq_diversity_accumulate";
-    int rc = check_common(a);
-    if (rc) return rc;
-    GumbelParams p;
-    if ((rc = fill_diversity_params(p, who, a, T, N, pos_div, {lse2, A}))) return rc;
-    if (!a->cb) return fail(VQ_E_BADARG, who, "cb is null");
-    if (a->M == 0) return 0;
-    if (!diversity_image_ok(a->M, a->D, N)) return fail(VQ_E_UNSUPPORTED, who, "packed row image >= 2 GiB or too many rows (use row chunks)");
-    const DiversityPlan pl = plan_diversity(a->H, a->M, a->K, a->D, N);
-    if (!workspace || !aligned16(workspace) || workspace_bytes < 4 * pl.floats)
-        return fail(VQ_E_BADARG, who, "workspace too small or misaligned (see vq_diversity_workspace_bytes)");
-    hipStream_t s = (hipStream_t)stream;
-    float *ws = (float *)workspace;
-    vqi::RowMap map{};  // (no second per-row array)
-    map.C = pl.Ch; map.Cp = pl.Cp; map.N = N; map.pos_div = pos_div;
-    map.stat = lse2; map.stat_hs = p.st_hs;
-    map.stat_img = ws + pl.lse_off; map.stat_img_hs = pl.Mp;
-    if ((rc = launch<vq_gumbel_pack_rows>(dim3((unsigned)((pl.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
-                                          (long long)a->x_rs, (long long)a->x_hs, (const float *)nullptr, 0ll, 0ll, (long long)a->M, pl.Mp, a->D,
-                                          padded_dim(a->D), a->metric, ws, (float *)nullptr, pl.img_floats, map)))
-        return rc;
-    p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
-    p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
-    p.img = ws; p.img_hs = pl.img_floats; p.img_bytes = (unsigned)(pl.img_floats * 4);
-    p.NR = a->K; p.NS = (long long)N * pl.Cp;
-    p.ntiles = pl.ntiles;
-    p.lse = ws + pl.lse_off; p.st_hs = pl.Mp;
-    p.div_spp = pl.spp; p.div_ch = (int)pl.Ch; p.div_pps = pl.pps;
-    p.out = ws + pl.part_off; p.out_rs = pl.rsK; p.out_hs = (long long)N * pl.rsK;
-    if ((rc = launch_gumbel(kDivAcc, p, a, pl.splits, s))) return rc;
-    const long long n = (long long)N * pl.rsK;
-    return launch<vq_diversity_reduce_heads>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_diversity_reduce_heads launch",
-                                             (const float *)p.out, n, pl.rsK, a->K, a->H, (float)((double)a->H * (double)pl.Ch), A);
-}
-
-int vq_diversity_delta_f32(const vq_args *a, float T, int N, int pos_div, const float *lse2, const float *U, float *delta,
-                           void *stream) {
-    int rc = check_common(a);
-    if (rc) return rc;
-    GumbelParams p;
-    if ((rc = fill_diversity_params(p, "vq_diversity_delta", a, T, N, pos_div, {lse2, U, delta}))) return rc;
-    if (a->M == 0) return 0;
-    if ((rc = fill_gumbel_rows(p, a))) return rc;
-    p.lse = (float *)lse2; p.delta = delta; p.U = U;
-    return launch_gumbel(kDivDelta, p, a, 1, (hipStream_t)stream);
-}
-
-int vq_diversity_backward_x_f32(const vq_args *a, const float *live_packed, int64_t live_pk_hs, float T, int N, int pos_div,
-                                const float *lse2, const float *delta, const float *U, float *grad_x, int64_t gx_rs, int64_t gx_hs,
-                                void *stream) {
-    int rc = check_common(a);
-    if (rc) return rc;
-    GumbelParams p;
-    if ((rc = fill_diversity_params(p, "vq_diversity_backward_x", a, T, N, pos_div, {lse2, delta, U}))) return rc;
-    if (!grad_x) return fail(VQ_E_BADARG, "vq_diversity_backward_x: grad_x is null");
-    if (a->M == 0) return 0;
-    if ((rc = fill_gumbel_rows(p, a))) return rc;
-    p.lse = (float *)lse2; p.delta = (float *)delta; p.U = U;
-    p.gimg = live_packed; p.gimg_hs = live_pk_hs;
-    p.out = grad_x; p.out_rs = gx_rs; p.out_hs = gx_hs;
-    return launch_gumbel(kDivX, p, a, 1, (hipStream_t)stream);
-}
-
-// The codes sweep (kDivC) over the same position-major image, the staged tiles split over blockIdx.z by kGumC's rule (every CU a
-// workgroup, at most 64 splits, at least one staged tile each).  Workspace, offsets in 4-byte units (documented in vq_mi355x.h):
-//   [x image H x img_floats][lse2 in image order H x Mp][delta in image order H x Mp][partials of gc: splits x H x K x D, splits > 1]
-struct DiversityCodesPlan {
-    DiversityPlan im;
-    long long delta_off, parts_off, floats;
-    int tiles_per_split, splits;
-};
-static DiversityCodesPlan plan_diversity_codes(int H, long long M, int K, int D, int N) {
-    DiversityCodesPlan pl;
-    pl.im = plan_diversity(H, M, K, D, N);
-    const long long blocks = (long long)((K + 127) / 128) * H;
-    long long want = (device_cus() + blocks - 1) / blocks;
-    if (want > 64) want = 64;
-    if (want > pl.im.ntiles) want = pl.im.ntiles;
-    if (want < 1) want = 1;
-    pl.tiles_per_split = (int)((pl.im.ntiles + want - 1) / want);
-    pl.splits = (pl.im.ntiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
-    pl.delta_off = pl.im.lse_off + (long long)H * pl.im.Mp;
-    pl.parts_off = pl.delta_off + (long long)H * pl.im.Mp;
-    pl.floats = pl.parts_off + (pl.splits > 1 ? (long long)pl.splits * H * K * D : 0);
-    return pl;
-}
-
-int64_t vq_diversity_codes_workspace_bytes(int H, int64_t M, int K, int D, int N) {
-    if (!diversity_shape_ok(H, M, K, D, N, 1) || M == 0 || D > 256 || !diversity_image_ok(M, D, N)) return 0;
-    return 4 * plan_diversity_codes(H, M, K, D, N).floats;
-}
-
-int vq_diversity_backward_codes_f32(const vq_args *a, float T, int N, int pos_div, const float *lse2, const float *delta,
-                                    const float *U, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream) {
-    static const char who[] = "vq_diversity_backward_codes";
-    int rc = check_common(a);
-    if (rc) return rc;
-    GumbelParams p;
-    if ((rc = fill_diversity_params(p, who, a, T, N, pos_div, {lse2, delta, U}))) return rc;
-    if (!grad_codes || !a->cb) return fail(VQ_E_BADARG, who, "null argument (grad_codes / cb)");
-    hipStream_t s = (hipStream_t)stream;
-    if (a->M == 0) return clear_grad_codes(a, grad_codes, s, "vq_diversity_backward_codes memset");
-    if (!diversity_image_ok(a->M, a->D, N)) return fail(VQ_E_UNSUPPORTED, who, "packed row image >= 2 GiB or too many rows (use row chunks)");
-    const DiversityCodesPlan pl = plan_diversity_codes(a->H, a->M, a->K, a->D, N);
-    if (!workspace || !aligned16(workspace) || workspace_bytes < 4 * pl.floats)
-        return fail(VQ_E_BADARG, who, "workspace too small or misaligned (see vq_diversity_codes_workspace_bytes)");
-    float *ws = (float *)workspace;
-    // the image is packed again here: keeping the forward's alive until backward would double the activation memory of the rows
-    vqi::RowMap map{};
-    map.C = pl.im.Ch; map.Cp = pl.im.Cp; map.N = N; map.pos_div = pos_div;
-    map.stat = lse2; map.stat_hs = p.st_hs;
-    map.stat_img = ws + pl.im.lse_off; map.stat_img_hs = pl.im.Mp;
-    map.stat2 = delta; map.stat2_img = ws + pl.delta_off;
-    if ((rc = launch<vq_gumbel_pack_rows>(dim3((unsigned)((pl.im.Mp + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_gumbel_pack_rows launch", a->x,
-                                          (long long)a->x_rs, (long long)a->x_hs, (const float *)nullptr, 0ll, 0ll, (long long)a->M, pl.im.Mp,
-                                          a->D, padded_dim(a->D), a->metric, ws, (float *)nullptr, pl.im.img_floats, map)))
-        return rc;
-    p.res = a->cb; p.res_rs = a->D; p.res_hs = a->cb_hs;
-    p.vec_res = vec4_ok(a->cb, {a->D, a->cb_hs}) ? 1 : 0;
-    p.img = ws; p.img_hs = pl.im.img_floats; p.img_bytes = (unsigned)(pl.im.img_floats * 4);
-    p.NR = a->K; p.NS = (long long)N * pl.im.Cp;
-    p.ntiles = pl.im.ntiles;
-    p.tiles_per_split = pl.tiles_per_split;
-    p.lse = ws + pl.im.lse_off; p.delta = ws + pl.delta_off; p.st_hs = pl.im.Mp;
-    p.U = U;
-    p.div_spp = pl.im.spp; p.div_ch = (int)pl.im.Ch;
-    const long long n = (long long)a->H * a->K * a->D;
-    float *parts = ws + pl.parts_off;
-    p.out = pl.splits > 1 ? parts : grad_codes;
-    p.out_rs = a->D; p.out_hs = (long long)a->K * a->D; p.out_zs = n;
-    if ((rc = launch_gumbel(kDivC, p, a, pl.splits, s))) return rc;
-    if (pl.splits == 1) return 0;
-    return launch<vq_gumbel_reduce_parts>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, "vq_gumbel_reduce_parts launch", (const float *)parts, n,
-                                          pl.splits, grad_codes);
-}
-
-// ---- cross-entropy loss, the gradient with respect to a learnable codebook: the kCeC role of vq_gumbel.inc --------------
-int64_t vq_ce_codes_workspace_bytes(int H, int64_t M, int K, int D) { return gumbel_workspace_bytes(H, M, K, D, false, true); }
-
-int vq_ce_backward_codes_f32(const vq_args *a, const float *lse, const int64_t *target, int64_t tgt_rs, int64_t tgt_hs,
-                             const float *coef, float *grad_codes, void *workspace, int64_t workspace_bytes, void *stream) {
-    static const char who[] = "vq_ce_backward_codes";
-    int rc = check_common(a);
-    if (rc) return rc;
-    if (!grad_codes || !a->cb || !coef) return fail(VQ_E_BADARG, who, "null argument (grad_codes / cb / coef)");
-    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, who, "D > 256 (use row chunks of vq_similarities_f32)");
-    hipStream_t s = (hipStream_t)stream;
-    if (a->M == 0) return clear_grad_codes(a, grad_codes, s, "vq_ce_backward_codes memset");
-    if (!lse || !target) return fail(VQ_E_BADARG, who, "null argument (lse / target)");
-    GumbelParams p;
-    GumbelWorkspace w;
-    memset(&p, 0, sizeof(p));
-    p.D = a->D;
-    p.st_hs = vq_gumbel_row_stride(a->M);
-    if ((rc = fill_gumbel_codes(p, who, kCrossEntropy, a, workspace, workspace_bytes, w))) return rc;
-    float *ws = (float *)workspace;
-    // the targets (-1: ignored, compared as 64-bit values) and the log-sum-exp at the sweep's 16-byte aligned head stride ...
-    if ((rc = launch<vq_gumbel_pack_ind>(dim3((unsigned)((p.st_hs + 255) / 256), (unsigned)a->H), dim3(256), 0, s, "vq_gumbel_pack_ind launch",
-                                         (const long long *)target, (long long)tgt_rs, (long long)tgt_hs, (long long)a->M, p.st_hs,
-                                         (int *)(ws + w.ind_off), a->K, lse, (long long)a->M, ws + w.lse_off)))
-        return rc;
-    // ... then the x image, an ignored row as padding
-    vqi::RowMap map{};
-    map.keep = p.ind32; map.keep_hs = p.st_hs;
-    if ((rc = pack_gumbel_rows(a, nullptr, 0, 0, w, ws, s, map))) return rc;
-    p.lse = ws + w.lse_off;
-    p.coef = coef;
-    return sweep_grad_codes(kCeC, p, a, w, ws, grad_codes, s);
-}
-
-// ---- orthogonal regularisation loss: the kOrth role of vq_gumbel.inc ---------------------------------------------------
-// n = a->K rows on both sides: resident from a->x, streamed from a->packed (the dot image of the same rows)
-int vq_orthogonal_gram_f32(const vq_args *a, float *rowsq, float *gram, int64_t g_rs, int64_t g_hs, void *stream) {
-    static const char who[] = "vq_orthogonal_gram";
-    if (!a) return fail(VQ_E_BADARG, who, "args is null");
-    if (a->H <= 0 || a->K <= 0 || a->D <= 0) return fail(VQ_E_BADARG, who, "H, K (the number of rows n) and D must be positive");
-    if (a->metric != VQ_METRIC_DOT) return fail(VQ_E_BADARG, who, "metric must be VQ_METRIC_DOT");
-    if (!a->x) return fail(VQ_E_BADARG, who, "x is null");
-    if (!a->packed) return fail(VQ_E_BADARG, who, "packed is null (the dot image of the rows)");
-    if (!rowsq || !aligned16(rowsq)) return fail(VQ_E_BADARG, who, "rowsq is null or not 16-byte aligned");
-    if (gram && !aligned16(gram)) return fail(VQ_E_BADARG, who, "gram is not 16-byte aligned");
-    if (a->D > 256) return fail(VQ_E_UNSUPPORTED, who, "D > 256");
-    if (vq_packed_floats(a->K, a->D) * 4 >= (1ll << 31)) return fail(VQ_E_UNSUPPORTED, who, "packed image >= 2 GiB");
-    GumbelParams p;
-    memset(&p, 0, sizeof(p));
-    p.D = a->D;
-    p.res = a->x; p.res_rs = a->x_rs; p.res_hs = a->x_hs;
-    p.vec_res = vec4_ok(a->x, {a->D, a->x_rs, a->x_hs}) ? 1 : 0;
-    p.img = a->packed; p.img_hs = a->pk_hs; p.img_bytes = (unsigned)(vq_packed_floats(a->K, a->D) * 4);
-    p.NR = a->K; p.NS = a->K;
-    const int tc = kTileCodes * sub_tiles(padded_dim(a->D));
-    p.ntiles = (a->K + tc - 1) / tc;
-    p.lse = rowsq; p.st_hs = vq_gumbel_row_stride(a->K);
-    p.out = gram; p.out_rs = g_rs; p.out_hs = g_hs;
-    return launch_gumbel(kOrth, p, a, 1, (hipStream_t)stream);
-}
+// ---- the resident/streamed sweep family (Gumbel, reinmax, diversity, cross-entropy codes, orthogonal): its plans, helpers and entries
+#include "vq_sweep_host.inc"
 
 int vq_max_fused_stages(int D, int want_sq_err) {
     // largest Q one residual launch can hold (winner indices and loss partials of every stage live in LDS); 0: no fused residual launch (D > 512)

@@ -248,7 +248,8 @@ def _alloc_workspace(nbytes: int, device):
 
 def _sized_workspace(sizer: str, device, *dims):
     """_alloc_workspace of ``sizer(*dims)`` bytes, for the sizers that answer <= 0 (and set vq_last_error) on a shape they reject."""
-    nbytes = int(getattr(load(), sizer)(*dims))
+    with torch.cuda.device(device):  # (a sizer may plan for the CUs of the current device)
+        nbytes = int(getattr(load(), sizer)(*dims))
     if nbytes <= 0:
         raise RuntimeError(f"{sizer}({', '.join(str(v) for v in dims)}) failed: {load().vq_last_error().decode()}")
     return _alloc_workspace(nbytes, device)
@@ -773,18 +774,14 @@ def ce_backward_codes(x: torch.Tensor, cb: torch.Tensor, lse: torch.Tensor, targ
     coef * d/dcodes sum over the rows with 0 <= target < K of (lse - logit[target]) (``out``: a contiguous destination).
     lse [H, M] from softmax_stats (scale 1), target [H, M] int64 (any strides), coef: 1-element fp32 device tensor.
     No rows: gc is all zeros.  Atomics-free: bit-identical from run to run on one device."""
-    _require_gpu(x, cb, lse, target, coef, out)
-    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous()
-    H, M, D = x.shape
-    K = cb.shape[1]
-    assert cb.shape[0] == H and cb.shape[2] == D and D <= CE_CODES_MAX_DIM
+    _require_gpu(lse, target, coef, out)
+    a = _codes_args(x, cb, None, metric)
+    H, M, K, D = a.H, a.M, a.K, a.D
+    assert D <= CE_CODES_MAX_DIM
     assert lse.dtype == torch.float32 and lse.is_contiguous() and tuple(lse.shape) == (H, M)
     assert target.dtype == torch.int64 and tuple(target.shape) == (H, M)
     assert coef.dtype == torch.float32 and coef.numel() == 1
-    if out is None:
-        out = torch.empty((H, K, D), dtype=torch.float32, device=x.device)
-    assert out.dtype == torch.float32 and tuple(out.shape) == (H, K, D) and out.is_contiguous() and out.device == x.device
-    a = _vq_args(x, cb, metric=metric)
+    out = _grad_codes_out(a, out, x.device)
     tail = (int(target.stride(1)), int(target.stride(0)), coef.data_ptr(), out.data_ptr())
     if M == 0:  # (the per-row arrays are empty and have no address; nothing reads them)
         _call("vq_ce_backward_codes_f32", x.device, a, None, None, *tail, None, 0)
@@ -808,15 +805,6 @@ def _grad_x_out(x, out):
         out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and tuple(out.shape) == tuple(x.shape) and out.device == x.device
     return (out, *_row_strides(out))
-
-
-def _gumbel_workspace(x, K, sizer):
-    """A 16-byte aligned workspace of ``sizer`` (vq_gumbel_workspace_bytes / vq_gumbel_reinmax_workspace_bytes) bytes."""
-    H, M, D = x.shape
-    with torch.cuda.device(x.device):  # (the plan splits the rows over the CUs of the current device)
-        nbytes = int(getattr(load(), sizer)(H, M, K, D))
-    assert nbytes > 0, f"{sizer}: unsupported shape"
-    return _alloc_workspace(nbytes, x.device)[0]
 
 
 def gumbel_stats(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, *, metric: int = EUCLID, tau: float = 1.0,
@@ -856,22 +844,35 @@ def gumbel_backward_codes(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, ls
     term is ema_accumulate of g).  Atomics-free: bit-identical from run to run on one device."""
     a, g_rs, g_hs = _codes_args(x, cb, g, metric)
     _check_stat_arrays(x, a.M, lse2, delta)
-    ws = _gumbel_workspace(x, a.K, "vq_gumbel_workspace_bytes")
-    gc = torch.empty((a.H, a.K, a.D), dtype=torch.float32, device=x.device)
+    ws, ws_bytes = _sized_workspace("vq_gumbel_workspace_bytes", x.device, a.H, a.M, a.K, a.D)
+    gc = _grad_codes_out(a, None, x.device)
     _call("vq_gumbel_backward_codes_f32", x.device, a, g.data_ptr(), g_rs, g_hs, float(tau), lse2.data_ptr(), delta.data_ptr(),
-          gc.data_ptr(), ws.data_ptr(), ws.numel() * 8)
+          gc.data_ptr(), ws.data_ptr(), ws_bytes)
     return gc
 
 
 def _codes_args(x, cb, g, metric):
-    """vq_args of the codes-resident Gumbel sweeps (a->x rows, a->cb the natural codebook) and the strides of g."""
+    """vq_args of the codes-resident sweeps (a->x rows [H, M, D], a->cb the natural codebook [H, K, D]); with the rows g of
+    the Gumbel entries (None: the entry has none), followed by the strides of g."""
     _require_gpu(x, cb, g)
-    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and g.dtype == torch.float32
-    assert x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous() and tuple(g.shape) == tuple(x.shape)
+    assert x.dtype == torch.float32 and cb.dtype == torch.float32
+    assert x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous()
     H, M, D = x.shape
     K = cb.shape[1]
-    assert cb.shape[0] == H and cb.shape[2] == D and gumbel_codes_supported(H, M, K, D)
-    return (_vq_args(x, cb, metric=metric), *_row_strides(g))
+    assert cb.shape[0] == H and cb.shape[2] == D
+    a = _vq_args(x, cb, metric=metric)
+    if g is None:
+        return a
+    assert g.dtype == torch.float32 and tuple(g.shape) == tuple(x.shape) and gumbel_codes_supported(H, M, K, D)
+    return (a, *_row_strides(g))
+
+
+def _grad_codes_out(a, out, device):
+    """The destination of a *_backward_codes sweep ([H, K, D] contiguous; allocated when None)."""
+    if out is None:
+        out = torch.empty((a.H, a.K, a.D), dtype=torch.float32, device=device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (a.H, a.K, a.D) and out.is_contiguous() and out.device == device
+    return out
 
 
 def _check_stat_arrays(x, n, *arrays):
@@ -900,7 +901,8 @@ def gumbel_reinmax_stats(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, *, 
 
 def gumbel_reinmax_workspace(x: torch.Tensor, K: int) -> torch.Tensor:
     """The workspace gumbel_reinmax_columns fills and gumbel_reinmax_backward_codes reuses (vq_gumbel_reinmax_workspace_bytes)."""
-    return _gumbel_workspace(x, K, "vq_gumbel_reinmax_workspace_bytes")
+    H, M, D = x.shape
+    return _sized_workspace("vq_gumbel_reinmax_workspace_bytes", x.device, H, M, K, D)[0]
 
 
 def gumbel_reinmax_columns(x: torch.Tensor, cb: torch.Tensor, g: torch.Tensor, lse2_tau: torch.Tensor, ind: torch.Tensor, *,
@@ -947,7 +949,7 @@ def gumbel_reinmax_backward_codes(x: torch.Tensor, cb: torch.Tensor, g: torch.Te
     _check_stat_arrays(x, a.M, *stats)
     _check_stat_arrays(x, a.K, col, e)
     _require_gpu(workspace)
-    gc = torch.empty((a.H, a.K, a.D), dtype=torch.float32, device=x.device)
+    gc = _grad_codes_out(a, None, x.device)
     _call("vq_gumbel_reinmax_backward_codes_f32", x.device, a, g.data_ptr(), g_rs, g_hs, float(tau), stats[0].data_ptr(),
           stats[1].data_ptr(), stats[2].data_ptr(), col.data_ptr(), e.data_ptr(), gc.data_ptr(), workspace.data_ptr(),
           workspace.numel() * workspace.element_size())
@@ -991,13 +993,11 @@ def diversity_accumulate(x: torch.Tensor, cb: torch.Tensor, lse2: torch.Tensor, 
     """The position table of the diversity loss -> A [n_positions, vq_gumbel_row_stride(K)] (0 past K): A[n, k] = mean over
     the heads and the rows m with (m // pos_div) % n_positions == n of softmax_k(-temperature * sim).  Atomics-free:
     bit-identical from run to run on one device."""
-    _require_gpu(x, cb, lse2)
-    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous()
-    H, M, D = x.shape
-    K = cb.shape[1]
-    assert cb.shape[0] == H and cb.shape[2] == D and diversity_supported(H, M, K, D, n_positions, pos_div)
+    _require_gpu(lse2)
+    a = _codes_args(x, cb, None, metric)
+    H, M, K, D = a.H, a.M, a.K, a.D
+    assert diversity_supported(H, M, K, D, n_positions, pos_div)
     _check_stat_arrays(x, M, lse2)
-    a = _vq_args(x, cb, metric=metric)
     ws, ws_bytes = _sized_workspace("vq_diversity_workspace_bytes", x.device, H, M, K, D, n_positions)
     A = torch.empty((n_positions, int(load().vq_gumbel_row_stride(K))), dtype=torch.float32, device=x.device)
     _call("vq_diversity_accumulate_f32", x.device, a, float(temperature), n_positions, pos_div, lse2.data_ptr(), A.data_ptr(),
@@ -1057,17 +1057,13 @@ def diversity_backward_codes(x: torch.Tensor, cb: torch.Tensor, lse2: torch.Tens
     """d/dcodes of the diversity loss for a learnable codebook, one fused sweep -> gc [H, K, D] (``out``: a contiguous
     destination); lse2, delta and U as for diversity_backward_x (the rows are packed again here, in position-major order).
     No rows: gc is all zeros.  Atomics-free: bit-identical from run to run on one device."""
-    _require_gpu(x, cb, lse2, delta, U, out)
-    assert x.dtype == torch.float32 and cb.dtype == torch.float32 and x.dim() == 3 and cb.dim() == 3 and cb.is_contiguous()
-    H, M, D = x.shape
-    K = cb.shape[1]
-    assert cb.shape[0] == H and cb.shape[2] == D and n_positions > 0 and pos_div > 0 and M % (n_positions * pos_div) == 0
-    if out is None:
-        out = torch.empty((H, K, D), dtype=torch.float32, device=x.device)
-    assert out.dtype == torch.float32 and tuple(out.shape) == (H, K, D) and out.is_contiguous() and out.device == x.device
+    _require_gpu(lse2, delta, U, out)
+    a = _codes_args(x, cb, None, metric)
+    H, M, K, D = a.H, a.M, a.K, a.D
+    assert n_positions > 0 and pos_div > 0 and M % (n_positions * pos_div) == 0
+    out = _grad_codes_out(a, out, x.device)
     _check_stat_arrays(x, M, lse2, delta)
     _check_position_table(U, n_positions, K, x.device)
-    a = _vq_args(x, cb, metric=metric)
     head = (float(temperature), n_positions, pos_div)
     if M == 0:  # (the per-row arrays are empty and have no address: any aligned one stands for them; nothing reads it)
         _call("vq_diversity_backward_codes_f32", x.device, a, *head, U.data_ptr(), U.data_ptr(), U.data_ptr(), out.data_ptr(), None, 0)
