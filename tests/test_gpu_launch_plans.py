@@ -1,4 +1,4 @@
-"""GPU: the launch plans for row counts that do not fill whole rounds of workgroups (csrc/vq_kernels.hip plan_k_split /
+"""GPU: the launch plans for row counts that do not fill whole rounds of workgroups (csrc/vq_search_plan.h plan_k_split /
 plan_main_tail): K split over several workgroups per row block, or whole rounds fused + the remainder as its own K-split call.
 Results must not depend on the plan: indices, winning distances and outputs equal the one-thread-per-row kernel on every row,
 the squared-error sum (one sum over both parts of a two-call plan) agrees to 1e-6, eval and training outputs alike."""
@@ -16,12 +16,12 @@ CASES = [
     (1, 70000, 1024, 256, 0),      # 274 row blocks: 256 fused + 18 as a K-split tail
     (1, 131073, 1024, 256, 0),     # 513 row blocks, the last one holds ONE row
     (1, 66000, 8192, 256, 0),      # 258 row blocks, long sweep
-    (1, 40000, 4096, 256, 1),      # 157 row blocks (< one round): K split 3 ways
+    (1, 40000, 4096, 256, 1),      # 157 row blocks (< one round): K split 8 ways
     (1, 40000, 4096, 512, 0),      # wave-pair kernel in keys mode
     (1, 70000, 8192, 64, 0),       # Dp = 64
     (1, 200000, 1024, 64, 1),
     (1, 150000, 4096, 128, 0),
-    (8, 10000, 8192, 64, 0),       # several heads: 320 workgroups = 256 fused (32 row blocks of every head) + a tail
+    (8, 10000, 8192, 64, 0),       # several heads: 320 workgroups, K split 4 ways (the whole-rounds + tail plan is within 5 % of it)
     (4, 20000, 2048, 256, 1),
     (6, 9000, 1024, 512, 0),       # heads that do not divide the CU count
 ]

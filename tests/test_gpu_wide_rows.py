@@ -2,7 +2,7 @@
 
 Such rows are swept in 512-dim slices whose distance chains wait in the workspace between two launches
 (vq_search_pair512<metric, false, 0, WIDE> -- vq_search_mfma<.., WIDE> for short sweeps and for the last, narrower slice --
-csrc/vq_kernels.hip run_wide); the chain of a (row, code)
+csrc/vq_search_host.inc run_wide); the chain of a (row, code)
 pair is still the oracle's k-ordered fmaf chain, so indices AND winning distances must be bit-identical to the CPU oracle.
 Covered: D just above 512 / not a multiple of 4 / several slices, K below one sub-tile and across two code chunks
 (4096 codes each), split-K launches (few row blocks) and unsplit ones (many), several row chunks (heads shrink the chunk),

@@ -1,8 +1,7 @@
 // vq_common.inc -- constants, error strings, the kernel-launch helper, metric / padded-dim dispatch, packed (value, index) keys.
 // Included by vq_kernels.hip inside its anonymous namespace (single translation unit).
 
-constexpr int kTileCodes = 32;
-constexpr int kPackSlack = 2048;  // floats of over-copy slack behind every packed image
+// (kTileCodes, kPackSlack, padded_dim, round_up, sub_tiles: vq_search_plan.h, shared with the launch plans)
 constexpr int kModeFused = 0;
 constexpr int kModeKeys = 1;      // packed keys, atomic MIN into ONE plane (the caller initialised it)
 constexpr int kModeKeyParts = 2;  // packed keys, plain stores: K split z writes plane z (no init, no atomics)
@@ -75,21 +74,6 @@ int with_padded_dim(int DP, F f, U on_unsupported) {
     }
     return on_unsupported();
 }
-
-inline int padded_dim(int D) {
-    if (D <= 32) return 32;
-    if (D <= 64) return 64;
-    if (D <= 128) return 128;
-    if (D <= 256) return 256;
-    if (D <= 512) return 512;
-    return 0;
-}
-
-inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
-
-// A staged LDS tile always carries ~33 KB: 32 codes at Dp >= 256, 64 / 128 / 256 codes at Dp = 128 / 64 / 32, so
-// the per-tile barrier and LDS-DMA issue are amortised over the same number of MFMAs at every dim.
-constexpr int sub_tiles(int DP) { return DP >= 256 ? 1 : 256 / DP; }
 
 // ------------------------------------------------------------------------------------------------
 // packed (value, index) keys: signed 64-bit, MIN wins, lowest index on equal values

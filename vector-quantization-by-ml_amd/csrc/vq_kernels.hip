@@ -49,7 +49,13 @@
 //   vq_lfq_decode.inc    the same for the lookup-free family: codes from the index bits, no table (vq_lfq_decode_f32)
 //   vq_diversity.inc     codebook diversity loss: the head-ordered sum of the position table (its sweeps are roles of vq_gumbel.inc)
 //   (orthogonal regularisation loss: the kOrth role of vq_gumbel.inc, no file of its own)
-//   this file           host-side dispatch and the C ABI (include/vq_mi355x.h)
+//   this file           the build parts, the templated launchers, the C ABI (include/vq_mi355x.h) of everything but the search
+//   vq_search_plan.h     how a search is launched, as pure arithmetic on values (device, environment switches, call): the geometry
+//                        shared with the kernels and the sizers, choose_search, plan_k_split / plan_main_tail / plan_residual_tail /
+//                        plan_keys / the wide-row plans, and plan_call -> a CallPlan of at most two legs.  Plain C++17, included
+//                        first (namespace vqi); tests/cabi/search_plan.cpp runs it alone on the CPU
+//   vq_search_host.inc   the search's host side (included below, build part 0): the readers of the device, the environment and the
+//                        call, the executor that walks a plan's legs, the search's C ABI
 //   vq_sweep_host.inc    the host side of vq_gumbel.inc's roles (included in the C ABI block below, build part 0): one plan and
 //                        workspace description, one codes-resident path, the Gumbel / reinmax / diversity / cross-entropy codes /
 //                        orthogonal entries
@@ -69,12 +75,13 @@
 #include <type_traits>
 
 #include "../../include/vq_mi355x.h"
+#include "vq_search_plan.h"
 
 // Build parts.  `hipcc ... vq_kernels.hip` (VQ_PART undefined) builds everything as ONE translation unit.  build.sh compiles
 // the same file once per part (-DVQ_PART=n, in parallel) and links the objects: every part sees the same templates, but only
 // its own launchers are defined -- and with them instantiated -- there; the other parts call them through the
 // vqi::part_* entry points declared below.
-//   0 C ABI, planners, small kernels (pack, scalar search, finalize, EMA, expiry, LFQ, FSQ, LQ, affine, decodes) 4 search Dp = 512 + wave-pair kernel
+//   0 C ABI, plan executor, small kernels (pack, scalar search, finalize, EMA, expiry, LFQ, FSQ, LQ, affine, decodes) 4 search Dp = 512 + wave-pair kernel
 //   1 search Dp = 32 / 64         2 search Dp = 128                             5 similarity / softmax-statistics sweeps
 //   3 search Dp = 256 + persistent kernel + full slices of wide rows            6 fused cross-entropy backward (+ live codes)
 //   7 Gumbel straight-through backward sweeps               8 Gumbel-max sampling sweeps + Gumbel reinmax backward sweeps
@@ -90,6 +97,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
+using namespace vqi;  // (vq_search_plan.h: the geometry the kernels share with the plans)
 
 #include "vq_common.inc"
 #if VQ_OWN(0)
@@ -119,143 +127,7 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-struct DevInfo {
-    int cus = 0;
-    int clock_mhz = 2400;  // shader clock (hipDeviceProp_t::clockRate), what the launch plans price a sub-tile with
-    bool ok = false;
-    char name[128] = "";
-};
-
-const DevInfo &dev_info() {
-    static thread_local DevInfo info;
-    static thread_local int cached_dev = -1;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        info.ok = false;
-        return info;
-    }
-    if (dev != cached_dev) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) {
-            info.cus = prop.multiProcessorCount;
-            if (prop.clockRate > 0) info.clock_mhz = prop.clockRate / 1000;
-            snprintf(info.name, sizeof(info.name), "%s", prop.gcnArchName);
-            info.ok = true;
-            cached_dev = dev;
-        } else {
-            info.ok = false;
-        }
-    }
-    return info;
-}
-
-inline int device_cus() {  // compute units of the current device; 256 when the device cannot be asked
-    const DevInfo &di = dev_info();
-    return di.ok && di.cus > 0 ? di.cus : 256;
-}
-
-// ---- which kernel runs a search launch ---------------------------------------------------------------------------------
-// Decided ONCE per launch (choose_search) and handed to everything that depends on it: the set-up of the screened sweep's
-// images, launch_search, and the reduction of the loss partials that the chosen kernel writes.  (The build parts pass the
-// choice to each other, so its type lives in the named namespace.)
-}  // namespace
-namespace vqi {
-enum SearchKind {
-    kResident,  // small codebook resident in LDS (vq_search_resident.inc)
-    kPersist,   // persistent workgroups at Dp = 256 (vq_search_persist.inc)
-    kPair,      // dims split over wave pairs at Dp = 512 (vq_search_pair.inc)
-    kOneBlock,  // one row block per workgroup (vq_search.inc)
-};
-struct SearchChoice {
-    SearchKind kind;
-    int waves;      // waves per workgroup of the chosen kernel
-    bool train;     // kPersist: the deferred copy does the straight-through / squared-error arithmetic
-    bool screened;  // kPersist: the fp16 screened sweep + the second pass over its listed rows
-    bool cached;    // screened: the images and the control block are the caller's (vq_args.screen), no pack kernel runs
-};
-}  // namespace vqi
-namespace {
-using vqi::SearchChoice, vqi::SearchKind, vqi::kResident, vqi::kPersist, vqi::kPair, vqi::kOneBlock;
-
-// workgroups per head (grid.x) of each kernel kind
-inline long long one_block_grid_x(long long M, int waves) { return (M + 32ll * waves - 1) / (32ll * waves); }
-inline long long pair_grid_x(long long M) { return (M + 127) / 128; }  // 8 waves = 4 pairs = 128 rows per workgroup
-inline long long persist_grid_x(long long M, int H, int cus) {  // one 8-wave workgroup per CU, the CUs shared by the heads
-    const long long nblk = (M + 255) / 256;
-    long long gx = cus / H;
-    if (gx < 1) gx = 1;
-    return gx > nblk ? nblk : gx;
-}
-// loss partials per head and stage that the chosen kernel writes: one per wave of every workgroup of the grids above
-// (the resident kernel carries no loss)
-inline long long loss_partials_per_head(const SearchChoice &c, long long M, int H, int cus) {
-    const long long gx = c.kind == kPersist ? persist_grid_x(M, H, cus) : c.kind == kPair ? pair_grid_x(M) : one_block_grid_x(M, c.waves);
-    return gx * c.waves;
-}
-
-// VQ_SINGLE_WAVE_512=1 in the environment selects the one-wave-per-row-block kernel for D > 256 (A/B measurements)
-bool use_pair512() {
-    static const bool off = getenv("VQ_SINGLE_WAVE_512") != nullptr;
-    return !off;
-}
-
-// the screened sweep's share of the workspace: [fp16 screen images][control block, kScrCtrlBytes][rows for the second pass: one uint32 per
-// row of the call, the full-search list from the front and the rescore list from the back].  A caller-cached screen image
-// (vq_args.screen, vq_screen_image_bytes) is the first two; the row list, which needs no initialisation, stays in the workspace.
-inline long long screen_list_bytes(int H, long long M) { return 4ll * H * M; }
-inline long long screen_image_bytes(int H, int ntiles) { return (long long)H * scr_image_bytes(ntiles) + kScrCtrlBytes; }
-inline long long screen_bytes(int H, long long M, int ntiles) { return screen_image_bytes(H, ntiles) + screen_list_bytes(H, M); }
-// sub-tiles per sweep for which the screened (and the persistent) kernel exists: one row per sub-tile needs 32; beyond ~100 the
-// finalize is < 1 % of a block
-constexpr int kPersistMinSub = 32, kPersistMaxSub = 96;
-
-// In order of precedence.  `waves` is the one-block kernel's workgroup size (the caller's plan); `scr_room` the bytes of
-// workspace the screened sweep may use (0: none), `scr_cached` whether the caller brought the images (then only the row list
-// has to fit the room).  Only a whole fused call (no K split, kModeFused) can be taken by the
-// resident or the persistent kernel: keys-mode searches and the slices of wide rows get wave pairs or one block.
-SearchChoice choose_search(int DP, int waves, const SearchParams &p, int H, int splits, int metric, int cus, long long scr_room = 0,
-                           bool scr_cached = false) {
-    SearchChoice c = {kOneBlock, waves, false, false, false};
-    const bool whole_call = splits == 1 && p.mode == kModeFused;
-    // Small codebook whose image fits the LDS beside the row slabs (resident_image_for set p.res_img_floats)
-    if (whole_call && p.res_img_floats > 0 && (DP == 32 || DP == 64 || DP == 128)) {
-        c.kind = kResident;
-        c.waves = 8;
-        return c;
-    }
-    // Plain call at Dp = 256 (one stage, aligned fp32 rows, >= 32 sub-tiles per sweep, several row blocks per CU): persistent
-    // workgroups that copy block b's winners during block b + 1's sweep.  VQ_NO_PERSIST=1 in the environment keeps the
-    // one-block-per-workgroup kernel (A/B measurements); VQ_NO_PERSIST_TRAIN=1 does so for training-mode calls (A/B and
-    // tests; read per call).
-    static const bool no_persist = getenv("VQ_NO_PERSIST") != nullptr;
-    const bool train = p.ste || p.loss_part;
-    const int nsub = p.ntiles * sub_tiles(DP);
-    if (whole_call && !no_persist && DP == 256 && waves == 8 && p.Q == 1 && !p.lse && !p.xt && p.vec_x && p.vec_fin && p.D % 4 == 0 &&
-        (p.out || p.loss_part) &&                                // (else nothing to copy)
-        !(train && getenv("VQ_NO_PERSIST_TRAIN") != nullptr) &&
-        nsub >= kPersistMinSub && nsub <= kPersistMaxSub &&
-        one_block_grid_x(p.M, waves) * H >= 2ll * cus) {         // at least two blocks per resident workgroup
-        c.kind = kPersist;
-        c.train = train;
-        // The screened sweep (vq_search_persist.inc, SCREEN): Euclid, inference, no winning distances requested, and its
-        // images and row list fit the room.  VQ_NO_SCREEN in the environment keeps the fp32 sweep (read per call: tests
-        // compare both in one process).
-        c.screened = !train && metric == VQ_METRIC_EUCLID && !p.best && getenv("VQ_NO_SCREEN") == nullptr &&
-                     (scr_cached ? screen_list_bytes(H, p.M) : screen_bytes(H, p.M, p.ntiles)) <= scr_room &&
-                     scr_image_bytes(p.ntiles) < (1ll << 31) && (long long)H * p.M < (1ll << 31);
-        c.cached = c.screened && scr_cached;
-        return c;
-    }
-    // The wave-pair kernel runs wave B one tile behind wave A: one extra step per sweep.  Worth it from 8 tiles per sweep on.
-    // Residual stacks as long as the winners of every stage fit its LDS (Q <= 26); VQ_PAIR_NO_MULTI=1: one-wave kernel (A/B;
-    // read per call: tests compare both kernels in one process).
-    if (DP == 512 && p.tiles_per_split >= 8 && use_pair512() &&
-        (p.Q == 1 || (getenv("VQ_PAIR_NO_MULTI") == nullptr && p.Q <= PairGeo::max_stages()))) {
-        c.kind = kPair;
-        c.waves = 8;
-    }
-    return c;
-}
+// (the launch plans: vq_search_plan.h; the executor that walks them and the search's C ABI: vq_search_host.inc)
 
 template <int DP, int WAVES, int METRIC, int MULTI, bool LSE = false, int XT = 0, int WIDE = 0>
 int launch_search_t(const SearchParams &p, int H, int splits, hipStream_t s) {
@@ -327,7 +199,7 @@ int launch_pack_scr(const float *packed, long long pk_hs, int K, int ntiles, int
 }
 
 template <int METRIC, bool TRAIN = false, bool SCREEN = false>
-int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s, bool scr_cached = false) {
+int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s, bool scr_cached = false, bool resolve_split = true) {
     using G = Geo<256, 8>;
     const size_t lds = (size_t)G::MAIN_FLOATS_S * 4 + 2 * 8 * 32 * 4;
     if constexpr (SCREEN) {  // this call's images, unless the caller brought them (then the control block is clean: see the second pass)
@@ -341,9 +213,8 @@ int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s, bool 
         // second pass: the rows of both lists, in stream order behind the sweep.  One workgroup per CU: the few full searches
         // of a usual call (tens) are split over several workgroups each, the other workgroups share the rescore batches, and
         // every workgroup stays for the exit ticket that leaves the control block clean (vq_resolve_rows_kernel).
-        // VQ_RESOLVE_NO_SPLIT in the environment: no split of the full searches (A/B measurements and tests; read per call like
-        // VQ_NO_STAGGER)
-        const int flags = getenv("VQ_RESOLVE_NO_SPLIT") ? kResolveNoSplit : 0;
+        // `resolve_split` false (Switches::resolve_no_split): no split of the full searches
+        const int flags = resolve_split ? 0 : kResolveNoSplit;
         return launch<vq_resolve_rows_kernel<256>, kBigLds>(dim3((unsigned)(cus > 0 ? cus : 1)), dim3(kResolveWaves * 64), resolve_lds_bytes<256>(), s,
                                                             "vq_resolve_rows launch", p, H, flags);
     }
@@ -353,7 +224,7 @@ int launch_persist_t(const SearchParams &p, int H, int cus, hipStream_t s, bool 
 // small codebooks: the image stays in LDS, one 8-wave workgroup per CU, waves walk 32-row blocks (vq_search_resident.inc)
 template <int DP, int METRIC>
 int launch_resident_t(const SearchParams &p, int H, int cus, hipStream_t s) {
-    const size_t lds = ResGeo<DP>::lds_bytes(p.res_img_floats, p.res_nbuf);
+    const size_t lds = resident_lds_bytes(p.res_img_floats, p.res_nbuf);
     const long long nwb = (p.M + 31) / 32;
     long long gx = cus / H;
     if (gx < 1) gx = 1;
@@ -503,21 +374,6 @@ int launch_orthogonal_m(const GumbelParams &p, int H, hipStream_t s) {
     return launch_gumbel_t<DP, VQ_METRIC_DOT, kOrth>(p, H, 1, s);
 }
 
-#ifndef VQ_EXP_RESIDENT_MIN_ROWS_PER_CU
-#define VQ_EXP_RESIDENT_MIN_ROWS_PER_CU 512  // rows per CU from which the resident-codebook kernel takes a small codebook
-#endif
-#ifndef VQ_EXP_WIDE_SLICE
-#define VQ_EXP_WIDE_SLICE 512  // dims per slice of rows wider than 512 dims (256: the round-2 scheme, twice the accumulator traffic)
-#endif
-constexpr int kWideSlice = VQ_EXP_WIDE_SLICE;                // dims per slice: 512 (4-wave workgroups) or 256 (8-wave)
-constexpr int kWideWaves = kWideSlice == 512 ? 4 : 8;
-constexpr int kWideRows = 32 * kWideWaves;                   // rows per workgroup
-#ifndef VQ_EXP_WIDE_CHUNK_MB
-#define VQ_EXP_WIDE_CHUNK_MB 512
-#endif
-constexpr long long kWideChunkBytes = (long long)VQ_EXP_WIDE_CHUNK_MB << 20;  // accumulator workspace per (row chunk, code chunk)
-constexpr int kWideCodes = 4096;                    // codes per chunk
-
 // one slice of rows wider than 512 dims: WIDE = 1 a full slice (Dp = the slice width only), 2 / 3 the last slice
 template <int DP>
 int launch_wide_any(int wide, const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
@@ -539,7 +395,7 @@ int launch_wide_any(int wide, const SearchParams &p, int H, int splits, int metr
 // ------------------------------------------------------------------------------------------------
 namespace vqi {
 template <int DP> int part_search(int waves, const SearchParams &p, int H, int splits, int metric, hipStream_t s);
-template <int DP> int part_wide(int wide, const SearchParams &p, int H, int splits, int metric, hipStream_t s);
+template <int DP> int part_wide(int wide, bool pairs, const SearchParams &p, int H, int splits, int metric, hipStream_t s);
 template <int DP> int part_resident(const SearchParams &p, int H, int cus, int metric, hipStream_t s);
 template <int DP> int part_aux(const AuxParams &p, int H, int metric, int mode, hipStream_t s);
 template <int DP> int part_ce_bwd(const CeBwdParams &p, int H, int metric, hipStream_t s);
@@ -570,7 +426,7 @@ int part_persist(const SearchChoice &c, const SearchParams &p, int H, int cus, i
 int part_pack_scr(const float *packed, long long pk_hs, int K, int ntiles, int H, char *img, long long img_hs, unsigned *ctrl, hipStream_t s);
 #define VQ_DECLARE_PARTS(DP)                                                                                         \
     template <> int part_search<DP>(int waves, const SearchParams &p, int H, int splits, int metric, hipStream_t s); \
-    template <> int part_wide<DP>(int wide, const SearchParams &p, int H, int splits, int metric, hipStream_t s);    \
+    template <> int part_wide<DP>(int wide, bool pairs, const SearchParams &p, int H, int splits, int metric, hipStream_t s); \
     template <> int part_aux<DP>(const AuxParams &p, int H, int metric, int mode, hipStream_t s);                    \
     template <> int part_ce_bwd<DP>(const CeBwdParams &p, int H, int metric, hipStream_t s);                          \
     template <> int part_sample<DP>(const AuxParams &p, int H, int metric, hipStream_t s);
@@ -588,7 +444,7 @@ VQ_DECLARE_PARTS(512)
     template <> int part_search<DP>(int waves, const SearchParams &p, int H, int splits, int metric, hipStream_t s) { \
         return waves == 8 ? launch_search_m<DP, 8>(p, H, splits, metric, s) : launch_search_m<DP, W4>(p, H, splits, metric, s); \
     }                                                                                                                 \
-    template <> int part_wide<DP>(int wide, const SearchParams &p, int H, int splits, int metric, hipStream_t s) {    \
+    template <> int part_wide<DP>(int wide, bool, const SearchParams &p, int H, int splits, int metric, hipStream_t s) { \
         return launch_wide_any<DP>(wide, p, H, splits, metric, s);                                                    \
     }
 #define VQ_DEFINE_RESIDENT_PART(DP) \
@@ -607,7 +463,7 @@ VQ_DEFINE_RESIDENT_PART(128)
 #if VQ_OWN(3)
 VQ_DEFINE_SEARCH_PART(256, 4)
 int part_persist(const SearchChoice &c, const SearchParams &p, int H, int cus, int metric, hipStream_t s) {
-    if (c.screened) return launch_persist_t<VQ_METRIC_EUCLID, false, true>(p, H, cus, s, c.cached);  // (choose_search: Euclid inference calls)
+    if (c.screened) return launch_persist_t<VQ_METRIC_EUCLID, false, true>(p, H, cus, s, c.cached, c.resolve_split);  // (choose_search: Euclid inference calls)
     return with_metric(metric, [&](auto m) {
         constexpr int ME = decltype(m)::value;
         return c.train ? launch_persist_t<ME, true>(p, H, cus, s) : launch_persist_t<ME>(p, H, cus, s);
@@ -621,12 +477,11 @@ int part_pack_scr(const float *packed, long long pk_hs, int K, int ntiles, int H
 template <> int part_search<512>(int, const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
     return launch_search_m<512, 4>(p, H, splits, metric, s);
 }
-template <> int part_wide<512>(int wide, const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
+template <> int part_wide<512>(int wide, bool pairs, const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
 #if VQ_EXP_WIDE_SLICE == 512
     // a 512-dim slice of wider rows: the wave-pair kernel (two waves per SIMD, accumulator hand-off) when the sweep is long
-    // enough for its extra pipeline step, else the one-wave kernel
-    // (a slice is one stage at Dp = 512, so the choice is wave pairs or one block whatever the device: no CU count needed)
-    if (choose_search(512, kWideWaves, p, H, splits, metric, 0).kind == kPair)
+    // enough for its extra pipeline step (`pairs`: pairs_worth_it), else the one-wave kernel
+    if (pairs)
         return with_metric(metric, [&](auto m) {
             constexpr int ME = decltype(m)::value;
             if (wide == 1) return launch_pair_t<ME, false, 0, 1>(p, H, splits, s);
@@ -635,7 +490,7 @@ template <> int part_wide<512>(int wide, const SearchParams &p, int H, int split
         });
     return launch_wide_any<512>(wide, p, H, splits, metric, s);
 #else
-    (void)wide; (void)p; (void)H; (void)splits; (void)metric; (void)s;
+    (void)wide; (void)pairs; (void)p; (void)H; (void)splits; (void)metric; (void)s;
     return fail(VQ_E_UNSUPPORTED, "vq_search: unsupported padded dim");
 #endif
 }
@@ -740,76 +595,9 @@ bool vec4_ok(const void *p, std::initializer_list<long long> strides, unsigned a
     return ((uintptr_t)p & (align - 1)) == 0;
 }
 
-// The screened sweep's fp16 images are built per call into the key area of the workspace, which a fused call does not use,
-// and behind them the control block and the two lists of rows for the second pass (vq_resolve_rows_kernel): the layout of
-// screen_bytes.  With the caller's image (`cached`: vq_args.screen, checked by check_screen) only the lists are in the workspace.
-void set_screen_image(SearchParams &p, const vq_args *a, bool cached) {
-    const long long img = scr_image_bytes(p.ntiles);
-    char *base = (char *)(cached ? a->screen : a->workspace);
-    p.scr = (const float *)base;
-    p.scr_hs = img;
-    p.scr_bytes = (unsigned)img;
-    p.scr_count = (unsigned *)(base + (long long)a->H * img);
-    p.scr_list = cached ? (unsigned *)a->workspace : p.scr_count + kScrCtrlBytes / 4;
-    // VQ_NO_STAGGER in the environment: all eight waves run the sweep's epilogue at the same place (A/B measurements and
-    // tests; read per call like VQ_NO_SCREEN)
-    p.scr_stagger = getenv("VQ_NO_STAGGER") == nullptr;
-}
-
-// Small codebook, plain inference call (one stage, no straight-through / loss / LSE, aligned fp32 rows of D % 16 == 0 dims,
-// Dp <= 128) whose image fits the LDS beside the row slabs, and enough rows to give every wave slot of the chip a few 32-row
-// blocks: the resident-codebook kernel.  VQ_NO_RESIDENT=1 in the environment keeps the tile-streaming kernels (A/B measurements).
-int resident_image_for(const vq_args *a, int DP, bool lse, int cus) {
-    static const bool off = getenv("VQ_NO_RESIDENT") != nullptr;
-    if (off || DP == 0 || DP > 128 || a->Q != 1 || lse || a->sq_err || !a->out || !a->idx || !a->cb || !a->packed) return 0;
-    if (a->flags & (VQ_F_STE | VQ_F_FORCE_SIMPLE | VQ_F_FORCE_SPLIT | VQ_F_X_F16 | VQ_F_X_BF16)) return 0;
-    if (a->D % 16 || !vec4_ok(a->x, {a->x_rs, a->x_hs})) return 0;
-    if (!vec4_ok(a->out, {a->out_rs, a->out_hs}) || !vec4_ok(a->cb, {a->cb_hs})) return 0;
-    const int nsub_k = (a->K + kTileCodes - 1) / kTileCodes;
-    if (nsub_k < DP / 16) return 0;  // (the sweep's first Dp / 16 sub-tiles carry the next block's slabs)
-    if (nsub_k > 8) return 0;        // measured (gpurun_out/r3/t5_res_ab.log): from K = 512 on the tile-streaming kernels are ahead again
-    const int img = resident_image_floats(a->K, DP);
-    const size_t lds = ((size_t)img + 8 * 512) * 4 + 2 * 8 * 32 * 4;
-    if (lds > 160 * 1024) return 0;
-    if ((long long)a->H * a->M < (long long)VQ_EXP_RESIDENT_MIN_ROWS_PER_CU * cus) return 0;
-    return img;
-}
-
-// launches the kernel that choose_search picked for (DP, p, H, splits)
-int launch_search(const SearchChoice &c, int DP, const SearchParams &p, int H, int splits, int metric, int cus, hipStream_t s) {
-    switch (c.kind) {
-        case kResident:  // (resident images exist for Dp <= 128 only)
-            if (DP == 32) return vqi::part_resident<32>(p, H, cus, metric, s);
-            if (DP == 64) return vqi::part_resident<64>(p, H, cus, metric, s);
-            if (DP == 128) return vqi::part_resident<128>(p, H, cus, metric, s);
-            break;
-        case kPersist: return vqi::part_persist(c, p, H, cus, metric, s);
-        case kPair: return vqi::part_pair(p, H, splits, metric, s);
-        case kOneBlock:
-            return with_padded_dim(DP, [&](auto dp) { return vqi::part_search<decltype(dp)::value>(c.waves, p, H, splits, metric, s); },
-                                   [] { return fail(VQ_E_UNSUPPORTED, "vq_search: unsupported padded dim"); });
-    }
-    return fail(VQ_E_UNSUPPORTED, "vq_search: unsupported padded dim");
-}
-
 int launch_aux(int DP, const AuxParams &p, int H, int metric, int mode, hipStream_t s) {
     return with_padded_dim(DP, [&](auto dp) { return vqi::part_aux<decltype(dp)::value>(p, H, metric, mode, s); },
                            [] { return fail(VQ_E_UNSUPPORTED, "vq_sweep_aux: unsupported padded dim"); });
-}
-
-// one slice of a wide-row sweep, by the padded width of the slice
-int launch_wide(int wide, int DP, const SearchParams &p, int H, int splits, int metric, hipStream_t s) {
-    return with_padded_dim(DP, [&](auto dp) { return vqi::part_wide<decltype(dp)::value>(wide, p, H, splits, metric, s); },
-                           [] { return fail(VQ_E_UNSUPPORTED, "vq_search: unsupported padded dim"); });
-}
-
-// a caller-cached screen image must be THE image of this call's codebooks' shape: anything else is an argument error
-int check_screen(const vq_args *a) {
-    if (!a->screen && a->screen_bytes == 0) return 0;
-    if (!a->screen || a->screen_bytes <= 0 || a->screen_bytes != vq_screen_image_bytes(a->H, a->K, a->D, a->metric))
-        return fail(VQ_E_BADARG, "vq_quantize: screen / screen_bytes do not match vq_screen_image_bytes(H, K, D, metric)");
-    if (!aligned16(a->screen)) return fail(VQ_E_BADARG, "vq_quantize: screen is not 16-byte aligned");
-    return 0;
 }
 
 int check_common(const vq_args *a) {
@@ -820,397 +608,9 @@ int check_common(const vq_args *a) {
     return 0;
 }
 
-// Workspace layout: [keys: H*M int64][loss partials: floats]
-// one plane of keys + room for the planes of a K split (few rows: <= 512 x 256 extra keys; a planned split of a mid-size row
-// count: a few planes) -- when the planes do not fit, the splits fall back to ONE plane combined with atomic MIN
-constexpr long long kKeyPlanesExtraBytes = 8ll << 20;
-long long ws_keys_bytes(int H, long long M) { return ((long long)H * M * 8 + 255) / 256 * 256 + kKeyPlanesExtraBytes; }
-// residual stacks of many rows: room at the END of the workspace for the residual rows of a tail run stage by stage (plan_residual_tail)
-constexpr long long kResidualTailBytes = 64ll << 20;
-inline long long residual_tail_room(int H, long long M, int Q) {  // (the row width is not known here: 512 dims, capped)
-    if (Q < 2) return 0;
-    const long long all = ((long long)H * M * 512 * 4 + 255) / 256 * 256;
-    return all < kResidualTailBytes ? all : kResidualTailBytes;
-}
-// loss partials: one float per wave, stage and 32 rows (16 rows for the wave-pair kernel of 256 < D <= 512)
-long long ws_loss_floats(int H, long long M, int Q) { return (long long)H * ((M + 15) / 16 + 16) * Q + (long long)H * 8192 + 64; }
-
-// keys + loss partials of a call, rounded to 256 bytes: what lies in front of the residual rows of a stack's staged tail
-long long ws_core_bytes(int H, long long M, int Q) { return (ws_keys_bytes(H, M) + ws_loss_floats(H, M, Q) * 4 + 256 + 255) / 256 * 256; }
-
-void fill_search_params(SearchParams &p, const vq_args *a) {
-    memset(&p, 0, sizeof(p));
-    p.x = a->x; p.x_rs = a->x_rs; p.x_hs = a->x_hs;
-    p.cb = a->cb; p.cb_hs = a->cb_hs; p.cb_qs = a->cb_qs;
-    p.packed = a->packed; p.pk_hs = a->pk_hs; p.pk_qs = a->pk_qs;
-    p.out = a->out; p.out_rs = a->out_rs; p.out_hs = a->out_hs;
-    p.idx = (long long *)a->idx; p.idx_rs = a->idx_rs; p.idx_hs = a->idx_hs; p.idx_qs = a->idx_qs;
-    p.best = a->best;
-    p.M = a->M; p.K = a->K; p.D = a->D; p.Q = a->Q;
-    {
-        const int tc = kTileCodes * sub_tiles(padded_dim(a->D) ? padded_dim(a->D) : 256);
-        p.ntiles = (a->K + tc - 1) / tc;
-    }
-    p.tiles_per_split = p.ntiles;
-    p.key_hs = a->M;
-    p.pk_bytes = (unsigned)(vq_packed_floats(a->K, a->D) * 4);
-
-    p.ste = (a->flags & VQ_F_STE) ? 1 : 0;
-    p.xt = (a->flags & VQ_F_X_F16) ? 1 : ((a->flags & VQ_F_X_BF16) ? 2 : 0);
-    p.vec_x = vec4_ok(a->x, {a->D, a->x_rs, a->x_hs}, p.xt ? 8 : 16) ? 1 : 0;  // (2-byte rows: four of them are 8 bytes)
-    p.vec_fin = (p.vec_x && (!a->out || vec4_ok(a->out, {a->out_rs, a->out_hs})) && (!a->cb || vec4_ok(a->cb, {a->cb_hs, a->cb_qs}))) ? 1 : 0;
-}
-
-// one stage of a residual stack run stage by stage (residual_tail_staged): where the next residual goes, whether `out` accumulates
-struct ResidualStage {
-    float *res_next;
-    int out_acc;
-};
-
-int run_finalize(const vq_args *a, const long long *keys, float *loss_part, hipStream_t s, int *nparts_out, int key_planes = 1,
-                 const ResidualStage *rst = nullptr) {
-    FinalizeParams f;
-    memset(&f, 0, sizeof(f));
-    if (rst) {
-        f.residual = 1;
-        f.res_next = rst->res_next;
-        f.out_acc = rst->out_acc;
-    }
-    f.keys = keys;
-    f.nparts = key_planes;
-    f.part_stride = (long long)a->H * a->M;
-    f.x = a->x; f.x_rs = a->x_rs; f.x_hs = a->x_hs;
-    f.cb = a->cb; f.cb_hs = a->cb_hs;
-    f.out = a->out; f.out_rs = a->out_rs; f.out_hs = a->out_hs;
-    f.idx = (long long *)a->idx; f.idx_rs = a->idx_rs; f.idx_hs = a->idx_hs;
-    f.best = a->best;
-    f.loss_part = loss_part;
-    f.M = a->M; f.D = a->D; f.metric = a->metric; f.ste = (a->flags & VQ_F_STE) ? 1 : 0;
-    f.vec = (vec4_ok(a->cb, {a->D, a->cb_hs}) && (!a->out || vec4_ok(a->out, {a->out_rs, a->out_hs})) &&
-             (!(f.ste || loss_part || f.res_next) || vec4_ok(a->x, {a->x_rs, a->x_hs})) &&  // (x is read for these only)
-             (!f.res_next || aligned16(f.res_next))) ? 1 : 0;
-    long long blocks = (a->M + 3) / 4;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    const dim3 grid((unsigned)blocks, (unsigned)a->H);
-    const int rc = rst ? launch<vq_finalize_kernel<true>>(grid, dim3(256), 0, s, "vq_finalize launch", f)
-                       : launch<vq_finalize_kernel<false>>(grid, dim3(256), 0, s, "vq_finalize launch", f);
-    if (rc) return rc;
-    if (nparts_out) *nparts_out = (int)(blocks * 4 * a->H);
-    return 0;
-}
-
-// sums the loss partials of a launch: grid = (stages, heads or 1); `sq_err_hs` > 0: the heads' sums that many doubles apart
-int reduce_loss(dim3 grid, hipStream_t s, const float *part, long long nparts, int Q, double *sq_err, int acc, int sq_err_hs = -1) {
-    return launch<vq_loss_reduce_kernel>(grid, dim3(256), 0, s, "vq_loss_reduce launch", part, nparts, Q, sq_err, acc, sq_err_hs);
-}
-
-// squared-error sums of a call: one per stage, per head with VQ_F_SQERR_PER_HEAD
-inline size_t sq_err_count(const vq_args *a) { return (size_t)a->Q * ((a->flags & VQ_F_SQERR_PER_HEAD) ? a->H : 1); }
-int clear_sq_err(double *sq_err, size_t n, hipStream_t s, const char *what) {
-    const hipError_t e = hipMemsetAsync(sq_err, 0, sizeof(double) * n, s);
-    return e == hipSuccess ? 0 : hip_fail(e, what);
-}
-
-// Rows per workgroup of the fused single-stage launch: 256 (8 waves x 32), 128 (4 wave pairs / 4 waves) at Dp = 512.
-// (At Dp <= 128 two 8-wave workgroups share a CU, but a lone one already runs at ~0.93 of the CU's MFMA rate, so a CU is
-//  still one slot of the rounds model below, to within a few percent.)
-inline int fused_rows_per_wg(int DP) { return DP == 512 ? 128 : 256; }
-
-// Time of one 32-code sub-tile of an 8-wave workgroup, microseconds, from the device's own clock instead of a constant
-// measured on one box: two waves share a SIMD and each issues Dp / 2 + 1 fp32 MFMAs of 64 cycles per sub-tile (Dp = 256 at
-// 2.4 GHz: 6.9 us; the 7.2 us measured in round 2 included the sweep's ~4 % of vector work).  Only the RATIO between a
-// sub-tile and the finalize's HBM time enters the plans.
-inline double sub_tile_us(int DP) {
-    const DevInfo &di = dev_info();
-    const double mhz = di.ok && di.clock_mhz > 0 ? (double)di.clock_mhz : 2400.0;
-    return 1.045 * 2.0 * (DP / 2 + 1) * 64.0 / mhz;
-}
-
-// Quantisation of the grid: with one workgroup per CU the launch runs in rounds of `cus` workgroups, and a row count just
-// above a multiple of cus x rows-per-workgroup pays a whole extra round (M = 70 000 at D = 256: 274 workgroups = 2 rounds for
-// 1.07 rounds of work).  Splitting K over S workgroups per row block makes the rounds shorter and fuller at the price of one
-// more prologue per split and the keys + finalize tail.  Costs in units of one sub-tile of sweep (8 waves): prologue ~1.5,
-// fused finalize ~1.2, keys-init + finalize kernels ~ 3 + rows x D x 8 bytes at ~5 TB/s.  Returns the best S (1 = stay fused).
-int plan_k_split(int DP, int H, long long M, int K, int D, int cus, double *cost = nullptr, double *fused_cost = nullptr) {
-    const int rpw = fused_rows_per_wg(DP);
-    const long long nblk = (M + rpw - 1) / rpw * H;
-    const int nsub = (K + kTileCodes - 1) / kTileCodes;
-    if (cost) *cost = *fused_cost = (double)((nblk + cus - 1) / cus) * (1.5 + nsub + 1.2);
-    if (nblk * 2 <= cus || nsub < 16) return 1;  // (few workgroups: the older rule below splits until the chip is full)
-    const double sub_us = sub_tile_us(DP);  // one sub-tile of all the workgroup's waves, microseconds
-    const double tail = 3.0 + (double)M * H * D * 8.0 / 5e6 / sub_us;  // keys init + finalize kernels
-    auto rounds = [&](long long wgs) { return (double)((wgs + cus - 1) / cus); };
-    const double fused = rounds(nblk) * (1.5 + nsub + 1.2);
-    double best = fused;
-    int best_s = 1;
-    for (int S = 2; S <= 16 && S * 8 <= nsub; ++S) {
-        const int per = (nsub + S - 1) / S;
-        const double t = rounds(nblk * S) * (1.5 + per) + tail;
-        if (t < best) {
-            best = t;
-            best_s = S;
-        }
-    }
-    if (best >= 0.88 * fused) return 1;
-    if (cost) *cost = best;
-    return best_s;
-}
-
-// The cut of a grid of `nblk_h` row blocks per head into whole rounds of `cus` workgroups that are also whole row blocks of
-// every head (every head gets the same cut), and the workgroups left for a last, partly filled round.
-struct RoundsCut {
-    long long full, rem;
-};
-inline RoundsCut whole_rounds(long long nblk_h, int H, int cus) {
-    long long full = nblk_h * H / cus;
-    while (full > 0 && (full * cus) % H) --full;
-    return {full, nblk_h * H - full * cus};
-}
-
-// Third remedy for the same quantisation: the row blocks that fill whole rounds run fused, the
-// remainder (fewer blocks than CUs) is searched by a second call, which splits K until the chip is full -- a short round
-// instead of a whole one.  Returns the rows of the fused part, 0 when the model does not predict >= 5 % over both alternatives.
-long long plan_main_tail(int DP, int H, long long M, int K, int D, int cus) {
-    const int rpw = fused_rows_per_wg(DP);
-    const auto [full, rem] = whole_rounds((M + rpw - 1) / rpw, H, cus);
-    const int nsub = (K + kTileCodes - 1) / kTileCodes;
-    if (full < 1 || rem == 0 || rem >= cus || nsub < 8) return 0;
-    double plan_cost = 0.0, fused_cost = 0.0;
-    plan_k_split(DP, H, M, K, D, cus, &plan_cost, &fused_cost);
-    int st = (int)((cus + rem - 1) / rem);
-    if (st > nsub / 8) st = nsub / 8;
-    if (st < 1) st = 1;
-    const int per = (nsub + st - 1) / st;
-    const double sub_us = sub_tile_us(DP);
-    const double tail = (double)((rem * st + cus - 1) / cus) * (1.5 + per) + 3.0 + (double)(rem * rpw) * D * 8.0 / 5e6 / sub_us;
-    // (rem counts workgroups of all heads together)
-    const double hybrid = (double)full * (1.5 + nsub + 1.2) + tail;
-    const double other = plan_cost < fused_cost ? plan_cost : fused_cost;
-    return hybrid < 0.95 * other ? full * cus / H * rpw : 0;
-}
-
-// ---- rows wider than 512 dims -------------------------------------------------------------------
-// The distance of a (row, code) pair is ONE k-ordered fmaf chain over all dims, so the sweep is cut along d into slices of
-// kWideSlice dims: slice j continues the chains slice j - 1 left in the workspace (the accumulators' own fragment layout: every
-// lane reads back exactly the 16-byte pieces it wrote, coalesced), and the last slice closes them with the norms and runs
-// the argmin into packed keys.  The workspace holds the chains of one (row chunk) x (code chunk) at a time.
-
-struct WidePlan {
-    int nd;            // slices
-    int kc;            // codes per chunk (multiple of 32)
-    long long mc;      // rows per chunk (multiple of kWideRows)
-    long long acc_bytes, xn_bytes;
-};
-
-WidePlan wide_plan(int H, long long M, int K, int D) {
-    WidePlan w;
-    w.nd = (D + kWideSlice - 1) / kWideSlice;
-    const int Kp = round_up(K, kTileCodes);
-    w.kc = Kp < kWideCodes ? Kp : kWideCodes;
-    const long long Mp = (M + kWideRows - 1) / kWideRows * kWideRows;
-    long long mc = kWideChunkBytes / ((long long)H * w.kc * 4) / kWideRows * kWideRows;
-    if (mc < kWideRows) mc = kWideRows;
-    if (mc > Mp) mc = Mp;
-    w.mc = mc;
-    w.acc_bytes = (long long)H * mc * w.kc * 4;
-    w.xn_bytes = 2 * (((long long)H * mc * 4 + 255) / 256 * 256);  // two buffers: a slice reads one and writes the other
-    return w;
-}
-
-long long wide_image_floats(int K) { return (long long)round_up(K, kTileCodes) * (kWideSlice + 4) + kPackSlack; }
-// the last slice is padded like a narrow row of its own width (32 ... kWideSlice dims) and packed in that layout
-int wide_last_dims(int D) { return D - (D - 1) / kWideSlice * kWideSlice; }
-long long wide_last_image_floats(int K, int D) {
-    const int DP = padded_dim(wide_last_dims(D));
-    return (long long)round_up(K, kTileCodes * sub_tiles(DP)) * (DP + 4) + kPackSlack;
-}
-
-bool wide_workspace_ok(const vq_args *a) {
-    const WidePlan w = wide_plan(a->H, a->M, a->K, a->D);
-    return a->workspace && a->workspace_bytes >= vq_workspace_bytes(a->H, a->M, 1) + w.acc_bytes + w.xn_bytes;
-}
-
-// One (row chunk, code chunk) covers all codes and every launch fills the chip without a K split: the last slice can finish
-// the inference call itself (idx, best, out = codebook[idx]) instead of going through keys and the finalize kernel.
-bool wide_fusable(const vq_args *a) {
-    if (a->Q != 1 || (a->flags & (VQ_F_STE | VQ_F_FORCE_SPLIT | VQ_F_FORCE_SIMPLE)) || a->sq_err || !a->out || !a->idx || !a->cb)
-        return false;
-    if (!vec4_ok(a->out, {a->D, a->out_rs, a->out_hs}) || !vec4_ok(a->cb, {a->cb_hs})) return false;
-    if (round_up(a->K, kTileCodes) > kWideCodes) return false;
-    const int cus = device_cus();
-    const WidePlan w = wide_plan(a->H, a->M, a->K, a->D);
-    const long long last_rows = a->M % w.mc ? a->M % w.mc : w.mc;  // the smallest row chunk
-    if (((last_rows + kWideRows - 1) / kWideRows) * a->H < cus) return false;
-    // a row count that leaves the last round of workgroups mostly empty is better served by a K split (keys path)
-    return plan_k_split(kWideSlice, a->H, w.mc < a->M ? w.mc : a->M, a->K, kWideSlice, cus) == 1;
-}
-
-// `keys` (search: argmin into packed keys), `sims` (the similarity matrix itself) or `fused` (the whole inference call)
-int run_wide(const vq_args *a, long long idx_offset, long long *keys, float *sims, long long sims_rs, long long sims_hs,
-             hipStream_t s, bool fused = false) {
-    if (!a->packed) return fail(VQ_E_BADARG, "vq: packed codebook is null");
-    if (a->flags & (VQ_F_X_F16 | VQ_F_X_BF16)) return fail(VQ_E_UNSUPPORTED, "vq: 2-byte rows need D <= 512");
-    const long long img = wide_image_floats(a->K);
-    if (img * 4 >= (1ll << 31)) return fail(VQ_E_UNSUPPORTED, "vq: packed codebook image >= 2 GiB (shard the codebook)");
-    const WidePlan w = wide_plan(a->H, a->M, a->K, a->D);
-    const long long base = vq_workspace_bytes(a->H, a->M, 1);
-    if (!a->workspace || a->workspace_bytes < base + w.acc_bytes + w.xn_bytes)
-        return fail(VQ_E_BADARG, "vq: workspace too small for rows wider than 512 dims (see vq_workspace_bytes_wide)");
-    float *acc_ws = (float *)((char *)a->workspace + base);
-    float *xn_ws = (float *)((char *)a->workspace + base + w.acc_bytes);
-    const int cus = device_cus();
-    const int Kp = round_up(a->K, kTileCodes);
-    const int d_last = wide_last_dims(a->D), dp_last = padded_dim(d_last);
-    for (long long m0 = 0; m0 < a->M; m0 += w.mc) {
-        const long long mrows = (a->M - m0 < w.mc) ? a->M - m0 : w.mc;
-        const long long nblk = (mrows + kWideRows - 1) / kWideRows;
-        for (int k0 = 0; k0 < Kp; k0 += w.kc) {
-            const int kcodes = (a->K - k0 < w.kc) ? a->K - k0 : w.kc;  // real codes of this chunk (> 0: k0 < Kp, K > Kp - 32)
-            const int nsub = (kcodes + kTileCodes - 1) / kTileCodes;
-            for (int j = 0; j < w.nd; ++j) {
-                const bool last = j + 1 == w.nd;
-                const int DP = last ? dp_last : kWideSlice;
-                const int rs = DP + 4;                                        // packed row stride of this slice's image
-                const long long img_j = last ? wide_last_image_floats(a->K, a->D) : img;
-                SearchParams p;
-                memset(&p, 0, sizeof(p));
-                p.x = a->x + m0 * a->x_rs + (long long)j * kWideSlice;
-                p.x_rs = a->x_rs; p.x_hs = a->x_hs;
-                p.packed = a->packed + (long long)j * img + (long long)k0 * rs;
-                p.pk_hs = a->pk_hs;
-                p.pk_bytes = (unsigned)((img_j - (long long)k0 * rs) * 4);
-                p.M = mrows; p.K = kcodes; p.D = last ? d_last : kWideSlice; p.Q = 1;
-                const int tc = kTileCodes * sub_tiles(DP);
-                p.ntiles = (kcodes + tc - 1) / tc;
-                // K is split over workgroups until the chip is full (one workgroup per CU at Dp = 512 / 8 waves at Dp = 256)
-                const long long fill = (long long)cus * ((DP == 512 || (kWideWaves == 8 && DP == 256)) ? 1 : 2);
-                int splits = 1;
-                if (nblk * a->H < fill) {
-                    splits = (int)((fill + nblk * a->H - 1) / (nblk * a->H));
-                    if (splits > p.ntiles) splits = p.ntiles;
-                } else if (!fused) {
-                    splits = plan_k_split(DP, a->H, mrows, kcodes, DP, cus);  // partly filled last round of workgroups
-                    if (splits > p.ntiles) splits = p.ntiles;
-                }
-                p.tiles_per_split = (p.ntiles + splits - 1) / splits;
-                splits = (p.ntiles + p.tiles_per_split - 1) / p.tiles_per_split;
-                p.mode = fused ? kModeFused : kModeKeys;
-                if (fused) {
-                    p.cb = a->cb; p.cb_hs = a->cb_hs;
-                    p.out = a->out + m0 * a->out_rs; p.out_rs = a->out_rs; p.out_hs = a->out_hs;
-                    p.idx = (long long *)a->idx + m0 * a->idx_rs; p.idx_rs = a->idx_rs; p.idx_hs = a->idx_hs;
-                    p.best = a->best ? a->best + m0 * a->idx_rs : nullptr;
-                    p.fin_D = a->D;
-                    splits = 1;
-                    p.tiles_per_split = p.ntiles;
-                }
-                p.keys = keys ? keys + m0 : nullptr;
-                p.key_hs = a->M;
-                p.idx_offset = idx_offset + k0;
-                p.vec_x = vec4_ok(a->x, {p.D, a->x_rs, a->x_hs}) ? 1 : 0;
-                p.acc_ws = acc_ws;
-                p.ws_hs = nblk * kWideWaves * (long long)nsub * 256;
-                p.ws_nsub = nsub;
-                p.acc_in = j > 0;
-                p.xn_ws = xn_ws + ((j + 1) & 1) * (w.xn_bytes / 8);
-                p.xn_out = xn_ws + (j & 1) * (w.xn_bytes / 8);
-                p.xn_hs = w.mc;
-                if (sims) {
-                    p.sims = sims + m0 * sims_rs + k0;
-                    p.sims_rs = sims_rs; p.sims_hs = sims_hs;
-                    p.vec_s = vec4_ok(sims, {a->K, sims_rs, sims_hs}) ? 1 : 0;
-                }
-                const int rc = launch_wide(!last ? 1 : (sims ? 3 : 2), DP, p, a->H, splits, a->metric, s);
-                if (rc) return rc;
-            }
-        }
-    }
-    return 0;
-}
-
-// How a keys-mode search of `a` is launched on this device: workgroup size and the number of K splits (= key planes when the
-// splits store into planes of their own instead of combining with atomic MIN).
-// Workgroup size of the one-block kernel and the workgroups of its grid: 8 waves (4 at Dp = 512: LDS), or 4 when the 8-wave
-// grid leaves CUs empty.
-struct WaveGrid {
-    int waves;
-    long long wgs;
-};
-inline WaveGrid wave_grid(int DP, int H, long long M, int cus, bool may_halve = true) {
-    WaveGrid g = {DP == 512 ? 4 : 8, 0};
-    g.wgs = H * one_block_grid_x(M, g.waves);
-    if (may_halve && g.waves == 8 && g.wgs < cus) g = {4, H * one_block_grid_x(M, 4)};
-    return g;
-}
-
-struct KeysPlan {
-    int DP, waves, splits, tiles_per_split;
-    bool mfma;  // false: the one-thread-per-row kernel / the sliced sweep of wide rows (one plane, atomic MIN)
-};
-
-KeysPlan plan_keys(const vq_args *a, int planned_splits) {
-    KeysPlan k;
-    k.DP = padded_dim(a->D);
-    k.mfma = k.DP != 0 && !(a->flags & VQ_F_FORCE_SIMPLE);
-    k.waves = 8;
-    k.splits = 1;
-    k.tiles_per_split = 1;
-    if (!k.mfma) return k;
-    const int cus = device_cus();
-    const int tc = kTileCodes * sub_tiles(k.DP);
-    const int ntiles = (a->K + tc - 1) / tc;
-    const WaveGrid g = wave_grid(k.DP, a->H, a->M, cus, /*may_halve=*/planned_splits == 0);  // (plan_k_split: full-size workgroups)
-    k.waves = g.waves;
-    const long long wgs = g.wgs;
-    // K is split until the chip is full: two 4-wave workgroups fit a CU at Dp <= 256, one (LDS) at Dp = 512 -- splitting
-    // further only repeats the prologue and, in the wave-pair kernel, the extra pipeline step
-    const long long fill = (long long)cus * (k.DP == 512 ? 1 : 2);
-    int splits = 1;
-    if (planned_splits > 0) {
-        splits = planned_splits < ntiles ? planned_splits : ntiles;  // (plan_k_split: full-size workgroups, S splits)
-    } else if (wgs < fill) {
-        splits = (int)((fill + wgs - 1) / wgs);
-        if (splits > ntiles) splits = ntiles;
-        if (splits < 1) splits = 1;
-    }
-    k.tiles_per_split = (ntiles + splits - 1) / splits;
-    k.splits = (ntiles + k.tiles_per_split - 1) / k.tiles_per_split;  // every split owns at least one tile
-    return k;
-}
-
-// `part_stride` > 0: K split z stores its keys into plane z (planes part_stride keys apart, plan_keys(..).splits of them,
-// nothing to initialise); 0: all splits combine into ONE plane with atomic MIN (the caller initialised it).
-int run_search_keys(const vq_args *a, long long idx_offset, long long *keys, hipStream_t s, int planned_splits = 0,
-                    long long part_stride = 0) {
-    const KeysPlan kp = plan_keys(a, planned_splits);
-    if (!kp.mfma && part_stride > 0) return fail(VQ_E_UNSUPPORTED, "vq: key planes need the MFMA kernel (D <= 512)");
-    if (kp.DP == 0 && !(a->flags & VQ_F_FORCE_SIMPLE)) return run_wide(a, idx_offset, keys, nullptr, 0, 0, s);
-    if (!kp.mfma) {
-        if (!a->cb) return fail(VQ_E_BADARG, "vq: natural codebook required for the scalar kernel");
-        return with_metric(a->metric, [&](auto m) {
-            return launch<vq_search_simple<decltype(m)::value>>(dim3((unsigned)((a->M + 63) / 64), (unsigned)a->H), dim3(64), 0, s, "vq_search_simple launch",
-                                                                a->x, a->x_rs, a->x_hs, a->cb, a->cb_hs, a->M, a->K, a->D, idx_offset, keys);
-        });
-    }
-    if (!a->packed) return fail(VQ_E_BADARG, "vq: packed codebook is null");
-    if (vq_packed_floats(a->K, a->D) * 4 >= (1ll << 31))
-        return fail(VQ_E_UNSUPPORTED, "vq: packed codebook image >= 2 GiB (shard the codebook)");
-    SearchParams p;
-    fill_search_params(p, a);
-    p.mode = part_stride > 0 ? kModeKeyParts : kModeKeys;
-    p.key_zs = part_stride;
-    p.keys = keys;
-    p.idx_offset = idx_offset;
-    p.Q = 1;
-    p.out = nullptr;
-    p.loss_part = nullptr;
-    p.tiles_per_split = kp.tiles_per_split;
-    const int cus = device_cus();  // (a keys-mode search is never a whole fused call: wave pairs or one block)
-    return launch_search(choose_search(kp.DP, kp.waves, p, a->H, kp.splits, a->metric, cus), kp.DP, p, a->H, kp.splits, a->metric, cus, s);
-}
-
 }  // namespace
+
+#include "vq_search_host.inc"
 
 // =================================================================================================
 // C ABI
@@ -1253,21 +653,19 @@ int64_t vq_packed_floats(int K, int D) {
 
 int64_t vq_workspace_bytes_wide(int H, int64_t M, int K, int D) {
     if (H <= 0 || M < 0 || K <= 0 || D <= 0) return 0;
-    const int64_t base = vq_workspace_bytes(H, M, 1);
-    if (padded_dim(D) != 0 || M == 0) return base;
-    const WidePlan w = wide_plan(H, M, K, D);
-    return base + w.acc_bytes + w.xn_bytes;
+    if (padded_dim(D) != 0 || M == 0) return workspace_bytes(H, M, 1);
+    return wide_workspace_bytes(H, M, wide_plan(H, M, K, D));
 }
 
 int64_t vq_workspace_bytes(int H, int64_t M, int Q) {
     if (H <= 0 || M < 0 || Q <= 0) return 0;
     // (+ residual stacks of many rows: room for the residual rows of a tail run stage by stage, see plan_residual_tail)
-    return ws_core_bytes(H, M, Q) + residual_tail_room(H, M, Q);
+    return workspace_bytes(H, M, Q);
 }
 
 int64_t vq_screen_image_bytes(int H, int K, int D, int metric) {
     if (H <= 0 || K <= 0 || D <= 0 || metric != VQ_METRIC_EUCLID || padded_dim(D) != 256) return 0;
-    const int ntiles = (K + kTileCodes * sub_tiles(256) - 1) / (kTileCodes * sub_tiles(256)), nsub = ntiles * sub_tiles(256);
+    const int ntiles = tiles_of(K, 256), nsub = ntiles * sub_tiles(256);
     if (nsub < kPersistMinSub || nsub > kPersistMaxSub) return 0;
     return screen_image_bytes(H, ntiles);
 }
@@ -1278,7 +676,7 @@ int vq_pack_screen_image_f32(const float *packed, int H, int64_t pk_hs, int K, i
     if (need == 0) return fail(VQ_E_UNSUPPORTED, "vq_pack_screen_image: no screened sweep for this shape (see vq_screen_image_bytes)");
     if (!packed || !screen || screen_bytes != need || !aligned16(packed) || !aligned16(screen) || pk_hs < vq_packed_floats(K, D))
         return fail(VQ_E_BADARG, "vq_pack_screen_image: bad argument");
-    const int ntiles = (K + kTileCodes - 1) / kTileCodes;  // (sub_tiles(256) == 1)
+    const int ntiles = tiles_of(K, 256);
     const long long img = scr_image_bytes(ntiles);
     return vqi::part_pack_scr(packed, pk_hs, K, ntiles, H, (char *)screen, img, (unsigned *)((char *)screen + (long long)H * img),
                               (hipStream_t)stream);
@@ -1311,313 +709,6 @@ int vq_pack_codebooks_f32(const float *cb, int n_codebooks, int64_t cb_stride, i
         return rc;
     return launch<vq_pack_flag_kernel>(dim3(n_codebooks), dim3(256), 0, s, "vq_pack launch", packed, pk_stride, K, DP + 4, DP, 1, pk_stride,
                                        (long long)vq_packed_floats(K, D));
-}
-
-int vq_keys_init(int64_t *keys, int64_t n, void *stream) {
-    if (!keys || n < 0) return fail(VQ_E_BADARG, "vq_keys_init: bad argument");
-    if (n == 0) return 0;
-    return launch<vq_keys_init_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, "vq_keys_init launch", (long long *)keys,
-                                       (long long)n);
-}
-
-int vq_search_keys_f32(const vq_args *a, int64_t idx_offset, int64_t *keys, void *stream) {
-    int rc = check_common(a);
-    if (rc) return rc;
-    if (a->Q != 1) return fail(VQ_E_BADARG, "vq_search_keys: Q must be 1");
-    if (!keys) return fail(VQ_E_BADARG, "vq_search_keys: keys is null");
-    if (idx_offset < 0 || idx_offset + a->K > 0xFFFFFFFFll) return fail(VQ_E_BADARG, "vq_search_keys: index range");
-    if (a->M == 0) return 0;
-    return run_search_keys(a, idx_offset, (long long *)keys, (hipStream_t)stream);
-}
-
-int vq_key_planes(const vq_args *a) {
-    if (check_common(a) || a->Q != 1 || a->M == 0) return 1;
-    const KeysPlan kp = plan_keys(a, 0);
-    return kp.mfma ? kp.splits : 1;
-}
-
-int vq_search_key_planes_f32(const vq_args *a, int64_t idx_offset, int64_t *keys, void *stream) {
-    int rc = check_common(a);
-    if (rc) return rc;
-    if (a->Q != 1) return fail(VQ_E_BADARG, "vq_search_key_planes: Q must be 1");
-    if (!keys) return fail(VQ_E_BADARG, "vq_search_key_planes: keys is null");
-    if (idx_offset < 0 || idx_offset + a->K > 0xFFFFFFFFll) return fail(VQ_E_BADARG, "vq_search_key_planes: index range");
-    if (a->M == 0) return 0;
-    const KeysPlan kp = plan_keys(a, 0);
-    if (!kp.mfma) {  // scalar kernel / wide rows: one plane, combined with atomic MIN
-        rc = vq_keys_init(keys, (int64_t)a->H * a->M, stream);
-        if (rc) return rc;
-        return run_search_keys(a, idx_offset, (long long *)keys, (hipStream_t)stream);
-    }
-    return run_search_keys(a, idx_offset, (long long *)keys, (hipStream_t)stream, 0, (long long)a->H * a->M);
-}
-
-int vq_finalize_key_planes_f32(const vq_args *a, const int64_t *keys, int n_planes, void *stream);
-
-int vq_finalize_keys_f32(const vq_args *a, const int64_t *keys, void *stream) { return vq_finalize_key_planes_f32(a, keys, 1, stream); }
-
-int vq_finalize_key_planes_f32(const vq_args *a, const int64_t *keys, int n_planes, void *stream) {
-    int rc = check_common(a);
-    if (rc) return rc;
-    if (n_planes < 1) return fail(VQ_E_BADARG, "vq_finalize_keys: n_planes must be >= 1");
-    if (a->Q != 1) return fail(VQ_E_BADARG, "vq_finalize_keys: Q must be 1");
-    if (a->M == 0) {  // (no rows: no keys either -- an empty tensor's address is null, as x's may be in check_common)
-        return a->sq_err ? clear_sq_err(a->sq_err, 1, (hipStream_t)stream, "vq_finalize_keys: clearing sq_err") : 0;
-    }
-    if (!keys || !a->cb) return fail(VQ_E_BADARG, "vq_finalize_keys: keys / cb is null");
-    hipStream_t s = (hipStream_t)stream;
-    float *loss_part = nullptr;
-    if (a->sq_err) {
-        if (!a->workspace || a->workspace_bytes < vq_workspace_bytes(a->H, a->M, 1))
-            return fail(VQ_E_BADARG, "vq_finalize_keys: workspace too small");
-        loss_part = (float *)((char *)a->workspace + ws_keys_bytes(a->H, a->M));
-    }
-    int nparts = 0;
-    rc = run_finalize(a, (const long long *)keys, loss_part, s, &nparts, n_planes);
-    if (rc) return rc;
-    return a->sq_err ? reduce_loss(dim3(1), s, loss_part, nparts, 1, a->sq_err, 0) : 0;
-}
-
-constexpr uint32_t kFlagAccumulateSqErr = 0x80000000u;  // never set by callers: quantize_entry masks it off
-
-// A single stage as  search into key planes (K split over workgroups: every split stores its winners into a plane of its own, no
-// init launch, no atomics; one plane + atomic MIN if the planes do not fit the workspace)  +  finalize (MIN over the planes,
-// gather, straight-through, squared error).  `rst`: the stage belongs to a residual stack run stage by stage.
-// `sq_err_hs` > 0: one squared-error sum per head, the heads `sq_err_hs` doubles apart (a stage of a grouped stack).
-static int split_stage(const vq_args *a, int planned_splits, int acc, void *stream, const ResidualStage *rst, int sq_err_hs = 0) {
-    hipStream_t s = (hipStream_t)stream;
-    long long *keys = (long long *)a->workspace;
-    float *loss_part = (float *)((char *)a->workspace + ws_keys_bytes(a->H, a->M));
-    const KeysPlan kp = plan_keys(a, planned_splits);
-    int planes = 1;
-    if (kp.mfma && (long long)kp.splits * a->H * a->M * 8 <= ws_keys_bytes(a->H, a->M)) planes = kp.splits;
-    int rc;
-    if (!kp.mfma || planes != kp.splits) {
-        rc = vq_keys_init((int64_t *)keys, (int64_t)a->H * a->M, stream);
-        if (rc) return rc;
-        planes = 1;
-    }
-    rc = run_search_keys(a, 0, keys, s, planned_splits, kp.mfma && planes == kp.splits ? (long long)a->H * a->M : 0);
-    if (rc) return rc;
-    int nparts = 0;
-    rc = run_finalize(a, keys, a->sq_err ? loss_part : nullptr, s, &nparts, planes, rst);
-    if (rc) return rc;
-    if (!a->sq_err) return 0;
-    if (sq_err_hs > 0)  // the finalize's partials are [head][nparts / H]
-        return reduce_loss(dim3(1, a->H), s, loss_part, nparts / a->H, 1, a->sq_err, acc, sq_err_hs);
-    return reduce_loss(dim3(1), s, loss_part, nparts, 1, a->sq_err, acc);
-}
-
-// ---- residual stacks whose row count leaves the last round of workgroups mostly empty -------------------------------------
-// A residual launch cannot split K (every stage needs the whole codebook per row), so M = 70 000 at cfg4's shape pays half a
-// round of 128-row workgroups for 7 % of a round of work.  The rows that fill whole rounds run on the fused kernel; the
-// remainder runs STAGE BY STAGE, each stage a K-split search over all CUs + a finalize that also writes the next residual
-// (r - quant, the fused kernel's arithmetic) into the workspace and accumulates `out`: 2-3 short launches per stage instead of
-// half a round of sweep per stage.  The same holds for a stack of FEW rows (less than one round: M = 8192 occupies 32 CUs, or 64
-// at one wave per SIMD): then every row runs stage by stage.  Returns the rows (per head) of the fused part -- 0: all rows
-// staged -- or -1 = keep the single fused launch.
-
-static long long plan_residual_tail(const vq_args *a, int DP, int cus) {
-    if (a->Q < 2 || DP == 0 || (a->flags & (VQ_F_FORCE_SIMPLE | VQ_F_FORCE_SPLIT))) return -1;
-    if (getenv("VQ_NO_RESIDUAL_TAIL") != nullptr) return -1;  // (read per call: tests run both plans in one process)
-    const int rpw = fused_rows_per_wg(DP);  // 256 (128 at Dp = 512)
-    const auto [full, rem] = whole_rounds((a->M + rpw - 1) / rpw, a->H, cus);
-    if (rem == 0) return -1;
-    const long long m1 = full * cus / a->H * rpw, mt = a->M - m1;
-    if (mt <= 0 || (long long)a->H * mt * a->D * 4 > residual_tail_room(a->H, a->M, a->Q)) return -1;  // (no room for the residual rows)
-    const int nsub = (a->K + kTileCodes - 1) / kTileCodes;
-    if (nsub < 8) return -1;  // (too short to split)
-    const double sweep_us = nsub * sub_tile_us(DP);  // one stage of one round
-    // the fused alternative: a whole round, or ~0.55 of one when 128-row workgroups fit one per CU (Dp <= 256: a lone 4-wave
-    // workgroup has the matrix pipe to itself, see quantize_impl)
-    const long long rem4 = ((mt + 127) / 128) * a->H;
-    const double fused_rounds = (DP <= 256 && rem4 <= cus) ? 0.55 : 1.0;
-    const double fused_us = fused_rounds * a->Q * sweep_us;
-    // staged: per stage ~20 us of launches + finalize, the tail's share of a round of sweep (K split: ~1.4 x for the extra prologues)
-    const double staged_us = a->Q * (20.0 + 1.4 * sweep_us * (double)rem / cus);
-    return staged_us < 0.8 * fused_us ? m1 : -1;
-}
-
-static int residual_tail_staged(const vq_args *a, long long m1, void *stream) {
-    const long long mt = a->M - m1;
-    // [H][mt][D], behind the keys and the loss partials of the whole call
-    float *R = (float *)((char *)a->workspace + ws_core_bytes(a->H, a->M, a->Q));
-    for (int q = 0; q < a->Q; ++q) {
-        vq_args t = *a;
-        t.M = mt;
-        t.Q = 1;
-        if (q == 0) {
-            t.x = a->x + m1 * a->x_rs;
-        } else {
-            t.x = R;
-            t.x_rs = a->D;
-            t.x_hs = mt * a->D;
-        }
-        t.cb = a->cb + (long long)q * a->cb_qs;
-        t.packed = a->packed + (long long)q * a->pk_qs;
-        if (a->out) t.out = a->out + m1 * a->out_rs;
-        t.idx = a->idx + m1 * a->idx_rs + (long long)q * a->idx_qs;
-        if (a->best) t.best = a->best + m1 * a->idx_rs + (long long)q * a->idx_qs;
-        if (a->sq_err) t.sq_err = a->sq_err + q;
-        t.workspace_bytes = ws_core_bytes(a->H, a->M, a->Q);
-        ResidualStage rst;
-        rst.res_next = (q + 1 < a->Q) ? R : nullptr;
-        rst.out_acc = q > 0;
-        t.flags &= ~VQ_F_SQERR_PER_HEAD;
-        const int by_head_hs = ((a->flags & VQ_F_SQERR_PER_HEAD) && a->sq_err) ? a->Q : 0;  // sq_err is [H][Q]: stage q of head h at h * Q + q
-        const int rc = split_stage(&t, 0, /*acc=*/1, stream, &rst, by_head_hs);  // (the fused part wrote sq_err[q]; this adds the tail's sum)
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-static int quantize_impl(const vq_args *a, void *stream, float *lse) {
-    int rc = check_common(a);
-    if (rc) return rc;
-    rc = check_screen(a);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (lse && (a->Q != 1 || padded_dim(a->D) == 0 || (a->flags & (VQ_F_FORCE_SIMPLE | VQ_F_FORCE_SPLIT))))
-        return fail(VQ_E_UNSUPPORTED, "vq_quantize_lse: needs Q == 1, D <= 512 and the fused MFMA path");
-    if ((a->flags & (VQ_F_X_F16 | VQ_F_X_BF16)) &&
-        (a->Q != 1 || padded_dim(a->D) == 0 || lse || a->sq_err || (a->flags & (VQ_F_STE | VQ_F_FORCE_SIMPLE))))
-        return fail(VQ_E_UNSUPPORTED, "vq_quantize: 2-byte rows are inference only (Q == 1, D <= 512, no STE / sq_err / lse)");
-    if (a->M > 0 && !a->idx) return fail(VQ_E_BADARG, "vq_quantize: idx is null");
-    if (a->M > 0 && !a->cb) return fail(VQ_E_BADARG, "vq_quantize: natural codebook is null");
-    if (a->M == 0) return a->sq_err ? clear_sq_err(a->sq_err, sq_err_count(a), s, "vq_quantize: clearing sq_err") : 0;
-    if (!a->workspace || a->workspace_bytes < vq_workspace_bytes(a->H, a->M, a->Q))
-        return fail(VQ_E_BADARG, "vq_quantize: workspace too small (see vq_workspace_bytes)");
-    long long *keys = (long long *)a->workspace;
-    float *loss_part = (float *)((char *)a->workspace + ws_keys_bytes(a->H, a->M));
-
-    const int DP = padded_dim(a->D);
-    const bool simple = (a->flags & VQ_F_FORCE_SIMPLE) || DP == 0;
-    const int cus = device_cus();
-
-    const int acc = (a->flags & kFlagAccumulateSqErr) ? 1 : 0;  // (internal: second call of a two-call plan adds its sum)
-    const int res_img = (simple || acc) ? 0 : resident_image_for(a, DP, lse != nullptr, cus);
-    if (!res_img && !simple && a->Q == 1 && !lse && !acc && !((a->flags & VQ_F_SQERR_PER_HEAD) && a->sq_err) &&
-        !(a->flags & (VQ_F_FORCE_SPLIT | VQ_F_X_F16 | VQ_F_X_BF16))) {
-        const long long m1 = plan_main_tail(DP, a->H, a->M, a->K, a->D, cus);
-        if (m1 > 0 && m1 < a->M) {  // whole rounds fused, then the remainder as its own (K-split) call
-            vq_args a1 = *a, a2 = *a;
-            a1.M = m1;
-            a2.M = a->M - m1;
-            a2.x = a->x + m1 * a->x_rs;
-            if (a->out) a2.out = a->out + m1 * a->out_rs;
-            a2.idx = a->idx + m1 * a->idx_rs;
-            if (a->best) a2.best = a->best + m1 * a->idx_rs;
-            if (a->sq_err) a2.flags |= kFlagAccumulateSqErr;  // one squared-error sum over both parts, fixed order
-            rc = quantize_impl(&a1, stream, nullptr);
-            if (rc) return rc;
-            return quantize_impl(&a2, stream, nullptr);
-        }
-    }
-
-    if (!simple && a->Q > 1 && !acc && a->packed && a->workspace_bytes >= vq_workspace_bytes(a->H, a->M, a->Q)) {
-        const long long m1 = plan_residual_tail(a, DP, cus);
-        if (m1 >= 0 && m1 < a->M) {  // whole rounds on the fused kernel, the remainder stage by stage (K split over all CUs)
-            if (m1 > 0) {
-                vq_args a1 = *a;
-                a1.M = m1;
-                rc = quantize_impl(&a1, stream, nullptr);
-                if (rc) return rc;
-            } else if (a->sq_err) {  // (no fused part: the stages ADD their sums)
-                rc = clear_sq_err(a->sq_err, sq_err_count(a), s, "vq_quantize: clearing sq_err");
-                if (rc) return rc;
-            }
-            return residual_tail_staged(a, m1, stream);
-        }
-    }
-
-    // ---- choose fused (one launch, no K split) or split (keys + finalize) ----
-    bool fused = !simple;
-    int planned_splits = 0;
-    int waves = (DP == 512) ? 4 : 8;
-    if (fused) {
-        const WaveGrid g = wave_grid(DP, a->H, a->M, cus);
-        waves = g.waves;
-        long long wgs = g.wgs;
-        // Residual stacks cannot split K (every stage needs the whole codebook per row), so a row count just above a multiple of
-        // cus x 256 used to pay a whole extra round of 8-wave workgroups.  Two 4-wave workgroups share a CU at the pace of one
-        // 8-wave workgroup, and a LONE 4-wave workgroup (one wave per SIMD: the matrix pipe to itself) finishes its 128 rows in
-        // about half a round -- so with 128-row workgroups the remainder costs half a round instead of a whole one whenever it
-        // fits one workgroup per CU (M = 70 000 at cfg4's shape: 2 rounds -> ~1.55).
-        if (waves == 8 && DP == 256 && a->Q > 1) {
-            const long long nblk4 = (long long)a->H * ((a->M + 127) / 128);
-            const long long full = nblk4 / (2ll * cus), rem = nblk4 % (2ll * cus);
-            const double t8 = (double)((wgs + cus - 1) / cus);
-            const double t4 = (double)full + (rem == 0 ? 0.0 : (rem <= cus ? 0.55 : 1.0));
-            if (t4 < 0.97 * t8) {
-                waves = 4;
-                wgs = nblk4;
-            }
-        }
-#ifdef VQ_EXP_WAVES
-        waves = VQ_EXP_WAVES;  // diagnostic builds only
-#endif
-        const int ntiles = (a->K + kTileCodes * sub_tiles(DP) - 1) / (kTileCodes * sub_tiles(DP));
-        // few workgroups and a long sweep: splitting K over workgroups fills the chip (Q == 1 only)
-        if (a->Q == 1 && wgs * 2 <= cus && ntiles * sub_tiles(DP) >= 8 && ntiles >= 2) fused = false;
-        if ((a->flags & VQ_F_FORCE_SPLIT) && a->Q == 1) fused = false;
-        if (fused && a->Q == 1 && !(a->flags & (VQ_F_X_F16 | VQ_F_X_BF16))) {
-            planned_splits = plan_k_split(DP, a->H, a->M, a->K, a->D, cus);  // grid quantisation (see plan_k_split)
-            if (planned_splits > 1) fused = false;
-        }
-        if (res_img) fused = true;  // small codebook resident in LDS: 32-row granularity, no plan needed
-        if (lse) fused = true;  // the log-sum-exp needs every code of a row in one workgroup
-        if ((a->flags & VQ_F_SQERR_PER_HEAD) && a->sq_err) fused = true;  // per-head partial sums exist on this path only
-    }
-
-    if (fused) {
-        if (!a->packed) return fail(VQ_E_BADARG, "vq_quantize: packed codebook is null");
-        if (vq_packed_floats(a->K, a->D) * 4 >= (1ll << 31))
-            return fail(VQ_E_UNSUPPORTED, "vq_quantize: packed codebook image >= 2 GiB (shard the codebook)");
-        SearchParams p;
-        fill_search_params(p, a);
-        p.mode = kModeFused;
-        p.loss_part = a->sq_err ? loss_part : nullptr;
-        p.lse = lse;
-        p.res_img_floats = res_img;
-        if (res_img) {
-            static const char *env = getenv("VQ_RES_SKEW");  // (diagnostic: start-up skew of the second wave per SIMD)
-            p.res_skew = env ? atoi(env) : 0;
-            const size_t full = ((size_t)res_img + 8 * (DP / 16) * 512) * 4 + 2 * 8 * 32 * 4;  // a slab buffer per slab of a block
-            p.res_nbuf = (DP < 128 && full <= 160 * 1024) ? DP / 16 : 1;
-        }
-        // the one decision which kernel runs this call: the screen images, the launch and the partials' count all follow it
-        const SearchChoice c = choose_search(DP, waves, p, a->H, 1, a->metric, cus, /*scr_room=*/ws_keys_bytes(a->H, a->M),
-                                             /*scr_cached=*/a->screen != nullptr);
-        if (c.screened) set_screen_image(p, a, c.cached);
-        rc = launch_search(c, DP, p, a->H, 1, a->metric, cus, s);
-        if (rc || !a->sq_err) return rc;
-        const long long per_head = loss_partials_per_head(c, a->M, a->H, cus);
-        const bool by_head = (a->flags & VQ_F_SQERR_PER_HEAD) != 0;
-        return reduce_loss(dim3(a->Q, by_head ? a->H : 1), s, loss_part, by_head ? per_head : per_head * a->H, a->Q, a->sq_err, acc);
-    }
-
-    if (DP == 0 && wide_fusable(a)) return run_wide(a, 0, nullptr, nullptr, 0, 0, s, true);
-    if (a->Q != 1) return fail(VQ_E_UNSUPPORTED, "vq_quantize: residual stages need the MFMA kernel (D <= 512)");
-    if ((a->flags & VQ_F_SQERR_PER_HEAD) && a->sq_err)
-        return fail(VQ_E_UNSUPPORTED, "vq_quantize: per-head squared errors need the MFMA kernel (D <= 512)");
-    return split_stage(a, fused ? 0 : planned_splits, acc, stream, nullptr);
-}
-
-// the public entries: kFlagAccumulateSqErr is internal, a caller's copy of the bit is dropped
-static int quantize_entry(const vq_args *a, void *stream, float *lse) {
-    if (a && (a->flags & kFlagAccumulateSqErr)) {
-        vq_args b = *a;
-        b.flags &= ~kFlagAccumulateSqErr;
-        return quantize_impl(&b, stream, lse);
-    }
-    return quantize_impl(a, stream, lse);
-}
-
-int vq_quantize_f32(const vq_args *a, void *stream) { return quantize_entry(a, stream, nullptr); }
-
-int vq_quantize_lse_f32(const vq_args *a, float *lse, void *stream) {
-    if (!lse && a && a->M > 0) return fail(VQ_E_BADARG, "vq_quantize_lse: lse is null");
-    return quantize_entry(a, stream, lse);
 }
 
 int vq_quantize_backward_f32(const vq_args *a, const float *grad_out, int64_t go_rs, int64_t go_hs, const double *grad_sq_err,
@@ -1853,8 +944,7 @@ static int fill_aux_params(AuxParams &p, const vq_args *a) {
     p.packed = a->packed; p.pk_hs = a->pk_hs;
     p.pk_bytes = (unsigned)(vq_packed_floats(a->K, a->D) * 4);
     p.M = a->M; p.K = a->K; p.D = a->D;
-    const int tc = kTileCodes * sub_tiles(padded_dim(a->D));
-    p.ntiles = (a->K + tc - 1) / tc;
+    p.ntiles = tiles_of(a->K, padded_dim(a->D));
     p.vec_x = vec4_ok(a->x, {a->D, a->x_rs, a->x_hs}) ? 1 : 0;
     return 0;
 }
@@ -1868,8 +958,11 @@ int vq_similarities_f32(const vq_args *a, float *sims, int64_t sims_rs, int64_t 
     const int DP = padded_dim(a->D);
     // rows wider than 512 dims: the sliced MFMA sweep when the caller provides its workspace (vq_workspace_bytes_wide),
     // else the one-thread-per-entry kernel
-    if (DP == 0 && !(a->flags & VQ_F_FORCE_SIMPLE) && a->packed && wide_workspace_ok(a))
-        return run_wide(a, 0, nullptr, sims, sims_rs, sims_hs, s);
+    if (DP == 0 && !(a->flags & VQ_F_FORCE_SIMPLE) && a->packed) {
+        const WidePlan w = wide_plan(a->H, a->M, a->K, a->D);
+        if (a->workspace && a->workspace_bytes >= wide_workspace_bytes(a->H, a->M, w))
+            return run_wide(a, w, 0, nullptr, sims, sims_rs, sims_hs, plan_device(), read_switches(), s);
+    }
     if ((a->flags & VQ_F_FORCE_SIMPLE) || DP == 0) {
         if (!a->cb) return fail(VQ_E_BADARG, "vq_similarities: natural codebook required for the scalar kernel");
         const long long n = a->M * (long long)a->K;

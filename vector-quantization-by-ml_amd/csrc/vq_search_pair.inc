@@ -29,6 +29,7 @@ struct PairGeo {
         return q;
     }
 };
+static_assert(PairGeo::max_stages() == kPairMaxStages, "vq_search_plan.h plans with this kernel's stage limit");
 
 // MULTI (round 3): residual stacks (1 eval arithmetic, 2 straight-through arithmetic, as in vq_search_mfma).  After every
 // sweep B publishes the winners, then BOTH waves of a pair gather their half (1 KiB) of the winners' packed rows slice by

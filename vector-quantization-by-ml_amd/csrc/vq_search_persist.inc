@@ -100,10 +100,8 @@ constexpr int kScrChunks = (kScrTileBytes + 1023) / 1024;      // 1-KiB wave cop
 // every workgroup of the pack kernel derives the head's exponents); then the two exponents e_c, e_x (s_c = 2^e_c, s_x = 2^e_x).
 constexpr int kScrTailMcn = 0, kScrTailEc = 1, kScrTailL1 = 2, kScrTailFlag = 3, kScrTailAbs = 4, kScrTailExp = 5;
 constexpr int kScrMaxExp = 62;
-// The room of an image is still that of the bf16-pair image this one replaced (32 * 1040 + 128 bytes per tile and 4 behind):
-// vq_screen_image_bytes is part of the ABI and callers have sized buffers by it.  The image uses the front of the room; the
-// rest is unused and never read.
-constexpr int kScrTileRoom = kTileCodes * 1040 + 128;
+// The room of an image (kScrTileRoom per tile and 4 bytes behind, scr_image_bytes: vq_search_plan.h) is still that of the
+// bf16-pair image this one replaced.  The image uses the front of the room; the rest is unused and never read.
 static_assert(kScrChunks * 1024 + 4 * kScrTailExp + 8 <= kScrTileRoom + 4, "tiles, over-copy and tail fit the room of one tile");
 // the MFMA group (of 16 per sub-tile) after which waves 4..7 run the sweep's epilogue; waves 0..3 run it after group 0
 // (8 = half a sub-tile; profiles/cfg2_stagger.md has the figures of 5, 6, 8, 10, 12 and 14, profiles/cfg2_tagged_keys.md
@@ -116,7 +114,6 @@ constexpr int kScrLateGroup = VQ_SCR_LATE_GROUP;
 #ifndef VQ_SCR_PF
 #define VQ_SCR_PF 3
 #endif
-inline long long scr_image_bytes(int ntiles) { return ((long long)ntiles * kScrTileRoom + 4ll * ntiles + 255) / 256 * 256; }
 #include "vq_resolve_plan.h"
 #include "vq_scr_keys.h"
 // The control block behind the images (SearchParams::scr_count points at it), 32-bit words: [0] rows on the full-search list,
@@ -124,8 +121,7 @@ inline long long scr_image_bytes(int ntiles) { return ((long long)ntiles * kScrT
 // reads them: tests and diagnostics do); from word kScrRowTicketWord on one ticket per split full-search row, and from
 // kScrSlotWord on kResolveMaxSplit 8-byte result slots for each (vq_resolve_plan.h).  vq_pack_scr_kernel zeroes the block; the
 // second pass leaves words 0..2 and every ticket zero again (vq_resolve_rows_kernel), so an image that outlives the call needs
-// no per-call zeroing.
-constexpr int kScrCtrlBytes = 16384;
+// no per-call zeroing.  (kScrCtrlBytes: vq_search_plan.h)
 constexpr int kScrTicketWord = 2, kScrLastCountsWord = 4, kScrRowTicketWord = 8;
 constexpr int kScrSlotWord = kScrRowTicketWord + (int)kResolveMaxSplitRows;
 static_assert(kScrSlotWord % 2 == 0 && (kScrSlotWord + 2 * (int)(kResolveMaxSplitRows * kResolveMaxSplit)) * 4 <= kScrCtrlBytes,

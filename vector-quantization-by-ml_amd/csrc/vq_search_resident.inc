@@ -28,13 +28,10 @@ struct ResGeo {
     static constexpr int CPS = DP >= 128 ? 1 : (32 / RPI + 7) / 8;  // copy accesses per sub-tile: everything is hidden from 8
                                                    // sub-tiles on (Dp = 128: from 16 on -- registers)
     static constexpr int RPSTEP = RPI * CPS;       // rows per copy step
-    // LDS: image | 8 waves x nbuf slabs | winners of two blocks.  nbuf = NSLAB (a whole block of rows in flight per wave) when
-    // that fits beside the image, else 1
-    static constexpr size_t lds_bytes(int img_floats, int nbuf) { return ((size_t)img_floats + 8 * nbuf * SLAB_F) * 4 + 2 * 8 * 32 * 4; }
+    // LDS: image | 8 waves x nbuf slabs | winners of two blocks (resident_lds_bytes, vq_search_plan.h).  nbuf = NSLAB (a whole
+    // block of rows in flight per wave) when that fits beside the image, else 1 (resident_buffers)
+    static_assert(resident_lds_bytes(0, 1) == (size_t)8 * SLAB_F * 4 + 2 * 8 * 32 * 4, "vq_search_plan.h sizes this kernel's LDS");
 };
-
-// floats of LDS the image of K codes takes: whole 1-KiB wave copies (the over-copy stays inside the image's slack)
-inline int resident_image_floats(int K, int DP) { return round_up(round_up(K, kTileCodes * sub_tiles(DP)) * (DP + 4), 256); }
 
 // global_load_lds_dwordx4: 16 bytes per lane from src + OFF (an instruction immediate) -> LDS at lds_dst + lane * 16.
 // The hardware adds the immediate to BOTH addresses (memory and LDS), so the LDS base handed to the instruction is
