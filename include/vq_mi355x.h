@@ -206,6 +206,27 @@ int vq_quantize_backward_f32(const vq_args *a, const float *grad_out, int64_t go
                              float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream);
 
 /*
+ * The rotation trick (Fifty et al., "Restructuring Vector Quantization with the Rotation Trick", arXiv 2410.06424, section
+ * 4.2): backward of the quantize step with respect to x when the straight-through estimator is replaced by the rotation
+ * and rescaling that carries each row onto its code.  The forward is vq_quantize_f32 with VQ_F_STE, unchanged.  For one
+ * stage with input row r (the residual that stage quantized), selected code c = cb[idx] and eps = 1e-6:
+ *   a = max(|r|, eps)   b = max(|c|, eps)   u = r / a   qh = c / b   s = u + qh   w = s / max(|s|, eps)
+ *   lam = |c| / a                                        (numerator unclamped)
+ *   rot(r) = lam * (r - 2 (r.w) w + 2 (r.u) qh)          (u, qh, w, lam constants of autograd; the value is c)
+ *   d/dr :  g  ->  lam * (g - 2 (g.w) w + 2 (g.qh) u)
+ * and every residual of a stack is x minus detached terms, so one pass computes
+ *   grad_x = sum_q lam_q (g - 2 (g.w_q) w_q + 2 (g.qh_q) u_q) + sum_q 2 * grad_sq_err[q] * (r_q - c_q[idx_q]),  g = grad_out.
+ * Degenerate rows follow the formula and stay finite: c = 0 gives a zero rotation term, c = -r gives s = 0 and w = 0,
+ * r = 0 gives u = 0 and lam = |c| * 1e6.  The codes receive no gradient through the output.
+ * Arguments as vq_quantize_backward_f32: a->x (strided rows and heads), a->cb (cb_qs = 0: shared codebook), a->idx as
+ * written by the forward (any strides), H, M, D, Q, flags (VQ_F_STE: the residual chain is recomputed with the forward's
+ * rule quant = r + (c - r); VQ_F_SQERR_PER_HEAD: grad_sq_err is [H][Q]); grad_out and grad_sq_err may each be NULL.
+ * D <= 1024 (the row is held in registers; wider rows: VQ_E_UNSUPPORTED).  M == 0 returns 0 without a launch.
+ */
+int vq_rotate_backward_f32(const vq_args *a, const float *grad_out, int64_t go_rs, int64_t go_hs, const double *grad_sq_err,
+                           float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream);
+
+/*
  * Training-state step that FOLLOWS the hot path -- exponential-moving-average codebook update.
  * vq_ema_accumulate_f32: counts[h*K + k] += 1 and sums[(h*K + k)*D + d] += x[h, m, d] for every row m assigned to
  *   code k = idx[h*idx_hs + m*idx_rs] (rows with mask[h*M + m] == 0 are skipped; mask may be NULL).  Rows whose index is

@@ -37,6 +37,8 @@
 //                        backward, codebook diversity loss, orthogonal regularisation loss, the cross-entropy loss's codes
 //                        gradient; the row / index packers and the split reductions
 //   vq_finalize_ema.inc scalar fallback search, finalize-from-keys, loss reduction, EMA codebook update
+//   vq_rotate.inc        the rotation trick: backward of the quantize step with the rotation-and-rescale gradient, one wave per
+//                        row with the row in registers (vq_rotate_backward_f32)
 //   vq_lfq.inc           lookup-free quantization: sign quantizer, factorised entropy loss forward / backward (stage axis)
 //   vq_rlfq.inc          residual LFQ: every stage's quantize step in one pass (residual in registers), its backward
 //   vq_fsq.inc           finite scalar quantization (FSQ / residual FSQ): every stage of every group in one pass, its
@@ -112,6 +114,7 @@ using namespace vqi;  // (vq_search_plan.h: the geometry the kernels share with 
 #include "vq_gumbel.inc"
 #if VQ_OWN(0)
 #include "vq_finalize_ema.inc"
+#include "vq_rotate.inc"
 #include "vq_expire.inc"
 #include "vq_lfq.inc"
 #include "vq_rlfq.inc"
@@ -732,6 +735,44 @@ int vq_quantize_backward_f32(const vq_args *a, const float *grad_out, int64_t go
     long long blocks = (a->M + 3) / 4;
     if (blocks > 8192) blocks = 8192;
     return launch<vq_quantize_backward_kernel>(dim3((unsigned)blocks, (unsigned)a->H), dim3(256), 0, (hipStream_t)stream, "vq_quantize_backward launch", p);
+}
+
+int vq_rotate_backward_f32(const vq_args *a, const float *grad_out, int64_t go_rs, int64_t go_hs, const double *grad_sq_err,
+                           float *grad_x, int64_t gx_rs, int64_t gx_hs, void *stream) {
+    int rc = check_common(a);
+    if (rc) return rc;
+    if (a->M == 0) return 0;
+    if (!a->cb || !a->idx || !grad_x) return fail(VQ_E_BADARG, "vq_rotate_backward: cb / idx / grad_x is null");
+    if (a->D > kRotateMaxDim) return fail(VQ_E_UNSUPPORTED, "vq_rotate_backward: rows of more than 1024 dims (the row is held in registers)");
+    QuantBwdParams p;
+    memset(&p, 0, sizeof(p));
+    p.x = a->x; p.x_rs = a->x_rs; p.x_hs = a->x_hs;
+    p.cb = a->cb; p.cb_hs = a->cb_hs; p.cb_qs = a->cb_qs;
+    p.idx = (const long long *)a->idx; p.idx_rs = a->idx_rs; p.idx_hs = a->idx_hs; p.idx_qs = a->idx_qs;
+    p.go = grad_out; p.go_rs = go_rs; p.go_hs = go_hs;
+    p.g_err = grad_sq_err;
+    p.g_err_hs = (a->flags & VQ_F_SQERR_PER_HEAD) ? a->Q : 0;
+    p.gx = grad_x; p.gx_rs = gx_rs; p.gx_hs = gx_hs;
+    p.M = a->M; p.D = a->D; p.Q = a->Q; p.ste = (a->flags & VQ_F_STE) ? 1 : 0;
+    p.vec = (vec4_ok(a->x, {a->D, a->x_rs, a->x_hs}) && vec4_ok(grad_x, {gx_rs, gx_hs}) && vec4_ok(a->cb, {a->cb_hs, a->cb_qs}) &&
+             (!grad_out || vec4_ok(grad_out, {go_rs, go_hs}))) ? 1 : 0;
+    long long blocks = (a->M + 3) / 4;
+    if (blocks > 8192) blocks = 8192;
+    const dim3 grid((unsigned)blocks, (unsigned)a->H);
+    hipStream_t s = (hipStream_t)stream;
+    const char *what = "vq_rotate_backward launch";
+    // the row in registers: N slots of V per lane, the smallest variant that holds D
+    const int slots = p.vec ? (a->D + 255) / 256 : (a->D + 63) / 64;
+    if (p.vec) {
+        if (slots <= 1) return launch<vq_rotate_backward_kernel<f32x4, 1>>(grid, dim3(256), 0, s, what, p);
+        if (slots <= 2) return launch<vq_rotate_backward_kernel<f32x4, 2>>(grid, dim3(256), 0, s, what, p);
+        return launch<vq_rotate_backward_kernel<f32x4, 4>>(grid, dim3(256), 0, s, what, p);
+    }
+    if (slots <= 1) return launch<vq_rotate_backward_kernel<float, 1>>(grid, dim3(256), 0, s, what, p);
+    if (slots <= 2) return launch<vq_rotate_backward_kernel<float, 2>>(grid, dim3(256), 0, s, what, p);
+    if (slots <= 4) return launch<vq_rotate_backward_kernel<float, 4>>(grid, dim3(256), 0, s, what, p);
+    if (slots <= 8) return launch<vq_rotate_backward_kernel<float, 8>>(grid, dim3(256), 0, s, what, p);
+    return launch<vq_rotate_backward_kernel<float, 16>>(grid, dim3(256), 0, s, what, p);
 }
 
 // Owner-computes launch plan: a wave owns cw codes (8 KiB of partial sums) and one of row_blocks contiguous row ranges

@@ -438,14 +438,16 @@ class Codebook(nn.Module):
     # ------------------------------------------------------------------ the hot path
     def quantize_flat(self, flat: torch.Tensor, *, ste: bool = False, want_sq_err: bool = False,
                       codebook_grad_from_err: bool = False, out=None, idx=None, want_lse: bool = False,
-                      frozen: bool = False):
+                      frozen: bool = False, rotate: bool = False):
         """flat [h, M, D] (strided rows fine) -> (out [h, M, D], idx [h, M] int64, sq_err [1] float64 | None).
+        ``rotate``: with ``ste``, the rows receive the rotation trick's gradient of the output instead of the
+        straight-through one (search.quantize_rows); nothing that is returned changes.
         ``want_lse``: a fourth element (lse [h, M], target_logit [h, M]) -- log-sum-exp of the row's similarities and the
         similarity of the chosen code, from the same sweep -- or None when the sampling is stochastic.
         ``frozen``: the caller will NOT run the EMA update after this search (freeze_codebook)."""
         if self._stochastic_requested():
             res = self._quantize_stochastic(flat, ste=ste, want_sq_err=want_sq_err,
-                                            codebook_grad_from_err=codebook_grad_from_err, idx=idx)
+                                            codebook_grad_from_err=codebook_grad_from_err, idx=idx, rotate=rotate)
             return (*res, None) if want_lse else res
         codes = self.effective_codes()
         packed = self.packed_codes()
@@ -468,7 +470,7 @@ class Codebook(nn.Module):
         try:
             res = search.quantize_rows(flat, codes[:, None], metric=self.metric, ste=ste, want_sq_err=want_sq_err,
                                        codebook_grad_from_err=codebook_grad_from_err, out=out, idx=idx, want_lse=lse_here,
-                                       packed=packed, screen=screen)
+                                       packed=packed, screen=screen, rotate=rotate)
         except Exception:
             self._screen = {}  # a call that failed may have left its counts behind in the image
             raise
@@ -508,14 +510,14 @@ class Codebook(nn.Module):
         out = x + (picked - x).detach() if ste else picked
         return out, ind, sq_err
 
-    def _quantize_stochastic(self, flat, *, ste, want_sq_err, codebook_grad_from_err, idx=None):
+    def _quantize_stochastic(self, flat, *, ste, want_sq_err, codebook_grad_from_err, idx=None, rotate=False):
         """Gumbel-max sampling of the code (utils/general.py:106-129): ind = argmax(similarities / temperature + g),
         g = -log(-log(u)).  RNG-dependent, so no parity with the reference's draws is possible.  Rows of up to 512 dims:
         ONE native sweep (vq_gumbel_sample_f32) that makes the noise in registers from a seed drawn on the device from torch's
         generator -- nothing of [h, M, K] exists.  Wider rows, backends without the sweep and VQ_NO_FUSED_SAMPLE=1 in the
         environment (A/B measurements): similarities from the native kernel in bounded row chunks, noise from torch's generator.
         The straight-through / reinmax relaxations are provided for the argmax selection (_quantize_relaxed), not for
-        sampled codes."""
+        sampled codes.  ``rotate``: the straight-through output carries the rotation trick's gradient, for the sampled codes."""
         import os
 
         from . import gumbel as gumbel_mod
@@ -553,7 +555,10 @@ class Codebook(nn.Module):
         if want_sq_err:
             target = picked if codebook_grad_from_err else picked.detach()
             sq_err = ((target - x) ** 2).sum(dtype=torch.float64).reshape(1)
-        out = x + (picked - x).detach() if ste else picked
+        if ste and rotate:
+            out = search.rotate_ste(x, picked)
+        else:
+            out = x + (picked - x).detach() if ste else picked
         return out, ind, sq_err
 
     def similarities(self, flat: torch.Tensor) -> torch.Tensor:

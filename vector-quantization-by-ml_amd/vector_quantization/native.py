@@ -75,6 +75,7 @@ _SIGNATURES = {
     "vq_finalize_keys_f32": (_int, (_ap, _vp, _vp)),
     "vq_finalize_key_planes_f32": (_int, (_ap, _vp, _int, _vp)),
     "vq_quantize_backward_f32": (_int, (_ap, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp)),
+    "vq_rotate_backward_f32": (_int, (_ap, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp)),
     "vq_ema_accumulate_f32": (_int, (_vp, _i64, _i64, _vp, _i64, _i64, _vp, _int, _i64, _int, _int, _vp, _vp, _vp)),
     "vq_ema_det_workspace_bytes": (_i64, (_int, _i64, _int, _int)),
     "vq_ema_accumulate_det_f32": (_int, (_vp, _i64, _i64, _vp, _i64, _i64, _vp, _int, _i64, _int, _int, _vp, _vp, _vp, _i64,
@@ -1137,7 +1138,7 @@ def gumbel_noise(seed: torch.Tensor, H: int, M: int, K: int, want_bits: bool = F
 
 def quantize_backward(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor, grad_out: torch.Tensor | None,
                       grad_sq_err: torch.Tensor | None, *, ste: bool, stages_share_codebook: bool = False,
-                      sq_err_per_head: bool = False) -> torch.Tensor:
+                      sq_err_per_head: bool = False, _entry: str = "vq_quantize_backward_f32") -> torch.Tensor:
     """d/dx of the quantize step in one pass: x [H, M, D] (strided rows ok), cb [H, Q|1, K, D], idx [H, M, Q] (any
     strides), grad_out [H, M, D] | None, grad_sq_err [Q] float64 | None  ->  grad_x [H, M, D] contiguous."""
     _require_gpu(x, cb, idx, grad_out, grad_sq_err)
@@ -1158,8 +1159,22 @@ def quantize_backward(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor, grad
     if grad_sq_err is not None:
         grad_sq_err = grad_sq_err.to(torch.float64).contiguous()
         assert grad_sq_err.numel() == (H * Q if sq_err_per_head else Q)
-    _call("vq_quantize_backward_f32", x.device, a, _ptr(grad_out), go_rs, go_hs, _ptr(grad_sq_err), gx.data_ptr(), D, M * D)
+    _call(_entry, x.device, a, _ptr(grad_out), go_rs, go_hs, _ptr(grad_sq_err), gx.data_ptr(), D, M * D)
     return gx
+
+
+ROTATE_MAX_DIM = 1024  # vq_rotate_backward_f32: the row is held in registers
+
+
+def rotate_backward(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor, grad_out: torch.Tensor | None,
+                    grad_sq_err: torch.Tensor | None, *, ste: bool = True, stages_share_codebook: bool = False,
+                    sq_err_per_head: bool = False) -> torch.Tensor:
+    """d/dx of the quantize step under the rotation trick in one pass (vq_rotate_backward_f32; the formula is in
+    include/vq_mi355x.h): the arguments and the result of ``quantize_backward``, D <= ROTATE_MAX_DIM.  ``ste`` selects the
+    rule the residual chain is recomputed with (the training forward's: True)."""
+    assert x.shape[-1] <= ROTATE_MAX_DIM, f"rotate_backward: rows of up to {ROTATE_MAX_DIM} dims"
+    return quantize_backward(x, cb, idx, grad_out, grad_sq_err, ste=ste, stages_share_codebook=stages_share_codebook,
+                             sq_err_per_head=sq_err_per_head, _entry="vq_rotate_backward_f32")
 
 
 def ema_accumulate_residual(x: torch.Tensor, cb: torch.Tensor, idx: torch.Tensor, *, ste: bool = True,

@@ -19,6 +19,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import losses
+from . import search
 from .codebook import Codebook
 from .params import CodebookParams
 
@@ -93,9 +94,13 @@ class VectorQuantize(nn.Module):
         codebook_shard_group=None,
         codebook_shard_reduction: str = "all_gather",
         codebook_shard_gather: str = "owner",
+        rotation_trick: bool = False,
     ):
         """Arguments up to ``sync_update_v`` are the reference's (vector_quantize_pytorch.py:39-60).  New, keyword-only in
-        spirit: ``codebook_shard_group`` (a process group, or True for the default group) shards the codebook's K codes over
+        spirit: ``rotation_trick`` (Fifty et al., arXiv 2410.06424, section 4.2) replaces the straight-through gradient of the
+        training forward by the rotation and rescaling that carries each row onto its code -- the forward and everything it
+        returns are unchanged, only ``x.grad`` differs (one fused native backward, search.rotate_backward_rows); eval ignores
+        it.  Also new: ``codebook_shard_group`` (a process group, or True for the default group) shards the codebook's K codes over
         the ranks -- ``codebook_params.codebook_size`` stays the GLOBAL K, ``_codebook`` (and the checkpoint) hold this
         rank's ``[K / G, D]`` rows, every rank sees the same tokens, and the forward is shard-local search -> packed
         (distance, index) keys -> one collective (``codebook_shard_reduction``: "all_gather" + local min, one hop over all
@@ -138,6 +143,22 @@ class VectorQuantize(nn.Module):
             "learnable codebook must be turned on"
         )
         self.sync_update_v = sync_update_v
+
+        self.rotation_trick = bool(rotation_trick)
+        if self.rotation_trick:
+            g = codebook_params.gumbel_params
+            g = asdict(g) if hasattr(g, "__dataclass_fields__") else dict(g or {})
+            if g.get("straight_through", False) or g.get("reinmax", False):
+                raise ValueError("rotation_trick and GumbelParams(straight_through=True) / reinmax both define the gradient of the "
+                                 "output: choose one")
+            if sync_update_v > 0.0:
+                raise ValueError("rotation_trick and sync_update_v > 0 both define the gradient of the output: choose one")
+            not_built = dict(codebook_shard_group=codebook_shard_group is not None and codebook_shard_group is not False,
+                             in_place_codebook_optimizer=in_place_codebook_optimizer is not None,
+                             use_affine=codebook_params.use_affine)
+            bad = [k for k, v in not_built.items() if v]
+            if bad:
+                raise NotImplementedError(f"rotation_trick is not provided together with {bad}")
 
         # ---- codebook sharded over the ranks of a process group (new capability: SURVEY 8e, BASELINE configs[4])
         self.shard_group = None
@@ -391,6 +412,7 @@ class VectorQuantize(nn.Module):
         commit_loss = diversity_loss = orthogonal_loss = inplace_loss = self.zero
         cb_grad_from_err = self.learnable_codebook and not freeze_codebook
         will_update = training and cb.ema_update and not freeze_codebook
+        rotate = self.rotation_trick and training and torch.is_grad_enabled()  # (eval: the flag is ignored)
 
         if self.in_place_codebook_optimizer is not None and training and not freeze_codebook:
             # vector_quantize_pytorch.py:234-259: one optimizer step on mse(quantize, x) with respect to the codebook,
@@ -436,7 +458,8 @@ class VectorQuantize(nn.Module):
             # the one native launch: search + gather + straight-through + squared error
             out, idx, sq_err, *rest = cb.quantize_flat(flat, ste=training, want_sq_err=want_sq_err,
                                                        codebook_grad_from_err=cb_grad_from_err, out=out_view,
-                                                       idx=idx_view, want_lse=ce_from_search, frozen=freeze_codebook)
+                                                       idx=idx_view, want_lse=ce_from_search, frozen=freeze_codebook,
+                                                       rotate=rotate)
             ce_stats = rest[0] if rest else None
             if want_sq_err:
                 commit_loss = (sq_err[0] / flat.numel()).to(torch.float32)
@@ -448,7 +471,9 @@ class VectorQuantize(nn.Module):
                 target = out if cb_grad_from_err else out.detach()
                 commit_loss = ((target - flat) ** 2)[flat_mask].mean()
             if training:
-                out = flat + (out - flat).detach()
+                # (rotate: every row gets the rotated gradient here; the masked-out rows' output is replaced by the input
+                # at the end of this forward, so they keep the gradient they have without the trick)
+                out = search.rotate_ste(flat, out) if rotate else flat + (out - flat).detach()
         if training and wide_input:
             out = out.double()
         if training and self.sync_update_v > 0.0:

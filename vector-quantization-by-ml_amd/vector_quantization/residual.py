@@ -81,6 +81,8 @@ def _mask_fusable(layers, x, mask, groups: int = 1) -> bool:
     a mask one flag per row and no device-side expiry (its kernel rebuilds r_q from the chain and does not know the mask)."""
     if search.masked_backend() is None:
         return False
+    if mask is not None and any(layer.rotation_trick and layer.training for layer in layers):
+        return False  # the rotation trick with a mask: the layer loop, each layer's one-stage backward is the fused kernel
     if mask is None:
         # quantize dropout on image / video input: the reference's own index shapes do not stack there
         # (residual_vq.py:198-208); the layer loop keeps that behaviour
@@ -212,6 +214,7 @@ class ResidualVQ(nn.Module):
                     or cb.transform_input.__name__ != "_identity"
                     or cb.metric != cb0.metric or cb.embeddings.shape != cb0.embeddings.shape
                     or layer.commitment_weight != first.commitment_weight
+                    or layer.rotation_trick != first.rotation_trick
                     or cb.learnable_codebook
                     # affine codebooks: every layer keeps its own running statistics of ITS residual rows
                     or cb.use_affine
@@ -290,7 +293,8 @@ class ResidualVQ(nn.Module):
             idx_buf = torch.empty((1, rows, Q), dtype=torch.int64, device=flat.device)
         if mask is None:
             out, idx, sq_err = search.quantize_rows(flat, codes, metric=cb0.metric, ste=training, want_sq_err=want_loss,
-                                                    share=self.shared_codebook, idx=idx_buf[..., :run], packed=packed)
+                                                    share=self.shared_codebook, idx=idx_buf[..., :run], packed=packed,
+                                                    rotate=training and first.rotation_trick)
             denom = flat.numel()
         else:
             out, idx, sq_err = search.quantize_rows_masked(flat, codes, row_mask, zero_idx, metric=cb0.metric, ste=training,
@@ -525,7 +529,8 @@ class GroupedResidualVQ(nn.Module):
         row_mask = None
         if mask is None:
             out, idx, sq_err = search.quantize_rows(flat, codes, metric=cb0.metric, ste=training, want_sq_err=want_loss,
-                                                    out=q_buf.permute(1, 0, 2), sq_err_per_head=True, packed=packed)
+                                                    out=q_buf.permute(1, 0, 2), sq_err_per_head=True, packed=packed,
+                                                    rotate=training and first.rotation_trick)
             denom = rows * d
         else:
             row_mask = mask.reshape(rows)

@@ -166,6 +166,15 @@ class _NativeBackend:
                                         sq_err_per_head=sq_err_per_head)
 
     @staticmethod
+    def rotate_backward(x, cb, idx, grad_out, grad_sq_err, *, ste=True, share, sq_err_per_head=False):
+        """d/dx of the quantize step under the rotation trick in one native pass (vq_rotate_backward_f32); None for rows the
+        kernel does not hold in registers (D > native.ROTATE_MAX_DIM: the caller runs the same formulas stage by stage)."""
+        if x.shape[-1] > native.ROTATE_MAX_DIM:
+            return None
+        return native.rotate_backward(x, cb, idx, grad_out, grad_sq_err, ste=ste, stages_share_codebook=share,
+                                      sq_err_per_head=sq_err_per_head)
+
+    @staticmethod
     def residual_mask(x, cb, idx, mask, zero_idx, *, train, want_sq_err, per_group=False, out=None):
         """The mask pass of a residual stack after the fused search (vq_residual_mask_f32): rewrites ``idx`` on the
         masked-out rows -> (out [G, M, D], sq_err over the kept rows | None)."""
@@ -349,6 +358,75 @@ def get_backend():
     return _backend
 
 
+# ------------------------------------------------------------------------------------------------
+# the rotation trick (Fifty et al., arXiv 2410.06424, section 4.2): the gradient of the quantize step with respect to x
+# ------------------------------------------------------------------------------------------------
+ROTATE_EPS = 1e-6
+
+
+def _rotate_stage(r, c, g):
+    """One stage's rotation term lam (g - 2 (g.w) w + 2 (g.qh) u) for rows r, their codes c and the incoming gradient g
+    (all [..., D]); the formula is stated in include/vq_mi355x.h (vq_rotate_backward_f32)."""
+    nc = c.norm(dim=-1, keepdim=True)
+    a, b = r.norm(dim=-1, keepdim=True).clamp(min=ROTATE_EPS), nc.clamp(min=ROTATE_EPS)
+    u, qh = r / a, c / b
+    s = u + qh
+    w = s / s.norm(dim=-1, keepdim=True).clamp(min=ROTATE_EPS)
+    return (nc / a) * (g - 2.0 * (g * w).sum(dim=-1, keepdim=True) * w + 2.0 * (g * qh).sum(dim=-1, keepdim=True) * u)
+
+
+def rotate_backward_rows(x, cb, idx, grad_out, grad_sq_err, *, ste=True, share=False, sq_err_per_head=False):
+    """grad_x [H, M, D] of the quantize step under the rotation trick: x [H, M, D], cb [H, Q | 1, K, D], idx [H, M, Q],
+    grad_out [H, M, D] | None, grad_sq_err [Q] ([H, Q] with ``sq_err_per_head``) | None.  One native pass
+    (``rotate_backward``) where the backend has it; the same formulas in torch, stage by stage, for rows wider than the
+    kernel holds, for a backend without the entry and with VQ_ROTATE_NO_FUSED=1 in the environment (read per call: A/B
+    timing, and tests that compare the two paths in one process).  Neither path waits for the device."""
+    fused = getattr(_backend, "rotate_backward", None)
+    if fused is not None and os.environ.get("VQ_ROTATE_NO_FUSED") != "1":
+        gx = fused(x, cb, idx, grad_out, grad_sq_err, ste=ste, share=share,
+                   **({"sq_err_per_head": True} if sq_err_per_head else {}))
+        if gx is not None:
+            return gx
+    H, M, D = x.shape
+    gx = torch.zeros((H, M, D), dtype=x.dtype, device=x.device)
+    harange = torch.arange(H, device=x.device)[:, None]
+    r = x
+    for q in range(idx.shape[-1]):
+        c = cb[:, 0 if share else q][harange, idx[..., q]]  # [H, M, D]
+        if grad_out is not None:
+            gx = gx + _rotate_stage(r, c, grad_out)
+        if grad_sq_err is not None:
+            w = (grad_sq_err[:, q, None, None] if sq_err_per_head else grad_sq_err[q]).to(x.dtype)
+            gx = gx + 2.0 * w * (r - c)
+        r = r - (r + (c - r) if ste else c)
+    return gx
+
+
+class _RotateSteFn(torch.autograd.Function):
+    """x + (picked - x) as the straight-through output computes it, with the rotation trick's gradient for x; ``picked``
+    (the selected code of every row, [H, M, D]) receives none.  For the callers that gather the codes themselves (sampled
+    codes, masked rows); the fused launches take ``quantize_rows(rotate=True)``."""
+
+    @staticmethod
+    def forward(ctx, x, picked):
+        picked = picked.detach()
+        ctx.save_for_backward(x, picked)
+        return x + (picked - x)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, picked = ctx.saved_tensors
+        H, M, _ = x.shape
+        # every row's code is row m of ``picked``: a one-stage call whose codebook is the gathered rows themselves
+        own = torch.arange(M, device=x.device)[None, :, None].expand(H, M, 1)
+        return rotate_backward_rows(x.detach(), picked[:, None].contiguous(), own, g, None), None
+
+
+def rotate_ste(x: torch.Tensor, picked: torch.Tensor) -> torch.Tensor:
+    """The straight-through output x + (picked - x).detach() [H, M, D] with the rotation trick's gradient (fp32 rows)."""
+    return _RotateSteFn.apply(x, picked)
+
+
 class _QuantizeFn(torch.autograd.Function):
     """Autograd wrapper.  The native op has no backward of its own; the gradients are the reference's:
 
@@ -358,11 +436,14 @@ class _QuantizeFn(torch.autograd.Function):
     * a learnable codebook receives  2 (c_q - r_q)  from sq_err when ``codebook_grad_from_err``
       (commitment loss not detached, vector_quantize_pytorch.py:263-269) and, in eval, the scatter of
       grad_out (out = codebook[idx]).
+    * ``rotate`` (the rotation trick; train only): the forward is the same launch, and the gradient of x is
+      ``rotate_backward_rows``' -- the output passes lam (g - 2 (g.w) w + 2 (g.qh) u) per stage instead of g; the codebook's
+      gradient is unchanged (the commitment-loss term only).
     """
 
     @staticmethod
     def forward(ctx, x, cb, metric, ste, want_sq_err, share, codebook_grad_from_err, out_buf, idx_buf, want_lse=False,
-                per_head=False, packed=None):
+                per_head=False, packed=None, rotate=False):
         extra = {}
         if want_lse:
             extra["want_lse"] = True
@@ -374,7 +455,7 @@ class _QuantizeFn(torch.autograd.Function):
                                 out=out_buf, idx=idx_buf, **extra)
         out, idx, best, sq_err = res[:4]
         ctx.save_for_backward(x, cb, idx)
-        ctx.ste, ctx.share, ctx.cb_err, ctx.per_head = ste, share, codebook_grad_from_err, per_head
+        ctx.ste, ctx.share, ctx.cb_err, ctx.per_head, ctx.rotate = ste, share, codebook_grad_from_err, per_head, rotate
         if sq_err is None:
             sq_err = torch.zeros((x.shape[0], idx.shape[-1]) if per_head else idx.shape[-1], dtype=torch.float64,
                                  device=x.device)
@@ -392,12 +473,18 @@ class _QuantizeFn(torch.autograd.Function):
         gx = gcb = None
         need_x = ctx.needs_input_grad[0]
         need_cb = ctx.needs_input_grad[1]
+        if getattr(ctx, "rotate", False) and need_x:
+            gx = rotate_backward_rows(x.detach(), cb.detach(), idx, g_out, g_err, ste=ctx.ste, share=ctx.share,
+                                      sq_err_per_head=ctx.per_head)
+            if not need_cb:
+                return gx, None, None, None, None, None, None, None, None, None, None, None, None
+            need_x = False  # (the loop below then makes the codebook's gradient only)
         fused = getattr(_backend, "quantize_backward", None)
         if fused is not None and need_x and not need_cb:
             # one pass over x / grad_out; no host synchronisation (the torch path below inspects g_err on the host)
             return (fused(x.detach(), cb.detach(), idx, g_out if ctx.ste else None, g_err, ste=ctx.ste, share=ctx.share,
                           **({"sq_err_per_head": True} if ctx.per_head else {})),
-                    None, None, None, None, None, None, None, None, None, None, None)
+                    None, None, None, None, None, None, None, None, None, None, None, None)
         if need_x:
             gx = g_out * float(Q) if ctx.ste else torch.zeros_like(x)
         if need_cb:
@@ -421,14 +508,14 @@ class _QuantizeFn(torch.autograd.Function):
                     gcb[:, 0 if ctx.share else q].index_put_((harange.expand_as(i), i), g_out, accumulate=True)
                 quant = r + (c - r) if ctx.ste else c
                 r = r - quant
-        return gx, gcb, None, None, None, None, None, None, None, None, None, None
+        return gx, gcb, None, None, None, None, None, None, None, None, None, None, None
 
 
 def quantize_rows(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, ste: bool = False,
                   want_sq_err: bool = False, share: bool = False, codebook_grad_from_err: bool = False,
                   out: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None, want_lse: bool = False,
                   sq_err_per_head: bool = False, packed: Optional[torch.Tensor] = None,
-                  screen: Optional[torch.Tensor] = None):
+                  screen: Optional[torch.Tensor] = None, rotate: bool = False):
     """x [H, M, D] (strided rows allowed), cb [H, Q, K, D] contiguous ([H, 1, K, D] when ``share``; the number
     of stages is then ``idx.shape[-1]``).  ``out`` / ``idx`` may be pre-allocated (strided) destination views.
 
@@ -440,7 +527,10 @@ def quantize_rows(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, st
     the native backend packs on every call.
     ``screen``: the cached screen image that goes with ``packed`` (``get_backend().pack_screen``); only a call that needs no
     gradient uses it.
+    ``rotate``: the rotation trick -- with ``ste``, x receives the rotated and rescaled gradient of the output instead of
+    the straight-through one (``rotate_backward_rows``); everything the forward returns is unchanged.
     """
+    assert ste or not rotate, "the rotation trick replaces the straight-through gradient: it needs ste"
     if packed is not None and not getattr(_backend, "uses_packed", False):
         packed = None
     if packed is None or not hasattr(_backend, "pack_screen"):
@@ -458,7 +548,7 @@ def quantize_rows(x: torch.Tensor, cb: torch.Tensor, *, metric: int = EUCLID, st
             x = x.float()  # the reference's x.float() (codebooks.py:354); the native inference launch does it in-kernel
     if needs_grad:
         res = _QuantizeFn.apply(x, cb, metric, ste, want_sq_err, share, codebook_grad_from_err, out, idx, want_lse,
-                                sq_err_per_head, packed)
+                                sq_err_per_head, packed, rotate)
         out, idx, sq_err = res[:3]
         if want_lse:
             return out, idx, (sq_err if want_sq_err else None), dict(best=res[3], lse=res[4])
