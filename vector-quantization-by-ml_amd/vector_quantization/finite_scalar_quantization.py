@@ -22,6 +22,7 @@ from torch import Tensor, int32, nn
 from torch.nn import Module
 
 from . import native
+from .residual_common import rows_contiguous
 
 MAX_FUSED_DIM = native.FSQ_MAX_DIM
 _INT32_MAX = 2**31 - 1
@@ -121,13 +122,6 @@ def fused_quantize(x: Tensor, levels, consts: Tensor, *, prebound: bool, want_id
 def decode_ok(indices: Tensor, levels) -> bool:
     return (indices.is_cuda and not _compiling() and indices.dtype in (torch.int32, torch.int64)
             and 1 <= len(levels) <= MAX_FUSED_DIM)
-
-
-def rows_contiguous(x: Tensor) -> Tensor:
-    """x [G, N, d] with each row's d values contiguous (the kernels' layout; any group and row strides)."""
-    if x.shape[2] > 1 and x.stride(2) != 1:
-        x = x.contiguous()
-    return x
 
 
 class FSQ(Module):

@@ -15,11 +15,18 @@ on ``cut + 1`` stages.  ``VQ_RVQ_NO_FUSED_MASK=1`` in the environment (read per 
 Heterogeneous stacks (per-layer input normalisation, k-means seeding on the first batch, channel-first layers,
 a mask together with device-side expiry) fall back to a per-layer loop in which each layer call is itself a
 native launch.
+
+The fused forward is written once: ``_fused_stack`` runs G homogeneous stacks on rows ``[G, rows, d]`` with the cached stage
+codes (``_stage_codes``) -- search or masked search, EMA step, dead-code expiry -- and ``_stage_losses`` turns its squared
+errors into the loss tensor.  ``ResidualVQ._forward_fused`` (one group, no destination view, one error sum per stage) and
+``GroupedResidualVQ._forward_fused`` (G groups read and written in place, errors per group) are the layout around that call.
+What the VQ, LFQ and FSQ stacks share beyond it -- the dropout draw, stage padding, the grouped loop over the stacks, the
+grouped decode's buffers -- is ``residual_common.py``.
 """
 from __future__ import annotations
 
 import random
-from typing import List, Optional
+from typing import List
 
 import torch
 import torch.distributed as dist
@@ -27,10 +34,7 @@ from torch import nn
 
 from . import search
 from .quantizer import VectorQuantize, _cached_zeros
-
-
-def _round_up(value: int, multiple: int) -> int:
-    return -(-value // multiple) * multiple
+from .residual_common import check_coarse, dropout_cut, grouped_decode_dest, grouped_decode_rows, grouped_fallback, pad_stages
 
 
 def _residual_chain(x: torch.Tensor, codes: torch.Tensor, idx: torch.Tensor, ste: bool) -> List[torch.Tensor]:
@@ -95,6 +99,102 @@ def _mask_fusable(layers, x, mask, groups: int = 1) -> bool:
     return not any(layer._codebook.expire_on_device for layer in layers)
 
 
+def _stage_codes(owner, cbs, lead):
+    """The natural codebooks of ``cbs`` stacked to [*lead, K, D] and their packed images for the fused launch, kept on
+    ``owner._stage_cache`` and rebuilt only when some codes changed (Codebook.codes_state): an inference forward neither
+    re-stacks nor re-packs."""
+    backend = search.get_backend()
+    if torch.compiler.is_compiling():  # traced: stack and pack are nodes of the graph (no identity-keyed cache in a trace)
+        codes = torch.stack([cb.embeddings.detach()[0] for cb in cbs]).unflatten(0, lead)
+        return codes, (backend.pack(codes, cbs[0].metric) if getattr(backend, "uses_packed", False) else None)
+    key = (tuple(cb.codes_state() for cb in cbs), cbs[0].metric, getattr(backend, "name", None))
+    if owner._stage_cache is None or owner._stage_cache[0] != key:
+        with torch.no_grad():
+            codes = torch.stack([cb.embeddings.detach()[0] for cb in cbs]).unflatten(0, lead)
+            packed = None
+            if getattr(backend, "uses_packed", False) and codes.is_cuda:
+                packed = backend.pack(codes, cbs[0].metric)
+        owner._stage_cache = (key, codes, packed)
+    return owner._stage_cache[1], owner._stage_cache[2]
+
+
+def _fused_stack(owner, stacks, flat, stage_codes, row_mask, run, share, freeze_codebook, out=None, idx=None, per_group=False):
+    """The fused forward of ``stacks`` -- G homogeneous ResidualVQ, ``owner`` holding their caches -- on the fp32 rows ``flat``
+    [G, rows, d] with ``stage_codes`` = owner._stage_codes() (fetched by the caller before it allocates its buffers): ONE launch
+    for the stages 0 .. run - 1 of every group; with ``row_mask`` [rows] the search runs on every row and the mask pass
+    (search.quantize_rows_masked) follows.  ``out`` / ``idx`` are destination views or None, ``per_group`` asks for the squared
+    errors per group.  Nothing waits for the device.
+
+    Returns (out [G, rows, d], idx [G, rows, run], sq_err [run] | [G, run] | None) and, in train mode, has done the EMA step of
+    every layer that ran."""
+    stack0 = stacks[0]
+    first = stack0.layers[0]
+    cb0 = first._codebook
+    training = owner.training
+    Q = stack0.num_quantizers
+    codes, packed = stage_codes  # [G, Q, K, d] ([1, 1, K, d] when shared); fusable stacks are not learnable
+    want_loss = training and first.has_commitment_loss
+    zero_idx = None if row_mask is None else _zero_row_indices(owner, codes, packed, cb0.metric, Q)[:, :run]
+    if run < Q and not share:  # quantize dropout: views of the first `run` codebooks and their images
+        codes, packed = codes[:, :run], (packed[:run] if packed is not None else None)
+    if row_mask is None:
+        out, idx, sq_err = search.quantize_rows(flat, codes, metric=cb0.metric, ste=training, want_sq_err=want_loss, share=share,
+                                                out=out, idx=idx, sq_err_per_head=per_group, packed=packed,
+                                                rotate=training and first.rotation_trick)
+    else:
+        out, idx, sq_err = search.quantize_rows_masked(flat, codes, row_mask, zero_idx, metric=cb0.metric, ste=training,
+                                                       want_sq_err=want_loss, share=share, out=out, idx=idx,
+                                                       sq_err_per_head=per_group, packed=packed)
+    if training and not freeze_codebook and cb0.ema_update:
+        with torch.no_grad():
+            chains = {}
+
+            def residual_rows(g, q):
+                if g not in chains:  # only needed when a code expired
+                    stage_codes = (codes[g].expand(run, -1, -1) if share else codes[g]).detach()
+                    if row_mask is None:
+                        chains[g] = _residual_chain(flat[g].detach(), stage_codes, idx[g], ste=True)
+                    else:
+                        chains[g] = _residual_chain_masked(flat[g].detach(), stage_codes, idx[g], row_mask)
+                return chains[g][q][None]
+
+            idx_ema = idx
+            if row_mask is not None:  # an index outside [0, K) ends a row's chain: masked-out rows contribute nothing
+                idx_ema = idx.clone()
+                idx_ema[:, :, 0].masked_fill_(~row_mask[None, :], -1)
+            # one pass rebuilds the residual chain from the indices and scatter-adds every stage's statistics
+            hits, sums = search.get_backend().ema_accumulate_residual(flat.detach(), codes.detach().contiguous(), idx_ema,
+                                                                      ste=True, share=share)
+            for g, stack in enumerate(stacks):
+                for q, layer in zip(range(run), stack.layers):  # (a slice of a ModuleList would build a new module)
+                    cbq = layer._codebook
+                    if cbq.ema_update:
+                        cbq.ema_apply(hits[g:g + 1, q], sums[g:g + 1, q])
+                        if cbq.expire_on_device:  # the kernel rebuilds r_q for the rows it picks, from flat[g] in place: no chain
+                            cbq.reseed_dead_codes((flat[g].detach(), codes[g].detach(), idx[g], q))
+                        else:
+                            cbq.reseed_dead_codes(lambda g=g, q=q: residual_rows(g, q))
+    return out, idx, sq_err
+
+
+def _stage_losses(owner, stacks, flat, row_mask, sq_err, run, shape):
+    """The fp32 commitment losses, ``shape`` = [..., Q], of a fused forward from its squared errors: cached zeros in eval (no fill
+    kernel per inference forward), fresh zeros in train mode without a commitment loss, zero columns for the stages dropout cut."""
+    if not owner.training:
+        return _cached_zeros(owner, "_zero_losses", shape, flat.device)
+    lead, Q = shape[:-1], shape[-1]
+    if sq_err is not None:
+        rows, d = flat.shape[1:]
+        # a mask: the kept rows are counted on the device; no kept row gives NaN, the reference's mean over nothing
+        denom = rows * d if row_mask is None else row_mask.sum() * d
+        losses = (sq_err / denom).to(torch.float32).reshape(*lead, run) * stacks[0].layers[0].commitment_weight
+    else:
+        losses = torch.zeros((*lead, run), dtype=torch.float32, device=flat.device)
+    if run < Q:
+        losses = torch.cat([losses, torch.zeros((*lead, Q - run), dtype=losses.dtype, device=flat.device)], dim=-1)
+    return losses
+
+
 class ResidualVQ(nn.Module):
     """Follows Algorithm 1 of https://arxiv.org/abs/2107.03312 (SoundStream), like the reference."""
 
@@ -142,13 +242,6 @@ class ResidualVQ(nn.Module):
         """[Q, K, D] stack of the per-layer codebooks."""
         return torch.stack([layer._codebook.embeddings[0] for layer in self.layers], dim=0)
 
-    def _check_coarse(self, indices):
-        if indices.shape[-1] < self.num_quantizers:
-            assert self.quantize_dropout > 0.0, (
-                "quantize dropout must be greater than 0 if you wish to reconstruct from a signal with less fine "
-                "quantizations"
-            )
-
     def _decode_tables(self):
         """The codebooks as the fused decode reads them, [1, Q | 1, K, D]: the learnable ones through the autograd graph,
         the others from the stack the fused forward keeps (_stage_codes)."""
@@ -174,14 +267,11 @@ class ResidualVQ(nn.Module):
 
     def get_codes_from_indices(self, indices):
         """indices [b, ..., q] (q may be < Q, -1 = dropped) -> [Q, b, ..., D]."""
-        self._check_coarse(indices)
+        check_coarse(self, indices.shape[-1])
         codes = self._decode_native(indices, want_sum=False)
         if codes is not None:
             return codes
-        q_given = indices.shape[-1]
-        if q_given < self.num_quantizers:
-            pad = indices.new_full((*indices.shape[:-1], self.num_quantizers - q_given), -1)
-            indices = torch.cat([indices, pad], dim=-1)
+        indices, _ = pad_stages(indices, self.num_quantizers)
         dropped = indices < 0
         safe = indices.clamp(min=0)
         books = self.codebooks
@@ -190,7 +280,7 @@ class ResidualVQ(nn.Module):
         return codes.masked_fill(dropped.movedim(-1, 0)[..., None], 0.0)
 
     def get_output_from_indices(self, indices):
-        self._check_coarse(indices)
+        check_coarse(self, indices.shape[-1])
         codes_sum = self._decode_native(indices, want_sum=True)  # nothing of [Q, N, D]: the stages are summed in registers
         if codes_sum is not None:
             return self.project_out(codes_sum)
@@ -250,27 +340,13 @@ class ResidualVQ(nn.Module):
         """Stacked natural codebooks [1, Q, K, D] ([1, 1, K, D] when shared) and their packed images for the fused launch,
         rebuilt only when some layer's codes changed (Codebook.codes_state): an inference forward neither re-stacks nor
         re-packs."""
-        cbs = [self.layers[0]._codebook] if self.shared_codebook else [layer._codebook for layer in self.layers]
-        backend = search.get_backend()
-        if torch.compiler.is_compiling():  # traced: stack and pack are nodes of the graph
-            codes = torch.stack([cb.embeddings.detach()[0] for cb in cbs], dim=0)[None].contiguous()
-            return codes, (backend.pack(codes, cbs[0].metric) if getattr(backend, "uses_packed", False) else None)
-        key = (tuple(cb.codes_state() for cb in cbs), cbs[0].metric, getattr(backend, "name", None))
-        if self._stage_cache is None or self._stage_cache[0] != key:
-            with torch.no_grad():
-                codes = torch.stack([cb.embeddings.detach()[0] for cb in cbs], dim=0)[None].contiguous()
-                packed = None
-                if getattr(backend, "uses_packed", False) and codes.is_cuda:
-                    packed = backend.pack(codes, cbs[0].metric)
-            self._stage_cache = (key, codes, packed)
-        return self._stage_cache[1], self._stage_cache[2]
+        if self.shared_codebook:
+            return _stage_codes(self, [self.layers[0]._codebook], (1, 1))
+        return _stage_codes(self, [layer._codebook for layer in self.layers], (1, self.num_quantizers))
 
     def _forward_fused(self, x, freeze_codebook, mask=None, cut=None):
-        """One launch for the stages 0 .. cut (all of them without quantize dropout); with ``mask`` [b, n] the search runs on
-        every row and the mask pass (search.quantize_rows_masked) follows -- nothing waits for the device in either."""
-        first = self.layers[0]
-        cb0 = first._codebook
-        training = self.training
+        """One launch for the stages 0 .. cut (all of them without quantize dropout): the rows as one group of _fused_stack,
+        which writes the indices of the stages that ran into their columns of the [..., Q] result."""
         lead, d = x.shape[:-1], x.shape[-1]
         flat = x.reshape(1, x.numel() // max(d, 1), d)
         wide_input = flat.dtype == torch.float64  # train mode: the reference's straight-through sums are in the input's width
@@ -278,84 +354,29 @@ class ResidualVQ(nn.Module):
             flat = flat.float()
         Q = self.num_quantizers
         run = Q if cut is None else cut + 1  # the stages that run; the dropped ones report index -1 and a zero loss
-        codes, packed = self._stage_codes()  # [1, Q, K, D] ([1, 1, K, D] when shared); fusable stacks are not learnable
-        want_loss = training and first.has_commitment_loss
         rows = flat.shape[1]
-        row_mask = zero_idx = None
-        if mask is not None:
-            row_mask = mask.reshape(rows)
-            zero_idx = _zero_row_indices(self, codes, packed, cb0.metric, Q)[:, :run]
+        row_mask = None if mask is None else mask.reshape(rows)
+        stage_codes = self._stage_codes()
         if run < Q:
             idx_buf = torch.full((1, rows, Q), -1, dtype=torch.int64, device=flat.device)
-            if not self.shared_codebook:  # views: the first `run` codebooks and their images
-                codes, packed = codes[:, :run], (packed[:run] if packed is not None else None)
         else:
             idx_buf = torch.empty((1, rows, Q), dtype=torch.int64, device=flat.device)
-        if mask is None:
-            out, idx, sq_err = search.quantize_rows(flat, codes, metric=cb0.metric, ste=training, want_sq_err=want_loss,
-                                                    share=self.shared_codebook, idx=idx_buf[..., :run], packed=packed,
-                                                    rotate=training and first.rotation_trick)
-            denom = flat.numel()
-        else:
-            out, idx, sq_err = search.quantize_rows_masked(flat, codes, row_mask, zero_idx, metric=cb0.metric, ste=training,
-                                                           want_sq_err=want_loss, share=self.shared_codebook,
-                                                           idx=idx_buf[..., :run], packed=packed)
-            denom = row_mask.sum() * d  # on the device: no kept row gives NaN, the reference's mean over nothing
-        if want_loss:
-            losses = (sq_err / denom).to(torch.float32)[None, :] * first.commitment_weight
-        elif training:
-            losses = torch.zeros((1, run), dtype=torch.float32, device=flat.device)
-        else:
-            losses = _cached_zeros(self, "_zero_losses", (1, Q), flat.device)  # no fill kernel per inference forward
-        if run < Q:  # (train mode only)
-            losses = torch.cat([losses, torch.zeros((1, Q - run), dtype=losses.dtype, device=flat.device)], dim=1)
-
-        if training and not freeze_codebook and cb0.ema_update:
-            with torch.no_grad():
-                stage_codes = codes[0].expand(run, -1, -1) if self.shared_codebook else codes[0]
-                chain = []
-
-                def residual_rows(q):
-                    if not chain:  # only needed when a code expired
-                        if row_mask is None:
-                            chain.extend(_residual_chain(flat[0].detach(), stage_codes.detach(), idx[0], ste=True))
-                        else:
-                            chain.extend(_residual_chain_masked(flat[0].detach(), stage_codes.detach(), idx[0], row_mask))
-                    return chain[q][None]
-
-                idx_ema = idx
-                if row_mask is not None:  # an index outside [0, K) ends a row's chain: masked-out rows contribute nothing
-                    idx_ema = idx.clone()
-                    idx_ema[0, :, 0].masked_fill_(~row_mask, -1)
-                # one pass rebuilds the residual chain from the indices and scatter-adds every stage's statistics
-                hits, sums = search.get_backend().ema_accumulate_residual(flat.detach(), codes.detach().contiguous(), idx_ema,
-                                                                          ste=True, share=self.shared_codebook)
-                for q, layer in enumerate(self.layers[:run]):
-                    layer._codebook.ema_apply(hits[:, q], sums[:, q])
-                    if layer._codebook.expire_on_device:  # the kernel rebuilds r_q for the rows it picks: no chain here
-                        layer._codebook.reseed_dead_codes((flat[0].detach(), codes[0].detach(), idx[0], q))
-                    else:
-                        layer._codebook.reseed_dead_codes(lambda q=q: residual_rows(q))
-        if training and wide_input:
+        out, _, sq_err = _fused_stack(self, (self,), flat, stage_codes, row_mask, run, self.shared_codebook, freeze_codebook,
+                                      idx=idx_buf[..., :run])
+        losses = _stage_losses(self, (self,), flat, row_mask, sq_err, run, (1, Q))
+        if self.training and wide_input:
             out = out.double()
         return out.reshape(*lead, d), idx_buf.reshape(*lead, Q), losses
 
     def _draw_cut(self, x, fixed_seed) -> int:
-        """The last stage that runs under quantize dropout (residual_vq.py:194-207): one draw per forward, from the given
-        seed, from a seed agreed between the replicas, or from the process-wide generator."""
-        Q = self.num_quantizers
-        if fixed_seed is not None:
-            rng = random.Random(fixed_seed)
-        elif dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        """The last stage that runs under quantize dropout (residual_common.dropout_cut): one draw per forward, from the
+        given seed, from a seed agreed between the replicas, or from the process-wide generator."""
+        rng = fixed_seed
+        if fixed_seed is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             seed = torch.tensor(random.randrange(10_000), device=x.device)
             dist.all_reduce(seed)
-            rng = random.Random(int(seed.item()))
-        else:
-            rng = random
-        cut = rng.randrange(self.quantize_dropout_cutoff_index, Q)
-        if self.quantize_dropout_multiple_of != 1:
-            cut = _round_up(cut + 1, self.quantize_dropout_multiple_of) - 1
-        return cut
+            rng = int(seed.item())
+        return dropout_cut(self.quantize_dropout_cutoff_index, self.num_quantizers, self.quantize_dropout_multiple_of, rng)
 
     def _forward_layers(self, x, mask, freeze_codebook, drop_active, fixed_seed):
         Q = self.num_quantizers
@@ -415,7 +436,7 @@ class GroupedResidualVQ(nn.Module):
                 if e.shape != first.shape or e.dtype != first.dtype or e.device != first.device:
                     return None
         for rvq in self.rvqs:
-            rvq._check_coarse(indices[0])
+            check_coarse(rvq, indices.shape[-1])
         cbs = [layer._codebook for rvq in self.rvqs for layer in rvq.layers]
         if torch.is_grad_enabled() and any(cb.embeddings.requires_grad for cb in cbs):
             return decode, self.codebooks
@@ -426,14 +447,13 @@ class GroupedResidualVQ(nn.Module):
         if uniform is not None:  # [G, Q, b, ..., d] written by one call
             decode, tables = uniform
             G, Q, d = self.groups, tables.shape[1], tables.shape[-1]
-            lead = indices.shape[1:-1]
-            flat = indices.reshape(G, -1, indices.shape[-1])
+            flat, lead = grouped_decode_rows(indices)
             if search.decode_needs_grad(tables):
                 _, codes = search.decode_rows(decode, tables, flat, drop_null=True, want_sum=False, want_all=True)
                 return codes.transpose(0, 1).reshape(G, Q, *lead, d)
-            buf = torch.empty((G, Q, flat.shape[1], d), dtype=torch.float32, device=flat.device)
-            search.decode_rows(decode, tables, flat, drop_null=True, want_sum=False, want_all=True, all_out=buf.transpose(0, 1))
-            return buf.reshape(G, Q, *lead, d)
+            codes, dest = grouped_decode_dest(flat, lead, d, Q)
+            search.decode_rows(decode, tables, flat, drop_null=True, want_sum=False, want_all=True, all_out=dest)
+            return codes
         return torch.stack(tuple(rvq.get_codes_from_indices(i) for rvq, i in zip(self.rvqs, indices)))
 
     def get_output_from_indices(self, indices):
@@ -441,14 +461,13 @@ class GroupedResidualVQ(nn.Module):
         if uniform is not None:  # the groups' sums written side by side on the feature axis by one call
             decode, tables = uniform
             G, d = self.groups, tables.shape[-1]
-            lead = indices.shape[1:-1]
-            flat = indices.reshape(G, -1, indices.shape[-1])
+            flat, lead = grouped_decode_rows(indices)
             if search.decode_needs_grad(tables):
                 out, _ = search.decode_rows(decode, tables, flat, drop_null=True)
                 return out.transpose(0, 1).reshape(*lead, G * d)
-            buf = torch.empty((flat.shape[1], G, d), dtype=torch.float32, device=flat.device)
-            search.decode_rows(decode, tables, flat, drop_null=True, sum_out=buf.transpose(0, 1))
-            return buf.reshape(*lead, G * d)
+            out, dest = grouped_decode_dest(flat, lead, d)
+            search.decode_rows(decode, tables, flat, drop_null=True, sum_out=dest)
+            return out
         outs = tuple(rvq.get_output_from_indices(i) for rvq, i in zip(self.rvqs, indices))
         return torch.cat(outs, dim=self.split_dim)
 
@@ -476,102 +495,34 @@ class GroupedResidualVQ(nn.Module):
         assert indices is None or len(indices) == 0, "cross-entropy to given indices is not supported"
         if self._fusable(x, mask):
             return self._forward_fused(x, return_all_codes, freeze_codebook, mask)
-        chunks = x.chunk(self.groups, dim=self.split_dim)
-        seed = random.randint(0, int(1e7))
-        outs = tuple(
-            rvq(chunk, mask=mask, return_all_codes=return_all_codes, freeze_codebook=freeze_codebook,
-                rand_quantize_dropout_fixed_seed=seed)
-            for rvq, chunk in zip(self.rvqs, chunks)
-        )
-        quantized, all_indices, losses, *maybe_codes = tuple(zip(*outs))
-        ret = (torch.cat(quantized, dim=self.split_dim), torch.stack(all_indices), torch.stack(losses))
-        if maybe_codes:
-            ret = (*ret, torch.stack(maybe_codes[0]))
-        return ret
+        seed = random.randint(0, int(1e7))  # (on this path only: the fused one consumes nothing of `random`)
+        return grouped_fallback(self.rvqs, x, self.split_dim, seed, return_all_codes, torch.stack, mask=mask,
+                                freeze_codebook=freeze_codebook)
 
     def _stage_codes(self):
         """[G, Q, K, d] natural codebooks + packed images of the one fused launch, rebuilt only when some codes changed."""
         cbs = [layer._codebook for rvq in self.rvqs for layer in rvq.layers]
-        backend = search.get_backend()
-        if torch.compiler.is_compiling():  # traced: stack and pack are nodes of the graph (no identity-keyed cache in a trace)
-            codes = torch.stack([torch.stack([layer._codebook.embeddings.detach()[0] for layer in rvq.layers], dim=0)
-                                 for rvq in self.rvqs], dim=0).contiguous()
-            return codes, (backend.pack(codes, cbs[0].metric) if getattr(backend, "uses_packed", False) else None)
-        key = (tuple(cb.codes_state() for cb in cbs), cbs[0].metric, getattr(backend, "name", None))
-        if self._stage_cache is None or self._stage_cache[0] != key:
-            with torch.no_grad():
-                codes = torch.stack([torch.stack([layer._codebook.embeddings.detach()[0] for layer in rvq.layers], dim=0)
-                                     for rvq in self.rvqs], dim=0).contiguous()
-                packed = None
-                if getattr(backend, "uses_packed", False) and codes.is_cuda:
-                    packed = backend.pack(codes, cbs[0].metric)
-            self._stage_cache = (key, codes, packed)
-        return self._stage_cache[1], self._stage_cache[2]
+        return _stage_codes(self, cbs, (self.groups, len(cbs) // self.groups))
 
     def _forward_fused(self, x, return_all_codes, freeze_codebook, mask=None):
-        """Groups on the kernel's head axis: x [..., G*d] is searched in place as a [G, rows, d] view; ``mask`` [b, n] is shared by
-        the groups (the search on every row, then one mask pass for all groups)."""
+        """Groups on the kernel's head axis: x [..., G*d] is searched in place as a [G, rows, d] view and the result written as
+        its [rows, G, d] counterpart, both by _fused_stack; ``mask`` [b, n] is shared by the groups, and squared errors come back
+        per group and stage."""
         G = self.groups
-        r0 = self.rvqs[0]
-        Q = r0.num_quantizers
-        first = r0.layers[0]
-        cb0 = first._codebook
+        rvqs = self.rvqs
         training = self.training
         lead = x.shape[:-1]
         d = self.dim // G
         xc = x if (x.is_contiguous() and x.dtype == torch.float32) else x.contiguous().float()
         rows = xc.numel() // self.dim
         flat = xc.view(rows, G, d).permute(1, 0, 2)
-        codes, packed = self._stage_codes()  # [G, Q, K, d]
-        want_loss = training and first.has_commitment_loss
+        stage_codes = self._stage_codes()  # [G, Q, K, d]
+        Q = stage_codes[0].shape[1]
         q_buf = torch.empty((rows, G, d), dtype=torch.float32, device=xc.device)
-        # one launch for all groups and stages; squared errors come back per group (head) and stage
-        row_mask = None
-        if mask is None:
-            out, idx, sq_err = search.quantize_rows(flat, codes, metric=cb0.metric, ste=training, want_sq_err=want_loss,
-                                                    out=q_buf.permute(1, 0, 2), sq_err_per_head=True, packed=packed,
-                                                    rotate=training and first.rotation_trick)
-            denom = rows * d
-        else:
-            row_mask = mask.reshape(rows)
-            zero_idx = _zero_row_indices(self, codes, packed, cb0.metric, Q)
-            out, idx, sq_err = search.quantize_rows_masked(flat, codes, row_mask, zero_idx, metric=cb0.metric, ste=training,
-                                                           want_sq_err=want_loss, out=q_buf.permute(1, 0, 2),
-                                                           sq_err_per_head=True, packed=packed)
-            denom = row_mask.sum() * d  # on the device
-        if want_loss:
-            losses = (sq_err / denom).to(torch.float32)[:, None, :] * first.commitment_weight
-        elif training:
-            losses = torch.zeros((G, 1, Q), dtype=torch.float32, device=xc.device)
-        else:
-            losses = _cached_zeros(self, "_zero_losses", (G, 1, Q), xc.device)
-        if training and not freeze_codebook and cb0.ema_update:
-            with torch.no_grad():
-                chains = {}
-
-                def residual_rows(g, q):
-                    if g not in chains:  # only when a code expired
-                        if row_mask is None:
-                            chains[g] = _residual_chain(flat[g].detach(), codes[g].detach(), idx[g], ste=True)
-                        else:
-                            chains[g] = _residual_chain_masked(flat[g].detach(), codes[g].detach(), idx[g], row_mask)
-                    return chains[g][q][None]
-
-                idx_ema = idx
-                if row_mask is not None:  # an index outside [0, K) ends a row's chain: masked-out rows contribute nothing
-                    idx_ema = idx.clone()
-                    idx_ema[:, :, 0].masked_fill_(~row_mask[None, :], -1)
-                hits, sums = search.get_backend().ema_accumulate_residual(flat.detach(), codes.detach().contiguous(), idx_ema,
-                                                                          ste=True, share=False)
-                for g, rvq in enumerate(self.rvqs):
-                    for q, layer in enumerate(rvq.layers):
-                        cbq = layer._codebook
-                        if cbq.ema_update:
-                            cbq.ema_apply(hits[g:g + 1, q], sums[g:g + 1, q])
-                            if cbq.expire_on_device:  # (flat[g]: a row-strided view of the input, read in place)
-                                cbq.reseed_dead_codes((flat[g].detach(), codes[g].detach(), idx[g], q))
-                            else:
-                                cbq.reseed_dead_codes(lambda g=g, q=q: residual_rows(g, q))
+        row_mask = None if mask is None else mask.reshape(rows)
+        out, idx, sq_err = _fused_stack(self, rvqs, flat, stage_codes, row_mask, Q, False, freeze_codebook,
+                                        out=q_buf.permute(1, 0, 2), per_group=True)
+        losses = _stage_losses(self, rvqs, flat, row_mask, sq_err, Q, (G, 1, Q))
         quantized = out.permute(1, 0, 2).reshape(*lead, self.dim)  # q_buf's memory; keeps the autograd edge of `out`
         if training and x.dtype == torch.float64:
             quantized = quantized.double()

@@ -19,7 +19,6 @@ DESIGN.md section 12 states the accuracy contract.
 from __future__ import annotations
 
 import random
-from math import ceil
 
 import torch
 import torch.nn.functional as F
@@ -28,10 +27,8 @@ from torch.nn import Module
 
 from . import finite_scalar_quantization as _fsq
 from .finite_scalar_quantization import FSQ
-
-
-def _round_up_multiple(num, mult):
-    return ceil(num / mult) * mult
+from .residual_common import (check_coarse, dropout_cut, group_rows_in, group_rows_out, grouped_fallback, pad_stages,
+                              rows_contiguous)
 
 
 def _fused_ok(rvq: "ResidualFSQ", x: torch.Tensor) -> bool:
@@ -42,14 +39,6 @@ def _fused_ok(rvq: "ResidualFSQ", x: torch.Tensor) -> bool:
     probe = x if x.dtype == torch.float32 else x.new_empty((0,), dtype=torch.float32)
     return (_fsq._fused_ok(probe, l0._level_values) and l0.num_codebooks == 1 and not l0.keep_num_codebooks_dim
             and not l0.channel_first and l0.return_indices and not l0.has_projections)
-
-
-def _pad_stages(idx: torch.Tensor, Q: int) -> torch.Tensor:
-    """Dropped stages: int64 indices of -1 (the reference stacks its int32 indices with int64 nulls, so the stack is int64)."""
-    S = idx.shape[-1]
-    if S == Q:
-        return idx
-    return torch.cat([idx.long(), idx.new_full((*idx.shape[:-1], Q - S), -1, dtype=torch.long)], dim=-1)
 
 
 class ResidualFSQ(Module):
@@ -113,10 +102,8 @@ class ResidualFSQ(Module):
         """indices [b, ..., q] -> [b, n, num_quantizers] (pack "b * q", then the -1 padding of coarse indices)."""
         quantize_dim = indices.shape[-1]
         indices = indices.reshape(indices.shape[0], -1, quantize_dim)
+        check_coarse(self, quantize_dim)
         if quantize_dim < self.num_quantizers:
-            assert self.quantize_dropout > 0.0, (
-                "quantize dropout must be greater than 0 if you wish to reconstruct from a signal with less fine quantizations"
-            )
             indices = F.pad(indices, (0, self.num_quantizers - quantize_dim), value=-1)
         return indices
 
@@ -167,11 +154,7 @@ class ResidualFSQ(Module):
         """The last active stage under quantize dropout (None: every stage runs), consuming `random` as the reference."""
         if not (self.training and self.quantize_dropout):
             return None
-        rand = random.Random(seed) if seed is not None else random
-        cut = rand.randrange(self.quantize_dropout_cutoff_index, self.num_quantizers)
-        if self.quantize_dropout_multiple_of != 1:
-            cut = _round_up_multiple(cut + 1, self.quantize_dropout_multiple_of) - 1
-        return cut
+        return dropout_cut(self.quantize_dropout_cutoff_index, self.num_quantizers, self.quantize_dropout_multiple_of, seed)
 
     def _kernel_consts(self, stages):
         consts = _fsq.cached_kernel_consts(self, self.layers[0]._levels, self.scales)
@@ -187,11 +170,11 @@ class ResidualFSQ(Module):
 
         if _fused_ok(self, x):
             d = len(self.levels)
-            xg = _fsq.rows_contiguous(x.float().reshape(1, -1, d))
+            xg = rows_contiguous(x.float().reshape(1, -1, d))
             with torch.autocast(device_type="cuda", enabled=False):
                 out, idx = _fsq.fused_quantize(xg, self.layers[0]._level_values, self._kernel_consts(stages), prebound=True)
             quantized_out = self.project_out(out.reshape(*x.shape[:-1], d))
-            all_indices = _pad_stages(idx.reshape(*x.shape[:-1], stages), num_quant)
+            all_indices, _ = pad_stages(idx.reshape(*x.shape[:-1], stages), num_quant)
         else:
             if not (x.is_cuda or _fsq._compiling()):
                 _fsq.native._require_gpu(x)
@@ -286,26 +269,7 @@ class GroupedResidualFSQ(Module):
         if split_dim == -1 and self._fused_ok(x):
             return self._forward_fused(x, return_all_codes, seed)
 
-        # split the feature dimension into groups
-
-        x = x.chunk(self.groups, dim=split_dim)
-
-        forward_kwargs = dict(return_all_codes=return_all_codes, rand_quantize_dropout_fixed_seed=seed)
-
-        # invoke residual vq on each group
-
-        out = tuple(rvq(chunk, **forward_kwargs) for rvq, chunk in zip(self.rvqs, x))
-        out = tuple(zip(*out))
-
-        # otherwise, get all the zipped outputs and combine them
-
-        quantized, all_indices, *maybe_all_codes = out
-
-        quantized = torch.cat(quantized, dim=split_dim)
-        all_indices = torch.stack(all_indices)
-
-        ret = (quantized, all_indices, *maybe_all_codes)
-        return ret
+        return grouped_fallback(self.rvqs, x, split_dim, seed, return_all_codes, tuple)
 
     def _fused_ok(self, x):
         rvq0 = self.rvqs[0]
@@ -325,20 +289,12 @@ class GroupedResidualFSQ(Module):
         lead = x.shape[:-1]
         d = len(rvq0.levels)
         consts = rvq0._kernel_consts(stages)
-        if rvq0.has_projections:
-            chunks = x.chunk(G, dim=-1)
-            xg = torch.stack([rvq.project_in(chunk).float().reshape(-1, d) for rvq, chunk in zip(self.rvqs, chunks)])
-        else:
-            # the chunk views in place (group stride d, row stride G * d) when each row's values are contiguous
-            xg = _fsq.rows_contiguous(x.float().reshape(-1, G, d).transpose(0, 1))
+        xg, _ = group_rows_in(x, self.rvqs, d, rvq0.has_projections)
         with torch.autocast(device_type="cuda", enabled=False):
             out, idx = _fsq.fused_quantize(xg, rvq0.layers[0]._level_values, consts, prebound=True,
                                            interleave=not rvq0.has_projections)
-        if rvq0.has_projections:
-            quantized = torch.cat([rvq.project_out(out[g].reshape(*lead, d)) for g, rvq in enumerate(self.rvqs)], dim=-1)
-        else:
-            quantized = out.transpose(0, 1).reshape(*lead, G * d)
-        all_indices = _pad_stages(idx.reshape(G, *lead, stages), Q)
+        quantized = group_rows_out(out, self.rvqs, lead, d, rvq0.has_projections)
+        all_indices, _ = pad_stages(idx.reshape(G, *lead, stages), Q)
         ret = (quantized, all_indices)
         if not return_all_codes:
             return ret

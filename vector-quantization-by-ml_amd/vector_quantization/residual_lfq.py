@@ -25,7 +25,7 @@ Decode side.  ``get_codes_from_indices`` and ``get_output_from_indices`` of devi
 from __future__ import annotations
 
 import random
-from math import ceil, log2, prod
+from math import log2, prod
 
 import torch
 import torch.nn.functional as F
@@ -33,14 +33,12 @@ from torch import nn
 
 from . import native, search
 from .lookup_free_quantization import _EPS, LFQ, _entropy, _maybe_distributed_mean
+from .residual_common import (check_coarse, dropout_cut, group_rows_in, group_rows_out, grouped_decode_dest, grouped_decode_rows,
+                              grouped_fallback, pad_stages, rows_contiguous)
 
 MAX_FUSED_STAGES = native.RLFQ_MAX_STAGES
 _ENTROPY_WS_BUDGET = 2 << 30  # bytes of staged-entropy workspace per call; more stages than fit run in several calls
 _INV_TEMPERATURE = 100.0  # ResidualLFQ.forward passes none to its layers: LFQ's default
-
-
-def _round_up_multiple(num, mult):
-    return ceil(num / mult) * mult
 
 
 def _compiling() -> bool:
@@ -130,14 +128,6 @@ class _RlfqTrain(torch.autograd.Function):
         return gx, None, None, None, None, None, None, None
 
 
-def _rows_contiguous(xg: torch.Tensor) -> torch.Tensor:
-    """xg [G, N, d] with each row's d values contiguous (the kernels' layout; any group and row strides): a copy only
-    when they are not, e.g. a batch-1 [b, d, t] feature map passed as .transpose(1, 2) (as LFQ's _rows_view does)."""
-    if xg.shape[2] > 1 and xg.stride(2) != 1:
-        xg = xg.contiguous()
-    return xg
-
-
 def _fused_ok(rvq: "ResidualLFQ", x: torch.Tensor, stages: int) -> bool:
     l0 = rvq.layers[0]
     return ((x.is_cuda or _compiling()) and 1 <= stages <= MAX_FUSED_STAGES
@@ -183,17 +173,6 @@ def _fused_forward(rvqs, xg: torch.Tensor, mask, stages: int):
         commit_loss = torch.zeros((G, stages), dtype=torch.float32, device=xg.device)
     losses = entropy_aux * l0.entropy_loss_weight + commit_loss * l0.commitment_loss_weight
     return out, idx, losses
-
-
-def _pad_stages(idx: torch.Tensor, losses: torch.Tensor, Q: int, loss_dtype):
-    """Dropped stages: indices -1 and a loss of 0 (residual_lfq.py:149-152)."""
-    S = idx.shape[-1]
-    losses = losses.to(loss_dtype)
-    if S == Q:
-        return idx, losses
-    idx = torch.cat([idx, idx.new_full((*idx.shape[:-1], Q - S), -1)], dim=-1)
-    losses = torch.cat([losses, losses.new_zeros((*losses.shape[:-1], Q - S))], dim=-1)
-    return idx, losses
 
 
 class ResidualLFQ(nn.Module):
@@ -254,23 +233,16 @@ class ResidualLFQ(nn.Module):
             a = a.reshape(self.num_quantizers, *lead, self.codebook_dim)
         return s, a
 
-    def _check_stage_count(self, quantize_dim):
-        if quantize_dim < self.num_quantizers:
-            assert self.quantize_dropout > 0.0, (
-                "quantize dropout must be greater than 0 if you wish to reconstruct from a signal with less fine quantizations"
-            )
-
     def get_codes_from_indices(self, indices):
         """indices [b, ..., q] (q <= num_quantizers; -1 = dropped) -> codes [num_quantizers, b, ..., codebook_dim], the
         unnormalised codes (bits_to_codes) of each stage, zero where dropped.  Computed from the index bits."""
         quantize_dim = indices.shape[-1]
         decode = search.lfq_decode_backend(indices, self.num_quantizers)
+        check_coarse(self, quantize_dim)
         if decode is not None:
-            self._check_stage_count(quantize_dim)
             return self._decode(decode, indices, False, True)[1]
         lead = indices.shape[:-1]
         indices = indices.reshape(lead[0] if len(lead) else 1, -1, quantize_dim)
-        self._check_stage_count(quantize_dim)
         if quantize_dim < self.num_quantizers:
             indices = F.pad(indices, (0, self.num_quantizers - quantize_dim), value=-1)
         dropped = indices == -1
@@ -286,7 +258,7 @@ class ResidualLFQ(nn.Module):
     def get_output_from_indices(self, indices):
         decode = search.lfq_decode_backend(indices, self.num_quantizers)
         if decode is not None:
-            self._check_stage_count(indices.shape[-1])
+            check_coarse(self, indices.shape[-1])
             return self.project_out(self._decode(decode, indices, True, False)[0])
         codes = self.get_codes_from_indices(indices)
         return self.project_out(codes.sum(dim=0))
@@ -295,11 +267,7 @@ class ResidualLFQ(nn.Module):
         """The last active stage under quantize dropout (None: every stage runs), consuming `random` as the reference."""
         if not (self.training and self.quantize_dropout):
             return None
-        rand = random.Random(seed) if seed is not None else random
-        cut = rand.randrange(self.quantize_dropout_cutoff_index, self.num_quantizers)
-        if self.quantize_dropout_multiple_of != 1:
-            cut = _round_up_multiple(cut + 1, self.quantize_dropout_multiple_of) - 1
-        return cut
+        return dropout_cut(self.quantize_dropout_cutoff_index, self.num_quantizers, self.quantize_dropout_multiple_of, seed)
 
     def forward(self, x, mask=None, return_all_codes=False, rand_quantize_dropout_fixed_seed=None):
         num_quant = self.num_quantizers
@@ -310,11 +278,11 @@ class ResidualLFQ(nn.Module):
         if _fused_ok(self, x, stages):
             xf = x.float()
             assert xf.shape[-1] == self.codebook_dim
-            xg = _rows_contiguous(xf.reshape(1, -1, self.codebook_dim))
+            xg = rows_contiguous(xf.reshape(1, -1, self.codebook_dim))
             with torch.autocast(device_type="cuda", enabled=False):
                 out, idx, losses = _fused_forward([self], xg, mask, stages)
             quantized_out = self.project_out(out.reshape(xf.shape))
-            all_indices, all_losses = _pad_stages(idx.reshape(*xf.shape[:-1], stages), losses[0], num_quant, x.dtype)
+            all_indices, all_losses = pad_stages(idx.reshape(*xf.shape[:-1], stages), num_quant, losses[0].to(x.dtype))
         else:
             quantized_out, all_indices, all_losses = self._forward_stagewise(x, mask, cut)
 
@@ -384,15 +352,14 @@ class GroupedResidualLFQ(nn.Module):
         if decode is not None:
             rvq0 = self.rvqs[0]
             G, Q, d = self.groups, rvq0.num_quantizers, rvq0.codebook_dim
-            lead = indices.shape[1:-1]
-            rvq0._check_stage_count(indices.shape[-1])
-            flat = indices.reshape(G, prod(lead), indices.shape[-1])
+            check_coarse(rvq0, indices.shape[-1])
+            flat, lead = grouped_decode_rows(indices)
             if _compiling():  # (the registered op returns fresh tensors)
                 codes = decode(flat, rvq0._stage_mags, d, drop_null=True, want_sum=False, want_all=True)[1].transpose(0, 1)
-            else:
-                codes = torch.empty((G, Q, flat.shape[1], d), dtype=torch.float32, device=indices.device)
-                decode(flat, rvq0._stage_mags, d, drop_null=True, want_sum=False, want_all=True, all_out=codes.transpose(0, 1))
-            return codes.reshape(G, Q, *lead, d)
+                return codes.reshape(G, Q, *lead, d)
+            codes, dest = grouped_decode_dest(flat, lead, d, Q)
+            decode(flat, rvq0._stage_mags, d, drop_null=True, want_sum=False, want_all=True, all_out=dest)
+            return codes
         codes = tuple(rvq.get_codes_from_indices(chunk_indices) for rvq, chunk_indices in zip(self.rvqs, indices))
         return torch.stack(codes)
 
@@ -400,17 +367,15 @@ class GroupedResidualLFQ(nn.Module):
         decode = self._decode_backend(indices)
         if decode is not None:
             rvq0 = self.rvqs[0]
-            G, d = self.groups, rvq0.codebook_dim
-            lead = indices.shape[1:-1]
-            rvq0._check_stage_count(indices.shape[-1])
-            flat = indices.reshape(G, prod(lead), indices.shape[-1])
-            N = flat.shape[1]
+            d = rvq0.codebook_dim
+            check_coarse(rvq0, indices.shape[-1])
+            flat, lead = grouped_decode_rows(indices)
             mags = rvq0._stage_mags
             if self.split_dim == -1 and not rvq0.has_projections and not _compiling():
                 # every group's sum lands in its columns of the concatenated result
-                out = torch.empty((N, G * d), dtype=torch.float32, device=indices.device)
-                decode(flat, mags, d, drop_null=True, sum_out=out.view(N, G, d).transpose(0, 1))
-                return out.view(*lead, G * d)
+                out, dest = grouped_decode_dest(flat, lead, d)
+                decode(flat, mags, d, drop_null=True, sum_out=dest)
+                return out
             sums, _ = decode(flat, mags, d, drop_null=True)
             outputs = tuple(rvq.project_out(sums[g].reshape(*lead, d)) for g, rvq in enumerate(self.rvqs))
             return torch.cat(outputs, dim=self.split_dim)
@@ -425,44 +390,21 @@ class GroupedResidualLFQ(nn.Module):
         cut = rvq0._dropout_cut(seed)  # every group gets the same seed, so the same cut
         Q = rvq0.num_quantizers
         stages = Q if cut is None else min(cut + 1, Q)
-        G = self.groups
-
         if split_dim == -1 and _fused_ok(rvq0, x, stages):
             return self._forward_fused(x, mask, return_all_codes, stages)
-
-        chunks = x.chunk(G, dim=split_dim)
-        forward_kwargs = dict(mask=mask, return_all_codes=return_all_codes, rand_quantize_dropout_fixed_seed=seed)
-        out = tuple(rvq(chunk, **forward_kwargs) for rvq, chunk in zip(self.rvqs, chunks))
-        out = tuple(zip(*out))
-        quantized, all_indices, commit_losses, *maybe_all_codes = out
-        quantized = torch.cat(quantized, dim=split_dim)
-        all_indices = torch.stack(all_indices)
-        commit_losses = torch.stack(commit_losses)
-        return (quantized, all_indices, commit_losses, *maybe_all_codes)
+        return grouped_fallback(self.rvqs, x, split_dim, seed, return_all_codes, tuple, mask=mask)
 
     def _forward_fused(self, x, mask, return_all_codes, stages):
         G = self.groups
         rvq0 = self.rvqs[0]
         Q = rvq0.num_quantizers
         lead = x.shape[:-1]
-        if rvq0.has_projections:
-            chunks = x.chunk(G, dim=-1)
-            xp = [rvq.project_in(chunk) for rvq, chunk in zip(self.rvqs, chunks)]
-            loss_dtype = xp[0].dtype
-            d = rvq0.codebook_dim
-            xg = torch.stack([t.float().reshape(-1, d) for t in xp])  # [G, N, d]
-        else:
-            loss_dtype = x.dtype
-            d = self.dim // G
-            # the chunk views in place (group stride d, row stride G * d) when each row's values are contiguous
-            xg = _rows_contiguous(x.float().reshape(-1, G, d).transpose(0, 1))
+        d = rvq0.codebook_dim  # (= dim / G without projections)
+        xg, loss_dtype = group_rows_in(x, self.rvqs, d, rvq0.has_projections)
         with torch.autocast(device_type="cuda", enabled=False):
             out, idx, losses = _fused_forward(list(self.rvqs), xg, mask, stages)
-        if rvq0.has_projections:
-            quantized = torch.cat([rvq.project_out(out[g].reshape(*lead, d)) for g, rvq in enumerate(self.rvqs)], dim=-1)
-        else:
-            quantized = out.transpose(0, 1).reshape(*lead, G * d)
-        all_indices, commit_losses = _pad_stages(idx.reshape(G, *lead, stages), losses, Q, loss_dtype)
+        quantized = group_rows_out(out, self.rvqs, lead, d, rvq0.has_projections)
+        all_indices, commit_losses = pad_stages(idx.reshape(G, *lead, stages), Q, losses.to(loss_dtype))
         ret = (quantized, all_indices, commit_losses)
         if not return_all_codes:
             return ret
