@@ -1,6 +1,7 @@
-"""The table of native calls that tests/test_gpu_uninitialised_memory.py (poisoned workspaces and outputs) and
-tests/test_gpu_input_extents.py (poisoned surroundings of the inputs) share: one small, path-selecting case per wrapper and
-launch path of vector_quantization.native.  A plain module: it holds no test.
+"""The table of native calls that tests/test_gpu_uninitialised_memory.py (poisoned workspaces and outputs),
+tests/test_gpu_input_extents.py (poisoned surroundings of the inputs) and tests/test_gpu_far_operands.py (one operand whose rows
+span more than 2^31 elements) share: one small, path-selecting case per wrapper and launch path of vector_quantization.native.
+A plain module: it holds no test, and every case stands here, so that the three suites see one table in any selection.
 
 Every device tensor a case hands to a wrapper comes from ONE hook, ``place(cpu_tensor, role)``: the inputs are built on the
 host and placed, so that a test can decide where they lie in device memory.  The default hook is ``.to(DEV)``; a test installs
@@ -18,8 +19,10 @@ from __future__ import annotations
 import contextlib
 import functools
 
+import numpy as np
 import torch
 
+import input_poison as ip
 import train_dense as td
 
 DEV = "cuda:0"
@@ -78,6 +81,17 @@ def dest(shape, dtype=torch.float32, row_dims: int = 1, name: str | None = None)
     return _hook[-1].dest(tuple(shape), dtype, row_dims, name)
 
 
+def lend(nbytes: int):
+    """``nbytes`` of poisoned device memory (uint8, all ones) for a case that lays out a destination of its own: the hook's
+    when it has an arena to lend (tests/input_poison.FarPlacer), else a fresh buffer."""
+    lender = getattr(_hook[-1], "lend", None)
+    if lender is not None:
+        return lender(nbytes)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    ip.arena_fill(buf)
+    return buf
+
+
 ROWS = dict(role="rows")                       # [.., M, D]: rows of D contiguous elements
 PER_ROW = dict(role="rows", row_dims=0)        # [H, M]: one element per row (idx, target, ind, mask)
 TABLES = dict(role="rows", row_dims=2)         # [.., K, D] / [N, C, d]: the last two dims are one contiguous row
@@ -123,7 +137,10 @@ PATHS = {
     "quantize-wave_pairs-*": (["vq_search_pair512", "vq_loss_reduce_kernel"], ["vq_search_mfma"]),
     "quantize-persistent*": (["vq_search_persist"], ["vq_search_mfma", "vq_resolve_rows_kernel"]),
     "quantize-one_block-ste-sq_err": (["vq_search_mfma"], ["vq_search_persist"]),
-    "quantize-resident-*": (["vq_search_resident"], ["vq_search_mfma"]),
+    "quantize-resident-dp*": (["vq_search_resident"], ["vq_search_mfma"]),
+    # (the contiguous call of the case takes the resident kernel; the one whose destination rows lie 144 MiB apart the
+    #  one-block tile-streaming kernel: describe_call keeps a call whose 32 rows of out span 2^32 bytes off the resident one)
+    "quantize-resident-wide-out-stride": (["vq_search_resident", "vq_search_mfma"], []),
     "quantize-force_split": (["vq_search_mfma", "vq_finalize_kernel", "vq_loss_reduce_kernel"], []),
     "quantize-per_head-overrules-force_split": (["vq_search_mfma", "vq_loss_reduce_kernel"], ["vq_finalize_kernel"]),
     "quantize-k_split-few_rows": (["vq_search_mfma", "vq_finalize_kernel", "vq_loss_reduce_kernel"], ["vq_keys_init_kernel"]),
@@ -225,6 +242,38 @@ _quantize_case("quantize-residual-fused-per_head", (2, 3000, 256, 64), 36, Q=3, 
 _quantize_case("quantize-residual-pair", (1, 1000, 1000, 300), 37, Q=3, ste=True, want_sq_err=True, env={"VQ_NO_RESIDUAL_TAIL": "1"})
 _quantize_case("quantize-residual-remainder-eval", (2, 36000, 1024, 128), 38, Q=3)
 _quantize_case("quantize-residual-remainder-train", (2, 36000, 1024, 128), 38, Q=3, ste=True, want_sq_err=True)
+
+WIDE_OUT_RS = 36 << 20  # floats between two rows of the destination: 31 rows of it are more than 2^32 bytes
+
+
+@case("quantize-resident-wide-out-stride")
+def _resident_wide_out_stride(native, poisoned):
+    """A shape the resident-codebook kernel takes (H * M reaches its rows-per-CU threshold), contiguous x, and a destination
+    view [H, M, D] with strides (D, WIDE_OUT_RS, 1): the heads interleaved inside each of 32 rows that lie 144 MiB apart, a span
+    of 4.7 GiB.  out and idx equal the contiguous call's bit for bit, and the buffer around the view keeps its poison (a store
+    whose 32-bit byte offset wrapped lands at a lower address of the same buffer)."""
+    H, M, K, D = -(-512 * _cus() // 32), 32, 64, 32
+    x = place(_cpu_randn((H, M, D), 45))
+    cb = place(_cpu_randn((H, 1, K, D), 46))
+    want = native.quantize(x, cb, want_best=False)
+    span = (M - 1) * WIDE_OUT_RS + (H - 1) * D + D
+    front = 256
+    buf = lend(front + span * 4 + 256)
+    shape, strides = (H, M, D), (D, WIDE_OUT_RS, 1)
+    out = buf[front:front + span * 4].view(torch.float32).as_strided(shape, strides)
+    got = native.quantize(x, cb, want_best=False, out=out)
+    torch.cuda.synchronize()
+    assert got["out"].data_ptr() == out.data_ptr()
+    dense = out.contiguous()
+    buf.as_strided((*shape, 4), (*(4 * s for s in strides), 1), front).fill_(0xFF)
+    errors = ip.arena_errors(buf)
+    assert not errors, f"a store outside the destination view [H, M, D] with strides {strides}: {errors[0]}"
+    assert torch.equal(got["idx"], want["idx"]), "idx differs from the contiguous call's"
+    differ = dense.view(torch.int32) != want["out"].view(torch.int32)
+    assert not bool(differ.any()), (f"out differs from the contiguous call's in {int(differ.sum())} element(s), the first at "
+                                    f"{torch.nonzero(differ)[0].tolist()}")
+    return {"quantize.out": dense, "quantize.idx": got["idx"]}
+
 
 SCR_M, SCR_K, SCR_D = 131072, 1024, 256
 SCR_TILES = SCR_K // 32
@@ -714,3 +763,121 @@ def _pack_screen(native, poisoned):
     return {"pack_screen.screen": screen}
 
 
+
+
+# ------------------------------------------------------------------------------------------------------- dead-code expiry
+EXPIRE_SEED = (0x0123456789ABCDEF, -0x0FEDCBA987654321)
+
+
+@case("expire_codes")
+def _expire_case(native, poisoned):
+    """Pool rows (row-strided: the poison suites pad them), a residual chain, and the normalisation; the three buffers are the
+    caller's, picked and the workspace the binding's."""
+    H, K, D, N = 2, 1100, 12, 300
+    g = torch.Generator().manual_seed(70)
+    sizes = torch.rand((H, K), generator=g) * 4.0
+    seed = place(torch.tensor(list(EXPIRE_SEED), dtype=torch.int64))
+    out = {}
+    for l2norm in (False, True):
+        cs, avg, emb = place(sizes.clone()), place(torch.randn((H, K, D), generator=g)), place(torch.randn((H, K, D), generator=g))
+        pool = place(torch.randn((H, N, D), generator=g), **ROWS)
+        n, picked = native.expire_codes(cs, avg, emb, pool, threshold=2.0, reset_cluster_size=2.0, l2norm=l2norm, seed=seed,
+                                        want_picked=True)
+        out.update({f"expire_codes.cluster_size_{l2norm}": cs, f"expire_codes.embed_avg_{l2norm}": avg,
+                    f"expire_codes.embeddings_{l2norm}": emb, f"expire_codes.n_expired_{l2norm}": n,
+                    f"expire_codes.picked_{l2norm}": picked})
+    Q, Kc, M = 3, 40, 200
+    x = place(torch.randn((1, M, D), generator=g), **ROWS)
+    codes = place(torch.randn((Q, Kc, D), generator=g) * 0.5)
+    idx = place(torch.randint(0, Kc, (1, M, Q), generator=g), **ROWS)
+    cs = place((torch.rand((1, Kc), generator=g) * 4.0))
+    avg, emb = place(torch.randn((1, Kc, D), generator=g)), place(torch.randn((1, Kc, D), generator=g))
+    n, picked = native.expire_codes(cs, avg, emb, None, chain=(x, codes, idx), stage=2, threshold=2.0, reset_cluster_size=2.0,
+                                    l2norm=False, seed=seed, want_picked=True)
+    out.update({"expire_codes.chain_cluster_size": cs, "expire_codes.chain_embed_avg": avg, "expire_codes.chain_embeddings": emb,
+                "expire_codes.chain_n_expired": n, "expire_codes.chain_picked": picked})
+    return out
+
+
+# ------------------------------------------------------------------------- the cross-entropy loss's codebook gradient
+def _ce_codes_case(name, shape, seed, metric=0):
+    @case(name)
+    def call(native, poisoned):
+        H, M, K, D = shape
+        x, cb = place(_cpu_randn((H, M, D), seed), **ROWS), place(_cpu_randn((H, K, D), seed + 1))
+        target = _cpu_randint(0, K, (H, M), seed + 2)
+        target[:, ::7] = -1  # ignored rows
+        target = place(target, **PER_ROW)
+        lse, _ = native.softmax_stats(x, cb, metric=metric, target=target)
+        coef = place(torch.tensor([0.37]))
+        return {"ce_backward_codes.grad_codes": native.ce_backward_codes(x, cb, lse, target, coef, metric=metric)}
+
+
+# one per launch path: one row split, several
+_ce_codes_case("ce_backward_codes-one-split", (2, 33, 300, 20), 111)
+_ce_codes_case("ce_backward_codes-splits", (1, 2100, 64, 32), 112, metric=1)
+
+
+# ------------------------------------------------------------------------------------- the masked residual stack's pass
+RESIDUAL_MASK_K = 11
+
+
+def _residual_mask_rows(kind, M, rng):
+    if kind == "all":
+        return np.ones(M, dtype=bool)
+    if kind == "none":
+        return np.zeros(M, dtype=bool)
+    if kind == "alternating":
+        return (np.arange(M) % 2 == 0)
+    if kind == "boundary":  # a ragged length: the boundary falls inside a wave's group of rows whatever the rows per access
+        return np.arange(M) < (M * 2 + 2) // 3
+    m = rng.random(M) < 0.6
+    m[M // 2] = False  # the row that holds the non-finite element
+    return m
+
+
+def residual_mask_inputs(G, M, D, Qn, share, kind, seed):
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((G, M, D)).astype(np.float32)
+    cb = (rng.standard_normal((G, 1 if share else Qn, RESIDUAL_MASK_K, D)) * 0.5).astype(np.float32)
+    idx = rng.integers(0, RESIDUAL_MASK_K, (G, M, Qn))
+    zero_idx = rng.integers(0, RESIDUAL_MASK_K, (G, Qn))
+    mask = _residual_mask_rows(kind, M, rng)
+    if kind == "nonfinite":
+        x[:, M // 2, D // 2] = np.inf if seed % 2 else np.nan
+    return x, cb, idx, zero_idx, mask
+
+
+@case("residual_mask-forward-and-backward")
+def _residual_mask_case(native, poisoned):
+    """Both lane mappings (one slice per lane, two slices), per-group and total sums; x, idx and grad_out row-strided (the
+    poison suites pad them), out the caller's."""
+    out = {}
+    for tag, (G, M, D, Qn, per_group) in (("d48", (2, 301, 48, 3, True)), ("d260", (1, 77, 260, 2, False))):
+        x, cb, idx, zero_idx, mask = residual_mask_inputs(G, M, D, Qn, False, "nonfinite", 31 + D)
+        xp = place(torch.from_numpy(x), **ROWS)
+        cbp = place(torch.from_numpy(cb))
+        idxp = place(torch.from_numpy(idx), **ROWS)
+        maskp, zp = place(torch.from_numpy(mask)), place(torch.from_numpy(zero_idx))
+        o, e = native.residual_mask(xp, cbp, idxp, maskp, zp, train=True, want_sq_err=True, sq_err_per_group=per_group,
+                                    out=dest((G, M, D)))
+        go = place(torch.randn((G, M, D), generator=torch.Generator().manual_seed(D)), **ROWS)
+        ge = place(torch.linspace(-1.0, 1.0, G * Qn if per_group else Qn, dtype=torch.float64))
+        gx = native.residual_mask_backward(xp, cbp, idxp, maskp, go, ge, train=True, sq_err_per_group=per_group)
+        out.update({f"residual_mask.out_{tag}": o, f"residual_mask.sq_err_{tag}": e, f"residual_mask.idx_{tag}": idxp,
+                    f"residual_mask_backward.grad_x_{tag}": gx})
+    return out
+
+
+# ------------------------------------------------------------------------------------------- the rotation trick's backward
+@case("rotate_backward-per-head-and-total")
+def _rotate_backward_case(native, poisoned):
+    """x, idx and grad_out row-strided (the poison suites pad them).  Both widths are no multiple of 4, so that the scalar
+    variants run wherever the rows are placed: the vector variants add a row's products in another order, and the suites
+    compare the runs bit for bit."""
+    out = {}
+    for tag, (H, M, D, Q, per_head) in (("d50", (2, 301, 50, 3, True)), ("d261", (1, 77, 261, 2, False))):
+        x, cb, idx, go, ge = td.backward_inputs(H, M, D, Q, td.BWD_K, 31 + D, per_head=per_head)
+        out[f"rotate_backward.grad_x_{tag}"] = native.rotate_backward(place(x, **ROWS), place(cb), place(idx, **ROWS),
+                                                                      place(go, **ROWS), place(ge), sq_err_per_head=per_head)
+    return out

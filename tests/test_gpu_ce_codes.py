@@ -6,9 +6,8 @@ The tolerance is the project's rule (tests/test_gpu_diversity_codes.py::_rule): 
 atol = max(GRAD_ATOL_OF_MAX, 4 x the error the reference's own fp32 op sequence has on the same inputs against fp64) of the
 largest fp64 entry, and GRAD_RTOL.  Every measured reference error and kernel error is printed.
 
-The module also adds its cases to the table of native calls (tests/native_cases.py), one per launch path (one row split,
-several), so that the two poison suites (tests/test_gpu_uninitialised_memory.py, tests/test_gpu_input_extents.py) cover the new
-call in a whole-suite run.  grad_codes is written completely: it needs no extent sentence."""
+The table of native calls (tests/native_cases.py) holds one case per launch path (one row split, several), so that the poison
+suites cover the call.  grad_codes is written completely: it needs no extent sentence."""
 from __future__ import annotations
 
 import copy
@@ -21,7 +20,6 @@ import torch
 from ce_codes_cases import CE_CODES_CASES
 from ce_codes_run import check_fixture, closed_form, reference_sequence
 from gumbel_run import GRAD_ATOL_OF_MAX, GRAD_RTOL, assert_grad_close  # noqa: F401  (GRAD_RTOL: assert_grad_close's default)
-from native_cases import PER_ROW, ROWS, _cpu_randint, _cpu_randn, case, place
 from test_ce_codes_host import documented_floats
 
 pytestmark = pytest.mark.gpu
@@ -216,24 +214,6 @@ def test_no_rows_clears_grad_codes():
     got = native.ce_backward_codes(x, cb, lse, target, torch.ones(1, device="cuda"), out=out)
     torch.cuda.synchronize()
     assert got.data_ptr() == out.data_ptr() and not bool(out.any())
-
-
-# --------------------------------------------------------------------------------------------- the table of native calls
-def _table_case(name, shape, seed, metric=0):
-    @case(name)
-    def call(native, poisoned):
-        H, M, K, D = shape
-        x, cb = place(_cpu_randn((H, M, D), seed), **ROWS), place(_cpu_randn((H, K, D), seed + 1))
-        target = _cpu_randint(0, K, (H, M), seed + 2)
-        target[:, ::7] = -1  # ignored rows
-        target = place(target, **PER_ROW)
-        lse, _ = native.softmax_stats(x, cb, metric=metric, target=target)
-        coef = place(torch.tensor([0.37]))
-        return {"ce_backward_codes.grad_codes": native.ce_backward_codes(x, cb, lse, target, coef, metric=metric)}
-
-
-_table_case("ce_backward_codes-one-split", (2, 33, 300, 20), 111)
-_table_case("ce_backward_codes-splits", (1, 2100, 64, 32), 112, metric=1)
 
 
 # ------------------------------------------------------------------------------------------------ the loss function

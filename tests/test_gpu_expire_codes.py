@@ -2,9 +2,8 @@
 they pick against the host statement of the rule (tests/expire_rule.py), every edge of the scan and of the copy, the
 normalisation against fp64, the residual chain bit for bit, poisoned buffers, and the registered custom op.
 
-The module also adds its case to the table of native calls (tests/native_cases.py), so that the two poison suites
-(tests/test_gpu_uninitialised_memory.py, tests/test_gpu_input_extents.py) run the new entry point like every other one and
-find its kernels launched."""
+The entry point's case stands in the table of native calls (tests/native_cases.py), so that the poison suites run it like
+every other one and find its kernels launched."""
 from __future__ import annotations
 
 import numpy as np
@@ -13,11 +12,11 @@ import torch
 
 import alloc_poison as ap
 import expire_rule as er
-from native_cases import DEV, ROWS, case, place
+from native_cases import DEV, EXPIRE_SEED
 
 pytestmark = pytest.mark.gpu
 
-SEED = (0x0123456789ABCDEF, -0x0FEDCBA987654321)
+SEED = EXPIRE_SEED
 
 
 def _native():
@@ -293,34 +292,3 @@ def test_degenerate_calls_and_bad_arguments():
     assert lib.vq_expire_codes_f32(*args(3, _seed().data_ptr(), None)) == -1 and b"pool" in lib.vq_last_error()
     assert lib.vq_expire_workspace_bytes(3, 100) >= 3 * 4 + 3 * 100 * 4
     torch.cuda.synchronize()
-
-
-# --------------------------------------------------------------------------------------------- the table of native calls
-@case("expire_codes")
-def _expire_case(native, poisoned):
-    """Pool rows (row-strided: the poison suites pad them), a residual chain, and the normalisation; the three buffers are the
-    caller's, picked and the workspace the binding's."""
-    H, K, D, N = 2, 1100, 12, 300
-    g = torch.Generator().manual_seed(70)
-    sizes = torch.rand((H, K), generator=g) * 4.0
-    seed = place(torch.tensor(list(SEED), dtype=torch.int64))
-    out = {}
-    for l2norm in (False, True):
-        cs, avg, emb = place(sizes.clone()), place(torch.randn((H, K, D), generator=g)), place(torch.randn((H, K, D), generator=g))
-        pool = place(torch.randn((H, N, D), generator=g), **ROWS)
-        n, picked = native.expire_codes(cs, avg, emb, pool, threshold=2.0, reset_cluster_size=2.0, l2norm=l2norm, seed=seed,
-                                        want_picked=True)
-        out.update({f"expire_codes.cluster_size_{l2norm}": cs, f"expire_codes.embed_avg_{l2norm}": avg,
-                    f"expire_codes.embeddings_{l2norm}": emb, f"expire_codes.n_expired_{l2norm}": n,
-                    f"expire_codes.picked_{l2norm}": picked})
-    Q, Kc, M = 3, 40, 200
-    x = place(torch.randn((1, M, D), generator=g), **ROWS)
-    codes = place(torch.randn((Q, Kc, D), generator=g) * 0.5)
-    idx = place(torch.randint(0, Kc, (1, M, Q), generator=g), **ROWS)
-    cs = place((torch.rand((1, Kc), generator=g) * 4.0))
-    avg, emb = place(torch.randn((1, Kc, D), generator=g)), place(torch.randn((1, Kc, D), generator=g))
-    n, picked = native.expire_codes(cs, avg, emb, None, chain=(x, codes, idx), stage=2, threshold=2.0, reset_cluster_size=2.0,
-                                    l2norm=False, seed=seed, want_picked=True)
-    out.update({"expire_codes.chain_cluster_size": cs, "expire_codes.chain_embed_avg": avg, "expire_codes.chain_embeddings": emb,
-                "expire_codes.chain_n_expired": n, "expire_codes.chain_picked": picked})
-    return out

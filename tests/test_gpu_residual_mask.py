@@ -3,9 +3,8 @@ of its rule (tests/residual_mask_rule.py) at every shape edge of its lane mappin
 forwards of ResidualVQ and GroupedResidualVQ against the layer-by-layer route (VQ_RVQ_NO_FUSED_MASK=1) and against the
 fixtures captured from the reference (tests/golden/make_golden_rvq_mask.py).
 
-The module also adds its case to the table of native calls (tests/native_cases.py), so that the two poison suites
-(tests/test_gpu_uninitialised_memory.py, tests/test_gpu_input_extents.py) run the two entry points like every other one and
-find their kernels launched."""
+The case of the two entry points in the table of native calls (tests/native_cases.py) shares this module's inputs
+(native_cases.residual_mask_inputs), so that the poison suites run them like every other one and find their kernels launched."""
 from __future__ import annotations
 
 import copy
@@ -17,13 +16,12 @@ import torch
 
 import residual_mask_rule as rule
 import train_dense as td
-from native_cases import DEV, ROWS, case, dest, place
+from native_cases import DEV, RESIDUAL_MASK_K as K_DIRECT, residual_mask_inputs as _inputs
 from rvq_mask_run import (BY_NAME, CASES, DIM, Q, build_module, case_inputs, check_against_fixture, ema_state, forward_backward,
                           grad_close, rel_close, run_case, same)
 
 pytestmark = pytest.mark.gpu
 
-K_DIRECT = 11
 MASKS = ("all", "none", "alternating", "boundary", "nonfinite")
 
 
@@ -32,32 +30,6 @@ def _native():
 
     native.load()
     return native
-
-
-def _mask(kind, M, rng):
-    if kind == "all":
-        return np.ones(M, dtype=bool)
-    if kind == "none":
-        return np.zeros(M, dtype=bool)
-    if kind == "alternating":
-        return (np.arange(M) % 2 == 0)
-    if kind == "boundary":  # a ragged length: the boundary falls inside a wave's group of rows whatever the rows per access
-        return np.arange(M) < (M * 2 + 2) // 3
-    m = rng.random(M) < 0.6
-    m[M // 2] = False  # the row that holds the non-finite element
-    return m
-
-
-def _inputs(G, M, D, Qn, share, kind, seed):
-    rng = np.random.default_rng(seed)
-    x = rng.standard_normal((G, M, D)).astype(np.float32)
-    cb = (rng.standard_normal((G, 1 if share else Qn, K_DIRECT, D)) * 0.5).astype(np.float32)
-    idx = rng.integers(0, K_DIRECT, (G, M, Qn))
-    zero_idx = rng.integers(0, K_DIRECT, (G, Qn))
-    mask = _mask(kind, M, rng)
-    if kind == "nonfinite":
-        x[:, M // 2, D // 2] = np.inf if seed % 2 else np.nan
-    return x, cb, idx, zero_idx, mask
 
 
 def _strided(t, pad, fill):
@@ -368,25 +340,3 @@ def test_masked_forward_and_backward_under_one_graph():
     for got, ref in zip(kept["out"], want):
         assert torch.equal(got, ref)
     assert xd.grad is not None and bool(xd.grad.any()) and torch.equal(xd.grad, tx.grad)
-
-
-# --------------------------------------------------------------------------------------------- the table of native calls
-@case("residual_mask-forward-and-backward")
-def _residual_mask_case(native, poisoned):
-    """Both lane mappings (one slice per lane, two slices), per-group and total sums; x, idx and grad_out row-strided (the
-    poison suites pad them), out the caller's."""
-    out = {}
-    for tag, (G, M, D, Qn, per_group) in (("d48", (2, 301, 48, 3, True)), ("d260", (1, 77, 260, 2, False))):
-        x, cb, idx, zero_idx, mask = _inputs(G, M, D, Qn, False, "nonfinite", 31 + D)
-        xp = place(torch.from_numpy(x), **ROWS)
-        cbp = place(torch.from_numpy(cb))
-        idxp = place(torch.from_numpy(idx), **ROWS)
-        maskp, zp = place(torch.from_numpy(mask)), place(torch.from_numpy(zero_idx))
-        o, e = native.residual_mask(xp, cbp, idxp, maskp, zp, train=True, want_sq_err=True, sq_err_per_group=per_group,
-                                    out=dest((G, M, D)))
-        go = place(torch.randn((G, M, D), generator=torch.Generator().manual_seed(D)), **ROWS)
-        ge = place(torch.linspace(-1.0, 1.0, G * Qn if per_group else Qn, dtype=torch.float64))
-        gx = native.residual_mask_backward(xp, cbp, idxp, maskp, go, ge, train=True, sq_err_per_group=per_group)
-        out.update({f"residual_mask.out_{tag}": o, f"residual_mask.sq_err_{tag}": e, f"residual_mask.idx_{tag}": idxp,
-                    f"residual_mask_backward.grad_x_{tag}": gx})
-    return out

@@ -7,8 +7,8 @@ D runs over train_dense.BWD_DIMS up to 1024, so every register variant (f32x4 x 
 and the scalar path run, and 252 / 260 straddle the first variant boundary.  Indices come from torch.randint: the kernel does not
 care whether they are winners.  Worst error / bound seen on an MI355X: profiles/rotation_trick.md.
 
-The module also adds its case to the table of native calls (tests/native_cases.py), so that the two poison suites run the new
-wrapper on poisoned allocations and on inputs embedded in poisoned buffers."""
+The wrapper's case in the table of native calls (tests/native_cases.py) lets the poison suites run it on poisoned allocations,
+on inputs embedded in poisoned buffers and on far operands."""
 from __future__ import annotations
 
 import numpy as np
@@ -17,7 +17,6 @@ import torch
 
 import rotation_dense as rd
 import train_dense as td
-from native_cases import ROWS, case, place
 
 pytestmark = pytest.mark.gpu
 
@@ -250,17 +249,3 @@ def test_inputs_are_left_unchanged(D):
     torch.cuda.synchronize()
     for t, k in zip((x, cb, idx, go, ge), keep):
         assert torch.equal(t, k)
-
-
-# --------------------------------------------------------------------------------------------- the table of native calls
-@case("rotate_backward-per-head-and-total")
-def _rotate_backward_case(native, poisoned):
-    """x, idx and grad_out row-strided (the poison suites pad them).  Both widths are no multiple of 4, so that the scalar
-    variants run wherever the rows are placed: the vector variants add a row's products in another order, and the suites
-    compare the runs bit for bit."""
-    out = {}
-    for tag, (H, M, D, Q, per_head) in (("d50", (2, 301, 50, 3, True)), ("d261", (1, 77, 261, 2, False))):
-        x, cb, idx, go, ge = td.backward_inputs(H, M, D, Q, td.BWD_K, 31 + D, per_head=per_head)
-        out[f"rotate_backward.grad_x_{tag}"] = native.rotate_backward(place(x, **ROWS), place(cb), place(idx, **ROWS),
-                                                                      place(go, **ROWS), place(ge), sq_err_per_head=per_head)
-    return out

@@ -76,7 +76,10 @@ Call describe_call(const vq_args *a, bool lse) {
     const bool out4 = vec4_ok(a->out, {a->out_rs, a->out_hs});
     c.vec_x = vec4_ok(a->x, {a->D, a->x_rs, a->x_hs}, (a->flags & (VQ_F_X_F16 | VQ_F_X_BF16)) ? 8 : 16);  // (2-byte rows: four of them are 8 bytes)
     c.vec_fin = c.vec_x && (!a->out || out4) && (!a->cb || vec4_ok(a->cb, {a->cb_hs, a->cb_qs}));
-    c.vec_res = vec4_ok(a->x, {a->x_rs, a->x_hs}) && out4 && vec4_ok(a->cb, {a->cb_hs});
+    // (the resident kernel's deferred copy adds a 32-bit byte offset of up to 31 rows of out to a block's base: 32 rows of out
+    //  must span less than 2^32 bytes; a wider, or a negative, row stride takes the tile-streaming kernels)
+    const bool out_rs32 = a->out_rs >= 0 && a->out_rs * 128 < (1ll << 32);
+    c.vec_res = vec4_ok(a->x, {a->x_rs, a->x_hs}) && out4 && out_rs32 && vec4_ok(a->cb, {a->cb_hs});
     c.vec_wide = vec4_ok(a->out, {a->D, a->out_rs, a->out_hs}) && vec4_ok(a->cb, {a->cb_hs});
     return c;
 }
