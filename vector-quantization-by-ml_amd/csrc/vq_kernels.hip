@@ -26,7 +26,9 @@
 //   vq_pack.inc          natural codebook -> packed image
 //   vq_search.inc        the hot kernel (tile geometry, LDS-DMA staging, MFMA fragment pipeline, tie-exact epilogue, finalize)
 //                        and what other sweep kernels share with it: load_x_fragments (a wave's rows -> B fragments + the
-//                        |x|^2 chain, for the training-side sweeps), stage_tile, lane_best_start, store_sims_subtile
+//                        |x|^2 chain, for the training-side sweeps), stage_tile, lane_best_start, store_sims_subtile; the
+//                        search kernels' back end: row_winner, close_lse, store_key, store_winner, fill_row_from_memory,
+//                        wide_acc_init, gather_wide_rows, store_loss_partials
 //   vq_search_pair.inc   the same search for 256 < D <= 512 with the dims split over a pair of waves (accumulator hand-off)
 //   vq_search_persist.inc  inference search at Dp = 256 with block b's gather hidden inside block b + 1's sweep
 //   vq_search_resident.inc small codebooks: the packed image stays in LDS, no barriers, rows streamed past it by LDS-DMA slabs

@@ -604,6 +604,123 @@ __device__ __forceinline__ float widen16(unsigned short b) {
     return __uint_as_float((unsigned)b << 16);
 }
 
+// ---- the back end shared by the search kernels: what follows the last MFMA of a sweep ------------------------------
+// Called by vq_search_mfma and vq_search_pair512; row_winner, fill_row_from_memory and store_winner by vq_search_persist
+// and vq_search_resident too.  Shared is what left every kernel's register allocation as it was; the residual update, the
+// fused finalize's row bodies and vq_search_mfma's own lane-half merge did not and are written out in their kernels
+// (profiles/search_backend_refactor.md has the figures).
+
+// The row's winner: resolve_best, then the two lane halves of each row merge (they saw disjoint codes; ties go to the
+// lowest index).  Lanes c and c + 32 leave with the same pair.  (vq_search_mfma spells the merge out: through this
+// helper one of its residual kernels is allocated one VGPR fewer.)
+template <int METRIC>
+__device__ __forceinline__ void row_winner(const LaneBest &lb, int h, int K, float &best_s, int &best_i) {
+    resolve_best<METRIC>(lb, h, K, best_s, best_i);
+    const float os = __shfl_xor(best_s, 32);
+    const int oi = __shfl_xor(best_i, 32);
+    const bool take = (METRIC == VQ_METRIC_EUCLID) ? (os < best_s || (os == best_s && oi < best_i))
+                                                   : (os > best_s || (os == best_s && oi < best_i));
+    if (take) {
+        best_s = os;
+        best_i = oi;
+    }
+}
+
+// log-sum-exp of a row's similarities over the whole codebook from the two lane halves' running (max, sum) pairs (fused
+// sweeps only: no K split).  Lane half 0 always saw code 0, so the merged maximum is finite.  A NaN similarity in the row
+// (`best_s` is NaN then, after the repair) makes the logsumexp NaN.  Every lane of the wave calls it (it shuffles).
+__device__ __forceinline__ float close_lse(const LaneBest &lb, float best_s) {
+    const float INF = __builtin_inff();
+    const float om = __shfl_xor(lb.run_m, 32), os = __shfl_xor(lb.run_s, 32);
+    const float mm = fmaxf(lb.run_m, om);
+    const float ssum = (lb.run_m > -INF ? lb.run_s * __builtin_amdgcn_exp2f(lb.run_m - mm) : 0.0f) +
+                       (om > -INF ? os * __builtin_amdgcn_exp2f(om - mm) : 0.0f);
+    const float lse_v = (mm + __builtin_amdgcn_logf(ssum)) * 0.6931471805599453f;
+    return (best_s != best_s) ? best_s : lse_v;
+}
+
+// keys mode: the row's (value, index) key, by atomic MIN or into this K split's own plane.  Called by lane c of a live row.
+template <int METRIC>
+__device__ __forceinline__ void store_key(const SearchParams &p, int head, long long row, float best_s, int best_i) {
+    const long long key = make_key<METRIC>(best_s, p.idx_offset + best_i);
+    long long *dst = p.keys + (long long)head * p.key_hs + row;
+    if (p.mode == kModeKeys) atomicMin(dst, key);
+    else dst[(long long)blockIdx.z * p.key_zs] = key;  // this K split's own plane
+}
+
+// fused mode: stage q's winner of a row (`idx_v`: the index, or the persistent kernel's packed candidates).  Called by
+// lane c of a live row.
+__device__ __forceinline__ void store_winner(const SearchParams &p, int head, long long row, int q, float best_s, long long idx_v) {
+    const long long o = (long long)head * p.idx_hs + row * p.idx_rs + (long long)q * p.idx_qs;
+    p.idx[o] = idx_v;
+    if (p.best) p.best[o] = best_s;
+}
+
+// The repair's `fill_row` for a row that is still in memory: row `grow`, widened and zero padded to DP floats, into
+// `rowbuf`; returns the start of its |x|^2 chain (the earlier slices' value for the last slice of a wide row, else 0).
+template <int METRIC, int DP, int XT, int WIDE>
+__device__ __forceinline__ float fill_row_from_memory(const SearchParams &p, int head, long long grow, float *rowbuf, int lane) {
+#pragma clang loop unroll(disable)
+    for (int d = lane; d < DP; d += 64) {
+        float v = 0.0f;
+        if (d < p.D) {
+            if constexpr (XT == 0)
+                v = p.x[(long long)head * p.x_hs + grow * p.x_rs + d];
+            else
+                v = widen16<XT>(((const unsigned short *)p.x)[(long long)head * p.x_hs + grow * p.x_rs + d]);
+        }
+        rowbuf[d] = v;
+    }
+    if constexpr (WIDE == 2) {
+        if (METRIC == VQ_METRIC_EUCLID && p.acc_in) return p.xn_ws[(long long)head * p.xn_hs + grow];
+    }
+    return 0.0f;
+}
+
+// The repair's `acc_init` for the last slice of a wide row: the chain the earlier slices left for (row rr of 32-row block
+// `rblock`, code k), read back from the accumulators' fragment layout (float4 index (sub-tile * 4 + g) * 64 + lane).
+__device__ __forceinline__ float wide_acc_init(const SearchParams &p, int head, long long rblock, int rr, int k) {
+    if (!p.acc_in) return 0.0f;
+    const float *wb = (const float *)((const f32x4 *)p.acc_ws + (long long)head * p.ws_hs + (rblock * p.ws_nsub) * 256);
+    const int r5 = k & 31;
+    return wb[((long long)((k >> 5) * 4 + (r5 >> 3)) * 64 + ((r5 >> 2) & 1) * 32 + rr) * 4 + (r5 & 3)];
+}
+
+// WIDE = 2 finish (rows wider than one launch holds, inference call, no K split): out[row] = codebook[widx[row]] over the
+// WHOLE row width for rows [lo, hi) of the 32-row block at row0 (natural layout, float4 per lane and 256 dims, four rows
+// in flight).
+__device__ __forceinline__ void gather_wide_rows(const SearchParams &p, int head, long long row0, int lo, int hi, const int *widx, int lane) {
+    const float *cbw = p.cb + (long long)head * p.cb_hs;
+    float *outw = p.out + (long long)head * p.out_hs;
+    constexpr int RBW = 4;
+    for (int rr0 = lo; rr0 < hi; rr0 += RBW) {
+        for (int d0 = 4 * lane; d0 < p.fin_D; d0 += 256) {
+            f32x4 v[RBW];
+#pragma unroll
+            for (int k = 0; k < RBW; ++k) {
+                const int rr = (rr0 + k < hi) ? rr0 + k : hi - 1;
+                v[k] = *(const f32x4 *)(cbw + (long long)widx[rr] * p.fin_D + d0);
+            }
+#pragma unroll
+            for (int k = 0; k < RBW; ++k)
+                if (rr0 + k < hi) __builtin_nontemporal_store(v[k], (f32x4 *)(outw + (row0 + rr0 + k) * p.out_rs + d0));
+        }
+    }
+}
+
+// The per-wave loss partials [head][workgroup][wave][Q]: each stage's per-lane partials (MULTI: `lerr`, element q at
+// lerr[q * 64]; one stage: `e0`) summed over the wave.
+template <int NWAVES, bool MULTI>
+__device__ __forceinline__ void store_loss_partials(const SearchParams &p, int head, const float *lerr, float e0, int wave, int lane) {
+    float *lp = p.loss_part + (((long long)head * gridDim.x + blockIdx.x) * NWAVES + wave) * p.Q;
+    for (int q = 0; q < (MULTI ? p.Q : 1); ++q) {
+        float e = MULTI ? lerr[q * 64] : e0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
+        if (lane == 0) lp[q] = e;
+    }
+}
+
 // MULTI: 0 one stage; 1 residual stages, eval arithmetic (r <- r - c); 2 residual stages, straight-through arithmetic.
 // (The two residual variants are separate instantiations: one update path per kernel keeps the stage loop's 128
 //  loop-carried residual registers in place -- with both paths behind a branch the allocator spills ~90 of them.)
@@ -929,32 +1046,10 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_search_mfm
                     }
                     return 0.0f;
                 }
-#pragma clang loop unroll(disable)
-                for (int d = lane; d < DP; d += 64) {
-                    float v = 0.0f;
-                    if (d < p.D) {
-                        if constexpr (XT == 0)
-                            v = xh[grow * p.x_rs + d];
-                        else
-                            v = widen16<XT>(((const unsigned short *)p.x)[(long long)head * p.x_hs + grow * p.x_rs + d]);
-                    }
-                    rowbuf[d] = v;
-                }
-                float xs0 = 0.0f;
-                if constexpr (WIDE == 2) {
-                    if (EUCLID && p.acc_in) xs0 = p.xn_ws[(long long)head * p.xn_hs + grow];
-                }
-                return xs0;
+                return fill_row_from_memory<METRIC, DP, XT, WIDE>(p, head, grow, rowbuf, lane);
             };
             auto acc_init = [&](int rr, int k) -> float {
-                if constexpr (WIDE == 2) {
-                    if (p.acc_in) {  // the chain over the earlier slices, in the accumulators' fragment layout (see ws_store)
-                        const float *wb = (const float *)((const f32x4 *)p.acc_ws + (long long)head * p.ws_hs +
-                                                          (((long long)blockIdx.x * WAVES + wave) * p.ws_nsub) * 256);
-                        const int r5 = k & 31;
-                        return wb[((long long)((k >> 5) * 4 + (r5 >> 3)) * 64 + ((r5 >> 2) & 1) * 32 + rr) * 4 + (r5 & 3)];
-                    }
-                }
+                if constexpr (WIDE == 2) return wide_acc_init(p, head, (long long)blockIdx.x * WAVES + wave, rr, k);
                 return 0.0f;
             };
             const int k0 = t0 * G::TILE_CODES;
@@ -963,13 +1058,7 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_search_mfm
         }
 
         if constexpr (LSE) {
-            // log-sum-exp of the similarities of this row over the whole codebook (fused sweeps only: no K split)
-            const float om = __shfl_xor(lb.run_m, 32), os = __shfl_xor(lb.run_s, 32);
-            const float mm = fmaxf(lb.run_m, om);  // lane half 0 always saw code 0: finite
-            const float ssum = (lb.run_m > -INF ? lb.run_s * __builtin_amdgcn_exp2f(lb.run_m - mm) : 0.0f) +
-                               (om > -INF ? os * __builtin_amdgcn_exp2f(om - mm) : 0.0f);
-            float lse_v = (mm + __builtin_amdgcn_logf(ssum)) * 0.6931471805599453f;
-            if (best_s != best_s) lse_v = best_s;  // a NaN similarity in the row: logsumexp is NaN
+            const float lse_v = close_lse(lb, best_s);
             if (h == 0 && row_ok) p.lse[(long long)head * p.M + row] = lse_v;
         }
 
@@ -977,21 +1066,12 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_search_mfm
             // keys mode is single-stage by contract, so the multi-stage kernels do not contain this exit at all: a second
             // latch on the stage loop made the allocator split the 128 loop-carried residual registers (187 spilled VGPRs)
             if (p.mode != kModeFused) {
-                if (h == 0 && row_ok) {
-                    const long long key = make_key<METRIC>(best_s, p.idx_offset + best_i);
-                    long long *dst = p.keys + (long long)head * p.key_hs + row;
-                    if (p.mode == kModeKeys) atomicMin(dst, key);
-                    else dst[(long long)blockIdx.z * p.key_zs] = key;  // this K split's own plane
-                }
+                if (h == 0 && row_ok) store_key<METRIC>(p, head, row, best_s, best_i);
                 continue;  // (single trip: leaves the stage loop)
             }
         }
 
-        if (h == 0 && row_ok) {
-            const long long o = (long long)head * p.idx_hs + row * p.idx_rs + (long long)q * p.idx_qs;
-            p.idx[o] = best_i;
-            if (p.best) p.best[o] = best_s;
-        }
+        if (h == 0 && row_ok) store_winner(p, head, row, q, best_s, best_i);
         sidx[(wave * p.Q + q) * 32 + c] = best_i;
         STAMP(4 + 5 * q + 2);
 
@@ -1053,25 +1133,7 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_search_mfm
     __builtin_amdgcn_s_setprio(2);
     if (WIDE == 1 || WIDE == 3 || p.mode != kModeFused) return;
     if constexpr (WIDE == 2) {
-        // rows wider than one launch holds, inference call, no K split: finish here -- out[row] = codebook[idx[row]] over the
-        // whole row width (natural layout, float4 per lane and 256 dims, four rows in flight)
-        const float *cbw = p.cb + (long long)head * p.cb_hs;
-        float *outw = p.out + (long long)head * p.out_hs;
-        const int nrows_w = (p.M - row0 >= 32) ? 32 : (int)(p.M - row0);
-        constexpr int RBW = 4;
-        for (int rr0 = 0; rr0 < nrows_w; rr0 += RBW) {
-            for (int d0 = 4 * lane; d0 < p.fin_D; d0 += 256) {
-                f32x4 v[RBW];
-#pragma unroll
-                for (int k = 0; k < RBW; ++k) {
-                    const int rr = (rr0 + k < nrows_w) ? rr0 + k : nrows_w - 1;
-                    v[k] = *(const f32x4 *)(cbw + (long long)sidx[wave * 32 + rr] * p.fin_D + d0);
-                }
-#pragma unroll
-                for (int k = 0; k < RBW; ++k)
-                    if (rr0 + k < nrows_w) __builtin_nontemporal_store(v[k], (f32x4 *)(outw + (row0 + rr0 + k) * p.out_rs + d0));
-            }
-        }
+        gather_wide_rows(p, head, row0, 0, (p.M - row0 >= 32) ? 32 : (int)(p.M - row0), sidx + wave * 32, lane);
         return;
     }
     if (p.out == nullptr && p.loss_part == nullptr) return;
@@ -1331,14 +1393,6 @@ __global__ void __launch_bounds__(WAVES * 64, (DP <= 256 ? 2 : 1)) vq_search_mfm
     }
     STAMP(3);
     STAMP_RT(61);
-    if (p.loss_part) {
-        float *lp = p.loss_part + (((long long)head * gridDim.x + blockIdx.x) * WAVES + wave) * p.Q;
-        for (int q = 0; q < (MULTI ? p.Q : 1); ++q) {
-            float e = MULTI ? lerr[q * 64] : e0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
-            if (lane == 0) lp[q] = e;
-        }
-    }
+    if (p.loss_part) store_loss_partials<WAVES, MULTI != 0>(p, head, lerr, e0, wave, lane);
 }
 

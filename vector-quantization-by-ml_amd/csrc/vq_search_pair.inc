@@ -335,23 +335,12 @@ __global__ void __launch_bounds__(512, 2) vq_search_pair512(const SearchParams p
 
         float best_s;
         int best_i;
-        resolve_best<METRIC>(lb, h, p.K, best_s, best_i);
-        {
-            const float os = __shfl_xor(best_s, 32);
-            const int oi = __shfl_xor(best_i, 32);
-            const bool take = EUCLID ? (os < best_s || (os == best_s && oi < best_i))
-                                     : (os > best_s || (os == best_s && oi < best_i));
-            if (take) {
-                best_s = os;
-                best_i = oi;
-            }
-        }
+        row_winner<METRIC>(lb, h, p.K, best_s, best_i);
         if constexpr (LSE) {
-            const float om = __shfl_xor(lb.run_m, 32), os = __shfl_xor(lb.run_s, 32);
-            const float mm = fmaxf(lb.run_m, om);
-            const float ssum = (lb.run_m > -INF ? lb.run_s * __builtin_amdgcn_exp2f(lb.run_m - mm) : 0.0f) +
-                               (om > -INF ? os * __builtin_amdgcn_exp2f(om - mm) : 0.0f);
-            if (h == 0 && row_ok) p.lse[(long long)head * p.M + row] = (mm + __builtin_amdgcn_logf(ssum)) * 0.6931471805599453f;
+            // (closed here, before the repair, which runs after the roles have joined: the NaN rule needs the repaired `best_s`
+            //  and is applied there -- hence a value that is no NaN in its place)
+            const float lse_v = close_lse(lb, 0.0f);  // (both lane halves: it exchanges their partial sums)
+            if (h == 0 && row_ok) p.lse[(long long)head * p.M + row] = lse_v;
         }
         // The winners leave the role-specific code through this wave's own staging region: what follows (the non-finite
         // repair, the stores) is compiled after the roles have joined, where no fragment register is live any more -- with
@@ -412,11 +401,7 @@ __global__ void __launch_bounds__(512, 2) vq_search_pair512(const SearchParams p
                 const int k1 = (t1 * 32 < p.K) ? t1 * 32 : p.K;
                 repair_nonfinite_rows<METRIC, 512>(todo, rowbuf, pk, t0 * 32, k1, lane, fill_row, acc_init, best_s, best_i);
             }
-            if (h == 0 && row_ok) {
-                const long long o = (long long)head * p.idx_hs + row * p.idx_rs + (long long)q * p.idx_qs;
-                p.idx[o] = best_i;
-                if (p.best) p.best[o] = best_s;
-            }
+            if (h == 0 && row_ok) store_winner(p, head, row, q, best_s, best_i);
             sidx[(pair * p.Q + q) * 32 + c] = best_i;
         }
         __syncthreads();  // the winners are visible to both waves; the dump is dead
@@ -475,34 +460,9 @@ __global__ void __launch_bounds__(512, 2) vq_search_pair512(const SearchParams p
         // non-finite inputs (rare, out of line; see repair_nonfinite_rows): the whole 512-dim row from memory
         if (const unsigned todo = nonfinite_rows(best_s, row_ok); __builtin_expect(todo != 0u, 0)) {
             float *rowbuf = mine;  // (2176 floats, idle since the sweep's last barrier)
-            auto fill_row = [&](int rr) -> float {
-                const long long grow = row0 + rr;
-#pragma clang loop unroll(disable)
-                for (int d = lane; d < 512; d += 64) {
-                    float v = 0.0f;
-                    if (d < p.D) {
-                        if constexpr (XT == 0)
-                            v = xh[grow * p.x_rs + d];
-                        else
-                            v = widen16<XT>(((const unsigned short *)p.x)[(long long)head * p.x_hs + grow * p.x_rs + d]);
-                    }
-                    rowbuf[d] = v;
-                }
-                float xs0 = 0.0f;
-                if constexpr (WIDE == 2) {
-                    if (EUCLID && p.acc_in) xs0 = p.xn_ws[(long long)head * p.xn_hs + grow];
-                }
-                return xs0;
-            };
+            auto fill_row = [&](int rr) -> float { return fill_row_from_memory<METRIC, 512, XT, WIDE>(p, head, row0 + rr, rowbuf, lane); };
             auto acc_init = [&](int rr, int k) -> float {
-                if constexpr (WIDE == 2) {
-                    if (p.acc_in) {  // the chain over the earlier slices, in the accumulators' fragment layout (see ws_store)
-                        const float *wb = (const float *)(wsw - lane);
-                        const int r5 = k & 31;
-                        return wb[((long long)((k >> 5) * 4 + (r5 >> 3)) * 64 + ((r5 >> 2) & 1) * 32 + rr) * 4 + (r5 & 3)];
-                    }
-                }
-                (void)rr; (void)k;
+                if constexpr (WIDE == 2) return wide_acc_init(p, head, (long long)blockIdx.x * 4 + pair, rr, k);
                 return 0.0f;
             };
             const int k1 = (t1 * 32 < p.K) ? t1 * 32 : p.K;
@@ -512,18 +472,9 @@ __global__ void __launch_bounds__(512, 2) vq_search_pair512(const SearchParams p
             }
         }
         if (p.mode != kModeFused) {
-            if (h == 0 && row_ok) {
-                const long long key = make_key<METRIC>(best_s, p.idx_offset + best_i);
-                long long *dst = p.keys + (long long)head * p.key_hs + row;
-                if (p.mode == kModeKeys) atomicMin(dst, key);
-                else dst[(long long)blockIdx.z * p.key_zs] = key;  // this K split's own plane
-            }
+            if (h == 0 && row_ok) store_key<METRIC>(p, head, row, best_s, best_i);
         } else {
-            if (h == 0 && row_ok) {
-                const long long o = (long long)head * p.idx_hs + row * p.idx_rs;
-                p.idx[o] = best_i;
-                if (p.best) p.best[o] = best_s;
-            }
+            if (h == 0 && row_ok) store_winner(p, head, row, 0, best_s, best_i);
             sidx[pair * 32 + c] = best_i;
         }
     }
@@ -534,27 +485,10 @@ __global__ void __launch_bounds__(512, 2) vq_search_pair512(const SearchParams p
     __builtin_amdgcn_s_setprio(2);
     if (p.out == nullptr && p.loss_part == nullptr) return;
     __syncthreads();  // the last stage's winners (written by the B waves) are visible to the A waves
-    if constexpr (WIDE == 2) {
-        // rows wider than one launch holds, inference call, no K split: finish here -- out[row] = codebook[idx[row]] over the
-        // WHOLE row width (natural layout, float4 per lane and 256 dims, four rows in flight; each wave of a pair takes 16 rows)
-        const float *cbw = p.cb + (long long)head * p.cb_hs;
-        float *outw = p.out + (long long)head * p.out_hs;
+    if constexpr (WIDE == 2) {  // (each wave of a pair takes 16 rows)
         const int prow = (p.M - row0 >= 32) ? 32 : (p.M - row0 > 0 ? (int)(p.M - row0) : 0);
         const int lo = role * 16, hi = (lo + 16 < prow) ? lo + 16 : prow;
-        constexpr int RBW = 4;
-        for (int rr0 = lo; rr0 < hi; rr0 += RBW) {
-            for (int d0 = 4 * lane; d0 < p.fin_D; d0 += 256) {
-                f32x4 v[RBW];
-#pragma unroll
-                for (int k = 0; k < RBW; ++k) {
-                    const int rr = (rr0 + k < hi) ? rr0 + k : hi - 1;
-                    v[k] = *(const f32x4 *)(cbw + (long long)sidx[pair * 32 + rr] * p.fin_D + d0);
-                }
-#pragma unroll
-                for (int k = 0; k < RBW; ++k)
-                    if (rr0 + k < hi) __builtin_nontemporal_store(v[k], (f32x4 *)(outw + (row0 + rr0 + k) * p.out_rs + d0));
-            }
-        }
+        gather_wide_rows(p, head, row0, lo, hi, sidx + pair * 32, lane);
         return;
     }
 
@@ -696,15 +630,7 @@ __global__ void __launch_bounds__(512, 2) vq_search_pair512(const SearchParams p
             }
         }
     }
-    if (p.loss_part) {
-        float *lp = p.loss_part + (((long long)head * gridDim.x + blockIdx.x) * WAVES + wave) * p.Q;
-        for (int q = 0; q < nq; ++q) {
-            float e = MULTI ? lerr[q * 64] : e0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o);
-            if (lane == 0) lp[q] = e;
-        }
-    }
+    if (p.loss_part) store_loss_partials<WAVES, MULTI != 0>(p, head, lerr, e0, wave, lane);
     STAMP(3);
     STAMP_RT(61);
 }

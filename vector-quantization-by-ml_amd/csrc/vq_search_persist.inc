@@ -1076,35 +1076,17 @@ __global__ void __launch_bounds__(WAVES * 64, 2) vq_search_persist(const SearchP
                     p.scr_list[at + __builtin_popcount(todo & ((1u << c) - 1u))] = (unsigned)((long long)head * p.M + row);
             }
         } else {
-        resolve_best<METRIC>(lb, h, p.K, best_s, best_i);
-        {
-            const float os = __shfl_xor(best_s, 32);
-            const int oi = __shfl_xor(best_i, 32);
-            const bool take = EUCLID ? (os < best_s || (os == best_s && oi < best_i))
-                                     : (os > best_s || (os == best_s && oi < best_i));
-            if (take) {
-                best_s = os;
-                best_i = oi;
-            }
-        }
+        row_winner<METRIC>(lb, h, p.K, best_s, best_i);
         // non-finite inputs (rare, out of line; see repair_nonfinite_rows)
         if (const unsigned todo = nonfinite_rows(best_s, row_ok); __builtin_expect(todo != 0u, 0)) {
             float *rowbuf = smem + G::NBUF * G::BUF_F4 * 4 + wave * (32 * XS);  // this wave's row staging region
-            auto fill_row = [&](int rr) -> float {
-#pragma clang loop unroll(disable)
-                for (int d = lane; d < DP; d += 64) rowbuf[d] = (d < p.D) ? xh[(row0 + rr) * p.x_rs + d] : 0.0f;
-                return 0.0f;
-            };
+            auto fill_row = [&](int rr) -> float { return fill_row_from_memory<METRIC, DP, 0, 0>(p, head, row0 + rr, rowbuf, lane); };
             auto acc_init = [&](int, int) -> float { return 0.0f; };
             repair_nonfinite_rows<METRIC, DP>(todo, rowbuf, pk, 0, p.K, lane, fill_row, acc_init, best_s, best_i);
         }
         }
         PSTAMP(3);
-        if (h == 0 && row_ok) {
-            const long long o = (long long)head * p.idx_hs + row * p.idx_rs;
-            p.idx[o] = has_cand ? cand : (long long)best_i;
-            if (p.best) p.best[o] = best_s;
-        }
+        if (h == 0 && row_ok) store_winner(p, head, row, 0, best_s, has_cand ? cand : (long long)best_i);
         int *mine = sidx + ((it & 1) * WAVES + wave) * 32;
         mine[c] = best_i;
         // this block becomes the one to copy during the next sweep (wave-private LDS: in order, no barrier needed)

@@ -314,25 +314,11 @@ __global__ void __launch_bounds__(512, 2) vq_search_resident(const SearchParams 
 
         float best_s;
         int best_i;
-        resolve_best<METRIC>(lb, h, p.K, best_s, best_i);
-        {
-            const float os = __shfl_xor(best_s, 32);
-            const int oi = __shfl_xor(best_i, 32);
-            const bool take = EUCLID ? (os < best_s || (os == best_s && oi < best_i))
-                                     : (os > best_s || (os == best_s && oi < best_i));
-            if (take) {
-                best_s = os;
-                best_i = oi;
-            }
-        }
+        row_winner<METRIC>(lb, h, p.K, best_s, best_i);
         // non-finite inputs (rare, out of line; see repair_nonfinite_rows).  The row buffer is slab buffer 0, which may hold (or
         // be receiving) rows of the block after next: wait for them, use it, fetch them again.
         if (const unsigned todo = nonfinite_rows(best_s, row_ok); __builtin_expect(todo != 0u, 0)) {
-            auto fill_row = [&](int rr) -> float {
-#pragma clang loop unroll(disable)
-                for (int d = lane; d < DP; d += 64) slab[d] = (d < p.D) ? xh[(row0 + rr) * p.x_rs + d] : 0.0f;
-                return 0.0f;
-            };
+            auto fill_row = [&](int rr) -> float { return fill_row_from_memory<METRIC, DP, 0, 0>(p, head, row0 + rr, slab, lane); };
             auto acc_init = [&](int, int) -> float { return 0.0f; };
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             repair_nonfinite_rows<METRIC, DP>(todo, slab, pk, 0, p.K, lane, fill_row, acc_init, best_s, best_i);
@@ -341,11 +327,7 @@ __global__ void __launch_bounds__(512, 2) vq_search_resident(const SearchParams 
                 slab_issue(IntC<0>{});
             }
         }
-        if (h == 0 && row_ok) {
-            const long long o = (long long)head * p.idx_hs + row * p.idx_rs;
-            p.idx[o] = best_i;
-            if (p.best) p.best[o] = best_s;
-        }
+        if (h == 0 && row_ok) store_winner(p, head, row, 0, best_s, best_i);
         int *mine = sidx + ((it & 1) * WAVES + wave) * 32;
         mine[c] = best_i;
         // this block becomes the one to copy during the next sweep (wave-private LDS: in order, no barrier needed)
